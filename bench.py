@@ -4,6 +4,9 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
 For N > 1 it is launched as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (one rank per GPU, RCCL); run directly with --gpus N > 1 it starts that launcher itself as a child.
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, ...);
+--dump-outputs DIR also writes what the last timed step computed; everything else the line can
+carry (posterior check, roofline, secondary measurements, CPU baseline) is measured with --full.
 
 A "step" is one complete inference run of the workload: BASELINE.json's metric is quoted on
 "HMM T=16 SMC" = configs[2]: 3-state HMM (reference include/models/models.hpp:114-141), T = 16
@@ -13,10 +16,10 @@ tests/golden/observations.npz (simulated from the model); particles
 device, so inputs are resident in HBM when the timed region starts.
 
 value        = particles (complete T-step traces) per second over all GPUs
-roofline     = dominant kernel (smc_step): algorithmic bytes per launch (56 B per
+roofline     = (--full) dominant kernel (smc_step): algorithmic bytes per launch (56 B per
                particle-step for the HMM) / mean launch duration measured with HIP events on the
                engine's own stream in a separate profiled pass of the same K steps
-cpu_baseline = the CPU oracle (oracle/cpprob_oracle.c, a port: the reference itself cannot be
+cpu_baseline = (--full) the CPU oracle (oracle/cpprob_oracle.c, a port: the reference itself cannot be
                built here) on one host core, compute-only, on a bounded sample
 """
 import argparse
@@ -61,6 +64,9 @@ def parse():
     p.add_argument("--loopback-ranks", type=int, default=0, help="N = 1 only: run the library's multi-GPU driver with this many ranks on the one GPU "
                    "(loopback transport: the whole exchange protocol, program order instead of collectives); --particles is then the WHOLE population")
     p.add_argument("--python-host", action="store_true", help="N > 1: drive the exchange scope from Python / torch.distributed instead of the library's C++ driver")
+    p.add_argument("--full", action="store_true", help="after the headline: the posterior check, the profiled pass and roofline, the live PMC passes, the "
+                   "secondary measurements and the CPU baseline (each still subject to --no-extras / --no-cpu-baseline / --no-live-pmc)")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float64)")
     return p.parse_args()
 
 
@@ -182,6 +188,32 @@ def timed_runs(eng, steps, warmup, world, device, island, first_index=0, exchang
     return dt, last
 
 
+DUMP_SAMPLE = 1 << 16           # particles in the seeded sample of the per-particle outputs
+DUMP_PARTICLE_BYTES = 32 << 20  # at most this much of them (a T = 128 trace is 1 KB)
+DUMP_COPY_LIMIT = 1 << 27       # elements: per-particle arrays larger than this are not read back at all
+
+
+def dump_outputs(d, stats, summ, eng=None):
+    """What the last timed run computed, as a caller of the timed path receives it, into d/<name>.npy (float64, under 40 MB):
+    the posterior statistics and the evidence; with one context (eng) also its step trace and, for a fixed seeded sample of
+    the particles, their final log-weights and surviving traces.  The inputs and the sample depend on the arguments alone,
+    so two builds run with the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"stats": stats, "log_evidence": [summ["log_evidence"]]}
+    if eng is not None:
+        arrays["ess"], arrays["resampled"] = eng.step_trace()
+        m = min(eng.n, DUMP_SAMPLE, DUMP_PARTICLE_BYTES // (8 * (eng.T + 1)))
+        idx = np.sort(np.random.default_rng(0).choice(eng.n, m, replace=False))
+        arrays["sample_index"] = idx
+        if eng.n <= DUMP_COPY_LIMIT:
+            arrays["logw_sample"] = eng.logw()[idx]
+        if eng.T * eng.n <= DUMP_COPY_LIMIT:
+            arrays["paths_sample"] = eng.paths()[:, idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+
 def guarded(fn, what):
     """Runs fn() on a helper thread with a deadline.  Creating an RCCL communicator and the first run over real links are
     collective and blocking: a transport that never completes cannot be recovered in-process, so the job ends with a message
@@ -214,9 +246,9 @@ def guarded(fn, what):
     return box.get("value")
 
 
-def timed_group_runs(group, steps, warmup, world, device, first_index=0):
+def timed_group_runs(group, steps, warmup, world, device, first_index=0, profile_run=True):
     """The same bracket for the library's own multi-GPU driver (cpprob_hip_group_run: a whole exchange-scope run per call,
-    RCCL collectives on the context's stream, no host synchronisation inside)."""
+    RCCL collectives on the context's stream, no host synchronisation inside).  profile_run=False: no profiled run behind the timed ones."""
     import torch
     import torch.distributed as dist
     # settle the transport before anything is timed: one run + results() (collective: every rank enters it), which repeats the run
@@ -248,14 +280,15 @@ def timed_group_runs(group, steps, warmup, world, device, first_index=0):
     # (step + totals, all-gather, pack, barrier, commit; how long the mailbox waits spun) and which transports the group settled on
     breakdown = None
     try:
-        group.profile(True)
-        group.run(first_index + warmup + steps)
-        group.results()
-        breakdown = group.profile_read()
-        group.profile(False)
-        breakdown["note"] = ("HIP events around the launches of one extra run (us per rank-step, the slowest local rank; a loopback group: the sum over its "
-                             "ranks, which share a stream); mailbox_wait = of all that, the time the waits spun on their peers' sequence numbers")
-        breakdown["transport_note"] = group.note()
+        if profile_run:
+            group.profile(True)
+            group.run(first_index + warmup + steps)
+            group.results()
+            breakdown = group.profile_read()
+            group.profile(False)
+            breakdown["note"] = ("HIP events around the launches of one extra run (us per rank-step, the slowest local rank; a loopback group: the sum over its "
+                                 "ranks, which share a stream); mailbox_wait = of all that, the time the waits spun on their peers' sequence numbers")
+            breakdown["transport_note"] = group.note()
     except Exception as e:        # noqa: reported under the key
         breakdown = {"error": str(e)}
     return dt, stats, summ, {"settling": settle, "timed_batch": reruns - settle, "rank_step_breakdown_us": breakdown}
@@ -573,7 +606,7 @@ def main():
             group.begin(spec["alg"], spec["model"], spec["obs"], n_global, seed=args.seed, resampler=rs_id, ess_threshold=spec["ess"])
         # (begin is collective over real links: it all-gathers hipIpc handles and proves the mailboxes by a round trip)
         guarded(begin_group, "cpprob_hip_group_begin (peer mappings, mailbox round trip)") if world > 1 else begin_group()
-        dt, stats, summ, reruns = timed_group_runs(group, args.steps, args.warmup, world, device)
+        dt, stats, summ, reruns = timed_group_runs(group, args.steps, args.warmup, world, device, profile_run=args.full)
         xtraffic = group.traffic()
         # Over real links the default transport (direct stores into peers' memory, mailbox collectives, trace words across ranks) has
         # only ever run on one GPU: if the answer it produced is not the posterior, say so and measure the conservative path instead
@@ -588,7 +621,7 @@ def main():
                 group.begin(spec["alg"], spec["model"], spec["obs"], n_global, seed=args.seed, resampler=rs_id, ess_threshold=spec["ess"],
                             flags=cp.capi.FLAG_WALK_READOUT)
             guarded(begin_conservative, "cpprob_hip_group_begin (conservative transport)")
-            dt, stats, summ, reruns = timed_group_runs(group, args.steps, args.warmup, world, device)
+            dt, stats, summ, reruns = timed_group_runs(group, args.steps, args.warmup, world, device, profile_run=args.full)
             xtraffic = group.traffic()
         last = (stats,)
     else:
@@ -598,16 +631,15 @@ def main():
         summ = None
     value = n_global * args.steps / dt
 
-    # posterior of the last timed run against the exact answer (validity of what was timed)
-    if last is not None:
-        stats = last[0]
-    else:
-        stats = eng.stats()
-    err = float(np.abs(stats - spec["exact"]).max())
     if summ is None:
         summ = eng.summary()
     if last is not None and len(last) == 3:
         summ["log_evidence"] = last[1]          # evidence of the joint population (shards combined), not of this rank's shard
+    step_form = int(summ.get("step_form", 0))
+    if args.full or args.dump_outputs:
+        stats = last[0] if last is not None else eng.stats()        # posterior statistics of the last timed run
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, stats, summ, eng if (group is None and world == 1) else None)
     if exchange and xtraffic is not None:
         tname = {0: "none", 1: "direct stores into the receiving rank's buffer (peer access / hipIpc), ordered by a 1-double all_gather", 2: "ncclSend/ncclRecv of fixed-capacity segments"}[xtraffic["transport"]]
         collective = "all_gather(24 bytes/rank) per step; migrating lineages: %s; all_reduce(T*K+3 doubles) per run" % tname
@@ -616,83 +648,87 @@ def main():
     else:
         collective = "none" if world == 1 else ("all_gather(4+T*K doubles/rank) once per run, asynchronous (no host synchronisation between runs)" if island else "all_gather(3 doubles/rank) per step + all_reduce(T*K doubles) per run")
 
-    # profiled pass: same K steps with HIP events around every launch on the engine's stream
-    # (per-shard kernels only: on several GPUs each rank profiles its own shard as an island)
-    n_prof = n if args.loopback_ranks <= 1 else max(1, n // args.loopback_ranks)       # (one loopback rank's shard)
-    if (world > 1 and not island) or exchange or group is not None:
-        eng.begin(spec["alg"], spec["model"], spec["obs"], n_prof, seed=args.seed, resampler=rs_id, ess_threshold=spec["ess"],
-                  particle_offset=rank * n_prof, n_global=world * n_prof, scope=cp.SCOPE_ISLAND, flags=rs_flags)
-    eng.profile_enable(True)
-    eng.profile_read(reset=True)
-    for i in range(args.steps):
-        eng.run(10_000 + i)
-    prof = eng.profile_read(reset=True)
-    eng.profile_enable(False)
-    dom = "sis" if spec["alg"] == cp.ALG_SIS else "smc_step"
-    dom_ms, dom_calls = prof[dom]
-    avg_s = dom_ms * 1e-3 / max(dom_calls, 1)
-    n_res_prof = eng.summary()["n_resampled"]
-    step_form = int(eng.summary().get("step_form", 0))
-    # the floor of a launch of this chain: the same run at 4096 particles (the same launches with nothing in them)
-    eng.begin(spec["alg"], spec["model"], spec["obs"], 4096, seed=args.seed, resampler=rs_id, ess_threshold=spec["ess"], flags=rs_flags)
-    for i in range(3):
-        eng.run(i)
-    eng.profile_enable(True)
-    eng.profile_read(reset=True)
-    for i in range(max(5, min(args.steps, 20))):
-        eng.run(11_000 + i)
-    floor = eng.profile_read(reset=True)
-    eng.profile_enable(False)
-    floor_us = floor[dom][0] * 1e3 / max(floor[dom][1], 1)
-    bytes_per_unit = ALGO_BYTES[spec["bytes_key"]]
-    light = {"hmm": 24, "lgssm": 32}.get(spec["bytes_key"], bytes_per_unit)      # a step that does not resample moves 2s + 2w
-    if spec["alg"] == cp.ALG_SIS:
-        bytes_per_unit = 16  # the sis kernel's own share of the 32 B: it writes value + logw; the read-out pass reads them back
-        bytes_per_launch = bytes_per_unit * n_prof
-    else:
-        # launches of a run: step 0 and the steps behind a generation that was not resampled move the light figure, the others the full one
-        full_launches = n_res_prof
-        bytes_per_launch = n_prof * (full_launches * bytes_per_unit + (T - full_launches) * light) / T
-    achieved = bytes_per_launch / avg_s / 1e9 if avg_s > 0 else 0.0
-    # HBM bytes per launch and issue counters from the PMC passes: collected by separate rocprofv3 --pmc runs of this same command
-    # (tools/profile_round.sh) and committed with their correction notes; bench.py itself cannot run the profiler
-    traffic, traffic_src, valu_frac, wait_frac, sq_src, sq_live = None, None, None, None, None, None
-    import glob
-    pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
-    if pmcs and spec["alg"] == cp.ALG_SMC and args.loopback_ranks <= 1:
-        with open(pmcs[-1]) as f:
-            pj = json.load(f)
-        rec = pj.get("workloads", {}).get("%s@%d" % (args.workload, n_prof))
-        if rec:
-            traffic = rec["step_kernel"]["hbm_bytes_per_launch_corrected"]
-            traffic_src = "committed profile profiles/%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on another box, gfx950-corrected): NOT measured in this run" % os.path.basename(pmcs[-1])
-            valu_frac = rec["step_kernel"].get("valu_issue_frac")
-            wait_frac = rec["step_kernel"].get("wait_frac")
-            sq_src = "committed profile profiles/%s: NOT measured in this run" % os.path.basename(pmcs[-1])
-    if rank == 0 and world == 1 and args.loopback_ranks <= 1 and not args.no_live_pmc:
-        live, why, sq_live = live_pmc_traffic(args.workload, n_prof, args.resampler, args.seed, args.flags, dom)
-        if sq_live and "wait_frac" in sq_live:
-            valu_frac, wait_frac, sq_src = sq_live["valu_issue_frac"], sq_live["wait_frac"], sq_live["measured_in"]
-        elif sq_live:
-            sq_src = (sq_src or "no committed profile") + "; live issue-counter pass unavailable: " + sq_live.get("error", "?")
-        if live is not None:
-            traffic, traffic_src = live, why
+    if args.full:
+        # posterior of the last timed run against the exact answer (validity of what was timed)
+        err = float(np.abs(stats - spec["exact"]).max())
+
+        # profiled pass: same K steps with HIP events around every launch on the engine's stream
+        # (per-shard kernels only: on several GPUs each rank profiles its own shard as an island)
+        n_prof = n if args.loopback_ranks <= 1 else max(1, n // args.loopback_ranks)       # (one loopback rank's shard)
+        if (world > 1 and not island) or exchange or group is not None:
+            eng.begin(spec["alg"], spec["model"], spec["obs"], n_prof, seed=args.seed, resampler=rs_id, ess_threshold=spec["ess"],
+                      particle_offset=rank * n_prof, n_global=world * n_prof, scope=cp.SCOPE_ISLAND, flags=rs_flags)
+        eng.profile_enable(True)
+        eng.profile_read(reset=True)
+        for i in range(args.steps):
+            eng.run(10_000 + i)
+        prof = eng.profile_read(reset=True)
+        eng.profile_enable(False)
+        dom = "sis" if spec["alg"] == cp.ALG_SIS else "smc_step"
+        dom_ms, dom_calls = prof[dom]
+        avg_s = dom_ms * 1e-3 / max(dom_calls, 1)
+        n_res_prof = eng.summary()["n_resampled"]
+        step_form = int(eng.summary().get("step_form", 0))
+        # the floor of a launch of this chain: the same run at 4096 particles (the same launches with nothing in them)
+        eng.begin(spec["alg"], spec["model"], spec["obs"], 4096, seed=args.seed, resampler=rs_id, ess_threshold=spec["ess"], flags=rs_flags)
+        for i in range(3):
+            eng.run(i)
+        eng.profile_enable(True)
+        eng.profile_read(reset=True)
+        for i in range(max(5, min(args.steps, 20))):
+            eng.run(11_000 + i)
+        floor = eng.profile_read(reset=True)
+        eng.profile_enable(False)
+        floor_us = floor[dom][0] * 1e3 / max(floor[dom][1], 1)
+        bytes_per_unit = ALGO_BYTES[spec["bytes_key"]]
+        light = {"hmm": 24, "lgssm": 32}.get(spec["bytes_key"], bytes_per_unit)      # a step that does not resample moves 2s + 2w
+        if spec["alg"] == cp.ALG_SIS:
+            bytes_per_unit = 16  # the sis kernel's own share of the 32 B: it writes value + logw; the read-out pass reads them back
+            bytes_per_launch = bytes_per_unit * n_prof
         else:
-            traffic_src = (traffic_src or "no committed profile for this workload and size") + "; live PMC passes unavailable: " + str(why)
-    hbm_frac_measured = (traffic / avg_s / 1e9 / HBM_PEAK_GBS) if (traffic and avg_s > 0) else None
-    # what bounds the dominant kernel at THIS size: within 2x of an empty launch of the same chain it is the chain's latency
-    # (kernel boundary, first round trip to memory, search, gather), whatever the byte convention says
-    bound = "latency" if (avg_s * 1e6 <= 2.0 * floor_us) else "hbm"
-    layout_bytes = LAYOUT_BYTES.get((spec["bytes_key"], step_form), bytes_per_unit)
-    achieved_layout = layout_bytes * n_prof / avg_s / 1e9 if avg_s > 0 else 0.0
-    roofline = {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "step_form": FORM_NAMES.get(step_form, str(step_form)) if spec["alg"] == cp.ALG_SMC else None,
-                "layout_bytes_per_unit": layout_bytes, "achieved_layout": achieved_layout, "frac_layout": achieved_layout / HBM_PEAK_GBS,
-                "traffic": traffic, "traffic_measured_in": traffic_src, "hbm_frac_measured": hbm_frac_measured, "valu_issue_frac": valu_frac, "wait_frac": wait_frac, "issue_counters_measured_in": sq_src,
-                "valu_insts_per_wave": sq_live.get("valu_insts_per_wave") if sq_live else None, "salu_insts_per_wave": sq_live.get("salu_insts_per_wave") if sq_live else None,
-                "launch_floor_us": floor_us, "floor_frac": floor_us / (avg_s * 1e6) if avg_s > 0 else None, "algorithmic_bytes_per_unit": bytes_per_unit, "algorithmic_bytes_per_unit_no_resampling": light if spec["alg"] == cp.ALG_SMC else None,
-                "units_per_launch": n_prof, "avg_launch_us": avg_s * 1e6, "launches": int(dom_calls), "resampling_launches_per_run": n_res_prof if spec["alg"] == cp.ALG_SMC else None,
-                "kernel_ms_per_step": {k: v[0] / args.steps for k, v in prof.items() if v[1]}}
+            # launches of a run: step 0 and the steps behind a generation that was not resampled move the light figure, the others the full one
+            full_launches = n_res_prof
+            bytes_per_launch = n_prof * (full_launches * bytes_per_unit + (T - full_launches) * light) / T
+        achieved = bytes_per_launch / avg_s / 1e9 if avg_s > 0 else 0.0
+        # HBM bytes per launch and issue counters from the PMC passes: collected by separate rocprofv3 --pmc runs of this same command
+        # (tools/profile_round.sh) and committed with their correction notes; bench.py itself cannot run the profiler
+        traffic, traffic_src, valu_frac, wait_frac, sq_src, sq_live = None, None, None, None, None, None
+        import glob
+        pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
+        if pmcs and spec["alg"] == cp.ALG_SMC and args.loopback_ranks <= 1:
+            with open(pmcs[-1]) as f:
+                pj = json.load(f)
+            rec = pj.get("workloads", {}).get("%s@%d" % (args.workload, n_prof))
+            if rec:
+                traffic = rec["step_kernel"]["hbm_bytes_per_launch_corrected"]
+                traffic_src = "committed profile profiles/%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on another box, gfx950-corrected): NOT measured in this run" % os.path.basename(pmcs[-1])
+                valu_frac = rec["step_kernel"].get("valu_issue_frac")
+                wait_frac = rec["step_kernel"].get("wait_frac")
+                sq_src = "committed profile profiles/%s: NOT measured in this run" % os.path.basename(pmcs[-1])
+        if rank == 0 and world == 1 and args.loopback_ranks <= 1 and not args.no_live_pmc:
+            live, why, sq_live = live_pmc_traffic(args.workload, n_prof, args.resampler, args.seed, args.flags, dom)
+            if sq_live and "wait_frac" in sq_live:
+                valu_frac, wait_frac, sq_src = sq_live["valu_issue_frac"], sq_live["wait_frac"], sq_live["measured_in"]
+            elif sq_live:
+                sq_src = (sq_src or "no committed profile") + "; live issue-counter pass unavailable: " + sq_live.get("error", "?")
+            if live is not None:
+                traffic, traffic_src = live, why
+            else:
+                traffic_src = (traffic_src or "no committed profile for this workload and size") + "; live PMC passes unavailable: " + str(why)
+        hbm_frac_measured = (traffic / avg_s / 1e9 / HBM_PEAK_GBS) if (traffic and avg_s > 0) else None
+        # what bounds the dominant kernel at THIS size: within 2x of an empty launch of the same chain it is the chain's latency
+        # (kernel boundary, first round trip to memory, search, gather), whatever the byte convention says
+        bound = "latency" if (avg_s * 1e6 <= 2.0 * floor_us) else "hbm"
+        layout_bytes = LAYOUT_BYTES.get((spec["bytes_key"], step_form), bytes_per_unit)
+        achieved_layout = layout_bytes * n_prof / avg_s / 1e9 if avg_s > 0 else 0.0
+        roofline = {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "step_form": FORM_NAMES.get(step_form, str(step_form)) if spec["alg"] == cp.ALG_SMC else None,
+                    "layout_bytes_per_unit": layout_bytes, "achieved_layout": achieved_layout, "frac_layout": achieved_layout / HBM_PEAK_GBS,
+                    "traffic": traffic, "traffic_measured_in": traffic_src, "hbm_frac_measured": hbm_frac_measured, "valu_issue_frac": valu_frac, "wait_frac": wait_frac, "issue_counters_measured_in": sq_src,
+                    "valu_insts_per_wave": sq_live.get("valu_insts_per_wave") if sq_live else None, "salu_insts_per_wave": sq_live.get("salu_insts_per_wave") if sq_live else None,
+                    "launch_floor_us": floor_us, "floor_frac": floor_us / (avg_s * 1e6) if avg_s > 0 else None, "algorithmic_bytes_per_unit": bytes_per_unit, "algorithmic_bytes_per_unit_no_resampling": light if spec["alg"] == cp.ALG_SMC else None,
+                    "units_per_launch": n_prof, "avg_launch_us": avg_s * 1e6, "launches": int(dom_calls), "resampling_launches_per_run": n_res_prof if spec["alg"] == cp.ALG_SMC else None,
+                    "kernel_ms_per_step": {k: v[0] / args.steps for k, v in prof.items() if v[1]}}
 
     out = {
         "metric": "particles/sec (whole node) + achieved HBM GB/s, HMM T=16 SMC" if args.workload == "hmm16_smc" else "particles/sec (whole node), " + args.workload,
@@ -703,9 +739,11 @@ def main():
                    "resampler": args.resampler, "ess_threshold": spec["ess"], "scope": scope, "n_global": n_global, "collective": collective,
                    "host": host if (world > 1 or group is not None) else "one context, one stream", "exchange_reruns": reruns, "flags": args.flags},
         "particle_steps_per_sec": value * T,
-        "roofline": roofline,
-        "posterior_max_abs_err_vs_exact": err, "log_evidence": summ["log_evidence"], "n_resampled": summ["n_resampled"],
+        "log_evidence": summ["log_evidence"], "n_resampled": summ["n_resampled"],
     }
+    if args.full:
+        out["roofline"] = roofline
+        out["posterior_max_abs_err_vs_exact"] = err
 
     if isinstance(reruns, dict) and "rank_step_breakdown_us" in reruns:
         bd = reruns.pop("rank_step_breakdown_us")
@@ -728,7 +766,8 @@ def main():
             sys.stdout.flush()
             os.write(real_stdout, (json.dumps(out) + "\n").encode())
 
-    if world > 1 and exchange and not args.no_extras:
+    extras = args.full and not args.no_extras
+    if world > 1 and exchange and extras:
         # secondary, labelled: the migration-free scopes on the same shards (every rank takes part).  "island": independent
         # populations combined once per run by their evidence -- no data-path collective; "global": one joint population, per-step
         # all-gather of 3 doubles per rank, resampling local to the shard (mass share carried) -- a different estimator from the
@@ -761,7 +800,7 @@ def main():
             emit()
             os._exit(0)
 
-    if rank == 0 and world == 1 and not args.no_extras and smc and group is None:
+    if rank == 0 and world == 1 and extras and smc and group is None:
         # secondary: the multi-GPU protocol at world = 1 -- the library's C++ driver with a single rank: per step the sharded step
         # kernel and the shard totals (a group of one has nobody to gather from or exchange with); then the same with EVERY call of
         # the multi-GPU path issued anyway (ncclAllGather per step, the ordering all-gather of the direct transport, ncclAllReduce)
@@ -780,7 +819,7 @@ def main():
             except Exception as e:
                 out[key] = {"error": str(e)}
 
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "hmm16_smc":
+    if rank == 0 and world == 1 and extras and args.workload == "hmm16_smc":
         # secondary: the SAME workload through the unchanged-model path -- models::hmm<16> as written against the CPProb statement API,
         # compiled for the device (CPPROB_REGISTER_MODEL) and called through cpprob::inference from the C++14 host (cpprob_main --generic):
         # trace replay, one launch of the model body per observe, device-side bookkeeping in between
@@ -835,7 +874,7 @@ def main():
         except Exception as e:
             out["generic_path"] = {"error": str(e)}
 
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "hmm16_smc" and args.resampler == "systematic":
+    if rank == 0 and world == 1 and extras and args.workload == "hmm16_smc" and args.resampler == "systematic":
         # secondary: the other two resamplers (thesis Alg. 1 p.36 is multinomial; remark p.36: systematic / stratified) on the headline
         # workload and on configs[3]'s per-GPU shape.  All three run on integers inside the step launch and equal the oracle's
         # ancestors bit for bit (tests/test_gpu_inference.py); multinomial in the strata form unless the literal form is named.
@@ -871,7 +910,7 @@ def main():
                        "resampler adds in front of its steps (strata form of multinomial: every step's stratum counts in two launches at the run's start)")
         out["resamplers"] = res
 
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "hmm16_smc" and args.resampler == "systematic" and group is None:
+    if rank == 0 and world == 1 and extras and args.workload == "hmm16_smc" and args.resampler == "systematic" and group is None:
         # secondary: the three resamplers as ONE joint population over eight loopback shards of this GPU (the whole exchange protocol on one
         # stream; exact: every run equals the one-GPU run's traces bit for bit, tests/test_gpu_group.py) -- multinomial (thesis Alg. 1) in
         # the strata form: regular intervals + the strata the ranks' boundaries cut (csrc/strata_cut.hpp)
@@ -892,7 +931,7 @@ def main():
         sh["note"] = "cpprob_hip_group_run, 8 loopback ranks sharing this GPU and one stream (the ranks' launches serialise: a protocol figure, not a scaling one); %d particles in all" % n
         out["sharded_resamplers"] = sh
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         # error bars: five run seeds of the headline configuration against the exact posterior
         eng.begin(spec["alg"], spec["model"], spec["obs"], n, seed=args.seed, resampler=cp.RESAMPLE_SYSTEMATIC, ess_threshold=spec["ess"])
         errs, lzs = [], []
@@ -904,7 +943,7 @@ def main():
                              "log_evidence": {"mean": float(np.mean(lzs)), "sd": float(np.std(lzs, ddof=1))},
                              "exact_log_evidence": spec.get("exact_logz")}
 
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "hmm16_smc":
+    if rank == 0 and world == 1 and extras and args.workload == "hmm16_smc":
         # secondary: the same particles without their history (keep_history = 0: two rows of values, no ancestors, no lineage
         # walk); predict hit t's statistics are then the FILTERING ones -- a different estimand from the headline's whole-trace
         # posterior, which is why this is not `value`
@@ -915,7 +954,7 @@ def main():
                                  "filter_max_abs_err_vs_exact": float(np.abs(eng.stats() - zf["hmm16_filter"]).max()),
                                  "note": "keep_history = 0: particle store O(N) instead of O(N T); 16 step launches + one bookkeeping wavefront"}
 
-    if rank == 0 and world == 1 and not args.no_extras and spec["alg"] == cp.ALG_SMC and not exchange:
+    if rank == 0 and world == 1 and extras and spec["alg"] == cp.ALG_SMC and not exchange:
         # secondary: the same runs with several contexts in flight.  One run is a dependent chain of ~19 launches whose
         # step kernels leave CUs idle at their tails; independent runs (replicates, other observation sets) on separate
         # contexts / HIP streams fill them.  Every run is unchanged -- same kernels, same 10^6 particles -- only overlapped.
@@ -944,7 +983,7 @@ def main():
         for e in engs[1:]:
             e.close()
 
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == "hmm16_smc":
+    if rank == 0 and world == 1 and extras and args.workload == "hmm16_smc":
         # secondary: BASELINE.json configs[1], gaussian_unknown_mean SIS at 10^7 particles
         g = workload_spec("gaussian_sis", os.path.join(ROOT, "tests", "golden", "observations.npz"))
         ng = 10_000_000
@@ -969,7 +1008,7 @@ def main():
             out["gaussian_sis_1e7"]["cpu_compute_only_1core"] = cpu_baseline("gaussian_sis", 4_000_000, args.seed)
             out["gaussian_sis_1e7"]["cpu_as_shipped_1core"] = cpu_as_shipped(200_000, args.seed)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_sample, args.seed)
         if "value" in out["cpu_baseline"]:
             out["gpu_over_cpu_1core"] = value / out["cpu_baseline"]["value"]
@@ -982,27 +1021,28 @@ def main():
             except Exception as e:
                 out["cpu_baseline"]["as_shipped_sis_1core"] = {"error": str(e)}
 
-    # the secondary numbers as scalars where the driver's record keeps them whole (`roofline`): every number README quotes
-    def _get(*ks):
-        d = out
-        for k in ks:
-            if not isinstance(d, dict) or k not in d:
-                return None
-            d = d[k]
-        return d
-    wl0 = "hmm16_smc@%d" % n
-    out["roofline"].update({
-        "generic_ms": _get("generic_path", "ms_per_run"), "generic_vs_fused": _get("generic_path", "vs_fused_kernels"),
-        "generic_vs_builtin_same_call": _get("generic_path", "vs_builtin_registration_same_call"), "generic_step_builds_used": _get("generic_path", "step_builds_used"),
-        "generic_no_step_builds_ms": _get("generic_path", "run_time_kernel_only_ms"),
-        "stratified_vs_systematic": _get("resamplers", wl0, "stratified", "vs_systematic"), "multinomial_vs_systematic": _get("resamplers", wl0, "multinomial", "vs_systematic"),
-        "lgssm100_1250000_systematic_ms": _get("resamplers", "lgssm100_smc@1250000", "systematic", "ms_per_run"),
-        "lgssm100_1250000_multinomial_vs_systematic": _get("resamplers", "lgssm100_smc@1250000", "multinomial", "vs_systematic"),
-        "gaussian_sis_particles_per_s": _get("gaussian_sis_1e7", "particles_per_sec"),
-        "gaussian_sis_hbm_frac": (_get("gaussian_sis_1e7", "sis_kernel_GBs") / HBM_PEAK_GBS) if _get("gaussian_sis_1e7", "sis_kernel_GBs") else None,
-        "pipelined_particles_per_s": _get("pipelined", "particles_per_sec"), "filtering_only_particles_per_s": _get("filtering_only", "particles_per_sec"),
-        "multinomial_8_loopback_shards_ms": _get("sharded_resamplers", "multinomial", "ms_per_run"), "systematic_8_loopback_shards_ms": _get("sharded_resamplers", "systematic", "ms_per_run"),
-    })
+    if args.full:
+        # the secondary numbers as scalars where the driver's record keeps them whole (`roofline`): every number README quotes
+        def _get(*ks):
+            d = out
+            for k in ks:
+                if not isinstance(d, dict) or k not in d:
+                    return None
+                d = d[k]
+            return d
+        wl0 = "hmm16_smc@%d" % n
+        out["roofline"].update({
+            "generic_ms": _get("generic_path", "ms_per_run"), "generic_vs_fused": _get("generic_path", "vs_fused_kernels"),
+            "generic_vs_builtin_same_call": _get("generic_path", "vs_builtin_registration_same_call"), "generic_step_builds_used": _get("generic_path", "step_builds_used"),
+            "generic_no_step_builds_ms": _get("generic_path", "run_time_kernel_only_ms"),
+            "stratified_vs_systematic": _get("resamplers", wl0, "stratified", "vs_systematic"), "multinomial_vs_systematic": _get("resamplers", wl0, "multinomial", "vs_systematic"),
+            "lgssm100_1250000_systematic_ms": _get("resamplers", "lgssm100_smc@1250000", "systematic", "ms_per_run"),
+            "lgssm100_1250000_multinomial_vs_systematic": _get("resamplers", "lgssm100_smc@1250000", "multinomial", "vs_systematic"),
+            "gaussian_sis_particles_per_s": _get("gaussian_sis_1e7", "particles_per_sec"),
+            "gaussian_sis_hbm_frac": (_get("gaussian_sis_1e7", "sis_kernel_GBs") / HBM_PEAK_GBS) if _get("gaussian_sis_1e7", "sis_kernel_GBs") else None,
+            "pipelined_particles_per_s": _get("pipelined", "particles_per_sec"), "filtering_only_particles_per_s": _get("filtering_only", "particles_per_sec"),
+            "multinomial_8_loopback_shards_ms": _get("sharded_resamplers", "multinomial", "ms_per_run"), "systematic_8_loopback_shards_ms": _get("sharded_resamplers", "systematic", "ms_per_run"),
+        })
     emit()
     if group is not None:
         group.close()

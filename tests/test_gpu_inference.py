@@ -1117,7 +1117,7 @@ def test_bench_two_ranks_on_one_gpu(scope, workload):
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--particles", "200000", "--scope", scope, "--no-cpu-baseline",
-               "--workload", workload, "--no-extras"]
+               "--workload", workload, "--no-extras", "--full"]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
         if p.returncode == 0:
             break
@@ -1149,6 +1149,38 @@ def test_bench_two_ranks_on_one_gpu(scope, workload):
             assert key in bd, bd
         assert bd["steps"] > 0 and bd["step_and_totals"] > 0 and bd["pack"] > 0 and "migrants: direct stores" in d["transport_note"]
         assert d["roofline"]["frac_layout"] <= 1.0 and d["roofline"]["layout_bytes_per_unit"] > 0 and "step_form" in d["roofline"]
+
+
+def test_bench_plain_run_dumps_the_last_timed_run(engine, golden_dir, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K runs and prints the headline line alone (roofline, secondary
+    measurements and CPU baseline are --full's); --dump-outputs DIR writes, as float64, the arrays of the last timed run --
+    equal to the same run (same seed, run index W + K - 1) made here."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, K, W = 200_000, 3, 2
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--particles", str(n), "--dump-outputs", str(d)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-1500:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == K and r["warmup"] == W and r["unit"] == "particles/s" and r["higher_is_better"] is True and r["dtype"] == "f64"
+    assert r["ms_per_step"] > 0 and abs(r["value"] * r["ms_per_step"] * 1e-3 / n - 1.0) < 1e-9
+    assert "roofline" not in r and "cpu_baseline" not in r and "resamplers" not in r
+    got = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) < 64 << 20
+    obs = _obs(golden_dir, "hmm16")
+    engine.begin(cp.ALG_SMC, cp.MODEL_HMM3, obs, n, seed=12345, resampler=cp.RESAMPLE_SYSTEMATIC, ess_threshold=2.0)
+    engine.run(W + K - 1)
+    s, stats, ess, resampled = engine.results()
+    idx = got["sample_index"].astype(np.int64)
+    assert len(idx) == min(n, 1 << 16) and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(got["stats"], stats)
+    np.testing.assert_array_equal(got["log_evidence"], [s["log_evidence"]])
+    np.testing.assert_array_equal(got["ess"], ess)
+    np.testing.assert_array_equal(got["resampled"], resampled)
+    np.testing.assert_array_equal(got["logw_sample"], engine.logw()[idx])
+    np.testing.assert_array_equal(got["paths_sample"], engine.paths()[:, idx])
 
 
 HMM2 = ([-1.5, 1.0], [[0.85, 0.15], [0.3, 0.7]])

@@ -232,11 +232,11 @@ def test_exact_solvers_self_consistency():
     assert abs(m - 2.323529411764706) < 1e-12 and abs(v - 1.0588235294117647) < 1e-12
 
 
-def test_oracle_under_sanitizers():
+def test_oracle_under_sanitizers(tmp_path):
     """run the CPU oracle under ASan/UBSan (the GPU pool offers no sanitizer)."""
     src = os.path.join(ROOT, "oracle", "cpprob_oracle.c")
-    exe = "/tmp/orc_asan_test"
-    drv = "/tmp/orc_asan_drv.c"
+    exe = str(tmp_path / "orc_asan_test")
+    drv = str(tmp_path / "orc_asan_drv.c")
     with open(drv, "w") as f:
         f.write('''
 #include <stdint.h>

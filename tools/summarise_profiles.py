@@ -71,7 +71,7 @@ for wl, n in (("hmm16_smc", 1000000), ("hmm16_smc", 10000000), ("lgssm100_smc", 
     base = "profiles/%s_%s_%d_kernel_stats" % (out_tag, wl, n)
     shutil.copy(ks, base + ".csv")
     rows = list(csv.DictReader(open(ks)))
-    md = "# rocprofv3 --kernel-trace --stats -- python3 bench.py --workload %s --particles %d --steps 10 --warmup 2 --no-cpu-baseline --no-extras (MI355X, %s)\n\n" % (wl, n, out_tag)
+    md = "# rocprofv3 --kernel-trace --stats -- python3 bench.py --workload %s --particles %d --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras (MI355X, %s)\n\n" % (wl, n, out_tag)
     md += "| kernel | calls | total us | avg us | min us | max us | % |\n|---|---|---|---|---|---|---|\n"
     for r in rows[:12]:
         md += "| `%s` | %s | %.1f | %.2f | %.2f | %.2f | %s |\n" % (r["Name"][:110], r["Calls"], float(r["TotalDurationNs"]) / 1e3, float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3, r["Percentage"])
@@ -112,7 +112,7 @@ for wl, n in (("hmm16_smc", 1000000), ("lgssm100_smc", 1250000)):
         if not ks:
             continue
         rows = list(csv.DictReader(open(ks)))
-        md = "# rocprofv3 --kernel-trace --stats -- python3 bench.py --workload %s --particles %d --resampler %s --steps 10 --warmup 2 --no-cpu-baseline --no-extras --no-live-pmc (MI355X, %s)\n\n" % (wl, n, rs_name, out_tag)
+        md = "# rocprofv3 --kernel-trace --stats -- python3 bench.py --workload %s --particles %d --resampler %s --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras --no-live-pmc (MI355X, %s)\n\n" % (wl, n, rs_name, out_tag)
         md += "| kernel | calls | total us | avg us | min us | max us | % |\n|---|---|---|---|---|---|---|\n"
         for r in rows[:12]:
             md += "| `%s` | %s | %.1f | %.2f | %.2f | %.2f | %s |\n" % (r["Name"][:120], r["Calls"], float(r["TotalDurationNs"]) / 1e3, float(r["AverageNs"]) / 1e3, float(r["MinNs"]) / 1e3, float(r["MaxNs"]) / 1e3, r["Percentage"])
@@ -131,7 +131,7 @@ for rs_name in ("multinomial", "systematic"):
     if not ks:
         continue
     rows = list(csv.DictReader(open(ks)))
-    md = "# rocprofv3 --kernel-trace --stats -- python3 bench.py --resampler %s --loopback-ranks 8 --steps 10 --warmup 2 --no-cpu-baseline --no-extras --no-live-pmc (MI355X, %s)\n\n" % (rs_name, out_tag)
+    md = "# rocprofv3 --kernel-trace --stats -- python3 bench.py --resampler %s --loopback-ranks 8 --steps 10 --warmup 2 --full --no-cpu-baseline --no-extras --no-live-pmc (MI355X, %s)\n\n" % (rs_name, out_tag)
     md += "hmm<16>, 10^6 particles as ONE population over eight loopback ranks of this GPU (one stream: the ranks' launches serialise).\n\n"
     md += "| kernel | calls | total us | avg us | min us | max us | % |\n|---|---|---|---|---|---|---|\n"
     for r in rows[:12]:
