@@ -140,6 +140,8 @@ struct cpprob_hip_ctx {
     uint32_t* d_q[2] = {nullptr, nullptr};                 // [ld] integer weights of the fixed-point form, ping-pong; the count form's trace words
     // trace words (trace_words.hpp): a single population's short discrete traces ride with the particles; the read-out streams them
     bool trace_mode = false; uint32_t* d_trace_cnt = nullptr; unsigned long long* d_trace_arrive = nullptr;
+    // the run's last step with the read-out folded in (step_counts.hpp: step_fold_tail): its counter sets, then the top arrival counter
+    uint32_t* d_fold = nullptr; size_t fold_cap = 0, fold_sets = 0; bool final_folded = false;
     // ... and of one shard of a joint population (remote lineages): the words by the step's parity, [rs] each -- annex columns included,
     // a migrant's word arrives with its state; trace_shard: every rank of the group has them
     uint32_t* d_tr[2] = {nullptr, nullptr}; size_t tr_cap = 0; bool trace_shard = false, trace_shard_run = false;
@@ -491,6 +493,7 @@ static void hier_view(const cpprob_hip_ctx* c, int copy, Hier& h)
 }
 
 static void hier_rotation(cpprob_hip_ctx* c, int t, int& kp, int& kn, int& kc);
+static void counts_final_view(cpprob_hip_ctx* c, CountsFinal& f, bool bookkeep);
 static void launch_strata(cpprob_hip_ctx* c);
 // multinomial resampling, strata form: the outputs the strata are drawn for -- the population's in the exchange scope, else this context's
 static uint64_t strata_outputs(const cpprob_hip_ctx* c) { return c->exchange ? c->pop_n : (uint64_t)c->n; }
@@ -528,17 +531,35 @@ void launch_step_counts(cpprob_hip_ctx* c, int t, const double* all_totals, int 
         if (c->trace_mode && !all_totals) { a.trace_prev = c->d_q[(t + 1) & 1]; a.trace_next = c->d_q[t & 1]; }
         if (c->step_protocol && c->trace_shard_run) { a.trace_prev = c->d_tr[(t + 1) & 1]; a.trace_next = c->d_tr[t & 1]; }
         ProfScope ps(c, 0);
+        // The run's last step with the read-out folded in (step_counts.hpp: step_fold_tail): a population of its own whose read-out is
+        // the trace words' counts (r07: -4.5 us a run at 10^6, -13 / -9 / -17 us at 10^5 / 4e6 / 10^7).  Filtering-only runs keep
+        // counts_filter_final_kernel, one wavefront: folded, their run measured 1.4 us slower at 10^6 (profiles/r07_notes.md).
+        // CPPROB_HIP_FLAG_SEPARATE_TRACE_READOUT keeps the last step ordinary and the read-out a launch of its own (trace_readout_kernel).
+        const bool fold = t + 1 == c->T && !all_totals && !c->step_protocol && !c->sharded && c->trace_mode && c->d_fold &&
+                          !(c->cfg.flags & CPPROB_HIP_FLAG_SEPARATE_TRACE_READOUT);
+        StepCountsLastArgs<Model> la{};
+        if (fold) {
+            static_cast<StepCountsArgs<Model>&>(la) = a;
+            la.fold.cnt = c->d_fold; la.fold.arrive = reinterpret_cast<unsigned long long*>(c->d_fold + c->fold_sets * kFoldSetWords);
+            la.fold.stats = c->d_stats;
+            counts_final_view(c, la.fold.f, true);
+            c->final_bookkeep_pending = false; c->final_folded = true;
+        }
         if (c->cfg.resampler == CPPROB_HIP_RESAMPLE_MULTINOMIAL) {
             a.strata_k = strata_k_of(c);
             if (t == 0) launch_strata(c);
             a.strata_offs = t > 0 ? c->d_strata + (size_t)(t - 1) * (((size_t)1 << a.strata_k) + 1) : nullptr;
             a.cut = cut_view(c);
+            la.strata_k = a.strata_k; la.strata_offs = a.strata_offs; la.cut = a.cut;
             if (all_totals) hipLaunchKernelGGL((smc_step_counts_kernel<Model, true, kFixMultinomial>), dim3(c->nb), dim3(kThreads), 0, c->stream, a);
+            else if (fold) hipLaunchKernelGGL((smc_step_counts_kernel<Model, false, kFixMultinomial, true>), dim3(c->nb), dim3(kThreads), 0, c->stream, la);
             else hipLaunchKernelGGL((smc_step_counts_kernel<Model, false, kFixMultinomial>), dim3(c->nb), dim3(kThreads), 0, c->stream, a);
         }
         else if (c->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED && all_totals) hipLaunchKernelGGL((smc_step_counts_kernel<Model, true, kFixStratified>), dim3(c->nb), dim3(kThreads), 0, c->stream, a);
+        else if (c->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED && fold) hipLaunchKernelGGL((smc_step_counts_kernel<Model, false, kFixStratified, true>), dim3(c->nb), dim3(kThreads), 0, c->stream, la);
         else if (c->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED) hipLaunchKernelGGL((smc_step_counts_kernel<Model, false, kFixStratified>), dim3(c->nb), dim3(kThreads), 0, c->stream, a);
         else if (all_totals) hipLaunchKernelGGL((smc_step_counts_kernel<Model, true>), dim3(c->nb), dim3(kThreads), 0, c->stream, a);
+        else if (fold) hipLaunchKernelGGL((smc_step_counts_kernel<Model, false, kFixSystematic, true>), dim3(c->nb), dim3(kThreads), 0, c->stream, la);
         else hipLaunchKernelGGL((smc_step_counts_kernel<Model, false>), dim3(c->nb), dim3(kThreads), 0, c->stream, a);
 #ifdef CPPROB_STAMPS
         {
@@ -927,7 +948,7 @@ void free_run_buffers(cpprob_hip_ctx* c)
 {
     dfree(c->d_obs); dfree(c->d_logw[0]); dfree(c->d_logw[1]); dfree(c->d_wrel[0]); dfree(c->d_wrel[1]); dfree(c->d_bf); dfree(c->d_ll_tab); dfree(c->d_values); dfree(c->d_anc); dfree(c->d_paths);
     dfree(c->d_part[0]); dfree(c->d_part[1]); dfree(c->d_e_tab); dfree(c->d_gpart); dfree(c->d_stile); dfree(c->d_gstat); dfree(c->d_bc); dfree(c->d_ess); dfree(c->d_resampled); dfree(c->d_stats_part); dfree(c->d_stats);
-    dfree(c->d_cdf); dfree(c->d_anc_pre); dfree(c->d_strata); dfree(c->d_strata_top); dfree(c->d_lz_trace); dfree(c->d_obound); dfree(c->d_hier); dfree(c->d_annex_base); dfree(c->d_fpart); dfree(c->d_filter_w); dfree(c->d_skip); dfree(c->d_q[0]); dfree(c->d_q[1]); dfree(c->d_trace_cnt); dfree(c->d_trace_arrive); dfree(c->d_tr[0]); dfree(c->d_tr[1]);
+    dfree(c->d_cdf); dfree(c->d_anc_pre); dfree(c->d_strata); dfree(c->d_strata_top); dfree(c->d_lz_trace); dfree(c->d_obound); dfree(c->d_hier); dfree(c->d_annex_base); dfree(c->d_fpart); dfree(c->d_filter_w); dfree(c->d_skip); dfree(c->d_q[0]); dfree(c->d_q[1]); dfree(c->d_trace_cnt); dfree(c->d_trace_arrive); dfree(c->d_fold); dfree(c->d_tr[0]); dfree(c->d_tr[1]);
     c->cap_particles = 0; c->cap_T = 0; c->annex_cap = 0; c->tr_cap = 0;
 }
 
@@ -1157,6 +1178,15 @@ int cpprob_hip_infer_begin(cpprob_hip_ctx* c, const cpprob_hip_config* cfg, cons
         }
         c->hier_q0_off = per_copy; c->hier_m0_off = per_copy + (size_t)c->nb; per_copy += 2 * (size_t)c->nb;
         c->hier.n_lev = nl; c->hier_per_copy = per_copy;
+        {
+            // the folded last step's counter sets: one per level-1 block (one at <= 64 tiles), then one per level-2 block; the top
+            // arrival counter on a line of its own behind them.  Zero here; every folded run leaves them zero.
+            const size_t sets = nl <= 1 ? 1 : (size_t)c->hier.n_ent[1] + (nl == 3 ? (size_t)c->hier.n_ent[2] : 0);
+            const size_t words = sets * kFoldSetWords + 32;
+            if (!c->d_fold || words > c->fold_cap) { dfree(c->d_fold); HIP_TRY(c, hipMalloc(&c->d_fold, words * sizeof(uint32_t))); c->fold_cap = words; }
+            c->fold_sets = sets;
+            HIP_TRY(c, hipMemsetAsync(c->d_fold, 0, words * sizeof(uint32_t), c->stream));
+        }
         for (int k = 0; k < 3; ++k)
             for (int l = 0; l < nl; ++l) c->hier.lvl[k][l] = c->d_hier + (size_t)k * per_copy + off[l];
         if (3 * per_copy > c->hier_entries) return fail(c, CPPROB_HIP_EDEVICE, "count hierarchy exceeds its allocation");
@@ -1304,7 +1334,7 @@ int cpprob_hip_infer_run(cpprob_hip_ctx* c, uint64_t run_index)
     c->cur = 0; c->cur_part = 0;
     c->sharded = false;
     if (!c->force_fp) c->n_requantised = 0;
-    c->final_from_counts = false; c->final_from_fixed = false;
+    c->final_from_counts = false; c->final_from_fixed = false; c->final_folded = false;
     bool readout_done = false, sis_bounded = false;
     (void)sis_bounded;
     if (c->cfg.algorithm == CPPROB_HIP_ALG_SIS) {
@@ -1381,7 +1411,7 @@ int cpprob_hip_infer_run(cpprob_hip_ctx* c, uint64_t run_index)
             }
             hipLaunchKernelGGL(filter_finalize_kernel, dim3(c->T), dim3(kThreads), 0, c->stream, (const double*)c->d_fpart, c->smooth_grid, c->K, c->is_int ? 1 : 0, c->d_stats, 1, (double*)nullptr);
         }
-    } else if (!readout_done) dispatch_model(c, [&](auto m) { launch_smooth<decltype(m)>(c, false); });
+    } else if (!readout_done && !c->final_folded) dispatch_model(c, [&](auto m) { launch_smooth<decltype(m)>(c, false); });
     HIP_TRY(c, hipGetLastError());
     c->ran = true;
     c->fixed_check_pending = c->fixed_mode && c->cfg.algorithm == CPPROB_HIP_ALG_SMC; c->last_was_infer_run = true; c->last_run_index = run_index;
@@ -1553,7 +1583,7 @@ int cpprob_hip_smc_step_begin(cpprob_hip_ctx* c, int32_t t, uint64_t run_index, 
         c->strata_pending = !sis && c->cfg.resampler == CPPROB_HIP_RESAMPLE_MULTINOMIAL && !(c->cfg.flags & CPPROB_HIP_FLAG_MULTINOMIAL_LITERAL);
         c->run_seed = c->cfg.seed + run_index; c->cur = 0; c->cur_part = 0; c->ran = false; c->annex_used = 0; c->plan.t = -1; c->x_plan_t = -1;
         c->n_requantised = 0; c->annex_used_before.clear();
-        c->final_from_counts = false; c->final_from_fixed = false;
+        c->final_from_counts = false; c->final_from_fixed = false; c->final_folded = false;
         c->counts_mode = false; c->fixed_mode = false;
         // the integer forms serve exact joint resampling (exchange scope) and a population held by this context alone; a shard that
         // resamples locally (global scope, several ranks) keeps the floating-point form and its mass-share bookkeeping

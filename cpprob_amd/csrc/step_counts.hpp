@@ -565,6 +565,61 @@ __device__ __forceinline__ void counts_strata_walk(const TableCdf& tc, const uin
     for (int i = 0; i < kPPT; ++i) if (live[i]) anc[i] = (int32_t)(n - 1);
 }
 
+// Trace words (trace_words.hpp): the pair counts n[t][key] of the read-out, key = 3 (x_t - 1) + x_{T-1} for x_t in {1, 2}.
+constexpr int kTraceMaxT = 16;                  // 2 bits a state in a 32-bit word
+constexpr int kTraceKeys = 6;                   // (x_t, x_{T-1}) pairs with x_t in {1, 2}
+
+// P(x_t = s | y) from a population's pair counts n[t * kTraceKeys + key] (raw: the un-normalised sum): the class sizes -- x_{T-1} = c
+// pairs with itself -- and the normaliser as counts_final_bookkeep takes it.  trace_readout_kernel and the folded last step.
+__device__ __forceinline__ double trace_stat(const unsigned long long* cnt, int T, int t, int s, double n_all, const double* e, bool raw)
+{
+    const double e0 = e[0], e1 = e[1], e2 = e[2];
+    const unsigned long long* last = cnt + (T - 1) * kTraceKeys;
+    const double N1 = (double)last[1], N2 = (double)last[5], N0 = n_all - N1 - N2;
+    const double W = fma(N2, e2, fma(N1, e1, __dmul_rn(N0, e0)));
+    const unsigned long long* row = cnt + t * kTraceKeys;
+    double n0, n1, n2;                                        // particles of class 0 / 1 / 2 whose trace held s at t
+    if (s == 0) { n0 = N0 - (double)(row[0] + row[3]); n1 = N1 - (double)(row[1] + row[4]); n2 = N2 - (double)(row[2] + row[5]); }
+    else { n0 = (double)row[3 * (s - 1)]; n1 = (double)row[3 * (s - 1) + 1]; n2 = (double)row[3 * (s - 1) + 2]; }
+    const double num = fma(n2, e2, fma(n1, e1, __dmul_rn(n0, e0)));
+    return raw ? num : num / W;
+}
+
+// Read-out of a single-shard run in the prefix-count form.  The last step is an ordinary step: it leaves its generation's counts
+// like any other, and what the read-out needs follows from them and the particles' states -- the final weight of a particle is
+// e[x] (three values), the normaliser W the same fma chain over the generation's totals that every step's prologue evaluates.  So
+// no log-weight / linear-weight arrays are written, no tile partials, and no normalisation launch sits between the last step and
+// the lineage walk: workgroup 0's first wavefront does the bookkeeping of the final generation on its way in.
+struct CountsFinal {
+    Hier h;                      // the final generation's counts (the copy the last step wrote)
+    double e[4];                 // exp(ll_s - max ll) of the last step, then max ll
+    double n_pop; int T;
+    int bookkeep;                // 0: the run's bookkeeping is done (a joint population's, by counts_final_ctrl_kernel; a repeated read-out)
+    StepCtrl* ctrl; double* ess_trace; int32_t* resampled;
+    double* filter_stats;        // filtering-only run: [T][3]; the final generation's row is written with its bookkeeping
+};
+
+// Bookkeeping of the final generation (scan_tail's, for a generation no resampling follows) from its totals.  One thread.
+__device__ __forceinline__ void counts_final_bookkeep(const CountsFinal& f, double tot0, double tot1)
+{
+    const double tot2 = f.n_pop - tot0 - tot1;
+    const double W = fma(tot2, f.e[2], fma(tot1, f.e[1], __dmul_rn(tot0, f.e[0])));
+    const double Q = fma(tot2, __dmul_rn(f.e[2], f.e[2]), fma(tot1, __dmul_rn(f.e[1], f.e[1]), __dmul_rn(tot0, __dmul_rn(f.e[0], f.e[0]))));
+    const double ess = W * W / Q;
+    StepCtrl* c = f.ctrl;
+    c->M = f.e[3]; c->W = W; c->Q = Q; c->ess = ess; c->do_resample = 0;
+    c->cdf_lo = 0.0; c->w_local = W; c->scale = 1.0; c->lw_after = 0.0; c->inv_stepw = f.n_pop / W; c->inv_global = f.n_pop / W;
+    const double lz = (f.T == 1) ? 0.0 : c->log_z;
+    if (f.T == 1) c->n_resampled = 0;
+    c->log_z = lz + (f.e[3] + log(W / f.n_pop));
+    if (f.ess_trace) f.ess_trace[f.T - 1] = ess;
+    if (f.resampled) f.resampled[f.T - 1] = 0;
+    if (f.filter_stats) {
+        double* fs = f.filter_stats + 3 * (f.T - 1);
+        fs[0] = __dmul_rn(tot0, f.e[0]) / W; fs[1] = __dmul_rn(tot1, f.e[1]) / W; fs[2] = __dmul_rn(tot2, f.e[2]) / W;
+    }
+}
+
 struct StepFound { Located loc; double inv, base0, base1, basev; int64_t l0, l1; int w0, w1; double W, c_lo, c_hi; };      // what the searching wavefront hands the other three
 
 #ifndef CPPROB_HAND_OVER
@@ -620,6 +675,222 @@ __device__ __forceinline__ void hier_publish(const Hier& h, int bid, int nb, uin
     if (h.n_lev >= 3 && (b2 << 12) == bid) l2[h.to_clear + (int64_t)b2 * kHierStride] = 0;
 }
 
+// Bookkeeping of generation t-1 for the host: ESS (thesis p.37), evidence.  One thread: workgroup 0's searching wavefront in an
+// ordinary step, the last workgroup to arrive in the run's last step when the read-out is folded into it (step_fold_tail).
+template <class Model>
+__device__ __forceinline__ void counts_step_bookkeep(const StepCountsArgs<Model>& a, int t, const TableCdf& tc, double W, double tot0, double tot1)
+{
+    const double mref = a.e_prev[3];
+    const double tot2 = a.n_pop - tot0 - tot1;
+    const double Q = fma(tot2, __dmul_rn(tc.e2, tc.e2), fma(tot1, __dmul_rn(tc.e1, tc.e1), __dmul_rn(tot0, __dmul_rn(tc.e0, tc.e0))));
+    const double ess = W * W / Q;
+    StepCtrl* c = a.ctrl;
+    c->M = mref; c->W = W; c->Q = Q; c->ess = ess; c->do_resample = 1;
+    c->cdf_lo = 0.0; c->w_local = W; c->scale = 1.0; c->u0 = tc.u0; c->inv_stepw = tc.inv; c->lw_after = 0.0; c->inv_global = tc.inv;
+    double lz = (t == 1) ? 0.0 : c->log_z;
+    int nr = (t == 1) ? 0 : c->n_resampled;
+    lz += mref + log(W / a.n_pop); nr += 1;
+    c->log_z = lz; c->n_resampled = nr;
+    if (a.ess_trace) a.ess_trace[t - 1] = ess;
+    if (a.resampled) a.resampled[t - 1] = 1;
+    if (a.filter_stats) {                              // predict hit t-1 under generation t-1's own weights
+        double* fs = a.filter_stats + 3 * (t - 1);
+        fs[0] = __dmul_rn(tot0, tc.e0) / W; fs[1] = __dmul_rn(tot1, tc.e1) / W; fs[2] = __dmul_rn(tot2, tc.e2) / W;
+    }
+}
+
+// ---- The run's last step with the read-out folded in (smc_step_counts_kernel<..., LAST = true>) ----
+// The trace-word read-out (trace_words.hpp) is a reduction to 6 T integers, and the last step holds all it reads: every particle's
+// trace word and state in registers, the final weights as kernel arguments.  So the last step counts them itself, and the workgroup
+// that arrives last writes the statistics and does the run's bookkeeping: no read-out launch, no second pass over the trace words.
+// (Without trace words the form is the bookkeeping alone; the host keeps filtering-only runs on counts_filter_final_kernel, one
+//  wavefront, which measured faster than the fold's tail: profiles/r07_notes.md.)
+//   counting   bit-parallel over the lane's four words: x_t = 1 and x_t = 2 as one bit at 2t each, added per class x_{T-1} over a
+//              pair of particles (2-bit fields), split into nibbles (even / odd t), one DPP step across lanes, bytes, three more:
+//              lane 15 of every row of 16 lanes holds the row's counts and leaves them in LDS (the walk's slots, free by then)
+//   reduction  a workgroup adds its counts into the counter set of its 64-tile block: no address takes more than 64 atomic adds
+//   arrival    through the hierarchy's own entries.  The level-1 add carries an arrival (the three-level publish's always does);
+//              the block's last tile adds one to the top counter (two levels), or forwards the block's set into that of its level-2
+//              block and arrives there (three levels).  <= 64 tiles: every workgroup arrives at the top counter
+//   last       collects and clears the top sets and the top counter (the arrival fields go with the copy's next clear), does the
+//              bookkeeping of generation T-2 and of the final generation, and writes the statistics
+// Generation T-2's bookkeeping moves from workgroup 0 to the last arriver because both write StepCtrl: plain stores of two
+// workgroups of one launch sit in the L2 of two XCDs and reach memory in no defined order.
+constexpr int kFoldSetWords = 128;                 // a counter set: [t][key] (t < T), then the block's state-0 and state-1 totals
+constexpr int kFoldN0 = kTraceMaxT * kTraceKeys, kFoldN1 = kFoldN0 + 1;
+constexpr int kFoldRows = kWaves * kWave / 16;     // rows of 16 lanes in a workgroup
+static_assert(kFoldN1 < kFoldSetWords && kFoldRows == 16, "fold layout");
+
+struct StepFold {
+    uint32_t* cnt;                                 // [level-1 blocks (one set at <= 64 tiles), then level-2 blocks][kFoldSetWords], zero between runs
+    unsigned long long* arrive;                    // top arrival counter, zero between runs
+    double* stats;                                 // [T][3] posterior statistics from the trace words (nullptr: a filtering-only run)
+    CountsFinal f;                                 // the final generation's bookkeeping (f.h unused)
+};
+template <class Model>
+struct StepCountsLastArgs : StepCountsArgs<Model> { StepFold fold; };
+template <class Model, bool LAST> struct StepArgsOf { using type = StepCountsArgs<Model>; };
+template <class Model> struct StepArgsOf<Model, true> { using type = StepCountsLastArgs<Model>; };
+
+// The lane's pair counts, reduced over its row of 16 lanes: rows[word * kFoldRows + row], word = (class * 4 + j) * 2 + (m & 1), byte
+// m >> 1 -- j = 2 (x_t - 1) + (t & 1), m = t >> 1 (<= 64 a byte).  All lanes active.
+template <class V>
+__device__ __forceinline__ void fold_count_rows(const uint32_t (&tw)[kPPT], const V (&x)[kPPT], const bool (&valid)[kPPT], uint32_t* rows)
+{
+    static_assert(kPPT == 4, "two pairs a lane");
+    constexpr uint32_t kLow = 0x55555555u, kField = 0x33333333u;
+    uint32_t acc[3][4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        uint32_t s1[3], s2[3];                     // x_t = 1 / x_t = 2 in the pair, per class: 2-bit fields at 2t (<= 2)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int k = 2 * p + h;
+            const uint32_t v = valid[k] ? tw[k] : 0u, v1 = v >> 1;
+            const uint32_t i1 = v & ~v1 & kLow, i2 = v1 & ~v & kLow;
+            const int cls = (int)x[k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const uint32_t a1 = cls == c ? i1 : 0u, a2 = cls == c ? i2 : 0u;
+                s1[c] = h ? s1[c] + a1 : a1; s2[c] = h ? s2[c] + a2 : a2;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const uint32_t q[4] = {s1[c] & kField, (s1[c] >> 2) & kField, s2[c] & kField, (s2[c] >> 2) & kField};   // nibble m: t = 2m / 2m + 1
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[c][j] = p ? acc[c][j] + q[j] : q[j];                                    // (<= 4)
+        }
+    }
+    const int lane = lane_id(), row = wave_id() * (kWave / 16) + (lane >> 4);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t w = acc[c][j] + (uint32_t)dpp_or_i32<kDppRowShr1>((int32_t)acc[c][j], 0);             // (<= 8: still nibbles)
+            uint32_t b[2] = {w & 0x0f0f0f0fu, (w >> 4) & 0x0f0f0f0fu};
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                b[hh] += (uint32_t)dpp_or_i32<kDppRowShr2>((int32_t)b[hh], 0);
+                b[hh] += (uint32_t)dpp_or_i32<kDppRowShr4>((int32_t)b[hh], 0);
+                b[hh] += (uint32_t)dpp_or_i32<kDppRowShr8>((int32_t)b[hh], 0);
+                if ((lane & 15) == 15) rows[((c * 4 + j) * 2 + hh) * kFoldRows + row] = b[hh];
+            }
+        }
+}
+
+// The workgroup's count of trace key i = t * kTraceKeys + 3 (x_t - 1) + x_{T-1}.
+__device__ __forceinline__ uint32_t fold_row_sum(const uint32_t* rows, int i)
+{
+    const int t = i / kTraceKeys, key = i - t * kTraceKeys, j = key < 3 ? (t & 1) : 2 + (t & 1), c = key < 3 ? key : key - 3;
+    const int m = t >> 1, word = (c * 4 + j) * 2 + (m & 1), sh = 8 * (m >> 1);
+    uint32_t s = 0;
+#pragma unroll
+    for (int r = 0; r < kFoldRows; ++r) s += (rows[word * kFoldRows + r] >> sh) & 0xffu;
+    return s;
+}
+
+// After the workgroup's counts are in LDS (rows) and its wavefronts' state totals in s_cnt, behind a barrier; every thread.
+// This tile's hierarchy entry is published here (hier_publish's work, with the arrivals above).
+template <class Model>
+__device__ __forceinline__ void step_fold_tail(const StepCountsLastArgs<Model>& a, int bid, int nb, bool traced, const int* s_cnt, int* s_flag, uint32_t* lds)
+{
+    const Hier& h = a.h;
+    const StepFold& fd = a.fold;
+    const int tid = threadIdx.x;
+    const int nk = traced ? a.T * kTraceKeys : 0;
+    const bool mine = tid < nk || tid == kFoldN0 || tid == kFoldN1;        // the counter this thread adds, forwards and collects
+    const int b1 = bid >> 6, b2 = bid >> 12;
+    uint64_t* l0 = const_cast<uint64_t*>(h.lvl[0]);
+    uint64_t* l1 = const_cast<uint64_t*>(h.lvl[1]);
+    uint64_t* l2 = const_cast<uint64_t*>(h.lvl[2]);
+    uint32_t* set1 = fd.cnt + (size_t)(h.n_lev == 1 ? 0 : b1) * kFoldSetWords;
+    if (mine) {
+        uint32_t v = 0;
+        if (tid < nk) v = fold_row_sum(lds, tid);
+        else {
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) v += (uint32_t)s_cnt[2 * w + (tid - kFoldN0)];
+        }
+        if (v) atomicAdd(set1 + tid, v);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // the adds performed before the workgroup's arrival is counted
+    __syncthreads();
+    uint64_t blk = 0;                                                    // (thread 0, three levels: its level-1 block's total)
+    if (tid == 0) {
+        uint32_t n0 = 0, n1 = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) { n0 += (uint32_t)s_cnt[2 * w]; n1 += (uint32_t)s_cnt[2 * w + 1]; }
+        const uint64_t ent = (uint64_t)n0 | ((uint64_t)n1 << 28);
+        l0[h.to_next + bid] = ent;
+        int st = 0;
+        if (h.n_lev == 1) st = atomicAdd(fd.arrive, 1ull) == (unsigned long long)(nb - 1) ? 2 : 0;
+        else {
+            const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long*>(l1 + h.to_next + (int64_t)b1 * kHierStride),
+                                                     (unsigned long long)(ent + (1ull << 56)));
+            const int tiles_in_block = nb - (b1 << 6) < 64 ? nb - (b1 << 6) : 64;
+            if ((int)(old >> 56) == tiles_in_block - 1) {
+                if (h.n_lev == 2) st = atomicAdd(fd.arrive, 1ull) == (unsigned long long)(h.n_ent[1] - 1) ? 2 : 0;
+                else { st = 1; blk = (old + ent) & ((1ull << 56) - 1); }
+            }
+        }
+        if (h.n_lev >= 2 && (b1 << 6) == bid) l1[h.to_clear + (int64_t)b1 * kHierStride] = 0;
+        if (h.n_lev >= 3 && (b2 << 12) == bid) l2[h.to_clear + (int64_t)b2 * kHierStride] = 0;
+        *s_flag = st;
+    }
+    __syncthreads();
+    int st = *s_flag;
+    if (st == 1) {
+        // three levels, the last tile of its level-1 block: the block's set into its level-2 block's, then the arrival there
+        uint32_t* set2 = fd.cnt + (size_t)(h.n_ent[1] + b2) * kFoldSetWords;
+        if (mine) { const uint32_t v = atomicExch(set1 + tid, 0u); if (v) atomicAdd(set2 + tid, v); }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long*>(l2 + h.to_next + (int64_t)b2 * kHierStride),
+                                                     (unsigned long long)(blk + (1ull << 56)));
+            const int blocks_in_block = h.n_ent[1] - (b2 << 6) < 64 ? h.n_ent[1] - (b2 << 6) : 64;
+            *s_flag = ((int)(old >> 56) == blocks_in_block - 1 && atomicAdd(fd.arrive, 1ull) == (unsigned long long)(h.n_ent[2] - 1)) ? 2 : 0;
+        }
+        __syncthreads();
+        st = *s_flag;
+    }
+    if (st != 2) return;
+
+    // last to arrive: every workgroup's adds have been performed.  Collect and clear (read where the adds were performed).
+    unsigned long long* s_n = reinterpret_cast<unsigned long long*>(lds + 512);   // (beyond the rows)
+    const int top_sets = h.n_lev == 1 ? 1 : h.n_ent[h.n_lev - 1];
+    uint32_t* top = fd.cnt + (size_t)(h.n_lev == 3 ? h.n_ent[1] : 0) * kFoldSetWords;
+    if (mine) {
+        unsigned long long n = 0;
+        for (int s0 = 0; s0 < top_sets; s0 += 16) {
+            uint32_t r[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) r[i] = s0 + i < top_sets ? atomicExch(top + (size_t)(s0 + i) * kFoldSetWords + tid, 0u) : 0u;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) n += r[i];
+        }
+        s_n[tid] = n;
+    }
+    if (tid == 0) atomicExch(fd.arrive, 0ull);
+    __syncthreads();
+    if (tid < kWave) {
+        if (a.t > 0) {                                                   // generation T-2's bookkeeping, as workgroup 0's search does it
+            const Cnt2 tl = hier_total(h);
+            if (tid == 0) {
+                TableCdf tc;
+                tc.e0 = a.e_prev[0]; tc.e1 = a.e_prev[1]; tc.e2 = a.e_prev[2]; tc.n_pop = a.n_pop; tc.u0 = a.u0;
+                const double tot0 = (double)tl.n0, tot1 = (double)tl.n1;
+                const double W = tc.cdf(tot0, tot1, tc.n_pop);
+                tc.inv = a.n_pop / W;
+                counts_step_bookkeep(a, a.t, tc, W, tot0, tot1);
+            }
+        }
+        if (tid == 0) counts_final_bookkeep(fd.f, (double)s_n[kFoldN0], (double)s_n[kFoldN1]);
+        if (traced && tid < 3 * a.T) fd.stats[tid] = trace_stat(s_n, a.T, tid / 3, tid - 3 * (tid / 3), fd.f.n_pop, fd.f.e, false);
+    }
+}
+
 // SHARDED: one shard of a joint population (exchange scope).  Compile-time forms: each keeps only the arguments it uses in scalar
 // registers.  The run's last step is a step like any other: the read-out works from the counts it leaves (smooth_counts_kernel).
 #ifdef CPPROB_COUNTS_WAVES
@@ -627,9 +898,11 @@ __device__ __forceinline__ void hier_publish(const Hier& h, int bid, int nb, uin
 #else
 #define CPPROB_COUNTS_OCC
 #endif
-template <class Model, bool SHARDED, int RS = kFixSystematic>
-__global__ __launch_bounds__(kThreads) CPPROB_COUNTS_OCC void smc_step_counts_kernel(StepCountsArgs<Model> a)
+// LAST: the run's last step with the read-out folded in (step_fold_tail; one population of its own).
+template <class Model, bool SHARDED, int RS = kFixSystematic, bool LAST = false>
+__global__ __launch_bounds__(kThreads) CPPROB_COUNTS_OCC void smc_step_counts_kernel(typename StepArgsOf<Model, LAST>::type a)
 {
+    static_assert(!(SHARDED && LAST), "the folded read-out serves a population of its own");
     using V = typename Model::value_t;
     using S = typename Model::store_t;
     static_assert(Model::kWeightTable == 3, "prefix-count form: three table values (two stored counts)");
@@ -759,25 +1032,8 @@ __global__ __launch_bounds__(kThreads) CPPROB_COUNTS_OCC void smc_step_counts_ke
             }
             const double W = tc.cdf(tot0, tot1, tc.n_pop);
             tc.inv = in_vgpr(a.n_pop / W);
-            if (bid == 0 && tid == 0) {                            // bookkeeping of step t-1 for the host: ESS (thesis p.37), evidence
-                const double mref = a.e_prev[3];
-                const double tot2 = a.n_pop - tot0 - tot1;
-                const double Q = fma(tot2, __dmul_rn(tc.e2, tc.e2), fma(tot1, __dmul_rn(tc.e1, tc.e1), __dmul_rn(tot0, __dmul_rn(tc.e0, tc.e0))));
-                const double ess = W * W / Q;
-                StepCtrl* c = a.ctrl;
-                c->M = mref; c->W = W; c->Q = Q; c->ess = ess; c->do_resample = 1;
-                c->cdf_lo = 0.0; c->w_local = W; c->scale = 1.0; c->u0 = tc.u0; c->inv_stepw = tc.inv; c->lw_after = 0.0; c->inv_global = tc.inv;
-                double lz = (t == 1) ? 0.0 : c->log_z;
-                int nr = (t == 1) ? 0 : c->n_resampled;
-                lz += mref + log(W / a.n_pop); nr += 1;
-                c->log_z = lz; c->n_resampled = nr;
-                if (a.ess_trace) a.ess_trace[t - 1] = ess;
-                if (a.resampled) a.resampled[t - 1] = 1;
-                if (a.filter_stats) {                              // predict hit t-1 under generation t-1's own weights
-                    double* fs = a.filter_stats + 3 * (t - 1);
-                    fs[0] = __dmul_rn(tot0, tc.e0) / W; fs[1] = __dmul_rn(tot1, tc.e1) / W; fs[2] = __dmul_rn(tot2, tc.e2) / W;
-                }
-            }
+            // bookkeeping of step t-1 for the host (the folded last step: its last arriver's)
+            if (!LAST && bid == 0 && tid == 0) counts_step_bookkeep(a, t, tc, W, tot0, tot1);
             Located loc{0, 0, 0, 0};
             int sw0 = 0, sw1 = 0;
             double c_lo = 0.0, c_hi = W;
@@ -888,49 +1144,18 @@ __global__ __launch_bounds__(kThreads) CPPROB_COUNTS_OCC void smc_step_counts_ke
         c1 += (uint32_t)__popcll(__ballot(valid[k] && s == 1));
     }
     if (lane_id() == 0) { s_cnt[2 * wave_id()] = (int)c0; s_cnt[2 * wave_id() + 1] = (int)c1; }
+    if constexpr (LAST) {
+        if (traced) fold_count_rows<V>(tw, x, valid, reinterpret_cast<uint32_t*>(L.slot));
+    }
     __syncthreads();
-    if (tid == 0) {
+    if constexpr (LAST) step_fold_tail<Model>(a, bid, nb, traced, s_cnt, s_cnt + 2 * kWaves, reinterpret_cast<uint32_t*>(L.slot));
+    else if (tid == 0) {
         uint32_t n0 = 0, n1 = 0;
 #pragma unroll
         for (int w = 0; w < kWaves; ++w) { n0 += (uint32_t)s_cnt[2 * w]; n1 += (uint32_t)s_cnt[2 * w + 1]; }
         hier_publish(a.h, bid, nb, n0, n1, true);
     }
     CPH_STAMP(5);
-}
-
-// Read-out of a single-shard run in the prefix-count form.  The last step is an ordinary step: it leaves its generation's counts
-// like any other, and what the read-out needs follows from them and the particles' states -- the final weight of a particle is
-// e[x] (three values), the normaliser W the same fma chain over the generation's totals that every step's prologue evaluates.  So
-// no log-weight / linear-weight arrays are written, no tile partials, and no normalisation launch sits between the last step and
-// the lineage walk: workgroup 0's first wavefront does the bookkeeping of the final generation on its way in.
-struct CountsFinal {
-    Hier h;                      // the final generation's counts (the copy the last step wrote)
-    double e[4];                 // exp(ll_s - max ll) of the last step, then max ll
-    double n_pop; int T;
-    int bookkeep;                // 0: the run's bookkeeping is done (a joint population's, by counts_final_ctrl_kernel; a repeated read-out)
-    StepCtrl* ctrl; double* ess_trace; int32_t* resampled;
-    double* filter_stats;        // filtering-only run: [T][3]; the final generation's row is written with its bookkeeping
-};
-
-// Bookkeeping of the final generation (scan_tail's, for a generation no resampling follows) from its totals.  One thread.
-__device__ __forceinline__ void counts_final_bookkeep(const CountsFinal& f, double tot0, double tot1)
-{
-    const double tot2 = f.n_pop - tot0 - tot1;
-    const double W = fma(tot2, f.e[2], fma(tot1, f.e[1], __dmul_rn(tot0, f.e[0])));
-    const double Q = fma(tot2, __dmul_rn(f.e[2], f.e[2]), fma(tot1, __dmul_rn(f.e[1], f.e[1]), __dmul_rn(tot0, __dmul_rn(f.e[0], f.e[0]))));
-    const double ess = W * W / Q;
-    StepCtrl* c = f.ctrl;
-    c->M = f.e[3]; c->W = W; c->Q = Q; c->ess = ess; c->do_resample = 0;
-    c->cdf_lo = 0.0; c->w_local = W; c->scale = 1.0; c->lw_after = 0.0; c->inv_stepw = f.n_pop / W; c->inv_global = f.n_pop / W;
-    const double lz = (f.T == 1) ? 0.0 : c->log_z;
-    if (f.T == 1) c->n_resampled = 0;
-    c->log_z = lz + (f.e[3] + log(W / f.n_pop));
-    if (f.ess_trace) f.ess_trace[f.T - 1] = ess;
-    if (f.resampled) f.resampled[f.T - 1] = 0;
-    if (f.filter_stats) {
-        double* fs = f.filter_stats + 3 * (f.T - 1);
-        fs[0] = __dmul_rn(tot0, f.e[0]) / W; fs[1] = __dmul_rn(tot1, f.e[1]) / W; fs[2] = __dmul_rn(tot2, f.e[2]) / W;
-    }
 }
 
 // The same for one shard of a joint population, from the all-gathered {n_0, n_1, particles} of every rank (exact doubles: the sums

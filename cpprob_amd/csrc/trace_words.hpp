@@ -19,8 +19,7 @@
 
 namespace cph {
 
-constexpr int kTraceMaxT = 16;                  // 2 bits a state in a 32-bit word
-constexpr int kTraceKeys = 6;                   // (x_t, x_{T-1}) pairs with x_t in {1, 2}: key = 3 (x_t - 1) + x_{T-1}
+// (kTraceMaxT, kTraceKeys and the statistics of the counts, trace_stat: step_counts.hpp, whose folded last step counts the same way)
 constexpr int kTraceSlots = 2;                  // counter sets the workgroups spread their atomic adds over (same-call A/B, read-out us:
                                                 // 8 sets 14.9, 4 13.3, 2 12.4, 1 12.9 -- the last workgroup's collect is one exchange per set)
 constexpr int kTraceLine = 32;                  // 32-bit words between two counters: a 128-byte line each
@@ -116,17 +115,7 @@ __global__ __launch_bounds__(kThreads) void trace_readout_kernel(TraceReadoutArg
     __syncthreads();
     if (tid < a.T * 3) {
         const int t = tid / 3, s = tid - 3 * t;
-        const double e0 = a.f.e[0], e1 = a.f.e[1], e2 = a.f.e[2];
-        // the class sizes -- x_{T-1} = c pairs with itself -- and the normaliser as counts_final_bookkeep takes it
-        const unsigned long long* last = s_n + (a.T - 1) * kTraceKeys;
-        const double N1 = (double)last[1], N2 = (double)last[5], N0 = (a.raw ? a.n_local : a.f.n_pop) - N1 - N2;
-        const double W = fma(N2, e2, fma(N1, e1, __dmul_rn(N0, e0)));
-        const unsigned long long* row = s_n + t * kTraceKeys;
-        double n0, n1, n2;                                        // particles of class 0 / 1 / 2 whose trace held s at t
-        if (s == 0) { n0 = N0 - (double)(row[0] + row[3]); n1 = N1 - (double)(row[1] + row[4]); n2 = N2 - (double)(row[2] + row[5]); }
-        else { n0 = (double)row[3 * (s - 1)]; n1 = (double)row[3 * (s - 1) + 1]; n2 = (double)row[3 * (s - 1) + 2]; }
-        const double num = fma(n2, e2, fma(n1, e1, __dmul_rn(n0, e0)));
-        a.stats[t * 3 + s] = a.raw ? num : num / W;
+        a.stats[t * 3 + s] = trace_stat(s_n, a.T, t, s, a.raw ? a.n_local : a.f.n_pop, a.f.e, a.raw != 0);
     }
 }
 

@@ -136,6 +136,8 @@ typedef struct cpprob_hip_config {
 #define CPPROB_HIP_FLAG_REPEAT_IN_FLOATING_POINT 256u /* fixed-point form: a run with a generation that lost its bits is repeated whole in the floating-point form
                                                         (the r03 / r04 behaviour) instead of being repaired from that generation on, in integers */
 #define CPPROB_HIP_FLAG_MULTINOMIAL_LITERAL 128u /* multinomial resampling: ancestor of output j = min{k : C_k > floor(u_j C_N)}, one search per output */
+#define CPPROB_HIP_FLAG_SEPARATE_TRACE_READOUT 1024u /* prefix-count form, a population of its own (A/B): the read-out of the trace words (or of a
+                                                        filtering-only run's final generation) as a launch after the last step, not folded into it */
 
 /* Posterior summary of a finished run -- what StatsPrinter prints
  * (include/cpprob/postprocess/stats_printer.hpp:42-79) plus SMC diagnostics. */
