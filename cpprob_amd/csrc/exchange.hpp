@@ -286,8 +286,10 @@ __global__ __launch_bounds__(kThreads) void exchange_cut_kernel(CutArgs a)
     }
     if (wv == 0) { if (lane <= world) s_P[lane] = lane < world ? Pl : total; if (lane <= world) s_begin[lane] = (uint32_t)a.shard_begin[lane]; if (lane < kWorldSlots) s_cnt[lane] = 0u; }
     __syncthreads();
+    // (table CDF: B_w = w * unit, ONE rounded product -- dmul_rn, so that no B_w below is contracted into the arithmetic that uses it:
+    //  counts_strata_walk and orc_strata_thresholds_table round the same product and then the same width and threshold)
     auto bound = [&](uint32_t w) -> T {
-        if constexpr (COUNTS) return (double)w * unit;
+        if constexpr (COUNTS) return dmul_rn((double)w, unit);
         else return strata_bound(total, (uint64_t)w, k);
     };
     const T Pb = s_P[b];
@@ -315,7 +317,7 @@ __global__ __launch_bounds__(kThreads) void exchange_cut_kernel(CutArgs a)
         const u32x4 blk = draw_block(a.seed, s >> 1, a.draw2);
         const uint64_t bits = (s & 1) ? bits53(blk.z, blk.w) : bits53(blk.x, blk.y);
         T tau;
-        if constexpr (COUNTS) tau = fma((double)bits * kTwoPowM53, b_hi - b_lo, b_lo);
+        if constexpr (COUNTS) tau = fma((double)bits * kTwoPowM53, dsub_rn(b_hi, b_lo), b_lo);
         else tau = b_lo + __umul64hi(bits << 11, b_hi - b_lo);
         uint32_t src = 0, dst = 0;
         for (int r = 1; r < world; ++r) { src += s_P[r] <= tau ? 1u : 0u; dst += s_begin[r] <= (uint32_t)s ? 1u : 0u; }       // (P and the shards' begins do not decrease)

@@ -53,7 +53,7 @@ struct TableCdf {
     __device__ __forceinline__ double cdf(double c0, double c1, double cv) const      // c*: GLOBAL inclusive counts
     {
         const double c2 = cv - c0 - c1;
-        return fma(c2, e2, fma(c1, e1, __dmul_rn(c0, e0)));
+        return fma(c2, e2, fma(c1, e1, dmul_rn(c0, e0)));
     }
     // (never negative: C >= 0 and u0 < 1; may exceed n_pop by rounding only for the population's last sources, whose surplus
     //  outputs nobody consumes -- the clamp of the stated arithmetic changes no ancestor)
@@ -61,7 +61,7 @@ struct TableCdf {
     // Stratified: output j sits at j + u_j (u_j = the 32-bit uniform of OUTPUT j), the sources up to CDF value C reach H = C * (N / W)
     // (one rounded product) and own the outputs with j + u_j < H: A = F + [u_F < H - F], F = floor(H) -- FixedCdf::first_stratified
     // with the table CDF in place of the integer mass; the CPU restatement: orc_resample_table_stratified.
-    __device__ __forceinline__ double h(double C) const { return __dmul_rn(C, inv); }
+    __device__ __forceinline__ double h(double C) const { return dmul_rn(C, inv); }
     __device__ __forceinline__ double first_stratified(double C) const
     {
         const double H = h(C), F = floor(H);
@@ -300,7 +300,7 @@ __device__ __forceinline__ void counts_walk(const TableCdf& tc, const S* __restr
             const uint32_t n2 = nvb + (uint32_t)(EDGE && upto > nvt ? nvt : upto) - n0 - n1;
             double c0 = (double)n0, c1 = (double)n1, c2 = (double)n2;
             if (sharded) { c0 += tc.base0; c1 += tc.base1; c2 += base2; }
-            const double C = fma(c2, tc.e2, fma(c1, tc.e1, __dmul_rn(c0, tc.e0)));
+            const double C = fma(c2, tc.e2, fma(c1, tc.e1, dmul_rn(c0, tc.e0)));
             if constexpr (RS == kFixStratified) {
                 // (L.ustrat: the outputs' uniforms, staged by the caller)
                 const double H = tc.h(C), F = floor(H), d = F - gj_first;
@@ -472,8 +472,8 @@ __device__ __forceinline__ void counts_strata_walk(const TableCdf& tc, const uin
         lane_strata4(offs, k, w0, w1, (uint32_t)j0, ws, live);
 #pragma unroll
         for (int i = 0; i < kPPT; ++i) {
-            const double b_lo = __dmul_rn((double)ws[i], unit), b_hi = __dmul_rn((double)(ws[i] + 1), unit);
-            tau[i] = live[i] ? fma(v[i], __dsub_rn(b_hi, b_lo), b_lo) : 0.0;
+            const double b_lo = dmul_rn((double)ws[i], unit), b_hi = dmul_rn((double)(ws[i] + 1), unit);
+            tau[i] = live[i] ? fma(v[i], dsub_rn(b_hi, b_lo), b_lo) : 0.0;
         }
     }
     // (j0 = the lane's first output in the POPULATION; of a shard's outputs only those whose threshold lies in its sources' range)
@@ -533,7 +533,7 @@ __device__ __forceinline__ void counts_strata_walk(const TableCdf& tc, const uin
                     const int upto = tid * kPPT + i + 1;
                     const uint32_t n0 = P0 + (packed & 0xffffu), n1 = P1 + (packed >> 16);
                     const uint32_t n2 = nvb + (uint32_t)((int64_t)upto > nvt ? (nvt > 0 ? nvt : 0) : upto) - n0 - n1;
-                    cdv[i] = fma((double)n2 + base2, tc.e2, fma((double)n1 + tc.base1, tc.e1, __dmul_rn((double)n0 + tc.base0, tc.e0)));
+                    cdv[i] = fma((double)n2 + base2, tc.e2, fma((double)n1 + tc.base1, tc.e1, dmul_rn((double)n0 + tc.base0, tc.e0)));
                 }
                 using D2 = double __attribute__((ext_vector_type(2)));
                 D2 a0, a1;
@@ -576,12 +576,12 @@ __device__ __forceinline__ double trace_stat(const unsigned long long* cnt, int 
     const double e0 = e[0], e1 = e[1], e2 = e[2];
     const unsigned long long* last = cnt + (T - 1) * kTraceKeys;
     const double N1 = (double)last[1], N2 = (double)last[5], N0 = n_all - N1 - N2;
-    const double W = fma(N2, e2, fma(N1, e1, __dmul_rn(N0, e0)));
+    const double W = fma(N2, e2, fma(N1, e1, dmul_rn(N0, e0)));
     const unsigned long long* row = cnt + t * kTraceKeys;
     double n0, n1, n2;                                        // particles of class 0 / 1 / 2 whose trace held s at t
     if (s == 0) { n0 = N0 - (double)(row[0] + row[3]); n1 = N1 - (double)(row[1] + row[4]); n2 = N2 - (double)(row[2] + row[5]); }
     else { n0 = (double)row[3 * (s - 1)]; n1 = (double)row[3 * (s - 1) + 1]; n2 = (double)row[3 * (s - 1) + 2]; }
-    const double num = fma(n2, e2, fma(n1, e1, __dmul_rn(n0, e0)));
+    const double num = fma(n2, e2, fma(n1, e1, dmul_rn(n0, e0)));
     return raw ? num : num / W;
 }
 
@@ -603,8 +603,8 @@ struct CountsFinal {
 __device__ __forceinline__ void counts_final_bookkeep(const CountsFinal& f, double tot0, double tot1)
 {
     const double tot2 = f.n_pop - tot0 - tot1;
-    const double W = fma(tot2, f.e[2], fma(tot1, f.e[1], __dmul_rn(tot0, f.e[0])));
-    const double Q = fma(tot2, __dmul_rn(f.e[2], f.e[2]), fma(tot1, __dmul_rn(f.e[1], f.e[1]), __dmul_rn(tot0, __dmul_rn(f.e[0], f.e[0]))));
+    const double W = fma(tot2, f.e[2], fma(tot1, f.e[1], dmul_rn(tot0, f.e[0])));
+    const double Q = fma(tot2, dmul_rn(f.e[2], f.e[2]), fma(tot1, dmul_rn(f.e[1], f.e[1]), dmul_rn(tot0, dmul_rn(f.e[0], f.e[0]))));
     const double ess = W * W / Q;
     StepCtrl* c = f.ctrl;
     c->M = f.e[3]; c->W = W; c->Q = Q; c->ess = ess; c->do_resample = 0;
@@ -616,7 +616,7 @@ __device__ __forceinline__ void counts_final_bookkeep(const CountsFinal& f, doub
     if (f.resampled) f.resampled[f.T - 1] = 0;
     if (f.filter_stats) {
         double* fs = f.filter_stats + 3 * (f.T - 1);
-        fs[0] = __dmul_rn(tot0, f.e[0]) / W; fs[1] = __dmul_rn(tot1, f.e[1]) / W; fs[2] = __dmul_rn(tot2, f.e[2]) / W;
+        fs[0] = dmul_rn(tot0, f.e[0]) / W; fs[1] = dmul_rn(tot1, f.e[1]) / W; fs[2] = dmul_rn(tot2, f.e[2]) / W;
     }
 }
 
@@ -682,7 +682,7 @@ __device__ __forceinline__ void counts_step_bookkeep(const StepCountsArgs<Model>
 {
     const double mref = a.e_prev[3];
     const double tot2 = a.n_pop - tot0 - tot1;
-    const double Q = fma(tot2, __dmul_rn(tc.e2, tc.e2), fma(tot1, __dmul_rn(tc.e1, tc.e1), __dmul_rn(tot0, __dmul_rn(tc.e0, tc.e0))));
+    const double Q = fma(tot2, dmul_rn(tc.e2, tc.e2), fma(tot1, dmul_rn(tc.e1, tc.e1), dmul_rn(tot0, dmul_rn(tc.e0, tc.e0))));
     const double ess = W * W / Q;
     StepCtrl* c = a.ctrl;
     c->M = mref; c->W = W; c->Q = Q; c->ess = ess; c->do_resample = 1;
@@ -695,7 +695,7 @@ __device__ __forceinline__ void counts_step_bookkeep(const StepCountsArgs<Model>
     if (a.resampled) a.resampled[t - 1] = 1;
     if (a.filter_stats) {                              // predict hit t-1 under generation t-1's own weights
         double* fs = a.filter_stats + 3 * (t - 1);
-        fs[0] = __dmul_rn(tot0, tc.e0) / W; fs[1] = __dmul_rn(tot1, tc.e1) / W; fs[2] = __dmul_rn(tot2, tc.e2) / W;
+        fs[0] = dmul_rn(tot0, tc.e0) / W; fs[1] = dmul_rn(tot1, tc.e1) / W; fs[2] = dmul_rn(tot2, tc.e2) / W;
     }
 }
 

@@ -19,6 +19,21 @@
 
 namespace cph {
 
+// A correctly rounded product / difference that the compiler may NOT contract into a neighbouring add: hipcc contracts a * b + c into
+// one fma by default, across statements and through inlined helpers, and HIP's __dmul_rn / __dsub_rn are a plain `*` / `-` unless the
+// device library's rounded operations are switched on -- they pin nothing.  The expressions that decide integers in the exact
+// resamplers (the CPU oracle is built with -ffp-contract=off) round as the oracle does only through these.
+__host__ __device__ __forceinline__ double dmul_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__host__ __device__ __forceinline__ double dsub_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 // One Horner step as ONE instruction.  hipcc turns fma(p, r, c) with a loop-invariant coefficient held in a VGPR into
 // v_mov_b64 + v_fmac_f64 (the two-address form needs a scratch copy of c): an extra vector-issue slot per step in kernels whose
 // bound IS vector issue.  The three-address VOP3 form takes c where it lies -- and it lies in a SCALAR register pair ("s": one

@@ -249,7 +249,7 @@ struct FixedCdf {
     uint64_t seed, draw, uid0;                 // stratified: the run's Philox key, the resampling's draw index, the id of output 0
     // first output NOT owned by the sources up to a LOCAL inclusive mass C = first output owned by the sources that follow
     __device__ __forceinline__ double g(uint64_t C) const { return ceil(fma(u64_to_double(base + C), inv, -u0)); }
-    __device__ __forceinline__ double h(uint64_t C) const { return __dmul_rn(u64_to_double(base + C), inv); }
+    __device__ __forceinline__ double h(uint64_t C) const { return dmul_rn(u64_to_double(base + C), inv); }
     __device__ __forceinline__ double first_stratified(uint64_t C) const
     {
         const double H = h(C), F = floor(H);

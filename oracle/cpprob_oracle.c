@@ -1091,6 +1091,7 @@ static void hmm_weight_table(double y, double e[3], double *mref)
     for (int s = 0; s < 3; ++s) e[s] = exp(l[s] - mx);
     if (mref) *mref = mx;
 }
+ORC_API void orc_hmm_weight_table(double y, double e[3], double *mref) { hmm_weight_table(y, e, mref); }
 
 /* ------------------------------------------------------------------------- */
 /* SMC driver (row a15).  Markov step form of the three state-space models:   */

@@ -87,6 +87,7 @@ def lib():
         L.orc_strata_thresholds_table.argtypes = [dbl, u64, u64, u64, _dp, _ip]
         L.orc_table_cdf.restype = dbl; L.orc_table_cdf.argtypes = [_u64p, _dp]
         L.orc_multinomial_strata.argtypes = [u64, u64, u64, C.c_int, _up]
+        L.orc_hmm_weight_table.argtypes = [dbl, _dp, _dp]
         L.orc_set_hmm.restype = C.c_int; L.orc_set_hmm.argtypes = [C.c_int, _dp, _dp]
         L.orc_smc.restype = C.c_int
         L.orc_smc.argtypes = [C.c_int, _dp, sz, u64, u64, C.c_int, dbl, C.c_void_p, C.c_void_p, _ip, _dp,
@@ -333,6 +334,24 @@ def strata_thresholds_table(W, seed, step, n_pop):
 
 def table_cdf(counts, e):
     return float(lib().orc_table_cdf(np.ascontiguousarray(counts, np.uint64), np.ascontiguousarray(e, np.float64)))
+
+
+def hmm_weight_table(y):
+    """(e[3], max ll): e[s] = exp(ll_s - max ll) of MODEL_HMM3 at observation y -- the table the weights of a generation are drawn from."""
+    e = np.zeros(3); mx = np.zeros(1)
+    lib().orc_hmm_weight_table(float(y), e, mx)
+    return e, float(mx[0])
+
+
+def resample_u0(seed, step):
+    """u0 of systematic resampling at `step`: the 53-bit uniform of draw RESAMPLE_DRAW_BASE + step of group 0."""
+    r = draw_block(seed, 0, RESAMPLE_DRAW_BASE + step)
+    return float(lib().orc_u01_53(int(r[0]), int(r[1])))
+
+
+def stratified_u(seed, step, j):
+    """u_j of stratified resampling at `step`: the 32-bit uniform of output j."""
+    return float(lib().orc_u01_32(lib().orc_draw_word(seed, j, RESAMPLE_DRAW_BASE + step)))
 
 
 def multinomial_strata(seed, step, n_out, n_particles=None):
