@@ -33,6 +33,8 @@ SYMBOLS = [
     "cpprob_hip_logpdf_poisson", "cpprob_hip_logpdf_uniform_smallint", "cpprob_hip_logpdf_discrete", "cpprob_hip_logsumexp_ess",
     "cpprob_hip_weighted_moments", "cpprob_hip_weighted_hist", "cpprob_hip_weighted_moments_columns", "cpprob_hip_weighted_hist_columns", "cpprob_hip_resample", "cpprob_hip_smc_bookkeep", "cpprob_hip_smc_bookkeep_fixed", "cpprob_hip_smc_bookkeep_fixed_rs", "cpprob_hip_generic_begin", "cpprob_hip_generic_begin_tiles", "cpprob_hip_generic_quantize", "cpprob_hip_generic_max", "cpprob_hip_generic_quantize_ref", "cpprob_hip_generic_totals", "cpprob_hip_generic_finish", "cpprob_hip_systematic_offset", "cpprob_hip_lineage_gather", "cpprob_hip_lineage_prepare", "cpprob_hip_readback_with_next_result", "cpprob_hip_lineage_moments", "cpprob_hip_lineage_hist", "cpprob_hip_gather_f64",
     "cpprob_hip_gather_i32", "cpprob_hip_profile_enable", "cpprob_hip_profile_read", "cpprob_hip_fastmath",
+    "cpprob_hip_batch_workspace_bytes", "cpprob_hip_batch_begin", "cpprob_hip_batch_run", "cpprob_hip_batch_results", "cpprob_hip_batch_results_device",
+    "cpprob_hip_batch_copy_store",
 ]
 
 
@@ -57,6 +59,28 @@ class Summary(C.Structure):
 
 
 FORM_FLOAT, FORM_COUNTS, FORM_FIXED = 0, 1, 2
+
+
+class BatchConfig(C.Structure):
+    _fields_ = [("algorithm", C.c_int32), ("model", C.c_int32), ("resampler", C.c_int32), ("keep_history", C.c_int32),
+                ("flags", C.c_uint32), ("ess_threshold", C.c_double), ("n_particles", C.c_uint64), ("n_problems", C.c_uint64)]
+
+
+BATCH_MAX_PARTICLES = 8192
+
+
+def batch_workspace_bytes(model, n_particles, n_problems, T, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
+    """cpprob_hip_batch_workspace_bytes: validates a batch configuration and returns its device bytes; no GPU needed."""
+    L = load_library()
+    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), int(n_particles), int(n_problems))
+    out = C.c_uint64()
+    rc = L.cpprob_hip_batch_workspace_bytes(C.byref(cfg), int(T), C.byref(out))
+    if rc:
+        msg = L.cpprob_hip_last_error(None)
+        e = CpprobHipError("cpprob_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+        e.code = rc
+        raise e
+    return out.value
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -182,6 +206,12 @@ def load_library(path=None):
         "cpprob_hip_gather_i32": (C.c_int, [vp, vp, vp, sz, vp]),
         "cpprob_hip_profile_enable": (C.c_int, [vp, i32]),
         "cpprob_hip_profile_read": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(i64), i32]),
+        "cpprob_hip_batch_workspace_bytes": (C.c_int, [C.POINTER(BatchConfig), sz, C.POINTER(u64)]),
+        "cpprob_hip_batch_begin": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(dbl), sz]),
+        "cpprob_hip_batch_run": (C.c_int, [vp, C.POINTER(u64)]),
+        "cpprob_hip_batch_results": (C.c_int, [vp, C.POINTER(Summary), vp, sz, vp, vp]),
+        "cpprob_hip_batch_results_device": (C.c_int, [vp, vp, sz]),
+        "cpprob_hip_batch_copy_store": (C.c_int, [vp, u64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -340,6 +370,57 @@ class Engine:
         out = np.zeros((self.T, self.n), np.int32 if self.is_int else np.float64)
         self._chk(self.L.cpprob_hip_copy_paths(self.h, out.ctypes.data, out.nbytes))
         return out
+
+    # ---- batched SMC: many small problems, one launch (include/cpprob_hip.h: cpprob_hip_batch_*) --------------------
+    @staticmethod
+    def batch_config(model, n_particles, n_problems, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
+        return BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), int(n_particles), int(n_problems))
+
+    @staticmethod
+    def batch_workspace_bytes(model, n_particles, n_problems, T, **kw):
+        """Device bytes a batch of n_problems problems of T observes needs: a pure host function (no device, no context)."""
+        return batch_workspace_bytes(model, n_particles, n_problems, T, **kw)
+
+    def batch_begin(self, model, observes, n_particles, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
+        """observes [B, T]: problem b's observation sequence in row b."""
+        obs = np.ascontiguousarray(observes, np.float64)
+        if obs.ndim != 2:
+            raise ValueError("observes must be [n_problems, T]")
+        cfg = self.batch_config(model, n_particles, obs.shape[0], resampler, ess_threshold, keep_history, algorithm, flags)
+        self._chk(self.L.cpprob_hip_batch_begin(self.h, C.byref(cfg), obs.ctypes.data_as(C.POINTER(C.c_double)), obs.shape[1]))
+        self.batch_B, self.batch_T, self.batch_n = obs.shape[0], obs.shape[1], int(n_particles)
+        self.batch_K = 3 if model == MODEL_HMM3 else 8
+        return self
+
+    def batch_run(self, seeds):
+        """One launch; problem b runs with Philox key seeds[b]."""
+        sd = np.ascontiguousarray(seeds, np.uint64)
+        if sd.shape != (self.batch_B,):
+            raise ValueError("one seed per problem")
+        self._chk(self.L.cpprob_hip_batch_run(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+    def batch_results(self):
+        """[summary dict] * B, stats [B, T, spp], ess [B, T], resampled [B, T] in one call and one synchronisation."""
+        B, T, K = self.batch_B, self.batch_T, self.batch_K
+        sums = (Summary * B)()
+        stats = np.zeros((B, T, K))
+        ess = np.zeros((B, T))
+        res = np.zeros((B, T), np.int32)
+        self._chk(self.L.cpprob_hip_batch_results(self.h, sums, stats.ctypes.data, stats.size, ess.ctypes.data, res.ctypes.data))
+        return [{f: getattr(s, f) for f, _ in Summary._fields_} for s in sums], stats, ess, res
+
+    def batch_results_device(self, out):
+        """[B, 4 + T spp] = {log_evidence, ess, log_norm, max_logw, stats...} per problem into a device tensor; no host sync."""
+        self._chk(self.L.cpprob_hip_batch_results_device(self.h, _dptr(out), out.numel()))
+
+    def batch_store(self, b):
+        """Problem b's particle store: (values [T, n] int32, ancestors [T, n] int32, final log-weights [n])."""
+        T, n = self.batch_T, self.batch_n
+        vals = np.zeros((T, n), np.int32)
+        anc = np.zeros((T, n), np.int32)
+        logw = np.zeros(n)
+        self._chk(self.L.cpprob_hip_batch_copy_store(self.h, int(b), vals.ctypes.data, anc.ctypes.data, logw.ctypes.data))
+        return vals, anc, logw
 
     # ---- sharded SMC ---------------------------------------------------------------------
     def step_begin(self, t, local_totals, run_index=0):

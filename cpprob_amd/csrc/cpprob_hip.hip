@@ -19,6 +19,7 @@
 #include "bookkeep_fixed.hpp"
 #include "trace_words.hpp"
 #include "device_collectives.hpp"
+#include "batch_smc.hpp"
 
 using namespace cph;
 
@@ -29,6 +30,8 @@ thread_local std::string g_last_error;      // per thread: contexts (and the gro
 struct EventPair { hipEvent_t a, b; int cls; int count; };
 
 }  // namespace
+
+namespace { struct BatchState; }   // cpprob_hip_batch_*: beside the single-run state, which it does not touch
 
 struct cpprob_hip_ctx {
     int device = 0;
@@ -177,6 +180,7 @@ struct cpprob_hip_ctx {
     std::vector<EventPair> ev_used, ev_free;
     double prof_ms[CPPROB_HIP_N_KERNEL_CLASSES] = {0};
     int64_t prof_calls[CPPROB_HIP_N_KERNEL_CLASSES] = {0};
+    BatchState* batch = nullptr;
 };
 
 namespace {
@@ -944,12 +948,106 @@ int dispatch_model(cpprob_hip_ctx* c, F&& f)
     return fail(c, CPPROB_HIP_EINVAL, "unknown model id");
 }
 
+// Per-step tables of the table-weight HMMs from an observation, and the transition thresholds of CPPROB_HIP_MODEL_HMM_TABLE: ONE host
+// statement of each, shared by the single-population begin and the batched begin (their draws and weights must agree bit for bit).
+//   hmm3_step_table  log N(y; state_mean[s], 1) for s = 0..2 (the functor the reference applies per particle, utils_normal_distribution.hpp:20-45),
+//                    e[s] = exp(ll_s - max ll) and max ll
+//   hmmk_step_ll     log N(y; mean[s], 1) for s < k, -inf beyond (8 entries)
+//   hmmk_thresholds  u >= c  <=>  word >= ceil(c 2^32) for the cumulative row weights, as for the three-state model ([k][8], ~0 beyond)
+void hmm3_step_table(double y, const double (&mean)[3], double* ll, double* e, double& mx)
+{
+    for (int s2 = 0; s2 < 3; ++s2) ll[s2] = normal_logpdf(y, mean[s2], 1.0);
+    mx = std::max(ll[0], std::max(ll[1], ll[2]));
+    for (int s2 = 0; s2 < 3; ++s2) e[s2] = std::exp(ll[s2] - mx);
+}
+void hmmk_step_ll(double y, const std::vector<double>& mean, int k, double* ll)
+{
+    for (int s2 = 0; s2 < 8; ++s2) ll[s2] = s2 < k ? normal_logpdf(y, mean[(size_t)s2], 1.0) : -INFINITY;
+}
+std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
+{
+    std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
+    for (int s2 = 0; s2 < k; ++s2) {
+        double tot = 0.0, acc = 0.0;
+        for (int j = 0; j < k; ++j) tot += trans[(size_t)s2 * k + j];
+        for (int j = 0; j + 1 < k; ++j) { acc += trans[(size_t)s2 * k + j]; thr[(size_t)s2 * 8 + j] = (uint64_t)std::ceil((acc / tot) * 4294967296.0); }
+    }
+    return thr;
+}
+
 void free_run_buffers(cpprob_hip_ctx* c)
 {
     dfree(c->d_obs); dfree(c->d_logw[0]); dfree(c->d_logw[1]); dfree(c->d_wrel[0]); dfree(c->d_wrel[1]); dfree(c->d_bf); dfree(c->d_ll_tab); dfree(c->d_values); dfree(c->d_anc); dfree(c->d_paths);
     dfree(c->d_part[0]); dfree(c->d_part[1]); dfree(c->d_e_tab); dfree(c->d_gpart); dfree(c->d_stile); dfree(c->d_gstat); dfree(c->d_bc); dfree(c->d_ess); dfree(c->d_resampled); dfree(c->d_stats_part); dfree(c->d_stats);
     dfree(c->d_cdf); dfree(c->d_anc_pre); dfree(c->d_strata); dfree(c->d_strata_top); dfree(c->d_lz_trace); dfree(c->d_obound); dfree(c->d_hier); dfree(c->d_annex_base); dfree(c->d_fpart); dfree(c->d_filter_w); dfree(c->d_skip); dfree(c->d_q[0]); dfree(c->d_q[1]); dfree(c->d_trace_cnt); dfree(c->d_trace_arrive); dfree(c->d_fold); dfree(c->d_tr[0]); dfree(c->d_tr[1]);
     c->cap_particles = 0; c->cap_T = 0; c->annex_cap = 0; c->tr_cap = 0;
+}
+
+// ---- batched SMC (cpprob_hip_batch_*, csrc/batch_smc.hpp) -------------------------------------------------------------------------
+// Device workspace of a batch: regions side by side, each starting on a 256-byte boundary (cpprob_hip_batch_workspace_bytes states the sum).
+struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, values, anc, total; };
+size_t batch_round(size_t x) { return (x + 255) / 256 * 256; }
+BatchLayout batch_layout(uint64_t B, uint64_t T, uint64_t n, int spp, bool keep)
+{
+    BatchLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += batch_round(bytes); return at; };
+    L.tab = take(B * T * kBatchTab * sizeof(double));
+    L.seeds = take(B * sizeof(uint64_t));
+    L.thr = take(8 * 8 * sizeof(uint64_t));
+    L.ctrl = take(B * kBatchCtrlBytes);
+    L.stats = take(B * T * (uint64_t)spp * sizeof(double));
+    L.ess = take(B * T * sizeof(double));
+    L.res = take(B * T * sizeof(int32_t));
+    L.nreq = take(B * sizeof(int32_t));
+    L.values = take(keep ? B * T * n : 0);
+    L.anc = take(keep ? B * T * n * sizeof(int32_t) : 0);
+    L.total = o;
+    return L;
+}
+
+struct BatchState {
+    cpprob_hip_batch_config cfg{};
+    bool begun = false, ran = false;
+    int T = 0, K = 0, hk = 0;
+    BatchLayout lay{};
+    std::vector<double> h_tab;                 // [B][T][kBatchTab]: the per-step tables the kernel reads (also the final log-weights' source)
+    std::vector<uint64_t> h_thr;               // HMM_TABLE: the rows' thresholds at begin
+    char* d_ws = nullptr; size_t cap = 0;
+    ModelParams mp{};
+};
+
+void batch_free(cpprob_hip_ctx* c)
+{
+    if (!c->batch) return;
+    dfree(c->batch->d_ws);
+    delete c->batch;
+    c->batch = nullptr;
+}
+
+// What a configuration and T admit, without a device: 0, or the error code with its message.
+int batch_check(const cpprob_hip_batch_config* cfg, size_t T, std::string& msg)
+{
+    if (!cfg) { msg = "NULL argument"; return CPPROB_HIP_EINVAL; }
+    if (cfg->algorithm == CPPROB_HIP_ALG_SIS) { msg = "batched runs are SMC only: SIS runs on the single-population path (cpprob_hip_infer_begin / _run)"; return CPPROB_HIP_EUNSUPPORTED; }
+    if (cfg->algorithm != CPPROB_HIP_ALG_SMC) { msg = "unknown algorithm"; return CPPROB_HIP_EINVAL; }
+    if (cfg->model < 0 || cfg->model > CPPROB_HIP_MODEL_HMM_TABLE) { msg = "unknown model id"; return CPPROB_HIP_EINVAL; }
+    if (cfg->model != CPPROB_HIP_MODEL_HMM3 && cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) {
+        msg = "batched runs hold the table-weight HMMs (CPPROB_HIP_MODEL_HMM3, CPPROB_HIP_MODEL_HMM_TABLE): run this model one problem at a time on the "
+              "single-population path (cpprob_hip_infer_begin / _run)";
+        return CPPROB_HIP_EUNSUPPORTED;
+    }
+    if (cfg->resampler == CPPROB_HIP_RESAMPLE_MULTINOMIAL) { msg = "batched runs resample systematically or stratified: multinomial resampling runs on the single-population path (cpprob_hip_infer_begin / _run)"; return CPPROB_HIP_EUNSUPPORTED; }
+    if (cfg->resampler != CPPROB_HIP_RESAMPLE_SYSTEMATIC && cfg->resampler != CPPROB_HIP_RESAMPLE_STRATIFIED) { msg = "unknown resampler"; return CPPROB_HIP_EINVAL; }
+    if (!(cfg->ess_threshold > 1.0)) { msg = "batched runs resample after every step (ess_threshold > 1): ESS-triggered schedules run on the single-population path (cpprob_hip_infer_begin / _run)"; return CPPROB_HIP_EUNSUPPORTED; }
+    if (cfg->keep_history != 0 && cfg->keep_history != 1) { msg = "keep_history must be 0 or 1"; return CPPROB_HIP_EINVAL; }
+    if (cfg->flags != 0) { msg = "flags are reserved and must be 0"; return CPPROB_HIP_EINVAL; }
+    if (cfg->n_particles == 0 || cfg->n_particles > (uint64_t)kBatchMaxN) { msg = "n_particles per problem must lie in 1 .. " + std::to_string(kBatchMaxN); return CPPROB_HIP_EINVAL; }
+    if (cfg->n_problems == 0 || cfg->n_problems > (uint64_t)INT32_MAX) { msg = "n_problems must lie in 1 .. 2^31 - 1"; return CPPROB_HIP_EINVAL; }
+    if (T == 0 || T > (size_t)INT32_MAX) { msg = "every problem needs 1 .. 2^31 - 1 observes"; return CPPROB_HIP_EINVAL; }
+    const long double est = (long double)cfg->n_problems * (long double)T * (64.0L + 8 * 8 + 12 + (cfg->keep_history ? 5.0L * cfg->n_particles : 0.0L));
+    if (est > 1e18L) { msg = "the batch's workspace does not fit 64-bit sizes"; return CPPROB_HIP_EINVAL; }
+    return 0;
 }
 
 }  // namespace
@@ -1004,6 +1102,7 @@ void cpprob_hip_destroy(cpprob_hip_ctx* c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     free_run_buffers(c);
+    batch_free(c);
     dfree(c->d_ctrl); dfree(c->d_local_totals); dfree(c->d_cut_tab); dfree(c->d_cut_head); dfree(c->d_cut_srccnt);
     dfree(c->d_send_src); dfree(c->d_hk_thr); dfree(c->d_hk_ll); dfree(c->d_hier_table); dfree(c->d_wpart); dfree(c->d_xplan); dfree(c->d_shard_begin); dfree(c->d_slot_of_rank); dfree(c->d_xsend); dfree(c->d_xrecv); dfree(c->d_peer_recv); dfree(c->d_peer_slot); dfree(c->d_sent); dfree(c->d_origin); dfree(c->d_remote); dfree(c->d_annex_all);
     if (c->h_obound) { (void)hipHostFree(c->h_obound); c->h_obound = nullptr; }
@@ -1266,21 +1365,13 @@ int cpprob_hip_infer_begin(cpprob_hip_ctx* c, const cpprob_hip_config* cfg, cons
     if (cfg->model == CPPROB_HIP_MODEL_HMM3) {
         // log N(y_t; state_mean[s], 1): three values per step, computed once with the same functor
         // the reference applies per particle (utils_normal_distribution.hpp:20-45)
-        std::vector<double> tab((size_t)c->T * 3);
-        for (int t = 0; t < c->T; ++t)
-            for (int s2 = 0; s2 < 3; ++s2) tab[(size_t)t * 3 + s2] = normal_logpdf(h_obs[t], c->mp.hmm_mean[s2], 1.0);
+        // (and the linear weights of the three values against their maximum: exp(ll - max), and the max itself)
+        std::vector<double> tab((size_t)c->T * 3), et((size_t)c->T * 4);
+        for (int t = 0; t < c->T; ++t) hmm3_step_table(h_obs[t], c->mp.hmm_mean, &tab[(size_t)t * 3], &et[(size_t)t * 4], et[(size_t)t * 4 + 3]);
         c->h_ll_tab = tab;
         HIP_TRY(c, hipMalloc(&c->d_ll_tab, tab.size() * sizeof(double)));
         HIP_TRY(c, hipMemcpy(c->d_ll_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
         c->mp.ll_tab = c->d_ll_tab;
-        // linear weights of the three values against their maximum: exp(ll - max), and the max itself
-        std::vector<double> et((size_t)c->T * 4);
-        for (int t = 0; t < c->T; ++t) {
-            const double* l = &tab[(size_t)t * 3];
-            const double mx = std::max(l[0], std::max(l[1], l[2]));
-            for (int s2 = 0; s2 < 3; ++s2) et[(size_t)t * 4 + s2] = std::exp(l[s2] - mx);
-            et[(size_t)t * 4 + 3] = mx;
-        }
         c->h_e_tab = et;
         dfree(c->d_e_tab);
         HIP_TRY(c, hipMalloc(&c->d_e_tab, et.size() * sizeof(double)));
@@ -1292,15 +1383,9 @@ int cpprob_hip_infer_begin(cpprob_hip_ctx* c, const cpprob_hip_config* cfg, cons
         // thresholds of the rows' inverse CDFs (u >= c  <=>  word >= ceil(c 2^32), as for the three-state model) and the
         // emission log-densities of every step
         const int k = c->hk;
-        std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
-        for (int s2 = 0; s2 < k; ++s2) {
-            double tot = 0.0, acc = 0.0;
-            for (int j = 0; j < k; ++j) tot += c->hk_trans[(size_t)s2 * k + j];
-            for (int j = 0; j + 1 < k; ++j) { acc += c->hk_trans[(size_t)s2 * k + j]; thr[(size_t)s2 * 8 + j] = (uint64_t)std::ceil((acc / tot) * 4294967296.0); }
-        }
-        std::vector<double> ll((size_t)c->T * 8, -INFINITY);
-        for (int t = 0; t < c->T; ++t)
-            for (int s2 = 0; s2 < k; ++s2) ll[(size_t)t * 8 + s2] = normal_logpdf(h_obs[t], c->hk_mean[(size_t)s2], 1.0);
+        const std::vector<uint64_t> thr = hmmk_thresholds(c->hk_trans, k);
+        std::vector<double> ll((size_t)c->T * 8);
+        for (int t = 0; t < c->T; ++t) hmmk_step_ll(h_obs[t], c->hk_mean, k, &ll[(size_t)t * 8]);
         dfree(c->d_hk_thr); dfree(c->d_hk_ll);
         HIP_TRY(c, hipMalloc(&c->d_hk_thr, thr.size() * sizeof(uint64_t)));
         HIP_TRY(c, hipMalloc(&c->d_hk_ll, ll.size() * sizeof(double)));
@@ -3313,6 +3398,171 @@ int cpprob_hip_profile_read(cpprob_hip_ctx* c, double* h_ms, int64_t* h_calls, i
     return 0;
 }
 
+
+// ---- batched SMC -----------------------------------------------------------------------------------------------------------------
+int cpprob_hip_batch_workspace_bytes(const cpprob_hip_batch_config* cfg, size_t T, uint64_t* out_bytes)
+{
+    std::string msg;
+    if (int rc = batch_check(cfg, T, msg)) return fail(nullptr, rc, msg);
+    if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
+    const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
+    *out_bytes = batch_layout(cfg->n_problems, T, cfg->n_particles, spp, cfg->keep_history == 1).total;
+    return 0;
+}
+
+int cpprob_hip_batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const double* h_obs, size_t T)
+{
+    if (!c || !cfg || !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    std::string msg;
+    if (int rc = batch_check(cfg, T, msg)) return fail(c, rc, msg);
+    if (cfg->model == CPPROB_HIP_MODEL_HMM_TABLE && c->hk < 2) return fail(c, CPPROB_HIP_ESTATE, "CPPROB_HIP_MODEL_HMM_TABLE: call cpprob_hip_set_hmm first");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->batch) c->batch = new BatchState();
+    BatchState* bs = c->batch;
+    bs->begun = false; bs->ran = false;
+    const uint64_t B = cfg->n_problems;
+    const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3;
+    const int spp = hmm3 ? 3 : 8;
+    host_model_params(bs->mp, cfg->model);
+    // the per-step tables of every problem, with the single path's own host expressions (cpprob_hip_infer_begin)
+    bs->h_tab.assign((size_t)B * T * kBatchTab, 0.0);
+    bs->h_thr.assign(64, ~0ull);
+    const int k = hmm3 ? 3 : c->hk;
+    for (uint64_t b = 0; b < B; ++b)
+        for (size_t t = 0; t < T; ++t) {
+            const double y = h_obs[b * T + t];
+            double* row = &bs->h_tab[(b * T + t) * kBatchTab];
+            if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
+            else hmmk_step_ll(y, c->hk_mean, k, row);
+        }
+    if (!hmm3) {
+        const std::vector<uint64_t> thr = hmmk_thresholds(c->hk_trans, k);
+        std::copy(thr.begin(), thr.end(), bs->h_thr.begin());
+    }
+    bs->lay = batch_layout(B, T, cfg->n_particles, spp, cfg->keep_history == 1);
+    if (bs->lay.total > bs->cap) {
+        // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
+        dfree(bs->d_ws); bs->cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_ws, bs->lay.total));
+        bs->cap = bs->lay.total;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bs->mp.hk = hmm3 ? 0 : k;
+    bs->mp.hk_thr = hmm3 ? nullptr : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+    bs->cfg = *cfg; bs->T = (int)T; bs->K = spp; bs->hk = k;
+    bs->begun = true;
+    return 0;
+}
+
+int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
+{
+    if (!c || !h_seeds) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint64_t B = bs->cfg.n_problems;
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    const bool keep = bs->cfg.keep_history == 1;
+    BatchArgs a{};
+    a.mp = bs->mp;
+    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
+    a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
+    a.values = keep ? reinterpret_cast<int8_t*>(bs->d_ws + bs->lay.values) : nullptr;
+    a.anc = keep ? reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.anc) : nullptr;
+    a.ctrl = bs->d_ws + bs->lay.ctrl;
+    a.stats = reinterpret_cast<double*>(bs->d_ws + bs->lay.stats);
+    a.ess = reinterpret_cast<double*>(bs->d_ws + bs->lay.ess);
+    a.resampled = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.res);
+    a.n_requant = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.nreq);
+    a.T = bs->T; a.n = (int)bs->cfg.n_particles; a.spp = bs->K; a.ess_frac = bs->cfg.ess_threshold;
+    const size_t lds = (size_t)batch_lds_bytes(a.n);
+    const bool strat = bs->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), lds, c->stream, a); };
+    if (bs->cfg.model == CPPROB_HIP_MODEL_HMM3) {
+        if (strat) { if (keep) go(batch_smc_kernel<ModelHmm3, kFixStratified, true>); else go(batch_smc_kernel<ModelHmm3, kFixStratified, false>); }
+        else { if (keep) go(batch_smc_kernel<ModelHmm3, kFixSystematic, true>); else go(batch_smc_kernel<ModelHmm3, kFixSystematic, false>); }
+    } else {
+        if (strat) { if (keep) go(batch_smc_kernel<ModelHmmK, kFixStratified, true>); else go(batch_smc_kernel<ModelHmmK, kFixStratified, false>); }
+        else { if (keep) go(batch_smc_kernel<ModelHmmK, kFixSystematic, true>); else go(batch_smc_kernel<ModelHmmK, kFixSystematic, false>); }
+    }
+    HIP_TRY(c, hipGetLastError());
+    bs->ran = true;
+    return 0;
+}
+
+int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, double* h_stats, size_t n_doubles, double* h_ess, int32_t* h_resampled)
+{
+    if (!c || !h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, T = (size_t)bs->T, need = B * T * (size_t)bs->K;
+    if (h_stats && n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "h_stats too small");
+    std::vector<char> ctrl(B * kBatchCtrlBytes);
+    std::vector<int32_t> nreq(B);
+    HIP_TRY(c, hipMemcpyAsync(ctrl.data(), bs->d_ws + bs->lay.ctrl, ctrl.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(nreq.data(), bs->d_ws + bs->lay.nreq, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (h_stats) HIP_TRY(c, hipMemcpyAsync(h_stats, bs->d_ws + bs->lay.stats, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_ess) HIP_TRY(c, hipMemcpyAsync(h_ess, bs->d_ws + bs->lay.ess, B * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_resampled) HIP_TRY(c, hipMemcpyAsync(h_resampled, bs->d_ws + bs->lay.res, B * T * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
+    for (size_t b = 0; b < B; ++b) {
+        StepCtrl h;
+        std::memcpy(&h, ctrl.data() + b * kBatchCtrlBytes, sizeof h);
+        cpprob_hip_summary* o = h_out + b;
+        o->log_evidence = h.log_z;
+        o->ess_final = h.ess;
+        o->log_norm = h.M + std::log(h.W);
+        o->max_logw = h.M;
+        o->n_predict = bs->T;
+        o->stats_per_predict = bs->K;
+        o->is_int = 1;
+        o->n_resampled = h.n_resampled;
+        o->step_form = hmm3 ? CPPROB_HIP_FORM_COUNTS : CPPROB_HIP_FORM_FIXED;
+        o->n_requantised = hmm3 ? 0 : nreq[b];
+    }
+    return 0;
+}
+
+int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_doubles)
+{
+    if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    const int64_t B = (int64_t)bs->cfg.n_problems, per = (int64_t)bs->T * bs->K;
+    if (n_doubles < (size_t)(B * (4 + per))) return fail(c, CPPROB_HIP_EINVAL, "d_out too small: n_problems * (4 + n_predict * stats_per_predict) doubles");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t total = B * (4 + per);
+    hipLaunchKernelGGL(batch_pack_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
+                       (const char*)(bs->d_ws + bs->lay.ctrl), (const double*)(bs->d_ws + bs->lay.stats), (int)per, B, d_out);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_values, int32_t* h_anc, double* h_logw)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->cfg.keep_history != 1) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t T = (size_t)bs->T, n = bs->cfg.n_particles;
+    std::vector<int8_t> v(T * n);
+    HIP_TRY(c, hipMemcpyAsync(v.data(), bs->d_ws + bs->lay.values + problem * T * n, T * n, hipMemcpyDeviceToHost, c->stream));
+    if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->d_ws + bs->lay.anc + problem * T * n * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (h_values) for (size_t i = 0; i < T * n; ++i) h_values[i] = v[i];
+    if (h_logw) {
+        // the final weights are table values: ll of the last step at the particle's state (what cpprob_hip_copy_logw returns)
+        const double* row = &bs->h_tab[((size_t)problem * T + (T - 1)) * kBatchTab];
+        for (size_t i = 0; i < n; ++i) h_logw[i] = row[(int)v[(T - 1) * n + i]];
+    }
+    return 0;
+}
 }  // extern "C"
 
 #include "group.hpp"

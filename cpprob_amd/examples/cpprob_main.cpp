@@ -10,12 +10,17 @@
 //                                                  equal entries, e.g. 0,0,0: every rank on that GPU)
 //                   --filtering_only (smc, built-in models: O(N) particle store, filtering statistics, no posterior files)
 //                   --no_dump  --json (print the in-memory result as one JSON line)
+//                   --batch_observes_file F (smc, built-in HMMs: one observation sequence a line, all in one batched launch; seeds --seed + line
+//                   index; one estimate a line, one JSON object a line under --json)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <array>
+#include <cstdint>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 #include <string>
 #include <tuple>
+#include <vector>
 
 #include "cpprob/cpprob.hpp"
 #include "cpprob/postprocess/stats_printer.hpp"
@@ -25,7 +30,7 @@
 namespace {
 
 struct Args {
-    std::string model, model_folder = ".", observes, observes_file, generated_file = "post";
+    std::string model, model_folder = ".", observes, observes_file, generated_file = "post", batch_observes_file;
     bool sis = false, smc = false, estimate = false, json = false;
     int repeat = 1;
     std::size_t n_samples = 10000;            // src/main.cpp:166
@@ -71,9 +76,40 @@ void print_json(const cpprob::gpu::Result& r)
     std::cout << "}" << std::endl;
 }
 
+// --batch_observes_file F: one observation sequence a line, all run as ONE batch (cpprob::gpu::inference_batch, smc, built-in HMMs);
+// problem i (line i) runs with seed --seed + i; one estimate a line: log-evidence, then P(x_t = s) row by row (--json: one JSON object a line)
+template <class F>
+int execute_batch(const F& model, const Args& a)
+{
+    if (!a.smc) { std::cerr << "--batch_observes_file runs SMC: set --smc" << std::endl; return EXIT_FAILURE; }
+    std::ifstream in(a.model_folder + "/" + a.batch_observes_file);
+    if (!in) { std::cerr << "cannot open " << a.model_folder << "/" << a.batch_observes_file << std::endl; return EXIT_FAILURE; }
+    std::vector<cpprob::tuple_observes_t<F>> observes;
+    std::vector<std::uint64_t> seeds;
+    std::string line;
+    while (std::getline(in, line)) {
+        cpprob::tuple_observes_t<F> o;
+        if (!cpprob::parse_string(line, o)) { std::cerr << "Could not parse the observations of line " << observes.size() << "." << std::endl; return EXIT_FAILURE; }
+        seeds.push_back(cpprob::gpu::options().seed + observes.size());
+        observes.push_back(o);
+    }
+    const std::vector<cpprob::gpu::Result> res = cpprob::gpu::inference_batch(cpprob::StateType::smc, model, observes, a.n_samples, seeds);
+    std::cout.precision(17);
+    for (const cpprob::gpu::Result& r : res) {
+        if (a.json) { print_json(r); continue; }
+        std::cout << r.log_evidence;
+        for (const auto& p : r.predicts)
+            for (double v : p.probabilities) std::cout << " " << v;
+        std::cout << std::endl;
+    }
+    cpprob::gpu::release_device_resources();
+    return EXIT_SUCCESS;
+}
+
 template <class F>
 int execute(const F& model, const Args& a)
 {
+    if (!a.batch_observes_file.empty()) return execute_batch(model, a);
     if (a.observes_file.empty() == a.observes.empty()) {
         std::cerr << R"(In SIS or SMC mode exactly one of the options "--observes" or "--observes_file" has to be set)" << std::endl;   // main.cpp:72-75
         return EXIT_FAILURE;
@@ -120,6 +156,7 @@ int main(int argc, char** argv)
         else if (f == "--n_samples" || f == "-n") a.n_samples = std::stoull(next());
         else if (f == "--observes" || f == "-o") a.observes = next();
         else if (f == "--observes_file") a.observes_file = next();
+        else if (f == "--batch_observes_file") a.batch_observes_file = next();   // one problem a line, one batched launch (built-in HMMs, smc)
         else if (f == "--generated_file") a.generated_file = next();
         else if (f == "--seed") opt.seed = std::stoull(next());
         else if (f == "--ess_threshold") opt.ess_threshold = std::stod(next());

@@ -35,7 +35,7 @@
 // The statements are part of the model's kernel, not functions it calls: the launch's mode reaches them as compile-time facts of the
 // kernel they are inlined into (cpprob/gpu.hpp: __builtin_assume), their counters live in its registers, and the step's observe ends
 // its wavefront.  Whatever the optimisation level says about inlining (at -O3 hipcc left them as calls), they are inlined.
-#define CPPROB_STATEMENT __attribute__((always_inline))
+#define CPPROB_STATEMENT inline __attribute__((always_inline))
 
 namespace cpprob {
 

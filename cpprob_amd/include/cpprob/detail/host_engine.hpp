@@ -493,6 +493,18 @@ int probe_markov_window(const Func& f, const ObsTuple& obs, const detail::TraceS
     return -1;
 }
 
+// ---- structural dry run on the host (one trace): statement counts, predict types and addresses -------------------------------
+template <class Func, class ObsTuple>
+void dry_run(StateType algorithm, const Func& f, const ObsTuple& obs, detail::TraceStructure& st)
+{
+    const StateType saved = algorithm;
+    State::set(StateType::dryrun);
+    detail::recorder() = &st;
+    try { call_f_tuple(f, obs); } catch (...) { detail::recorder() = nullptr; State::set(saved); throw; }
+    detail::recorder() = nullptr;
+    State::set(saved);
+}
+
 // ---- the body of cpprob::inference -------------------------------------------------------------------
 template <class Func, class... Args>
 void run_inference(StateType algorithm, const Func& f, const std::tuple<Args...>& observes, std::size_t n, const std::string& file)
@@ -503,14 +515,7 @@ void run_inference(StateType algorithm, const Func& f, const std::tuple<Args...>
 
     // structural dry run on the host (one trace): statement counts, predict types and addresses
     detail::TraceStructure st;
-    {
-        const StateType saved = algorithm;
-        State::set(StateType::dryrun);
-        detail::recorder() = &st;
-        try { call_f_tuple(f, obs); } catch (...) { detail::recorder() = nullptr; State::set(saved); throw; }
-        detail::recorder() = nullptr;
-        State::set(saved);
-    }
+    dry_run(algorithm, f, obs, st);
     if (st.n_observe == 0) throw std::runtime_error("cpprob::inference: the model executes no observe statement");
     if (algorithm == StateType::smc && options().markov_probe) {
         st.window = probe_markov_window(f, obs, st);
@@ -549,6 +554,72 @@ void run_inference(StateType algorithm, const Func& f, const std::tuple<Args...>
     else if (e->generic) e->generic(algorithm, &obs, n, st, opt, res, store);
     else throw std::runtime_error("cpprob::inference: registry entry without a launcher");
     if (opt.dump) dump_posterior(file, st, hs, opt.dump_max_particles);      // finish_trace() x n + finish_infer()
+}
+
+// ---- many problems of one model in ONE launch (cpprob_hip_batch_*): models bound by CPPROB_REGISTER_BUILTIN to the table-weight HMMs ----
+// observes[b] is problem b's observes tuple (all of one length), seeds[b] its Philox key: result b is what cpprob::inference with
+// options().seed = seeds[b] computes (no posterior files).  Resampler, keep_history (false: filtering statistics), ess_threshold (must
+// be > 1: every step) and device come from options(), as for cpprob::inference.
+template <class Func, class... Args>
+std::vector<Result> inference_batch(StateType algorithm, const Func& f, const std::vector<std::tuple<Args...>>& observes, std::size_t n,
+                                    const std::vector<std::uint64_t>& seeds)
+{
+    using ObsTuple = tuple_observes_t<Func>;
+    static_assert(std::tuple_size<ObsTuple>::value == sizeof...(Args), "the observes tuple must have one element per model argument");
+    if (algorithm != StateType::smc)
+        throw std::runtime_error("cpprob::gpu::inference_batch: batched runs are StateType::smc only -- run SIS with cpprob::inference");
+    if (observes.empty()) throw std::runtime_error("cpprob::gpu::inference_batch: no problems");
+    if (seeds.size() != observes.size()) throw std::runtime_error("cpprob::gpu::inference_batch: one seed per problem");
+    const ObsTuple obs0(observes[0]);
+    detail::TraceStructure st;
+    dry_run(algorithm, f, obs0, st);
+    const Key key = key_of(f, std::integral_constant<bool, detail::fn_traits<std::remove_cv_t<std::remove_reference_t<Func>>>::is_function>{});
+    const Entry* e = find_entry(key);
+    if (!e || (e->builtin_model != CPPROB_HIP_MODEL_HMM3 && e->builtin_model != CPPROB_HIP_MODEL_HMM_TABLE))
+        throw std::runtime_error("cpprob::gpu::inference_batch: batched runs need a model bound by CPPROB_REGISTER_BUILTIN to CPPROB_HIP_MODEL_HMM3 or "
+                                 "CPPROB_HIP_MODEL_HMM_TABLE -- run this model one problem at a time with cpprob::inference");
+    std::vector<double> flat;
+    std::size_t T = 0;
+    for (std::size_t b = 0; b < observes.size(); ++b) {
+        const std::vector<double> o = flatten(ObsTuple(observes[b]));
+        if (b == 0) T = o.size();
+        else if (o.size() != T) throw std::runtime_error("cpprob::gpu::inference_batch: every problem needs the same number of observes");
+        flat.insert(flat.end(), o.begin(), o.end());
+    }
+    if (st.int_ids.size() != T) throw std::runtime_error("built-in model kernel and the model function disagree on the number of predict statements");
+    const Options& opt = options();
+    ContextLease lease(opt.device);
+    Context& ctx = *lease;
+    cpprob_hip_batch_config bc{};
+    bc.algorithm = CPPROB_HIP_ALG_SMC;
+    bc.model = e->builtin_model;
+    bc.resampler = opt.resampler;
+    bc.keep_history = opt.keep_history ? 1 : 0;
+    bc.flags = 0;
+    bc.ess_threshold = opt.ess_threshold;
+    bc.n_particles = n;
+    bc.n_problems = observes.size();
+    const std::size_t B = observes.size();
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx.check(cpprob_hip_batch_begin(ctx.get(), &bc, flat.data(), T), "cpprob_hip_batch_begin");
+    ctx.check(cpprob_hip_batch_run(ctx.get(), seeds.data()), "cpprob_hip_batch_run");
+    std::vector<cpprob_hip_summary> sums(B);
+    const std::size_t K = e->builtin_model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
+    std::vector<double> stats(B * T * K), ess(B * T);
+    ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    lease.done();
+    std::vector<Result> out(B);
+    for (std::size_t b = 0; b < B; ++b) {
+        Result& r = out[b];
+        const cpprob_hip_summary& s = sums[b];
+        r.n_particles = n; r.log_evidence = s.log_evidence; r.ess = s.ess_final; r.log_norm = s.log_norm; r.n_resampled = s.n_resampled;
+        r.used_builtin = true; r.step_form = s.step_form; r.run_seconds = seconds;
+        fill_predict_names(r, st);
+        for (std::size_t t = 0; t < T; ++t) r.predicts[t].probabilities.assign(stats.begin() + (b * T + t) * K, stats.begin() + (b * T + t + 1) * K);
+        r.step_ess.assign(ess.begin() + b * T, ess.begin() + (b + 1) * T);
+    }
+    return out;
 }
 
 }  // namespace gpu

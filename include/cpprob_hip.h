@@ -222,6 +222,45 @@ int cpprob_hip_copy_ancestors(cpprob_hip_ctx* ctx, int32_t* h_anc, size_t n_byte
 int cpprob_hip_copy_logw(cpprob_hip_ctx* ctx, double* h_logw, size_t n_bytes);
 int cpprob_hip_copy_paths(cpprob_hip_ctx* ctx, void* h_paths, size_t n_bytes);
 
+/* ---- many small problems in one launch (batched SMC) ---------------------------------------------------------------------
+ * B independent problems of one table-weight HMM, each with its own observation sequence (all of length T), seed and results, run
+ * as ONE launch: one workgroup per problem holds its whole population in LDS and runs every step and the read-out.  Problem b
+ * computes what a one-context SMC run begun with seed h_seeds[b] (particle_offset 0, run_index 0) computes: the same states and
+ * ancestors, the same evidence, ESS and resampling flags, and the same statistics up to the last bits of the final division.
+ * Supported: algorithm SMC, model HMM3 (prefix counts) or HMM_TABLE (fixed-point weights; the table of cpprob_hip_set_hmm at
+ * batch_begin, shared by the batch), systematic or stratified resampling after every step (ess_threshold > 1), 1 <= n <= 8192
+ * particles per problem, any T >= 1 and B >= 1.  Everything else returns CPPROB_HIP_EUNSUPPORTED (multinomial resampling,
+ * ESS-triggered schedules, SIS, the Gaussian models) and runs on the single-population path.  The batch state lives beside a
+ * context's single-run state: infer_* runs and batch runs may interleave on one context and keep their own results. */
+typedef struct cpprob_hip_batch_config {
+    int32_t algorithm;      /* must be CPPROB_HIP_ALG_SMC                                                           */
+    int32_t model;          /* CPPROB_HIP_MODEL_HMM3 | CPPROB_HIP_MODEL_HMM_TABLE                                   */
+    int32_t resampler;      /* CPPROB_HIP_RESAMPLE_SYSTEMATIC | CPPROB_HIP_RESAMPLE_STRATIFIED                      */
+    int32_t keep_history;   /* 1: smoothed statistics + a per-problem particle store; 0: filtering statistics, O(B n) */
+    uint32_t flags;         /* must be 0 (reserved)                                                                 */
+    double ess_threshold;   /* must be > 1 (every-step schedule)                                                    */
+    uint64_t n_particles;   /* per problem, 1 .. 8192                                                               */
+    uint64_t n_problems;    /* B                                                                                    */
+} cpprob_hip_batch_config;
+/* Pure host function (no device, no context): validates cfg and T and returns the device bytes a batch needs.  The workspace is ten
+ * regions, each rounded up to a multiple of 256 bytes: 64 B T (per-step tables), 8 B (seeds), 512 (transition rows), 256 B (control
+ * blocks), 8 B T spp (statistics), 8 B T (ESS), 4 B T (resampling flags), 4 B (requantised generations), and with keep_history = 1
+ * B T n (states) and 4 B T n (ancestors); spp = 3 (HMM3) or 8 (HMM_TABLE).  A context's workspace grows to the largest batch begun. */
+int cpprob_hip_batch_workspace_bytes(const cpprob_hip_batch_config* cfg, size_t T, uint64_t* out_bytes);
+/* h_observes[B][T].  Validates, sizes the workspace, evaluates the per-step tables and uploads them (synchronising). */
+int cpprob_hip_batch_begin(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const double* h_observes, size_t T);
+/* One launch, asynchronous: problem b runs with Philox key h_seeds[b] (explicit per problem: neighbours never share streams). */
+int cpprob_hip_batch_run(cpprob_hip_ctx* ctx, const uint64_t* h_seeds);
+/* h_out[B] (filled as a one-problem run fills its summary), h_stats[B][T][spp] (n_doubles its capacity), h_ess[B][T] and
+ * h_resampled[B][T]; the last three may be NULL.  Synchronises. */
+int cpprob_hip_batch_results(cpprob_hip_ctx* ctx, cpprob_hip_summary* h_out, double* h_stats, size_t n_doubles, double* h_ess, int32_t* h_resampled);
+/* The same left on the device, stream-ordered, no host synchronisation: d_out[B][4 + T spp] = {log_evidence, ess_final, log_norm,
+ * max_logw, stats...} per problem, cpprob_hip_infer_results_device's layout. */
+int cpprob_hip_batch_results_device(cpprob_hip_ctx* ctx, double* d_out, size_t n_doubles);
+/* Problem `problem`'s particle store: h_values[T][n], h_anc[T][n] (cpprob_hip_copy_values / _ancestors' layout) and the final
+ * log-weights h_logw[n]; any may be NULL.  keep_history = 1 only (else CPPROB_HIP_ESTATE).  Synchronises. */
+int cpprob_hip_batch_copy_store(cpprob_hip_ctx* ctx, uint64_t problem, int32_t* h_values, int32_t* h_anc, double* h_logw);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
