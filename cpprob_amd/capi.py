@@ -34,7 +34,7 @@ SYMBOLS = [
     "cpprob_hip_weighted_moments", "cpprob_hip_weighted_hist", "cpprob_hip_weighted_moments_columns", "cpprob_hip_weighted_hist_columns", "cpprob_hip_resample", "cpprob_hip_smc_bookkeep", "cpprob_hip_smc_bookkeep_fixed", "cpprob_hip_smc_bookkeep_fixed_rs", "cpprob_hip_generic_begin", "cpprob_hip_generic_begin_tiles", "cpprob_hip_generic_quantize", "cpprob_hip_generic_max", "cpprob_hip_generic_quantize_ref", "cpprob_hip_generic_totals", "cpprob_hip_generic_finish", "cpprob_hip_systematic_offset", "cpprob_hip_lineage_gather", "cpprob_hip_lineage_prepare", "cpprob_hip_readback_with_next_result", "cpprob_hip_lineage_moments", "cpprob_hip_lineage_hist", "cpprob_hip_gather_f64",
     "cpprob_hip_gather_i32", "cpprob_hip_profile_enable", "cpprob_hip_profile_read", "cpprob_hip_fastmath",
     "cpprob_hip_batch_workspace_bytes", "cpprob_hip_batch_begin", "cpprob_hip_batch_run", "cpprob_hip_batch_results", "cpprob_hip_batch_results_device",
-    "cpprob_hip_batch_copy_store",
+    "cpprob_hip_batch_copy_store", "cpprob_hip_batch_problems_workspace_bytes", "cpprob_hip_batch_begin_problems",
 ]
 
 
@@ -75,6 +75,34 @@ def batch_workspace_bytes(model, n_particles, n_problems, T, resampler=RESAMPLE_
     cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), int(n_particles), int(n_problems))
     out = C.c_uint64()
     rc = L.cpprob_hip_batch_workspace_bytes(C.byref(cfg), int(T), C.byref(out))
+    if rc:
+        msg = L.cpprob_hip_last_error(None)
+        e = CpprobHipError("cpprob_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+        e.code = rc
+        raise e
+    return out.value
+
+
+def _problem_shapes(T, n_particles):
+    """(h_T uint32 [B], h_n uint32 [B]) of a batch of problems; n_particles an int (every problem's) or one value a problem."""
+    h_T = np.ascontiguousarray(T, np.uint32).reshape(-1)
+    h_n = np.ascontiguousarray(n_particles, np.uint32).reshape(-1)
+    if h_n.size == 1 and h_T.size != 1:
+        h_n = np.full(h_T.size, h_n[0], np.uint32)
+    if h_n.shape != h_T.shape:
+        raise ValueError("one particle count per problem (or one for all)")
+    return h_T, h_n
+
+
+def batch_problems_workspace_bytes(model, T, n_particles, max_particles=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
+    """cpprob_hip_batch_problems_workspace_bytes: the device bytes of a batch whose problem b has T[b] observes and n_particles[b]
+    particles (an int: every problem's); max_particles is cfg.n_particles (default: the largest of n_particles).  No GPU needed."""
+    L = load_library()
+    h_T, h_n = _problem_shapes(T, n_particles)
+    top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), top, int(h_T.size))
+    out = C.c_uint64()
+    rc = L.cpprob_hip_batch_problems_workspace_bytes(C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out))
     if rc:
         msg = L.cpprob_hip_last_error(None)
         e = CpprobHipError("cpprob_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
@@ -212,6 +240,8 @@ def load_library(path=None):
         "cpprob_hip_batch_results": (C.c_int, [vp, C.POINTER(Summary), vp, sz, vp, vp]),
         "cpprob_hip_batch_results_device": (C.c_int, [vp, vp, sz]),
         "cpprob_hip_batch_copy_store": (C.c_int, [vp, u64, vp, vp, vp]),
+        "cpprob_hip_batch_problems_workspace_bytes": (C.c_int, [C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]),
+        "cpprob_hip_batch_begin_problems": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -259,6 +289,7 @@ class Engine:
         self.T = 0
         self.is_int = False
         self.K = 0
+        self.batch_shapes = None              # (h_T, h_n) of a batch begun by batch_begin_problems
 
     def close(self):
         if getattr(self, "h", None):
@@ -390,6 +421,33 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_begin(self.h, C.byref(cfg), obs.ctypes.data_as(C.POINTER(C.c_double)), obs.shape[1]))
         self.batch_B, self.batch_T, self.batch_n = obs.shape[0], obs.shape[1], int(n_particles)
         self.batch_K = 3 if model == MODEL_HMM3 else 8
+        self.batch_shapes = None
+        return self
+
+    def batch_begin_problems(self, model, observes, n_particles, tables=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
+                             max_particles=None):
+        """A batch whose problems differ.  observes: a list of 1-D arrays, problem b's own sequence (any lengths); n_particles: an int
+        or one count a problem; tables (MODEL_HMM_TABLE): None (the set_hmm table for every problem) or (means [B, k], transition
+        [B, k, k]), problem b's own table.  batch_results() then returns arrays padded to the longest problem (rows t >= T_b zero) and
+        batch_store(b) problem b's own [T_b, n_b]."""
+        seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in observes]
+        h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
+        flat = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0))
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(model, top, len(seqs), resampler, ess_threshold, keep_history, algorithm, flags)
+        k, means, trans = 0, None, None
+        if tables is not None:
+            means = np.ascontiguousarray(tables[0], np.float64)
+            trans = np.ascontiguousarray(tables[1], np.float64)
+            if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != len(seqs):
+                raise ValueError("tables = (means [B, k], transition [B, k, k])")
+            k = means.shape[1]
+        self._chk(self.L.cpprob_hip_batch_begin_problems(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                         flat.ctypes.data_as(C.POINTER(C.c_double)), k, None if means is None else means.ctypes.data,
+                                                         None if trans is None else trans.ctypes.data))
+        self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
+        self.batch_K = 3 if model == MODEL_HMM3 else 8
+        self.batch_shapes = (h_T, h_n)
         return self
 
     def batch_run(self, seeds):
@@ -414,8 +472,13 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_results_device(self.h, _dptr(out), out.numel()))
 
     def batch_store(self, b):
-        """Problem b's particle store: (values [T, n] int32, ancestors [T, n] int32, final log-weights [n])."""
+        """Problem b's particle store: (values [T, n] int32, ancestors [T, n] int32, final log-weights [n]); after batch_begin_problems
+        T and n are problem b's own."""
         T, n = self.batch_T, self.batch_n
+        if self.batch_shapes is not None:
+            if not 0 <= int(b) < self.batch_B:
+                raise ValueError("problem index out of range")
+            T, n = int(self.batch_shapes[0][int(b)]), int(self.batch_shapes[1][int(b)])
         vals = np.zeros((T, n), np.int32)
         anc = np.zeros((T, n), np.int32)
         logw = np.zeros(n)

@@ -985,7 +985,7 @@ void free_run_buffers(cpprob_hip_ctx* c)
 
 // ---- batched SMC (cpprob_hip_batch_*, csrc/batch_smc.hpp) -------------------------------------------------------------------------
 // Device workspace of a batch: regions side by side, each starting on a 256-byte boundary (cpprob_hip_batch_workspace_bytes states the sum).
-struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, values, anc, total; };
+struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, values, anc, total, prob, order; };
 size_t batch_round(size_t x) { return (x + 255) / 256 * 256; }
 BatchLayout batch_layout(uint64_t B, uint64_t T, uint64_t n, int spp, bool keep)
 {
@@ -1006,9 +1006,36 @@ BatchLayout batch_layout(uint64_t B, uint64_t T, uint64_t n, int spp, bool keep)
     return L;
 }
 
+// ... and of a batch begun by cpprob_hip_batch_begin_problems: the small regions padded to T_max rows a problem, one threshold table
+// a problem, the descriptors and the dispatch order, and the particle store packed (sum of T_b n_b entries): twelve regions
+// (cpprob_hip_batch_problems_workspace_bytes states the sum).
+struct BatchProblemsShape { uint64_t T_max = 0, n_max = 0, steps = 0; };      // steps = sum of T_b n_b
+BatchLayout batch_layout_problems(uint64_t B, const BatchProblemsShape& sh, int spp, bool keep)
+{
+    BatchLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { const size_t at = o; o += batch_round(bytes); return at; };
+    L.tab = take(B * sh.T_max * kBatchTab * sizeof(double));
+    L.seeds = take(B * sizeof(uint64_t));
+    L.thr = take(B * 64 * sizeof(uint64_t));
+    L.ctrl = take(B * kBatchCtrlBytes);
+    L.stats = take(B * sh.T_max * (uint64_t)spp * sizeof(double));
+    L.ess = take(B * sh.T_max * sizeof(double));
+    L.res = take(B * sh.T_max * sizeof(int32_t));
+    L.nreq = take(B * sizeof(int32_t));
+    L.prob = take(B * sizeof(BatchProblem));
+    L.order = take(B * sizeof(int32_t));
+    L.values = take(keep ? sh.steps : 0);
+    L.anc = take(keep ? sh.steps * sizeof(int32_t) : 0);
+    L.total = o;
+    return L;
+}
+
 struct BatchState {
     cpprob_hip_batch_config cfg{};
     bool begun = false, ran = false;
+    bool het = false;                          // begun by cpprob_hip_batch_begin_problems: T = T_max, the shapes in `prob`
+    std::vector<BatchProblem> prob;            // het: [B]
     int T = 0, K = 0, hk = 0;
     BatchLayout lay{};
     std::vector<double> h_tab;                 // [B][T][kBatchTab]: the per-step tables the kernel reads (also the final log-weights' source)
@@ -1047,6 +1074,26 @@ int batch_check(const cpprob_hip_batch_config* cfg, size_t T, std::string& msg)
     if (T == 0 || T > (size_t)INT32_MAX) { msg = "every problem needs 1 .. 2^31 - 1 observes"; return CPPROB_HIP_EINVAL; }
     const long double est = (long double)cfg->n_problems * (long double)T * (64.0L + 8 * 8 + 12 + (cfg->keep_history ? 5.0L * cfg->n_particles : 0.0L));
     if (est > 1e18L) { msg = "the batch's workspace does not fit 64-bit sizes"; return CPPROB_HIP_EINVAL; }
+    return 0;
+}
+
+// The same for a batch of problems with their own shapes: batch_check first (T = the longest problem's), then every T_b and n_b.
+int batch_check_problems(const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, BatchProblemsShape& sh, std::string& msg)
+{
+    sh = BatchProblemsShape();
+    const bool scan = cfg && h_T && h_n && cfg->n_problems <= (uint64_t)INT32_MAX;
+    if (scan) for (uint64_t b = 0; b < cfg->n_problems; ++b) sh.T_max = std::max<uint64_t>(sh.T_max, h_T[b]);
+    if (int rc = batch_check(cfg, scan ? (size_t)sh.T_max : 1, msg)) return rc;
+    if (!h_T || !h_n) { msg = "NULL argument"; return CPPROB_HIP_EINVAL; }
+    for (uint64_t b = 0; b < cfg->n_problems; ++b) {
+        if (h_T[b] == 0 || h_T[b] > (uint32_t)INT32_MAX) { msg = "problem " + std::to_string(b) + ": every problem needs 1 .. 2^31 - 1 observes"; return CPPROB_HIP_EINVAL; }
+        if (h_n[b] == 0 || h_n[b] > cfg->n_particles) {
+            msg = "problem " + std::to_string(b) + ": its particle count must lie in 1 .. cfg->n_particles (the batch's largest)";
+            return CPPROB_HIP_EINVAL;
+        }
+        sh.n_max = std::max<uint64_t>(sh.n_max, h_n[b]);
+        sh.steps += (uint64_t)h_T[b] * h_n[b];
+    }
     return 0;
 }
 
@@ -3451,7 +3498,109 @@ int cpprob_hip_batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->mp.hk = hmm3 ? 0 : k;
     bs->mp.hk_thr = hmm3 ? nullptr : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
-    bs->cfg = *cfg; bs->T = (int)T; bs->K = spp; bs->hk = k;
+    bs->cfg = *cfg; bs->T = (int)T; bs->K = spp; bs->hk = k; bs->het = false;
+    bs->begun = true;
+    return 0;
+}
+
+int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, uint64_t* out_bytes)
+{
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(nullptr, rc, msg);
+    if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
+    const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
+    *out_bytes = batch_layout_problems(cfg->n_problems, sh, spp, cfg->keep_history == 1).total;
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                    const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition)
+{
+    if (!c || !cfg || !h_T || !h_n || !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    const uint64_t B = cfg->n_problems;
+    const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3;
+    const bool own = h_means || h_transition;                 // per-problem tables
+    if (own && (!h_means || !h_transition)) return fail(c, CPPROB_HIP_EINVAL, "per-problem tables need both h_means and h_transition");
+    if (hmm3 && own) return fail(c, CPPROB_HIP_EINVAL, "CPPROB_HIP_MODEL_HMM3 has its own table: h_means and h_transition must be NULL");
+    if (!hmm3 && !own && c->hk < 2) return fail(c, CPPROB_HIP_ESTATE, "CPPROB_HIP_MODEL_HMM_TABLE: call cpprob_hip_set_hmm first, or pass per-problem tables");
+    const int k = hmm3 ? 3 : (own ? (int)k_in : c->hk);
+    if (own) {
+        if (k_in < 2 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "the table model holds 2 .. 8 states");
+        // per table what cpprob_hip_set_hmm demands
+        for (uint64_t b = 0; b < B; ++b) {
+            const double* tr = h_transition + b * (size_t)k * k;
+            const std::string at = "problem " + std::to_string(b) + ": ";
+            for (int s2 = 0; s2 < k; ++s2) {
+                double tot = 0.0;
+                for (int j = 0; j < k; ++j) { const double w = tr[(size_t)s2 * k + j]; if (!(w >= 0.0) || !std::isfinite(w)) return fail(c, CPPROB_HIP_EINVAL, at + "transition weights must be finite and >= 0"); tot += w; }
+                if (!(tot > 0.0)) return fail(c, CPPROB_HIP_EINVAL, at + "a transition row without mass");
+                if (!std::isfinite(h_means[b * (size_t)k + s2])) return fail(c, CPPROB_HIP_EINVAL, at + "state means must be finite");
+            }
+        }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->batch) c->batch = new BatchState();
+    BatchState* bs = c->batch;
+    bs->begun = false; bs->ran = false;
+    const int spp = hmm3 ? 3 : 8;
+    const size_t Tm = (size_t)sh.T_max;
+    host_model_params(bs->mp, cfg->model);
+    // the per-step tables and thresholds of every problem, with the single path's own host expressions (cpprob_hip_infer_begin) on the
+    // problem's own means / transition rows; rows t >= T_b stay zero
+    bs->h_tab.assign((size_t)B * Tm * kBatchTab, 0.0);
+    bs->h_thr.assign((size_t)B * 64, ~0ull);
+    bs->prob.resize(B);
+    std::vector<double> mean, trans;
+    if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
+    std::vector<uint64_t> thr_shared;
+    if (!hmm3 && !own) thr_shared = hmmk_thresholds(trans, k);
+    size_t at_obs = 0;
+    int64_t at_store = 0;
+    for (uint64_t b = 0; b < B; ++b) {
+        if (own) { mean.assign(h_means + b * (size_t)k, h_means + (b + 1) * (size_t)k); trans.assign(h_transition + b * (size_t)k * k, h_transition + (b + 1) * (size_t)k * k); }
+        for (size_t t = 0; t < h_T[b]; ++t) {
+            const double y = h_obs[at_obs + t];
+            double* row = &bs->h_tab[(b * Tm + t) * kBatchTab];
+            if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
+            else hmmk_step_ll(y, mean, k, row);
+        }
+        if (!hmm3) {
+            const std::vector<uint64_t> thr = own ? hmmk_thresholds(trans, k) : thr_shared;
+            std::copy(thr.begin(), thr.end(), bs->h_thr.begin() + (size_t)b * 64);
+        }
+        bs->prob[b].T = (int32_t)h_T[b]; bs->prob[b].n = (int32_t)h_n[b]; bs->prob[b].store = at_store;
+        at_obs += h_T[b];
+        at_store += (int64_t)h_T[b] * h_n[b];
+    }
+    // the longest chains first (steps x LDS passes a step), ties by index: the launch's tail is made of short problems; no result
+    // depends on the order
+    std::vector<int32_t> order(B);
+    for (uint64_t b = 0; b < B; ++b) order[b] = (int32_t)b;
+    auto cost = [&](int32_t b) { return (uint64_t)h_T[b] * ((h_n[b] + (uint64_t)kTile - 1) / kTile); };
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cost(x) > cost(y); });
+    bs->lay = batch_layout_problems(B, sh, spp, cfg->keep_history == 1);
+    if (bs->lay.total > bs->cap) {
+        // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
+        dfree(bs->d_ws); bs->cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_ws, bs->lay.total));
+        bs->cap = bs->lay.total;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.prob, bs->prob.data(), B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.order, order.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    // the padded rows t >= T_b are never written by a run: zero once (the workspace may have held another batch)
+    HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.stats, 0, B * Tm * (size_t)spp * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.ess, 0, B * Tm * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.res, 0, B * Tm * sizeof(int32_t), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bs->mp.hk = hmm3 ? 0 : k;
+    bs->mp.hk_thr = nullptr;                                  // (the kernel points it at the problem's own rows)
+    bs->cfg = *cfg; bs->T = (int)Tm; bs->K = spp; bs->hk = k; bs->het = true;
     bs->begun = true;
     return 0;
 }
@@ -3465,7 +3614,7 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
     const uint64_t B = bs->cfg.n_problems;
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     const bool keep = bs->cfg.keep_history == 1;
-    BatchArgs a{};
+    BatchHetArgs a{};                         // (a uniform batch launches on its BatchArgs part)
     a.mp = bs->mp;
     a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
     a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
@@ -3479,8 +3628,21 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
     a.T = bs->T; a.n = (int)bs->cfg.n_particles; a.spp = bs->K; a.ess_frac = bs->cfg.ess_threshold;
     const size_t lds = (size_t)batch_lds_bytes(a.n);
     const bool strat = bs->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), lds, c->stream, a); };
-    if (bs->cfg.model == CPPROB_HIP_MODEL_HMM3) {
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), lds, c->stream, static_cast<const BatchArgs&>(a)); };
+    auto go_het = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), lds, c->stream, a); };
+    if (bs->het) {
+        a.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+        a.thr = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+        a.order = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.order);
+        a.T_max = bs->T;
+        if (bs->cfg.model == CPPROB_HIP_MODEL_HMM3) {
+            if (strat) { if (keep) go_het(batch_smc_kernel<ModelHmm3, kFixStratified, true, true>); else go_het(batch_smc_kernel<ModelHmm3, kFixStratified, false, true>); }
+            else { if (keep) go_het(batch_smc_kernel<ModelHmm3, kFixSystematic, true, true>); else go_het(batch_smc_kernel<ModelHmm3, kFixSystematic, false, true>); }
+        } else {
+            if (strat) { if (keep) go_het(batch_smc_kernel<ModelHmmK, kFixStratified, true, true>); else go_het(batch_smc_kernel<ModelHmmK, kFixStratified, false, true>); }
+            else { if (keep) go_het(batch_smc_kernel<ModelHmmK, kFixSystematic, true, true>); else go_het(batch_smc_kernel<ModelHmmK, kFixSystematic, false, true>); }
+        }
+    } else if (bs->cfg.model == CPPROB_HIP_MODEL_HMM3) {
         if (strat) { if (keep) go(batch_smc_kernel<ModelHmm3, kFixStratified, true>); else go(batch_smc_kernel<ModelHmm3, kFixStratified, false>); }
         else { if (keep) go(batch_smc_kernel<ModelHmm3, kFixSystematic, true>); else go(batch_smc_kernel<ModelHmm3, kFixSystematic, false>); }
     } else {
@@ -3517,7 +3679,7 @@ int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, doubl
         o->ess_final = h.ess;
         o->log_norm = h.M + std::log(h.W);
         o->max_logw = h.M;
-        o->n_predict = bs->T;
+        o->n_predict = bs->het ? bs->prob[b].T : bs->T;
         o->stats_per_predict = bs->K;
         o->is_int = 1;
         o->n_resampled = h.n_resampled;
@@ -3536,6 +3698,7 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_d
     if (n_doubles < (size_t)(B * (4 + per))) return fail(c, CPPROB_HIP_EINVAL, "d_out too small: n_problems * (4 + n_predict * stats_per_predict) doubles");
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t total = B * (4 + per);
+    // (a batch of problems: per = T_max spp; rows t >= T_b are zero -- begin cleared them and no run writes them)
     hipLaunchKernelGGL(batch_pack_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
                        (const char*)(bs->d_ws + bs->lay.ctrl), (const double*)(bs->d_ws + bs->lay.stats), (int)per, B, d_out);
     HIP_TRY(c, hipGetLastError());
@@ -3550,15 +3713,17 @@ int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_
     if (bs->cfg.keep_history != 1) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
     if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t T = (size_t)bs->T, n = bs->cfg.n_particles;
+    // (a batch of problems: the problem's own [T_b][n_b] at its packed offset; its table rows are T_max apart)
+    const size_t T = bs->het ? (size_t)bs->prob[problem].T : (size_t)bs->T, n = bs->het ? (size_t)bs->prob[problem].n : (size_t)bs->cfg.n_particles;
+    const size_t first = bs->het ? (size_t)bs->prob[problem].store : (size_t)problem * T * n;
     std::vector<int8_t> v(T * n);
-    HIP_TRY(c, hipMemcpyAsync(v.data(), bs->d_ws + bs->lay.values + problem * T * n, T * n, hipMemcpyDeviceToHost, c->stream));
-    if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->d_ws + bs->lay.anc + problem * T * n * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v.data(), bs->d_ws + bs->lay.values + first, T * n, hipMemcpyDeviceToHost, c->stream));
+    if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->d_ws + bs->lay.anc + first * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (h_values) for (size_t i = 0; i < T * n; ++i) h_values[i] = v[i];
     if (h_logw) {
         // the final weights are table values: ll of the last step at the particle's state (what cpprob_hip_copy_logw returns)
-        const double* row = &bs->h_tab[((size_t)problem * T + (T - 1)) * kBatchTab];
+        const double* row = &bs->h_tab[((size_t)problem * (size_t)bs->T + (T - 1)) * kBatchTab];
         for (size_t i = 0; i < n; ++i) h_logw[i] = row[(int)v[(T - 1) * n + i]];
     }
     return 0;

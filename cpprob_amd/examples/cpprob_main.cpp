@@ -12,6 +12,8 @@
 //                   --no_dump  --json (print the in-memory result as one JSON line)
 //                   --batch_observes_file F (smc, built-in HMMs: one observation sequence a line, all in one batched launch; seeds --seed + line
 //                   index; one estimate a line, one JSON object a line under --json)
+//                   --batch_tables_file F (smc, no --model: one table-weight HMM problem a line, "[means...] [transition, row-major...]
+//                   [observes...]"; tables and lengths may differ from line to line; all in one batched launch, seeds and output as above)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <array>
 #include <cstdint>
@@ -30,7 +32,7 @@
 namespace {
 
 struct Args {
-    std::string model, model_folder = ".", observes, observes_file, generated_file = "post", batch_observes_file;
+    std::string model, model_folder = ".", observes, observes_file, generated_file = "post", batch_observes_file, batch_tables_file;
     bool sis = false, smc = false, estimate = false, json = false;
     int repeat = 1;
     std::size_t n_samples = 10000;            // src/main.cpp:166
@@ -106,6 +108,45 @@ int execute_batch(const F& model, const Args& a)
     return EXIT_SUCCESS;
 }
 
+// --batch_tables_file F: one problem of the k-state table HMM a line -- its means (k numbers), its transition weights (k x k, row-major)
+// and its observes (any number), three lists in the grammar of --observes; k is the length of the first list of the first line.  All
+// lines run as ONE batch (cpprob::gpu::hmm_table_batch) with --n_samples particles each; output as for --batch_observes_file.
+int execute_batch_tables(const Args& a)
+{
+    if (!a.smc) { std::cerr << "--batch_tables_file runs SMC: set --smc" << std::endl; return EXIT_FAILURE; }
+    std::ifstream in(a.model_folder + "/" + a.batch_tables_file);
+    if (!in) { std::cerr << "cannot open " << a.model_folder << "/" << a.batch_tables_file << std::endl; return EXIT_FAILURE; }
+    std::vector<cpprob::gpu::HmmTable> tables;
+    std::vector<std::vector<double>> observes;
+    std::vector<std::uint64_t> seeds;
+    std::string line;
+    std::size_t k = 0;
+    while (std::getline(in, line)) {
+        const std::size_t at = tables.size();
+        std::tuple<std::vector<double>, std::vector<double>, std::vector<double>> p;
+        if (!cpprob::parse_string(line, p)) { std::cerr << "Could not parse line " << at << ": expected [means] [transition] [observes]." << std::endl; return EXIT_FAILURE; }
+        if (at == 0) k = std::get<0>(p).size();
+        if (std::get<0>(p).size() != k) { std::cerr << "line " << at << ": " << std::get<0>(p).size() << " means, but the first line has " << k << "." << std::endl; return EXIT_FAILURE; }
+        if (std::get<1>(p).size() != k * k) { std::cerr << "line " << at << ": the transition list holds " << std::get<1>(p).size() << " weights, not k x k = " << k * k << "." << std::endl; return EXIT_FAILURE; }
+        if (std::get<2>(p).empty()) { std::cerr << "line " << at << ": no observes." << std::endl; return EXIT_FAILURE; }
+        tables.push_back(cpprob::gpu::HmmTable{std::get<0>(p), std::get<1>(p)});
+        observes.push_back(std::get<2>(p));
+        seeds.push_back(cpprob::gpu::options().seed + at);
+    }
+    if (tables.empty()) { std::cerr << "no problems in " << a.batch_tables_file << std::endl; return EXIT_FAILURE; }
+    const std::vector<cpprob::gpu::Result> res = cpprob::gpu::hmm_table_batch(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds);
+    std::cout.precision(17);
+    for (const cpprob::gpu::Result& r : res) {
+        if (a.json) { print_json(r); continue; }
+        std::cout << r.log_evidence;
+        for (const auto& p : r.predicts)
+            for (double v : p.probabilities) std::cout << " " << v;
+        std::cout << std::endl;
+    }
+    cpprob::gpu::release_device_resources();
+    return EXIT_SUCCESS;
+}
+
 template <class F>
 int execute(const F& model, const Args& a)
 {
@@ -157,6 +198,7 @@ int main(int argc, char** argv)
         else if (f == "--observes" || f == "-o") a.observes = next();
         else if (f == "--observes_file") a.observes_file = next();
         else if (f == "--batch_observes_file") a.batch_observes_file = next();   // one problem a line, one batched launch (built-in HMMs, smc)
+        else if (f == "--batch_tables_file") a.batch_tables_file = next();       // one table-HMM problem a line: [means] [transition] [observes]
         else if (f == "--generated_file") a.generated_file = next();
         else if (f == "--seed") opt.seed = std::stoull(next());
         else if (f == "--ess_threshold") opt.ess_threshold = std::stod(next());
@@ -183,6 +225,7 @@ int main(int argc, char** argv)
     }
     if (a.sis == a.smc) { std::cerr << "exactly one of --sis / --smc has to be set" << std::endl; return EXIT_FAILURE; }
     try {
+        if (!a.batch_tables_file.empty()) return execute_batch_tables(a);     // (the model is the table HMM: --model is not read)
         if (a.model == "gaussian_unknown_mean") return execute(models::gaussian_unknown_mean<double>, a);     // main.cpp:123-130
         if (a.model == "gaussian_readme") return execute(models::gaussian_readme<double>, a);
         if (a.model == "linear_gaussian_1d25") return execute(models::linear_gaussian_1d<25>, a);

@@ -622,6 +622,79 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     return out;
 }
 
+// ---- one table-weight HMM under many parameter settings, ragged sequences, per-problem particle counts (cpprob_hip_batch_begin_problems) ----
+// Problem b is CPPROB_HIP_MODEL_HMM_TABLE with tables[b] (k = means.size() states, the same k for all; transition row-major k x k, rows
+// of weights), observes[b] (any length >= 1), n[b] particles and Philox key seeds[b]; result b is what a one-problem run with that
+// table computes: log_evidence, ess, one predict per observe ("state[t]": P(x_t = s), s < k) and the per-step ESS.  tables, observes
+// and n of size 1 are shared by all problems; the number of problems is seeds.size().  Resampler, keep_history (false: filtering
+// statistics), ess_threshold (must be > 1: every step) and device come from options(), as for inference_batch.
+struct HmmTable { std::vector<double> means, transition; };
+
+inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes,
+                                           const std::vector<std::size_t>& n, const std::vector<std::uint64_t>& seeds)
+{
+    const std::size_t B = seeds.size();
+    if (B == 0) throw std::runtime_error("cpprob::gpu::hmm_table_batch: no problems (one seed per problem)");
+    auto fits = [B](std::size_t have) { return have == B || have == 1; };
+    if (!fits(tables.size()) || !fits(observes.size()) || !fits(n.size()))
+        throw std::runtime_error("cpprob::gpu::hmm_table_batch: tables, observes and n hold one entry per seed, or one entry shared by all problems");
+    const std::size_t k = tables[0].means.size();
+    std::vector<double> means, trans, flat;
+    std::vector<std::uint32_t> T(B), np(B);
+    std::size_t T_max = 0, n_max = 0;
+    for (std::size_t b = 0; b < B; ++b) {
+        const HmmTable& tb = tables[tables.size() == 1 ? 0 : b];
+        if (tb.means.size() != k || tb.transition.size() != k * k)
+            throw std::runtime_error("cpprob::gpu::hmm_table_batch: problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
+        means.insert(means.end(), tb.means.begin(), tb.means.end());
+        trans.insert(trans.end(), tb.transition.begin(), tb.transition.end());
+        const std::vector<double>& o = observes[observes.size() == 1 ? 0 : b];
+        flat.insert(flat.end(), o.begin(), o.end());
+        const std::size_t nb = n[n.size() == 1 ? 0 : b];
+        if (o.size() > 0x7fffffffu || nb > 0x7fffffffu) throw std::runtime_error("cpprob::gpu::hmm_table_batch: problem " + std::to_string(b) + ": too large for a batch");
+        T[b] = static_cast<std::uint32_t>(o.size()); np[b] = static_cast<std::uint32_t>(nb);
+        T_max = std::max(T_max, o.size()); n_max = std::max(n_max, nb);
+    }
+    const Options& opt = options();
+    ContextLease lease(opt.device);
+    Context& ctx = *lease;
+    cpprob_hip_batch_config bc{};
+    bc.algorithm = CPPROB_HIP_ALG_SMC;
+    bc.model = CPPROB_HIP_MODEL_HMM_TABLE;
+    bc.resampler = opt.resampler;
+    bc.keep_history = opt.keep_history ? 1 : 0;
+    bc.flags = 0;
+    bc.ess_threshold = opt.ess_threshold;
+    bc.n_particles = n_max;
+    bc.n_problems = B;
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx.check(cpprob_hip_batch_begin_problems(ctx.get(), &bc, T.data(), np.data(), flat.data(), static_cast<std::int32_t>(k), means.data(), trans.data()),
+              "cpprob_hip_batch_begin_problems");
+    ctx.check(cpprob_hip_batch_run(ctx.get(), seeds.data()), "cpprob_hip_batch_run");
+    std::vector<cpprob_hip_summary> sums(B);
+    const std::size_t K = 8;
+    std::vector<double> stats(B * T_max * K), ess(B * T_max);
+    ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+    const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    lease.done();
+    std::vector<Result> out(B);
+    for (std::size_t b = 0; b < B; ++b) {
+        Result& r = out[b];
+        const cpprob_hip_summary& s = sums[b];
+        r.n_particles = np[b]; r.log_evidence = s.log_evidence; r.ess = s.ess_final; r.log_norm = s.log_norm; r.n_resampled = s.n_resampled;
+        r.used_builtin = true; r.step_form = s.step_form; r.run_seconds = seconds;
+        r.predicts.resize(T[b]);
+        for (std::size_t t = 0; t < T[b]; ++t) {
+            PredictStats& p = r.predicts[t];
+            p.address = "state[" + std::to_string(t) + "]";
+            p.is_int = true;
+            p.probabilities.assign(stats.begin() + (b * T_max + t) * K, stats.begin() + (b * T_max + t) * K + k);
+        }
+        r.step_ess.assign(ess.begin() + b * T_max, ess.begin() + b * T_max + T[b]);
+    }
+    return out;
+}
+
 }  // namespace gpu
 }  // namespace cpprob
 #endif

@@ -261,6 +261,35 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* ctx, double* d_out, size_t n
  * log-weights h_logw[n]; any may be NULL.  keep_history = 1 only (else CPPROB_HIP_ESTATE).  Synchronises. */
 int cpprob_hip_batch_copy_store(cpprob_hip_ctx* ctx, uint64_t problem, int32_t* h_values, int32_t* h_anc, double* h_logw);
 
+/* A batch whose problems differ: a second way to begin, in which problem b brings its own number of observes h_T[b], its own particle
+ * count h_n[b] and, for CPPROB_HIP_MODEL_HMM_TABLE, its own table -- the same sequence under many parameter settings (a likelihood
+ * grid, many chains of particle-marginal Metropolis-Hastings), or a ragged collection of sequences.  Problem b still computes what a
+ * one-context SMC run with that table, those observes, h_n[b] particles and seed h_seeds[b] computes.  cpprob_hip_batch_run, _results,
+ * _results_device and _copy_store serve a batch begun either way; the two begins may follow each other on one context (the workspace
+ * only grows).  After this begin:
+ *   - the small results are padded to T_max = max h_T so they stay plain arrays: h_stats[B][T_max][spp], h_ess[B][T_max],
+ *     h_resampled[B][T_max], d_out[B][4 + T_max spp]; rows t >= h_T[b] are zero; cpprob_hip_summary::n_predict of problem b is h_T[b];
+ *   - the particle store is packed: cpprob_hip_batch_copy_store(problem) returns h_values / h_anc [h_T[b]][h_n[b]] and h_logw[h_n[b]].
+ * cfg is as for cpprob_hip_batch_begin, with n_particles = the LARGEST per-problem particle count: it sizes every workgroup's LDS
+ * (6 bytes a particle, n rounded up to 1024), so a workgroup of few particles still reserves the largest problem's share and LDS caps
+ * the workgroups a compute unit holds as if all were that large (3 at 8192, 6 at 4096); a caller with a few large and many small
+ * problems may prefer two batches.  Workgroups are dispatched longest problem first (h_T[b] * ceil(h_n[b] / 1024), ties by index); no
+ * result depends on that order or on the other problems.
+ *
+ * Pure host function (no device, no context): validates cfg (as cpprob_hip_batch_workspace_bytes does, same codes), every h_T[b] >= 1
+ * and 1 <= h_n[b] <= cfg->n_particles <= 8192, and returns the device bytes.  The workspace is twelve regions, each rounded up to a
+ * multiple of 256 bytes: 64 B T_max (per-step tables), 8 B (seeds), 512 B (transition rows, one table a problem), 256 B (control
+ * blocks), 8 B T_max spp (statistics), 8 B T_max (ESS), 4 B T_max (resampling flags), 4 B (requantised generations), 16 B (problem
+ * descriptors), 4 B (dispatch order), and with keep_history = 1 S (states) and 4 S (ancestors), S = sum over b of h_T[b] h_n[b]. */
+int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, uint64_t* out_bytes);
+/* h_T[B], h_n[B]; h_observes packed: problem b's h_T[b] observes start at the sum of h_T[0..b).  CPPROB_HIP_MODEL_HMM_TABLE: k states
+ * (2 .. 8, one k per batch), h_means[B][k] and h_transition[B][k][k] = problem b's table, validated as cpprob_hip_set_hmm validates
+ * (CPPROB_HIP_EINVAL names the problem); both NULL (k ignored): the context's cpprob_hip_set_hmm table for every problem.
+ * CPPROB_HIP_MODEL_HMM3: both NULL, anything else CPPROB_HIP_EINVAL.  Tables and thresholds are evaluated per problem with the host
+ * statements of the single-population begin; uploads and synchronises. */
+int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                    const double* h_observes, int32_t k, const double* h_means, const double* h_transition);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
