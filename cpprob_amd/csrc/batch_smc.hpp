@@ -20,8 +20,14 @@
 // After the last step the read-out runs in the same workgroup: the lineage walk over the problem's rows (keep_history = 1; integer
 // sums per predict hit, trace_stat's evaluation for HMM3) or nothing (filtering: the books wrote every row).  Workgroups never wait
 // on each other.  LDS: 4 bytes of ancestor + 2 bytes of state per particle (48 KiB at n = 8192), so the limit is an LDS limit.
+//
+// Two kinds of batch run through it; they differ only in where a workgroup's scalars come from (BatchArgs).  Uniform
+// (cpprob_hip_batch_begin): workgroup i runs problem i, every problem has T_max steps and n particles, the thresholds are one table and
+// the particle store is [B][T_max][n].  Described (cpprob_hip_batch_begin_problems): workgroup i runs problem order[i] (the longest
+// chains first) with the T, n and packed store offset of its BatchProblem and, for HMM_TABLE, its own thresholds.  Either way problem b
+// owns rows b T_max + t of the small per-step regions (tab, stats, ess, resampled), of which a described problem writes its first T_b.
+// The launch's dynamic LDS is batch_lds_bytes of the batch's largest n; each workgroup carves it by its own npad.
 #pragma once
-#include <type_traits>
 #include "step_counts.hpp"
 #include "step_fixed.hpp"
 
@@ -34,29 +40,25 @@ static_assert(sizeof(StepCtrl) <= kBatchCtrlBytes, "a problem's control block");
 
 __host__ __device__ inline int64_t batch_lds_bytes(int64_t n) { const int64_t np = (n + kTile - 1) / kTile * kTile; return np * 6; }
 
-struct BatchArgs {
-    ModelParams mp;                            // HMM3: hmm_thr; HMM_TABLE: hk, hk_thr (the batch's own copy of the table)
-    const double* tab;                         // [B][T][kBatchTab]
-    const uint64_t* seeds;                     // [B]
-    int8_t* values; int32_t* anc;              // [B][T][n] (keep_history), else nullptr
-    char* ctrl;                                // [B] control blocks of kBatchCtrlBytes
-    double* stats; double* ess; int32_t* resampled;   // [B][T][spp], [B][T], [B][T]
-    int32_t* n_requant;                        // [B]
-    int T, n, spp;
-    double ess_frac;
-};
-
-// A batch whose problems differ (cpprob_hip_batch_begin_problems): every problem brings its own length, particle count and, for
-// HMM_TABLE, its own transition thresholds.  The small per-step regions (tab, stats, ess, resampled) are padded to T_max rows a problem;
-// the particle store is packed: problem b's values / anc hold T_b * n_b entries from element `store` on.  BatchArgs::T / n are unused
-// (mp.hk_thr too); the launch's dynamic LDS is batch_lds_bytes of the batch's largest n, each workgroup carves it by its own npad.
+// A described problem: its length, its particle count and the first of its T * n entries in the packed values / anc.
 struct BatchProblem { int32_t T, n; int64_t store; };
 static_assert(sizeof(BatchProblem) == 16, "one problem's descriptor");
-struct BatchHetArgs : BatchArgs {
-    const BatchProblem* prob;                  // [B]
-    const uint64_t* thr;                       // [B][64] (HMM_TABLE): problem b's rows, the layout of ModelParams::hk_thr
-    const int32_t* order;                      // [B]: workgroup i runs problem order[i] (the longest chains first)
-    int T_max;
+
+struct BatchArgs {
+    ModelParams mp;                            // HMM3: hmm_thr; HMM_TABLE: hk (the thresholds are `thr`: mp.hk_thr is not read)
+    const double* tab;                         // [B][T_max][kBatchTab]
+    const uint64_t* seeds;                     // [B]
+    const uint64_t* thr;                       // HMM_TABLE: problem b's 64 words at thr + b * thr_stride, the layout of ModelParams::hk_thr
+    const BatchProblem* prob;                  // [B], described batch; nullptr: uniform
+    const int32_t* order;                      // [B], described batch: workgroup i runs problem order[i]
+    int8_t* values; int32_t* anc;              // keep_history: [B][T_max][n] (uniform) or packed by prob[b].store; else nullptr
+    char* ctrl;                                // [B] control blocks of kBatchCtrlBytes
+    double* stats; double* ess; int32_t* resampled;   // [B][T_max][spp], [B][T_max], [B][T_max]
+    int32_t* n_requant;                        // [B]
+    int T_max, n;                              // T_max: rows a problem holds in the small regions; uniform: every problem's T = T_max and n
+    int thr_stride;                            // words: 0 (one shared table) or 64 (a table a problem)
+    int spp;
+    double ess_frac;
 };
 
 __device__ __forceinline__ uint32_t batch_sel8(const uint32_t (&q)[8], int s)
@@ -67,8 +69,8 @@ __device__ __forceinline__ uint32_t batch_sel8(const uint32_t (&q)[8], int s)
     return r;
 }
 
-template <class Model, int RS, bool KEEP, bool HET = false>
-__global__ __launch_bounds__(kThreads) void batch_smc_kernel(std::conditional_t<HET, BatchHetArgs, BatchArgs> a)
+template <class Model, int RS, bool KEEP>
+__global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
 {
     using V = typename Model::value_t;
     constexpr bool kCounts = Model::kWeightTable == 3;          // HMM3: prefix counts; HMM_TABLE: fixed-point masses
@@ -79,12 +81,10 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(std::conditional_t<
     __shared__ unsigned long long s_rows[2][kTraceKeys];        // read-out (HMM3): the pair counts of hit t, then of hit T-1
     __shared__ uint64_t s_acc[2][kWaves][8];                    // read-out: per-wavefront sums of a hit
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
-    // the problem this workgroup runs, its shape and its first entry in values / anc; T_row: the rows a problem holds in tab / stats / ess / resampled
-    const int b = [&] { if constexpr (HET) return (int)a.order[blockIdx.x]; else return (int)blockIdx.x; }();
-    const int n = [&] { if constexpr (HET) return (int)a.prob[b].n; else return a.n; }();
-    const int T = [&] { if constexpr (HET) return (int)a.prob[b].T; else return a.T; }();
-    const int T_row = [&] { if constexpr (HET) return a.T_max; else return a.T; }();
-    constexpr bool kOwnThr = HET && Model::kWeightTable != 3;   // HMM_TABLE: this problem's transition thresholds
+    // the problem this workgroup runs and its shape (workgroup-uniform: scalar loads and selects)
+    const int b = a.order ? (int)a.order[blockIdx.x] : (int)blockIdx.x;
+    const int n = a.prob ? (int)a.prob[b].n : a.n;
+    const int T = a.prob ? (int)a.prob[b].T : a.T_max;
     const int npad = (n + kTile - 1) / kTile * kTile, passes = npad / kTile;
     int32_t* A = reinterpret_cast<int32_t*>(s_batch);                                       // ancestors of the next generation (slots while the comb runs; paths in the read-out)
     uint8_t* S0 = reinterpret_cast<uint8_t*>(A + npad);
@@ -92,26 +92,23 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(std::conditional_t<
     const double n_pop = (double)n;
     const int k_states = kCounts ? 3 : a.mp.hk;
     const uint64_t seed = a.seeds[b];
-    const double* tab = a.tab + (int64_t)b * T_row * kBatchTab;
+    const double* tab = a.tab + (int64_t)b * a.T_max * kBatchTab;
     StepCtrl* ctrl = reinterpret_cast<StepCtrl*>(a.ctrl + (int64_t)b * kBatchCtrlBytes);
-    double* ess_b = a.ess + (int64_t)b * T_row;
-    int32_t* res_b = a.resampled + (int64_t)b * T_row;
-    double* st_b = a.stats + (int64_t)b * T_row * a.spp;
-    int8_t* val_b = KEEP && !HET ? a.values + (int64_t)b * T * n : nullptr;
-    int32_t* anc_b = KEEP && !HET ? a.anc + (int64_t)b * T * n : nullptr;
-    // HET: the problem's packed offset is read from its descriptor where a row is addressed (one scalar load).  Held in registers
-    // across the steps instead, that 64-bit value makes <HMM3, stratified, KEEP> reserve a 68-byte private segment
-    // (profiles/r09_notes.md, "Kernel resources"); the uniform kernel's offset is recomputable from kernel arguments.
-    auto val_rows = [&] { if constexpr (HET) return a.values + a.prob[b].store; else return val_b; };
-    auto anc_rows = [&] { if constexpr (HET) return a.anc + a.prob[b].store; else return anc_b; };
+    double* ess_b = a.ess + (int64_t)b * a.T_max;
+    int32_t* res_b = a.resampled + (int64_t)b * a.T_max;
+    double* st_b = a.stats + (int64_t)b * a.T_max * a.spp;
+    // The problem's first entry in values / anc is formed where a row is addressed (a scalar load or multiply), not held across the
+    // steps: held in registers, that 64-bit value made <HMM3, stratified, KEEP> reserve a 68-byte private segment
+    // (profiles/r09_notes.md, "Kernel resources").
+    auto store = [&]() -> int64_t { return a.prob ? a.prob[b].store : (int64_t)b * T * n; };
     if (tid == 0) { ctrl->lz_trace = nullptr; ctrl->first_bad = -1; ctrl->log_z = 0.0; ctrl->n_resampled = 0; ctrl->fix_gap = 0.0; }
     int n_requant = 0;
     uint32_t q_fin[8] = {0, 0, 0, 0, 0, 0, 0, 0};              // HMM_TABLE: the final generation's weight of each state
     uint64_t S_fin = 0;
-    // HMM_TABLE, HET: the problem's 64 threshold words staged in LDS once; every draw reads its row there.  (Left in global memory
+    // HMM_TABLE: the problem's 64 threshold words staged in LDS once; every draw reads its row there.  (Left in global memory
     // the same batch runs 6 % slower: profiles/r09_notes.md, "Threshold staging".)
-    __shared__ uint64_t s_thr[kOwnThr ? 64 : 1];
-    if constexpr (kOwnThr) { if (tid < 64) s_thr[tid] = a.thr[(int64_t)b * 64 + tid]; __syncthreads(); }
+    __shared__ uint64_t s_thr[kCounts ? 1 : 64];                // (HMM3: unused, and takes no LDS)
+    if constexpr (!kCounts) { if (tid < 64) s_thr[tid] = a.thr[(int64_t)b * a.thr_stride + tid]; __syncthreads(); }
     for (int t = 0; t < T; ++t) {
         uint8_t* cur = (t & 1) ? S1 : S0;
         const uint8_t* prv = (t & 1) ? S0 : S1;
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(std::conditional_t<
             }
             typename Model::Rand r;
             Model::draw4(seed, (uint64_t)i0, t, r);
-            if constexpr (kOwnThr) {
+            if constexpr (!kCounts) {
                 ModelParams mp_b = a.mp;                                  // the batch's parameters, hk_thr pointed at this problem's staged rows
                 mp_b.hk_thr = s_thr;
                 Model::apply4(mp_b, t, r, prev, x);
@@ -143,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(std::conditional_t<
                 cur[i] = (uint8_t)s;
                 cA += s < 4 ? 1ull << (16 * s) : 0ull;
                 cB += s >= 4 ? 1ull << (16 * (s - 4)) : 0ull;
-                if (KEEP) { val_rows()[(int64_t)t * n + i] = (int8_t)s; anc_rows()[(int64_t)t * n + i] = an[k]; }
+                if (KEEP) { a.values[store() + (int64_t)t * n + i] = (int8_t)s; a.anc[store() + (int64_t)t * n + i] = an[k]; }
             }
         }
         // ---- count ----
@@ -296,8 +293,8 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(std::conditional_t<
         const double* e_fin = tab + (int64_t)(T - 1) * kBatchTab + 3;
         for (int t = T - 1; t >= 0; --t) {
             uint64_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};                       // HMM3: pair counts by key; HMM_TABLE: weight sums by state
-            const int8_t* vrow = val_rows() + (int64_t)t * n;
-            const int32_t* arow = anc_rows() + (int64_t)t * n;
+            const int8_t* vrow = a.values + store() + (int64_t)t * n;
+            const int32_t* arow = a.anc + store() + (int64_t)t * n;
             for (int p = 0; p < passes; ++p) {
 #pragma unroll
                 for (int k = 0; k < kPPT; ++k) {

@@ -984,59 +984,41 @@ void free_run_buffers(cpprob_hip_ctx* c)
 }
 
 // ---- batched SMC (cpprob_hip_batch_*, csrc/batch_smc.hpp) -------------------------------------------------------------------------
-// Device workspace of a batch: regions side by side, each starting on a 256-byte boundary (cpprob_hip_batch_workspace_bytes states the sum).
-struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, values, anc, total, prob, order; };
+// Device workspace of a batch: regions side by side, each starting on a 256-byte boundary; an empty region takes no bytes.
+//   uniform    (cpprob_hip_batch_begin: T_rows = T, tables = 1, no descriptors, entries = B T n): ten regions,
+//              cpprob_hip_batch_workspace_bytes states the sum
+//   described  (cpprob_hip_batch_begin_problems: T_rows = T_max, tables = B, descriptors and dispatch order, entries = sum of T_b n_b,
+//              the particle store packed): twelve regions, cpprob_hip_batch_problems_workspace_bytes states the sum
+struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, prob, order, values, anc, total; };
 size_t batch_round(size_t x) { return (x + 255) / 256 * 256; }
-BatchLayout batch_layout(uint64_t B, uint64_t T, uint64_t n, int spp, bool keep)
+BatchLayout batch_layout(uint64_t B, uint64_t T_rows, uint64_t tables, bool described, uint64_t entries, int spp, bool keep)
 {
     BatchLayout L{};
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += batch_round(bytes); return at; };
-    L.tab = take(B * T * kBatchTab * sizeof(double));
+    L.tab = take(B * T_rows * kBatchTab * sizeof(double));
     L.seeds = take(B * sizeof(uint64_t));
-    L.thr = take(8 * 8 * sizeof(uint64_t));
+    L.thr = take(tables * 64 * sizeof(uint64_t));
     L.ctrl = take(B * kBatchCtrlBytes);
-    L.stats = take(B * T * (uint64_t)spp * sizeof(double));
-    L.ess = take(B * T * sizeof(double));
-    L.res = take(B * T * sizeof(int32_t));
+    L.stats = take(B * T_rows * (uint64_t)spp * sizeof(double));
+    L.ess = take(B * T_rows * sizeof(double));
+    L.res = take(B * T_rows * sizeof(int32_t));
     L.nreq = take(B * sizeof(int32_t));
-    L.values = take(keep ? B * T * n : 0);
-    L.anc = take(keep ? B * T * n * sizeof(int32_t) : 0);
+    L.prob = take(described ? B * sizeof(BatchProblem) : 0);
+    L.order = take(described ? B * sizeof(int32_t) : 0);
+    L.values = take(keep ? entries : 0);
+    L.anc = take(keep ? entries * sizeof(int32_t) : 0);
     L.total = o;
     return L;
 }
-
-// ... and of a batch begun by cpprob_hip_batch_begin_problems: the small regions padded to T_max rows a problem, one threshold table
-// a problem, the descriptors and the dispatch order, and the particle store packed (sum of T_b n_b entries): twelve regions
-// (cpprob_hip_batch_problems_workspace_bytes states the sum).
 struct BatchProblemsShape { uint64_t T_max = 0, n_max = 0, steps = 0; };      // steps = sum of T_b n_b
-BatchLayout batch_layout_problems(uint64_t B, const BatchProblemsShape& sh, int spp, bool keep)
-{
-    BatchLayout L{};
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += batch_round(bytes); return at; };
-    L.tab = take(B * sh.T_max * kBatchTab * sizeof(double));
-    L.seeds = take(B * sizeof(uint64_t));
-    L.thr = take(B * 64 * sizeof(uint64_t));
-    L.ctrl = take(B * kBatchCtrlBytes);
-    L.stats = take(B * sh.T_max * (uint64_t)spp * sizeof(double));
-    L.ess = take(B * sh.T_max * sizeof(double));
-    L.res = take(B * sh.T_max * sizeof(int32_t));
-    L.nreq = take(B * sizeof(int32_t));
-    L.prob = take(B * sizeof(BatchProblem));
-    L.order = take(B * sizeof(int32_t));
-    L.values = take(keep ? sh.steps : 0);
-    L.anc = take(keep ? sh.steps * sizeof(int32_t) : 0);
-    L.total = o;
-    return L;
-}
 
 struct BatchState {
     cpprob_hip_batch_config cfg{};
     bool begun = false, ran = false;
-    bool het = false;                          // begun by cpprob_hip_batch_begin_problems: T = T_max, the shapes in `prob`
-    std::vector<BatchProblem> prob;            // het: [B]
-    int T = 0, K = 0, hk = 0;
+    std::vector<BatchProblem> prob;            // [B]: every problem's T, n and first entry in the particle store (a uniform batch's too)
+    bool described = false;                    // cpprob_hip_batch_begin_problems: descriptors, dispatch order and a threshold table a problem on the device
+    int T = 0, K = 0, hk = 0;                  // T: rows a problem holds in the small regions (the longest problem's)
     BatchLayout lay{};
     std::vector<double> h_tab;                 // [B][T][kBatchTab]: the per-step tables the kernel reads (also the final log-weights' source)
     std::vector<uint64_t> h_thr;               // HMM_TABLE: the rows' thresholds at begin
@@ -1095,6 +1077,89 @@ int batch_check_problems(const cpprob_hip_batch_config* cfg, const uint32_t* h_T
         sh.steps += (uint64_t)h_T[b] * h_n[b];
     }
     return 0;
+}
+
+// Begins a checked batch.  Described (h_T, h_n given): problem b has h_T[b] observes, consecutive in h_obs, and h_n[b] particles;
+// uniform (both NULL): every problem has T_max observes and cfg->n_particles particles.  HMM_TABLE of k states: problem b's own table
+// (h_means [B][k], h_transition [B][k][k]) or, both NULL, the table of cpprob_hip_set_hmm.
+int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_max, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
+                int k, const double* h_means, const double* h_transition)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->batch) c->batch = new BatchState();
+    BatchState* bs = c->batch;
+    bs->begun = false; bs->ran = false;
+    const uint64_t B = cfg->n_problems;
+    const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3, described = h_T != nullptr, own = h_means != nullptr;
+    const int spp = hmm3 ? 3 : 8;
+    const uint64_t tables = described ? B : 1;
+    host_model_params(bs->mp, cfg->model);
+    bs->mp.hk = hmm3 ? 0 : k;
+    // the per-step tables and thresholds of every problem, with the single path's own host expressions (cpprob_hip_infer_begin) on the
+    // problem's means / transition rows; rows t >= T_b stay zero
+    bs->h_tab.assign((size_t)B * T_max * kBatchTab, 0.0);
+    bs->h_thr.assign((size_t)tables * 64, ~0ull);
+    bs->prob.resize(B);
+    std::vector<double> mean, trans;
+    if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
+    std::vector<uint64_t> thr;
+    size_t at_obs = 0;
+    int64_t at_store = 0;
+    for (uint64_t b = 0; b < B; ++b) {
+        const size_t T_b = described ? h_T[b] : T_max, n_b = described ? h_n[b] : (size_t)cfg->n_particles;
+        if (own) { mean.assign(h_means + b * (size_t)k, h_means + (b + 1) * (size_t)k); trans.assign(h_transition + b * (size_t)k * k, h_transition + (b + 1) * (size_t)k * k); }
+        for (size_t t = 0; t < T_b; ++t) {
+            const double y = h_obs[at_obs + t];
+            double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
+            if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
+            else hmmk_step_ll(y, mean, k, row);
+        }
+        if (!hmm3 && b < tables) {
+            if (own || b == 0) thr = hmmk_thresholds(trans, k);
+            std::copy(thr.begin(), thr.end(), bs->h_thr.begin() + (size_t)b * 64);
+        }
+        bs->prob[b].T = (int32_t)T_b; bs->prob[b].n = (int32_t)n_b; bs->prob[b].store = at_store;
+        at_obs += T_b;
+        at_store += (int64_t)(T_b * n_b);
+    }
+    bs->lay = batch_layout(B, T_max, tables, described, (uint64_t)at_store, spp, cfg->keep_history == 1);
+    if (bs->lay.total > bs->cap) {
+        // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
+        dfree(bs->d_ws); bs->cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_ws, bs->lay.total));
+        bs->cap = bs->lay.total;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    std::vector<int32_t> order;                               // (lives until the synchronisation below)
+    if (described) {
+        // the longest chains first (steps x LDS passes a step), ties by index: the launch's tail is made of short problems; no result
+        // depends on the order
+        order.resize(B);
+        for (uint64_t b = 0; b < B; ++b) order[b] = (int32_t)b;
+        auto cost = [&](int32_t b) { return (uint64_t)h_T[b] * ((h_n[b] + (uint64_t)kTile - 1) / kTile); };
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cost(x) > cost(y); });
+        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.prob, bs->prob.data(), B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.order, order.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        // the padded rows t >= T_b are never written by a run: zero once (the workspace may have held another batch)
+        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.stats, 0, B * T_max * (size_t)spp * sizeof(double), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.ess, 0, B * T_max * sizeof(double), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.res, 0, B * T_max * sizeof(int32_t), c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
+    bs->begun = true;
+    return 0;
+}
+
+// The eight kernels of cpprob_hip_batch_run.
+using BatchKernel = void (*)(BatchArgs);
+template <class Model>
+BatchKernel batch_kernel(bool stratified, bool keep)
+{
+    static constexpr BatchKernel k[2][2] = {{batch_smc_kernel<Model, kFixSystematic, false>, batch_smc_kernel<Model, kFixSystematic, true>},
+                                            {batch_smc_kernel<Model, kFixStratified, false>, batch_smc_kernel<Model, kFixStratified, true>}};
+    return k[stratified][keep];
 }
 
 }  // namespace
@@ -3453,7 +3518,7 @@ int cpprob_hip_batch_workspace_bytes(const cpprob_hip_batch_config* cfg, size_t 
     if (int rc = batch_check(cfg, T, msg)) return fail(nullptr, rc, msg);
     if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
     const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
-    *out_bytes = batch_layout(cfg->n_problems, T, cfg->n_particles, spp, cfg->keep_history == 1).total;
+    *out_bytes = batch_layout(cfg->n_problems, T, 1, false, cfg->n_problems * T * cfg->n_particles, spp, cfg->keep_history == 1).total;
     return 0;
 }
 
@@ -3463,44 +3528,7 @@ int cpprob_hip_batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg
     std::string msg;
     if (int rc = batch_check(cfg, T, msg)) return fail(c, rc, msg);
     if (cfg->model == CPPROB_HIP_MODEL_HMM_TABLE && c->hk < 2) return fail(c, CPPROB_HIP_ESTATE, "CPPROB_HIP_MODEL_HMM_TABLE: call cpprob_hip_set_hmm first");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->batch) c->batch = new BatchState();
-    BatchState* bs = c->batch;
-    bs->begun = false; bs->ran = false;
-    const uint64_t B = cfg->n_problems;
-    const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3;
-    const int spp = hmm3 ? 3 : 8;
-    host_model_params(bs->mp, cfg->model);
-    // the per-step tables of every problem, with the single path's own host expressions (cpprob_hip_infer_begin)
-    bs->h_tab.assign((size_t)B * T * kBatchTab, 0.0);
-    bs->h_thr.assign(64, ~0ull);
-    const int k = hmm3 ? 3 : c->hk;
-    for (uint64_t b = 0; b < B; ++b)
-        for (size_t t = 0; t < T; ++t) {
-            const double y = h_obs[b * T + t];
-            double* row = &bs->h_tab[(b * T + t) * kBatchTab];
-            if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
-            else hmmk_step_ll(y, c->hk_mean, k, row);
-        }
-    if (!hmm3) {
-        const std::vector<uint64_t> thr = hmmk_thresholds(c->hk_trans, k);
-        std::copy(thr.begin(), thr.end(), bs->h_thr.begin());
-    }
-    bs->lay = batch_layout(B, T, cfg->n_particles, spp, cfg->keep_history == 1);
-    if (bs->lay.total > bs->cap) {
-        // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
-        dfree(bs->d_ws); bs->cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_ws, bs->lay.total));
-        bs->cap = bs->lay.total;
-    }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    bs->mp.hk = hmm3 ? 0 : k;
-    bs->mp.hk_thr = hmm3 ? nullptr : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
-    bs->cfg = *cfg; bs->T = (int)T; bs->K = spp; bs->hk = k; bs->het = false;
-    bs->begun = true;
-    return 0;
+    return batch_begin(c, cfg, T, nullptr, nullptr, h_obs, cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : c->hk, nullptr, nullptr);
 }
 
 int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, uint64_t* out_bytes)
@@ -3510,7 +3538,7 @@ int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg
     if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(nullptr, rc, msg);
     if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
     const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
-    *out_bytes = batch_layout_problems(cfg->n_problems, sh, spp, cfg->keep_history == 1).total;
+    *out_bytes = batch_layout(cfg->n_problems, sh.T_max, cfg->n_problems, true, sh.steps, spp, cfg->keep_history == 1).total;
     return 0;
 }
 
@@ -3542,67 +3570,7 @@ int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_co
             }
         }
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->batch) c->batch = new BatchState();
-    BatchState* bs = c->batch;
-    bs->begun = false; bs->ran = false;
-    const int spp = hmm3 ? 3 : 8;
-    const size_t Tm = (size_t)sh.T_max;
-    host_model_params(bs->mp, cfg->model);
-    // the per-step tables and thresholds of every problem, with the single path's own host expressions (cpprob_hip_infer_begin) on the
-    // problem's own means / transition rows; rows t >= T_b stay zero
-    bs->h_tab.assign((size_t)B * Tm * kBatchTab, 0.0);
-    bs->h_thr.assign((size_t)B * 64, ~0ull);
-    bs->prob.resize(B);
-    std::vector<double> mean, trans;
-    if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
-    std::vector<uint64_t> thr_shared;
-    if (!hmm3 && !own) thr_shared = hmmk_thresholds(trans, k);
-    size_t at_obs = 0;
-    int64_t at_store = 0;
-    for (uint64_t b = 0; b < B; ++b) {
-        if (own) { mean.assign(h_means + b * (size_t)k, h_means + (b + 1) * (size_t)k); trans.assign(h_transition + b * (size_t)k * k, h_transition + (b + 1) * (size_t)k * k); }
-        for (size_t t = 0; t < h_T[b]; ++t) {
-            const double y = h_obs[at_obs + t];
-            double* row = &bs->h_tab[(b * Tm + t) * kBatchTab];
-            if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
-            else hmmk_step_ll(y, mean, k, row);
-        }
-        if (!hmm3) {
-            const std::vector<uint64_t> thr = own ? hmmk_thresholds(trans, k) : thr_shared;
-            std::copy(thr.begin(), thr.end(), bs->h_thr.begin() + (size_t)b * 64);
-        }
-        bs->prob[b].T = (int32_t)h_T[b]; bs->prob[b].n = (int32_t)h_n[b]; bs->prob[b].store = at_store;
-        at_obs += h_T[b];
-        at_store += (int64_t)h_T[b] * h_n[b];
-    }
-    // the longest chains first (steps x LDS passes a step), ties by index: the launch's tail is made of short problems; no result
-    // depends on the order
-    std::vector<int32_t> order(B);
-    for (uint64_t b = 0; b < B; ++b) order[b] = (int32_t)b;
-    auto cost = [&](int32_t b) { return (uint64_t)h_T[b] * ((h_n[b] + (uint64_t)kTile - 1) / kTile); };
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cost(x) > cost(y); });
-    bs->lay = batch_layout_problems(B, sh, spp, cfg->keep_history == 1);
-    if (bs->lay.total > bs->cap) {
-        // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
-        dfree(bs->d_ws); bs->cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_ws, bs->lay.total));
-        bs->cap = bs->lay.total;
-    }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.prob, bs->prob.data(), B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.order, order.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    // the padded rows t >= T_b are never written by a run: zero once (the workspace may have held another batch)
-    HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.stats, 0, B * Tm * (size_t)spp * sizeof(double), c->stream));
-    HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.ess, 0, B * Tm * sizeof(double), c->stream));
-    HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.res, 0, B * Tm * sizeof(int32_t), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    bs->mp.hk = hmm3 ? 0 : k;
-    bs->mp.hk_thr = nullptr;                                  // (the kernel points it at the problem's own rows)
-    bs->cfg = *cfg; bs->T = (int)Tm; bs->K = spp; bs->hk = k; bs->het = true;
-    bs->begun = true;
-    return 0;
+    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition);
 }
 
 int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
@@ -3614,10 +3582,14 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
     const uint64_t B = bs->cfg.n_problems;
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     const bool keep = bs->cfg.keep_history == 1;
-    BatchHetArgs a{};                         // (a uniform batch launches on its BatchArgs part)
+    BatchArgs a{};
     a.mp = bs->mp;
     a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
     a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
+    a.thr = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+    a.thr_stride = bs->described ? 64 : 0;
+    a.prob = bs->described ? reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob) : nullptr;
+    a.order = bs->described ? reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.order) : nullptr;
     a.values = keep ? reinterpret_cast<int8_t*>(bs->d_ws + bs->lay.values) : nullptr;
     a.anc = keep ? reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.anc) : nullptr;
     a.ctrl = bs->d_ws + bs->lay.ctrl;
@@ -3625,30 +3597,10 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
     a.ess = reinterpret_cast<double*>(bs->d_ws + bs->lay.ess);
     a.resampled = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.res);
     a.n_requant = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.nreq);
-    a.T = bs->T; a.n = (int)bs->cfg.n_particles; a.spp = bs->K; a.ess_frac = bs->cfg.ess_threshold;
-    const size_t lds = (size_t)batch_lds_bytes(a.n);
+    a.T_max = bs->T; a.n = (int)bs->cfg.n_particles; a.spp = bs->K; a.ess_frac = bs->cfg.ess_threshold;
     const bool strat = bs->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), lds, c->stream, static_cast<const BatchArgs&>(a)); };
-    auto go_het = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), lds, c->stream, a); };
-    if (bs->het) {
-        a.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-        a.thr = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
-        a.order = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.order);
-        a.T_max = bs->T;
-        if (bs->cfg.model == CPPROB_HIP_MODEL_HMM3) {
-            if (strat) { if (keep) go_het(batch_smc_kernel<ModelHmm3, kFixStratified, true, true>); else go_het(batch_smc_kernel<ModelHmm3, kFixStratified, false, true>); }
-            else { if (keep) go_het(batch_smc_kernel<ModelHmm3, kFixSystematic, true, true>); else go_het(batch_smc_kernel<ModelHmm3, kFixSystematic, false, true>); }
-        } else {
-            if (strat) { if (keep) go_het(batch_smc_kernel<ModelHmmK, kFixStratified, true, true>); else go_het(batch_smc_kernel<ModelHmmK, kFixStratified, false, true>); }
-            else { if (keep) go_het(batch_smc_kernel<ModelHmmK, kFixSystematic, true, true>); else go_het(batch_smc_kernel<ModelHmmK, kFixSystematic, false, true>); }
-        }
-    } else if (bs->cfg.model == CPPROB_HIP_MODEL_HMM3) {
-        if (strat) { if (keep) go(batch_smc_kernel<ModelHmm3, kFixStratified, true>); else go(batch_smc_kernel<ModelHmm3, kFixStratified, false>); }
-        else { if (keep) go(batch_smc_kernel<ModelHmm3, kFixSystematic, true>); else go(batch_smc_kernel<ModelHmm3, kFixSystematic, false>); }
-    } else {
-        if (strat) { if (keep) go(batch_smc_kernel<ModelHmmK, kFixStratified, true>); else go(batch_smc_kernel<ModelHmmK, kFixStratified, false>); }
-        else { if (keep) go(batch_smc_kernel<ModelHmmK, kFixSystematic, true>); else go(batch_smc_kernel<ModelHmmK, kFixSystematic, false>); }
-    }
+    const BatchKernel kern = bs->cfg.model == CPPROB_HIP_MODEL_HMM3 ? batch_kernel<ModelHmm3>(strat, keep) : batch_kernel<ModelHmmK>(strat, keep);
+    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), (size_t)batch_lds_bytes(a.n), c->stream, a);
     HIP_TRY(c, hipGetLastError());
     bs->ran = true;
     return 0;
@@ -3679,7 +3631,7 @@ int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, doubl
         o->ess_final = h.ess;
         o->log_norm = h.M + std::log(h.W);
         o->max_logw = h.M;
-        o->n_predict = bs->het ? bs->prob[b].T : bs->T;
+        o->n_predict = bs->prob[b].T;
         o->stats_per_predict = bs->K;
         o->is_int = 1;
         o->n_resampled = h.n_resampled;
@@ -3713,9 +3665,8 @@ int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_
     if (bs->cfg.keep_history != 1) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
     if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
     HIP_TRY(c, hipSetDevice(c->device));
-    // (a batch of problems: the problem's own [T_b][n_b] at its packed offset; its table rows are T_max apart)
-    const size_t T = bs->het ? (size_t)bs->prob[problem].T : (size_t)bs->T, n = bs->het ? (size_t)bs->prob[problem].n : (size_t)bs->cfg.n_particles;
-    const size_t first = bs->het ? (size_t)bs->prob[problem].store : (size_t)problem * T * n;
+    // the problem's own [T_b][n_b] from its first entry in the store on; its table rows are bs->T apart
+    const size_t T = (size_t)bs->prob[problem].T, n = (size_t)bs->prob[problem].n, first = (size_t)bs->prob[problem].store;
     std::vector<int8_t> v(T * n);
     HIP_TRY(c, hipMemcpyAsync(v.data(), bs->d_ws + bs->lay.values + first, T * n, hipMemcpyDeviceToHost, c->stream));
     if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->d_ws + bs->lay.anc + first * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

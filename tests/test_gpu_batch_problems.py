@@ -1,4 +1,4 @@
-"""Batched SMC over problems that differ (include/cpprob_hip.h: cpprob_hip_batch_begin_problems; csrc/batch_smc.hpp, HET = true):
+"""Batched SMC over problems that differ (include/cpprob_hip.h: cpprob_hip_batch_begin_problems; csrc/batch_smc.hpp, a described batch):
 every problem brings its own transition table and emission means, its own number of observes and its own particle count.  Problem b
 must still be what a one-problem run with its table, observes, particle count and seed computes -- the oracle's states and ancestors,
 its flags, ESS and evidence, its statistics -- independent of the other problems, of the dispatch order and of every packed offset.
@@ -431,6 +431,35 @@ def test_both_begins_and_single_runs_coexist_on_one_context(engine):
     engine.batch_begin(cp.MODEL_HMM3, obs_u, n)
     engine.batch_run(seeds_u)
     equal(batch_read(2), ref_u)
+
+
+@pytest.mark.parametrize("keep", [True, False])
+@pytest.mark.parametrize("rs", RESAMPLERS)
+def test_uniform_batch_on_the_workspace_of_a_described_one(engine, rs, keep):
+    """Both begins share one workspace and one kernel: a uniform batch begun after a described one finds that batch's descriptors,
+    dispatch order and per-problem thresholds still on the device and must read none of them.  B = 3 both times, so every stale slot
+    has a problem that would use it; n = 1025 needs a second pass over the population.  Every problem of the uniform batch is the
+    oracle's under the table set in between."""
+    k, B = 5, 3
+    shapes = [(9, 777), (2, 2), (5, 1025)]
+    means, trans = _tables(k, B, 61)
+    rng = np.random.default_rng(23)
+    obs = [_table_obs(means[b], T, rng) for b, (T, _) in enumerate(shapes)]
+    engine.batch_begin_problems(cp.MODEL_HMM_TABLE, obs, [n for _, n in shapes], tables=(means, trans), resampler=rs, keep_history=keep)
+    engine.batch_run(_seeds(B, 3))
+    m2, t2 = _tables(k, 1, 62)
+    assert not np.array_equal(m2[0], means[0]) and not np.array_equal(t2[0], trans[0])
+    _set_table(engine, m2[0], t2[0])
+    T, n = 4, 1025
+    obs_u = np.stack([_table_obs(m2[0], T, rng) for _ in range(B)])
+    seeds = _seeds(B, 4)
+    engine.batch_begin(cp.MODEL_HMM_TABLE, obs_u, n, resampler=rs, keep_history=keep)
+    engine.batch_run(seeds)
+    summ, stats, ess, res = engine.batch_results()
+    assert stats.shape == (B, T, 8) and ess.shape == (B, T) and res.shape == (B, T)
+    for b in range(B):
+        assert summ[b]["n_predict"] == T
+        _check_problem(engine, b, obs_u[b], n, seeds[b], rs, cp.MODEL_HMM_TABLE, summ[b], stats[b], ess[b], res[b], k=k, keep=keep)
 
 
 # ---- 8. C++ / CLI -----------------------------------------------------------------------------------------------------------------

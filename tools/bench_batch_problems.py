@@ -3,14 +3,16 @@
 (profiles/r09_notes.md).  Device-synchronised wall time; every form is warmed up, the forms of a cell are timed in alternation
 `--reps` times (each timing the median of `--inner` runs) and the median and the spread (max - min) over the repeats are reported.
 Cells (--cells):
-  uniform   HMM_TABLE, B = 1024, n = 4096, T = 16, keep_history 1 and 0: the same batch begun by batch_begin (the uniform kernel) and by
-            batch_begin_problems (the heterogeneous kernel, shared table)
+  uniform   --model (HMM_TABLE or HMM3), B = 1024, n = 4096, T = 16, keep_history 1 and 0: the same batch begun by batch_begin and by
+            batch_begin_problems (shared table); both run the one kernel, so the two forms show what the descriptors cost.  Also the
+            host time of batch_begin alone (begin_ms)
   order     a skewed batch (1024 problems, T_b log-uniform in 4 .. 128, n_b in {512, 4096}) in the dispatch order of the loaded library
   buys      B = 1024 tables x one sequence, T = 16, n = 1024 and 4096: one heterogeneous batch (begin + run + results) against, per table,
             set_hmm + batch_begin of one problem + batch_run + batch_results, timed on `--sample` tables and scaled to B
 --libs A B ...: the cells run in child processes that load these builds of the library in alternation (CPPROB_HIP_LIB) -- how
-profiles/r09_notes.md compared the shipped kernel with builds that read the thresholds from global memory or keep the caller's dispatch order.
-usage: python tools/bench_batch_problems.py [--cells uniform order buys] [--reps 3] [--inner 5] [--sample 128] [--libs A B ...]
+profiles/r09_notes.md compared the shipped kernel with builds that read the thresholds from global memory or keep the caller's dispatch
+order, and profiles/r10_notes.md the one kernel with the parent commit's two.
+usage: python tools/bench_batch_problems.py [--cells uniform order buys] [--model table|hmm3] [--reps 3] [--inner 5] [--sample 128] [--libs A B ...]
 One JSON line per measurement."""
 import argparse
 import json
@@ -58,19 +60,20 @@ def cell_uniform(cp, args, emit, keeps=(True, False)):
     means, trans = tables(1, 3, 7)
     obs = np.stack([exact.simulate_hmm(T, 1000 + b) for b in range(B)])
     seeds = np.arange(1000, 1000 + B, dtype=np.uint64)
+    model = cp.MODEL_HMM3 if args.model == "hmm3" else cp.MODEL_HMM_TABLE
     eu, eh = cp.Engine(0), cp.Engine(0)
     for e in (eu, eh):
         e.set_hmm(means[0], trans[0])
     for keep in keeps:
-        eu.batch_begin(cp.MODEL_HMM_TABLE, obs, n, keep_history=keep)
-        eh.batch_begin_problems(cp.MODEL_HMM_TABLE, list(obs), n, keep_history=keep)
+        begin_ms = timed(lambda: eu.batch_begin(model, obs, n, keep_history=keep), args.inner) * 1e3
+        eh.batch_begin_problems(model, list(obs), n, keep_history=keep)
 
         def run(e):
             e.batch_run(seeds)
             e.sync()
         r = alternate({"uniform": lambda: run(eu), "problems": lambda: run(eh)}, args.reps, args.inner)
         same = all(np.array_equal(x, y) for x, y in zip(eu.batch_results()[1:], eh.batch_results()[1:]))
-        emit(dict(cell="uniform", B=B, n=n, T=T, keep_history=int(keep), uniform_ms=r["uniform"][0], uniform_spread_ms=r["uniform"][1],
+        emit(dict(cell="uniform", model=args.model, B=B, n=n, T=T, keep_history=int(keep), begin_ms=begin_ms, uniform_ms=r["uniform"][0], uniform_spread_ms=r["uniform"][1],
                   problems_ms=r["problems"][0], problems_spread_ms=r["problems"][1], results_equal=bool(same)))
     eu.close()
     eh.close()
@@ -146,7 +149,7 @@ def across_libs(args, emit):
     for _ in range(args.reps):
         for lib in args.libs:
             env = dict(os.environ, CPPROB_HIP_LIB=lib)
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--cells"] + args.cells + ["--reps", "1", "--inner", str(args.inner), "--sample", str(args.sample)],
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--cells"] + args.cells + ["--model", args.model, "--reps", "1", "--inner", str(args.inner), "--sample", str(args.sample)],
                                env=env, capture_output=True, text=True, timeout=600)
             if p.returncode:
                 raise RuntimeError("child with %s failed (%d): %s" % (lib, p.returncode, p.stderr[-2000:]))
@@ -166,6 +169,7 @@ def across_libs(args, emit):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cells", nargs="+", default=["uniform", "order", "buys"])
+    ap.add_argument("--model", choices=["table", "hmm3"], default="table", help="the uniform cell's model")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--sample", type=int, default=128)

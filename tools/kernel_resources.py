@@ -23,7 +23,7 @@ def main():
         def g(k):
             m = re.search(k + r": (\d+)", b)
             return m.group(1) if m else "?"
-        print("%-130s VGPR %s AGPR %s SGPR %s spill %s scratch %s occ %s LDS %s" % (dn[:130], g("VGPRs"), g("AGPRs"), g("SGPRs"), g("VGPR Spill"), g(r"ScratchSize \[bytes/lane\]"),
+        print("%-130s VGPR %s AGPR %s SGPR %s spill %s scratch %s occ %s LDS %s" % (dn[:130], g("VGPRs"), g("AGPRs"), g("SGPRs"), g("VGPRs Spill"), g(r"ScratchSize \[bytes/lane\]"),
                                                                                       g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")))
 
 
