@@ -15,13 +15,15 @@ SCOPE_GLOBAL, SCOPE_ISLAND, SCOPE_EXCHANGE = 0, 1, 2
 FLAG_FLOATING_POINT_STEP, FLAG_NO_SKIP_ROWS, FLAG_SIS_PER_TILE, FLAG_SIS_SEPARATE_READOUT, FLAG_WREL_STORED, FLAG_FP_TILE_PARTIALS, FLAG_WALK_READOUT = 1, 2, 4, 8, 16, 32, 64
 FLAG_MULTINOMIAL_LITERAL, FLAG_REPEAT_IN_FLOATING_POINT, FLAG_PAIRED_STEP_LAUNCH = 128, 256, 512
 FLAG_SEPARATE_TRACE_READOUT = 1024      # the trace-word / filtering-only read-out as a launch after the last step, not folded into it
+FLAG_SERIAL_RUNS = 2048                 # run lanes off: every run of the context on its one stream (A/B of cpprob_hip_infer_lanes)
+SERIAL_STREAM, SERIAL_PROFILE, SERIAL_SHARD, SERIAL_FLAG, SERIAL_MEMORY, SERIAL_SIZE = 1, 2, 3, 4, 5, 6      # cpprob_hip_infer_lanes: serial_reason
 N_KERNEL_CLASSES = 6
 KERNEL_CLASS_NAMES = ["smc_step", "scan_partials", "smooth", "finalize", "sis", "resample"]
 
 # every symbol include/cpprob_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "cpprob_hip_abi_version", "cpprob_hip_build_id", "cpprob_hip_device_count", "cpprob_hip_create", "cpprob_hip_destroy", "cpprob_hip_last_error",
-    "cpprob_hip_stream", "cpprob_hip_sync", "cpprob_hip_set_hmm", "cpprob_hip_infer_begin", "cpprob_hip_infer_run", "cpprob_hip_infer_summary",
+    "cpprob_hip_stream", "cpprob_hip_sync", "cpprob_hip_set_hmm", "cpprob_hip_infer_begin", "cpprob_hip_infer_run", "cpprob_hip_infer_lanes", "cpprob_hip_infer_summary",
     "cpprob_hip_infer_stats", "cpprob_hip_infer_results", "cpprob_hip_infer_results_device", "cpprob_hip_infer_step_trace", "cpprob_hip_copy_values", "cpprob_hip_copy_ancestors",
     "cpprob_hip_copy_logw", "cpprob_hip_copy_paths", "cpprob_hip_smc_step_begin", "cpprob_hip_smc_step_end",
     "cpprob_hip_smc_finish", "cpprob_hip_smc_first_bad_generation", "cpprob_hip_smc_repair_begin", "cpprob_hip_smc_repair_end", "cpprob_hip_filter_masses", "cpprob_hip_exchange_plan", "cpprob_hip_exchange_pack", "cpprob_hip_exchange_commit", "cpprob_hip_exchange_setup", "cpprob_hip_exchange_transport",
@@ -152,6 +154,7 @@ def load_library(path=None):
         "cpprob_hip_set_hmm": (C.c_int, [vp, i32, C.POINTER(dbl), C.POINTER(dbl)]),
         "cpprob_hip_infer_begin": (C.c_int, [vp, C.POINTER(Config), C.POINTER(dbl), sz]),
         "cpprob_hip_infer_run": (C.c_int, [vp, u64]),
+        "cpprob_hip_infer_lanes": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64), C.POINTER(i32)]),
         "cpprob_hip_infer_summary": (C.c_int, [vp, C.POINTER(Summary)]),
         "cpprob_hip_infer_stats": (C.c_int, [vp, C.POINTER(dbl), sz]),
         "cpprob_hip_infer_results": (C.c_int, [vp, vp, vp, sz, vp, vp]),
@@ -311,6 +314,7 @@ class Engine:
 
     @property
     def stream_ptr(self):
+        """The context's hipStream_t.  Reading it pins the context to that one stream until it is closed: no run lanes (lanes())."""
         return self.L.cpprob_hip_stream(self.h)
 
     def sync(self):
@@ -351,6 +355,13 @@ class Engine:
 
     def run(self, run_index=0):
         self._chk(self.L.cpprob_hip_infer_run(self.h, int(run_index)))
+
+    def lanes(self):
+        """Run lanes of this context (cpprob_hip_infer_lanes): depth = lanes begun (1: the context alone), last_lane = lane of the
+        last run, lane_bytes = device bytes the further lanes hold, serial_reason = 0 or SERIAL_*.  Changes nothing."""
+        d, last, nbytes, why = C.c_int32(), C.c_int32(), C.c_uint64(), C.c_int32()
+        self._chk(self.L.cpprob_hip_infer_lanes(self.h, C.byref(d), C.byref(last), C.byref(nbytes), C.byref(why)))
+        return {"depth": d.value, "last_lane": last.value, "lane_bytes": nbytes.value, "serial_reason": why.value}
 
     def summary(self):
         s = Summary()

@@ -26,6 +26,7 @@ using namespace cph;
 namespace {
 
 thread_local std::string g_last_error;      // per thread: contexts (and the group driver's workers) live on threads of their own
+thread_local hipError_t g_last_hip_error = hipSuccess;   // the HIP error behind the last CPPROB_HIP_EDEVICE of HIP_TRY (run lanes: out of memory or not)
 
 struct EventPair { hipEvent_t a, b; int cls; int count; };
 
@@ -181,6 +182,19 @@ struct cpprob_hip_ctx {
     double prof_ms[CPPROB_HIP_N_KERNEL_CLASSES] = {0};
     int64_t prof_calls[CPPROB_HIP_N_KERNEL_CLASSES] = {0};
     BatchState* batch = nullptr;
+
+    // run lanes: cpprob_hip_infer_run calls that follow each other directly go round robin over up to kLaneDepth - 1 further contexts of
+    // the library's own -- each a whole context: its own stream, workspace, hierarchy rotation, counters and pinned block, begun as
+    // this one was -- so that independent runs overlap on the device.  Lane 0 is the context itself; reads go to the lane that ran last.
+    bool is_lane = false;                                  // a lane of another context: never routes
+    std::vector<cpprob_hip_ctx*> lanes; std::vector<char> lane_begun;      // [lane - 1]; begun with the configuration in force
+    int lane_last = 0;                                     // lane of the last run
+    bool lane_chain = false;                               // the previous entry point on this context was cpprob_hip_infer_run
+    bool lanes_busy = false;                               // a further lane may have work in flight
+    int lane_pin = 0;                                      // CPPROB_HIP_SERIAL_* that pinned the context serial until it is destroyed
+    uint64_t lane_bytes = 0;                               // device bytes of the further lanes' population-sized arrays (a lane: of its own)
+    cpprob_hip_config lane_cfg{}; std::vector<double> lane_obs;            // what cpprob_hip_infer_begin was given
+    hipEvent_t lane_ev = nullptr;                          // orders cpprob_hip_infer_results_device against a lane's stream
 };
 
 namespace {
@@ -195,8 +209,10 @@ int fail(cpprob_hip_ctx* ctx, int code, const std::string& msg)
 #define HIP_TRY(ctx, expr)                                                                                  \
     do {                                                                                                    \
         hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess)                                                                              \
+        if (e__ != hipSuccess) {                                                                            \
+            g_last_hip_error = e__;                                                                         \
             return fail(ctx, CPPROB_HIP_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e__));       \
+        }                                                                                                   \
     } while (0)
 
 template <class T>
@@ -1164,6 +1180,147 @@ BatchKernel batch_kernel(bool stratified, bool keep)
 
 }  // namespace
 
+// ---- run lanes ---------------------------------------------------------------------------------------------------------------------
+// One run is a chain of dependent launches, each short next to its own latency chain (profiles/r06_notes.md section 9): it leaves
+// most of the chip idle, and only independent runs can fill it.  Runs of one begun problem that differ in their run index are
+// independent; they serialised because a context has one stream and one workspace.  Here cpprob_hip_infer_run calls that follow each
+// other DIRECTLY go round robin over kLaneDepth lanes (the rule depends on the call sequence alone, never on timing); a caller who
+// reads every run's results before the next run never leaves lane 0.  Depth and size limit: measured, profiles/r11_notes.md.
+#ifndef CPPROB_LANE_DEPTH
+#define CPPROB_LANE_DEPTH 3
+#endif
+#ifndef CPPROB_LANE_MAX_TILES
+#define CPPROB_LANE_MAX_TILES 10240
+#endif
+namespace {
+// Depth 3: 0.074-0.078 ms per hmm<16> run of 10^6 particles against 0.083-0.089 with 2 lanes and 0.092-0.095 with 4 (a process opens 4
+// hardware queues and something else of the process holds one: a fourth stream shares a queue and serialises with its neighbour).
+constexpr int kLaneDepth = CPPROB_LANE_DEPTH;                            // lanes of a context, lane 0 included
+// Up to 10240 tiles of 1024 particles (profiles/r11_notes.md section 3): the gain is 50 % at 977 tiles, 27 % at 3907 and 3.8 % (hmm<16>) /
+// 6.7 % (linear_gaussian_1d<100>) at 9766, above the spread for every workload measured.  At 12208 tiles hmm<128> on the ESS schedule
+// still gains 3.6 % but hmm<16> 0.22 % against a spread of 2.7 %: lanes there would engage where a measured gain does not exceed it.
+constexpr int64_t kLaneMaxTiles = CPPROB_LANE_MAX_TILES;
+constexpr uint64_t kLaneMemShare = 4;                                    // the further lanes hold at most 1 / kLaneMemShare of the memory free without them
+static_assert(kLaneDepth >= 1 && kLaneDepth <= 4, "a context never owns more than 4 streams");
+
+int lanes_wait(cpprob_hip_ctx* c)                                        // every further lane's stream has drained
+{
+    if (!c->lanes_busy) return 0;
+    for (cpprob_hip_ctx* l : c->lanes)
+        if (l) HIP_TRY(c, hipStreamSynchronize(l->stream));
+    c->lanes_busy = false;
+    return 0;
+}
+// entry points that act on the context's own state: they end a sequence of back-to-back runs and find every lane idle
+inline int lanes_own(cpprob_hip_ctx* c)
+{
+    c->lane_chain = false;
+    return c->lanes_busy ? lanes_wait(c) : 0;
+}
+#define LANES_OWN(c)                                                       \
+    do {                                                                   \
+        if (c) { if (int rc__ = lanes_own(c)) return rc__; }               \
+    } while (0)
+
+int lane_serial_reason(const cpprob_hip_ctx* c)
+{
+    if (c->lane_pin) return c->lane_pin;
+    if (c->profile) return CPPROB_HIP_SERIAL_PROFILE;                    // (the per-class events are stream-ordered)
+    if (c->exchange || c->cfg.n_global != c->cfg.n_particles) return CPPROB_HIP_SERIAL_SHARD;
+    if (c->cfg.flags & CPPROB_HIP_FLAG_SERIAL_RUNS) return CPPROB_HIP_SERIAL_FLAG;
+    if ((int64_t)c->nb > kLaneMaxTiles) return CPPROB_HIP_SERIAL_SIZE;
+    return kLaneDepth < 2 ? CPPROB_HIP_SERIAL_FLAG : 0;
+}
+
+inline cpprob_hip_ctx* lane_of_last(cpprob_hip_ctx* c) { return c->lane_last == 0 ? c : c->lanes[(size_t)c->lane_last - 1]; }
+
+// device bytes a begin of this configuration allocates: the arrays that grow with the population, as sized for ld particles and T steps
+// (the rest is a few KB; free memory as hipMemGetInfo reports it does not move for allocations the runtime serves from a chunk it holds)
+uint64_t lane_estimate_bytes(const cpprob_hip_ctx* c, uint64_t ld, uint64_t T)
+{
+    const uint64_t rows = c->keep ? T : 2;
+    uint64_t b = ld * (4 * sizeof(double) + 2 * sizeof(uint32_t)) + rows * ld * c->ssz + (c->keep ? T * ld * sizeof(int32_t) : 0);
+    if (c->cfg.algorithm == CPPROB_HIP_ALG_SMC && c->cfg.resampler == CPPROB_HIP_RESAMPLE_MULTINOMIAL) b += ld * (sizeof(double) + sizeof(int32_t));
+    b += (uint64_t)c->nb * 512 + (uint64_t)c->walk_cap * T * 8 * sizeof(double) + ((uint64_t)1 << 20);
+    return b;
+}
+
+void lane_drop(cpprob_hip_ctx* c, size_t k)
+{
+    if (c->lanes[k]) { c->lane_bytes -= std::min(c->lane_bytes, c->lanes[k]->lane_bytes); cpprob_hip_destroy(c->lanes[k]); }
+    c->lanes[k] = nullptr; c->lane_begun[k] = 0;
+}
+
+// Lane `lane` >= 1, created and begun as the context was, the first time it is needed.  *out = nullptr without an error: its memory does
+// not fit -- the lane is freed and the context pinned serial.
+int lane_get(cpprob_hip_ctx* c, int lane, cpprob_hip_ctx** out)
+{
+    *out = nullptr;
+    const size_t k = (size_t)lane - 1;
+    if (c->lanes.size() <= k) { c->lanes.resize(k + 1, nullptr); c->lane_begun.resize(k + 1, 0); }
+    if (c->lanes[k] && c->lane_begun[k]) { *out = c->lanes[k]; return 0; }
+    size_t free0 = 0, total = 0;
+    HIP_TRY(c, hipMemGetInfo(&free0, &total));
+    cpprob_hip_ctx* l = c->lanes[k];
+    const bool fits_old = l && l->d_values && l->cap_particles >= (size_t)c->ld && l->cap_T >= c->T && l->cap_keep == c->keep && l->cap_int == c->is_int;
+    const uint64_t need = fits_old ? 0 : lane_estimate_bytes(c, (uint64_t)c->ld, (uint64_t)c->T);
+    if (c->lane_bytes + need > ((uint64_t)free0 + c->lane_bytes) / kLaneMemShare) {
+        lane_drop(c, k);
+        c->lane_pin = CPPROB_HIP_SERIAL_MEMORY;
+        return 0;
+    }
+    int rc = 0;
+    g_last_hip_error = hipSuccess;
+    if (!l) {
+        rc = cpprob_hip_create(c->device, &l);
+        if (rc == 0) { l->is_lane = true; c->lanes[k] = l; }
+    }
+    if (rc == 0 && c->lane_cfg.model == CPPROB_HIP_MODEL_HMM_TABLE) rc = cpprob_hip_set_hmm(l, c->hk, c->hk_mean.data(), c->hk_trans.data());
+    if (rc == 0) rc = cpprob_hip_infer_begin(l, &c->lane_cfg, c->lane_obs.data(), c->lane_obs.size());
+    if (rc == CPPROB_HIP_EDEVICE && g_last_hip_error == hipErrorOutOfMemory) {
+        // (an allocation failed after all: no error, the caller's runs go on one at a time; any other device error is the caller's)
+        (void)hipGetLastError();
+        if (c->lanes[k]) lane_drop(c, k);
+        c->lane_pin = CPPROB_HIP_SERIAL_MEMORY;
+        return 0;
+    }
+    if (rc) return fail(c, rc, l ? l->err : g_last_error);
+    // what the lane holds now (its own field; allocations only grow while a begin can reuse them)
+    c->lane_bytes -= std::min(c->lane_bytes, l->lane_bytes);
+    l->lane_bytes = lane_estimate_bytes(l, (uint64_t)l->cap_particles, (uint64_t)l->cap_T);
+    c->lane_bytes += l->lane_bytes;
+    l->force_fp = c->force_fp;
+    c->lane_begun[k] = 1;
+    *out = l;
+    return 0;
+}
+
+void lanes_invalidate(cpprob_hip_ctx* c)                                 // a new configuration: the lanes are begun again at their next use
+{
+    for (char& b : c->lane_begun) b = 0;
+    c->lane_last = 0; c->lane_chain = false;
+}
+
+// the reads: on the lane of the last run; its error is the context's
+template <class F>
+int lane_read(cpprob_hip_ctx* c, F&& f)
+{
+    if (!c || c->is_lane) return f(c);
+    c->lane_chain = false;
+    cpprob_hip_ctx* l = lane_of_last(c);
+    const int rc = f(l);
+    if (rc && l != c) fail(c, rc, l->err);
+    if (l->force_fp) {
+        // (the run was repeated in the floating-point form: as on one stream, every later run of this configuration takes that form)
+        c->force_fp = true;
+        for (cpprob_hip_ctx* o : c->lanes) if (o) o->force_fp = true;
+    }
+    return rc;
+}
+
+int infer_run_impl(cpprob_hip_ctx* c, uint64_t run_index);
+}  // namespace
+
 extern "C" {
 
 int cpprob_hip_abi_version(void) { return CPPROB_HIP_ABI_VERSION; }
@@ -1213,6 +1370,9 @@ void cpprob_hip_destroy(cpprob_hip_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (cpprob_hip_ctx* l : c->lanes) cpprob_hip_destroy(l);
+    c->lanes.clear(); c->lane_begun.clear();
+    if (c->lane_ev) { (void)hipEventDestroy(c->lane_ev); c->lane_ev = nullptr; }
     free_run_buffers(c);
     batch_free(c);
     dfree(c->d_ctrl); dfree(c->d_local_totals); dfree(c->d_cut_tab); dfree(c->d_cut_head); dfree(c->d_cut_srccnt);
@@ -1227,13 +1387,20 @@ void cpprob_hip_destroy(cpprob_hip_ctx* c)
     delete c;
 }
 
-void* cpprob_hip_stream(cpprob_hip_ctx* c) { return c ? (void*)c->stream : nullptr; }
+void* cpprob_hip_stream(cpprob_hip_ctx* c)
+{
+    if (!c) return nullptr;
+    // a handed-out stream promises stream order to its holder: from here on every run of this context is enqueued on it
+    if (lanes_own(c)) return nullptr;                  // (a lane's work failed: cpprob_hip_last_error says how)
+    if (!c->is_lane) c->lane_pin = CPPROB_HIP_SERIAL_STREAM;
+    return (void*)c->stream;
+}
 
 int cpprob_hip_sync(cpprob_hip_ctx* c)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return lanes_own(c);                               // (every lane)
 }
 
 int cpprob_hip_set_hmm(cpprob_hip_ctx* c, int32_t k, const double* h_means, const double* h_transition)
@@ -1248,12 +1415,14 @@ int cpprob_hip_set_hmm(cpprob_hip_ctx* c, int32_t k, const double* h_means, cons
     }
     c->hk = k; c->hk_mean.assign(h_means, h_means + k); c->hk_trans.assign(h_transition, h_transition + (size_t)k * k);
     c->begun = false;                                   // (a run in flight keeps the tables it was begun with; the next begin takes these)
+    lanes_invalidate(c);
     return 0;
 }
 
 int cpprob_hip_infer_begin(cpprob_hip_ctx* c, const cpprob_hip_config* cfg, const double* h_obs, size_t n_obs)
 {
     if (!c || !cfg || !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    LANES_OWN(c);
     if (cfg->algorithm != CPPROB_HIP_ALG_SIS && cfg->algorithm != CPPROB_HIP_ALG_SMC)
         return fail(c, CPPROB_HIP_EUNSUPPORTED, "algorithm must be sis or smc (compile/csis/dryrun are outside this engine)");
     if (cfg->model < 0 || cfg->model > CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EINVAL, "unknown model id");
@@ -1282,6 +1451,13 @@ int cpprob_hip_infer_begin(cpprob_hip_ctx* c, const cpprob_hip_config* cfg, cons
                                                  "stratum, so a rank's sources own one interval of outputs plus its share of the strata the ranks' boundaries cut (not the literal form, "
                                                  "not the floating-point step, not keep_history = 0)");
     c->cfg = *cfg;
+    // (validated: from here on the old problem is gone -- the lanes are begun again at their next use, with this configuration)
+    lanes_invalidate(c);
+    if (!c->is_lane) {
+        const cpprob_hip_config cfg_in = *cfg;          // (cfg and h_obs may be the copies themselves)
+        std::vector<double> obs_in(h_obs, h_obs + n_obs);
+        c->lane_cfg = cfg_in; c->lane_obs.swap(obs_in);
+    }
     // a model with ONE observe statement has nothing to resample between: smc is sis (the components of its vector-valued
     // statements are rows of the particle store, not resampling points)
     if (cfg->model == CPPROB_HIP_MODEL_GAUSSIAN_2D_UNKNOWN_MEAN) c->cfg.algorithm = CPPROB_HIP_ALG_SIS;
@@ -1523,6 +1699,34 @@ int cpprob_hip_infer_begin(cpprob_hip_ctx* c, const cpprob_hip_config* cfg, cons
 int cpprob_hip_infer_run(cpprob_hip_ctx* c, uint64_t run_index)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    if (c->is_lane) return infer_run_impl(c, run_index);
+    if (!c->begun) { c->lane_chain = false; return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_infer_begin has not been called"); }
+    // which lane: the one that ran last; the next one, round robin, when this call directly follows another run
+    int lane = c->lane_last;
+    if (lane_serial_reason(c) != 0) {
+        if (int rc = lanes_wait(c)) return rc;
+        lane = 0;
+    } else if (c->lane_chain) lane = (c->lane_last + 1) % kLaneDepth;
+    cpprob_hip_ctx* l = c;
+    if (lane > 0) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (int rc = lane_get(c, lane, &l)) { c->lane_chain = false; return rc; }
+        if (!l) {                                       // (it did not fit: one at a time from here on)
+            if (int rc = lanes_wait(c)) return rc;
+            lane = 0; l = c;
+        }
+    }
+    const int rc = infer_run_impl(l, run_index);
+    if (rc && l != c) fail(c, rc, l->err);
+    c->lane_last = lane; c->lane_chain = rc == 0;
+    if (lane > 0) c->lanes_busy = true;
+    return rc;
+}
+
+}  // extern "C"
+namespace {
+int infer_run_impl(cpprob_hip_ctx* c, uint64_t run_index)
+{
     if (!c->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_infer_begin has not been called");
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->cfg.resample_scope != CPPROB_HIP_SCOPE_ISLAND && c->cfg.n_global != c->cfg.n_particles)
@@ -1612,6 +1816,20 @@ int cpprob_hip_infer_run(cpprob_hip_ctx* c, uint64_t run_index)
     HIP_TRY(c, hipGetLastError());
     c->ran = true;
     c->fixed_check_pending = c->fixed_mode && c->cfg.algorithm == CPPROB_HIP_ALG_SMC; c->last_was_infer_run = true; c->last_run_index = run_index;
+    return 0;
+}
+}  // namespace
+extern "C" {
+
+int cpprob_hip_infer_lanes(cpprob_hip_ctx* c, int32_t* depth, int32_t* last_lane, uint64_t* lane_bytes, int32_t* serial_reason)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    int d = 1;
+    for (size_t k = 0; k < c->lanes.size(); ++k) d += (c->lanes[k] && c->lane_begun[k]) ? 1 : 0;
+    if (depth) *depth = d;
+    if (last_lane) *last_lane = c->lane_last;
+    if (lane_bytes) *lane_bytes = c->lane_bytes;
+    if (serial_reason) *serial_reason = c->begun ? lane_serial_reason(c) : c->lane_pin;
     return 0;
 }
 
@@ -1761,7 +1979,7 @@ int settle_fixed(cpprob_hip_ctx* c)
                                                "repair it in the run (cpprob_hip_smc_repair_begin / _end on every rank, from the first offending generation: StepCtrl::first_bad "
                                                "through cpprob_hip_smc_first_bad_generation) or repeat the run with CPPROB_HIP_FLAG_FLOATING_POINT_STEP");
     c->force_fp = true;
-    return cpprob_hip_infer_run(c, c->last_run_index);
+    return infer_run_impl(c, c->last_run_index);
 }
 }  // namespace
 extern "C" {
@@ -1770,9 +1988,11 @@ static int ensure_shard_trace(cpprob_hip_ctx* c, bool& words);
 
 int cpprob_hip_smc_step_begin(cpprob_hip_ctx* c, int32_t t, uint64_t run_index, double* d_local_totals)
 {
+    LANES_OWN(c);
     if (!c || !d_local_totals) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_infer_begin has not been called");
     if (t < 0 || t >= c->T) return fail(c, CPPROB_HIP_EINVAL, "step out of range");
+    c->lane_last = 0;                                   // (the step protocol runs on the context itself: its results are read there)
     HIP_TRY(c, hipSetDevice(c->device));
     const bool sis = c->cfg.algorithm == CPPROB_HIP_ALG_SIS;
     if (sis && t != c->T - 1) return fail(c, CPPROB_HIP_EINVAL, "SIS shards run in one launch: call step_begin(T-1) only");
@@ -1847,6 +2067,7 @@ int cpprob_hip_smc_step_begin(cpprob_hip_ctx* c, int32_t t, uint64_t run_index, 
 
 int cpprob_hip_smc_step_end(cpprob_hip_ctx* c, int32_t t, const double* d_all_totals, int32_t world, int32_t rank)
 {
+    LANES_OWN(c);
     if (!c || !d_all_totals) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun || !c->step_protocol || t != c->step_t) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_smc_step_end(t) follows cpprob_hip_smc_step_begin(t)");
     if (world < 1 || world > 1024 || rank < 0 || rank >= world) return fail(c, CPPROB_HIP_EINVAL, "bad world/rank (1 <= world <= 1024)");
@@ -1915,7 +2136,12 @@ static int shard_repair_begin(cpprob_hip_ctx* c, int g, double* d_local3)
 
 extern "C" {
 
+static int smc_first_bad_generation_impl(cpprob_hip_ctx* c, int32_t* h_generation, double* h_gap);
 int cpprob_hip_smc_first_bad_generation(cpprob_hip_ctx* c, int32_t* h_generation, double* h_gap)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return smc_first_bad_generation_impl(l, h_generation, h_gap); });
+}
+static int smc_first_bad_generation_impl(cpprob_hip_ctx* c, int32_t* h_generation, double* h_gap)
 {
     if (!c || !h_generation) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_infer_begin has not been called");
@@ -1930,6 +2156,7 @@ int cpprob_hip_smc_first_bad_generation(cpprob_hip_ctx* c, int32_t* h_generation
 
 int cpprob_hip_smc_repair_begin(cpprob_hip_ctx* c, int32_t g, double* d_local3)
 {
+    LANES_OWN(c);
     if (!c || !d_local3) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun || !c->step_protocol || !c->fixed_mode || !c->keep || !c->d_lz_trace) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_smc_repair_begin: a history-keeping step-protocol run on fixed-point weights");
     if (g < 0 || g >= c->T) return fail(c, CPPROB_HIP_EINVAL, "generation out of range");
@@ -1941,6 +2168,7 @@ int cpprob_hip_smc_repair_begin(cpprob_hip_ctx* c, int32_t g, double* d_local3)
 
 int cpprob_hip_smc_repair_end(cpprob_hip_ctx* c, int32_t g, const double* d_all3, int32_t world, int32_t rank, double* d_local3)
 {
+    LANES_OWN(c);
     if (!c || !d_all3 || !d_local3) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun || !c->step_protocol || !c->fixed_mode) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_smc_repair_end follows cpprob_hip_smc_repair_begin");
     if (g < 0 || g >= c->T || world < 1 || world > kWave || rank < 0 || rank >= world) return fail(c, CPPROB_HIP_EINVAL, "bad generation / world / rank");
@@ -1970,6 +2198,7 @@ int cpprob_hip_smc_repair_end(cpprob_hip_ctx* c, int32_t g, const double* d_all3
 
 int cpprob_hip_smc_finish(cpprob_hip_ctx* c)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->begun || !c->step_protocol || c->step_t != c->T - 1) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_smc_finish follows the last step's cpprob_hip_smc_step_end");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1985,7 +2214,12 @@ int cpprob_hip_smc_finish(cpprob_hip_ctx* c)
     return 0;
 }
 
+static int filter_masses_impl(cpprob_hip_ctx* c, double** d_masses, int32_t* joint_already);
 int cpprob_hip_filter_masses(cpprob_hip_ctx* c, double** d_masses, int32_t* joint_already)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return filter_masses_impl(l, d_masses, joint_already); });
+}
+static int filter_masses_impl(cpprob_hip_ctx* c, double** d_masses, int32_t* joint_already)
 {
     if (!c || !d_masses || !joint_already) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun || c->keep) return fail(c, CPPROB_HIP_ESTATE, "not a filtering-only run (keep_history = 0)");
@@ -2186,6 +2420,7 @@ extern "C" {
 int cpprob_hip_exchange_plan(cpprob_hip_ctx* c, int32_t t, int32_t world, int32_t rank, const uint64_t* h_shard_begin, uint64_t* h_send_counts,
                              uint64_t* h_recv_counts, int32_t* h_do_resample)
 {
+    LANES_OWN(c);
     if (!c || !h_shard_begin || !h_send_counts || !h_recv_counts) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->exchange) return fail(c, CPPROB_HIP_ESTATE, "the context was not begun with resample_scope = CPPROB_HIP_SCOPE_EXCHANGE");
     if (c->cfg.resampler == CPPROB_HIP_RESAMPLE_MULTINOMIAL)
@@ -2211,6 +2446,7 @@ int cpprob_hip_exchange_plan(cpprob_hip_ctx* c, int32_t t, int32_t world, int32_
 
 int cpprob_hip_exchange_pack(cpprob_hip_ctx* c, int32_t t, void* d_send)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     auto& p = c->plan;
     if (!c->exchange || p.t != t) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_exchange_plan(t) has not run");
@@ -2225,6 +2461,7 @@ int cpprob_hip_exchange_pack(cpprob_hip_ctx* c, int32_t t, void* d_send)
 
 int cpprob_hip_exchange_commit(cpprob_hip_ctx* c, int32_t t, const void* d_recv)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     auto& p = c->plan;
     if (!c->exchange || p.t != t) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_exchange_plan(t) has not run");
@@ -2245,6 +2482,7 @@ int cpprob_hip_exchange_commit(cpprob_hip_ctx* c, int32_t t, const void* d_recv)
 // ---- exchange, stream-ordered form: fixed-capacity transport segments, no host synchronisation inside a run ----
 int cpprob_hip_exchange_setup(cpprob_hip_ctx* c, int32_t world, int32_t rank, const uint64_t* h_shard_begin, int32_t all_peers, uint64_t records_per_peer)
 {
+    LANES_OWN(c);
     if (!c || !h_shard_begin) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun || !c->exchange) return fail(c, CPPROB_HIP_ESTATE, "begin the context with resample_scope = CPPROB_HIP_SCOPE_EXCHANGE first");
     if (records_per_peer == 0) return fail(c, CPPROB_HIP_EINVAL, "records_per_peer must be > 0");
@@ -2276,6 +2514,7 @@ int cpprob_hip_exchange_setup(cpprob_hip_ctx* c, int32_t world, int32_t rank, co
 
 int cpprob_hip_exchange_direct(cpprob_hip_ctx* c, void* const* h_peer_recv)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->x_fixed) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_exchange_setup has not run");
     if (!h_peer_recv) { c->x_direct = false; return 0; }
@@ -2325,6 +2564,7 @@ static int ensure_shard_trace(cpprob_hip_ctx* c, bool& words)
 
 int cpprob_hip_exchange_store(cpprob_hip_ctx* c, cpprob_hip_store* out)
 {
+    LANES_OWN(c);
     if (!c || !out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->begun || !c->exchange || !c->keep) return fail(c, CPPROB_HIP_ESTATE, "no history-keeping exchange-scope run begun");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2344,6 +2584,7 @@ int cpprob_hip_exchange_store(cpprob_hip_ctx* c, cpprob_hip_store* out)
 
 int cpprob_hip_exchange_remote(cpprob_hip_ctx* c, const cpprob_hip_store* h_stores)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->x_fixed || !c->x_direct) return fail(c, CPPROB_HIP_ESTATE, "remote lineages ride the direct transport: cpprob_hip_exchange_setup and _direct first");
     if (!h_stores) { c->x_remote = false; c->trace_shard = false; return 0; }
@@ -2374,6 +2615,7 @@ int cpprob_hip_exchange_remote(cpprob_hip_ctx* c, const cpprob_hip_store* h_stor
 
 int cpprob_hip_exchange_traffic(cpprob_hip_ctx* c, int64_t* h_sent_per_step, size_t n_steps, uint64_t* h_records, uint64_t* h_bytes)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->exchange || !c->d_xplan || !c->d_sent) return fail(c, CPPROB_HIP_ESTATE, "no exchange-scope run on a fixed transport");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2392,6 +2634,7 @@ int cpprob_hip_exchange_traffic(cpprob_hip_ctx* c, int64_t* h_sent_per_step, siz
 int cpprob_hip_exchange_transport(cpprob_hip_ctx* c, void** d_send, void** d_recv, int32_t* n_peers, int32_t* h_peers, uint64_t* records_per_peer,
                                   uint64_t* bytes_per_value)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->x_fixed) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_exchange_setup has not run");
     if (d_send) *d_send = c->d_xsend;
@@ -2405,6 +2648,7 @@ int cpprob_hip_exchange_transport(cpprob_hip_ctx* c, void** d_send, void** d_rec
 
 int cpprob_hip_exchange_pack_async(cpprob_hip_ctx* c, int32_t t)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->exchange || !c->x_fixed) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_exchange_setup has not run");
     if (!c->step_protocol || c->step_t != t || !c->x_all_totals) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_exchange_pack_async(t) follows cpprob_hip_smc_step_end(t)");
@@ -2446,6 +2690,7 @@ int cpprob_hip_exchange_pack_async(cpprob_hip_ctx* c, int32_t t)
 
 int cpprob_hip_exchange_commit_async(cpprob_hip_ctx* c, int32_t t)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->exchange || !c->x_fixed || c->x_plan_t != t) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_exchange_pack_async(t) has not run");
     if (c->x_peers.empty()) return 0;
@@ -2458,6 +2703,7 @@ int cpprob_hip_exchange_commit_async(cpprob_hip_ctx* c, int32_t t)
 
 int cpprob_hip_exchange_status(cpprob_hip_ctx* c, int32_t* h_overflow, uint64_t* h_annex_used)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->exchange || !c->d_xplan) return fail(c, CPPROB_HIP_ESTATE, "no exchange-scope run");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2471,7 +2717,12 @@ int cpprob_hip_exchange_status(cpprob_hip_ctx* c, int32_t* h_overflow, uint64_t*
     return 0;
 }
 
+static int infer_summary_impl(cpprob_hip_ctx* c, cpprob_hip_summary* out);
 int cpprob_hip_infer_summary(cpprob_hip_ctx* c, cpprob_hip_summary* out)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return infer_summary_impl(l, out); });
+}
+static int infer_summary_impl(cpprob_hip_ctx* c, cpprob_hip_summary* out)
 {
     if (!c || !out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2508,7 +2759,12 @@ static void fill_summary(const cpprob_hip_ctx* c, const StepCtrl& h, cpprob_hip_
     out->step_form = c->cfg.algorithm != CPPROB_HIP_ALG_SMC ? CPPROB_HIP_FORM_FLOAT : (c->fixed_mode ? CPPROB_HIP_FORM_FIXED : (c->counts_mode ? CPPROB_HIP_FORM_COUNTS : CPPROB_HIP_FORM_FLOAT));
     out->n_requantised = c->fixed_mode ? c->n_requantised : 0;
 }
+static int infer_results_impl(cpprob_hip_ctx* c, cpprob_hip_summary* out, double* h_stats, size_t n_doubles, double* h_ess, int32_t* h_resampled);
 int cpprob_hip_infer_results(cpprob_hip_ctx* c, cpprob_hip_summary* out, double* h_stats, size_t n_doubles, double* h_ess, int32_t* h_resampled)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return infer_results_impl(l, out, h_stats, n_doubles, h_ess, h_resampled); });
+}
+static int infer_results_impl(cpprob_hip_ctx* c, cpprob_hip_summary* out, double* h_stats, size_t n_doubles, double* h_ess, int32_t* h_resampled)
 {
     if (!c || !out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2550,7 +2806,12 @@ int cpprob_hip_infer_results(cpprob_hip_ctx* c, cpprob_hip_summary* out, double*
     return fail(c, CPPROB_HIP_ESTATE, "the run did not settle");
 }
 
+static int infer_stats_impl(cpprob_hip_ctx* c, double* h_stats, size_t n_doubles);
 int cpprob_hip_infer_stats(cpprob_hip_ctx* c, double* h_stats, size_t n_doubles)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return infer_stats_impl(l, h_stats, n_doubles); });
+}
+static int infer_stats_impl(cpprob_hip_ctx* c, double* h_stats, size_t n_doubles)
 {
     if (!c || !h_stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2565,17 +2826,34 @@ int cpprob_hip_infer_stats(cpprob_hip_ctx* c, double* h_stats, size_t n_doubles)
 int cpprob_hip_infer_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_doubles)
 {
     if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
+    c->lane_chain = false;
+    cpprob_hip_ctx* const l = c->is_lane ? c : lane_of_last(c);       // (same configuration: T and K are the context's)
+    if (!l->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
     const size_t need = 4 + (size_t)c->T * c->K;
     if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "d_out too small");
     HIP_TRY(c, hipSetDevice(c->device));
     const int ns = c->T * c->K;
-    hipLaunchKernelGGL(pack_results_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream, c->d_ctrl, c->d_stats, ns, d_out);
+    if (l != c) {
+        // the last run sits on a lane: the context's stream waits for it, and the lane's next run for this copy
+        if (!c->lane_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lane_ev, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->lane_ev, l->stream));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->lane_ev, 0));
+    }
+    hipLaunchKernelGGL(pack_results_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, c->stream, l->d_ctrl, l->d_stats, ns, d_out);
     HIP_TRY(c, hipGetLastError());
+    if (l != c) {
+        HIP_TRY(c, hipEventRecord(c->lane_ev, c->stream));
+        HIP_TRY(c, hipStreamWaitEvent(l->stream, c->lane_ev, 0));
+    }
     return 0;
 }
 
+static int infer_step_trace_impl(cpprob_hip_ctx* c, double* h_ess, int32_t* h_resampled);
 int cpprob_hip_infer_step_trace(cpprob_hip_ctx* c, double* h_ess, int32_t* h_resampled)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return infer_step_trace_impl(l, h_ess, h_resampled); });
+}
+static int infer_step_trace_impl(cpprob_hip_ctx* c, double* h_ess, int32_t* h_resampled)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2602,7 +2880,12 @@ static int copy_rows(cpprob_hip_ctx* c, void* h, const void* d, size_t elem, siz
     return 0;
 }
 
+static int copy_values_impl(cpprob_hip_ctx* c, void* h, size_t n_bytes);
 int cpprob_hip_copy_values(cpprob_hip_ctx* c, void* h, size_t n_bytes)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return copy_values_impl(l, h, n_bytes); });
+}
+static int copy_values_impl(cpprob_hip_ctx* c, void* h, size_t n_bytes)
 {
     if (!c || !h) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2620,7 +2903,12 @@ int cpprob_hip_copy_values(cpprob_hip_ctx* c, void* h, size_t n_bytes)
     return copy_rows(c, h, c->d_paths, vsz, (size_t)c->T, n_bytes, (size_t)c->ld);
 }
 
+static int copy_ancestors_impl(cpprob_hip_ctx* c, int32_t* h, size_t n_bytes);
 int cpprob_hip_copy_ancestors(cpprob_hip_ctx* c, int32_t* h, size_t n_bytes)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return copy_ancestors_impl(l, h, n_bytes); });
+}
+static int copy_ancestors_impl(cpprob_hip_ctx* c, int32_t* h, size_t n_bytes)
 {
     if (!c || !h) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2638,7 +2926,12 @@ int cpprob_hip_copy_ancestors(cpprob_hip_ctx* c, int32_t* h, size_t n_bytes)
     return 0;
 }
 
+static int copy_logw_impl(cpprob_hip_ctx* c, double* h, size_t n_bytes);
 int cpprob_hip_copy_logw(cpprob_hip_ctx* c, double* h, size_t n_bytes)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return copy_logw_impl(l, h, n_bytes); });
+}
+static int copy_logw_impl(cpprob_hip_ctx* c, double* h, size_t n_bytes)
 {
     if (!c || !h) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2659,7 +2952,12 @@ int cpprob_hip_copy_logw(cpprob_hip_ctx* c, double* h, size_t n_bytes)
     return copy_rows(c, h, c->d_logw[c->cur], sizeof(double), 1, n_bytes, (size_t)c->ld);
 }
 
+static int copy_paths_impl(cpprob_hip_ctx* c, void* h, size_t n_bytes);
 int cpprob_hip_copy_paths(cpprob_hip_ctx* c, void* h, size_t n_bytes)
+{
+    return lane_read(c, [&](cpprob_hip_ctx* l) { return copy_paths_impl(l, h, n_bytes); });
+}
+static int copy_paths_impl(cpprob_hip_ctx* c, void* h, size_t n_bytes)
 {
     if (!c || !h) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!c->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished run");
@@ -2667,7 +2965,7 @@ int cpprob_hip_copy_paths(cpprob_hip_ctx* c, void* h, size_t n_bytes)
     if (!c->keep) return fail(c, CPPROB_HIP_ESTATE, "the run kept no history (keep_history = 0): traces and ancestors do not exist; its statistics are the filtering ones");
     const size_t vsz = c->is_int ? sizeof(int32_t) : sizeof(double);
     // SIS: every trace is its own line -- the paths are the values (and a fused-read-out run keeps no linear weights to re-run the read-out on)
-    if (c->cfg.algorithm == CPPROB_HIP_ALG_SIS) return cpprob_hip_copy_values(c, h, n_bytes);
+    if (c->cfg.algorithm == CPPROB_HIP_ALG_SIS) return copy_values_impl(c, h, n_bytes);
     if (!c->d_paths) HIP_TRY(c, hipMalloc(&c->d_paths, (size_t)c->cap_T * c->cap_particles * vsz));
     dispatch_model(c, [&](auto m) { launch_smooth<decltype(m)>(c, true); });
     HIP_TRY(c, hipGetLastError());
@@ -2682,6 +2980,7 @@ int cpprob_hip_copy_paths(cpprob_hip_ctx* c, void* h, size_t n_bytes)
 
 int cpprob_hip_philox_blocks(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uint64_t draw, size_t n, uint32_t* d_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(philox_blocks_kernel, GRID1(n), seed, pid0, draw, (int64_t)n, d_out);
@@ -2691,6 +2990,7 @@ int cpprob_hip_philox_blocks(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, ui
 
 int cpprob_hip_draw_normal(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uint64_t draw, double mean, double sigma, size_t n, double* d_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(draw_normal_kernel, GRID1(n), seed, pid0, draw, mean, sigma, (int64_t)n, d_out);
@@ -2700,6 +3000,7 @@ int cpprob_hip_draw_normal(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uint
 
 int cpprob_hip_draw_uniform_smallint(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uint64_t draw, int64_t a, int64_t b, size_t n, int32_t* d_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (b < a) return fail(c, CPPROB_HIP_EINVAL, "uniform_smallint needs a <= b");
     if (n == 0) return 0;
@@ -2719,6 +3020,7 @@ static int make_dw(cpprob_hip_ctx* c, const double* w, int32_t k, DiscreteW& dw)
 
 int cpprob_hip_draw_discrete(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uint64_t draw, const double* h_w, int32_t k, size_t n, int32_t* d_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     DiscreteW dw;
     if (int rc = make_dw(c, h_w, k, dw)) return rc;
@@ -2730,6 +3032,7 @@ int cpprob_hip_draw_discrete(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, ui
 
 int cpprob_hip_draw_uniform_real(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uint64_t draw, double a, double b, size_t n, double* d_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(draw_uniform_real_kernel, GRID1(n), seed, pid0, draw, a, b, (int64_t)n, d_out);
@@ -2739,6 +3042,7 @@ int cpprob_hip_draw_uniform_real(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0
 
 int cpprob_hip_draw_poisson(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uint64_t draw, double mean, size_t n, int32_t* d_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!(mean >= 0.0)) return fail(c, CPPROB_HIP_EINVAL, "poisson needs mean >= 0");
     if (n == 0) return 0;
@@ -2749,6 +3053,7 @@ int cpprob_hip_draw_poisson(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uin
 
 int cpprob_hip_logpdf_normal(cpprob_hip_ctx* c, const double* x, const double* mean, const double* sigma, size_t n, double* out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(logpdf_normal_kernel, GRID1(n), x, mean, sigma, (int64_t)n, out);
@@ -2758,6 +3063,7 @@ int cpprob_hip_logpdf_normal(cpprob_hip_ctx* c, const double* x, const double* m
 
 int cpprob_hip_logpdf_uniform_real(cpprob_hip_ctx* c, const double* x, const double* a, const double* b, size_t n, double* out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(logpdf_uniform_real_kernel, GRID1(n), x, a, b, (int64_t)n, out);
@@ -2767,6 +3073,7 @@ int cpprob_hip_logpdf_uniform_real(cpprob_hip_ctx* c, const double* x, const dou
 
 int cpprob_hip_logpdf_poisson(cpprob_hip_ctx* c, const int32_t* x, const double* mean, size_t n, double* out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(logpdf_poisson_kernel, GRID1(n), x, mean, (int64_t)n, out);
@@ -2776,6 +3083,7 @@ int cpprob_hip_logpdf_poisson(cpprob_hip_ctx* c, const int32_t* x, const double*
 
 int cpprob_hip_logpdf_uniform_smallint(cpprob_hip_ctx* c, const int32_t* x, int64_t a, int64_t b, size_t n, double* out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(logpdf_smallint_kernel, GRID1(n), x, a, b, (int64_t)n, out);
@@ -2785,6 +3093,7 @@ int cpprob_hip_logpdf_uniform_smallint(cpprob_hip_ctx* c, const int32_t* x, int6
 
 int cpprob_hip_logpdf_discrete(cpprob_hip_ctx* c, const int32_t* x, const double* h_w, int32_t k, size_t n, double* out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     DiscreteW dw;
     if (int rc = make_dw(c, h_w, k, dw)) return rc;
@@ -2806,6 +3115,7 @@ __global__ void fix_weight_kernel(const double* __restrict__ x, int64_t n, doubl
 extern "C" {
 int cpprob_hip_fastmath(cpprob_hip_ctx* c, int32_t which, const double* d_x, size_t n, double* d_out0, double* d_out1)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (which < 0 || which > 3) return fail(c, CPPROB_HIP_EINVAL, "which: 0 log01, 1 sincospi02, 2 exp_nonpos, 3 fix_weight");
     if (!d_x || !d_out0 || (which == 1 && !d_out1)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
@@ -2818,6 +3128,7 @@ int cpprob_hip_fastmath(cpprob_hip_ctx* c, int32_t which, const double* d_x, siz
 
 int cpprob_hip_logsumexp_ess(cpprob_hip_ctx* c, const double* d_logw, size_t n, double* h_out3)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_logw || !h_out3) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (n == 0) { h_out3[0] = 0; h_out3[1] = 0; h_out3[2] = 0; return 0; }   // empty: value-initialised (empirical_distribution.hpp:131-133)
@@ -2994,6 +3305,7 @@ extern "C" {
 
 int cpprob_hip_readback_with_next_result(cpprob_hip_ctx* c, const void* d_src, void* h_dst, size_t bytes)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (bytes != 0 && (!d_src || !h_dst)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (bytes > ((size_t)1 << 20) || (bytes & 3)) return fail(c, CPPROB_HIP_EINVAL, "a read-back that rides a result's is a small one (<= 1 MiB, whole 4-byte words)");
@@ -3003,6 +3315,7 @@ int cpprob_hip_readback_with_next_result(cpprob_hip_ctx* c, const void* d_src, v
 
 int cpprob_hip_lineage_prepare(cpprob_hip_ctx* c, const int32_t* h_gen, int32_t H, int32_t T)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!h_gen || T < 1 || H < 1) return fail(c, CPPROB_HIP_EINVAL, "need h_gen, T >= 1 and H >= 1");
     return upload_first_rows(c, h_gen, H, T);
@@ -3011,6 +3324,7 @@ int cpprob_hip_lineage_prepare(cpprob_hip_ctx* c, const int32_t* h_gen, int32_t 
 int cpprob_hip_lineage_moments(cpprob_hip_ctx* c, const int32_t* d_anc, const int32_t* d_resampled, int32_t T, size_t n, const double* d_cols, const int32_t* h_gen, int32_t H,
                                const double* d_logw, double* h_out4)
 {
+    LANES_OWN(c);
     RideDisarm ride_guard{c};
     BB_PRELUDE(c);
     if (int rc = lineage_args_ok(c, d_anc, d_resampled, T, n, d_cols, h_gen, H, d_logw, h_out4)) return rc;
@@ -3028,6 +3342,7 @@ int cpprob_hip_lineage_moments(cpprob_hip_ctx* c, const int32_t* d_anc, const in
 int cpprob_hip_lineage_hist(cpprob_hip_ctx* c, const int32_t* d_anc, const int32_t* d_resampled, int32_t T, size_t n, const int32_t* d_cols, const int32_t* h_gen, int32_t H,
                             const double* d_logw, int32_t k, double* h_out, double* h_lse_ess)
 {
+    LANES_OWN(c);
     RideDisarm ride_guard{c};
     BB_PRELUDE(c);
     if (int rc = lineage_args_ok(c, d_anc, d_resampled, T, n, d_cols, h_gen, H, d_logw, h_out)) return rc;
@@ -3043,6 +3358,7 @@ int cpprob_hip_lineage_hist(cpprob_hip_ctx* c, const int32_t* d_anc, const int32
 
 int cpprob_hip_weighted_moments_columns(cpprob_hip_ctx* c, const double* d_x, size_t n_cols, size_t col_stride, const double* d_logw, size_t n, double* h_out4)
 {
+    LANES_OWN(c);
     RideDisarm ride_guard{c};
     BB_PRELUDE(c);
     if (!d_x || !d_logw || !h_out4) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
@@ -3061,6 +3377,7 @@ int cpprob_hip_weighted_moments_columns(cpprob_hip_ctx* c, const double* d_x, si
 int cpprob_hip_weighted_hist_columns(cpprob_hip_ctx* c, const int32_t* d_x, size_t n_cols, size_t col_stride, const double* d_logw, size_t n, int32_t k, double* h_out,
                                      double* h_lse_ess)
 {
+    LANES_OWN(c);
     RideDisarm ride_guard{c};
     BB_PRELUDE(c);
     if (!d_x || !d_logw || !h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
@@ -3077,6 +3394,7 @@ int cpprob_hip_weighted_hist_columns(cpprob_hip_ctx* c, const int32_t* d_x, size
 
 int cpprob_hip_weighted_moments(cpprob_hip_ctx* c, const double* d_x, const double* d_logw, size_t n, double* h_out4)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_x || !d_logw || !h_out4) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (n == 0) return fail(c, CPPROB_HIP_EINVAL, "empty distribution");
@@ -3090,6 +3408,7 @@ int cpprob_hip_weighted_moments(cpprob_hip_ctx* c, const double* d_x, const doub
 
 int cpprob_hip_weighted_hist(cpprob_hip_ctx* c, const int32_t* d_x, const double* d_logw, size_t n, int32_t k, double* h_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_x || !d_logw || !h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (k < 1 || k > 8) return fail(c, CPPROB_HIP_EINVAL, "need 1 <= k <= 8");
@@ -3103,6 +3422,7 @@ int cpprob_hip_weighted_hist(cpprob_hip_ctx* c, const int32_t* d_x, const double
 int cpprob_hip_resample(cpprob_hip_ctx* c, int32_t kind, const double* d_logw, size_t n_in, uint64_t seed, uint64_t step, uint64_t j0, size_t n_out,
                         uint64_t n_total_out, int32_t* d_anc)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_logw || !d_anc) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (n_in == 0) return fail(c, CPPROB_HIP_EINVAL, "cannot resample an empty population");
@@ -3133,6 +3453,7 @@ int cpprob_hip_resample(cpprob_hip_ctx* c, int32_t kind, const double* d_logw, s
 int cpprob_hip_smc_bookkeep(cpprob_hip_ctx* c, int32_t kind, const double* d_logw, size_t n, uint64_t seed, int32_t step, int32_t last, double ess_frac,
                             double* d_ess, int32_t* d_resampled, double* d_log_z, int32_t* d_anc)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_logw || !d_ess || !d_resampled || !d_log_z || !d_anc) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (n == 0 || n > (size_t)INT32_MAX - kTile) return fail(c, CPPROB_HIP_EINVAL, "population size out of range");
@@ -3211,12 +3532,14 @@ extern "C" {
 int cpprob_hip_smc_bookkeep_fixed(cpprob_hip_ctx* c, const double* d_logw, size_t n, uint64_t seed, int32_t step, int32_t last, double ess_frac,
                                   double* d_ess, int32_t* d_resampled, double* d_log_z, int32_t* d_anc)
 {
+    LANES_OWN(c);
     return cpprob_hip_smc_bookkeep_fixed_rs(c, CPPROB_HIP_RESAMPLE_SYSTEMATIC, d_logw, n, seed, step, last, ess_frac, d_ess, d_resampled, d_log_z, d_anc);
 }
 
 int cpprob_hip_smc_bookkeep_fixed_rs(cpprob_hip_ctx* c, int32_t kind, const double* d_logw, size_t n, uint64_t seed, int32_t step, int32_t last, double ess_frac,
                                      double* d_ess, int32_t* d_resampled, double* d_log_z, int32_t* d_anc)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (kind < CPPROB_HIP_RESAMPLE_SYSTEMATIC || kind > CPPROB_HIP_RESAMPLE_MULTINOMIAL) return fail(c, CPPROB_HIP_EINVAL, "unknown resampler");
     if (!d_logw || !d_ess || !d_resampled || !d_log_z || (!last && !d_anc)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
@@ -3386,11 +3709,13 @@ static int generic_begin(cpprob_hip_ctx* c, size_t n, int block, cpprob_hip_gene
 }
 int cpprob_hip_generic_begin(cpprob_hip_ctx* c, size_t n, cpprob_hip_generic_layout* out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     return generic_begin(c, n, kGenBlock, out);
 }
 int cpprob_hip_generic_begin_tiles(cpprob_hip_ctx* c, size_t n, cpprob_hip_generic_layout* out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     return generic_begin(c, n, kTile, out);
 }
@@ -3409,21 +3734,25 @@ static int generic_exact_passes(cpprob_hip_ctx* c, int32_t t, const double* d_lo
 }
 int cpprob_hip_generic_quantize(cpprob_hip_ctx* c, int32_t t, const double* d_logw, size_t n)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     return generic_exact_passes(c, t, d_logw, n, true, true, 0, 0.0);
 }
 int cpprob_hip_generic_max(cpprob_hip_ctx* c, int32_t t, const double* d_logw, size_t n)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     return generic_exact_passes(c, t, d_logw, n, true, false, 0, 0.0);
 }
 int cpprob_hip_generic_quantize_ref(cpprob_hip_ctx* c, int32_t t, const double* d_logw, size_t n, double ref)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     return generic_exact_passes(c, t, d_logw, n, false, true, 1, ref);
 }
 int cpprob_hip_generic_totals(cpprob_hip_ctx* c, int32_t t, size_t n, uint64_t* d_out3)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_out3 || t < 0) return fail(c, CPPROB_HIP_EINVAL, "bad argument");
     const int nb = (int)((n + (size_t)c->gen_block - 1) / (size_t)c->gen_block);
@@ -3437,6 +3766,7 @@ int cpprob_hip_generic_totals(cpprob_hip_ctx* c, int32_t t, size_t n, uint64_t* 
 
 int cpprob_hip_generic_finish(cpprob_hip_ctx* c, int32_t T, size_t n, double gap_limit, double* d_ess, int32_t* d_resampled, double* d_log_z, int32_t* d_flags)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_ess || !d_resampled || !d_log_z || !d_flags || T < 1) return fail(c, CPPROB_HIP_EINVAL, "bad argument");
     const int nb = (int)((n + (size_t)c->gen_block - 1) / (size_t)c->gen_block);
@@ -3455,6 +3785,7 @@ double cpprob_hip_systematic_offset(uint64_t seed, uint64_t step) { return host_
 int cpprob_hip_lineage_gather(cpprob_hip_ctx* c, const int32_t* d_anc, const int32_t* d_resampled, int32_t T, size_t n, const void* d_cols, int32_t is_int,
                               const int32_t* h_gen, int32_t H, void* d_out)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (!d_anc || !d_resampled || !d_cols || !h_gen || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (T < 1 || H < 0) return fail(c, CPPROB_HIP_EINVAL, "bad T / H");
@@ -3469,6 +3800,7 @@ int cpprob_hip_lineage_gather(cpprob_hip_ctx* c, const int32_t* d_anc, const int
 
 int cpprob_hip_gather_f64(cpprob_hip_ctx* c, const double* src, const int32_t* idx, size_t n, double* dst)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(gather_kernel<double>, GRID1(n), src, idx, (int64_t)n, dst);
@@ -3478,6 +3810,7 @@ int cpprob_hip_gather_f64(cpprob_hip_ctx* c, const double* src, const int32_t* i
 
 int cpprob_hip_gather_i32(cpprob_hip_ctx* c, const int32_t* src, const int32_t* idx, size_t n, int32_t* dst)
 {
+    LANES_OWN(c);
     BB_PRELUDE(c);
     if (n == 0) return 0;
     hipLaunchKernelGGL(gather_kernel<int32_t>, GRID1(n), src, idx, (int64_t)n, dst);
@@ -3487,6 +3820,7 @@ int cpprob_hip_gather_i32(cpprob_hip_ctx* c, const int32_t* src, const int32_t* 
 
 int cpprob_hip_profile_enable(cpprob_hip_ctx* c, int32_t on)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     c->profile = on != 0;
     return 0;
@@ -3494,6 +3828,7 @@ int cpprob_hip_profile_enable(cpprob_hip_ctx* c, int32_t on)
 
 int cpprob_hip_profile_read(cpprob_hip_ctx* c, double* h_ms, int64_t* h_calls, int32_t reset)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (auto& ep : c->ev_used) {
@@ -3524,6 +3859,7 @@ int cpprob_hip_batch_workspace_bytes(const cpprob_hip_batch_config* cfg, size_t 
 
 int cpprob_hip_batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const double* h_obs, size_t T)
 {
+    LANES_OWN(c);
     if (!c || !cfg || !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     std::string msg;
     if (int rc = batch_check(cfg, T, msg)) return fail(c, rc, msg);
@@ -3545,6 +3881,7 @@ int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg
 int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
                                     const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition)
 {
+    LANES_OWN(c);
     if (!c || !cfg || !h_T || !h_n || !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     std::string msg;
     BatchProblemsShape sh;
@@ -3575,6 +3912,7 @@ int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_co
 
 int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
 {
+    LANES_OWN(c);
     if (!c || !h_seeds) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
@@ -3608,6 +3946,7 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
 
 int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, double* h_stats, size_t n_doubles, double* h_ess, int32_t* h_resampled)
 {
+    LANES_OWN(c);
     if (!c || !h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
@@ -3643,6 +3982,7 @@ int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, doubl
 
 int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_doubles)
 {
+    LANES_OWN(c);
     if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
@@ -3659,6 +3999,7 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_d
 
 int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_values, int32_t* h_anc, double* h_logw)
 {
+    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");

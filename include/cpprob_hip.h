@@ -13,7 +13,7 @@
  *   - Every function returns 0 on success, a negative CPPROB_HIP_E* code otherwise;
  *     cpprob_hip_last_error(ctx) then describes the failure.  Library code never exits
  *     (the reference's exit()/terminate() paths, SURVEY section 5, are not reproduced).
- *   - A context owns one device, one HIP stream and all device buffers of a run.  No process
+ *   - A context owns one device, one HIP stream (plus those of its run lanes: cpprob_hip_infer_lanes) and all device buffers of a run.  No process
  *     globals (the reference's State::state_, StateInfer::trace_, TraceInfer::ids_predict_,
  *     src/cpprob/state.cpp:20-21,148-155, are per-context here).  One run at a time per context;
  *     contexts are independent and may live on different threads.
@@ -138,6 +138,7 @@ typedef struct cpprob_hip_config {
 #define CPPROB_HIP_FLAG_MULTINOMIAL_LITERAL 128u /* multinomial resampling: ancestor of output j = min{k : C_k > floor(u_j C_N)}, one search per output */
 #define CPPROB_HIP_FLAG_SEPARATE_TRACE_READOUT 1024u /* prefix-count form, a population of its own (A/B): the read-out of the trace words (or of a
                                                         filtering-only run's final generation) as a launch after the last step, not folded into it */
+#define CPPROB_HIP_FLAG_SERIAL_RUNS 2048u        /* run lanes (below, cpprob_hip_infer_lanes) off (A/B): every cpprob_hip_infer_run of this context on its one stream */
 
 /* Posterior summary of a finished run -- what StatsPrinter prints
  * (include/cpprob/postprocess/stats_printer.hpp:42-79) plus SMC diagnostics. */
@@ -171,7 +172,9 @@ int cpprob_hip_device_count(void);
 int cpprob_hip_create(int device, cpprob_hip_ctx** out);
 void cpprob_hip_destroy(cpprob_hip_ctx* ctx);
 const char* cpprob_hip_last_error(const cpprob_hip_ctx* ctx); /* ctx may be NULL: global message */
-/* The context's hipStream_t, for event timing / interop by the caller. */
+/* The context's hipStream_t, for event timing / interop by the caller.  From this call on every run of the context is enqueued on
+ * this stream alone (no run lanes: cpprob_hip_infer_lanes), until the context is destroyed -- also for a caller that only wanted to time
+ * with events.  Waits for lanes already used; NULL (and cpprob_hip_last_error) if their work failed. */
 void* cpprob_hip_stream(cpprob_hip_ctx* ctx);
 int cpprob_hip_sync(cpprob_hip_ctx* ctx);
 
@@ -197,6 +200,45 @@ int cpprob_hip_infer_results(cpprob_hip_ctx* ctx, cpprob_hip_summary* out, doubl
 int cpprob_hip_set_hmm(cpprob_hip_ctx* ctx, int32_t k, const double* h_means, const double* h_transition);
 int cpprob_hip_infer_begin(cpprob_hip_ctx* ctx, const cpprob_hip_config* cfg, const double* h_observes, size_t n_observes);
 int cpprob_hip_infer_run(cpprob_hip_ctx* ctx, uint64_t run_index);
+/* Run lanes.  One run is a chain of dependent launches that leaves most of the device idle; runs that differ only in run_index are
+ * independent.  A context therefore owns up to 3 LANES: lane 0 is the context itself, the further ones are created and begun by the
+ * library the first time they are needed, each with its own stream and its own complete workspace (same configuration, observes and
+ * cpprob_hip_set_hmm table), so that runs enqueued back to back overlap on the device.  Each run computes what it computes alone.
+ *   which lane   a rule of the call sequence alone (never of timing): a cpprob_hip_infer_run that DIRECTLY follows another
+ *                cpprob_hip_infer_run of this context goes to the next lane, round robin; any other entry point in between (a read,
+ *                cpprob_hip_sync, a building block ...; not cpprob_hip_infer_lanes and cpprob_hip_last_error) ends the sequence: the
+ *                next run goes where the last one ran (lane 0 after a begin).  run -> results -> run -> results never leaves lane 0 and
+ *                allocates nothing.
+ *   reads        cpprob_hip_infer_summary / _stats / _results / _step_trace, cpprob_hip_copy_*, cpprob_hip_smc_first_bad_generation and
+ *                cpprob_hip_filter_masses act on the lane of the LAST run (the fixed-point check and repair run there): they return the
+ *                last run's results, as before; earlier runs' results are overwritten lane by lane, as they were on one stream.
+ *                cpprob_hip_infer_results_device enqueues on the context's own stream, behind an event recorded after that lane's run.
+ *   waits        cpprob_hip_sync waits for every lane; cpprob_hip_destroy frees them; cpprob_hip_infer_begin and cpprob_hip_set_hmm
+ *                invalidate them (begun again at their next use, allocations reused where they suffice).  Every other entry point --
+ *                the step protocol, cpprob_hip_generic_*, the building blocks, cpprob_hip_batch_*, cpprob_hip_exchange_*, profiling --
+ *                first waits for every lane and then works on the context itself, as before.
+ *   memory       every further lane holds what the context's begin allocated (*lane_bytes); together at most a quarter of the device
+ *                memory that was free without them (hipMemGetInfo, asked before allocating).
+ *   serial       runs stay on the context's one stream -- after waiting for lanes already used -- when (*serial_reason):
+ *                STREAM  cpprob_hip_stream was called: a handed-out stream promises stream order; holds until destroy;
+ *                PROFILE cpprob_hip_profile_enable is on (the per-class events are stream-ordered);
+ *                SHARD   the context holds a shard of a joint population (n_global != n_particles) or is in the exchange scope;
+ *                FLAG    CPPROB_HIP_FLAG_SERIAL_RUNS;
+ *                MEMORY  a further lane did not fit (that lane is freed, no error is returned); holds until destroy;
+ *                SIZE    more than 10240 tiles of 1024 particles (~1.05 10^7): a launch of that size fills the device by itself and the
+ *                        measured gain falls inside the run-to-run spread (profiles/r11_notes.md).
+ *   several contexts   a process opens four hardware queues: three lanes fill them.  Two contexts that both use lanes still gain
+ *                (0.075 ms per hmm<16> run of 10^6 particles against 0.083 without); THREE OR MORE CONTEXTS KEPT IN FLIGHT AT ONCE lose
+ *                about 10 % against plain ones (0.077-0.083 against 0.070): begin them with CPPROB_HIP_FLAG_SERIAL_RUNS.
+ * depth = lanes begun with the configuration in force (1: the context alone), last_lane = lane of the last run, lane_bytes = device
+ * bytes of the further lanes' population-sized arrays (weights, particle store, ancestors: all but a few KB of what they hold), serial_reason = 0 or CPPROB_HIP_SERIAL_*; any pointer may be NULL.  Pure introspection. */
+#define CPPROB_HIP_SERIAL_STREAM 1
+#define CPPROB_HIP_SERIAL_PROFILE 2
+#define CPPROB_HIP_SERIAL_SHARD 3
+#define CPPROB_HIP_SERIAL_FLAG 4
+#define CPPROB_HIP_SERIAL_MEMORY 5
+#define CPPROB_HIP_SERIAL_SIZE 6
+int cpprob_hip_infer_lanes(cpprob_hip_ctx* ctx, int32_t* depth, int32_t* last_lane, uint64_t* lane_bytes, int32_t* serial_reason);
 int cpprob_hip_infer_summary(cpprob_hip_ctx* ctx, cpprob_hip_summary* out);
 int cpprob_hip_infer_stats(cpprob_hip_ctx* ctx, double* h_stats, size_t n_doubles);
 /* The same results left ON THE DEVICE, stream-ordered, no host synchronisation: d_out (device, caller-owned, at least
