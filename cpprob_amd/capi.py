@@ -11,6 +11,8 @@ ALG_SIS, ALG_SMC = 2, 4
 MODEL_GAUSSIAN_UNKNOWN_MEAN, MODEL_GAUSSIAN_README, MODEL_LINEAR_GAUSSIAN_1D, MODEL_HMM3, MODEL_GAUSSIAN_2D_UNKNOWN_MEAN, MODEL_HMM_TABLE = 0, 1, 2, 3, 4, 5
 RESAMPLE_SYSTEMATIC, RESAMPLE_STRATIFIED, RESAMPLE_MULTINOMIAL = 0, 1, 2
 SCOPE_GLOBAL, SCOPE_ISLAND, SCOPE_EXCHANGE = 0, 1, 2
+VARIATE_SMALLINT, VARIATE_DISCRETE, VARIATE_UNIFORM_REAL, VARIATE_POISSON, VARIATE_NORMAL = 0, 1, 2, 3, 4   # cpprob_hip_variate_from_bits
+POISSON_MAX_MEAN = 1.0e4                      # CPPROB_HIP_POISSON_MAX_MEAN: draw_poisson refuses a larger mean
 # cpprob_hip_config::flags (A/B forms; 0 = the measured optimum)
 FLAG_FLOATING_POINT_STEP, FLAG_NO_SKIP_ROWS, FLAG_SIS_PER_TILE, FLAG_SIS_SEPARATE_READOUT, FLAG_WREL_STORED, FLAG_FP_TILE_PARTIALS, FLAG_WALK_READOUT = 1, 2, 4, 8, 16, 32, 64
 FLAG_MULTINOMIAL_LITERAL, FLAG_REPEAT_IN_FLOATING_POINT, FLAG_PAIRED_STEP_LAUNCH = 128, 256, 512
@@ -34,7 +36,7 @@ SYMBOLS = [
     "cpprob_hip_draw_discrete", "cpprob_hip_draw_uniform_real", "cpprob_hip_draw_poisson", "cpprob_hip_logpdf_normal", "cpprob_hip_logpdf_uniform_real",
     "cpprob_hip_logpdf_poisson", "cpprob_hip_logpdf_uniform_smallint", "cpprob_hip_logpdf_discrete", "cpprob_hip_logsumexp_ess",
     "cpprob_hip_weighted_moments", "cpprob_hip_weighted_hist", "cpprob_hip_weighted_moments_columns", "cpprob_hip_weighted_hist_columns", "cpprob_hip_resample", "cpprob_hip_smc_bookkeep", "cpprob_hip_smc_bookkeep_fixed", "cpprob_hip_smc_bookkeep_fixed_rs", "cpprob_hip_generic_begin", "cpprob_hip_generic_begin_tiles", "cpprob_hip_generic_quantize", "cpprob_hip_generic_max", "cpprob_hip_generic_quantize_ref", "cpprob_hip_generic_totals", "cpprob_hip_generic_finish", "cpprob_hip_systematic_offset", "cpprob_hip_lineage_gather", "cpprob_hip_lineage_prepare", "cpprob_hip_readback_with_next_result", "cpprob_hip_lineage_moments", "cpprob_hip_lineage_hist", "cpprob_hip_gather_f64",
-    "cpprob_hip_gather_i32", "cpprob_hip_profile_enable", "cpprob_hip_profile_read", "cpprob_hip_fastmath",
+    "cpprob_hip_gather_i32", "cpprob_hip_profile_enable", "cpprob_hip_profile_read", "cpprob_hip_fastmath", "cpprob_hip_variate_from_bits",
     "cpprob_hip_batch_workspace_bytes", "cpprob_hip_batch_begin", "cpprob_hip_batch_run", "cpprob_hip_batch_results", "cpprob_hip_batch_results_device",
     "cpprob_hip_batch_copy_store", "cpprob_hip_batch_problems_workspace_bytes", "cpprob_hip_batch_begin_problems",
 ]
@@ -211,6 +213,7 @@ def load_library(path=None):
         "cpprob_hip_logpdf_uniform_smallint": (C.c_int, [vp, vp, i64, i64, sz, vp]),
         "cpprob_hip_logpdf_discrete": (C.c_int, [vp, vp, C.POINTER(dbl), i32, sz, vp]),
         "cpprob_hip_fastmath": (C.c_int, [vp, i32, vp, sz, vp, vp]),
+        "cpprob_hip_variate_from_bits": (C.c_int, [vp, i32, C.POINTER(dbl), i32, vp, sz, vp, vp]),
         "cpprob_hip_logsumexp_ess": (C.c_int, [vp, vp, sz, C.POINTER(dbl)]),
         "cpprob_hip_weighted_moments": (C.c_int, [vp, vp, vp, sz, C.POINTER(dbl)]),
         "cpprob_hip_weighted_hist": (C.c_int, [vp, vp, vp, sz, i32, C.POINTER(dbl)]),
@@ -581,6 +584,12 @@ class Engine:
     def fastmath(self, which, x, out0, out1=None):
         """which: 0 log01, 1 sincospi02 (out0 = sin, out1 = cos), 2 exp_nonpos, 3 fix_weight against reference 0; torch float64 tensors on this device."""
         self._chk(self.L.cpprob_hip_fastmath(self.h, int(which), _dptr(x), x.numel(), _dptr(out0), _dptr(out1)))
+
+    def variate_from_bits(self, which, params, blocks, out0, out1=None):
+        """The library's variate generators on chosen Philox blocks: blocks is an [n, 4] tensor of 32-bit words, which one of VARIATE_*,
+        params its parameters ((a, b), the weights, (a, b), (mean,), ()); float64 results in out0 (and out1: normal's second output)."""
+        p = (C.c_double * max(1, len(params)))(*params)
+        self._chk(self.L.cpprob_hip_variate_from_bits(self.h, int(which), p, len(params), _dptr(blocks), blocks.numel() // 4, _dptr(out0), _dptr(out1)))
 
     def logsumexp_ess(self, logw):
         out = (C.c_double * 3)()

@@ -3003,15 +3003,26 @@ int cpprob_hip_draw_uniform_smallint(cpprob_hip_ctx* c, uint64_t seed, uint64_t 
     LANES_OWN(c);
     BB_PRELUDE(c);
     if (b < a) return fail(c, CPPROB_HIP_EINVAL, "uniform_smallint needs a <= b");
+    if (a < INT32_MIN || b > INT32_MAX) return fail(c, CPPROB_HIP_EINVAL, "uniform_smallint writes int32: a and b must fit");
     if (n == 0) return 0;
     hipLaunchKernelGGL(draw_smallint_kernel, GRID1(n), seed, pid0, draw, a, b, (int64_t)n, d_out);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }
 
+// what cpprob_hip_set_hmm asks of a transition row: the generator divides by the total
+static int check_weights(cpprob_hip_ctx* c, const double* w, int32_t k)
+{
+    double tot = 0.0;
+    for (int i = 0; i < k; ++i) { if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(c, CPPROB_HIP_EINVAL, "discrete: weights must be finite and >= 0"); tot += w[i]; }
+    if (!(tot > 0.0) || !std::isfinite(tot)) return fail(c, CPPROB_HIP_EINVAL, "discrete: the weights' total must be positive and finite");
+    return 0;
+}
+
 static int make_dw(cpprob_hip_ctx* c, const double* w, int32_t k, DiscreteW& dw)
 {
     if (!w || k < 1 || k > 8) return fail(c, CPPROB_HIP_EINVAL, "discrete: need 1 <= k <= 8 weights");
+    if (int rc = check_weights(c, w, k)) return rc;
     std::memset(&dw, 0, sizeof dw);
     for (int i = 0; i < k; ++i) dw.w[i] = w[i];
     dw.k = k;
@@ -3044,7 +3055,7 @@ int cpprob_hip_draw_poisson(cpprob_hip_ctx* c, uint64_t seed, uint64_t pid0, uin
 {
     LANES_OWN(c);
     BB_PRELUDE(c);
-    if (!(mean >= 0.0)) return fail(c, CPPROB_HIP_EINVAL, "poisson needs mean >= 0");
+    if (!(mean >= 0.0 && mean <= CPPROB_HIP_POISSON_MAX_MEAN)) return fail(c, CPPROB_HIP_EINVAL, "poisson needs 0 <= mean <= CPPROB_HIP_POISSON_MAX_MEAN");
     if (n == 0) return 0;
     hipLaunchKernelGGL(draw_poisson_kernel, GRID1(n), seed, pid0, draw, mean, (int64_t)n, d_out);
     HIP_TRY(c, hipGetLastError());
@@ -3122,6 +3133,34 @@ int cpprob_hip_fastmath(cpprob_hip_ctx* c, int32_t which, const double* d_x, siz
     if (n == 0) return 0;
     if (which == 3) hipLaunchKernelGGL(fix_weight_kernel, GRID1(n), d_x, (int64_t)n, d_out0);
     else hipLaunchKernelGGL(fastmath_kernel, GRID1(n), (int)which, d_x, (int64_t)n, d_out0, d_out1);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+static_assert(CPPROB_HIP_POISSON_MAX_MEAN == kPoissonMaxMean, "the header documents the generator's limit");
+int cpprob_hip_variate_from_bits(cpprob_hip_ctx* c, int32_t which, const double* h_params, int32_t n_params, const uint32_t* d_blocks, size_t n,
+                                 double* d_out0, double* d_out1)
+{
+    LANES_OWN(c);
+    BB_PRELUDE(c);
+    static const int32_t want[5] = {2, 0, 2, 1, 0};    // parameters per generator (discrete: 1 .. 8 weights)
+    if (which < 0 || which > CPPROB_HIP_VARIATE_NORMAL) return fail(c, CPPROB_HIP_EINVAL, "which: 0 uniform_smallint, 1 discrete, 2 uniform_real, 3 poisson, 4 normal");
+    if (which == CPPROB_HIP_VARIATE_DISCRETE ? (n_params < 1 || n_params > 8) : n_params != want[which]) return fail(c, CPPROB_HIP_EINVAL, "wrong number of parameters");
+    if ((n_params && !h_params) || !d_blocks || !d_out0 || (which == CPPROB_HIP_VARIATE_NORMAL && !d_out1)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    VariateParams vp;
+    std::memset(&vp, 0, sizeof vp);
+    for (int i = 0; i < n_params; ++i) vp.p[i] = h_params[i];
+    vp.k = n_params;
+    if (which == CPPROB_HIP_VARIATE_SMALLINT) {
+        const double a = vp.p[0], b = vp.p[1];
+        if (!(std::fabs(a) <= 0x1p53 && std::fabs(b) <= 0x1p53) || a != std::floor(a) || b != std::floor(b) || b < a || b - a > 4294967295.0)
+            return fail(c, CPPROB_HIP_EINVAL, "uniform_smallint needs integers a <= b with b - a < 2^32");
+    }
+    else if (which == CPPROB_HIP_VARIATE_DISCRETE) { if (int rc = check_weights(c, vp.p, n_params)) return rc; }
+    else if (which == CPPROB_HIP_VARIATE_POISSON && !(vp.p[0] >= 0.0 && vp.p[0] <= CPPROB_HIP_POISSON_MAX_MEAN))
+        return fail(c, CPPROB_HIP_EINVAL, "poisson needs 0 <= mean <= CPPROB_HIP_POISSON_MAX_MEAN");
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(variate_from_bits_kernel, GRID1(n), (int)which, vp, d_blocks, (int64_t)n, d_out0, d_out1);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }

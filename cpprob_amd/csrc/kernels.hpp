@@ -1994,6 +1994,26 @@ __global__ void fastmath_kernel(int which, const double* __restrict__ x, int64_t
     else out0[i] = exp_nonpos(x[i]);
 }
 
+// The variate generators of cpprob/detail/rng.hpp on caller-given Philox blocks instead of (seed, particle, ordinal): element i applies the
+// library's own function to block i.  which: 0 uniform_smallint{p[0], p[1]} on word 0, 1 discrete{p[0..k)} on word 0, 2 uniform_real{p[0], p[1]}
+// and 3 poisson{p[0]} on the 53 bits of words 0 and 1, 4 standard normal on all four (out0 = x, out1 = y).  Integers come back as doubles.
+struct VariateParams { double p[8]; int k; };
+__global__ void variate_from_bits_kernel(int which, VariateParams vp, const uint32_t* __restrict__ blocks, int64_t n, double* __restrict__ out0,
+                                         double* __restrict__ out1)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32x4 r{blocks[4 * i], blocks[4 * i + 1], blocks[4 * i + 2], blocks[4 * i + 3]};
+    if (which == 0) {
+        const int64_t a = (int64_t)vp.p[0], b = (int64_t)vp.p[1];
+        out0[i] = (double)((int64_t)smallint_from_word(r.x, 0, (uint64_t)(b - a)) + a);
+    }
+    else if (which == 1) out0[i] = (double)discrete_from_u_dyn(u01_32(r.x), vp.p, vp.k);
+    else if (which == 2) out0[i] = uniform_real_from_u(u01_53(r.x, r.y), vp.p[0], vp.p[1]);
+    else if (which == 3) out0[i] = (double)poisson_from_u(u01_53(r.x, r.y), vp.p[0]);
+    else { double x, y; box_muller(r, x, y); out0[i] = x; out1[i] = y; }
+}
+
 template <class T>
 __global__ void gather_kernel(const T* __restrict__ src, const int32_t* __restrict__ idx, int64_t n, T* __restrict__ dst)
 {

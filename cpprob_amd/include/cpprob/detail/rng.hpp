@@ -133,19 +133,49 @@ __device__ __forceinline__ uint32_t discrete_from_u_dyn(double u, const double* 
     return idx;
 }
 
-// boost::random::uniform_real_distribution<>{a, b}(rng)
+// boost::random::uniform_real_distribution<>{a, b}(rng): a + (b - a) u on [a, b), product and sum rounded once (correctly rounded where
+// b - a is exact).  The sum can round up to b (a = 1, b = 2, u = 1 - 2^-53: 2 - 2^-53 is a tie, and ties go to even); Boost's generator
+// rejects such a value, this one returns the largest double below b.
+__device__ __forceinline__ double uniform_real_from_u(double u, double a, double b)
+{
+    const double x = fma(b - a, u, a);
+    return (x >= b && a < b) ? nextafter(b, a) : x;
+}
 __device__ __forceinline__ double draw_uniform_real(uint64_t seed, uint64_t pid, uint64_t draw, double a, double b)
 {
-    return a + (b - a) * draw_u01_53(seed, pid, draw);
+    return uniform_real_from_u(draw_u01_53(seed, pid, draw), a, b);
 }
 
-// boost::random::poisson_distribution<>{mean}(rng): inversion by sequential search on one 53-bit uniform
-// (k = 0; p = F = exp(-mean); while u > F: ++k, p *= mean / k, F += p).  Exact law; cost O(mean).
+// boost::random::poisson_distribution<>{mean}(rng): inversion of one 53-bit uniform, summed outwards from the mode m = floor(mean) on
+// weights relative to the mode's (t_m = 1, t_{k+1} = t_k mean / (k+1), t_{k-1} = t_k k / mean): no exp(-mean) to underflow or to lose
+// bits, O(sqrt(mean)) terms.  Pass 1 sums the weights below the mode downwards (A), then A and those from the mode upwards (S), each
+// side until a term no longer changes its sum; pass 2 walks the same terms for the least k whose cumulative weight reaches u S and
+// never leaves [lo, hi], the terms pass 1 added, so it ends for every u.  Plain IEEE + - * /, none contracted: the CPU oracle
+// restates it bit for bit.  The computed CDF is within (2 W + 8 sqrt(mean) + 16) 2^-53 of the exact one, W the number of terms added
+// (tests/variate_cases.py derives it): below 2^-40 up to kPoissonMaxMean.  A mean outside [0, kPoissonMaxMean] (NaN too) is
+// clamped into it -- the C entry refuses one; the law there is unspecified.
+constexpr double kPoissonMaxMean = 1.0e4;
 __device__ __forceinline__ int64_t poisson_from_u(double u, double mean)
 {
-    int64_t k = 0;
-    double p = exp(-mean), F = p;
-    while (u > F && k < 100000) { ++k; p *= mean / (double)k; F += p; }
+#pragma clang fp contract(off)
+    mean = fmin(fmax(mean, 0.0), kPoissonMaxMean);
+    const int64_t m = (int64_t)mean;
+    double A = 0.0, t = 1.0;
+    int64_t lo = m, hi = m;                               // the terms added: [lo, hi]
+    while (lo > 0) { t *= (double)lo / mean; if (A + t == A) break; A += t; --lo; }
+    double S = A;
+    t = 1.0;
+    for (;;) { S += t; t *= mean / (double)(hi + 1); if (S + t == S) break; ++hi; }
+    const double T = u * S;
+    int64_t k = m;
+    t = 1.0;
+    if (T > A) {                                          // at or above the mode: C = cumulative weight of [lo, k]
+        double C = A + t;
+        while (T > C && k < hi) { ++k; t *= mean / (double)k; C += t; }
+    } else {                                              // below it: C = cumulative weight of [lo, k - 1]
+        double C = A;
+        while (T <= C && k > lo) { t *= (double)k / mean; C -= t; --k; }
+    }
     return k;
 }
 __device__ __forceinline__ int64_t draw_poisson(uint64_t seed, uint64_t pid, uint64_t draw, double mean)

@@ -550,7 +550,15 @@ int cpprob_hip_draw_normal(cpprob_hip_ctx* ctx, uint64_t seed, uint64_t pid0, ui
 int cpprob_hip_draw_uniform_smallint(cpprob_hip_ctx* ctx, uint64_t seed, uint64_t pid0, uint64_t draw, int64_t a, int64_t b, size_t n, int32_t* d_out);
 int cpprob_hip_draw_discrete(cpprob_hip_ctx* ctx, uint64_t seed, uint64_t pid0, uint64_t draw, const double* h_weights, int32_t k, size_t n, int32_t* d_out);
 int cpprob_hip_draw_uniform_real(cpprob_hip_ctx* ctx, uint64_t seed, uint64_t pid0, uint64_t draw, double a, double b, size_t n, double* d_out);
-/* poisson: inversion by sequential search on the particle's 53-bit uniform (exact law, cost O(mean)) */
+/* The laws are pinned to the exact quantile functions at the particle's exact uniform (tests/test_gpu_variates.py): uniform_smallint
+ * (a and b must fit int32) and discrete (weights finite and >= 0, total positive and finite; CPPROB_HIP_EINVAL otherwise) are the exact
+ * quantile; uniform_real is one of the two doubles next to a + (b - a) u and always in [a, b); normal is within 3 2^-52 relative of
+ * sqrt(-2 ln u) sin / cos(pi w).
+ * poisson: inversion of the particle's 53-bit uniform u, summed outwards from the mode in O(sqrt(mean)) terms.  For 0 <= mean <=
+ * CPPROB_HIP_POISSON_MAX_MEAN the result is the exact quantile at some u' within (2 W + 8 sqrt(mean) + 16) 2^-53 of u, W the number of
+ * terms summed (about 18 sqrt(mean); 1762 at 10^4): below 2^-40; it never exceeds the exact quantile of 1 - 2^-54.  A mean above the
+ * limit, negative or NaN is refused with CPPROB_HIP_EINVAL (the device function clamps it and terminates; its law there is unspecified). */
+#define CPPROB_HIP_POISSON_MAX_MEAN 1.0e4
 int cpprob_hip_draw_poisson(cpprob_hip_ctx* ctx, uint64_t seed, uint64_t pid0, uint64_t draw, double mean, size_t n, int32_t* d_out);
 
 /* logpdf functors (include/cpprob/distributions/utils_*.hpp), elementwise. */
@@ -566,6 +574,20 @@ int cpprob_hip_logpdf_discrete(cpprob_hip_ctx* ctx, const int32_t* d_x, const do
  * (0, 2] (d_out0 = sin(pi x), d_out1 = cos(pi x)), 2 exp_nonpos on [-745, 0]; 3: the fixed-point weight min(rint(exp(x) 2^32), 2^32 - 1)
  * of a log-weight x <= 0 against the reference 0 (fixed_mass.hpp: fix_weight), as a double.  Unit-parity surface: tests sweep the domain edges. */
 int cpprob_hip_fastmath(cpprob_hip_ctx* ctx, int32_t which, const double* d_x, size_t n, double* d_out0, double* d_out1);
+
+/* The variate generators above on chosen bits: element i applies the library's own generator function to the Philox block
+ * d_blocks[4*i .. 4*i+3] instead of the block of (seed, particle, ordinal), so that tests reach inputs no seed does (the top uniform has
+ * probability 2^-53).  h_params (host, n_params doubles): SMALLINT {a, b} (integers, b - a < 2^32) on word 0; DISCRETE 1 .. 8 weights on
+ * word 0; UNIFORM_REAL {a, b} and POISSON {mean} on the 53 bits of words 0 and 1 (lo | (hi >> 11) << 32); NORMAL none, all four words,
+ * d_out0 = s sin(pi w), d_out1 = s cos(pi w) (d_out1 is used by NORMAL alone).  Integer results are written as doubles.  Weights and
+ * means are refused as by the draw entries.  Unit-parity surface: the draw entries and the models do not go through it. */
+#define CPPROB_HIP_VARIATE_SMALLINT 0
+#define CPPROB_HIP_VARIATE_DISCRETE 1
+#define CPPROB_HIP_VARIATE_UNIFORM_REAL 2
+#define CPPROB_HIP_VARIATE_POISSON 3
+#define CPPROB_HIP_VARIATE_NORMAL 4
+int cpprob_hip_variate_from_bits(cpprob_hip_ctx* ctx, int32_t which, const double* h_params, int32_t n_params, const uint32_t* d_blocks, size_t n,
+                                 double* d_out0, double* d_out1);
 
 /* EmpiricalDistribution (include/cpprob/postprocess/empirical_distribution.hpp):
  * h_out[0] = max, [1] = logsumexp (:125-143), [2] = ESS = (sum W^2)^-1. */

@@ -158,11 +158,17 @@ ORC_API double orc_draw_normal(uint64_t seed, uint64_t pid, uint64_t draw, doubl
     return mean + sigma * orc_draw_std_normal(seed, pid, draw);
 }
 
+/* The generators as functions of a block's bits (cpprob_hip_variate_from_bits on the device); the by-seed forms below apply them to
+ * the particle's word or word pair. */
 /* uniform_smallint<size_t>{a, b}: a + floor(word * range / 2^32) */
-ORC_API uint64_t orc_draw_smallint(uint64_t seed, uint64_t pid, uint64_t draw, uint64_t a, uint64_t b)
+ORC_API uint64_t orc_smallint_from_bits(uint32_t w, uint64_t a, uint64_t b)
 {
     uint64_t range = b - a + 1;
-    return a + (((uint64_t)orc_draw_word(seed, pid, draw) * range) >> 32);
+    return a + (((uint64_t)w * range) >> 32);
+}
+ORC_API uint64_t orc_draw_smallint(uint64_t seed, uint64_t pid, uint64_t draw, uint64_t a, uint64_t b)
+{
+    return orc_smallint_from_bits(orc_draw_word(seed, pid, draw), a, b);
 }
 
 /* discrete_distribution over k weights: inverse CDF on the normalised cumulative
@@ -179,26 +185,57 @@ static uint64_t discrete_from_u(double u, const double *w, int k)
     }
     return idx;
 }
-
+ORC_API uint64_t orc_discrete_from_bits(uint32_t word, const double *w, int k) { return discrete_from_u(orc_u01_32(word), w, k); }
 ORC_API uint64_t orc_draw_discrete(uint64_t seed, uint64_t pid, uint64_t draw, const double *w, int k)
 {
-    return discrete_from_u(orc_u01_32(orc_draw_word(seed, pid, draw)), w, k);
+    return orc_discrete_from_bits(orc_draw_word(seed, pid, draw), w, k);
 }
 
-/* uniform_real_distribution{a,b}: a + (b-a)*u, u in [0,1) from 53 bits */
+/* uniform_real_distribution{a,b}: a + (b-a)*u, u in [0,1) from 53 bits, product and sum rounded once; a sum that rounds up to b
+ * (a < b) becomes the largest double below b: the law is [a, b) */
+ORC_API double orc_uniform_real_from_bits(uint32_t lo, uint32_t hi, double a, double b)
+{
+    double x = fma(b - a, orc_u01_53(lo, hi), a);
+    return (x >= b && a < b) ? nextafter(b, a) : x;
+}
 ORC_API double orc_draw_uniform_real(uint64_t seed, uint64_t pid, uint64_t draw, double a, double b)
 {
-    return a + (b - a) * orc_draw_u01_53(seed, pid, draw);
+    uint32_t r[4];
+    orc_draw_block(seed, pid >> 1, draw, r);
+    return (pid & 1) ? orc_uniform_real_from_bits(r[2], r[3], a, b) : orc_uniform_real_from_bits(r[0], r[1], a, b);
 }
 
-/* poisson_distribution{mean}: inversion by sequential search on the 53-bit uniform */
+/* poisson_distribution{mean}: inversion of the 53-bit uniform, summed outwards from the mode m = floor(mean) on weights relative to the
+ * mode's: pass 1 sums the terms below the mode downwards (A), then A and those from the mode upwards (S), each side until a term no
+ * longer changes its sum; pass 2 walks the same terms [lo, hi] for the least k whose cumulative weight reaches u S.  The statements of
+ * cpprob/detail/rng.hpp's poisson_from_u, none contracted there or here (-ffp-contract=off): the same bits. */
+#define ORC_POISSON_MAX_MEAN 1.0e4
+ORC_API int64_t orc_poisson_from_bits(uint32_t lo_word, uint32_t hi_word, double mean)
+{
+    double u = orc_u01_53(lo_word, hi_word);
+    mean = fmin(fmax(mean, 0.0), ORC_POISSON_MAX_MEAN);
+    int64_t m = (int64_t)mean, lo = m, hi = m, k = m;
+    double A = 0.0, t = 1.0;
+    while (lo > 0) { t *= (double)lo / mean; if (A + t == A) break; A += t; --lo; }
+    double S = A;
+    t = 1.0;
+    for (;;) { S += t; t *= mean / (double)(hi + 1); if (S + t == S) break; ++hi; }
+    double T = u * S;
+    t = 1.0;
+    if (T > A) {
+        double C = A + t;
+        while (T > C && k < hi) { ++k; t *= mean / (double)k; C += t; }
+    } else {
+        double C = A;
+        while (T <= C && k > lo) { t *= (double)k / mean; C -= t; --k; }
+    }
+    return k;
+}
 ORC_API int64_t orc_draw_poisson(uint64_t seed, uint64_t pid, uint64_t draw, double mean)
 {
-    double u = orc_draw_u01_53(seed, pid, draw);
-    int64_t k = 0;
-    double p = exp(-mean), F = p;
-    while (u > F && k < 100000) { ++k; p *= mean / (double)k; F += p; }
-    return k;
+    uint32_t r[4];
+    orc_draw_block(seed, pid >> 1, draw, r);
+    return (pid & 1) ? orc_poisson_from_bits(r[2], r[3], mean) : orc_poisson_from_bits(r[0], r[1], mean);
 }
 
 /* ------------------------------------------------------------------------- */
