@@ -39,6 +39,7 @@ SYMBOLS = [
     "cpprob_hip_gather_i32", "cpprob_hip_profile_enable", "cpprob_hip_profile_read", "cpprob_hip_fastmath", "cpprob_hip_variate_from_bits",
     "cpprob_hip_batch_workspace_bytes", "cpprob_hip_batch_begin", "cpprob_hip_batch_run", "cpprob_hip_batch_results", "cpprob_hip_batch_results_device",
     "cpprob_hip_batch_copy_store", "cpprob_hip_batch_problems_workspace_bytes", "cpprob_hip_batch_begin_problems",
+    "cpprob_hip_batch_online_workspace_bytes", "cpprob_hip_batch_begin_online", "cpprob_hip_batch_advance", "cpprob_hip_batch_lengths",
 ]
 
 
@@ -107,6 +108,23 @@ def batch_problems_workspace_bytes(model, T, n_particles, max_particles=None, re
     cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), top, int(h_T.size))
     out = C.c_uint64()
     rc = L.cpprob_hip_batch_problems_workspace_bytes(C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out))
+    if rc:
+        msg = L.cpprob_hip_last_error(None)
+        e = CpprobHipError("cpprob_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+        e.code = rc
+        raise e
+    return out.value
+
+
+def batch_online_workspace_bytes(model, capacity, n_particles, max_particles=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
+    """cpprob_hip_batch_online_workspace_bytes: the device bytes of a batch advanced in pieces, whose problem b may reach capacity[b]
+    observes with n_particles[b] particles (an int: every problem's); max_particles is cfg.n_particles.  No GPU needed."""
+    L = load_library()
+    h_T, h_n = _problem_shapes(capacity, n_particles)
+    top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), top, int(h_T.size))
+    out = C.c_uint64()
+    rc = L.cpprob_hip_batch_online_workspace_bytes(C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out))
     if rc:
         msg = L.cpprob_hip_last_error(None)
         e = CpprobHipError("cpprob_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
@@ -248,6 +266,10 @@ def load_library(path=None):
         "cpprob_hip_batch_copy_store": (C.c_int, [vp, u64, vp, vp, vp]),
         "cpprob_hip_batch_problems_workspace_bytes": (C.c_int, [C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]),
         "cpprob_hip_batch_begin_problems": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, vp, vp]),
+        "cpprob_hip_batch_online_workspace_bytes": (C.c_int, [C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]),
+        "cpprob_hip_batch_begin_online": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, vp, vp, C.POINTER(u64)]),
+        "cpprob_hip_batch_advance": (C.c_int, [vp, C.POINTER(C.c_uint32), vp, C.c_int32]),
+        "cpprob_hip_batch_lengths": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -464,6 +486,51 @@ class Engine:
         self.batch_shapes = (h_T, h_n)
         return self
 
+    def batch_begin_online(self, model, capacity, n_particles, seeds, tables=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC,
+                           flags=0, max_particles=None):
+        """A batch whose observes arrive over time.  capacity: the most observes problem b may reach, one a problem; n_particles and
+        tables as for batch_begin_problems; seeds: one Philox key a problem, for the life of the batch.  Every problem starts at
+        length 0; batch_advance() feeds it.  batch_results() returns arrays padded to the largest capacity and batch_store(b) the
+        [L_b, n_b] rows reached."""
+        h_T, h_n = _problem_shapes(capacity, n_particles)
+        sd = np.ascontiguousarray(seeds, np.uint64)
+        if sd.shape != h_T.shape:
+            raise ValueError("one seed per problem")
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(model, top, h_T.size, resampler, ess_threshold, keep_history, algorithm, flags)
+        k, means, trans = 0, None, None
+        if tables is not None:
+            means = np.ascontiguousarray(tables[0], np.float64)
+            trans = np.ascontiguousarray(tables[1], np.float64)
+            if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != h_T.size:
+                raise ValueError("tables = (means [B, k], transition [B, k, k])")
+            k = means.shape[1]
+        self._chk(self.L.cpprob_hip_batch_begin_online(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), k,
+                                                       None if means is None else means.ctypes.data, None if trans is None else trans.ctypes.data,
+                                                       sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        self.batch_B, self.batch_T, self.batch_n = int(h_T.size), int(h_T.max()), top
+        self.batch_K = 3 if model == MODEL_HMM3 else 8
+        self.batch_shapes = (np.zeros(h_T.size, np.uint32), h_n)
+        return self
+
+    def batch_advance(self, new_observes, readout=True):
+        """new_observes: a list of 1-D arrays, problem b's new observes (possibly none).  One launch over the new steps, enqueued
+        without waiting.  readout=False (keep_history only) leaves the smoothed statistics to a later advance with readout=True,
+        which may carry no observes at all."""
+        seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in new_observes]
+        if len(seqs) != self.batch_B:
+            raise ValueError("one (possibly empty) sequence per problem")
+        h_dT = np.array([len(o) for o in seqs], np.uint32)
+        flat = np.ascontiguousarray(np.concatenate(seqs)) if seqs else np.zeros(0)
+        self._chk(self.L.cpprob_hip_batch_advance(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), flat.ctypes.data if flat.size else None, 1 if readout else 0))
+        self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
+
+    def batch_lengths(self):
+        """The observes every problem of an online batch has seen so far (uint32 [B])."""
+        out = np.zeros(self.batch_B, np.uint32)
+        self._chk(self.L.cpprob_hip_batch_lengths(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
     def batch_run(self, seeds):
         """One launch; problem b runs with Philox key seeds[b]."""
         sd = np.ascontiguousarray(seeds, np.uint64)
@@ -471,14 +538,15 @@ class Engine:
             raise ValueError("one seed per problem")
         self._chk(self.L.cpprob_hip_batch_run(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
 
-    def batch_results(self):
-        """[summary dict] * B, stats [B, T, spp], ess [B, T], resampled [B, T] in one call and one synchronisation."""
+    def batch_results(self, with_stats=True):
+        """[summary dict] * B, stats [B, T, spp], ess [B, T], resampled [B, T] in one call and one synchronisation.  with_stats=False:
+        stats is None (what an online batch serves between an advance without read-out and the next one with it)."""
         B, T, K = self.batch_B, self.batch_T, self.batch_K
         sums = (Summary * B)()
-        stats = np.zeros((B, T, K))
+        stats = np.zeros((B, T, K)) if with_stats else None
         ess = np.zeros((B, T))
         res = np.zeros((B, T), np.int32)
-        self._chk(self.L.cpprob_hip_batch_results(self.h, sums, stats.ctypes.data, stats.size, ess.ctypes.data, res.ctypes.data))
+        self._chk(self.L.cpprob_hip_batch_results(self.h, sums, stats.ctypes.data if with_stats else None, stats.size if with_stats else 0, ess.ctypes.data, res.ctypes.data))
         return [{f: getattr(s, f) for f, _ in Summary._fields_} for s in sums], stats, ess, res
 
     def batch_results_device(self, out):

@@ -27,6 +27,16 @@
 // chains first) with the T, n and packed store offset of its BatchProblem and, for HMM_TABLE, its own thresholds.  Either way problem b
 // owns rows b T_max + t of the small per-step regions (tab, stats, ess, resampled), of which a described problem writes its first T_b.
 // The launch's dynamic LDS is batch_lds_bytes of the batch's largest n; each workgroup carves it by its own npad.
+//
+// A third kind is advanced in pieces (cpprob_hip_batch_begin_online / _advance): a launch runs steps [first[b], prob[b].T) of problem
+// b, and what it leaves equals a one-shot run of prob[b].T steps bit for bit.  In the shorter run generation first - 1 was final (no
+// resampling, the final books); now it is an ordinary one.  So a resumed workgroup enters the step loop one generation early, at
+// t = first - 1, with the draw replaced by a reload of that generation's states (row first - 1 of its values, or its carry region in
+// a filtering batch) and the books' running values (log_z, n_resampled, fix_gap, first_bad, n_requantised) put back to what they were
+// before that generation's final books (BatchSnap, written where every piece ends).  Count, books, comb and prefix maximum of the
+// reloaded generation are then the loop's own, in the resampling form, with the junction's own Philox draw.  A piece without steps
+// (first = T) re-keeps the final books, to the same values, on its way to the read-out; without a read-out to do (first = -1: the
+// host knows the problem's statistics are those of its length) it returns at once.
 #pragma once
 #include "step_counts.hpp"
 #include "step_fixed.hpp"
@@ -44,6 +54,10 @@ __host__ __device__ inline int64_t batch_lds_bytes(int64_t n) { const int64_t np
 struct BatchProblem { int32_t T, n; int64_t store; };
 static_assert(sizeof(BatchProblem) == 16, "one problem's descriptor");
 
+// What generation T - 1's final books overwrite, as it stood before them: where the next piece resumes.
+struct BatchSnap { double log_z, fix_gap; int32_t n_resampled, first_bad, n_requant, pad_; };
+static_assert(sizeof(BatchSnap) == 32, "one problem's snapshot");
+
 struct BatchArgs {
     ModelParams mp;                            // HMM3: hmm_thr; HMM_TABLE: hk (the thresholds are `thr`: mp.hk_thr is not read)
     const double* tab;                         // [B][T_max][kBatchTab]
@@ -59,6 +73,11 @@ struct BatchArgs {
     int thr_stride;                            // words: 0 (one shared table) or 64 (a table a problem)
     int spp;
     double ess_frac;
+    // a batch advanced in pieces (the RESUME kernels; the others read none of these)
+    const int32_t* first;                      // [B]: problem b's first step of this launch (its length before it); -1: nothing to do for it
+    BatchSnap* snap;                           // [B]
+    uint8_t* carry;                            // filtering: problem b's final generation, n bytes at carry + prob[b].store
+    int skip_readout;                          // keep_history: 1 leaves the lineage walk to a later piece
 };
 
 __device__ __forceinline__ uint32_t batch_sel8(const uint32_t (&q)[8], int s)
@@ -69,7 +88,9 @@ __device__ __forceinline__ uint32_t batch_sel8(const uint32_t (&q)[8], int s)
     return r;
 }
 
-template <class Model, int RS, bool KEEP>
+// RESUME: the kernel of a batch advanced in pieces.  (A template parameter, not a run-time switch on a.first: with the switch the two
+// <HMM3, KEEP> kernels of the one-shot batches reserved a 68-byte private segment -- profiles/r12_notes.md, "Kernel resources".)
+template <class Model, int RS, bool KEEP, bool RESUME = false>
 __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
 {
     using V = typename Model::value_t;
@@ -85,6 +106,8 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
     const int b = a.order ? (int)a.order[blockIdx.x] : (int)blockIdx.x;
     const int n = a.prob ? (int)a.prob[b].n : a.n;
     const int T = a.prob ? (int)a.prob[b].T : a.T_max;
+    const int t_first = RESUME ? (int)a.first[b] : 0;
+    if (RESUME && (t_first < 0 || (t_first == T && (!KEEP || a.skip_readout)))) return;     // neither steps nor a read-out to do
     const int npad = (n + kTile - 1) / kTile * kTile, passes = npad / kTile;
     int32_t* A = reinterpret_cast<int32_t*>(s_batch);                                       // ancestors of the next generation (slots while the comb runs; paths in the read-out)
     uint8_t* S0 = reinterpret_cast<uint8_t*>(A + npad);
@@ -101,22 +124,39 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
     // steps: held in registers, that 64-bit value made <HMM3, stratified, KEEP> reserve a 68-byte private segment
     // (profiles/r09_notes.md, "Kernel resources").
     auto store = [&]() -> int64_t { return a.prob ? a.prob[b].store : (int64_t)b * T * n; };
-    if (tid == 0) { ctrl->lz_trace = nullptr; ctrl->first_bad = -1; ctrl->log_z = 0.0; ctrl->n_resampled = 0; ctrl->fix_gap = 0.0; }
     int n_requant = 0;
+    if (RESUME && t_first > 0) {
+        const BatchSnap sn = a.snap[b];
+        n_requant = sn.n_requant;
+        if (tid == 0) { ctrl->lz_trace = nullptr; ctrl->first_bad = sn.first_bad; ctrl->log_z = sn.log_z; ctrl->n_resampled = sn.n_resampled; ctrl->fix_gap = sn.fix_gap; }
+    } else if (tid == 0) { ctrl->lz_trace = nullptr; ctrl->first_bad = -1; ctrl->log_z = 0.0; ctrl->n_resampled = 0; ctrl->fix_gap = 0.0; }
     uint32_t q_fin[8] = {0, 0, 0, 0, 0, 0, 0, 0};              // HMM_TABLE: the final generation's weight of each state
     uint64_t S_fin = 0;
     // HMM_TABLE: the problem's 64 threshold words staged in LDS once; every draw reads its row there.  (Left in global memory
     // the same batch runs 6 % slower: profiles/r09_notes.md, "Threshold staging".)
     __shared__ uint64_t s_thr[kCounts ? 1 : 64];                // (HMM3: unused, and takes no LDS)
     if constexpr (!kCounts) { if (tid < 64) s_thr[tid] = a.thr[(int64_t)b * a.thr_stride + tid]; __syncthreads(); }
-    for (int t = 0; t < T; ++t) {
+    for (int t = RESUME && t_first > 0 ? t_first - 1 : 0; t < T; ++t) {
         uint8_t* cur = (t & 1) ? S1 : S0;
         const uint8_t* prv = (t & 1) ? S0 : S1;
-        // ---- draw ----
+        // ---- draw (a resumed problem's first pass through the loop: generation first - 1 comes back from memory) ----
         uint64_t cA = 0, cB = 0;
+        const bool reload = RESUME && t < t_first;
         for (int p = 0; p < passes; ++p) {
             const int i0 = p * kTile + tid * kPPT;
             if (i0 >= n) continue;
+            if (reload) {
+#pragma unroll
+                for (int k = 0; k < kPPT; ++k) {
+                    const int i = i0 + k;
+                    if (i >= n) continue;
+                    const int s = KEEP ? (int)a.values[store() + (int64_t)t * n + i] : (int)a.carry[store() + i];
+                    cur[i] = (uint8_t)s;
+                    cA += s < 4 ? 1ull << (16 * s) : 0ull;
+                    cB += s >= 4 ? 1ull << (16 * (s - 4)) : 0ull;
+                }
+                continue;
+            }
             V prev[kPPT], x[kPPT];
             int32_t an[kPPT];
 #pragma unroll
@@ -178,6 +218,7 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
                     ca.filter_stats = KEEP ? nullptr : st_b;
                     counts_step_bookkeep(ca, t + 1, tc, W, tot0, tot1);
                 } else {
+                    if (RESUME) { BatchSnap sn{}; sn.log_z = ctrl->log_z; sn.n_resampled = ctrl->n_resampled; sn.first_bad = -1; a.snap[b] = sn; }
                     CountsFinal f{};
                     f.e[0] = row[3]; f.e[1] = row[4]; f.e[2] = row[5]; f.e[3] = row[6];
                     f.n_pop = n_pop; f.T = T; f.bookkeep = 1; f.ctrl = ctrl; f.ess_trace = ess_b; f.resampled = res_b;
@@ -201,6 +242,12 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
             const FixedDecision d = fixed_decide(S, Q, n_pop, a.ess_frac, resample);
             fc.inv = d.inv; fc.u0 = u0; fc.n_pop = n_pop; fc.base = 0; fc.seed = seed; fc.draw = draw; fc.uid0 = 0;
             if (tid == 0) {
+                if (RESUME && !resample) {
+                    BatchSnap sn{};
+                    sn.log_z = ctrl->log_z; sn.fix_gap = ctrl->fix_gap; sn.n_resampled = ctrl->n_resampled; sn.first_bad = ctrl->first_bad;
+                    sn.n_requant = n_requant - (requant ? 1 : 0);
+                    a.snap[b] = sn;
+                }
                 ctrl->ref_cur = ref;
                 fixed_bookkeep(ctrl, t, d, ref, n_pop, u0, ess_b, res_b, !resample, M);
                 if (!KEEP) {
@@ -214,7 +261,10 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
                 S_fin = S;
             }
         }
-        if (!resample) break;
+        if (!resample) {
+            if (RESUME && !KEEP && !reload) for (int j = tid; j < n; j += kThreads) a.carry[store() + j] = cur[j];   // what the next piece resumes from
+            break;
+        }
         // ---- comb: each source marks the first output it owns ----
         auto first_of = [&](uint64_t prefix, int upto) -> int {           // first output owned by the sources after `upto` particles
             double g;
@@ -284,6 +334,7 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
     }
     if (tid == 0 && a.n_requant) a.n_requant[b] = n_requant;
     if constexpr (KEEP) {
+        if (RESUME && a.skip_readout) return;
         // ---- read-out: the lineage walk, hit T-1 back to 0, integer sums per hit ----
         const uint8_t* fin = ((T - 1) & 1) ? S1 : S0;
         for (int p = 0; p < passes; ++p)

@@ -1005,9 +1005,11 @@ void free_run_buffers(cpprob_hip_ctx* c)
 //              cpprob_hip_batch_workspace_bytes states the sum
 //   described  (cpprob_hip_batch_begin_problems: T_rows = T_max, tables = B, descriptors and dispatch order, entries = sum of T_b n_b,
 //              the particle store packed): twelve regions, cpprob_hip_batch_problems_workspace_bytes states the sum
-struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, prob, order, values, anc, total; };
+//   online     (cpprob_hip_batch_begin_online: a described batch of the capacities, then every problem's first step of a launch, its
+//              snapshot and, filtering, its carried generation -- carry = sum of n_b): cpprob_hip_batch_online_workspace_bytes
+struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, prob, order, values, anc, first, snap, carry, total; };
 size_t batch_round(size_t x) { return (x + 255) / 256 * 256; }
-BatchLayout batch_layout(uint64_t B, uint64_t T_rows, uint64_t tables, bool described, uint64_t entries, int spp, bool keep)
+BatchLayout batch_layout(uint64_t B, uint64_t T_rows, uint64_t tables, bool described, uint64_t entries, int spp, bool keep, bool online = false, uint64_t carry = 0)
 {
     BatchLayout L{};
     size_t o = 0;
@@ -1024,10 +1026,13 @@ BatchLayout batch_layout(uint64_t B, uint64_t T_rows, uint64_t tables, bool desc
     L.order = take(described ? B * sizeof(int32_t) : 0);
     L.values = take(keep ? entries : 0);
     L.anc = take(keep ? entries * sizeof(int32_t) : 0);
+    L.first = take(online ? B * sizeof(int32_t) : 0);
+    L.snap = take(online ? B * sizeof(BatchSnap) : 0);
+    L.carry = take(online && !keep ? carry : 0);
     L.total = o;
     return L;
 }
-struct BatchProblemsShape { uint64_t T_max = 0, n_max = 0, steps = 0; };      // steps = sum of T_b n_b
+struct BatchProblemsShape { uint64_t T_max = 0, n_max = 0, steps = 0, particles = 0; };      // steps = sum of T_b n_b, particles = sum of n_b
 
 struct BatchState {
     cpprob_hip_batch_config cfg{};
@@ -1040,12 +1045,29 @@ struct BatchState {
     std::vector<uint64_t> h_thr;               // HMM_TABLE: the rows' thresholds at begin
     char* d_ws = nullptr; size_t cap = 0;
     ModelParams mp{};
+    // a batch advanced in pieces (cpprob_hip_batch_begin_online): prob[b].T is the length reached, prob[b].store the problem's first
+    // entry in a store sized by the capacities (keep_history = 1) or its first byte in the carry region (keep_history = 0)
+    bool online = false, walked = true;        // walked: the statistics on the device are those of the lengths reached
+    std::vector<char> walked_b;                // [B]: ... problem b's (keep_history = 1: the lineage walk has run over its rows)
+    std::vector<uint32_t> cap_T;               // [B]
+    std::vector<double> means;                 // HMM_TABLE: [tables][hk], the rows an advance evaluates its steps' tables with
+    double* pin_tab = nullptr; size_t pin_tab_cap = 0;      // pinned mirror of the table region: an advance writes its new rows only
+    // pinned descriptors of an advance in flight, kOnlineSlots in turn: {BatchProblem[B], first[B], order[B]}; a slot is written
+    // again once the copies that read it have run (its event)
+    static constexpr int kOnlineSlots = 4;
+    char* pin_desc = nullptr; size_t pin_desc_cap = 0, slot_bytes = 0;
+    hipEvent_t slot_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
+    uint64_t n_advance = 0;
+    const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
 void batch_free(cpprob_hip_ctx* c)
 {
     if (!c->batch) return;
-    dfree(c->batch->d_ws);
+    dfree(c->batch->d_ws);                     // (hipFree waits for the device: no copy still reads the pinned buffers)
+    if (c->batch->pin_tab) (void)hipHostFree(c->batch->pin_tab);
+    if (c->batch->pin_desc) (void)hipHostFree(c->batch->pin_desc);
+    for (hipEvent_t e : c->batch->slot_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
     c->batch = nullptr;
 }
@@ -1091,6 +1113,7 @@ int batch_check_problems(const cpprob_hip_batch_config* cfg, const uint32_t* h_T
         }
         sh.n_max = std::max<uint64_t>(sh.n_max, h_n[b]);
         sh.steps += (uint64_t)h_T[b] * h_n[b];
+        sh.particles += h_n[b];
     }
     return 0;
 }
@@ -1098,9 +1121,12 @@ int batch_check_problems(const cpprob_hip_batch_config* cfg, const uint32_t* h_T
 // Begins a checked batch.  Described (h_T, h_n given): problem b has h_T[b] observes, consecutive in h_obs, and h_n[b] particles;
 // uniform (both NULL): every problem has T_max observes and cfg->n_particles particles.  HMM_TABLE of k states: problem b's own table
 // (h_means [B][k], h_transition [B][k][k]) or, both NULL, the table of cpprob_hip_set_hmm.
+// Online (h_T = the capacities, h_obs NULL, h_seeds given): every problem starts without observes; cpprob_hip_batch_advance evaluates
+// its rows, with the statements below, as they arrive.
 int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_max, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
-                int k, const double* h_means, const double* h_transition)
+                int k, const double* h_means, const double* h_transition, const uint64_t* h_seeds = nullptr)
 {
+    const bool online = h_seeds != nullptr;
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->batch) c->batch = new BatchState();
     BatchState* bs = c->batch;
@@ -1113,18 +1139,43 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->mp.hk = hmm3 ? 0 : k;
     // the per-step tables and thresholds of every problem, with the single path's own host expressions (cpprob_hip_infer_begin) on the
     // problem's means / transition rows; rows t >= T_b stay zero
-    bs->h_tab.assign((size_t)B * T_max * kBatchTab, 0.0);
+    bs->online = false;
+    if (online) {
+        // (advances of the batch this one replaces may still read the pinned buffers)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const size_t tab_bytes = (size_t)B * T_max * kBatchTab * sizeof(double);
+        if (tab_bytes > bs->pin_tab_cap) {
+            if (bs->pin_tab) { (void)hipHostFree(bs->pin_tab); bs->pin_tab = nullptr; bs->pin_tab_cap = 0; }
+            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_tab), tab_bytes, hipHostMallocDefault));
+            bs->pin_tab_cap = tab_bytes;
+        }
+        std::memset(bs->pin_tab, 0, tab_bytes);
+        bs->slot_bytes = batch_round((size_t)B * (sizeof(BatchProblem) + 2 * sizeof(int32_t)));
+        if (bs->slot_bytes * BatchState::kOnlineSlots > bs->pin_desc_cap) {
+            if (bs->pin_desc) { (void)hipHostFree(bs->pin_desc); bs->pin_desc = nullptr; bs->pin_desc_cap = 0; }
+            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_desc), bs->slot_bytes * BatchState::kOnlineSlots, hipHostMallocDefault));
+            bs->pin_desc_cap = bs->slot_bytes * BatchState::kOnlineSlots;
+        }
+        for (hipEvent_t& e : bs->slot_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        bs->cap_T.assign(h_T, h_T + B);
+        bs->walked_b.assign(B, 1);
+        bs->means.clear();
+        bs->n_advance = 0;
+        bs->h_tab.clear();
+    } else bs->h_tab.assign((size_t)B * T_max * kBatchTab, 0.0);
     bs->h_thr.assign((size_t)tables * 64, ~0ull);
     bs->prob.resize(B);
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
     size_t at_obs = 0;
-    int64_t at_store = 0;
+    int64_t at_store = 0, at_carry = 0;
+    if (online && !hmm3 && !own) bs->means = mean;
     for (uint64_t b = 0; b < B; ++b) {
         const size_t T_b = described ? h_T[b] : T_max, n_b = described ? h_n[b] : (size_t)cfg->n_particles;
         if (own) { mean.assign(h_means + b * (size_t)k, h_means + (b + 1) * (size_t)k); trans.assign(h_transition + b * (size_t)k * k, h_transition + (b + 1) * (size_t)k * k); }
-        for (size_t t = 0; t < T_b; ++t) {
+        if (online && own) bs->means.insert(bs->means.end(), mean.begin(), mean.end());
+        for (size_t t = 0; t < (online ? 0 : T_b); ++t) {
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
@@ -1134,20 +1185,35 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
             if (own || b == 0) thr = hmmk_thresholds(trans, k);
             std::copy(thr.begin(), thr.end(), bs->h_thr.begin() + (size_t)b * 64);
         }
-        bs->prob[b].T = (int32_t)T_b; bs->prob[b].n = (int32_t)n_b; bs->prob[b].store = at_store;
+        bs->prob[b].T = online ? 0 : (int32_t)T_b; bs->prob[b].n = (int32_t)n_b;
+        bs->prob[b].store = online && cfg->keep_history != 1 ? at_carry : at_store;
         at_obs += T_b;
         at_store += (int64_t)(T_b * n_b);
+        at_carry += (int64_t)n_b;
     }
-    bs->lay = batch_layout(B, T_max, tables, described, (uint64_t)at_store, spp, cfg->keep_history == 1);
+    bs->lay = batch_layout(B, T_max, tables, described, (uint64_t)at_store, spp, cfg->keep_history == 1, online, (uint64_t)at_carry);
     if (bs->lay.total > bs->cap) {
         // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
         dfree(bs->d_ws); bs->cap = 0;
         HIP_TRY(c, hipMalloc(&bs->d_ws, bs->lay.total));
         bs->cap = bs->lay.total;
     }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (online) HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.tab, 0, (size_t)B * T_max * kBatchTab * sizeof(double), c->stream));
+    else HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
+    std::vector<char> ctrl0;
+    if (online) {
+        // no observes yet: a problem's summary reads as zeros (log_norm = M + log W) until its first advance
+        ctrl0.assign((size_t)B * kBatchCtrlBytes, 0);
+        StepCtrl z{};
+        z.W = 1.0;
+        for (uint64_t b = 0; b < B; ++b) std::memcpy(ctrl0.data() + b * kBatchCtrlBytes, &z, sizeof z);
+        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.ctrl, ctrl0.data(), ctrl0.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.nreq, 0, B * sizeof(int32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.snap, 0, B * sizeof(BatchSnap), c->stream));
+    }
     if (described) {
         // the longest chains first (steps x LDS passes a step), ties by index: the launch's tail is made of short problems; no result
         // depends on the order
@@ -1164,19 +1230,22 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
-    bs->begun = true;
+    bs->online = online; bs->walked = true;
+    bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
 
-// The eight kernels of cpprob_hip_batch_run.
+// The eight kernels of cpprob_hip_batch_run, and the eight of cpprob_hip_batch_advance.
 using BatchKernel = void (*)(BatchArgs);
-template <class Model>
+template <class Model, bool RESUME>
 BatchKernel batch_kernel(bool stratified, bool keep)
 {
-    static constexpr BatchKernel k[2][2] = {{batch_smc_kernel<Model, kFixSystematic, false>, batch_smc_kernel<Model, kFixSystematic, true>},
-                                            {batch_smc_kernel<Model, kFixStratified, false>, batch_smc_kernel<Model, kFixStratified, true>}};
+    static constexpr BatchKernel k[2][2] = {{batch_smc_kernel<Model, kFixSystematic, false, RESUME>, batch_smc_kernel<Model, kFixSystematic, true, RESUME>},
+                                            {batch_smc_kernel<Model, kFixStratified, false, RESUME>, batch_smc_kernel<Model, kFixStratified, true, RESUME>}};
     return k[stratified][keep];
 }
+template <class Model>
+BatchKernel batch_kernel(bool stratified, bool keep, bool resume) { return resume ? batch_kernel<Model, true>(stratified, keep) : batch_kernel<Model, false>(stratified, keep); }
 
 }  // namespace
 
@@ -3917,6 +3986,8 @@ int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg
     return 0;
 }
 
+static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, int32_t k_in, const double* h_means, const double* h_transition, int& k);
+
 int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
                                     const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition)
 {
@@ -3925,13 +3996,21 @@ int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_co
     std::string msg;
     BatchProblemsShape sh;
     if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    int k = 0;
+    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
+    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition);
+}
+
+// The tables of a batch of problems (cpprob_hip_batch_begin_problems, _begin_online): per problem, or the context's; k = the states.
+static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, int32_t k_in, const double* h_means, const double* h_transition, int& k)
+{
     const uint64_t B = cfg->n_problems;
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3;
     const bool own = h_means || h_transition;                 // per-problem tables
     if (own && (!h_means || !h_transition)) return fail(c, CPPROB_HIP_EINVAL, "per-problem tables need both h_means and h_transition");
     if (hmm3 && own) return fail(c, CPPROB_HIP_EINVAL, "CPPROB_HIP_MODEL_HMM3 has its own table: h_means and h_transition must be NULL");
     if (!hmm3 && !own && c->hk < 2) return fail(c, CPPROB_HIP_ESTATE, "CPPROB_HIP_MODEL_HMM_TABLE: call cpprob_hip_set_hmm first, or pass per-problem tables");
-    const int k = hmm3 ? 3 : (own ? (int)k_in : c->hk);
+    k = hmm3 ? 3 : (own ? (int)k_in : c->hk);
     if (own) {
         if (k_in < 2 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "the table model holds 2 .. 8 states");
         // per table what cpprob_hip_set_hmm demands
@@ -3946,20 +4025,21 @@ int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_co
             }
         }
     }
-    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition);
+    return 0;
 }
 
-int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
+// One launch over the begun batch: every problem from step 0 (cpprob_hip_batch_run), or its piece (cpprob_hip_batch_advance).
+static int batch_launch(cpprob_hip_ctx* c, BatchState* bs, bool readout)
 {
-    LANES_OWN(c);
-    if (!c || !h_seeds) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    BatchState* bs = c->batch;
-    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
-    HIP_TRY(c, hipSetDevice(c->device));
     const uint64_t B = bs->cfg.n_problems;
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     const bool keep = bs->cfg.keep_history == 1;
     BatchArgs a{};
+    if (bs->online) {
+        a.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
+        a.snap = reinterpret_cast<BatchSnap*>(bs->d_ws + bs->lay.snap);
+        a.carry = keep ? nullptr : reinterpret_cast<uint8_t*>(bs->d_ws + bs->lay.carry);
+        a.skip_readout = keep && !readout ? 1 : 0;
+    }
     a.mp = bs->mp;
     a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
     a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
@@ -3976,10 +4056,129 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
     a.n_requant = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.nreq);
     a.T_max = bs->T; a.n = (int)bs->cfg.n_particles; a.spp = bs->K; a.ess_frac = bs->cfg.ess_threshold;
     const bool strat = bs->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED;
-    const BatchKernel kern = bs->cfg.model == CPPROB_HIP_MODEL_HMM3 ? batch_kernel<ModelHmm3>(strat, keep) : batch_kernel<ModelHmmK>(strat, keep);
+    const BatchKernel kern = bs->cfg.model == CPPROB_HIP_MODEL_HMM3 ? batch_kernel<ModelHmm3>(strat, keep, bs->online) : batch_kernel<ModelHmmK>(strat, keep, bs->online);
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), (size_t)batch_lds_bytes(a.n), c->stream, a);
     HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
+{
+    LANES_OWN(c);
+    if (!c || !h_seeds) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
+    if (bs->online) return fail(c, CPPROB_HIP_ESTATE, "a batch begun by cpprob_hip_batch_begin_online is advanced (cpprob_hip_batch_advance), not run");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, bs->cfg.n_problems * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_launch(c, bs, true)) return rc;
     bs->ran = true;
+    return 0;
+}
+
+int cpprob_hip_batch_online_workspace_bytes(const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n, uint64_t* out_bytes)
+{
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_Tcap, h_n, sh, msg)) return fail(nullptr, rc, msg);
+    if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
+    const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
+    *out_bytes = batch_layout(cfg->n_problems, sh.T_max, cfg->n_problems, true, sh.steps, spp, cfg->keep_history == 1, true, sh.particles).total;
+    return 0;
+}
+
+int cpprob_hip_batch_begin_online(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
+                                  int32_t k_in, const double* h_means, const double* h_transition, const uint64_t* h_seeds)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_Tcap || !h_n || !h_seeds) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_Tcap, h_n, sh, msg)) return fail(c, rc, msg);
+    int k = 0;
+    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
+    return batch_begin(c, cfg, (size_t)sh.T_max, h_Tcap, h_n, nullptr, k, h_means, h_transition, h_seeds);
+}
+
+int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs, int32_t readout)
+{
+    LANES_OWN(c);
+    if (!c || !h_dT) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->online) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_advance serves a batch begun by cpprob_hip_batch_begin_online");
+    const uint64_t B = bs->cfg.n_problems;
+    uint64_t total = 0;
+    for (uint64_t b = 0; b < B; ++b) {
+        if ((uint64_t)bs->prob[b].T + h_dT[b] > bs->cap_T[b])
+            return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": " + std::to_string(h_dT[b]) + " more observes after " + std::to_string(bs->prob[b].T) +
+                                              " exceed its capacity of " + std::to_string(bs->cap_T[b]));
+        total += h_dT[b];
+    }
+    if (total && !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // this advance's descriptors: its slot is free once the copies of the advance that used it last have run
+    const int slot = (int)(bs->n_advance % BatchState::kOnlineSlots);
+    if (bs->n_advance >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->slot_done[slot]));
+    char* sl = bs->pin_desc + (size_t)slot * bs->slot_bytes;
+    BatchProblem* pr = reinterpret_cast<BatchProblem*>(sl);
+    int32_t* first = reinterpret_cast<int32_t*>(sl + B * sizeof(BatchProblem));
+    int32_t* order = first + B;
+    const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3, keep = bs->cfg.keep_history == 1;
+    const size_t hk = (size_t)bs->hk, T_max = (size_t)bs->T, row_bytes = kBatchTab * sizeof(double);
+    const bool own = !hmm3 && bs->means.size() > hk;
+    std::vector<double> mean;
+    if (!hmm3 && !own) mean = bs->means;
+    size_t at_obs = 0;
+    for (uint64_t b = 0; b < B; ++b) {
+        const size_t L = (size_t)bs->prob[b].T;
+        if (own && h_dT[b]) mean.assign(bs->means.begin() + (ptrdiff_t)(b * hk), bs->means.begin() + (ptrdiff_t)((b + 1) * hk));
+        for (size_t t = L; t < L + h_dT[b]; ++t) {
+            const double y = h_obs[at_obs++];
+            double* row = bs->pin_tab + (b * T_max + t) * kBatchTab;
+            if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
+            else hmmk_step_ll(y, mean, (int)hk, row);
+        }
+        // (a problem without observes, or without new ones and with its read-out done, has nothing to do)
+        const bool idle = h_dT[b] == 0 && (L == 0 || !keep || bs->walked_b[b] || !readout);
+        first[b] = idle ? -1 : (int32_t)L;
+        if (keep && !idle) bs->walked_b[b] = readout ? 1 : 0;
+        order[b] = (int32_t)b;
+        bs->prob[b].T = (int32_t)(L + h_dT[b]);
+        pr[b] = bs->prob[b];
+    }
+    // the longest pieces first, ties by index
+    auto cost = [&](int32_t b) { return (uint64_t)h_dT[b] * (((uint64_t)bs->prob[b].n + kTile - 1) / kTile); };
+    std::stable_sort(order, order + B, [&](int32_t x, int32_t y) { return cost(x) > cost(y); });
+    // the new rows: one strided copy per run of problems that share first step and piece length
+    for (uint64_t b = 0; b < B;) {
+        uint64_t e = b + 1;
+        while (e < B && bs->prob[e].T == bs->prob[b].T && h_dT[e] == h_dT[b]) ++e;
+        if (h_dT[b]) {
+            const size_t at = ((size_t)b * T_max + (size_t)first[b]) * row_bytes;      // (h_dT[b] > 0: first[b] is its length before)
+            HIP_TRY(c, hipMemcpy2DAsync(bs->d_ws + bs->lay.tab + at, T_max * row_bytes, reinterpret_cast<const char*>(bs->pin_tab) + at, T_max * row_bytes,
+                                        (size_t)h_dT[b] * row_bytes, (size_t)(e - b), hipMemcpyHostToDevice, c->stream));
+        }
+        b = e;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.prob, pr, B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.first, first, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.order, order, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(bs->slot_done[slot], c->stream));
+    ++bs->n_advance;
+    bool work = false, walked = true;
+    for (uint64_t b = 0; b < B; ++b) { work = work || first[b] >= 0; walked = walked && bs->walked_b[b]; }
+    if (work) if (int rc = batch_launch(c, bs, readout != 0)) return rc;
+    bs->walked = walked;
+    return 0;
+}
+
+int cpprob_hip_batch_lengths(cpprob_hip_ctx* c, uint32_t* h_L)
+{
+    LANES_OWN(c);
+    if (!c || !h_L) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->online) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_lengths serves a batch begun by cpprob_hip_batch_begin_online");
+    for (uint64_t b = 0; b < bs->cfg.n_problems; ++b) h_L[b] = (uint32_t)bs->prob[b].T;
     return 0;
 }
 
@@ -3991,6 +4190,7 @@ int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, doubl
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, T = (size_t)bs->T, need = B * T * (size_t)bs->K;
+    if (h_stats && !bs->walked) return fail(c, CPPROB_HIP_ESTATE, "the statistics wait for an advance with readout = 1 (cpprob_hip_batch_advance)");
     if (h_stats && n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "h_stats too small");
     std::vector<char> ctrl(B * kBatchCtrlBytes);
     std::vector<int32_t> nreq(B);
@@ -4025,6 +4225,7 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_d
     if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (!bs->walked) return fail(c, CPPROB_HIP_ESTATE, "the statistics wait for an advance with readout = 1 (cpprob_hip_batch_advance)");
     const int64_t B = (int64_t)bs->cfg.n_problems, per = (int64_t)bs->T * bs->K;
     if (n_doubles < (size_t)(B * (4 + per))) return fail(c, CPPROB_HIP_EINVAL, "d_out too small: n_problems * (4 + n_predict * stats_per_predict) doubles");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -4052,9 +4253,9 @@ int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_
     if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->d_ws + bs->lay.anc + first * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (h_values) for (size_t i = 0; i < T * n; ++i) h_values[i] = v[i];
-    if (h_logw) {
+    if (h_logw && T > 0) {
         // the final weights are table values: ll of the last step at the particle's state (what cpprob_hip_copy_logw returns)
-        const double* row = &bs->h_tab[((size_t)problem * (size_t)bs->T + (T - 1)) * kBatchTab];
+        const double* row = bs->tab_host() + ((size_t)problem * (size_t)bs->T + (T - 1)) * kBatchTab;
         for (size_t i = 0; i < n; ++i) h_logw[i] = row[(int)v[(T - 1) * n + i]];
     }
     return 0;

@@ -14,7 +14,9 @@
 //                   index; one estimate a line, one JSON object a line under --json)
 //                   --batch_tables_file F (smc, no --model: one table-weight HMM problem a line, "[means...] [transition, row-major...]
 //                   [observes...]"; tables and lengths may differ from line to line; all in one batched launch, seeds and output as above)
+//                   --stream_chunk K (with --batch_tables_file: the observes are fed K a problem at a time, one launch a chunk; same output)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdlib>
@@ -36,6 +38,7 @@ struct Args {
     bool sis = false, smc = false, estimate = false, json = false;
     int repeat = 1;
     std::size_t n_samples = 10000;            // src/main.cpp:166
+    std::size_t stream_chunk = 0;             // --batch_tables_file: feed every problem's observes this many at a time (0: all at once)
 };
 
 void print_json(const cpprob::gpu::Result& r)
@@ -134,7 +137,24 @@ int execute_batch_tables(const Args& a)
         seeds.push_back(cpprob::gpu::options().seed + at);
     }
     if (tables.empty()) { std::cerr << "no problems in " << a.batch_tables_file << std::endl; return EXIT_FAILURE; }
-    const std::vector<cpprob::gpu::Result> res = cpprob::gpu::hmm_table_batch(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds);
+    std::vector<cpprob::gpu::Result> res;
+    if (a.stream_chunk == 0) res = cpprob::gpu::hmm_table_batch(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds);
+    else {
+        // --stream_chunk K: the same batch fed K observes a problem at a time (cpprob::gpu::HmmTableStream); the last chunk may be
+        // shorter, a problem that has run out gets none, and only the last advance does the read-out.  The output is the same.
+        std::vector<std::size_t> cap;
+        std::size_t longest = 0;
+        for (const auto& o : observes) { cap.push_back(o.size()); longest = std::max(longest, o.size()); }
+        cpprob::gpu::HmmTableStream stream(tables, cap, std::vector<std::size_t>{a.n_samples}, seeds);
+        for (std::size_t at = 0; at < longest; at += a.stream_chunk) {
+            std::vector<std::vector<double>> piece(observes.size());
+            for (std::size_t b = 0; b < observes.size(); ++b) {
+                const std::size_t lo = std::min(at, observes[b].size()), hi = std::min(at + a.stream_chunk, observes[b].size());
+                piece[b].assign(observes[b].begin() + static_cast<std::ptrdiff_t>(lo), observes[b].begin() + static_cast<std::ptrdiff_t>(hi));
+            }
+            res = stream.advance(piece, at + a.stream_chunk >= longest);
+        }
+    }
     std::cout.precision(17);
     for (const cpprob::gpu::Result& r : res) {
         if (a.json) { print_json(r); continue; }
@@ -199,6 +219,7 @@ int main(int argc, char** argv)
         else if (f == "--observes_file") a.observes_file = next();
         else if (f == "--batch_observes_file") a.batch_observes_file = next();   // one problem a line, one batched launch (built-in HMMs, smc)
         else if (f == "--batch_tables_file") a.batch_tables_file = next();       // one table-HMM problem a line: [means] [transition] [observes]
+        else if (f == "--stream_chunk") a.stream_chunk = std::stoull(next());    // --batch_tables_file: the observes arrive this many at a time
         else if (f == "--generated_file") a.generated_file = next();
         else if (f == "--seed") opt.seed = std::stoull(next());
         else if (f == "--ess_threshold") opt.ess_threshold = std::stod(next());

@@ -695,6 +695,103 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
     return out;
 }
 
+// ---- the same problems with observes that arrive over time (cpprob_hip_batch_begin_online / _advance) ----
+// Constructed from what hmm_table_batch takes, with capacities (the most observes a problem may reach) in the observes' place; the
+// number of problems is seeds.size(), and tables, capacities and n of size 1 are shared by all.  advance() hands problem b its new
+// observes (new_observes[b], possibly empty; one entry per problem), runs the new steps only and returns every problem's result so
+// far: bit for bit what hmm_table_batch returns for the observes seen so far.  A problem without observes has no predicts yet.
+// readout = false (keep_history only) leaves the smoothed predicts to a later advance and returns results without predicts; an
+// advance of empty sequences with readout = true then returns them.  Options are read once, by the constructor.  The object holds
+// one context until it is destroyed.
+class HmmTableStream {
+public:
+    HmmTableStream(const std::vector<HmmTable>& tables, const std::vector<std::size_t>& capacities, const std::vector<std::size_t>& n,
+                   const std::vector<std::uint64_t>& seeds)
+        : B_(seeds.size()), k_(tables.empty() ? 0 : tables[0].means.size()), keep_(options().keep_history), lease_(options().device)
+    {
+        if (B_ == 0) throw std::runtime_error("cpprob::gpu::HmmTableStream: no problems (one seed per problem)");
+        const std::size_t B = B_;
+        auto fits = [B](std::size_t have) { return have == B || have == 1; };
+        if (!fits(tables.size()) || !fits(capacities.size()) || !fits(n.size()))
+            throw std::runtime_error("cpprob::gpu::HmmTableStream: tables, capacities and n hold one entry per seed, or one entry shared by all problems");
+        std::vector<double> means, trans;
+        std::vector<std::uint32_t> cap(B_);
+        np_.resize(B_);
+        std::size_t n_max = 0;
+        for (std::size_t b = 0; b < B_; ++b) {
+            const HmmTable& tb = tables[tables.size() == 1 ? 0 : b];
+            if (tb.means.size() != k_ || tb.transition.size() != k_ * k_)
+                throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
+            means.insert(means.end(), tb.means.begin(), tb.means.end());
+            trans.insert(trans.end(), tb.transition.begin(), tb.transition.end());
+            const std::size_t cb = capacities[capacities.size() == 1 ? 0 : b], nb = n[n.size() == 1 ? 0 : b];
+            if (cb > 0x7fffffffu || nb > 0x7fffffffu) throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": too large for a batch");
+            cap[b] = static_cast<std::uint32_t>(cb); np_[b] = static_cast<std::uint32_t>(nb);
+            T_max_ = std::max(T_max_, cb); n_max = std::max(n_max, nb);
+        }
+        const Options& opt = options();
+        cpprob_hip_batch_config bc{};
+        bc.algorithm = CPPROB_HIP_ALG_SMC;
+        bc.model = CPPROB_HIP_MODEL_HMM_TABLE;
+        bc.resampler = opt.resampler;
+        bc.keep_history = keep_ ? 1 : 0;
+        bc.flags = 0;
+        bc.ess_threshold = opt.ess_threshold;
+        bc.n_particles = n_max;
+        bc.n_problems = B_;
+        Context& ctx = *lease_;
+        ctx.check(cpprob_hip_batch_begin_online(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), seeds.data()),
+                  "cpprob_hip_batch_begin_online");
+        lease_.done();
+    }
+    HmmTableStream(const HmmTableStream&) = delete;
+    HmmTableStream& operator=(const HmmTableStream&) = delete;
+
+    std::vector<Result> advance(const std::vector<std::vector<double>>& new_observes, bool readout = true)
+    {
+        if (new_observes.size() != B_) throw std::runtime_error("cpprob::gpu::HmmTableStream: one (possibly empty) sequence of new observes per problem");
+        std::vector<std::uint32_t> dT(B_), L(B_);
+        std::vector<double> flat;
+        for (std::size_t b = 0; b < B_; ++b) {
+            if (new_observes[b].size() > 0x7fffffffu) throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": too large for a batch");
+            dT[b] = static_cast<std::uint32_t>(new_observes[b].size());
+            flat.insert(flat.end(), new_observes[b].begin(), new_observes[b].end());
+        }
+        Context& ctx = *lease_;
+        const auto t0 = std::chrono::steady_clock::now();
+        ctx.check(cpprob_hip_batch_advance(ctx.get(), dT.data(), flat.empty() ? nullptr : flat.data(), readout ? 1 : 0), "cpprob_hip_batch_advance");
+        ctx.check(cpprob_hip_batch_lengths(ctx.get(), L.data()), "cpprob_hip_batch_lengths");
+        const bool with_stats = readout || !keep_;
+        const std::size_t K = 8;
+        std::vector<cpprob_hip_summary> sums(B_);
+        std::vector<double> stats(with_stats ? B_ * T_max_ * K : 0), ess(B_ * T_max_);
+        ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), with_stats ? stats.data() : nullptr, stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+        const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::vector<Result> out(B_);
+        for (std::size_t b = 0; b < B_; ++b) {
+            Result& r = out[b];
+            const cpprob_hip_summary& s = sums[b];
+            r.n_particles = np_[b]; r.log_evidence = s.log_evidence; r.ess = s.ess_final; r.log_norm = s.log_norm; r.n_resampled = s.n_resampled;
+            r.used_builtin = true; r.step_form = s.step_form; r.run_seconds = seconds;
+            r.predicts.resize(with_stats ? L[b] : 0);
+            for (std::size_t t = 0; t < r.predicts.size(); ++t) {
+                PredictStats& p = r.predicts[t];
+                p.address = "state[" + std::to_string(t) + "]";
+                p.is_int = true;
+                p.probabilities.assign(stats.begin() + (b * T_max_ + t) * K, stats.begin() + (b * T_max_ + t) * K + k_);
+            }
+            r.step_ess.assign(ess.begin() + b * T_max_, ess.begin() + b * T_max_ + L[b]);
+        }
+        return out;
+    }
+
+private:
+    std::size_t B_, k_, T_max_ = 0;
+    bool keep_;
+    std::vector<std::uint32_t> np_;
+    ContextLease lease_;
+};
+
 }  // namespace gpu
 }  // namespace cpprob
 #endif

@@ -332,6 +332,42 @@ int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg
 int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
                                     const double* h_observes, int32_t k, const double* h_means, const double* h_transition);
 
+/* A batch whose observes arrive over time: a third way to begin, with capacities instead of lengths and without observes, followed by
+ * any number of cpprob_hip_batch_advance calls, each of which hands every problem zero or more new observes and runs the new steps
+ * only.  After any sequence of advances problem b has seen its first L_b observes, and everything the library returns for it --
+ * summaries, h_stats, h_ess, h_resampled, d_out, the particle store -- is bit for bit what a batch begun by
+ * cpprob_hip_batch_begin_problems with h_T[b] = L_b (same tables, particle counts and seeds) and run once returns: feeding T observes
+ * one at a time costs T steps, not T^2 / 2.  (In the shorter run generation L_b - 1 was final; the next piece re-keeps its books in the
+ * resampling form, resamples it with that junction's own Philox draw and goes on: csrc/batch_smc.hpp.)  A problem with L_b = 0 has no
+ * results yet: its rows are zero, its summary is zero and its n_predict is 0.  cpprob_hip_batch_results, _results_device and
+ * _copy_store serve the batch with lengths L_b and the padding T_max = max h_Tcap; cpprob_hip_batch_run returns CPPROB_HIP_ESTATE on
+ * it, as cpprob_hip_batch_advance and _lengths do on a batch begun the other ways.  Any begin replaces it; infer_* runs may interleave.
+ *
+ * Pure host function (no device, no context): validates as cpprob_hip_batch_problems_workspace_bytes does (same codes, same refusals;
+ * the capacities h_Tcap[b] >= 1 stand in for the lengths) and returns the device bytes.  The workspace is the twelve regions of a
+ * batch of problems of lengths h_Tcap (above), then, each rounded up to a multiple of 256 bytes: 4 B (every problem's first step of
+ * a launch), 32 B (the books before the last generation's final bookkeeping: what a later piece rewinds to) and, with
+ * keep_history = 0, N (the last generation's states, a byte a particle), N = sum over b of h_n[b]. */
+int cpprob_hip_batch_online_workspace_bytes(const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n, uint64_t* out_bytes);
+/* h_Tcap[B], h_n[B]; k, h_means and h_transition as for cpprob_hip_batch_begin_problems (both NULL: the context's cpprob_hip_set_hmm
+ * table; CPPROB_HIP_MODEL_HMM3: both NULL); h_seeds[B]: problem b's Philox key for the life of the batch.  Every problem starts at
+ * length 0.  Besides the device workspace the batch holds pinned host memory: a mirror of the per-step tables (64 B T_max bytes).
+ * Uploads and synchronises. */
+int cpprob_hip_batch_begin_online(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
+                                  int32_t k, const double* h_means, const double* h_transition, const uint64_t* h_seeds);
+/* Problem b receives h_dT[b] >= 0 new observes, packed in problem order in h_observes (NULL if every h_dT[b] is 0).  If some
+ * L_b + h_dT[b] exceeds h_Tcap[b]: CPPROB_HIP_EINVAL naming the problem, and nothing changes.  Otherwise the new steps' table rows are
+ * evaluated on the host (the begin's own statements) into the pinned mirror, copied stream-ordered, and ONE launch is enqueued; the
+ * call returns without waiting (h_dT and h_observes are consumed before it returns).  Workgroups are dispatched longest piece first
+ * (h_dT[b] * ceil(h_n[b] / 1024), ties by index); a problem without new observes costs a workgroup that returns at once.
+ * readout (keep_history = 1 only; ignored with keep_history = 0, whose books write every statistics row as they go): 1 ends the launch
+ * with the lineage walk over all L_b rows, as a one-shot run does; 0 skips it, and until an advance with readout = 1 has been
+ * enqueued cpprob_hip_batch_results with a non-NULL h_stats and cpprob_hip_batch_results_device return CPPROB_HIP_ESTATE (summaries,
+ * ESS, flags and the store are served).  That advance may have every h_dT[b] = 0: it then does the walk and nothing else. */
+int cpprob_hip_batch_advance(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const double* h_observes, int32_t readout);
+/* h_L[B]: the lengths reached so far (host state: no synchronisation). */
+int cpprob_hip_batch_lengths(cpprob_hip_ctx* ctx, uint32_t* h_L);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
