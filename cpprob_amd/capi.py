@@ -40,6 +40,7 @@ SYMBOLS = [
     "cpprob_hip_batch_workspace_bytes", "cpprob_hip_batch_begin", "cpprob_hip_batch_run", "cpprob_hip_batch_results", "cpprob_hip_batch_results_device",
     "cpprob_hip_batch_copy_store", "cpprob_hip_batch_problems_workspace_bytes", "cpprob_hip_batch_begin_problems",
     "cpprob_hip_batch_online_workspace_bytes", "cpprob_hip_batch_begin_online", "cpprob_hip_batch_advance", "cpprob_hip_batch_lengths",
+    "cpprob_hip_batch_paths_layout", "cpprob_hip_batch_paths", "cpprob_hip_batch_paths_device",
 ]
 
 
@@ -131,6 +132,25 @@ def batch_online_workspace_bytes(model, capacity, n_particles, max_particles=Non
         e.code = rc
         raise e
     return out.value
+
+
+def batch_paths_layout(T, n, max_particles=0):
+    """cpprob_hip_batch_paths_layout: where problem b's traces sit in the packed output of Engine.batch_paths /
+    batch_paths_device.  T[b], n[b]: its length (0 allowed) and particle count (an int: every problem's).  Returns (first, wfirst),
+    uint64 [B + 1]: problem b owns entries first[b]:first[b + 1] ([T_b, m_b], m_b = n_b or min(n_b, max_particles)) and weights
+    wfirst[b]:wfirst[b + 1].  No GPU needed."""
+    L = load_library()
+    h_T, h_n = _problem_shapes(T, n)
+    first = np.zeros(h_T.size + 1, np.uint64)
+    wfirst = np.zeros(h_T.size + 1, np.uint64)
+    rc = L.cpprob_hip_batch_paths_layout(h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), int(h_T.size), int(max_particles),
+                                         first.ctypes.data_as(C.POINTER(C.c_uint64)), wfirst.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc:
+        msg = L.cpprob_hip_last_error(None)
+        e = CpprobHipError("cpprob_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+        e.code = rc
+        raise e
+    return first, wfirst
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -270,6 +290,9 @@ def load_library(path=None):
         "cpprob_hip_batch_begin_online": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, vp, vp, C.POINTER(u64)]),
         "cpprob_hip_batch_advance": (C.c_int, [vp, C.POINTER(C.c_uint32), vp, C.c_int32]),
         "cpprob_hip_batch_lengths": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "cpprob_hip_batch_paths_layout": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, u64, C.POINTER(u64), C.POINTER(u64)]),
+        "cpprob_hip_batch_paths": (C.c_int, [vp, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_paths_device": (C.c_int, [vp, u64, vp, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -566,6 +589,34 @@ class Engine:
         logw = np.zeros(n)
         self._chk(self.L.cpprob_hip_batch_copy_store(self.h, int(b), vals.ctypes.data, anc.ctypes.data, logw.ctypes.data))
         return vals, anc, logw
+
+    def _batch_problem_shapes(self):
+        """(T uint32 [B], n uint32 [B]) of the batch last begun / advanced."""
+        if self.batch_shapes is not None:
+            return self.batch_shapes
+        return np.full(self.batch_B, self.batch_T, np.uint32), np.full(self.batch_B, self.batch_n, np.uint32)
+
+    def batch_paths(self, max_particles=0):
+        """The surviving lineages of every problem, resolved on the device in one launch (cpprob_hip_batch_paths): (paths, logw), two
+        lists with one entry per problem -- paths[b] int32 [T_b, m_b], the trajectory that ends in final particle i in column i, and
+        logw[b] float64 [m_b], its final log-weight; m_b = n_b, or min(n_b, max_particles).  A problem of length 0 (online batch)
+        returns [0, m_b] and [0]."""
+        h_T, h_n = self._batch_problem_shapes()
+        first, wfirst = batch_paths_layout(h_T, h_n, max_particles)
+        flat = np.zeros(int(first[-1]), np.int32)
+        w = np.zeros(int(wfirst[-1]))
+        self._chk(self.L.cpprob_hip_batch_paths(self.h, int(max_particles), flat.ctypes.data, flat.size, w.ctypes.data, w.size))
+        paths, logw = [], []
+        for b in range(self.batch_B):
+            m = int(h_n[b]) if not max_particles else min(int(h_n[b]), int(max_particles))
+            paths.append(flat[int(first[b]):int(first[b + 1])].reshape(int(h_T[b]), m))
+            logw.append(w[int(wfirst[b]):int(wfirst[b + 1])])
+        return paths, logw
+
+    def batch_paths_device(self, paths_i8, logw=None, max_particles=0):
+        """The same left in device tensors, enqueued behind the run / advance without a host synchronisation: paths_i8 torch int8,
+        logw torch float64 or None, packed as batch_paths_layout(T, n, max_particles) says (their numel() are the capacities)."""
+        self._chk(self.L.cpprob_hip_batch_paths_device(self.h, int(max_particles), _dptr(paths_i8), paths_i8.numel(), _dptr(logw), 0 if logw is None else logw.numel()))
 
     # ---- sharded SMC ---------------------------------------------------------------------
     def step_begin(self, t, local_totals, run_index=0):

@@ -20,6 +20,7 @@
 #include "trace_words.hpp"
 #include "device_collectives.hpp"
 #include "batch_smc.hpp"
+#include "batch_paths.hpp"
 
 using namespace cph;
 
@@ -1058,6 +1059,13 @@ struct BatchState {
     char* pin_desc = nullptr; size_t pin_desc_cap = 0, slot_bytes = 0;
     hipEvent_t slot_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_advance = 0;
+    // posterior traces (cpprob_hip_batch_paths, _paths_device; csrc/batch_paths.hpp): the problems' descriptors on the device, their
+    // pinned sources (kOnlineSlots in turn, as an advance's) and the host variant's device staging; none of it in the workspace
+    char* d_pdesc = nullptr; size_t pdesc_cap = 0;
+    char* pin_pdesc = nullptr;
+    hipEvent_t pdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
+    uint64_t n_paths = 0;
+    char* d_stage = nullptr; size_t stage_cap = 0;
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -1068,6 +1076,9 @@ void batch_free(cpprob_hip_ctx* c)
     if (c->batch->pin_tab) (void)hipHostFree(c->batch->pin_tab);
     if (c->batch->pin_desc) (void)hipHostFree(c->batch->pin_desc);
     for (hipEvent_t e : c->batch->slot_done) if (e) (void)hipEventDestroy(e);
+    dfree(c->batch->d_pdesc); dfree(c->batch->d_stage);
+    if (c->batch->pin_pdesc) (void)hipHostFree(c->batch->pin_pdesc);
+    for (hipEvent_t e : c->batch->pdesc_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
     c->batch = nullptr;
 }
@@ -1234,6 +1245,10 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
+
+// The packed layout of a batch's traces (cpprob_hip_batch_paths_layout): problem b's T_b x m_b entries from first[b] on and its m_b
+// weights from wfirst[b] on, m_b = n_b or min(n_b, max_particles); a problem of length 0 owns neither.  first[B] / wfirst[B]: the totals.
+inline uint64_t batch_paths_m(uint64_t n, uint64_t max_particles) { return max_particles && max_particles < n ? max_particles : n; }
 
 // The eight kernels of cpprob_hip_batch_run, and the eight of cpprob_hip_batch_advance.
 using BatchKernel = void (*)(BatchArgs);
@@ -4258,6 +4273,127 @@ int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_
         const double* row = bs->tab_host() + ((size_t)problem * (size_t)bs->T + (T - 1)) * kBatchTab;
         for (size_t i = 0; i < n; ++i) h_logw[i] = row[(int)v[(T - 1) * n + i]];
     }
+    return 0;
+}
+
+// ---- posterior traces of a batch (csrc/batch_paths.hpp) ---------------------------------------------------------------------------
+int cpprob_hip_batch_paths_layout(const uint32_t* h_T, const uint32_t* h_n, uint64_t n_problems, uint64_t max_particles, uint64_t* h_first, uint64_t* h_wfirst)
+{
+    if (!h_T || !h_n) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
+    if (n_problems == 0) return fail(nullptr, CPPROB_HIP_EINVAL, "n_problems must be at least 1");
+    for (uint64_t b = 0; b < n_problems; ++b)
+        if (h_n[b] == 0 || h_n[b] > (uint32_t)kBatchMaxN)
+            return fail(nullptr, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": its particle count must lie in 1 .. " + std::to_string(kBatchMaxN));
+    uint64_t first = 0, wfirst = 0;
+    for (uint64_t b = 0; b < n_problems; ++b) {
+        if (h_first) h_first[b] = first;
+        if (h_wfirst) h_wfirst[b] = wfirst;
+        const uint64_t m = batch_paths_m(h_n[b], max_particles);
+        first += (uint64_t)h_T[b] * m;
+        wfirst += h_T[b] ? m : 0;
+    }
+    if (h_first) h_first[n_problems] = first;
+    if (h_wfirst) h_wfirst[n_problems] = wfirst;
+    return 0;
+}
+
+// The state a batch's traces need (as cpprob_hip_batch_copy_store), then the packed totals against the caller's capacities.
+static int batch_paths_check(cpprob_hip_ctx* c, uint64_t max_particles, size_t n_entries, bool with_logw, size_t n_weights, uint64_t& entries, uint64_t& weights)
+{
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->cfg.keep_history != 1) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
+    entries = 0; weights = 0;
+    for (const BatchProblem& pr : bs->prob) {
+        const uint64_t m = batch_paths_m((uint64_t)pr.n, max_particles);
+        entries += (uint64_t)pr.T * m;
+        weights += pr.T ? m : 0;
+    }
+    if (n_entries < entries) return fail(c, CPPROB_HIP_EINVAL, "the paths buffer is too small: " + std::to_string(entries) + " entries (cpprob_hip_batch_paths_layout)");
+    if (with_logw && n_weights < weights) return fail(c, CPPROB_HIP_EINVAL, "the log-weight buffer is too small: " + std::to_string(weights) + " weights (cpprob_hip_batch_paths_layout)");
+    return 0;
+}
+
+// Enqueues the descriptors' copy and the walk on the context's stream; waits for nothing but the pinned slot it writes (the copy
+// that read it kOnlineSlots calls ago).
+static int batch_paths_enqueue(cpprob_hip_ctx* c, uint64_t max_particles, int8_t* d_paths, double* d_logw)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems, bytes = batch_round(B * sizeof(BatchPathsProblem));
+    if (bytes > bs->pdesc_cap) {
+        // (earlier calls' copies may still read the buffers this replaces)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        dfree(bs->d_pdesc); bs->pdesc_cap = 0;
+        if (bs->pin_pdesc) { (void)hipHostFree(bs->pin_pdesc); bs->pin_pdesc = nullptr; }
+        HIP_TRY(c, hipMalloc(&bs->d_pdesc, bytes));
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_pdesc), bytes * BatchState::kOnlineSlots, hipHostMallocDefault));
+        for (hipEvent_t& e : bs->pdesc_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        bs->pdesc_cap = bytes; bs->n_paths = 0;
+    }
+    const int slot = (int)(bs->n_paths % BatchState::kOnlineSlots);
+    if (bs->n_paths >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->pdesc_done[slot]));
+    BatchPathsProblem* pd = reinterpret_cast<BatchPathsProblem*>(bs->pin_pdesc + (size_t)slot * bs->pdesc_cap);
+    int64_t first = 0, wfirst = 0;
+    int m_top = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const BatchProblem& pr = bs->prob[b];
+        const int m = (int)batch_paths_m((uint64_t)pr.n, max_particles);
+        pd[b].T = pr.T; pd[b].n = pr.n; pd[b].m = m; pd[b].pad_ = 0;
+        pd[b].store = pr.store; pd[b].first = first; pd[b].wfirst = wfirst;
+        first += (int64_t)pr.T * m;
+        if (pr.T) { wfirst += m; m_top = std::max(m_top, m); }
+    }
+    if (m_top == 0) return 0;                                  // (an online batch before its first observes: nothing to resolve)
+    HIP_TRY(c, hipMemcpyAsync(bs->d_pdesc, pd, B * sizeof(BatchPathsProblem), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(bs->pdesc_done[slot], c->stream));
+    ++bs->n_paths;
+    BatchPathsArgs a{};
+    a.desc = reinterpret_cast<const BatchPathsProblem*>(bs->d_pdesc);
+    a.values = reinterpret_cast<const int8_t*>(bs->d_ws + bs->lay.values);
+    a.anc = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.anc);
+    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
+    a.paths = d_paths; a.logw = d_logw; a.T_max = bs->T;
+    hipLaunchKernelGGL(batch_paths_kernel, dim3((unsigned)B, (unsigned)((m_top + kTile - 1) / kTile)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_paths_device(cpprob_hip_ctx* c, uint64_t max_particles, int8_t* d_paths, size_t n_entries, double* d_logw, size_t n_weights)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t entries = 0, weights = 0;
+    if (int rc = batch_paths_check(c, max_particles, n_entries, d_logw != nullptr, n_weights, entries, weights)) return rc;
+    if (!d_paths && entries) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_paths_enqueue(c, max_particles, d_paths, d_logw);
+}
+
+int cpprob_hip_batch_paths(cpprob_hip_ctx* c, uint64_t max_particles, int32_t* h_paths, size_t n_entries, double* h_logw, size_t n_weights)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t entries = 0, weights = 0;
+    if (int rc = batch_paths_check(c, max_particles, n_entries, h_logw != nullptr, n_weights, entries, weights)) return rc;
+    if (!h_paths && entries) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (entries == 0) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchState* bs = c->batch;
+    // device staging: the weights (8-byte aligned) in front of the int8 entries
+    const size_t w_bytes = batch_round((h_logw ? (size_t)weights : 0) * sizeof(double)), need = w_bytes + (size_t)entries;
+    if (need > bs->stage_cap) {
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
+        bs->stage_cap = need;
+    }
+    double* d_logw = h_logw ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
+    int8_t* d_paths = reinterpret_cast<int8_t*>(bs->d_stage + w_bytes);
+    if (int rc = batch_paths_enqueue(c, max_particles, d_paths, d_logw)) return rc;
+    std::vector<int8_t> v((size_t)entries);
+    HIP_TRY(c, hipMemcpyAsync(v.data(), d_paths, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
+    if (h_logw) HIP_TRY(c, hipMemcpyAsync(h_logw, d_logw, (size_t)weights * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < (size_t)entries; ++i) h_paths[i] = v[i];
     return 0;
 }
 }  // extern "C"

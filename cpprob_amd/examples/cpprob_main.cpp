@@ -9,12 +9,14 @@
 //                   --gpus N | --devices a,b,...  (one joint population sharded over several GPUs: exact global resampling, RCCL over xGMI;
 //                                                  equal entries, e.g. 0,0,0: every rank on that GPU)
 //                   --filtering_only (smc, built-in models: O(N) particle store, filtering statistics, no posterior files)
-//                   --no_dump  --json (print the in-memory result as one JSON line)
+//                   --no_dump  --dump_max_particles M  --json (print the in-memory result as one JSON line)
 //                   --batch_observes_file F (smc, built-in HMMs: one observation sequence a line, all in one batched launch; seeds --seed + line
 //                   index; one estimate a line, one JSON object a line under --json)
 //                   --batch_tables_file F (smc, no --model: one table-weight HMM problem a line, "[means...] [transition, row-major...]
 //                   [observes...]"; tables and lengths may differ from line to line; all in one batched launch, seeds and output as above)
 //                   --stream_chunk K (with --batch_tables_file: the observes are fed K a problem at a time, one launch a chunk; same output)
+//                   --batch_dump (both batch modes and --stream_chunk: problem b's posterior traces as <model_folder>/<generated_file>_smc_<b>.int / .ids,
+//                   the files of a single run of that problem; resolved on the device in one launch)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <algorithm>
 #include <array>
@@ -35,7 +37,7 @@ namespace {
 
 struct Args {
     std::string model, model_folder = ".", observes, observes_file, generated_file = "post", batch_observes_file, batch_tables_file;
-    bool sis = false, smc = false, estimate = false, json = false;
+    bool sis = false, smc = false, estimate = false, json = false, batch_dump = false;
     int repeat = 1;
     std::size_t n_samples = 10000;            // src/main.cpp:166
     std::size_t stream_chunk = 0;             // --batch_tables_file: feed every problem's observes this many at a time (0: all at once)
@@ -98,6 +100,7 @@ int execute_batch(const F& model, const Args& a)
         seeds.push_back(cpprob::gpu::options().seed + observes.size());
         observes.push_back(o);
     }
+    if (a.batch_dump) cpprob::gpu::options().batch_dump_file = a.model_folder + "/" + a.generated_file + "_smc";
     const std::vector<cpprob::gpu::Result> res = cpprob::gpu::inference_batch(cpprob::StateType::smc, model, observes, a.n_samples, seeds);
     std::cout.precision(17);
     for (const cpprob::gpu::Result& r : res) {
@@ -138,6 +141,8 @@ int execute_batch_tables(const Args& a)
     }
     if (tables.empty()) { std::cerr << "no problems in " << a.batch_tables_file << std::endl; return EXIT_FAILURE; }
     std::vector<cpprob::gpu::Result> res;
+    const std::string dump_prefix = a.model_folder + "/" + a.generated_file + "_smc";
+    if (a.batch_dump && a.stream_chunk == 0) cpprob::gpu::options().batch_dump_file = dump_prefix;
     if (a.stream_chunk == 0) res = cpprob::gpu::hmm_table_batch(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds);
     else {
         // --stream_chunk K: the same batch fed K observes a problem at a time (cpprob::gpu::HmmTableStream); the last chunk may be
@@ -154,6 +159,7 @@ int execute_batch_tables(const Args& a)
             }
             res = stream.advance(piece, at + a.stream_chunk >= longest);
         }
+        if (a.batch_dump) stream.dump(dump_prefix);
     }
     std::cout.precision(17);
     for (const cpprob::gpu::Result& r : res) {
@@ -220,6 +226,8 @@ int main(int argc, char** argv)
         else if (f == "--batch_observes_file") a.batch_observes_file = next();   // one problem a line, one batched launch (built-in HMMs, smc)
         else if (f == "--batch_tables_file") a.batch_tables_file = next();       // one table-HMM problem a line: [means] [transition] [observes]
         else if (f == "--stream_chunk") a.stream_chunk = std::stoull(next());    // --batch_tables_file: the observes arrive this many at a time
+        else if (f == "--batch_dump") a.batch_dump = true;                         // the batch modes: problem b's traces as <generated_file>_smc_<b>.int / .ids
+        else if (f == "--dump_max_particles") opt.dump_max_particles = std::stoull(next());   // the posterior files hold the first M traces only (0: all)
         else if (f == "--generated_file") a.generated_file = next();
         else if (f == "--seed") opt.seed = std::stoull(next());
         else if (f == "--ess_threshold") opt.ess_threshold = std::stod(next());

@@ -556,9 +556,42 @@ void run_inference(StateType algorithm, const Func& f, const std::tuple<Args...>
     if (opt.dump) dump_posterior(file, st, hs, opt.dump_max_particles);      // finish_trace() x n + finish_infer()
 }
 
+// ---- posterior files of a batch: problem b's traces as <prefix>_<b>.int / .ids --------------------------------------------------
+// One cpprob_hip_batch_paths call resolves every problem's first m_b = min(n_b, max_particles) lineages on the device; problem b's
+// share of the packed result fills a HostStore and goes through dump_posterior with structure(b)'s addresses.  T[b], n[b]: the
+// lengths and particle counts of the batch last run on ctx.  A problem without observes writes no .int file.
+template <class Structure>
+void dump_batch_posterior(Context& ctx, const std::string& prefix, const std::vector<std::uint32_t>& T, const std::vector<std::uint32_t>& n,
+                          std::size_t max_particles, const Structure& structure)
+{
+    const std::size_t B = T.size();
+    std::vector<std::uint64_t> first(B + 1), wfirst(B + 1);
+    if (cpprob_hip_batch_paths_layout(T.data(), n.data(), B, max_particles, first.data(), wfirst.data()))
+        throw std::runtime_error(std::string("cpprob_hip_batch_paths_layout: ") + cpprob_hip_last_error(nullptr));
+    std::vector<std::int32_t> paths(static_cast<std::size_t>(first[B]));
+    std::vector<double> logw(static_cast<std::size_t>(wfirst[B]));
+    ctx.check(cpprob_hip_batch_paths(ctx.get(), max_particles, paths.data(), paths.size(), logw.data(), logw.size()), "cpprob_hip_batch_paths");
+    for (std::size_t b = 0; b < B; ++b) {
+        const std::size_t m = (max_particles && max_particles < n[b]) ? max_particles : n[b];
+        HostStore hs;
+        hs.n = T[b] ? m : 0;
+        hs.ints.assign(paths.begin() + static_cast<std::ptrdiff_t>(first[b]), paths.begin() + static_cast<std::ptrdiff_t>(first[b + 1]));
+        hs.logw.assign(logw.begin() + static_cast<std::ptrdiff_t>(wfirst[b]), logw.begin() + static_cast<std::ptrdiff_t>(wfirst[b + 1]));
+        dump_posterior(prefix + "_" + std::to_string(b), structure(b), hs, 0);
+    }
+}
+
+// The trace structure of a table-HMM problem of T observes: one int predict per observe, "state[t]".
+inline detail::TraceStructure hmm_table_structure(std::size_t T)
+{
+    detail::TraceStructure st;
+    for (std::size_t t = 0; t < T; ++t) st.int_ids.push_back(st.id_of("state[" + std::to_string(t) + "]"));
+    return st;
+}
+
 // ---- many problems of one model in ONE launch (cpprob_hip_batch_*): models bound by CPPROB_REGISTER_BUILTIN to the table-weight HMMs ----
 // observes[b] is problem b's observes tuple (all of one length), seeds[b] its Philox key: result b is what cpprob::inference with
-// options().seed = seeds[b] computes (no posterior files).  Resampler, keep_history (false: filtering statistics), ess_threshold (must
+// options().seed = seeds[b] computes (posterior files: options().batch_dump_file, problem b's as <batch_dump_file>_<b>.int / .ids).  Resampler, keep_history (false: filtering statistics), ess_threshold (must
 // be > 1: every step) and device come from options(), as for cpprob::inference.
 template <class Func, class... Args>
 std::vector<Result> inference_batch(StateType algorithm, const Func& f, const std::vector<std::tuple<Args...>>& observes, std::size_t n,
@@ -588,6 +621,8 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     }
     if (st.int_ids.size() != T) throw std::runtime_error("built-in model kernel and the model function disagree on the number of predict statements");
     const Options& opt = options();
+    if (!opt.keep_history && !opt.batch_dump_file.empty())
+        throw std::runtime_error("cpprob::gpu::inference_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -608,6 +643,9 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     std::vector<double> stats(B * T * K), ess(B * T);
     ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!opt.batch_dump_file.empty())
+        dump_batch_posterior(ctx, opt.batch_dump_file, std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(T)), std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(n)),
+                             opt.dump_max_particles, [&st](std::size_t) -> const detail::TraceStructure& { return st; });
     lease.done();
     std::vector<Result> out(B);
     for (std::size_t b = 0; b < B; ++b) {
@@ -656,6 +694,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
         T_max = std::max(T_max, o.size()); n_max = std::max(n_max, nb);
     }
     const Options& opt = options();
+    if (!opt.keep_history && !opt.batch_dump_file.empty())
+        throw std::runtime_error("cpprob::gpu::hmm_table_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -676,6 +716,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
     std::vector<double> stats(B * T_max * K), ess(B * T_max);
     ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (!opt.batch_dump_file.empty())
+        dump_batch_posterior(ctx, opt.batch_dump_file, T, np, opt.dump_max_particles, [&T](std::size_t b) { return hmm_table_structure(T[b]); });
     lease.done();
     std::vector<Result> out(B);
     for (std::size_t b = 0; b < B; ++b) {
@@ -701,7 +743,9 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // observes (new_observes[b], possibly empty; one entry per problem), runs the new steps only and returns every problem's result so
 // far: bit for bit what hmm_table_batch returns for the observes seen so far.  A problem without observes has no predicts yet.
 // readout = false (keep_history only) leaves the smoothed predicts to a later advance and returns results without predicts; an
-// advance of empty sequences with readout = true then returns them.  Options are read once, by the constructor.  The object holds
+// advance of empty sequences with readout = true then returns them.  dump(prefix) writes every problem's posterior traces for the
+// lengths reached, as hmm_table_batch does for options().batch_dump_file (whether or not the last advance did its read-out).
+// Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
 public:
@@ -785,9 +829,20 @@ public:
         return out;
     }
 
+    // Problem b's posterior as <prefix>_<b>.int / .ids for the lengths reached: the first dump_max_ traces (0 = all).
+    void dump(const std::string& prefix)
+    {
+        if (!keep_) throw std::runtime_error("cpprob::gpu::HmmTableStream: a filtering-only run (options().keep_history = false) keeps no traces to dump");
+        Context& ctx = *lease_;
+        std::vector<std::uint32_t> L(B_);
+        ctx.check(cpprob_hip_batch_lengths(ctx.get(), L.data()), "cpprob_hip_batch_lengths");
+        dump_batch_posterior(ctx, prefix, L, np_, dump_max_, [&L](std::size_t b) { return hmm_table_structure(L[b]); });
+    }
+
 private:
     std::size_t B_, k_, T_max_ = 0;
     bool keep_;
+    std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;
 };

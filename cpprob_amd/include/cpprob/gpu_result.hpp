@@ -27,6 +27,9 @@ struct Options {
     double ess_threshold = 0.5;                       // smc: resample when ESS < threshold * N (thesis p.37); > 1: every step
     bool dump = true;                                 // write <file>.real/.int/.ids like the reference (state.cpp:193-202)
     std::size_t dump_max_particles = 0;               // 0 = all particles
+    std::string batch_dump_file;                      // batched runs (inference_batch, hmm_table_batch): not empty = write problem b's posterior as
+                                                      // <batch_dump_file>_<b>.int / .ids, the first dump_max_particles traces (0 = all) resolved on
+                                                      // the device in one launch (cpprob_hip_batch_paths); empty: no files
     bool markov_probe = true;                         // smc, unchanged-model path: test on the host whether a step depends on more than the last few
                                                       // sampled values; a model that does not is replayed from that window only (O(T) instead of O(T^2))
     bool markov_crosscheck = true;                    // ... and certify the probe's window on the device before using it: a pilot population under windowed

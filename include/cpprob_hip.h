@@ -368,6 +368,29 @@ int cpprob_hip_batch_advance(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const do
 /* h_L[B]: the lengths reached so far (host state: no synchronisation). */
 int cpprob_hip_batch_lengths(cpprob_hip_ctx* ctx, uint32_t* h_L);
 
+/* Posterior traces of a batch: the surviving lineages of EVERY problem of the batch last run (or last advanced), resolved by ONE
+ * launch (csrc/batch_paths.hpp) -- what cpprob_hip_copy_paths delivers for a single population.  For final particle i < m_b of
+ * problem b, entry [t][i] is the state at step t of the trajectory that ends in particle i, and weight [i] is its final log-weight:
+ * the table double cpprob_hip_batch_copy_store returns, bit for bit.  m_b = n_b when max_particles is 0, else min(n_b, max_particles):
+ * the first m_b traces only (Options::dump_max_particles), so that a few traces of many problems do not move the whole store.
+ * The output is packed: problem b's [T_b][m_b] entries start at first_b = sum over b' < b of T_b' m_b' and its m_b weights at
+ * wfirst_b = sum over b' < b with T_b' > 0 of m_b'; T_b = h_T[b] (a uniform batch: T), an online batch: the length
+ * cpprob_hip_batch_lengths reports, served whether or not the last advance did its read-out.  A problem of length 0 owns neither
+ * entries nor weights.  keep_history = 1 only, and only after a run (else CPPROB_HIP_ESTATE, as cpprob_hip_batch_copy_store).
+ *
+ * Pure host function (no device, no context): the packed layout.  h_first[B + 1] (entries) and h_wfirst[B + 1] (weights), the last
+ * element the total; either may be NULL.  h_T[b] may be 0.  CPPROB_HIP_EINVAL: NULL h_T / h_n, n_problems == 0, an h_n[b] of 0 or
+ * above 8192. */
+int cpprob_hip_batch_paths_layout(const uint32_t* h_T, const uint32_t* h_n, uint64_t n_problems, uint64_t max_particles,
+                                  uint64_t* h_first, uint64_t* h_wfirst);
+/* Host copies: h_paths int32 (cpprob_hip_copy_paths' element type), n_entries / n_weights the capacities in elements
+ * (CPPROB_HIP_EINVAL when too small, nothing written); h_logw may be NULL.  Stages int8 on the device and widens.  Synchronises. */
+int cpprob_hip_batch_paths(cpprob_hip_ctx* ctx, uint64_t max_particles, int32_t* h_paths, size_t n_entries, double* h_logw, size_t n_weights);
+/* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation: d_paths int8 (the
+ * store's own element), d_logw may be NULL.  (The problems' descriptors travel through pinned host memory, four calls deep: the
+ * fifth call in a row waits for the first one's copy, nothing else.) */
+int cpprob_hip_batch_paths_device(cpprob_hip_ctx* ctx, uint64_t max_particles, int8_t* d_paths, size_t n_entries, double* d_logw, size_t n_weights);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
