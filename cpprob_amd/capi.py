@@ -41,6 +41,7 @@ SYMBOLS = [
     "cpprob_hip_batch_copy_store", "cpprob_hip_batch_problems_workspace_bytes", "cpprob_hip_batch_begin_problems",
     "cpprob_hip_batch_online_workspace_bytes", "cpprob_hip_batch_begin_online", "cpprob_hip_batch_advance", "cpprob_hip_batch_lengths",
     "cpprob_hip_batch_paths_layout", "cpprob_hip_batch_paths", "cpprob_hip_batch_paths_device",
+    "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
 ]
 
 
@@ -151,6 +152,22 @@ def batch_paths_layout(T, n, max_particles=0):
         e.code = rc
         raise e
     return first, wfirst
+
+
+def batch_smooth_layout(T, n_traj):
+    """cpprob_hip_batch_smooth_layout: where problem b's backward trajectories sit in the packed output of Engine.batch_smooth /
+    batch_smooth_device.  T[b]: its length (0 allowed).  Returns first, uint64 [B + 1]: problem b owns entries first[b]:first[b + 1]
+    ([T_b, n_traj]).  No GPU needed."""
+    L = load_library()
+    h_T = np.ascontiguousarray(T, np.uint32).reshape(-1)
+    first = np.zeros(h_T.size + 1, np.uint64)
+    rc = L.cpprob_hip_batch_smooth_layout(h_T.ctypes.data_as(C.POINTER(C.c_uint32)), int(h_T.size), int(n_traj), first.ctypes.data_as(C.POINTER(C.c_uint64)))
+    if rc:
+        msg = L.cpprob_hip_last_error(None)
+        e = CpprobHipError("cpprob_hip error %d: %s" % (rc, msg.decode() if msg else "?"))
+        e.code = rc
+        raise e
+    return first
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -293,6 +310,9 @@ def load_library(path=None):
         "cpprob_hip_batch_paths_layout": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64, u64, C.POINTER(u64), C.POINTER(u64)]),
         "cpprob_hip_batch_paths": (C.c_int, [vp, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_paths_device": (C.c_int, [vp, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_smooth_layout": (C.c_int, [C.POINTER(C.c_uint32), u64, u64, C.POINTER(u64)]),
+        "cpprob_hip_batch_smooth": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_smooth_device": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -617,6 +637,24 @@ class Engine:
         """The same left in device tensors, enqueued behind the run / advance without a host synchronisation: paths_i8 torch int8,
         logw torch float64 or None, packed as batch_paths_layout(T, n, max_particles) says (their numel() are the capacities)."""
         self._chk(self.L.cpprob_hip_batch_paths_device(self.h, int(max_particles), _dptr(paths_i8), paths_i8.numel(), _dptr(logw), 0 if logw is None else logw.numel()))
+
+    def batch_smooth(self, n_traj=0, draw_index=0):
+        """Backward smoothing of every problem (cpprob_hip_batch_smooth): (marginals [B, T_max, spp], the layout of batch_results'
+        stats, and a list of int32 [T_b, n_traj] arrays, problem b's backward-simulated trajectories in its columns).  draw_index
+        (< 2^16) selects the trajectories' Philox draws: another index, other trajectories; the marginals do not depend on it."""
+        h_T, _ = self._batch_problem_shapes()
+        first = batch_smooth_layout(h_T, n_traj)
+        marg = np.zeros((self.batch_B, self.batch_T, self.batch_K))
+        flat = np.zeros(int(first[-1]), np.int32)
+        self._chk(self.L.cpprob_hip_batch_smooth(self.h, int(n_traj), int(draw_index), marg.ctypes.data, marg.size, flat.ctypes.data if n_traj else None, flat.size))
+        return marg, [flat[int(first[b]):int(first[b + 1])].reshape(int(h_T[b]), int(n_traj)) for b in range(self.batch_B)]
+
+    def batch_smooth_device(self, marginals=None, traj_i8=None, n_traj=0, draw_index=0):
+        """The same left in device tensors, enqueued behind the run / advance without a host synchronisation: marginals torch float64
+        [B, T_max, spp] or None, traj_i8 torch int8 packed as batch_smooth_layout(T, n_traj) says or None (their numel() are the
+        capacities)."""
+        self._chk(self.L.cpprob_hip_batch_smooth_device(self.h, int(n_traj), int(draw_index), _dptr(marginals), 0 if marginals is None else marginals.numel(),
+                                                        _dptr(traj_i8), 0 if traj_i8 is None else traj_i8.numel()))
 
     # ---- sharded SMC ---------------------------------------------------------------------
     def step_begin(self, t, local_totals, run_index=0):

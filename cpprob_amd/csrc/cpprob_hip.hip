@@ -21,6 +21,7 @@
 #include "device_collectives.hpp"
 #include "batch_smc.hpp"
 #include "batch_paths.hpp"
+#include "batch_smooth.hpp"
 
 using namespace cph;
 
@@ -1066,6 +1067,13 @@ struct BatchState {
     hipEvent_t pdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_paths = 0;
     char* d_stage = nullptr; size_t stage_cap = 0;
+    // backward smoothing (cpprob_hip_batch_smooth, _smooth_device; csrc/batch_smooth.hpp): the m table ([sum of T_b][8] doubles, grown
+    // lazily), the problems' descriptors with the HMM3 thresholds behind them, and their pinned sources, kOnlineSlots in turn
+    double* d_mass = nullptr; size_t mass_rows = 0;
+    char* d_sdesc = nullptr; size_t sdesc_cap = 0;
+    char* pin_sdesc = nullptr;
+    hipEvent_t sdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
+    uint64_t n_smooth = 0;
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -1079,6 +1087,9 @@ void batch_free(cpprob_hip_ctx* c)
     dfree(c->batch->d_pdesc); dfree(c->batch->d_stage);
     if (c->batch->pin_pdesc) (void)hipHostFree(c->batch->pin_pdesc);
     for (hipEvent_t e : c->batch->pdesc_done) if (e) (void)hipEventDestroy(e);
+    dfree(c->batch->d_mass); dfree(c->batch->d_sdesc);
+    if (c->batch->pin_sdesc) (void)hipHostFree(c->batch->pin_sdesc);
+    for (hipEvent_t e : c->batch->sdesc_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
     c->batch = nullptr;
 }
@@ -4394,6 +4405,146 @@ int cpprob_hip_batch_paths(cpprob_hip_ctx* c, uint64_t max_particles, int32_t* h
     if (h_logw) HIP_TRY(c, hipMemcpyAsync(h_logw, d_logw, (size_t)weights * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < (size_t)entries; ++i) h_paths[i] = v[i];
+    return 0;
+}
+// ---- backward smoothing of a batch (csrc/batch_smooth.hpp) ------------------------------------------------------------------------
+int cpprob_hip_batch_smooth_layout(const uint32_t* h_T, uint64_t n_problems, uint64_t n_traj, uint64_t* h_first)
+{
+    if (!h_T || !h_first) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
+    if (n_problems == 0) return fail(nullptr, CPPROB_HIP_EINVAL, "n_problems must be at least 1");
+    if (n_traj > (uint64_t)kBackwardMaxTraj) return fail(nullptr, CPPROB_HIP_EINVAL, "n_traj must lie in 0 .. 2^20");
+    for (uint64_t b = 0; b < n_problems; ++b)
+        if (h_T[b] > (uint32_t)kBackwardMaxT) return fail(nullptr, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": backward smoothing serves lengths up to 2^24");
+    uint64_t rows = 0;
+    for (uint64_t b = 0; b < n_problems; ++b) { h_first[b] = n_traj * rows; rows += h_T[b]; }
+    h_first[n_problems] = n_traj * rows;
+    return 0;
+}
+
+// The state backward smoothing needs (as cpprob_hip_batch_copy_store), the arguments' ranges, then the totals against the capacities.
+static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, bool with_marg, size_t n_doubles, bool with_traj, size_t n_entries, uint64_t& doubles, uint64_t& entries)
+{
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->cfg.keep_history != 1) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
+    if (draw_index >= (uint64_t)kBackwardMaxDraws) return fail(c, CPPROB_HIP_EINVAL, "draw_index must lie in 0 .. 2^16 - 1");
+    if (n_traj > (uint64_t)kBackwardMaxTraj) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 0 .. 2^20");
+    uint64_t rows = 0;
+    for (size_t b = 0; b < bs->prob.size(); ++b) {
+        if (bs->prob[b].T > kBackwardMaxT) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": backward smoothing serves lengths up to 2^24");
+        rows += (uint64_t)bs->prob[b].T;
+    }
+    doubles = (uint64_t)bs->cfg.n_problems * (uint64_t)bs->T * (uint64_t)bs->K;
+    entries = n_traj * rows;
+    if (with_marg && n_doubles < doubles) return fail(c, CPPROB_HIP_EINVAL, "the marginals buffer is too small: " + std::to_string(doubles) + " doubles (n_problems * T_max * stats_per_predict)");
+    if (with_traj && n_entries < entries) return fail(c, CPPROB_HIP_EINVAL, "the trajectories buffer is too small: " + std::to_string(entries) + " entries (cpprob_hip_batch_smooth_layout)");
+    return 0;
+}
+
+// Enqueues the descriptors' copy, the counting pass and the smoothing pass on the context's stream; waits for nothing but the pinned
+// slot it writes (the copy that read it kOnlineSlots calls ago) and, where a buffer of its own has to grow, for the calls before it.
+static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
+    const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
+    if (d_marg) HIP_TRY(c, hipMemsetAsync(d_marg, 0, B * (size_t)bs->T * (size_t)bs->K * sizeof(double), c->stream));   // rows t >= T_b, states >= k
+    size_t rows = 0;
+    int T_top = 0;
+    for (const BatchProblem& pr : bs->prob) { rows += (size_t)pr.T; T_top = std::max(T_top, (int)pr.T); }
+    if (rows == 0 || (!d_marg && (!d_traj || n_traj == 0))) return 0;       // (an online batch before its first observes, or nothing asked for)
+    if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
+        // (earlier calls' copies and kernels may still read the buffers this replaces)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (bytes > bs->sdesc_cap) {
+            dfree(bs->d_sdesc); bs->sdesc_cap = 0;
+            if (bs->pin_sdesc) { (void)hipHostFree(bs->pin_sdesc); bs->pin_sdesc = nullptr; }
+            HIP_TRY(c, hipMalloc(&bs->d_sdesc, bytes));
+            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_sdesc), bytes * BatchState::kOnlineSlots, hipHostMallocDefault));
+            for (hipEvent_t& e : bs->sdesc_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            bs->sdesc_cap = bytes; bs->n_smooth = 0;
+        }
+        if (rows > bs->mass_rows) {
+            dfree(bs->d_mass); bs->mass_rows = 0;
+            HIP_TRY(c, hipMalloc(&bs->d_mass, rows * 8 * sizeof(double)));
+            bs->mass_rows = rows;
+        }
+    }
+    const int slot = (int)(bs->n_smooth % BatchState::kOnlineSlots);
+    if (bs->n_smooth >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->sdesc_done[slot]));
+    char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap;
+    BatchSmoothProblem* pd = reinterpret_cast<BatchSmoothProblem*>(sl);
+    const size_t thr_at = bs->sdesc_cap - thr_bytes;
+    int64_t at = 0;
+    for (size_t b = 0; b < B; ++b) {
+        const BatchProblem& pr = bs->prob[b];
+        pd[b].T = pr.T; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at;
+        at += pr.T;
+    }
+    // CPPROB_HIP_MODEL_HMM3: its thresholds as a table row set of CPPROB_HIP_MODEL_HMM_TABLE ([k][8], entries 0..k-2), behind the descriptors
+    uint64_t* h3 = reinterpret_cast<uint64_t*>(sl + thr_at);
+    for (int i = 0; i < 64; ++i) h3[i] = ~0ull;
+    for (int s2 = 0; s2 < 3; ++s2) for (int j = 0; j < 2; ++j) h3[s2 * 8 + j] = bs->mp.hmm_thr[s2][j];
+    HIP_TRY(c, hipMemcpyAsync(bs->d_sdesc, sl, bs->sdesc_cap, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(bs->sdesc_done[slot], c->stream));
+    ++bs->n_smooth;
+    BatchSmoothArgs a{};
+    a.desc = reinterpret_cast<const BatchSmoothProblem*>(bs->d_sdesc);
+    a.values = reinterpret_cast<const int8_t*>(bs->d_ws + bs->lay.values);
+    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
+    a.thr = hmm3 ? reinterpret_cast<const uint64_t*>(bs->d_sdesc + thr_at) : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+    a.thr_stride = !hmm3 && bs->described ? 64 : 0;
+    a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
+    a.mass = bs->d_mass; a.marg = d_marg; a.traj = n_traj ? d_traj : nullptr;
+    a.draw_base = kBackwardDrawBase + (draw_index << 24);
+    a.T_max = bs->T; a.k = hmm3 ? 3 : bs->hk; a.spp = bs->K; a.n_traj = (int)n_traj;
+    a.lds_bytes = (int)std::min<int64_t>((int64_t)T_top * 64, kBackwardLdsMax);
+    // the counting pass: at least ~8192 workgroups where the batch has that many steps, a workgroup walking the steps gridDim.y apart
+    const unsigned gy = (unsigned)std::min<uint64_t>((uint64_t)T_top, std::max<uint64_t>(8, (8192 + B - 1) / B));
+    hipLaunchKernelGGL(batch_smooth_count_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    const unsigned tiles = a.traj ? (unsigned)((n_traj + kTile - 1) / kTile) : 0u;
+    if (hmm3) hipLaunchKernelGGL(batch_smooth_kernel<3>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
+    else hipLaunchKernelGGL(batch_smooth_kernel<8>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_smooth_device(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, n_traj, draw_index, d_marginals != nullptr, n_doubles, d_traj != nullptr, n_entries, doubles, entries)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_smooth_enqueue(c, n_traj, draw_index, d_marginals, d_traj);
+}
+
+int cpprob_hip_batch_smooth(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* h_marginals, size_t n_doubles, int32_t* h_traj, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, n_traj, draw_index, h_marginals != nullptr, n_doubles, h_traj != nullptr, n_entries, doubles, entries)) return rc;
+    const bool with_traj = h_traj && entries;
+    if (!h_marginals && !with_traj) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchState* bs = c->batch;
+    // device staging: the marginals (8-byte aligned) in front of the int8 entries
+    const size_t m_bytes = batch_round((h_marginals ? (size_t)doubles : 0) * sizeof(double)), need = m_bytes + (with_traj ? (size_t)entries : 0);
+    if (need > bs->stage_cap) {
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
+        bs->stage_cap = need;
+    }
+    double* d_marg = h_marginals ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
+    int8_t* d_traj = with_traj ? reinterpret_cast<int8_t*>(bs->d_stage + m_bytes) : nullptr;
+    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj)) return rc;
+    std::vector<int8_t> v(with_traj ? (size_t)entries : 0);
+    if (with_traj) HIP_TRY(c, hipMemcpyAsync(v.data(), d_traj, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
+    if (h_marginals) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
     return 0;
 }
 }  // extern "C"

@@ -581,6 +581,33 @@ void dump_batch_posterior(Context& ctx, const std::string& prefix, const std::ve
     }
 }
 
+// ---- backward smoothing of a batch (cpprob_hip_batch_smooth): Options::backward_smoothing, ::backward_trajectories ----------------
+// The statistics of the batch last run on ctx -- [B][T_max][K], the layout of cpprob_hip_batch_results' h_stats -- replaced by the
+// backward smoother's marginals.
+inline void batch_backward_marginals(Context& ctx, std::vector<double>& stats)
+{
+    ctx.check(cpprob_hip_batch_smooth(ctx.get(), 0, 0, stats.data(), stats.size(), nullptr, 0), "cpprob_hip_batch_smooth");
+}
+
+// dump_batch_posterior with problem b's M backward-simulated trajectories (draw_index 0) in the lineages' place: equal weights.
+template <class Structure>
+void dump_batch_backward(Context& ctx, const std::string& prefix, const std::vector<std::uint32_t>& T, std::size_t M, const Structure& structure)
+{
+    const std::size_t B = T.size();
+    std::vector<std::uint64_t> first(B + 1);
+    if (cpprob_hip_batch_smooth_layout(T.data(), B, M, first.data()))
+        throw std::runtime_error(std::string("cpprob_hip_batch_smooth_layout: ") + cpprob_hip_last_error(nullptr));
+    std::vector<std::int32_t> traj(static_cast<std::size_t>(first[B]));
+    ctx.check(cpprob_hip_batch_smooth(ctx.get(), M, 0, nullptr, 0, traj.data(), traj.size()), "cpprob_hip_batch_smooth");
+    for (std::size_t b = 0; b < B; ++b) {
+        HostStore hs;
+        hs.n = T[b] ? M : 0;
+        hs.ints.assign(traj.begin() + static_cast<std::ptrdiff_t>(first[b]), traj.begin() + static_cast<std::ptrdiff_t>(first[b + 1]));
+        hs.logw.assign(hs.n, 0.0);
+        dump_posterior(prefix + "_" + std::to_string(b), structure(b), hs, 0);
+    }
+}
+
 // The trace structure of a table-HMM problem of T observes: one int predict per observe, "state[t]".
 inline detail::TraceStructure hmm_table_structure(std::size_t T)
 {
@@ -623,6 +650,8 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     const Options& opt = options();
     if (!opt.keep_history && !opt.batch_dump_file.empty())
         throw std::runtime_error("cpprob::gpu::inference_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
+    if (!opt.keep_history && opt.backward_smoothing)
+        throw std::runtime_error("cpprob::gpu::inference_batch: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -642,8 +671,12 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     const std::size_t K = e->builtin_model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
     std::vector<double> stats(B * T * K), ess(B * T);
     ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+    if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (!opt.batch_dump_file.empty())
+    if (!opt.batch_dump_file.empty() && opt.backward_trajectories)
+        dump_batch_backward(ctx, opt.batch_dump_file, std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(T)), opt.backward_trajectories,
+                            [&st](std::size_t) -> const detail::TraceStructure& { return st; });
+    else if (!opt.batch_dump_file.empty())
         dump_batch_posterior(ctx, opt.batch_dump_file, std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(T)), std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(n)),
                              opt.dump_max_particles, [&st](std::size_t) -> const detail::TraceStructure& { return st; });
     lease.done();
@@ -696,6 +729,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
     const Options& opt = options();
     if (!opt.keep_history && !opt.batch_dump_file.empty())
         throw std::runtime_error("cpprob::gpu::hmm_table_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
+    if (!opt.keep_history && opt.backward_smoothing)
+        throw std::runtime_error("cpprob::gpu::hmm_table_batch: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -715,8 +750,11 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
     const std::size_t K = 8;
     std::vector<double> stats(B * T_max * K), ess(B * T_max);
     ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+    if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (!opt.batch_dump_file.empty())
+    if (!opt.batch_dump_file.empty() && opt.backward_trajectories)
+        dump_batch_backward(ctx, opt.batch_dump_file, T, opt.backward_trajectories, [&T](std::size_t b) { return hmm_table_structure(T[b]); });
+    else if (!opt.batch_dump_file.empty())
         dump_batch_posterior(ctx, opt.batch_dump_file, T, np, opt.dump_max_particles, [&T](std::size_t b) { return hmm_table_structure(T[b]); });
     lease.done();
     std::vector<Result> out(B);
@@ -745,6 +783,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // readout = false (keep_history only) leaves the smoothed predicts to a later advance and returns results without predicts; an
 // advance of empty sequences with readout = true then returns them.  dump(prefix) writes every problem's posterior traces for the
 // lengths reached, as hmm_table_batch does for options().batch_dump_file (whether or not the last advance did its read-out).
+// options().backward_smoothing: the predicts are the backward smoother's marginals, after every advance whatever its readout;
+// options().backward_trajectories = M > 0: dump() writes M backward-simulated trajectories a problem in the lineages' place.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -754,6 +794,8 @@ public:
         : B_(seeds.size()), k_(tables.empty() ? 0 : tables[0].means.size()), keep_(options().keep_history), lease_(options().device)
     {
         if (B_ == 0) throw std::runtime_error("cpprob::gpu::HmmTableStream: no problems (one seed per problem)");
+        if (!keep_ && backward_)
+            throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         const std::size_t B = B_;
         auto fits = [B](std::size_t have) { return have == B || have == 1; };
         if (!fits(tables.size()) || !fits(capacities.size()) || !fits(n.size()))
@@ -805,11 +847,13 @@ public:
         const auto t0 = std::chrono::steady_clock::now();
         ctx.check(cpprob_hip_batch_advance(ctx.get(), dT.data(), flat.empty() ? nullptr : flat.data(), readout ? 1 : 0), "cpprob_hip_batch_advance");
         ctx.check(cpprob_hip_batch_lengths(ctx.get(), L.data()), "cpprob_hip_batch_lengths");
-        const bool with_stats = readout || !keep_;
+        // (the backward smoother reads the store, not the read-out: its marginals are there after every advance)
+        const bool with_stats = readout || !keep_ || backward_;
         const std::size_t K = 8;
         std::vector<cpprob_hip_summary> sums(B_);
         std::vector<double> stats(with_stats ? B_ * T_max_ * K : 0), ess(B_ * T_max_);
-        ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), with_stats ? stats.data() : nullptr, stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+        ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), with_stats && !backward_ ? stats.data() : nullptr, stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+        if (backward_) batch_backward_marginals(ctx, stats);
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::vector<Result> out(B_);
         for (std::size_t b = 0; b < B_; ++b) {
@@ -836,12 +880,15 @@ public:
         Context& ctx = *lease_;
         std::vector<std::uint32_t> L(B_);
         ctx.check(cpprob_hip_batch_lengths(ctx.get(), L.data()), "cpprob_hip_batch_lengths");
-        dump_batch_posterior(ctx, prefix, L, np_, dump_max_, [&L](std::size_t b) { return hmm_table_structure(L[b]); });
+        if (backward_traj_) dump_batch_backward(ctx, prefix, L, backward_traj_, [&L](std::size_t b) { return hmm_table_structure(L[b]); });
+        else dump_batch_posterior(ctx, prefix, L, np_, dump_max_, [&L](std::size_t b) { return hmm_table_structure(L[b]); });
     }
 
 private:
     std::size_t B_, k_, T_max_ = 0;
     bool keep_;
+    bool backward_ = options().backward_smoothing;
+    std::size_t backward_traj_ = options().backward_trajectories;
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

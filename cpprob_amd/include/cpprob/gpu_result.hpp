@@ -30,6 +30,11 @@ struct Options {
     std::string batch_dump_file;                      // batched runs (inference_batch, hmm_table_batch): not empty = write problem b's posterior as
                                                       // <batch_dump_file>_<b>.int / .ids, the first dump_max_particles traces (0 = all) resolved on
                                                       // the device in one launch (cpprob_hip_batch_paths); empty: no files
+    bool backward_smoothing = false;                  // batched runs (inference_batch, hmm_table_batch, HmmTableStream; keep_history only): the results'
+                                                      // statistics are the backward smoother's marginals (cpprob_hip_batch_smooth: every generation's
+                                                      // whole filtering approximation) instead of the surviving lineages'
+    std::size_t backward_trajectories = 0;            // ... and, not 0, with batch_dump_file: problem b's files hold this many backward-simulated
+                                                      // trajectories with equal weights in place of the lineages
     bool markov_probe = true;                         // smc, unchanged-model path: test on the host whether a step depends on more than the last few
                                                       // sampled values; a model that does not is replayed from that window only (O(T) instead of O(T^2))
     bool markov_crosscheck = true;                    // ... and certify the probe's window on the device before using it: a pilot population under windowed

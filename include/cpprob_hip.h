@@ -391,6 +391,34 @@ int cpprob_hip_batch_paths(cpprob_hip_ctx* ctx, uint64_t max_particles, int32_t*
  * fifth call in a row waits for the first one's copy, nothing else.) */
 int cpprob_hip_batch_paths_device(cpprob_hip_ctx* ctx, uint64_t max_particles, int8_t* d_paths, size_t n_entries, double* d_logw, size_t n_weights);
 
+/* Backward smoothing of a batch (csrc/batch_smooth.hpp): the smoothed marginals P(x_t = s | y) and backward-simulated trajectories of
+ * EVERY problem of the batch last run (or last advanced), from every generation's whole filtering approximation instead of the
+ * lineages that survive to the end -- with resampling after every step those have coalesced to a handful of ancestors at the early
+ * steps.  Generation t of problem b enters as the k integers m_t[s] = (particles in state s) * fix_weight(ll_t[s], M_t), M_t the
+ * largest ll_t[s] over the states present, and the transition law as the integers P[s][s'] its thresholds realise on 32-bit words;
+ * csrc/batch_smooth.hpp and DESIGN.md section 5 state the arithmetic, which contracts no product into a sum, so the trajectories are
+ * a pure function of integers and IEEE operations.  Trajectory j of problem b draws the 53-bit uniform of word pair j & 1 of Philox
+ * block (key: the problem's run seed -- an online batch: its seed at begin --, group j >> 1, draw 2^41 + (draw_index << 24) + t) at
+ * step t: draw_index < 2^16 gives fresh, reproducible trajectories call after call.
+ * Marginals: [B][T_max][stats_per_predict] doubles, the layout and padding of cpprob_hip_batch_results' h_stats (rows t >= T_b and
+ * states >= k are zero).  Trajectories: problem b's [T_b][n_traj] entries from n_traj * (sum over b' < b of T_b') on, T_b as for
+ * cpprob_hip_batch_paths; a problem of length 0 owns none and its marginal rows are zero.  Either output may be NULL; n_traj may be
+ * 0 when the trajectories are NULL.  keep_history = 1 only, and only after a run (else CPPROB_HIP_ESTATE, as
+ * cpprob_hip_batch_copy_store); CPPROB_HIP_EINVAL: a capacity too small (nothing written), draw_index >= 2^16, n_traj > 2^20, a
+ * problem longer than 2^24.  The call reads the store and the per-step tables and changes nothing the other entry points return;
+ * the m table (64 B a step of the batch) is an allocation of the context's own, grown when needed, not part of the batch workspace.
+ *
+ * Pure host function (no device, no context): h_first[B + 1], problem b's first trajectory entry, the last element the total.
+ * h_T[b] may be 0.  CPPROB_HIP_EINVAL: NULL h_T / h_first, n_problems == 0, n_traj > 2^20, an h_T[b] above 2^24. */
+int cpprob_hip_batch_smooth_layout(const uint32_t* h_T, uint64_t n_problems, uint64_t n_traj, uint64_t* h_first);
+/* Host copies: h_marginals doubles, h_traj int32 (cpprob_hip_batch_paths' element type); n_doubles / n_entries the capacities in
+ * elements.  Stages on the device and widens.  Synchronises. */
+int cpprob_hip_batch_smooth(cpprob_hip_ctx* ctx, uint64_t n_traj, uint64_t draw_index, double* h_marginals, size_t n_doubles, int32_t* h_traj, size_t n_entries);
+/* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation: d_traj int8.  (The
+ * problems' descriptors travel through pinned host memory, four calls deep, as cpprob_hip_batch_paths_device's do; a call that has to
+ * grow the m table waits for the calls before it.) */
+int cpprob_hip_batch_smooth_device(cpprob_hip_ctx* ctx, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
