@@ -42,6 +42,7 @@ SYMBOLS = [
     "cpprob_hip_batch_online_workspace_bytes", "cpprob_hip_batch_begin_online", "cpprob_hip_batch_advance", "cpprob_hip_batch_lengths",
     "cpprob_hip_batch_paths_layout", "cpprob_hip_batch_paths", "cpprob_hip_batch_paths_device",
     "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
+    "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device",
 ]
 
 
@@ -313,6 +314,8 @@ def load_library(path=None):
         "cpprob_hip_batch_smooth_layout": (C.c_int, [C.POINTER(C.c_uint32), u64, u64, C.POINTER(u64)]),
         "cpprob_hip_batch_smooth": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_device": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_smooth_lag": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_smooth_lag_device": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, u64, u64, vp, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -655,6 +658,44 @@ class Engine:
         capacities)."""
         self._chk(self.L.cpprob_hip_batch_smooth_device(self.h, int(n_traj), int(draw_index), _dptr(marginals), 0 if marginals is None else marginals.numel(),
                                                         _dptr(traj_i8), 0 if traj_i8 is None else traj_i8.numel()))
+
+    def _batch_lag_shapes(self, lag, from_steps):
+        """(L uint32 [B], from uint32 [B] or None, W uint32 [B], n_rows) of a fixed-lag call on the batch last begun / advanced."""
+        h_T, _ = self._batch_problem_shapes()
+        h_T = np.ascontiguousarray(h_T, np.uint32)
+        h_from = None if from_steps is None else np.ascontiguousarray(from_steps, np.uint32)
+        if h_from is not None and h_from.shape != h_T.shape:
+            raise ValueError("one first step per problem")
+        left = h_T.astype(np.int64) - (0 if h_from is None else h_from.astype(np.int64))
+        W = np.minimum(int(lag) + 1, h_T.astype(np.int64)).astype(np.uint32)
+        return h_T, h_from, W, max(int(left.max()) if left.size else 0, 0)
+
+    def batch_smooth_lag(self, lag, from_steps=None, n_traj=0, draw_index=0):
+        """Fixed-lag smoothing of every problem (cpprob_hip_batch_smooth_lag): (marginals [B, n_rows, spp], a list of int32
+        [W_b, n_traj] arrays).  Row r of problem b is G_{from_b + r} = P(x_t | y_0 .. y_min(t + lag, L_b - 1)) at t = from_b + r, zero
+        past its length; from_steps None: every problem from step 0; n_rows = max(L_b - from_b).  The trajectories are the last
+        W_b = min(lag + 1, L_b) rows of batch_smooth(n_traj, draw_index)'s.  On an online batch the call costs the rows asked for,
+        whatever length the stream has reached."""
+        h_T, h_from, W, n_rows = self._batch_lag_shapes(lag, from_steps)
+        first = batch_smooth_layout(W, n_traj)
+        marg = np.zeros((self.batch_B, n_rows, self.batch_K))
+        flat = np.zeros(int(first[-1]), np.int32)
+        self._chk(self.L.cpprob_hip_batch_smooth_lag(self.h, int(lag), None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows, int(n_traj),
+                                                     int(draw_index), marg.ctypes.data if marg.size else None, marg.size, flat.ctypes.data if n_traj else None, flat.size))
+        return marg, [flat[int(first[b]):int(first[b + 1])].reshape(int(W[b]), int(n_traj)) for b in range(self.batch_B)]
+
+    def batch_smooth_lag_device(self, lag, from_steps=None, marginals=None, traj_i8=None, n_traj=0, draw_index=0):
+        """The same left in device tensors, enqueued behind the run / advance without a host synchronisation: marginals torch float64
+        [B, n_rows, spp] (n_rows = its second dimension) or None, traj_i8 torch int8 packed as batch_smooth_layout(W, n_traj) says or
+        None (their numel() are the capacities)."""
+        _, h_from, _, n_rows = self._batch_lag_shapes(lag, from_steps)
+        if marginals is not None:
+            if marginals.dim() != 3:
+                raise ValueError("marginals must be [B, n_rows, spp]")
+            n_rows = int(marginals.shape[1])
+        self._chk(self.L.cpprob_hip_batch_smooth_lag_device(self.h, int(lag), None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows, int(n_traj),
+                                                            int(draw_index), _dptr(marginals), 0 if marginals is None else marginals.numel(),
+                                                            _dptr(traj_i8), 0 if traj_i8 is None else traj_i8.numel()))
 
     # ---- sharded SMC ---------------------------------------------------------------------
     def step_begin(self, t, local_totals, run_index=0):

@@ -26,6 +26,16 @@
 // 64 T bytes fit the launch's dynamic LDS, its m table; longer problems read m from global memory (L2-resident: every tile of the
 // problem reads the same rows).  A lane owns trajectories tid, tid + 256, ... of its tile -- kPPT independent chains -- and walks t
 // backwards: k products, k sums and one Philox block a step and trajectory; consecutive lanes write consecutive bytes of output row t.
+//
+// Fixed-lag smoothing (cpprob_hip_batch_smooth_lag, _smooth_lag_device) works on the same table.  G_t is the recursion above started
+// from the filtering masses of the end step e(t) = min(t + lag, T - 1) instead of T - 1: final once lag more steps have run, and a
+// function of rows t .. e(t) alone.  The counting pass takes a range of rows a problem ([cfrom, cto): an online batch's table is
+// addressed by capacity, rows never move, and the host counts the rows that arrived since its last call); batch_smooth_lag_kernel's
+// work items are (problem, end step), a wavefront each: the item of end e < T - 1 walks lag steps and writes G_{e - lag}, the item of
+// end T - 1 writes every requested t >= T - 1 - lag in one walk.  Both it and smooth_marginals take their steps through
+// smooth_marginal_start / smooth_marginal_step, so the rows whose end is T - 1 are the full smoother's bits.  The trajectories stop at
+// a lower step `lo` (the window's first step; 0 for the full call), stage rows lo .. T - 1 only, and keep the absolute step in the draw
+// ordinal: a window row is the full call's row.
 #pragma once
 #include "batch_smc.hpp"
 
@@ -37,10 +47,12 @@ constexpr int kBackwardMaxDraws = 1 << 16;          // draw_index < this: the or
 constexpr uint64_t kBackwardDrawBase = 1ull << 41;  // clear of the particles' statement ordinals and of the resampling draws at 2^40 + ...
 constexpr int kBackwardLdsMax = 32768;              // bytes of m table a tile stages: T <= 512
 
-// Problem b as the passes need it: its length, particles, first entry in the store and the rows of the problems before it (its first
-// row in the m table; n_traj times that is its first trajectory entry).
-struct BatchSmoothProblem { int32_t T, n; int64_t store, rows; };
-static_assert(sizeof(BatchSmoothProblem) == 24, "one problem's smoothing descriptor");
+// Problem b as the passes need it: its length, particles, first entry in the store, its first row in the m table (the rows of the
+// problems before it, or their capacities: an online batch), its first row of trajectory output (n_traj times that is its first
+// entry), the rows [cfrom, cto) the counting pass owes, the step the trajectories stop at and the first step whose fixed-lag marginal
+// is wanted (output row 0).
+struct BatchSmoothProblem { int32_t T, n; int64_t store, rows, trows; int32_t cfrom, cto, lo, mfrom; };
+static_assert(sizeof(BatchSmoothProblem) == 48, "one problem's smoothing descriptor");
 
 struct BatchSmoothArgs {
     const BatchSmoothProblem* desc;            // [B]
@@ -49,10 +61,11 @@ struct BatchSmoothArgs {
     const uint64_t* thr;                       // problem b's 64 threshold words at thr + b * thr_stride, the layout of ModelParams::hk_thr
     const uint64_t* seeds;                     // [B]
     double* mass;                              // [sum of T_b][8]: m_t[0..8) of row desc[b].rows + t
-    double* marg;                              // [B][T_max][spp], zeroed by the caller; nullptr: not wanted
-    int8_t* traj;                              // packed: problem b's [T_b][n_traj] from n_traj * desc[b].rows on; nullptr: not wanted
+    double* marg;                              // [B][marg_rows][spp], zeroed by the caller; nullptr: not wanted
+    int8_t* traj;                              // packed: problem b's [T_b - lo_b][n_traj] from n_traj * desc[b].trows on; nullptr: not wanted
     uint64_t draw_base;                        // kBackwardDrawBase + (draw_index << 24)
     int T_max, k, spp, thr_stride, n_traj, lds_bytes;
+    int marg_rows, lag;                        // rows a problem in marg (T_max: the full call); batch_smooth_lag_kernel's lag
 };
 
 __global__ __launch_bounds__(kThreads) void batch_smooth_count_kernel(BatchSmoothArgs a)
@@ -62,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void batch_smooth_count_kernel(BatchSmoot
     const BatchSmoothProblem d = a.desc[b];                     // workgroup-uniform
     const int8_t* vals = a.values + d.store;
     int round = 0;
-    for (int t = (int)blockIdx.y; t < d.T; t += (int)gridDim.y, ++round) {
+    for (int t = d.cfrom + (int)blockIdx.y; t < d.cto; t += (int)gridDim.y, ++round) {   // (an empty range: the workgroup returns at once)
         const int8_t* row = vals + (int64_t)t * d.n;
         uint64_t cA = 0, cB = 0;
         for (int i = tid; i < d.n; i += kThreads) {             // (byte loads: a row starts where the rows before it end)
@@ -102,35 +115,74 @@ __device__ __forceinline__ double smooth_trans_mass(const uint64_t* thr, int k, 
     return u64_to_double(hi - lo);
 }
 
-// The marginals of one problem on one wavefront: lane (s', s) = 8 s' + s.
+// The recursion's start on one wavefront, lane (s', s) = 8 s' + s: g_e[s] of the filtering masses m_fin of the end step, the same in
+// the eight lanes (., s).
+__device__ __forceinline__ double smooth_marginal_start(const double* m_fin, int s)
+{
+#pragma clang fp contract(off)
+    uint64_t tot = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tot += (uint64_t)m_fin[j];
+    return m_fin[s] / u64_to_double(tot);
+}
+
+// One step of it: g_t[s] from g_{t+1} (in g), the step's masses m = m_t[0..8) and p = double(P[s][s']).  The one statement of the
+// step: the full-length marginals and the fixed-lag kernel both walk through here.
+__device__ __forceinline__ double smooth_marginal_step(const double* m, double p, double g, int sp, int s)
+{
+#pragma clang fp contract(off)
+    const double mt = m[s];
+    const double av = dmul_rn(mt, p);
+    double D = 0.0, Dm = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { D = D + __shfl(av, sp * 8 + j); Dm = Dm + m[j]; }
+    const bool none = D == 0.0;                                 // (the defensive rule: the row falls back to the filtering masses)
+    const double num = none ? mt : av, den = none ? Dm : D;
+    const double g_sp = __shfl(g, sp);                          // lane (0, s') holds g_{t+1}[s']
+    const double term = g_sp != 0.0 ? dmul_rn(num / den, g_sp) : 0.0;   // (a term left out and a zero added are the same sum)
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = acc + __shfl(term, j * 8 + s);
+    return acc;
+}
+
+// The marginals of one problem on one wavefront.
 __device__ __forceinline__ void smooth_marginals(const BatchSmoothArgs& a, int b, int T, const double* mass, const uint64_t* thr)
 {
 #pragma clang fp contract(off)
     const int lane = lane_id(), sp = lane >> 3, s = lane & 7;
     const double p = smooth_trans_mass(thr, a.k, s, sp);
-    double* out = a.marg + (int64_t)b * a.T_max * a.spp;
-    const double* m_fin = mass + (int64_t)(T - 1) * 8;
-    uint64_t tot = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) tot += (uint64_t)m_fin[j];
-    double g = m_fin[s] / u64_to_double(tot);                   // g_{t+1}[s], the same in the eight lanes (., s)
+    double* out = a.marg + (int64_t)b * a.marg_rows * a.spp;
+    double g = smooth_marginal_start(mass + (int64_t)(T - 1) * 8, s);
     if (sp == 0 && s < a.spp) out[(int64_t)(T - 1) * a.spp + s] = g;
     for (int t = T - 2; t >= 0; --t) {
-        const double* m = mass + (int64_t)t * 8;
-        const double mt = m[s];
-        const double av = dmul_rn(mt, p);
-        double D = 0.0, Dm = 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { D = D + __shfl(av, sp * 8 + j); Dm = Dm + m[j]; }
-        const bool none = D == 0.0;                             // (the defensive rule: the row falls back to the filtering masses)
-        const double num = none ? mt : av, den = none ? Dm : D;
-        const double g_sp = __shfl(g, sp);                      // lane (0, s') holds g_{t+1}[s']
-        const double term = g_sp != 0.0 ? dmul_rn(num / den, g_sp) : 0.0;   // (a term left out and a zero added are the same sum)
-        double acc = 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc = acc + __shfl(term, j * 8 + s);
-        g = acc;
+        g = smooth_marginal_step(mass + (int64_t)t * 8, p, g, sp, s);
         if (sp == 0 && s < a.spp) out[(int64_t)t * a.spp + s] = g;
+    }
+}
+
+// Fixed-lag marginals: blockIdx.x the problem; item blockIdx.y * kWaves + wavefront (and the items gridDim.y * kWaves apart) has the
+// end step T - 1 - item.  Output row t - mfrom.  The items are independent: no barrier, no atomics, no result that depends on the grid.
+__global__ __launch_bounds__(kThreads) void batch_smooth_lag_kernel(BatchSmoothArgs a)
+{
+#pragma clang fp contract(off)
+    const int b = (int)blockIdx.x, lane = lane_id(), sp = lane >> 3, s = lane & 7;
+    const BatchSmoothProblem d = a.desc[b];                     // workgroup-uniform
+    // the ends that own a row: T - 1 (every t >= T - 1 - lag asked for) and mfrom + lag .. T - 2 (t = end - lag)
+    const int items = d.mfrom >= d.T ? 0 : (d.T - d.mfrom - a.lag > 1 ? d.T - d.mfrom - a.lag : 1);
+    const double* mass = a.mass + d.rows * 8;
+    const double p = smooth_trans_mass(a.thr + (int64_t)b * a.thr_stride, a.k, s, sp);
+    double* out = a.marg + ((int64_t)b * a.marg_rows - d.mfrom) * a.spp;
+    const bool put = sp == 0 && s < a.spp;
+    for (int item = (int)blockIdx.y * kWaves + wave_id(); item < items; item += (int)gridDim.y * kWaves) {   // (wavefront-uniform)
+        const int e = d.T - 1 - item;
+        const int first = e - a.lag > d.mfrom ? e - a.lag : d.mfrom;   // the step the walk ends at
+        double g = smooth_marginal_start(mass + (int64_t)e * 8, s);
+        if (put && (item == 0 || e == first)) out[(int64_t)e * a.spp + s] = g;
+        for (int t = e - 1; t >= first; --t) {
+            g = smooth_marginal_step(mass + (int64_t)t * 8, p, g, sp, s);
+            if (put && (item == 0 || t == first)) out[(int64_t)t * a.spp + s] = g;
+        }
     }
 }
 
@@ -157,7 +209,7 @@ template <int K>
 __global__ __launch_bounds__(kThreads) void batch_smooth_kernel(BatchSmoothArgs a)
 {
 #pragma clang fp contract(off)
-    extern __shared__ __attribute__((aligned(16))) double s_mass[];    // [T][8] where it fits
+    extern __shared__ __attribute__((aligned(16))) double s_mass[];    // [T - lo][8] where it fits
     __shared__ double s_pt[64];                                         // s_pt[8 s' + s] = double(P[s][s'])
     const int b = (int)blockIdx.x, tid = threadIdx.x;
     const BatchSmoothProblem d = a.desc[b];                     // workgroup-uniform
@@ -171,23 +223,24 @@ __global__ __launch_bounds__(kThreads) void batch_smooth_kernel(BatchSmoothArgs 
     const int i0 = ((int)blockIdx.y - 1) * kTile;
     if (!a.traj || i0 >= a.n_traj) return;                      // a tile past the trajectories asked for
     if (tid < 64) s_pt[tid] = smooth_trans_mass(thr, a.k, tid & 7, tid >> 3);
-    const bool staged = (int64_t)d.T * 64 <= (int64_t)a.lds_bytes;
-    if (staged) for (int i = tid; i < d.T * 8; i += kThreads) s_mass[i] = mass[i];
+    const int lo = d.lo;                                        // the first step walked: output row 0
+    const bool staged = (int64_t)(d.T - lo) * 64 <= (int64_t)a.lds_bytes;
+    if (staged) for (int i = tid; i < (d.T - lo) * 8; i += kThreads) s_mass[i] = mass[(int64_t)lo * 8 + i];
     __syncthreads();
     const uint64_t seed = a.seeds[b];
-    int8_t* out = a.traj + d.rows * a.n_traj;
+    int8_t* out = a.traj + d.trows * a.n_traj;
     int x[kPPT];
     lane_fill(x, 0);
-    for (int t = d.T - 1; t >= 0; --t) {
+    for (int t = d.T - 1; t >= lo; --t) {
         double m[K];
         if (staged) {
 #pragma unroll
-            for (int s = 0; s < K; ++s) m[s] = s_mass[t * 8 + s];
+            for (int s = 0; s < K; ++s) m[s] = s_mass[(t - lo) * 8 + s];
         } else {
 #pragma unroll
             for (int s = 0; s < K; ++s) m[s] = mass[(int64_t)t * 8 + s];
         }
-        int8_t* orow = out + (int64_t)t * a.n_traj;
+        int8_t* orow = out + (int64_t)(t - lo) * a.n_traj;
 #pragma unroll
         for (int q = 0; q < kPPT; ++q) {
             const int j = i0 + q * kThreads + tid;              // (a lane past n_traj walks along and stores nothing)

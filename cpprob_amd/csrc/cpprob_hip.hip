@@ -1067,9 +1067,11 @@ struct BatchState {
     hipEvent_t pdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_paths = 0;
     char* d_stage = nullptr; size_t stage_cap = 0;
-    // backward smoothing (cpprob_hip_batch_smooth, _smooth_device; csrc/batch_smooth.hpp): the m table ([sum of T_b][8] doubles, grown
-    // lazily), the problems' descriptors with the HMM3 thresholds behind them, and their pinned sources, kOnlineSlots in turn
+    // backward smoothing (cpprob_hip_batch_smooth*, _smooth_lag*; csrc/batch_smooth.hpp): the m table ([sum of T_b][8] doubles -- an
+    // online batch: of its capacities, rows never move --, grown lazily), the problems' descriptors with the HMM3 thresholds behind
+    // them, and their pinned sources, kOnlineSlots in turn
     double* d_mass = nullptr; size_t mass_rows = 0;
+    std::vector<uint32_t> counted;             // [B], online batch: its rows [0, counted_b) of the m table are valid (any begin: none)
     char* d_sdesc = nullptr; size_t sdesc_cap = 0;
     char* pin_sdesc = nullptr;
     hipEvent_t sdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
@@ -1154,6 +1156,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     BatchState* bs = c->batch;
     bs->begun = false; bs->ran = false;
     const uint64_t B = cfg->n_problems;
+    bs->counted.assign(B, 0);
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3, described = h_T != nullptr, own = h_means != nullptr;
     const int spp = hmm3 ? 3 : 8;
     const uint64_t tables = described ? B : 1;
@@ -4441,18 +4444,23 @@ static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_
     return 0;
 }
 
+// A fixed-lag call's own arguments (cpprob_hip_batch_smooth_lag); the full calls pass none.
+struct BatchSmoothLag { uint64_t lag; const uint32_t* from; uint64_t n_rows; };
+
 // Enqueues the descriptors' copy, the counting pass and the smoothing pass on the context's stream; waits for nothing but the pinned
 // slot it writes (the copy that read it kOnlineSlots calls ago) and, where a buffer of its own has to grow, for the calls before it.
-static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj)
+// An online batch's m table is addressed by capacity and kept: the pass counts rows [counted_b, L_b) and moves the watermark.
+static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
     const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
-    if (d_marg) HIP_TRY(c, hipMemsetAsync(d_marg, 0, B * (size_t)bs->T * (size_t)bs->K * sizeof(double), c->stream));   // rows t >= T_b, states >= k
-    size_t rows = 0;
-    int T_top = 0;
-    for (const BatchProblem& pr : bs->prob) { rows += (size_t)pr.T; T_top = std::max(T_top, (int)pr.T); }
-    if (rows == 0 || (!d_marg && (!d_traj || n_traj == 0))) return 0;       // (an online batch before its first observes, or nothing asked for)
+    const size_t marg_rows = lg ? (size_t)lg->n_rows : (size_t)bs->T;
+    if (d_marg && marg_rows) HIP_TRY(c, hipMemsetAsync(d_marg, 0, B * marg_rows * (size_t)bs->K * sizeof(double), c->stream));   // rows past the problem's, states >= k
+    const bool with_traj = d_traj && n_traj;
+    size_t rows = 0, reached = 0;
+    for (size_t b = 0; b < B; ++b) { reached += (size_t)bs->prob[b].T; rows += bs->online ? (size_t)bs->cap_T[b] : (size_t)bs->prob[b].T; }
+    if (reached == 0 || (!d_marg && !with_traj)) return 0;                  // (an online batch before its first observes, or nothing asked for)
     if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
         // (earlier calls' copies and kernels may still read the buffers this replaces)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -4466,6 +4474,7 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         }
         if (rows > bs->mass_rows) {
             dfree(bs->d_mass); bs->mass_rows = 0;
+            bs->counted.assign(B, 0);                                       // (the rows counted so far went with the table)
             HIP_TRY(c, hipMalloc(&bs->d_mass, rows * 8 * sizeof(double)));
             bs->mass_rows = rows;
         }
@@ -4475,11 +4484,23 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap;
     BatchSmoothProblem* pd = reinterpret_cast<BatchSmoothProblem*>(sl);
     const size_t thr_at = bs->sdesc_cap - thr_bytes;
-    int64_t at = 0;
+    int64_t at = 0, at_traj = 0;
+    int range_top = 0, W_top = 0;
+    int64_t items_top = 0;
     for (size_t b = 0; b < B; ++b) {
         const BatchProblem& pr = bs->prob[b];
-        pd[b].T = pr.T; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at;
-        at += pr.T;
+        const int L = pr.T, W = lg ? (int)std::min<uint64_t>(lg->lag + 1, (uint64_t)L) : L;
+        const int mfrom = lg && lg->from ? (int)lg->from[b] : 0;
+        pd[b].T = L; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at; pd[b].trows = at_traj;
+        pd[b].lo = L - W; pd[b].mfrom = mfrom; pd[b].cto = L;
+        // the rows the pass owes: an online batch's new ones; a run batch's -- nothing is kept -- those this call reads
+        if (bs->online) pd[b].cfrom = (int)bs->counted[b];
+        else pd[b].cfrom = lg ? std::min(d_marg ? mfrom : L, with_traj ? L - W : L) : 0;
+        at += bs->online ? (int64_t)bs->cap_T[b] : (int64_t)L;
+        at_traj += W;
+        range_top = std::max(range_top, pd[b].cto - pd[b].cfrom);
+        W_top = std::max(W_top, W);
+        if (lg && mfrom < L) items_top = std::max<int64_t>(items_top, std::max<int64_t>(1, (int64_t)L - mfrom - (int64_t)lg->lag));
     }
     // CPPROB_HIP_MODEL_HMM3: its thresholds as a table row set of CPPROB_HIP_MODEL_HMM_TABLE ([k][8], entries 0..k-2), behind the descriptors
     uint64_t* h3 = reinterpret_cast<uint64_t*>(sl + thr_at);
@@ -4495,14 +4516,26 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     a.thr = hmm3 ? reinterpret_cast<const uint64_t*>(bs->d_sdesc + thr_at) : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
     a.thr_stride = !hmm3 && bs->described ? 64 : 0;
     a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
-    a.mass = bs->d_mass; a.marg = d_marg; a.traj = n_traj ? d_traj : nullptr;
+    a.mass = bs->d_mass; a.marg = d_marg; a.traj = with_traj ? d_traj : nullptr;
     a.draw_base = kBackwardDrawBase + (draw_index << 24);
     a.T_max = bs->T; a.k = hmm3 ? 3 : bs->hk; a.spp = bs->K; a.n_traj = (int)n_traj;
-    a.lds_bytes = (int)std::min<int64_t>((int64_t)T_top * 64, kBackwardLdsMax);
-    // the counting pass: at least ~8192 workgroups where the batch has that many steps, a workgroup walking the steps gridDim.y apart
-    const unsigned gy = (unsigned)std::min<uint64_t>((uint64_t)T_top, std::max<uint64_t>(8, (8192 + B - 1) / B));
-    hipLaunchKernelGGL(batch_smooth_count_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
+    a.marg_rows = (int)marg_rows; a.lag = lg ? (int)lg->lag : 0;
+    a.lds_bytes = (int)std::min<int64_t>((int64_t)W_top * 64, kBackwardLdsMax);
+    // the counting pass: at least ~8192 workgroups where the batch owes that many rows, a workgroup walking the rows gridDim.y apart
+    if (range_top > 0) {
+        const unsigned gy = (unsigned)std::min<uint64_t>((uint64_t)range_top, std::max<uint64_t>(8, (8192 + B - 1) / B));
+        hipLaunchKernelGGL(batch_smooth_count_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+        if (bs->online) for (size_t b = 0; b < B; ++b) bs->counted[b] = (uint32_t)bs->prob[b].T;
+    }
+    if (lg && d_marg && items_top > 0) {
+        // (problem, end step) a wavefront: the ends gridDim.y * kWaves apart where a problem has more than the grid holds
+        const unsigned gy = (unsigned)std::min<int64_t>((items_top + kWaves - 1) / kWaves, 4096);
+        hipLaunchKernelGGL(batch_smooth_lag_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (lg && !a.traj) return 0;
+    if (lg) a.marg = nullptr;                                               // (the pass below: the window's trajectories only)
     const unsigned tiles = a.traj ? (unsigned)((n_traj + kTile - 1) / kTile) : 0u;
     if (hmm3) hipLaunchKernelGGL(batch_smooth_kernel<3>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
     else hipLaunchKernelGGL(batch_smooth_kernel<8>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
@@ -4543,6 +4576,71 @@ int cpprob_hip_batch_smooth(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_in
     std::vector<int8_t> v(with_traj ? (size_t)entries : 0);
     if (with_traj) HIP_TRY(c, hipMemcpyAsync(v.data(), d_traj, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
     if (h_marginals) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
+    return 0;
+}
+
+// cpprob_hip_batch_smooth_lag's arguments against the batch's state (batch_smooth_check first), then the totals against the capacities.
+static int batch_smooth_lag_check(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, uint64_t n_traj, uint64_t draw_index,
+                                  bool with_marg, size_t n_doubles, bool with_traj, size_t n_entries, uint64_t& doubles, uint64_t& entries)
+{
+    uint64_t full_doubles = 0, full_entries = 0;
+    if (int rc = batch_smooth_check(c, n_traj, draw_index, false, 0, false, 0, full_doubles, full_entries)) return rc;
+    if (lag > (uint64_t)kBackwardMaxT) return fail(c, CPPROB_HIP_EINVAL, "lag must lie in 0 .. 2^24");
+    BatchState* bs = c->batch;
+    uint64_t win = 0;
+    for (size_t b = 0; b < bs->prob.size(); ++b) {
+        const uint64_t L = (uint64_t)bs->prob[b].T, from = h_from ? h_from[b] : 0;
+        if (from > L) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": from = " + std::to_string(from) + " lies past its length of " + std::to_string(L));
+        if (with_marg && L - from > n_rows)
+            return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": " + std::to_string(L - from) + " rows asked for, n_rows = " + std::to_string(n_rows));
+        win += std::min<uint64_t>(lag + 1, L);
+    }
+    doubles = (uint64_t)bs->cfg.n_problems * n_rows * (uint64_t)bs->K;
+    entries = n_traj * win;
+    if (with_marg && n_doubles < doubles) return fail(c, CPPROB_HIP_EINVAL, "the marginals buffer is too small: " + std::to_string(doubles) + " doubles (n_problems * n_rows * stats_per_predict)");
+    if (with_traj && n_entries < entries) return fail(c, CPPROB_HIP_EINVAL, "the trajectories buffer is too small: " + std::to_string(entries) + " entries (cpprob_hip_batch_smooth_layout of the windows)");
+    return 0;
+}
+
+int cpprob_hip_batch_smooth_lag_device(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, uint64_t n_traj, uint64_t draw_index,
+                                       double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_lag_check(c, lag, h_from, n_rows, n_traj, draw_index, d_marginals != nullptr, n_doubles, d_traj != nullptr, n_entries, doubles, entries)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const BatchSmoothLag lg{lag, h_from, n_rows};
+    return batch_smooth_enqueue(c, n_traj, draw_index, d_marginals, d_traj, &lg);
+}
+
+int cpprob_hip_batch_smooth_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, uint64_t n_traj, uint64_t draw_index,
+                                double* h_marginals, size_t n_doubles, int32_t* h_traj, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_lag_check(c, lag, h_from, n_rows, n_traj, draw_index, h_marginals != nullptr, n_doubles, h_traj != nullptr, n_entries, doubles, entries)) return rc;
+    const bool with_marg = h_marginals && doubles, with_traj = h_traj && entries;
+    if (!with_marg && !with_traj) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchState* bs = c->batch;
+    // device staging: the marginals (8-byte aligned) in front of the int8 entries
+    const size_t m_bytes = batch_round((with_marg ? (size_t)doubles : 0) * sizeof(double)), need = m_bytes + (with_traj ? (size_t)entries : 0);
+    if (need > bs->stage_cap) {
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
+        bs->stage_cap = need;
+    }
+    double* d_marg = with_marg ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
+    int8_t* d_traj = with_traj ? reinterpret_cast<int8_t*>(bs->d_stage + m_bytes) : nullptr;
+    const BatchSmoothLag lg{lag, h_from, n_rows};
+    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj, &lg)) return rc;
+    std::vector<int8_t> v(with_traj ? (size_t)entries : 0);
+    if (with_traj) HIP_TRY(c, hipMemcpyAsync(v.data(), d_traj, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
+    if (with_marg) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
     return 0;

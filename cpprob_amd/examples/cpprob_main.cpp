@@ -20,6 +20,8 @@
 //                   --backward_smoothing (the batch modes: the printed P(x_t = s) are the backward smoother's marginals -- every generation's
 //                   whole filtering approximation -- instead of the surviving lineages')   --backward_trajectories M (with --batch_dump: the
 //                   files hold M backward-simulated trajectories a problem, equal weights, in the lineages' place)
+//                   --smoothing_lag L (the batch modes and --stream_chunk: the printed P(x_t = s) are the fixed-lag marginals
+//                   P(x_t | y_0 .. y_min(t + L, T - 1)); with --stream_chunk every chunk costs its own steps; same output)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <algorithm>
 #include <array>
@@ -231,6 +233,7 @@ int main(int argc, char** argv)
         else if (f == "--stream_chunk") a.stream_chunk = std::stoull(next());    // --batch_tables_file: the observes arrive this many at a time
         else if (f == "--batch_dump") a.batch_dump = true;                         // the batch modes: problem b's traces as <generated_file>_smc_<b>.int / .ids
         else if (f == "--backward_smoothing") opt.backward_smoothing = true;      // the batch modes: statistics from the backward smoother (cpprob_hip_batch_smooth)
+        else if (f == "--smoothing_lag") opt.smoothing_lag = std::stol(next());    // the batch modes: fixed-lag marginals (cpprob_hip_batch_smooth_lag)
         else if (f == "--backward_trajectories") opt.backward_trajectories = std::stoull(next());   // ... and --batch_dump writes this many backward-simulated trajectories
         else if (f == "--dump_max_particles") opt.dump_max_particles = std::stoull(next());   // the posterior files hold the first M traces only (0: all)
         else if (f == "--generated_file") a.generated_file = next();

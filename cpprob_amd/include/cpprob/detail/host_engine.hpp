@@ -589,6 +589,14 @@ inline void batch_backward_marginals(Context& ctx, std::vector<double>& stats)
     ctx.check(cpprob_hip_batch_smooth(ctx.get(), 0, 0, stats.data(), stats.size(), nullptr, 0), "cpprob_hip_batch_smooth");
 }
 
+// Options::smoothing_lag: the fixed-lag marginals of the steps from[b] on (nullptr: every problem from step 0) of the batch last run
+// or advanced on ctx, [B][n_rows][K] (cpprob_hip_batch_smooth_lag).
+inline void batch_lag_marginals(Context& ctx, std::size_t lag, const std::uint32_t* from, std::size_t n_rows, std::vector<double>& rows)
+{
+    if (rows.empty()) return;
+    ctx.check(cpprob_hip_batch_smooth_lag(ctx.get(), lag, from, n_rows, 0, 0, rows.data(), rows.size(), nullptr, 0), "cpprob_hip_batch_smooth_lag");
+}
+
 // dump_batch_posterior with problem b's M backward-simulated trajectories (draw_index 0) in the lineages' place: equal weights.
 template <class Structure>
 void dump_batch_backward(Context& ctx, const std::string& prefix, const std::vector<std::uint32_t>& T, std::size_t M, const Structure& structure)
@@ -652,6 +660,8 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
         throw std::runtime_error("cpprob::gpu::inference_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
     if (!opt.keep_history && opt.backward_smoothing)
         throw std::runtime_error("cpprob::gpu::inference_batch: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
+    if (!opt.keep_history && opt.smoothing_lag >= 0)
+        throw std::runtime_error("cpprob::gpu::inference_batch: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -671,7 +681,8 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     const std::size_t K = e->builtin_model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
     std::vector<double> stats(B * T * K), ess(B * T);
     ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
-    if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
+    if (opt.smoothing_lag >= 0) batch_lag_marginals(ctx, static_cast<std::size_t>(opt.smoothing_lag), nullptr, T, stats);
+    else if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!opt.batch_dump_file.empty() && opt.backward_trajectories)
         dump_batch_backward(ctx, opt.batch_dump_file, std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(T)), opt.backward_trajectories,
@@ -731,6 +742,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
         throw std::runtime_error("cpprob::gpu::hmm_table_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
     if (!opt.keep_history && opt.backward_smoothing)
         throw std::runtime_error("cpprob::gpu::hmm_table_batch: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
+    if (!opt.keep_history && opt.smoothing_lag >= 0)
+        throw std::runtime_error("cpprob::gpu::hmm_table_batch: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -750,7 +763,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
     const std::size_t K = 8;
     std::vector<double> stats(B * T_max * K), ess(B * T_max);
     ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
-    if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
+    if (opt.smoothing_lag >= 0) batch_lag_marginals(ctx, static_cast<std::size_t>(opt.smoothing_lag), nullptr, T_max, stats);
+    else if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (!opt.batch_dump_file.empty() && opt.backward_trajectories)
         dump_batch_backward(ctx, opt.batch_dump_file, T, opt.backward_trajectories, [&T](std::size_t b) { return hmm_table_structure(T[b]); });
@@ -785,6 +799,10 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // lengths reached, as hmm_table_batch does for options().batch_dump_file (whether or not the last advance did its read-out).
 // options().backward_smoothing: the predicts are the backward smoother's marginals, after every advance whatever its readout;
 // options().backward_trajectories = M > 0: dump() writes M backward-simulated trajectories a problem in the lineages' place.
+// options().smoothing_lag = lag >= 0: the predicts are the fixed-lag marginals P(x_t | y_0 .. y_min(t + lag, L - 1)), after every
+// advance whatever its readout.  An advance asks the device for the steps from max(0, L_before - lag) on -- those whose estimate the
+// new observes can still change -- and the object keeps the final rows on the host: the work of an advance is that of its new steps,
+// and the predicts depend on the lengths reached alone, never on how the observes were cut into advances.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -796,6 +814,8 @@ public:
         if (B_ == 0) throw std::runtime_error("cpprob::gpu::HmmTableStream: no problems (one seed per problem)");
         if (!keep_ && backward_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
+        if (!keep_ && lag_ >= 0)
+            throw std::runtime_error("cpprob::gpu::HmmTableStream: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         const std::size_t B = B_;
         auto fits = [B](std::size_t have) { return have == B || have == 1; };
         if (!fits(tables.size()) || !fits(capacities.size()) || !fits(n.size()))
@@ -829,6 +849,7 @@ public:
         ctx.check(cpprob_hip_batch_begin_online(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), seeds.data()),
                   "cpprob_hip_batch_begin_online");
         lease_.done();
+        if (lag_ >= 0) { lagged_.assign(B_ * T_max_ * 8, 0.0); L_prev_.assign(B_, 0); }
     }
     HmmTableStream(const HmmTableStream&) = delete;
     HmmTableStream& operator=(const HmmTableStream&) = delete;
@@ -848,12 +869,28 @@ public:
         ctx.check(cpprob_hip_batch_advance(ctx.get(), dT.data(), flat.empty() ? nullptr : flat.data(), readout ? 1 : 0), "cpprob_hip_batch_advance");
         ctx.check(cpprob_hip_batch_lengths(ctx.get(), L.data()), "cpprob_hip_batch_lengths");
         // (the backward smoother reads the store, not the read-out: its marginals are there after every advance)
-        const bool with_stats = readout || !keep_ || backward_;
+        const bool lagged = lag_ >= 0, with_stats = readout || !keep_ || backward_ || lagged;
         const std::size_t K = 8;
         std::vector<cpprob_hip_summary> sums(B_);
-        std::vector<double> stats(with_stats ? B_ * T_max_ * K : 0), ess(B_ * T_max_);
-        ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), with_stats && !backward_ ? stats.data() : nullptr, stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
-        if (backward_) batch_backward_marginals(ctx, stats);
+        std::vector<double> stats(with_stats && !lagged ? B_ * T_max_ * K : 0), ess(B_ * T_max_);
+        ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), with_stats && !backward_ && !lagged ? stats.data() : nullptr, stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+        if (lagged) {
+            // the steps the new observes can still change: from max(0, L_before - lag) on; the rows before them are final and kept
+            std::vector<std::uint32_t> from(B_);
+            std::size_t n_rows = 0;
+            for (std::size_t b = 0; b < B_; ++b) {
+                from[b] = L_prev_[b] > static_cast<std::size_t>(lag_) ? static_cast<std::uint32_t>(L_prev_[b] - static_cast<std::size_t>(lag_)) : 0u;
+                n_rows = std::max<std::size_t>(n_rows, L[b] - from[b]);
+            }
+            std::vector<double> rows(B_ * n_rows * K);
+            batch_lag_marginals(ctx, static_cast<std::size_t>(lag_), from.data(), n_rows, rows);
+            for (std::size_t b = 0; b < B_; ++b) {
+                std::copy(rows.begin() + static_cast<std::ptrdiff_t>(b * n_rows * K), rows.begin() + static_cast<std::ptrdiff_t>((b * n_rows + (L[b] - from[b])) * K),
+                          lagged_.begin() + static_cast<std::ptrdiff_t>((b * T_max_ + from[b]) * K));
+                L_prev_[b] = L[b];
+            }
+        } else if (backward_) batch_backward_marginals(ctx, stats);
+        const std::vector<double>& shown = lagged ? lagged_ : stats;
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::vector<Result> out(B_);
         for (std::size_t b = 0; b < B_; ++b) {
@@ -866,7 +903,7 @@ public:
                 PredictStats& p = r.predicts[t];
                 p.address = "state[" + std::to_string(t) + "]";
                 p.is_int = true;
-                p.probabilities.assign(stats.begin() + (b * T_max_ + t) * K, stats.begin() + (b * T_max_ + t) * K + k_);
+                p.probabilities.assign(shown.begin() + (b * T_max_ + t) * K, shown.begin() + (b * T_max_ + t) * K + k_);
             }
             r.step_ess.assign(ess.begin() + b * T_max_, ess.begin() + b * T_max_ + L[b]);
         }
@@ -889,6 +926,9 @@ private:
     bool keep_;
     bool backward_ = options().backward_smoothing;
     std::size_t backward_traj_ = options().backward_trajectories;
+    long lag_ = options().smoothing_lag;
+    std::vector<double> lagged_;               // smoothing_lag: [B][T_max][8], the fixed-lag rows so far (rows below L - lag are final)
+    std::vector<std::size_t> L_prev_;          // ... and the lengths they stand for
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

@@ -35,6 +35,10 @@ struct Options {
                                                       // whole filtering approximation) instead of the surviving lineages'
     std::size_t backward_trajectories = 0;            // ... and, not 0, with batch_dump_file: problem b's files hold this many backward-simulated
                                                       // trajectories with equal weights in place of the lineages
+    long smoothing_lag = -1;                          // batched runs, keep_history only; >= 0: the results' statistics are the fixed-lag marginals
+                                                      // P(x_t | y_0 .. y_min(t + lag, L - 1)) (cpprob_hip_batch_smooth_lag; it takes precedence over
+                                                      // backward_smoothing).  HmmTableStream asks for the steps not yet final only: an advance costs its
+                                                      // new steps, whatever length the stream has reached.  Negative: off
     bool markov_probe = true;                         // smc, unchanged-model path: test on the host whether a step depends on more than the last few
                                                       // sampled values; a model that does not is replayed from that window only (O(T) instead of O(T^2))
     bool markov_crosscheck = true;                    // ... and certify the probe's window on the device before using it: a pilot population under windowed

@@ -419,6 +419,39 @@ int cpprob_hip_batch_smooth(cpprob_hip_ctx* ctx, uint64_t n_traj, uint64_t draw_
  * grow the m table waits for the calls before it.) */
 int cpprob_hip_batch_smooth_device(cpprob_hip_ctx* ctx, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries);
 
+/* Fixed-lag smoothing of a batch, at the cost of the steps asked for.  With L_b problem b's length (as for cpprob_hip_batch_smooth; an
+ * online batch: cpprob_hip_batch_lengths, served whether or not the last advance did its read-out) and lag >= 0:
+ *   end step of t      e(t) = min(t + lag, L_b - 1)
+ *   fixed-lag marginal G_t[s] = P(x_t = s | y_0 .. y_e(t)): the recursion of cpprob_hip_batch_smooth started at the end step,
+ *                      g_e[s] = double(m_e[s]) / double(sum_s m_e[s]), g_u[s] = sum over s' = 0..k-1 of (a_u[s'][s] / D_u[s']) g_{u+1}[s']
+ *                      for u = e - 1 .. t (terms with g_{u+1}[s'] = 0 left out, the sums in that order, every product one rounded
+ *                      operation, nothing contracted), G_t = g_t
+ *   lag = 0: the normalised filtering masses.  t >= L_b - 1 - lag: row t of cpprob_hip_batch_smooth's marginals, bit for bit (the
+ *   same device function walks both).  t + lag <= L_b - 1: step t is FINAL -- G_t reads rows t .. t + lag alone and is the same at
+ *   every later length, however an online batch was cut into advances.
+ *   window             the last W_b = min(lag + 1, L_b) steps, those whose end is L_b - 1
+ *   windowed trajectories: the backward simulation of cpprob_hip_batch_smooth stopped after W_b steps; the draws keep the absolute step
+ *                      (2^41 + (draw_index << 24) + t, group j >> 1, word pair j & 1), so a window row is the same row of
+ *                      cpprob_hip_batch_smooth with the same n_traj and draw_index.
+ * Marginals: [B][n_rows][stats_per_predict] doubles; row r of problem b is G_{from_b + r} for from_b + r < L_b, every other row and
+ * the states >= k are zero.  h_from: [B], or NULL for all 0.  n_rows >= max over b of (L_b - from_b).  Trajectories: problem b's
+ * [W_b][n_traj] entries (row r is step L_b - W_b + r), packed as cpprob_hip_batch_smooth_layout lays out the lengths W_b.  Either
+ * output may be NULL; n_traj may be 0.  keep_history = 1 only, and only after a run (else CPPROB_HIP_ESTATE).  CPPROB_HIP_EINVAL
+ * (nothing written; the message names the problem where one is at fault): from_b > L_b, n_rows too small, lag > 2^24, a capacity too
+ * small, draw_index >= 2^16, n_traj > 2^20, a problem longer than 2^24.
+ * Cost.  An online batch's m table is addressed by capacity (64 B times the sum of the capacities, the context's own allocation, made
+ * on first use, not part of the batch workspace) and kept: this call, cpprob_hip_batch_smooth and _smooth_device count only the rows
+ * that arrived since the last of them, and any batch begin forgets the table.  The call's own work is the rows asked for times
+ * (lag + 1) k^2, whatever length the stream has reached.  A run batch (cpprob_hip_batch_run rewrites the store) caches nothing: this
+ * call counts the rows it reads, the full calls every row.  The call changes nothing any other entry point returns.
+ * Host copies: h_traj int32.  Stages on the device and widens.  Synchronises. */
+int cpprob_hip_batch_smooth_lag(cpprob_hip_ctx* ctx, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, uint64_t n_traj, uint64_t draw_index,
+                                double* h_marginals, size_t n_doubles, int32_t* h_traj, size_t n_entries);
+/* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation: d_traj int8 (h_from
+ * stays a host array, read before the call returns). */
+int cpprob_hip_batch_smooth_lag_device(cpprob_hip_ctx* ctx, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, uint64_t n_traj, uint64_t draw_index,
+                                       double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
