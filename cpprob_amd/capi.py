@@ -42,7 +42,7 @@ SYMBOLS = [
     "cpprob_hip_batch_online_workspace_bytes", "cpprob_hip_batch_begin_online", "cpprob_hip_batch_advance", "cpprob_hip_batch_lengths",
     "cpprob_hip_batch_paths_layout", "cpprob_hip_batch_paths", "cpprob_hip_batch_paths_device",
     "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
-    "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device",
+    "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device", "cpprob_hip_batch_smooth_grid",
 ]
 
 
@@ -316,6 +316,7 @@ def load_library(path=None):
         "cpprob_hip_batch_smooth_device": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_lag": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_lag_device": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_smooth_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -696,6 +697,13 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_smooth_lag_device(self.h, int(lag), None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows, int(n_traj),
                                                             int(draw_index), _dptr(marginals), 0 if marginals is None else marginals.numel(),
                                                             _dptr(traj_i8), 0 if traj_i8 is None else traj_i8.numel()))
+
+    def batch_smooth_grid(self):
+        """(gridDim.y of the counting launch, gridDim.y of the fixed-lag launch) of this context's last smoothing call
+        (cpprob_hip_batch_smooth_grid); 0 where the launch did not happen.  Host only."""
+        cy, ly = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self.L.cpprob_hip_batch_smooth_grid(self.h, C.byref(cy), C.byref(ly)))
+        return int(cy.value), int(ly.value)
 
     # ---- sharded SMC ---------------------------------------------------------------------
     def step_begin(self, t, local_totals, run_index=0):

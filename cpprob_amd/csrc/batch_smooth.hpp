@@ -46,6 +46,8 @@ constexpr int kBackwardMaxTraj = 1 << 20;           // trajectories a problem in
 constexpr int kBackwardMaxDraws = 1 << 16;          // draw_index < this: the ordinals stay inside [2^41, 2^42)
 constexpr uint64_t kBackwardDrawBase = 1ull << 41;  // clear of the particles' statement ordinals and of the resampling draws at 2^40 + ...
 constexpr int kBackwardLdsMax = 32768;              // bytes of m table a tile stages: T <= 512
+constexpr int kSmoothCountGroups = 8192;            // workgroups the counting pass aims at: gridDim.y = min(rows owed, max(8, ceil(this / B)))
+constexpr int kSmoothLagGridMax = 4096;             // gridDim.y of batch_smooth_lag_kernel at most: kWaves times it items a problem and trip
 
 // Problem b as the passes need it: its length, particles, first entry in the store, its first row in the m table (the rows of the
 // problems before it, or their capacities: an online batch), its first row of trajectory output (n_traj times that is its first

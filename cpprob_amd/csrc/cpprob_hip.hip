@@ -1076,6 +1076,7 @@ struct BatchState {
     char* pin_sdesc = nullptr;
     hipEvent_t sdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_smooth = 0;
+    unsigned smooth_gy_count = 0, smooth_gy_lag = 0;        // gridDim.y of the last smoothing call's counting and lag launches (0: none)
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -4428,6 +4429,7 @@ int cpprob_hip_batch_smooth_layout(const uint32_t* h_T, uint64_t n_problems, uin
 static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, bool with_marg, size_t n_doubles, bool with_traj, size_t n_entries, uint64_t& doubles, uint64_t& entries)
 {
     BatchState* bs = c->batch;
+    if (bs) bs->smooth_gy_count = bs->smooth_gy_lag = 0;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
     if (bs->cfg.keep_history != 1) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
     if (draw_index >= (uint64_t)kBackwardMaxDraws) return fail(c, CPPROB_HIP_EINVAL, "draw_index must lie in 0 .. 2^16 - 1");
@@ -4521,18 +4523,20 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     a.T_max = bs->T; a.k = hmm3 ? 3 : bs->hk; a.spp = bs->K; a.n_traj = (int)n_traj;
     a.marg_rows = (int)marg_rows; a.lag = lg ? (int)lg->lag : 0;
     a.lds_bytes = (int)std::min<int64_t>((int64_t)W_top * 64, kBackwardLdsMax);
-    // the counting pass: at least ~8192 workgroups where the batch owes that many rows, a workgroup walking the rows gridDim.y apart
+    // the counting pass: at least ~kSmoothCountGroups workgroups where the batch owes that many rows, a workgroup walking the rows gridDim.y apart
     if (range_top > 0) {
-        const unsigned gy = (unsigned)std::min<uint64_t>((uint64_t)range_top, std::max<uint64_t>(8, (8192 + B - 1) / B));
+        const unsigned gy = (unsigned)std::min<uint64_t>((uint64_t)range_top, std::max<uint64_t>(8, ((uint64_t)kSmoothCountGroups + B - 1) / B));
         hipLaunchKernelGGL(batch_smooth_count_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());
+        bs->smooth_gy_count = gy;
         if (bs->online) for (size_t b = 0; b < B; ++b) bs->counted[b] = (uint32_t)bs->prob[b].T;
     }
     if (lg && d_marg && items_top > 0) {
         // (problem, end step) a wavefront: the ends gridDim.y * kWaves apart where a problem has more than the grid holds
-        const unsigned gy = (unsigned)std::min<int64_t>((items_top + kWaves - 1) / kWaves, 4096);
+        const unsigned gy = (unsigned)std::min<int64_t>((items_top + kWaves - 1) / kWaves, kSmoothLagGridMax);
         hipLaunchKernelGGL(batch_smooth_lag_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());
+        bs->smooth_gy_lag = gy;
     }
     if (lg && !a.traj) return 0;
     if (lg) a.marg = nullptr;                                               // (the pass below: the window's trajectories only)
@@ -4643,6 +4647,15 @@ int cpprob_hip_batch_smooth_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t*
     if (with_marg) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
+    return 0;
+}
+
+int cpprob_hip_batch_smooth_grid(cpprob_hip_ctx* c, uint32_t* count_grid_y, uint32_t* lag_grid_y)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    if (!count_grid_y || !lag_grid_y) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    *count_grid_y = c->batch ? c->batch->smooth_gy_count : 0u;
+    *lag_grid_y = c->batch ? c->batch->smooth_gy_lag : 0u;
     return 0;
 }
 }  // extern "C"

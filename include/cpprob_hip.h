@@ -451,6 +451,11 @@ int cpprob_hip_batch_smooth_lag(cpprob_hip_ctx* ctx, uint64_t lag, const uint32_
  * stays a host array, read before the call returns). */
 int cpprob_hip_batch_smooth_lag_device(cpprob_hip_ctx* ctx, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, uint64_t n_traj, uint64_t draw_index,
                                        double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries);
+/* The grids of the context's last smoothing call (any of the four above), host only: gridDim.y of its counting launch -- a workgroup
+ * walks the rows of its problem that far apart -- and of its fixed-lag launch -- a wavefront takes the end steps 4 times that far
+ * apart --, 0 where the launch did not happen (or no batch is begun).  The results do not depend on either; tests read them to know
+ * how many rounds and trips a shape produced. */
+int cpprob_hip_batch_smooth_grid(cpprob_hip_ctx* ctx, uint32_t* count_grid_y, uint32_t* lag_grid_y);
 
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):

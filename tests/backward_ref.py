@@ -119,14 +119,19 @@ def trajectories(m, P, seed, n_traj, draw_index=0):
     return out
 
 
-def trajectories_fast(m, P, seed, n_traj, draw_index=0):
+def trajectories_fast(m, P, seed, n_traj, draw_index=0, columns=None):
     """trajectories(), with the uniforms drawn a block (two trajectories) at a time and the walk vectorised over the trajectories:
-    the same doubles compared with the same doubles."""
+    the same doubles compared with the same doubles.  columns: the trajectories wanted (indices below n_traj, any order); the
+    result then holds those columns of the full [T][n_traj] only, and only their blocks are drawn."""
     T, k = len(m), len(m[0])
-    out = np.zeros((T, n_traj), np.int32)
+    cols = np.arange(n_traj, dtype=np.int64) if columns is None else np.asarray(columns, np.int64).reshape(-1)
+    assert cols.size == 0 or (0 <= int(cols.min()) and int(cols.max()) < n_traj)
+    out = np.zeros((T, cols.size), np.int32)
     L = O.lib()
-    x = np.zeros(n_traj, np.int64)
+    x = np.zeros(cols.size, np.int64)
     blk = np.zeros(4, np.uint32)
+    blocks, where = np.unique(cols >> 1, return_inverse=True)      # block g serves trajectories 2 g and 2 g + 1
+    half = cols & 1
     for t in range(T - 1, -1, -1):
         if t == T - 1:
             rows = [[float(v) for v in m[t]]] * k
@@ -134,13 +139,13 @@ def trajectories_fast(m, P, seed, n_traj, draw_index=0):
             rows = [_weights(m[t], P, sn)[0] for sn in range(k)]
         cums = np.array([np.cumsum(np.array(w)) for w in rows])
         last = np.array([max([s for s in range(k) if w[s] > 0.0] or [0]) for w in rows])
-        u = np.zeros(n_traj)
-        for g in range((n_traj + 1) // 2):
-            L.orc_draw_block(int(seed), g, DRAW_BASE + (int(draw_index) << 24) + t, blk)
-            u[2 * g] = L.orc_u01_53(int(blk[0]), int(blk[1]))
-            if 2 * g + 1 < n_traj:
-                u[2 * g + 1] = L.orc_u01_53(int(blk[2]), int(blk[3]))
-        c = cums[x]                                         # [n_traj][k]
+        ub = np.zeros((blocks.size, 2))
+        for i, g in enumerate(blocks):
+            L.orc_draw_block(int(seed), int(g), DRAW_BASE + (int(draw_index) << 24) + t, blk)
+            ub[i, 0] = L.orc_u01_53(int(blk[0]), int(blk[1]))
+            ub[i, 1] = L.orc_u01_53(int(blk[2]), int(blk[3]))
+        u = ub[where, half]
+        c = cums[x]                                         # [columns][k]
         target = u * c[:, k - 1]
         above = c > target[:, None]
         first = np.argmax(above, axis=1)

@@ -15,7 +15,7 @@ from oracle import oracle as O
 
 EINVAL = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device")
+NEW = ("cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device", "cpprob_hip_batch_smooth_grid")
 N_PROBLEMS, T, N = 64, 32, 256
 
 
@@ -67,6 +67,20 @@ def test_vectorised_walk_is_the_plain_one(problems):
     for di in (0, 3):
         assert np.array_equal(R.trajectories(m, P, 77, 33, di), R.trajectories_fast(m, P, 77, 33, di))
     assert not np.array_equal(R.trajectories_fast(m, P, 77, 33, 0), R.trajectories_fast(m, P, 77, 33, 3))
+
+
+def test_columns_are_the_full_walks_columns(problems):
+    """trajectories_fast(columns=...) draws only the blocks it needs and returns those columns of the full result: both ends of
+    the range, both halves of a block, repeats and an order that is not sorted."""
+    _, _, (m, P), _ = problems[7]
+    M = 1025
+    full = R.trajectories_fast(m, P, 91, M, 255)
+    rng = np.random.default_rng(3)
+    for cols in ([0], [M - 1], [1024, 0, 1, 1, 513, 2, 1023], rng.choice(M, 300, replace=False), np.arange(M), []):
+        got = R.trajectories_fast(m, P, 91, M, 255, columns=cols)
+        assert got.dtype == np.int32 and got.shape == (T, len(cols))
+        assert np.array_equal(got, full[:, np.asarray(cols, np.int64)]), cols
+    assert np.array_equal(R.trajectories_fast(m, P, 91, 1 << 20, 255, columns=[5, 1024]), full[:, [5, 1024]])     # (n_traj is a bound only)
 
 
 def test_integer_masses_of_the_hmm3_table():

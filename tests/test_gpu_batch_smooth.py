@@ -106,7 +106,7 @@ def _described(k):
 
 
 @pytest.mark.parametrize("rs", RESAMPLERS)
-@pytest.mark.parametrize("k", [2, 8])
+@pytest.mark.parametrize("k", [2, 3, 5, 7, 8])
 def test_described_table_batch(engine, k, rs):
     Ts, ns, means, trans, obs = _described(k)
     B, M = len(Ts), 300

@@ -66,7 +66,7 @@ def _assert_rows(what, b, marg_b, ref_g, frm, k):
 
 # ---- 1. described batch ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rs", RESAMPLERS)
-@pytest.mark.parametrize("k", [2, 8])
+@pytest.mark.parametrize("k", [2, 3, 5, 7, 8])
 def test_described_table_batch(engine, k, rs):
     Ts, ns, M = [1, 2, 7, 23], [1, 300, 777, 1025], 33
     B = len(Ts)
