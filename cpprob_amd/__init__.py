@@ -10,4 +10,7 @@ from .capi import (ALG_SIS, ALG_SMC, MODEL_GAUSSIAN_README, MODEL_GAUSSIAN_UNKNO
                    MODEL_LINEAR_GAUSSIAN_1D, MODEL_HMM_TABLE, RESAMPLE_MULTINOMIAL, RESAMPLE_STRATIFIED, RESAMPLE_SYSTEMATIC,
                    SCOPE_GLOBAL, SCOPE_ISLAND, SCOPE_EXCHANGE, Engine, Group, CpprobHipError, load_library)
 
+from . import em  # noqa: F401
+from .em import hmm_table_em, m_step  # noqa: F401
+
 __version__ = "0.1.0"

@@ -43,6 +43,7 @@ SYMBOLS = [
     "cpprob_hip_batch_paths_layout", "cpprob_hip_batch_paths", "cpprob_hip_batch_paths_device",
     "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
     "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device", "cpprob_hip_batch_smooth_grid",
+    "cpprob_hip_batch_smooth_stats", "cpprob_hip_batch_smooth_stats_device",
 ]
 
 
@@ -169,6 +170,15 @@ def batch_smooth_layout(T, n_traj):
         e.code = rc
         raise e
     return first
+
+
+STATS_PER_PROBLEM = 88                        # doubles a problem of cpprob_hip_batch_smooth_stats: xi[8][8], occ[8], occ_y[8], occ_yy[8]
+
+
+def split_stats(rec):
+    """The records [B, 88] of cpprob_hip_batch_smooth_stats as a dict of views: xi [B, 8, 8], occ, occ_y, occ_yy [B, 8]."""
+    rec = np.asarray(rec).reshape(-1, STATS_PER_PROBLEM)
+    return {"xi": rec[:, :64].reshape(-1, 8, 8), "occ": rec[:, 64:72], "occ_y": rec[:, 72:80], "occ_yy": rec[:, 80:88]}
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -317,6 +327,8 @@ def load_library(path=None):
         "cpprob_hip_batch_smooth_lag": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_lag_device": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "cpprob_hip_batch_smooth_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_smooth_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -697,6 +709,30 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_smooth_lag_device(self.h, int(lag), None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows, int(n_traj),
                                                             int(draw_index), _dptr(marginals), 0 if marginals is None else marginals.numel(),
                                                             _dptr(traj_i8), 0 if traj_i8 is None else traj_i8.numel()))
+
+    def _batch_packed_observes(self, observes):
+        """observes as the statistics calls take them: one flat float64 array, problem after problem by the lengths reached.  A list
+        of 1-D arrays (one a problem) or an array [B, T] of a uniform batch."""
+        if isinstance(observes, np.ndarray):
+            return np.ascontiguousarray(observes, np.float64).reshape(-1)
+        seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in observes]
+        return np.ascontiguousarray(np.concatenate(seqs)) if seqs else np.zeros(0)
+
+    def batch_smooth_stats(self, observes=None):
+        """Expected sufficient statistics of every problem (cpprob_hip_batch_smooth_stats), the E-step of cpprob_amd.em: a dict of
+        xi [B, 8, 8] (expected transitions s -> s'), occ [B, 8] (expected visits), occ_y and occ_yy [B, 8] (visits weighted by y_t
+        and y_t^2; zero without observes).  observes: a list of 1-D arrays, problem b's sequence up to the length it has reached, or
+        an array [B, T] of a uniform batch."""
+        rec = np.zeros((self.batch_B, STATS_PER_PROBLEM))
+        flat = None if observes is None else self._batch_packed_observes(observes)
+        self._chk(self.L.cpprob_hip_batch_smooth_stats(self.h, None if flat is None or flat.size == 0 else flat.ctypes.data, 0 if flat is None else flat.size,
+                                                       rec.ctypes.data, rec.size))
+        return split_stats(rec)
+
+    def batch_smooth_stats_device(self, stats, observes=None):
+        """The same left in a device tensor, enqueued behind the run / advance without a host synchronisation: stats torch float64
+        [B, 88] (split_stats names its columns), observes a torch float64 tensor packed as above or None."""
+        self._chk(self.L.cpprob_hip_batch_smooth_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
 
     def batch_smooth_grid(self):
         """(gridDim.y of the counting launch, gridDim.y of the fixed-lag launch) of this context's last smoothing call

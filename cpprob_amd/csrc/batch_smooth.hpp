@@ -33,7 +33,7 @@
 // addressed by capacity, rows never move, and the host counts the rows that arrived since its last call); batch_smooth_lag_kernel's
 // work items are (problem, end step), a wavefront each: the item of end e < T - 1 walks lag steps and writes G_{e - lag}, the item of
 // end T - 1 writes every requested t >= T - 1 - lag in one walk.  Both it and smooth_marginals take their steps through
-// smooth_marginal_start / smooth_marginal_step, so the rows whose end is T - 1 are the full smoother's bits.  The trajectories stop at
+// smooth_marginal_start / smooth_marginal_term / smooth_marginal_sum, so the rows whose end is T - 1 are the full smoother's bits.  The trajectories stop at
 // a lower step `lo` (the window's first step; 0 for the full call), stage rows lo .. T - 1 only, and keep the absolute step in the draw
 // ordinal: a window row is the full call's row.
 #pragma once
@@ -128,12 +128,13 @@ __device__ __forceinline__ double smooth_marginal_start(const double* m_fin, int
     return m_fin[s] / u64_to_double(tot);
 }
 
-// One step of it: g_t[s] from g_{t+1} (in g), the step's masses m = m_t[0..8) and p = double(P[s][s']).  The one statement of the
-// step: the full-length marginals and the fixed-lag kernel both walk through here.
-__device__ __forceinline__ double smooth_marginal_step(const double* m, double p, double g, int sp, int s)
+// One step of it in two parts, the one statement of the step: the full-length marginals, the fixed-lag kernel and the sufficient
+// statistics (csrc/batch_suffstats.hpp) all walk through here.  The term of lane (s', s): (a_t[s'][s] / D_t[s']) g_{t+1}[s'], the
+// two-slice posterior P(x_t = s, x_{t+1} = s' | y), from g_{t+1} (in g), mt = m_t[s], the step's masses m = m_t[0..8) (their ordered
+// sum serves the defensive rule) and p = double(P[s][s']).
+__device__ __forceinline__ double smooth_marginal_term(double mt, const double (&m)[8], double p, double g, int sp)
 {
 #pragma clang fp contract(off)
-    const double mt = m[s];
     const double av = dmul_rn(mt, p);
     double D = 0.0, Dm = 0.0;
 #pragma unroll
@@ -141,11 +142,25 @@ __device__ __forceinline__ double smooth_marginal_step(const double* m, double p
     const bool none = D == 0.0;                                 // (the defensive rule: the row falls back to the filtering masses)
     const double num = none ? mt : av, den = none ? Dm : D;
     const double g_sp = __shfl(g, sp);                          // lane (0, s') holds g_{t+1}[s']
-    const double term = g_sp != 0.0 ? dmul_rn(num / den, g_sp) : 0.0;   // (a term left out and a zero added are the same sum)
+    return g_sp != 0.0 ? dmul_rn(num / den, g_sp) : 0.0;        // (a term left out and a zero added are the same sum)
+}
+
+// g_t[s]: the terms of the lanes (., s) summed in the order s' = 0..7, the same in the eight lanes (., s).
+__device__ __forceinline__ double smooth_marginal_sum(double term, int s)
+{
+#pragma clang fp contract(off)
     double acc = 0.0;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc = acc + __shfl(term, j * 8 + s);
     return acc;
+}
+
+// Row `row` = m_t[0..8) of the m table as the pair takes it: the lane's own mass returned, the eight in m.
+__device__ __forceinline__ double smooth_load_row(const double* row, int s, double (&m)[8])
+{
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m[j] = row[j];
+    return row[s];
 }
 
 // The marginals of one problem on one wavefront.
@@ -158,7 +173,9 @@ __device__ __forceinline__ void smooth_marginals(const BatchSmoothArgs& a, int b
     double g = smooth_marginal_start(mass + (int64_t)(T - 1) * 8, s);
     if (sp == 0 && s < a.spp) out[(int64_t)(T - 1) * a.spp + s] = g;
     for (int t = T - 2; t >= 0; --t) {
-        g = smooth_marginal_step(mass + (int64_t)t * 8, p, g, sp, s);
+        double m[8];
+        const double mt = smooth_load_row(mass + (int64_t)t * 8, s, m);
+        g = smooth_marginal_sum(smooth_marginal_term(mt, m, p, g, sp), s);
         if (sp == 0 && s < a.spp) out[(int64_t)t * a.spp + s] = g;
     }
 }
@@ -182,7 +199,9 @@ __global__ __launch_bounds__(kThreads) void batch_smooth_lag_kernel(BatchSmoothA
         double g = smooth_marginal_start(mass + (int64_t)e * 8, s);
         if (put && (item == 0 || e == first)) out[(int64_t)e * a.spp + s] = g;
         for (int t = e - 1; t >= first; --t) {
-            g = smooth_marginal_step(mass + (int64_t)t * 8, p, g, sp, s);
+            double m[8];
+            const double mt = smooth_load_row(mass + (int64_t)t * 8, s, m);
+            g = smooth_marginal_sum(smooth_marginal_term(mt, m, p, g, sp), s);
             if (put && (item == 0 || t == first)) out[(int64_t)t * a.spp + s] = g;
         }
     }

@@ -22,6 +22,7 @@
 #include "batch_smc.hpp"
 #include "batch_paths.hpp"
 #include "batch_smooth.hpp"
+#include "batch_suffstats.hpp"
 
 using namespace cph;
 
@@ -4448,11 +4449,15 @@ static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_
 
 // A fixed-lag call's own arguments (cpprob_hip_batch_smooth_lag); the full calls pass none.
 struct BatchSmoothLag { uint64_t lag; const uint32_t* from; uint64_t n_rows; };
+// A statistics call's own (cpprob_hip_batch_smooth_stats): the observes (or nullptr) and the records, both on the device.
+struct BatchSmoothStats { const double* d_obs; double* d_stats; };
 
 // Enqueues the descriptors' copy, the counting pass and the smoothing pass on the context's stream; waits for nothing but the pinned
 // slot it writes (the copy that read it kOnlineSlots calls ago) and, where a buffer of its own has to grow, for the calls before it.
 // An online batch's m table is addressed by capacity and kept: the pass counts rows [counted_b, L_b) and moves the watermark.
-static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr)
+// st: the smoothing pass is batch_smooth_stats_kernel (csrc/batch_suffstats.hpp) and nothing else is written.
+static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr,
+                                const BatchSmoothStats* st = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
@@ -4462,7 +4467,8 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     const bool with_traj = d_traj && n_traj;
     size_t rows = 0, reached = 0;
     for (size_t b = 0; b < B; ++b) { reached += (size_t)bs->prob[b].T; rows += bs->online ? (size_t)bs->cap_T[b] : (size_t)bs->prob[b].T; }
-    if (reached == 0 || (!d_marg && !with_traj)) return 0;                  // (an online batch before its first observes, or nothing asked for)
+    if (st && reached == 0) HIP_TRY(c, hipMemsetAsync(st->d_stats, 0, B * (size_t)kSuffStats * sizeof(double), c->stream));
+    if (reached == 0 || (!d_marg && !with_traj && !st)) return 0;           // (an online batch before its first observes, or nothing asked for)
     if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
         // (earlier calls' copies and kernels may still read the buffers this replaces)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -4537,6 +4543,14 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         hipLaunchKernelGGL(batch_smooth_lag_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());
         bs->smooth_gy_lag = gy;
+    }
+    if (st) {
+        BatchSmoothStatsArgs sa{};
+        sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = st->d_obs; sa.stats = st->d_stats;
+        sa.B = (int)B; sa.k = a.k; sa.thr_stride = a.thr_stride;
+        hipLaunchKernelGGL(batch_smooth_stats_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, sa);
+        HIP_TRY(c, hipGetLastError());
+        return 0;
     }
     if (lg && !a.traj) return 0;
     if (lg) a.marg = nullptr;                                               // (the pass below: the window's trajectories only)
@@ -4647,6 +4661,59 @@ int cpprob_hip_batch_smooth_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t*
     if (with_marg) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
+    return 0;
+}
+
+// cpprob_hip_batch_smooth_stats' arguments against the batch's state (batch_smooth_check first).
+static int batch_smooth_stats_check(cpprob_hip_ctx* c, bool with_obs, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& rows)
+{
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
+    if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    if (with_obs && (uint64_t)n_observes != rows)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    const uint64_t need = (uint64_t)bs->cfg.n_problems * (uint64_t)kSuffStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
+    return 0;
+}
+
+int cpprob_hip_batch_smooth_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t rows = 0;
+    if (int rc = batch_smooth_stats_check(c, d_observes != nullptr, n_observes, d_stats, n_doubles, rows)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const BatchSmoothStats st{d_observes, d_stats};
+    return batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, &st);
+}
+
+int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t rows = 0;
+    if (int rc = batch_smooth_stats_check(c, h_observes != nullptr, n_observes, h_stats, n_doubles, rows)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchState* bs = c->batch;
+    // device staging: the records in front of the observes
+    const size_t s_bytes = (size_t)bs->cfg.n_problems * kSuffStats * sizeof(double), need = s_bytes + (h_observes ? (size_t)rows * sizeof(double) : 0);
+    if (need > bs->stage_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
+        bs->stage_cap = need;
+    }
+    double* d_stats = reinterpret_cast<double*>(bs->d_stage);
+    double* d_obs = h_observes && rows ? reinterpret_cast<double*>(bs->d_stage + s_bytes) : nullptr;
+    if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const BatchSmoothStats st{d_obs, d_stats};
+    if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, &st)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

@@ -22,6 +22,9 @@
 //                   files hold M backward-simulated trajectories a problem, equal weights, in the lineages' place)
 //                   --smoothing_lag L (the batch modes and --stream_chunk: the printed P(x_t = s) are the fixed-lag marginals
 //                   P(x_t | y_0 .. y_min(t + L, T - 1)); with --stream_chunk every chunk costs its own steps; same output)
+//                   --em_iterations N (with --batch_tables_file, not with --stream_chunk: particle EM -- N runs, each followed by the
+//                   backward smoother's expected sufficient statistics and an M-step on every problem's table; the usual output is the
+//                   last run's, then the fitted tables follow, one "[means] [transition]" line a problem in the input's grammar)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <algorithm>
 #include <array>
@@ -31,6 +34,7 @@
 #include <iostream>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "cpprob/cpprob.hpp"
@@ -46,6 +50,7 @@ struct Args {
     int repeat = 1;
     std::size_t n_samples = 10000;            // src/main.cpp:166
     std::size_t stream_chunk = 0;             // --batch_tables_file: feed every problem's observes this many at a time (0: all at once)
+    std::size_t em_iterations = 0;            // --batch_tables_file: fit the tables by this many iterations of particle EM (0: none)
 };
 
 void print_json(const cpprob::gpu::Result& r)
@@ -145,10 +150,17 @@ int execute_batch_tables(const Args& a)
         seeds.push_back(cpprob::gpu::options().seed + at);
     }
     if (tables.empty()) { std::cerr << "no problems in " << a.batch_tables_file << std::endl; return EXIT_FAILURE; }
+    if (a.em_iterations && a.stream_chunk) { std::cerr << "--em_iterations begins a fresh batch an iteration: not with --stream_chunk" << std::endl; return EXIT_FAILURE; }
     std::vector<cpprob::gpu::Result> res;
+    std::vector<cpprob::gpu::HmmTable> fitted;
     const std::string dump_prefix = a.model_folder + "/" + a.generated_file + "_smc";
     if (a.batch_dump && a.stream_chunk == 0) cpprob::gpu::options().batch_dump_file = dump_prefix;
-    if (a.stream_chunk == 0) res = cpprob::gpu::hmm_table_batch(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds);
+    if (a.em_iterations) {
+        cpprob::gpu::HmmTableFit fit = cpprob::gpu::hmm_table_fit(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds, a.em_iterations);
+        res = std::move(fit.results);
+        fitted = std::move(fit.tables);
+    }
+    else if (a.stream_chunk == 0) res = cpprob::gpu::hmm_table_batch(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds);
     else {
         // --stream_chunk K: the same batch fed K observes a problem at a time (cpprob::gpu::HmmTableStream); the last chunk may be
         // shorter, a problem that has run out gets none, and only the last advance does the read-out.  The output is the same.
@@ -173,6 +185,13 @@ int execute_batch_tables(const Args& a)
         for (const auto& p : r.predicts)
             for (double v : p.probabilities) std::cout << " " << v;
         std::cout << std::endl;
+    }
+    for (const cpprob::gpu::HmmTable& t : fitted) {
+        std::cout << "[";
+        for (std::size_t s = 0; s < t.means.size(); ++s) std::cout << (s ? " " : "") << t.means[s];
+        std::cout << "] [";
+        for (std::size_t i = 0; i < t.transition.size(); ++i) std::cout << (i ? " " : "") << t.transition[i];
+        std::cout << "]" << std::endl;
     }
     cpprob::gpu::release_device_resources();
     return EXIT_SUCCESS;
@@ -231,6 +250,7 @@ int main(int argc, char** argv)
         else if (f == "--batch_observes_file") a.batch_observes_file = next();   // one problem a line, one batched launch (built-in HMMs, smc)
         else if (f == "--batch_tables_file") a.batch_tables_file = next();       // one table-HMM problem a line: [means] [transition] [observes]
         else if (f == "--stream_chunk") a.stream_chunk = std::stoull(next());    // --batch_tables_file: the observes arrive this many at a time
+        else if (f == "--em_iterations") a.em_iterations = std::stoull(next());  // --batch_tables_file: particle EM on the tables (cpprob::gpu::hmm_table_fit)
         else if (f == "--batch_dump") a.batch_dump = true;                         // the batch modes: problem b's traces as <generated_file>_smc_<b>.int / .ids
         else if (f == "--backward_smoothing") opt.backward_smoothing = true;      // the batch modes: statistics from the backward smoother (cpprob_hip_batch_smooth)
         else if (f == "--smoothing_lag") opt.smoothing_lag = std::stol(next());    // the batch modes: fixed-lag marginals (cpprob_hip_batch_smooth_lag)

@@ -712,40 +712,53 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
 // statistics), ess_threshold (must be > 1: every step) and device come from options(), as for inference_batch.
 struct HmmTable { std::vector<double> means, transition; };
 
-inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes,
-                                           const std::vector<std::size_t>& n, const std::vector<std::uint64_t>& seeds)
+// The problems of hmm_table_batch / hmm_table_fit as cpprob_hip_batch_begin_problems takes them.
+struct HmmTableProblems {
+    std::size_t k = 0, T_max = 0, n_max = 0;
+    std::vector<double> means, trans, flat;     // [B][k], [B][k][k], the observes packed problem after problem
+    std::vector<std::uint32_t> T, np;           // [B]
+};
+
+inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes,
+                                                const std::vector<std::size_t>& n, std::size_t B)
 {
-    const std::size_t B = seeds.size();
-    if (B == 0) throw std::runtime_error("cpprob::gpu::hmm_table_batch: no problems (one seed per problem)");
+    if (B == 0) throw std::runtime_error(who + ": no problems (one seed per problem)");
     auto fits = [B](std::size_t have) { return have == B || have == 1; };
     if (!fits(tables.size()) || !fits(observes.size()) || !fits(n.size()))
-        throw std::runtime_error("cpprob::gpu::hmm_table_batch: tables, observes and n hold one entry per seed, or one entry shared by all problems");
-    const std::size_t k = tables[0].means.size();
-    std::vector<double> means, trans, flat;
-    std::vector<std::uint32_t> T(B), np(B);
-    std::size_t T_max = 0, n_max = 0;
+        throw std::runtime_error(who + ": tables, observes and n hold one entry per seed, or one entry shared by all problems");
+    HmmTableProblems pk;
+    pk.k = tables[0].means.size();
+    pk.T.resize(B); pk.np.resize(B);
     for (std::size_t b = 0; b < B; ++b) {
         const HmmTable& tb = tables[tables.size() == 1 ? 0 : b];
-        if (tb.means.size() != k || tb.transition.size() != k * k)
-            throw std::runtime_error("cpprob::gpu::hmm_table_batch: problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
-        means.insert(means.end(), tb.means.begin(), tb.means.end());
-        trans.insert(trans.end(), tb.transition.begin(), tb.transition.end());
+        if (tb.means.size() != pk.k || tb.transition.size() != pk.k * pk.k)
+            throw std::runtime_error(who + ": problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
+        pk.means.insert(pk.means.end(), tb.means.begin(), tb.means.end());
+        pk.trans.insert(pk.trans.end(), tb.transition.begin(), tb.transition.end());
         const std::vector<double>& o = observes[observes.size() == 1 ? 0 : b];
-        flat.insert(flat.end(), o.begin(), o.end());
+        pk.flat.insert(pk.flat.end(), o.begin(), o.end());
         const std::size_t nb = n[n.size() == 1 ? 0 : b];
-        if (o.size() > 0x7fffffffu || nb > 0x7fffffffu) throw std::runtime_error("cpprob::gpu::hmm_table_batch: problem " + std::to_string(b) + ": too large for a batch");
-        T[b] = static_cast<std::uint32_t>(o.size()); np[b] = static_cast<std::uint32_t>(nb);
-        T_max = std::max(T_max, o.size()); n_max = std::max(n_max, nb);
+        if (o.size() > 0x7fffffffu || nb > 0x7fffffffu) throw std::runtime_error(who + ": problem " + std::to_string(b) + ": too large for a batch");
+        pk.T[b] = static_cast<std::uint32_t>(o.size()); pk.np[b] = static_cast<std::uint32_t>(nb);
+        pk.T_max = std::max(pk.T_max, o.size()); pk.n_max = std::max(pk.n_max, nb);
     }
     const Options& opt = options();
     if (!opt.keep_history && !opt.batch_dump_file.empty())
-        throw std::runtime_error("cpprob::gpu::hmm_table_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
+        throw std::runtime_error(who + ": a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
     if (!opt.keep_history && opt.backward_smoothing)
-        throw std::runtime_error("cpprob::gpu::hmm_table_batch: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
+        throw std::runtime_error(who + ": backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     if (!opt.keep_history && opt.smoothing_lag >= 0)
-        throw std::runtime_error("cpprob::gpu::hmm_table_batch: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
-    ContextLease lease(opt.device);
-    Context& ctx = *lease;
+        throw std::runtime_error(who + ": fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
+    return pk;
+}
+
+// One batch of the packed problems on ctx: begin, run, results (options().backward_smoothing / ::smoothing_lag as hmm_table_batch
+// states them) and, where dump is set, options().batch_dump_file.  The batch stays on ctx for the calls that read it.
+inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTableProblems& pk, const std::vector<std::uint64_t>& seeds, bool dump)
+{
+    const Options& opt = options();
+    const std::size_t B = seeds.size(), k = pk.k, T_max = pk.T_max;
+    const std::vector<std::uint32_t>& T = pk.T;
     cpprob_hip_batch_config bc{};
     bc.algorithm = CPPROB_HIP_ALG_SMC;
     bc.model = CPPROB_HIP_MODEL_HMM_TABLE;
@@ -753,10 +766,10 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
     bc.keep_history = opt.keep_history ? 1 : 0;
     bc.flags = 0;
     bc.ess_threshold = opt.ess_threshold;
-    bc.n_particles = n_max;
+    bc.n_particles = pk.n_max;
     bc.n_problems = B;
     const auto t0 = std::chrono::steady_clock::now();
-    ctx.check(cpprob_hip_batch_begin_problems(ctx.get(), &bc, T.data(), np.data(), flat.data(), static_cast<std::int32_t>(k), means.data(), trans.data()),
+    ctx.check(cpprob_hip_batch_begin_problems(ctx.get(), &bc, T.data(), pk.np.data(), pk.flat.data(), static_cast<std::int32_t>(k), pk.means.data(), pk.trans.data()),
               "cpprob_hip_batch_begin_problems");
     ctx.check(cpprob_hip_batch_run(ctx.get(), seeds.data()), "cpprob_hip_batch_run");
     std::vector<cpprob_hip_summary> sums(B);
@@ -766,16 +779,15 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
     if (opt.smoothing_lag >= 0) batch_lag_marginals(ctx, static_cast<std::size_t>(opt.smoothing_lag), nullptr, T_max, stats);
     else if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (!opt.batch_dump_file.empty() && opt.backward_trajectories)
+    if (dump && !opt.batch_dump_file.empty() && opt.backward_trajectories)
         dump_batch_backward(ctx, opt.batch_dump_file, T, opt.backward_trajectories, [&T](std::size_t b) { return hmm_table_structure(T[b]); });
-    else if (!opt.batch_dump_file.empty())
-        dump_batch_posterior(ctx, opt.batch_dump_file, T, np, opt.dump_max_particles, [&T](std::size_t b) { return hmm_table_structure(T[b]); });
-    lease.done();
+    else if (dump && !opt.batch_dump_file.empty())
+        dump_batch_posterior(ctx, opt.batch_dump_file, T, pk.np, opt.dump_max_particles, [&T](std::size_t b) { return hmm_table_structure(T[b]); });
     std::vector<Result> out(B);
     for (std::size_t b = 0; b < B; ++b) {
         Result& r = out[b];
         const cpprob_hip_summary& s = sums[b];
-        r.n_particles = np[b]; r.log_evidence = s.log_evidence; r.ess = s.ess_final; r.log_norm = s.log_norm; r.n_resampled = s.n_resampled;
+        r.n_particles = pk.np[b]; r.log_evidence = s.log_evidence; r.ess = s.ess_final; r.log_norm = s.log_norm; r.n_resampled = s.n_resampled;
         r.used_builtin = true; r.step_form = s.step_form; r.run_seconds = seconds;
         r.predicts.resize(T[b]);
         for (std::size_t t = 0; t < T[b]; ++t) {
@@ -787,6 +799,63 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
         r.step_ess.assign(ess.begin() + b * T_max, ess.begin() + b * T_max + T[b]);
     }
     return out;
+}
+
+inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes,
+                                           const std::vector<std::size_t>& n, const std::vector<std::uint64_t>& seeds)
+{
+    const HmmTableProblems pk = pack_hmm_table_problems("cpprob::gpu::hmm_table_batch", tables, observes, n, seeds.size());
+    ContextLease lease(options().device);
+    std::vector<Result> out = run_hmm_table_problems(*lease, pk, seeds, true);
+    lease.done();
+    return out;
+}
+
+// ---- particle EM for the tables (cpprob_hip_batch_smooth_stats) ----
+// Fits every problem's table to its observes: iteration i runs the batch of hmm_table_batch with the current tables and the keys
+// seeds[b] + i, takes the backward smoother's expected sufficient statistics (the E-step, on the device) and sets
+//   transition[s][s'] = xi[s][s'] / (xi[s][0] + .. + xi[s][k-1]),   means[s] = occ_y[s] / occ[s]
+// (the M-step; a row or a state without mass keeps its value; the emission's sigma is 1 and not fitted).  Returns the fitted tables
+// and the results of the last run -- those of the tables that run began with.  options().keep_history must be set;
+// options().batch_dump_file is written by the last run.
+struct HmmTableFit { std::vector<HmmTable> tables; std::vector<Result> results; };
+
+inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes, const std::vector<std::size_t>& n,
+                                 const std::vector<std::uint64_t>& seeds, std::size_t iterations)
+{
+    const std::size_t B = seeds.size();
+    HmmTableProblems pk = pack_hmm_table_problems("cpprob::gpu::hmm_table_fit", tables, observes, n, B);
+    if (!options().keep_history)
+        throw std::runtime_error("cpprob::gpu::hmm_table_fit: the statistics read the particle store: a filtering-only run (options().keep_history = false) keeps none");
+    const std::size_t k = pk.k, R = 88;
+    HmmTableFit fit;
+    ContextLease lease(options().device);
+    Context& ctx = *lease;
+    std::vector<double> rec(B * R);
+    std::vector<std::uint64_t> keys(B);
+    for (std::size_t it = 0; it < iterations; ++it) {
+        for (std::size_t b = 0; b < B; ++b) keys[b] = seeds[b] + it;
+        fit.results = run_hmm_table_problems(ctx, pk, keys, it + 1 == iterations);
+        ctx.check(cpprob_hip_batch_smooth_stats(ctx.get(), pk.flat.empty() ? nullptr : pk.flat.data(), pk.flat.size(), rec.data(), rec.size()),
+                  "cpprob_hip_batch_smooth_stats");
+        for (std::size_t b = 0; b < B; ++b) {
+            const double* r = rec.data() + b * R;
+            for (std::size_t s = 0; s < k; ++s) {
+                double row = 0.0;
+                for (std::size_t j = 0; j < k; ++j) row = row + r[8 * s + j];
+                if (row > 0.0)
+                    for (std::size_t j = 0; j < k; ++j) pk.trans[(b * k + s) * k + j] = r[8 * s + j] / row;
+                if (r[64 + s] > 0.0) pk.means[b * k + s] = r[72 + s] / r[64 + s];
+            }
+        }
+    }
+    lease.done();
+    fit.tables.resize(B);
+    for (std::size_t b = 0; b < B; ++b) {
+        fit.tables[b].means.assign(pk.means.begin() + static_cast<std::ptrdiff_t>(b * k), pk.means.begin() + static_cast<std::ptrdiff_t>((b + 1) * k));
+        fit.tables[b].transition.assign(pk.trans.begin() + static_cast<std::ptrdiff_t>(b * k * k), pk.trans.begin() + static_cast<std::ptrdiff_t>((b + 1) * k * k));
+    }
+    return fit;
 }
 
 // ---- the same problems with observes that arrive over time (cpprob_hip_batch_begin_online / _advance) ----

@@ -457,6 +457,27 @@ int cpprob_hip_batch_smooth_lag_device(cpprob_hip_ctx* ctx, uint64_t lag, const 
  * how many rounds and trips a shape produced. */
 int cpprob_hip_batch_smooth_grid(cpprob_hip_ctx* ctx, uint32_t* count_grid_y, uint32_t* lag_grid_y);
 
+/* Expected sufficient statistics of a batch (csrc/batch_suffstats.hpp): the E-step of an EM fit of the problems' tables, from the
+ * backward smoother's own walk.  The term the recursion of cpprob_hip_batch_smooth forms for (s', s) at step t,
+ * (a_t[s'][s] / D_t[s']) g_{t+1}[s'], is the two-slice posterior P(x_t = s, x_{t+1} = s' | y); with T_b problem b's length and y_t
+ * its observes the call returns, a problem,
+ *   xi[s][s'] = sum over t = T_b - 2 .. 0 of that term      (expected transitions s -> s')
+ *   occ[s]    = sum over t = T_b - 1 .. 0 of g_t[s]         (expected visits)
+ *   occ_y[s]  = sum over t of g_t[s] * y_t,   occ_yy[s] = sum over t of g_t[s] * (y_t * y_t)
+ * every accumulator from 0.0, one addition a step in that order of t, every product one rounded multiplication, nothing contracted:
+ * g_t are cpprob_hip_batch_smooth's marginals bit for bit and the record is a pure function of integers and IEEE operations.
+ * Record: 88 doubles a problem -- xi at 8 s + s', then occ[8], occ_y[8], occ_yy[8]; states >= k are zero, a problem of length 0 is
+ * all zero, a problem of length 1 has xi = 0.  n_doubles >= 88 n_problems.
+ * Observes: the problems' sequences packed one after the other by the lengths reached (cpprob_hip_batch_begin_problems' layout; a
+ * uniform batch: [B][T]), n_observes their total; NULL (n_observes is then not read): occ_y and occ_yy stay zero.
+ * keep_history = 1 only, and only after a run (else CPPROB_HIP_ESTATE); CPPROB_HIP_EINVAL (nothing written): a capacity too small,
+ * n_observes not the sum of the lengths, a problem longer than 2^24.  The call shares the m table and its counting pass with the
+ * smoothing calls above (an online batch: whichever of them comes first counts the new rows, none counts a row twice) and changes
+ * nothing any other entry point returns.  Synchronises. */
+int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+/* The same between device buffers, enqueued on the context's stream after the run / advance, no host synchronisation. */
+int cpprob_hip_batch_smooth_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
