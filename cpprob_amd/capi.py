@@ -38,7 +38,7 @@ SYMBOLS = [
     "cpprob_hip_weighted_moments", "cpprob_hip_weighted_hist", "cpprob_hip_weighted_moments_columns", "cpprob_hip_weighted_hist_columns", "cpprob_hip_resample", "cpprob_hip_smc_bookkeep", "cpprob_hip_smc_bookkeep_fixed", "cpprob_hip_smc_bookkeep_fixed_rs", "cpprob_hip_generic_begin", "cpprob_hip_generic_begin_tiles", "cpprob_hip_generic_quantize", "cpprob_hip_generic_max", "cpprob_hip_generic_quantize_ref", "cpprob_hip_generic_totals", "cpprob_hip_generic_finish", "cpprob_hip_systematic_offset", "cpprob_hip_lineage_gather", "cpprob_hip_lineage_prepare", "cpprob_hip_readback_with_next_result", "cpprob_hip_lineage_moments", "cpprob_hip_lineage_hist", "cpprob_hip_gather_f64",
     "cpprob_hip_gather_i32", "cpprob_hip_profile_enable", "cpprob_hip_profile_read", "cpprob_hip_fastmath", "cpprob_hip_variate_from_bits",
     "cpprob_hip_batch_workspace_bytes", "cpprob_hip_batch_begin", "cpprob_hip_batch_run", "cpprob_hip_batch_results", "cpprob_hip_batch_results_device",
-    "cpprob_hip_batch_copy_store", "cpprob_hip_batch_problems_workspace_bytes", "cpprob_hip_batch_begin_problems",
+    "cpprob_hip_batch_copy_store", "cpprob_hip_batch_copy_masses", "cpprob_hip_batch_problems_workspace_bytes", "cpprob_hip_batch_begin_problems",
     "cpprob_hip_batch_online_workspace_bytes", "cpprob_hip_batch_begin_online", "cpprob_hip_batch_advance", "cpprob_hip_batch_lengths",
     "cpprob_hip_batch_paths_layout", "cpprob_hip_batch_paths", "cpprob_hip_batch_paths_device",
     "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
@@ -76,12 +76,19 @@ class BatchConfig(C.Structure):
 
 
 BATCH_MAX_PARTICLES = 8192
+BATCH_KEEP_MASSES = 2                         # cpprob_hip_batch_config::flags: a filtering-only batch keeps the smoother's m table
 
 
-def batch_workspace_bytes(model, n_particles, n_problems, T, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
-    """cpprob_hip_batch_workspace_bytes: validates a batch configuration and returns its device bytes; no GPU needed."""
+def _batch_flags(flags, keep_masses):
+    return int(flags) | (BATCH_KEEP_MASSES if keep_masses else 0)
+
+
+def batch_workspace_bytes(model, n_particles, n_problems, T, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
+                          keep_masses=False):
+    """cpprob_hip_batch_workspace_bytes: validates a batch configuration and returns its device bytes; no GPU needed.  keep_masses
+    (with keep_history=False): the batch keeps the backward smoother's m table, 64 bytes a problem and step."""
     L = load_library()
-    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), int(n_particles), int(n_problems))
+    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, _batch_flags(flags, keep_masses), float(ess_threshold), int(n_particles), int(n_problems))
     out = C.c_uint64()
     rc = L.cpprob_hip_batch_workspace_bytes(C.byref(cfg), int(T), C.byref(out))
     if rc:
@@ -103,13 +110,14 @@ def _problem_shapes(T, n_particles):
     return h_T, h_n
 
 
-def batch_problems_workspace_bytes(model, T, n_particles, max_particles=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
+def batch_problems_workspace_bytes(model, T, n_particles, max_particles=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
+                                   keep_masses=False):
     """cpprob_hip_batch_problems_workspace_bytes: the device bytes of a batch whose problem b has T[b] observes and n_particles[b]
     particles (an int: every problem's); max_particles is cfg.n_particles (default: the largest of n_particles).  No GPU needed."""
     L = load_library()
     h_T, h_n = _problem_shapes(T, n_particles)
     top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
-    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), top, int(h_T.size))
+    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, _batch_flags(flags, keep_masses), float(ess_threshold), top, int(h_T.size))
     out = C.c_uint64()
     rc = L.cpprob_hip_batch_problems_workspace_bytes(C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out))
     if rc:
@@ -120,13 +128,14 @@ def batch_problems_workspace_bytes(model, T, n_particles, max_particles=None, re
     return out.value
 
 
-def batch_online_workspace_bytes(model, capacity, n_particles, max_particles=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
+def batch_online_workspace_bytes(model, capacity, n_particles, max_particles=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
+                                 keep_masses=False):
     """cpprob_hip_batch_online_workspace_bytes: the device bytes of a batch advanced in pieces, whose problem b may reach capacity[b]
     observes with n_particles[b] particles (an int: every problem's); max_particles is cfg.n_particles.  No GPU needed."""
     L = load_library()
     h_T, h_n = _problem_shapes(capacity, n_particles)
     top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
-    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, int(flags), float(ess_threshold), top, int(h_T.size))
+    cfg = BatchConfig(int(algorithm), int(model), int(resampler), 1 if keep_history else 0, _batch_flags(flags, keep_masses), float(ess_threshold), top, int(h_T.size))
     out = C.c_uint64()
     rc = L.cpprob_hip_batch_online_workspace_bytes(C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(out))
     if rc:
@@ -312,6 +321,7 @@ def load_library(path=None):
         "cpprob_hip_batch_results": (C.c_int, [vp, C.POINTER(Summary), vp, sz, vp, vp]),
         "cpprob_hip_batch_results_device": (C.c_int, [vp, vp, sz]),
         "cpprob_hip_batch_copy_store": (C.c_int, [vp, u64, vp, vp, vp]),
+        "cpprob_hip_batch_copy_masses": (C.c_int, [vp, u64, vp, sz]),
         "cpprob_hip_batch_problems_workspace_bytes": (C.c_int, [C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]),
         "cpprob_hip_batch_begin_problems": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, vp, vp]),
         "cpprob_hip_batch_online_workspace_bytes": (C.c_int, [C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]),
@@ -507,12 +517,15 @@ class Engine:
         """Device bytes a batch of n_problems problems of T observes needs: a pure host function (no device, no context)."""
         return batch_workspace_bytes(model, n_particles, n_problems, T, **kw)
 
-    def batch_begin(self, model, observes, n_particles, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0):
-        """observes [B, T]: problem b's observation sequence in row b."""
+    def batch_begin(self, model, observes, n_particles, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
+                    keep_masses=False):
+        """observes [B, T]: problem b's observation sequence in row b.  keep_masses (with keep_history=False, here and in the other
+        two begins): the run keeps the backward smoother's m table, 64 bytes a problem and step, and batch_smooth, batch_smooth_lag and
+        batch_smooth_stats serve the filtering-only batch; batch_masses(b) reads the table."""
         obs = np.ascontiguousarray(observes, np.float64)
         if obs.ndim != 2:
             raise ValueError("observes must be [n_problems, T]")
-        cfg = self.batch_config(model, n_particles, obs.shape[0], resampler, ess_threshold, keep_history, algorithm, flags)
+        cfg = self.batch_config(model, n_particles, obs.shape[0], resampler, ess_threshold, keep_history, algorithm, _batch_flags(flags, keep_masses))
         self._chk(self.L.cpprob_hip_batch_begin(self.h, C.byref(cfg), obs.ctypes.data_as(C.POINTER(C.c_double)), obs.shape[1]))
         self.batch_B, self.batch_T, self.batch_n = obs.shape[0], obs.shape[1], int(n_particles)
         self.batch_K = 3 if model == MODEL_HMM3 else 8
@@ -520,7 +533,7 @@ class Engine:
         return self
 
     def batch_begin_problems(self, model, observes, n_particles, tables=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
-                             max_particles=None):
+                             max_particles=None, keep_masses=False):
         """A batch whose problems differ.  observes: a list of 1-D arrays, problem b's own sequence (any lengths); n_particles: an int
         or one count a problem; tables (MODEL_HMM_TABLE): None (the set_hmm table for every problem) or (means [B, k], transition
         [B, k, k]), problem b's own table.  batch_results() then returns arrays padded to the longest problem (rows t >= T_b zero) and
@@ -529,7 +542,7 @@ class Engine:
         h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
         flat = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0))
         top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
-        cfg = self.batch_config(model, top, len(seqs), resampler, ess_threshold, keep_history, algorithm, flags)
+        cfg = self.batch_config(model, top, len(seqs), resampler, ess_threshold, keep_history, algorithm, _batch_flags(flags, keep_masses))
         k, means, trans = 0, None, None
         if tables is not None:
             means = np.ascontiguousarray(tables[0], np.float64)
@@ -546,7 +559,7 @@ class Engine:
         return self
 
     def batch_begin_online(self, model, capacity, n_particles, seeds, tables=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC,
-                           flags=0, max_particles=None):
+                           flags=0, max_particles=None, keep_masses=False):
         """A batch whose observes arrive over time.  capacity: the most observes problem b may reach, one a problem; n_particles and
         tables as for batch_begin_problems; seeds: one Philox key a problem, for the life of the batch.  Every problem starts at
         length 0; batch_advance() feeds it.  batch_results() returns arrays padded to the largest capacity and batch_store(b) the
@@ -556,7 +569,7 @@ class Engine:
         if sd.shape != h_T.shape:
             raise ValueError("one seed per problem")
         top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
-        cfg = self.batch_config(model, top, h_T.size, resampler, ess_threshold, keep_history, algorithm, flags)
+        cfg = self.batch_config(model, top, h_T.size, resampler, ess_threshold, keep_history, algorithm, _batch_flags(flags, keep_masses))
         k, means, trans = 0, None, None
         if tables is not None:
             means = np.ascontiguousarray(tables[0], np.float64)
@@ -625,6 +638,15 @@ class Engine:
         logw = np.zeros(n)
         self._chk(self.L.cpprob_hip_batch_copy_store(self.h, int(b), vals.ctypes.data, anc.ctypes.data, logw.ctypes.data))
         return vals, anc, logw
+
+    def batch_masses(self, b):
+        """Problem b's rows of the m table (cpprob_hip_batch_copy_masses), float64 [T_b, 8]: m_t[s] = cnt_t[s] * fix_weight(ll_t[s], M_t),
+        integers below 2^45; a batch begun with keep_masses=True only."""
+        inside = 0 <= int(b) < self.batch_B                  # (an index out of range: the library's own refusal)
+        T = self.batch_T if self.batch_shapes is None or not inside else int(self.batch_shapes[0][int(b)])
+        out = np.zeros((T, 8))
+        self._chk(self.L.cpprob_hip_batch_copy_masses(self.h, int(b), out.ctypes.data, out.size))
+        return out
 
     def _batch_problem_shapes(self):
         """(T uint32 [B], n uint32 [B]) of the batch last begun / advanced."""

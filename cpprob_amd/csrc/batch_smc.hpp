@@ -78,7 +78,31 @@ struct BatchArgs {
     BatchSnap* snap;                           // [B]
     uint8_t* carry;                            // filtering: problem b's final generation, n bytes at carry + prob[b].store
     int skip_readout;                          // keep_history: 1 leaves the lineage walk to a later piece
+    // a filtering batch that keeps the backward smoother's m table (CPPROB_HIP_BATCH_KEEP_MASSES: the MASS kernels; the others do not read it)
+    double* mass;                              // [B][T_max][8]: row (b, t) at (b T_max + t) * 8, as tab; nullptr: not kept
 };
+
+// The m table of the backward smoother (csrc/batch_smooth.hpp), formed where a generation's counts stand: entry s of the row of a
+// generation with per-state counts cnt and log-weights ll[0..k), m[s] = cnt[s] * fix_weight(ll[s], M), M the largest ll over the
+// states with cnt > 0 -- the exact maximum, not the step's reference (the bound B_t unless the generation was requantised: q[s] of
+// the step is another number whenever the bound-setting state is unoccupied).  batch_smooth_count_kernel's statement on the counts
+// it re-derives from the store; the two agree bit for bit.  (cnt is indexed by constants only: it lives in registers.)
+__host__ __device__ inline double batch_mass(const uint32_t (&cnt)[8], const double* ll, int k, int s)
+{
+    double M = -INFINITY;
+    uint32_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (j < k && cnt[j]) M = fmax(M, ll[j]);
+        mine = j == s ? cnt[j] : mine;
+    }
+    return s < k ? u64_to_double((uint64_t)mine * fix_weight(ll[s], M)) : 0.0;
+}
+// ... and the whole row m[0..8), states >= k zero
+__host__ __device__ inline void batch_mass_row(const uint32_t (&cnt)[8], const double* ll, int k, double* out)
+{
+    for (int s = 0; s < 8; ++s) out[s] = batch_mass(cnt, ll, k, s);
+}
 
 __device__ __forceinline__ uint32_t batch_sel8(const uint32_t (&q)[8], int s)
 {
@@ -90,7 +114,10 @@ __device__ __forceinline__ uint32_t batch_sel8(const uint32_t (&q)[8], int s)
 
 // RESUME: the kernel of a batch advanced in pieces.  (A template parameter, not a run-time switch on a.first: with the switch the two
 // <HMM3, KEEP> kernels of the one-shot batches reserved a 68-byte private segment -- profiles/r12_notes.md, "Kernel resources".)
-template <class Model, int RS, bool KEEP, bool RESUME = false>
+// MASS: the kernel of a filtering batch that keeps the m table (KEEP = false only).  (A template parameter too: as a run-time switch
+// on a.mass the eight filtering kernels took 5 .. 10 more VGPRs and up to twice the SGPR spills, and <HMM_TABLE, systematic> fell from
+// five wavefronts a SIMD to four, for batches that never ask for the rows -- profiles/r18_notes.md, "Kernel resources".)
+template <class Model, int RS, bool KEEP, bool RESUME = false, bool MASS = false>
 __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
 {
     using V = typename Model::value_t;
@@ -198,6 +225,11 @@ __global__ __launch_bounds__(kThreads) void batch_smc_kernel(BatchArgs a)
         if (resample) for (int j = tid; j < n; j += kThreads) A[j] = -1;      // (every draw has read its ancestor: the barrier above)
         // ---- books ----
         const double* row = tab + (int64_t)t * kBatchTab;
+        // the generation's row of the m table (a filtering batch that keeps it): the first eight lanes of wavefront 1, an entry each,
+        // beside thread 0's books; no later phase reads it.  (A resumed problem's reloaded generation: the same values again.)
+        if constexpr (MASS && !KEEP) {
+            if (tid >= kWave && tid < kWave + 8) a.mass[((int64_t)b * a.T_max + t) * 8 + (tid - kWave)] = batch_mass(cnt, row, k_states, tid - kWave);
+        }
         const uint64_t draw = kResampleDrawBase + (uint64_t)(t + 1);          // the resampling in front of step t + 1
         double u0 = 0.0;
         if (resample) { const u32x4 r = draw_block(seed, 0, draw); u0 = u01_53(r.x, r.y); }

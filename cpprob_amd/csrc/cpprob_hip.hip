@@ -1010,9 +1010,12 @@ void free_run_buffers(cpprob_hip_ctx* c)
 //              the particle store packed): twelve regions, cpprob_hip_batch_problems_workspace_bytes states the sum
 //   online     (cpprob_hip_batch_begin_online: a described batch of the capacities, then every problem's first step of a launch, its
 //              snapshot and, filtering, its carried generation -- carry = sum of n_b): cpprob_hip_batch_online_workspace_bytes
-struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, prob, order, values, anc, first, snap, carry, total; };
+//   masses     (CPPROB_HIP_BATCH_KEEP_MASSES, any of the three; keep_history = 0): the m table [B][T_rows][8] last, so that every
+//              other region sits where it sits without the bit
+struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, prob, order, values, anc, first, snap, carry, mass, total; };
 size_t batch_round(size_t x) { return (x + 255) / 256 * 256; }
-BatchLayout batch_layout(uint64_t B, uint64_t T_rows, uint64_t tables, bool described, uint64_t entries, int spp, bool keep, bool online = false, uint64_t carry = 0)
+inline bool batch_masses(const cpprob_hip_batch_config* cfg) { return (cfg->flags & CPPROB_HIP_BATCH_KEEP_MASSES) != 0; }
+BatchLayout batch_layout(uint64_t B, uint64_t T_rows, uint64_t tables, bool described, uint64_t entries, int spp, bool keep, bool online = false, uint64_t carry = 0, bool masses = false)
 {
     BatchLayout L{};
     size_t o = 0;
@@ -1032,6 +1035,7 @@ BatchLayout batch_layout(uint64_t B, uint64_t T_rows, uint64_t tables, bool desc
     L.first = take(online ? B * sizeof(int32_t) : 0);
     L.snap = take(online ? B * sizeof(BatchSnap) : 0);
     L.carry = take(online && !keep ? carry : 0);
+    L.mass = take(masses ? B * T_rows * 8 * sizeof(double) : 0);
     L.total = o;
     return L;
 }
@@ -1072,6 +1076,7 @@ struct BatchState {
     // online batch: of its capacities, rows never move --, grown lazily), the problems' descriptors with the HMM3 thresholds behind
     // them, and their pinned sources, kOnlineSlots in turn
     double* d_mass = nullptr; size_t mass_rows = 0;
+    // (a filtering batch with CPPROB_HIP_BATCH_KEEP_MASSES has its m table in the workspace, written by the run: none of these three)
     std::vector<uint32_t> counted;             // [B], online batch: its rows [0, counted_b) of the m table are valid (any begin: none)
     char* d_sdesc = nullptr; size_t sdesc_cap = 0;
     char* pin_sdesc = nullptr;
@@ -1114,7 +1119,8 @@ int batch_check(const cpprob_hip_batch_config* cfg, size_t T, std::string& msg)
     if (cfg->resampler != CPPROB_HIP_RESAMPLE_SYSTEMATIC && cfg->resampler != CPPROB_HIP_RESAMPLE_STRATIFIED) { msg = "unknown resampler"; return CPPROB_HIP_EINVAL; }
     if (!(cfg->ess_threshold > 1.0)) { msg = "batched runs resample after every step (ess_threshold > 1): ESS-triggered schedules run on the single-population path (cpprob_hip_infer_begin / _run)"; return CPPROB_HIP_EUNSUPPORTED; }
     if (cfg->keep_history != 0 && cfg->keep_history != 1) { msg = "keep_history must be 0 or 1"; return CPPROB_HIP_EINVAL; }
-    if (cfg->flags != 0) { msg = "flags are reserved and must be 0"; return CPPROB_HIP_EINVAL; }
+    if (cfg->flags & ~CPPROB_HIP_BATCH_KEEP_MASSES) { msg = "flags are reserved and must be 0"; return CPPROB_HIP_EINVAL; }
+    if (cfg->flags && cfg->keep_history == 1) { msg = "CPPROB_HIP_BATCH_KEEP_MASSES is for filtering-only batches (keep_history = 0): a batch with keep_history = 1 is smoothed from its particle store"; return CPPROB_HIP_EINVAL; }
     if (cfg->n_particles == 0 || cfg->n_particles > (uint64_t)kBatchMaxN) { msg = "n_particles per problem must lie in 1 .. " + std::to_string(kBatchMaxN); return CPPROB_HIP_EINVAL; }
     if (cfg->n_problems == 0 || cfg->n_problems > (uint64_t)INT32_MAX) { msg = "n_problems must lie in 1 .. 2^31 - 1"; return CPPROB_HIP_EINVAL; }
     if (T == 0 || T > (size_t)INT32_MAX) { msg = "every problem needs 1 .. 2^31 - 1 observes"; return CPPROB_HIP_EINVAL; }
@@ -1218,7 +1224,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         at_store += (int64_t)(T_b * n_b);
         at_carry += (int64_t)n_b;
     }
-    bs->lay = batch_layout(B, T_max, tables, described, (uint64_t)at_store, spp, cfg->keep_history == 1, online, (uint64_t)at_carry);
+    bs->lay = batch_layout(B, T_max, tables, described, (uint64_t)at_store, spp, cfg->keep_history == 1, online, (uint64_t)at_carry, batch_masses(cfg));
     if (bs->lay.total > bs->cap) {
         // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
         dfree(bs->d_ws); bs->cap = 0;
@@ -1266,17 +1272,22 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
 // weights from wfirst[b] on, m_b = n_b or min(n_b, max_particles); a problem of length 0 owns neither.  first[B] / wfirst[B]: the totals.
 inline uint64_t batch_paths_m(uint64_t n, uint64_t max_particles) { return max_particles && max_particles < n ? max_particles : n; }
 
-// The eight kernels of cpprob_hip_batch_run, and the eight of cpprob_hip_batch_advance.
+// The eight kernels of cpprob_hip_batch_run, and the eight of cpprob_hip_batch_advance; a filtering batch that keeps its masses
+// (CPPROB_HIP_BATCH_KEEP_MASSES) has four of its own for either.
 using BatchKernel = void (*)(BatchArgs);
 template <class Model, bool RESUME>
-BatchKernel batch_kernel(bool stratified, bool keep)
+BatchKernel batch_kernel(bool stratified, bool keep, bool masses)
 {
     static constexpr BatchKernel k[2][2] = {{batch_smc_kernel<Model, kFixSystematic, false, RESUME>, batch_smc_kernel<Model, kFixSystematic, true, RESUME>},
                                             {batch_smc_kernel<Model, kFixStratified, false, RESUME>, batch_smc_kernel<Model, kFixStratified, true, RESUME>}};
-    return k[stratified][keep];
+    static constexpr BatchKernel km[2] = {batch_smc_kernel<Model, kFixSystematic, false, RESUME, true>, batch_smc_kernel<Model, kFixStratified, false, RESUME, true>};
+    return masses && !keep ? km[stratified] : k[stratified][keep];
 }
 template <class Model>
-BatchKernel batch_kernel(bool stratified, bool keep, bool resume) { return resume ? batch_kernel<Model, true>(stratified, keep) : batch_kernel<Model, false>(stratified, keep); }
+BatchKernel batch_kernel(bool stratified, bool keep, bool resume, bool masses)
+{
+    return resume ? batch_kernel<Model, true>(stratified, keep, masses) : batch_kernel<Model, false>(stratified, keep, masses);
+}
 
 }  // namespace
 
@@ -3992,7 +4003,7 @@ int cpprob_hip_batch_workspace_bytes(const cpprob_hip_batch_config* cfg, size_t 
     if (int rc = batch_check(cfg, T, msg)) return fail(nullptr, rc, msg);
     if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
     const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
-    *out_bytes = batch_layout(cfg->n_problems, T, 1, false, cfg->n_problems * T * cfg->n_particles, spp, cfg->keep_history == 1).total;
+    *out_bytes = batch_layout(cfg->n_problems, T, 1, false, cfg->n_problems * T * cfg->n_particles, spp, cfg->keep_history == 1, false, 0, batch_masses(cfg)).total;
     return 0;
 }
 
@@ -4013,7 +4024,7 @@ int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg
     if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(nullptr, rc, msg);
     if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
     const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
-    *out_bytes = batch_layout(cfg->n_problems, sh.T_max, cfg->n_problems, true, sh.steps, spp, cfg->keep_history == 1).total;
+    *out_bytes = batch_layout(cfg->n_problems, sh.T_max, cfg->n_problems, true, sh.steps, spp, cfg->keep_history == 1, false, 0, batch_masses(cfg)).total;
     return 0;
 }
 
@@ -4085,9 +4096,10 @@ static int batch_launch(cpprob_hip_ctx* c, BatchState* bs, bool readout)
     a.ess = reinterpret_cast<double*>(bs->d_ws + bs->lay.ess);
     a.resampled = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.res);
     a.n_requant = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.nreq);
+    a.mass = batch_masses(&bs->cfg) ? reinterpret_cast<double*>(bs->d_ws + bs->lay.mass) : nullptr;
     a.T_max = bs->T; a.n = (int)bs->cfg.n_particles; a.spp = bs->K; a.ess_frac = bs->cfg.ess_threshold;
     const bool strat = bs->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED;
-    const BatchKernel kern = bs->cfg.model == CPPROB_HIP_MODEL_HMM3 ? batch_kernel<ModelHmm3>(strat, keep, bs->online) : batch_kernel<ModelHmmK>(strat, keep, bs->online);
+    const BatchKernel kern = bs->cfg.model == CPPROB_HIP_MODEL_HMM3 ? batch_kernel<ModelHmm3>(strat, keep, bs->online, a.mass != nullptr) : batch_kernel<ModelHmmK>(strat, keep, bs->online, a.mass != nullptr);
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), (size_t)batch_lds_bytes(a.n), c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return 0;
@@ -4114,7 +4126,7 @@ int cpprob_hip_batch_online_workspace_bytes(const cpprob_hip_batch_config* cfg, 
     if (int rc = batch_check_problems(cfg, h_Tcap, h_n, sh, msg)) return fail(nullptr, rc, msg);
     if (!out_bytes) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
     const int spp = cfg->model == CPPROB_HIP_MODEL_HMM3 ? 3 : 8;
-    *out_bytes = batch_layout(cfg->n_problems, sh.T_max, cfg->n_problems, true, sh.steps, spp, cfg->keep_history == 1, true, sh.particles).total;
+    *out_bytes = batch_layout(cfg->n_problems, sh.T_max, cfg->n_problems, true, sh.steps, spp, cfg->keep_history == 1, true, sh.particles, batch_masses(cfg)).total;
     return 0;
 }
 
@@ -4292,6 +4304,24 @@ int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_
     return 0;
 }
 
+int cpprob_hip_batch_copy_masses(cpprob_hip_ctx* c, uint64_t problem, double* h_out, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (!batch_masses(&bs->cfg)) return fail(c, CPPROB_HIP_ESTATE, "the batch keeps no masses: begin it with keep_history = 0 and CPPROB_HIP_BATCH_KEEP_MASSES");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    const size_t T = (size_t)bs->prob[problem].T;
+    if (n_doubles < T * 8) return fail(c, CPPROB_HIP_EINVAL, "h_out too small: " + std::to_string(T * 8) + " doubles (8 a step of the problem)");
+    if (T == 0) return 0;
+    if (!h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(h_out, bs->d_ws + bs->lay.mass + (size_t)problem * (size_t)bs->T * 8 * sizeof(double), T * 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 // ---- posterior traces of a batch (csrc/batch_paths.hpp) ---------------------------------------------------------------------------
 int cpprob_hip_batch_paths_layout(const uint32_t* h_T, const uint32_t* h_n, uint64_t n_problems, uint64_t max_particles, uint64_t* h_first, uint64_t* h_wfirst)
 {
@@ -4432,7 +4462,7 @@ static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_
     BatchState* bs = c->batch;
     if (bs) bs->smooth_gy_count = bs->smooth_gy_lag = 0;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
-    if (bs->cfg.keep_history != 1) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
+    if (bs->cfg.keep_history != 1 && !batch_masses(&bs->cfg)) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
     if (draw_index >= (uint64_t)kBackwardMaxDraws) return fail(c, CPPROB_HIP_EINVAL, "draw_index must lie in 0 .. 2^16 - 1");
     if (n_traj > (uint64_t)kBackwardMaxTraj) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 0 .. 2^20");
     uint64_t rows = 0;
@@ -4465,10 +4495,14 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     const size_t marg_rows = lg ? (size_t)lg->n_rows : (size_t)bs->T;
     if (d_marg && marg_rows) HIP_TRY(c, hipMemsetAsync(d_marg, 0, B * marg_rows * (size_t)bs->K * sizeof(double), c->stream));   // rows past the problem's, states >= k
     const bool with_traj = d_traj && n_traj;
+    // a filtering batch with masses: the run wrote the m table into the workspace, rows by T_max as the per-step tables'; nothing to
+    // count, no table of the context's own
+    const bool kept = batch_masses(&bs->cfg);
     size_t rows = 0, reached = 0;
     for (size_t b = 0; b < B; ++b) { reached += (size_t)bs->prob[b].T; rows += bs->online ? (size_t)bs->cap_T[b] : (size_t)bs->prob[b].T; }
     if (st && reached == 0) HIP_TRY(c, hipMemsetAsync(st->d_stats, 0, B * (size_t)kSuffStats * sizeof(double), c->stream));
     if (reached == 0 || (!d_marg && !with_traj && !st)) return 0;           // (an online batch before its first observes, or nothing asked for)
+    if (kept) rows = 0;
     if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
         // (earlier calls' copies and kernels may still read the buffers this replaces)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -4502,7 +4536,8 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         pd[b].T = L; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at; pd[b].trows = at_traj;
         pd[b].lo = L - W; pd[b].mfrom = mfrom; pd[b].cto = L;
         // the rows the pass owes: an online batch's new ones; a run batch's -- nothing is kept -- those this call reads
-        if (bs->online) pd[b].cfrom = (int)bs->counted[b];
+        if (kept) { pd[b].rows = (int64_t)b * bs->T; pd[b].store = 0; pd[b].cfrom = L; }
+        else if (bs->online) pd[b].cfrom = (int)bs->counted[b];
         else pd[b].cfrom = lg ? std::min(d_marg ? mfrom : L, with_traj ? L - W : L) : 0;
         at += bs->online ? (int64_t)bs->cap_T[b] : (int64_t)L;
         at_traj += W;
@@ -4519,18 +4554,18 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     ++bs->n_smooth;
     BatchSmoothArgs a{};
     a.desc = reinterpret_cast<const BatchSmoothProblem*>(bs->d_sdesc);
-    a.values = reinterpret_cast<const int8_t*>(bs->d_ws + bs->lay.values);
+    a.values = kept ? nullptr : reinterpret_cast<const int8_t*>(bs->d_ws + bs->lay.values);
     a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
     a.thr = hmm3 ? reinterpret_cast<const uint64_t*>(bs->d_sdesc + thr_at) : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
     a.thr_stride = !hmm3 && bs->described ? 64 : 0;
     a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
-    a.mass = bs->d_mass; a.marg = d_marg; a.traj = with_traj ? d_traj : nullptr;
+    a.mass = kept ? reinterpret_cast<double*>(bs->d_ws + bs->lay.mass) : bs->d_mass; a.marg = d_marg; a.traj = with_traj ? d_traj : nullptr;
     a.draw_base = kBackwardDrawBase + (draw_index << 24);
     a.T_max = bs->T; a.k = hmm3 ? 3 : bs->hk; a.spp = bs->K; a.n_traj = (int)n_traj;
     a.marg_rows = (int)marg_rows; a.lag = lg ? (int)lg->lag : 0;
     a.lds_bytes = (int)std::min<int64_t>((int64_t)W_top * 64, kBackwardLdsMax);
     // the counting pass: at least ~kSmoothCountGroups workgroups where the batch owes that many rows, a workgroup walking the rows gridDim.y apart
-    if (range_top > 0) {
+    if (range_top > 0 && !kept) {
         const unsigned gy = (unsigned)std::min<uint64_t>((uint64_t)range_top, std::max<uint64_t>(8, ((uint64_t)kSmoothCountGroups + B - 1) / B));
         hipLaunchKernelGGL(batch_smooth_count_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());

@@ -31,12 +31,13 @@ def m_step(stats, means, trans):
     return means, trans
 
 
-def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iterations, resampler=RESAMPLE_SYSTEMATIC):
+def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iterations, resampler=RESAMPLE_SYSTEMATIC, keep_history=True):
     """Batched particle EM.  observes: a list of B 1-D sequences, or one sequence every problem shares (restarts: one sequence under
     B initial tables); means0 [B, k], trans0 [B, k, k] the initial tables; seeds [B].  Iteration i begins a batch with the current
     tables (batch_begin_problems), runs it with seeds + i, takes the statistics and the M-step.  Returns (means [iterations + 1, B, k],
     trans [iterations + 1, B, k, k], log_evidence [iterations, B]): the tables before every iteration and after the last, and the
-    log-evidence estimate of every iteration's run (of the tables it began with)."""
+    log-evidence estimate of every iteration's run (of the tables it began with).  keep_history=False: the batches are filtering-only
+    and keep the smoother's masses (keep_masses) -- the same arrays bit for bit, without a particle store."""
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
     B = means.shape[0]
@@ -48,7 +49,8 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
     sd = np.ascontiguousarray(seeds, np.uint64)
     m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(iterations), B))
     for it in range(int(iterations)):
-        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), resampler=resampler)
+        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), resampler=resampler, keep_history=bool(keep_history),
+                                    keep_masses=not keep_history)
         engine.batch_run(sd + np.uint64(it))
         stats = engine.batch_smooth_stats(seqs)
         ev[it] = [s["log_evidence"] for s in engine.batch_results()[0]]

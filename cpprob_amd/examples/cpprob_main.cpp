@@ -9,6 +9,9 @@
 //                   --gpus N | --devices a,b,...  (one joint population sharded over several GPUs: exact global resampling, RCCL over xGMI;
 //                                                  equal entries, e.g. 0,0,0: every rank on that GPU)
 //                   --filtering_only (smc, built-in models: O(N) particle store, filtering statistics, no posterior files)
+//                   --keep_masses (the batch modes and --stream_chunk, with --filtering_only: the runs keep the backward smoother's masses,
+//                   64 bytes a problem and step, so --backward_smoothing, --backward_trajectories, --smoothing_lag and --em_iterations
+//                   serve the filtering-only batch; same output as without the two flags)
 //                   --no_dump  --dump_max_particles M  --json (print the in-memory result as one JSON line)
 //                   --batch_observes_file F (smc, built-in HMMs: one observation sequence a line, all in one batched launch; seeds --seed + line
 //                   index; one estimate a line, one JSON object a line under --json)
@@ -261,6 +264,7 @@ int main(int argc, char** argv)
         else if (f == "--ess_threshold") opt.ess_threshold = std::stod(next());
         else if (f == "--resampler") { const std::string r = next(); opt.resampler = r == "multinomial" ? 2 : (r == "stratified" ? 1 : 0); }
         else if (f == "--generic") opt.prefer_builtin = false;
+        else if (f == "--keep_masses") opt.keep_masses = true;                     // the batch modes, with --filtering_only: CPPROB_HIP_BATCH_KEEP_MASSES
         else if (f == "--filtering_only") { opt.keep_history = false; opt.dump = false; }   // smc, built-in models: O(N) particle store, filtering statistics
         else if (f == "--islands") opt.islands = true;                          // unchanged-model smc over several ranks: independent runs combined by evidence
         else if (f == "--joint_across_devices") opt.joint_across_devices = true; // ... or the joint population even across physical GPUs (unvalidated on real links)

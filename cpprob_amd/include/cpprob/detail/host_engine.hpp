@@ -656,11 +656,12 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     }
     if (st.int_ids.size() != T) throw std::runtime_error("built-in model kernel and the model function disagree on the number of predict statements");
     const Options& opt = options();
-    if (!opt.keep_history && !opt.batch_dump_file.empty())
+    const bool masses = !opt.keep_history && opt.keep_masses;      // (a filtering-only batch that keeps the smoother's masses)
+    if (!opt.keep_history && !opt.batch_dump_file.empty() && !(masses && opt.backward_trajectories))
         throw std::runtime_error("cpprob::gpu::inference_batch: a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
-    if (!opt.keep_history && opt.backward_smoothing)
+    if (!opt.keep_history && !masses && opt.backward_smoothing)
         throw std::runtime_error("cpprob::gpu::inference_batch: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
-    if (!opt.keep_history && opt.smoothing_lag >= 0)
+    if (!opt.keep_history && !masses && opt.smoothing_lag >= 0)
         throw std::runtime_error("cpprob::gpu::inference_batch: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     ContextLease lease(opt.device);
     Context& ctx = *lease;
@@ -669,7 +670,7 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     bc.model = e->builtin_model;
     bc.resampler = opt.resampler;
     bc.keep_history = opt.keep_history ? 1 : 0;
-    bc.flags = 0;
+    bc.flags = masses ? CPPROB_HIP_BATCH_KEEP_MASSES : 0;
     bc.ess_threshold = opt.ess_threshold;
     bc.n_particles = n;
     bc.n_problems = observes.size();
@@ -743,11 +744,12 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
         pk.T_max = std::max(pk.T_max, o.size()); pk.n_max = std::max(pk.n_max, nb);
     }
     const Options& opt = options();
-    if (!opt.keep_history && !opt.batch_dump_file.empty())
+    const bool masses = !opt.keep_history && opt.keep_masses;      // (a filtering-only batch that keeps the smoother's masses)
+    if (!opt.keep_history && !opt.batch_dump_file.empty() && !(masses && opt.backward_trajectories))
         throw std::runtime_error(who + ": a filtering-only run (options().keep_history = false) keeps no traces to dump: clear options().batch_dump_file");
-    if (!opt.keep_history && opt.backward_smoothing)
+    if (!opt.keep_history && !masses && opt.backward_smoothing)
         throw std::runtime_error(who + ": backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
-    if (!opt.keep_history && opt.smoothing_lag >= 0)
+    if (!opt.keep_history && !masses && opt.smoothing_lag >= 0)
         throw std::runtime_error(who + ": fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     return pk;
 }
@@ -764,7 +766,7 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
     bc.model = CPPROB_HIP_MODEL_HMM_TABLE;
     bc.resampler = opt.resampler;
     bc.keep_history = opt.keep_history ? 1 : 0;
-    bc.flags = 0;
+    bc.flags = !opt.keep_history && opt.keep_masses ? CPPROB_HIP_BATCH_KEEP_MASSES : 0;
     bc.ess_threshold = opt.ess_threshold;
     bc.n_particles = pk.n_max;
     bc.n_problems = B;
@@ -816,7 +818,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // seeds[b] + i, takes the backward smoother's expected sufficient statistics (the E-step, on the device) and sets
 //   transition[s][s'] = xi[s][s'] / (xi[s][0] + .. + xi[s][k-1]),   means[s] = occ_y[s] / occ[s]
 // (the M-step; a row or a state without mass keeps its value; the emission's sigma is 1 and not fitted).  Returns the fitted tables
-// and the results of the last run -- those of the tables that run began with.  options().keep_history must be set;
+// and the results of the last run -- those of the tables that run began with.  options().keep_history must be set, or options().keep_masses
+// with it (the statistics then come from the masses the filtering-only runs keep);
 // options().batch_dump_file is written by the last run.
 struct HmmTableFit { std::vector<HmmTable> tables; std::vector<Result> results; };
 
@@ -825,7 +828,7 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 {
     const std::size_t B = seeds.size();
     HmmTableProblems pk = pack_hmm_table_problems("cpprob::gpu::hmm_table_fit", tables, observes, n, B);
-    if (!options().keep_history)
+    if (!options().keep_history && !options().keep_masses)
         throw std::runtime_error("cpprob::gpu::hmm_table_fit: the statistics read the particle store: a filtering-only run (options().keep_history = false) keeps none");
     const std::size_t k = pk.k, R = 88;
     HmmTableFit fit;
@@ -878,12 +881,12 @@ class HmmTableStream {
 public:
     HmmTableStream(const std::vector<HmmTable>& tables, const std::vector<std::size_t>& capacities, const std::vector<std::size_t>& n,
                    const std::vector<std::uint64_t>& seeds)
-        : B_(seeds.size()), k_(tables.empty() ? 0 : tables[0].means.size()), keep_(options().keep_history), lease_(options().device)
+        : B_(seeds.size()), k_(tables.empty() ? 0 : tables[0].means.size()), keep_(options().keep_history), masses_(!options().keep_history && options().keep_masses), lease_(options().device)
     {
         if (B_ == 0) throw std::runtime_error("cpprob::gpu::HmmTableStream: no problems (one seed per problem)");
-        if (!keep_ && backward_)
+        if (!keep_ && !masses_ && backward_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
-        if (!keep_ && lag_ >= 0)
+        if (!keep_ && !masses_ && lag_ >= 0)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         const std::size_t B = B_;
         auto fits = [B](std::size_t have) { return have == B || have == 1; };
@@ -910,7 +913,7 @@ public:
         bc.model = CPPROB_HIP_MODEL_HMM_TABLE;
         bc.resampler = opt.resampler;
         bc.keep_history = keep_ ? 1 : 0;
-        bc.flags = 0;
+        bc.flags = masses_ ? CPPROB_HIP_BATCH_KEEP_MASSES : 0;
         bc.ess_threshold = opt.ess_threshold;
         bc.n_particles = n_max;
         bc.n_problems = B_;
@@ -982,7 +985,7 @@ public:
     // Problem b's posterior as <prefix>_<b>.int / .ids for the lengths reached: the first dump_max_ traces (0 = all).
     void dump(const std::string& prefix)
     {
-        if (!keep_) throw std::runtime_error("cpprob::gpu::HmmTableStream: a filtering-only run (options().keep_history = false) keeps no traces to dump");
+        if (!keep_ && !(masses_ && backward_traj_)) throw std::runtime_error("cpprob::gpu::HmmTableStream: a filtering-only run (options().keep_history = false) keeps no traces to dump");
         Context& ctx = *lease_;
         std::vector<std::uint32_t> L(B_);
         ctx.check(cpprob_hip_batch_lengths(ctx.get(), L.data()), "cpprob_hip_batch_lengths");
@@ -992,7 +995,7 @@ public:
 
 private:
     std::size_t B_, k_, T_max_ = 0;
-    bool keep_;
+    bool keep_, masses_;                       // masses_: a filtering-only batch that keeps the smoother's masses (options().keep_masses)
     bool backward_ = options().backward_smoothing;
     std::size_t backward_traj_ = options().backward_trajectories;
     long lag_ = options().smoothing_lag;

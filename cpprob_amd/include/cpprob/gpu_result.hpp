@@ -47,6 +47,9 @@ struct Options {
     bool keep_history = true;                         // smc, built-in models on one GPU: false = filtering only -- O(N) particle store instead of O(N T),
                                                       // every predict hit's numbers under its own generation's weights, no posterior files
                                                       // (cpprob_hip_config::keep_history)
+    bool keep_masses = false;                         // batched runs with keep_history = false: the run keeps the backward smoother's masses (64 bytes a
+                                                      // problem and step, CPPROB_HIP_BATCH_KEEP_MASSES), so backward_smoothing, backward_trajectories,
+                                                      // smoothing_lag and hmm_table_fit serve the filtering-only batch; lineage dumps stay refused
     std::uint64_t particle_offset = 0;                // (set by the engine when it shards a population: global id of this shard's first particle)
     bool progress = false;
     bool islands = false;                             // smc over several ranks, unchanged models: independent SMC runs combined by their evidence instead of

@@ -279,11 +279,19 @@ typedef struct cpprob_hip_batch_config {
     int32_t model;          /* CPPROB_HIP_MODEL_HMM3 | CPPROB_HIP_MODEL_HMM_TABLE                                   */
     int32_t resampler;      /* CPPROB_HIP_RESAMPLE_SYSTEMATIC | CPPROB_HIP_RESAMPLE_STRATIFIED                      */
     int32_t keep_history;   /* 1: smoothed statistics + a per-problem particle store; 0: filtering statistics, O(B n) */
-    uint32_t flags;         /* must be 0 (reserved)                                                                 */
+    uint32_t flags;         /* 0 or CPPROB_HIP_BATCH_KEEP_MASSES (keep_history = 0 only); every other bit is reserved  */
     double ess_threshold;   /* must be > 1 (every-step schedule)                                                    */
     uint64_t n_particles;   /* per problem, 1 .. 8192                                                               */
     uint64_t n_problems;    /* B                                                                                    */
 } cpprob_hip_batch_config;
+/* cpprob_hip_batch_config::flags.  A filtering-only batch (keep_history = 0) that keeps the m table of the backward smoother: the
+ * eight integer masses m_t[s] = cnt_t[s] * fix_weight(ll_t[s], M_t) of every (problem, step), written by the run itself where the
+ * step's counts stand (csrc/batch_smc.hpp) into one more workspace region of 64 B T bytes (the last one; a batch of problems: 64 B T_max,
+ * an online batch: of the largest capacity), rounded as the others.  cpprob_hip_batch_smooth*, _smooth_lag* and _smooth_stats* then
+ * serve the batch as they serve one with keep_history = 1 -- the same bits, without a counting launch, a particle store or ancestors:
+ * O(n) memory a problem plus 64 bytes a step.  The lineage read-outs (cpprob_hip_batch_copy_store, _paths*) keep returning
+ * CPPROB_HIP_ESTATE: there are no lineages.  With keep_history = 1 the bit is CPPROB_HIP_EINVAL. */
+#define CPPROB_HIP_BATCH_KEEP_MASSES 2u
 /* Pure host function (no device, no context): validates cfg and T and returns the device bytes a batch needs.  The workspace is ten
  * regions, each rounded up to a multiple of 256 bytes: 64 B T (per-step tables), 8 B (seeds), 512 (transition rows), 256 B (control
  * blocks), 8 B T spp (statistics), 8 B T (ESS), 4 B T (resampling flags), 4 B (requantised generations), and with keep_history = 1
@@ -302,6 +310,10 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* ctx, double* d_out, size_t n
 /* Problem `problem`'s particle store: h_values[T][n], h_anc[T][n] (cpprob_hip_copy_values / _ancestors' layout) and the final
  * log-weights h_logw[n]; any may be NULL.  keep_history = 1 only (else CPPROB_HIP_ESTATE).  Synchronises. */
 int cpprob_hip_batch_copy_store(cpprob_hip_ctx* ctx, uint64_t problem, int32_t* h_values, int32_t* h_anc, double* h_logw);
+/* Problem `problem`'s rows of the m table after a finished run (or advance): h_out[T_b][8], T_b its length (an online batch: the
+ * length reached), n_doubles the capacity of h_out.  A batch begun with CPPROB_HIP_BATCH_KEEP_MASSES only (else CPPROB_HIP_ESTATE);
+ * CPPROB_HIP_EINVAL: a problem index out of range or fewer than 8 T_b doubles.  Synchronises. */
+int cpprob_hip_batch_copy_masses(cpprob_hip_ctx* ctx, uint64_t problem, double* h_out, size_t n_doubles);
 
 /* A batch whose problems differ: a second way to begin, in which problem b brings its own number of observes h_T[b], its own particle
  * count h_n[b] and, for CPPROB_HIP_MODEL_HMM_TABLE, its own table -- the same sequence under many parameter settings (a likelihood
