@@ -12,5 +12,7 @@ from .capi import (ALG_SIS, ALG_SMC, MODEL_GAUSSIAN_README, MODEL_GAUSSIAN_UNKNO
 
 from . import em  # noqa: F401
 from .em import hmm_table_em, m_step  # noqa: F401
+from . import forecast  # noqa: F401
+from .forecast import observation_forecast, predictive_log_likelihood  # noqa: F401
 
 __version__ = "0.1.0"

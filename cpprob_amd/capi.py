@@ -44,6 +44,7 @@ SYMBOLS = [
     "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
     "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device", "cpprob_hip_batch_smooth_grid",
     "cpprob_hip_batch_smooth_stats", "cpprob_hip_batch_smooth_stats_device",
+    "cpprob_hip_batch_forecast", "cpprob_hip_batch_forecast_device", "cpprob_hip_batch_predictive", "cpprob_hip_batch_predictive_device",
 ]
 
 
@@ -181,6 +182,7 @@ def batch_smooth_layout(T, n_traj):
     return first
 
 
+FORECAST_MAX_HORIZON, FORECAST_MAX_TRAJ, FORECAST_MAX_DRAWS = 1 << 24, 1 << 20, 1 << 16      # cpprob_hip_batch_forecast: horizon <, n_traj <=, draw_index <
 STATS_PER_PROBLEM = 88                        # doubles a problem of cpprob_hip_batch_smooth_stats: xi[8][8], occ[8], occ_y[8], occ_yy[8]
 
 
@@ -339,6 +341,10 @@ def load_library(path=None):
         "cpprob_hip_batch_smooth_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "cpprob_hip_batch_smooth_stats": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_forecast": (C.c_int, [vp, u64, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_forecast_device": (C.c_int, [vp, u64, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_predictive": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, vp, sz]),
+        "cpprob_hip_batch_predictive_device": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -755,6 +761,73 @@ class Engine:
         """The same left in a device tensor, enqueued behind the run / advance without a host synchronisation: stats torch float64
         [B, 88] (split_stats names its columns), observes a torch float64 tensor packed as above or None."""
         self._chk(self.L.cpprob_hip_batch_smooth_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    @staticmethod
+    def _forecast_args(horizon, n_traj, draw_index):
+        """The ranges cpprob_hip_batch_forecast refuses, checked before anything is allocated."""
+        horizon, n_traj, draw_index = int(horizon), int(n_traj), int(draw_index)
+        if not 1 <= horizon < FORECAST_MAX_HORIZON:
+            raise ValueError("horizon must lie in 1 .. 2^24 - 1")
+        if not 0 <= n_traj <= FORECAST_MAX_TRAJ:
+            raise ValueError("n_traj must lie in 0 .. 2^20")
+        if not 0 <= draw_index < FORECAST_MAX_DRAWS:
+            raise ValueError("draw_index must lie in 0 .. 2^16 - 1")
+        return horizon, n_traj, draw_index
+
+    def batch_forecast(self, horizon, n_traj=0, draw_index=0):
+        """Forecasts of every problem (cpprob_hip_batch_forecast): (marginals [B, horizon, spp], row h - 1 the law of the state h
+        steps past the last observe, P(x_{L-1+h} | y_0 .. y_{L-1}); trajectories int32 [B, horizon + 1, n_traj], simulated futures
+        whose row 0 is the present state).  A problem of length 0 has rows of zeros.  draw_index (< 2^16) selects the trajectories'
+        Philox draws; the marginals do not depend on it.  cpprob_amd.forecast.observation_forecast turns the marginals into the
+        forecast of the observe itself."""
+        horizon, n_traj, draw_index = self._forecast_args(horizon, n_traj, draw_index)
+        marg = np.zeros((self.batch_B, horizon, self.batch_K))
+        traj = np.zeros((self.batch_B, horizon + 1, n_traj), np.int32)
+        self._chk(self.L.cpprob_hip_batch_forecast(self.h, horizon, n_traj, draw_index, marg.ctypes.data, marg.size, traj.ctypes.data if n_traj else None, traj.size))
+        return marg, traj
+
+    def batch_forecast_device(self, horizon, marginals=None, traj_i8=None, n_traj=0, draw_index=0):
+        """The same left in device tensors, enqueued behind the run / advance without a host synchronisation: marginals torch float64
+        [B, horizon, spp] or None, traj_i8 torch int8 [B, horizon + 1, n_traj] or None (their numel() are the capacities)."""
+        horizon, n_traj, draw_index = self._forecast_args(horizon, n_traj, draw_index)
+        self._chk(self.L.cpprob_hip_batch_forecast_device(self.h, horizon, n_traj, draw_index, _dptr(marginals), 0 if marginals is None else marginals.numel(),
+                                                          _dptr(traj_i8), 0 if traj_i8 is None else traj_i8.numel()))
+
+    def _batch_predictive_shapes(self, from_steps):
+        """(from uint32 [B] or None, n_rows) of a predictive call on the batch last begun / advanced."""
+        h_T, _ = self._batch_problem_shapes()
+        h_T = np.ascontiguousarray(h_T, np.uint32)
+        if from_steps is None:
+            return None, (int(h_T.max()) if h_T.size else 0) + 1
+        f = np.asarray(from_steps)
+        if f.shape != h_T.shape:
+            raise ValueError("one first step per problem")
+        if f.size and (f.min() < 0 or f.max() >= 1 << 32):
+            raise ValueError("from_steps must be steps, 0 .. 2^32 - 1")
+        h_from = np.ascontiguousarray(f, np.uint32)
+        left = h_T.astype(np.int64) + 1 - h_from.astype(np.int64)
+        return h_from, max(int(left.max()) if left.size else 0, 0)
+
+    def batch_predictive(self, from_steps=None):
+        """One-step predictive rows of every problem (cpprob_hip_batch_predictive): [B, n_rows, spp]; row r of problem b is
+        P(x_t | y_0 .. y_{t-1}) at t = from_b + r <= L_b (t = 0: the uniform initial law; t = L_b: the forecast's first row), zero
+        past it.  from_steps None: every problem from step 0; n_rows = max(L_b + 1 - from_b).
+        cpprob_amd.forecast.predictive_log_likelihood scores the observes with them."""
+        h_from, n_rows = self._batch_predictive_shapes(from_steps)
+        rows = np.zeros((self.batch_B, n_rows, self.batch_K))
+        if rows.size == 0:
+            return rows
+        self._chk(self.L.cpprob_hip_batch_predictive(self.h, None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows, rows.ctypes.data, rows.size))
+        return rows
+
+    def batch_predictive_device(self, rows, from_steps=None):
+        """The same left in a device tensor, enqueued behind the run / advance without a host synchronisation: rows torch float64
+        [B, n_rows, spp] (n_rows = its second dimension)."""
+        if rows is None or rows.dim() != 3:
+            raise ValueError("rows must be [B, n_rows, spp]")
+        h_from, _ = self._batch_predictive_shapes(from_steps)
+        self._chk(self.L.cpprob_hip_batch_predictive_device(self.h, None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), int(rows.shape[1]),
+                                                            _dptr(rows), rows.numel()))
 
     def batch_smooth_grid(self):
         """(gridDim.y of the counting launch, gridDim.y of the fixed-lag launch) of this context's last smoothing call

@@ -23,6 +23,7 @@
 #include "batch_paths.hpp"
 #include "batch_smooth.hpp"
 #include "batch_suffstats.hpp"
+#include "batch_forecast.hpp"
 
 using namespace cph;
 
@@ -4481,18 +4482,24 @@ static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_
 struct BatchSmoothLag { uint64_t lag; const uint32_t* from; uint64_t n_rows; };
 // A statistics call's own (cpprob_hip_batch_smooth_stats): the observes (or nullptr) and the records, both on the device.
 struct BatchSmoothStats { const double* d_obs; double* d_stats; };
+// A forecast call's own (cpprob_hip_batch_forecast: horizon > 0; cpprob_hip_batch_predictive: horizon = 0, the first rows wanted and
+// the rows a problem of the output).
+struct BatchForecast { uint64_t horizon; const uint32_t* from; uint64_t n_rows; };
 
 // Enqueues the descriptors' copy, the counting pass and the smoothing pass on the context's stream; waits for nothing but the pinned
 // slot it writes (the copy that read it kOnlineSlots calls ago) and, where a buffer of its own has to grow, for the calls before it.
 // An online batch's m table is addressed by capacity and kept: the pass counts rows [counted_b, L_b) and moves the watermark.
 // st: the smoothing pass is batch_smooth_stats_kernel (csrc/batch_suffstats.hpp) and nothing else is written.
+// fc: the pass after the counting is batch_forecast_kernel or batch_predictive_kernel (csrc/batch_forecast.hpp); a run batch counts
+// row L - 1 (the forecast) or rows max(from_b, 1) - 1 .. L - 1 (the predictive rows) only.
 static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr,
-                                const BatchSmoothStats* st = nullptr)
+                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
     const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
-    const size_t marg_rows = lg ? (size_t)lg->n_rows : (size_t)bs->T;
+    const bool predictive = fc && fc->horizon == 0;
+    const size_t marg_rows = fc ? (size_t)(predictive ? fc->n_rows : fc->horizon) : lg ? (size_t)lg->n_rows : (size_t)bs->T;
     if (d_marg && marg_rows) HIP_TRY(c, hipMemsetAsync(d_marg, 0, B * marg_rows * (size_t)bs->K * sizeof(double), c->stream));   // rows past the problem's, states >= k
     const bool with_traj = d_traj && n_traj;
     // a filtering batch with masses: the run wrote the m table into the workspace, rows by T_max as the per-step tables'; nothing to
@@ -4501,7 +4508,9 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     size_t rows = 0, reached = 0;
     for (size_t b = 0; b < B; ++b) { reached += (size_t)bs->prob[b].T; rows += bs->online ? (size_t)bs->cap_T[b] : (size_t)bs->prob[b].T; }
     if (st && reached == 0) HIP_TRY(c, hipMemsetAsync(st->d_stats, 0, B * (size_t)kSuffStats * sizeof(double), c->stream));
-    if (reached == 0 || (!d_marg && !with_traj && !st)) return 0;           // (an online batch before its first observes, or nothing asked for)
+    // a forecast before the first observes: rows of zeros; the predictive row 0 needs no row of the table and goes on
+    if (fc && !predictive && reached == 0 && with_traj) HIP_TRY(c, hipMemsetAsync(d_traj, 0, B * (size_t)(fc->horizon + 1) * (size_t)n_traj, c->stream));
+    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st)) return 0;   // (an online batch before its first observes, or nothing asked for)
     if (kept) rows = 0;
     if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
         // (earlier calls' copies and kernels may still read the buffers this replaces)
@@ -4532,12 +4541,13 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     for (size_t b = 0; b < B; ++b) {
         const BatchProblem& pr = bs->prob[b];
         const int L = pr.T, W = lg ? (int)std::min<uint64_t>(lg->lag + 1, (uint64_t)L) : L;
-        const int mfrom = lg && lg->from ? (int)lg->from[b] : 0;
+        const int mfrom = lg && lg->from ? (int)lg->from[b] : (fc && fc->from ? (int)fc->from[b] : 0);
         pd[b].T = L; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at; pd[b].trows = at_traj;
         pd[b].lo = L - W; pd[b].mfrom = mfrom; pd[b].cto = L;
         // the rows the pass owes: an online batch's new ones; a run batch's -- nothing is kept -- those this call reads
         if (kept) { pd[b].rows = (int64_t)b * bs->T; pd[b].store = 0; pd[b].cfrom = L; }
         else if (bs->online) pd[b].cfrom = (int)bs->counted[b];
+        else if (fc) pd[b].cfrom = predictive ? std::min(std::max(mfrom, 1) - 1, L) : std::max(L - 1, 0);
         else pd[b].cfrom = lg ? std::min(d_marg ? mfrom : L, with_traj ? L - W : L) : 0;
         at += bs->online ? (int64_t)bs->cap_T[b] : (int64_t)L;
         at_traj += W;
@@ -4571,6 +4581,26 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         HIP_TRY(c, hipGetLastError());
         bs->smooth_gy_count = gy;
         if (bs->online) for (size_t b = 0; b < B; ++b) bs->counted[b] = (uint32_t)bs->prob[b].T;
+    }
+    if (fc) {
+        BatchForecastArgs fa{};
+        fa.desc = a.desc; fa.mass = a.mass; fa.thr = a.thr; fa.seeds = a.seeds; fa.marg = d_marg; fa.traj = a.traj;
+        fa.draw_base = kForecastDrawBase + (draw_index << 24);
+        fa.k = a.k; fa.spp = a.spp; fa.thr_stride = a.thr_stride; fa.n_traj = (int)n_traj; fa.H = (int)fc->horizon; fa.rows = (int)marg_rows;
+        if (predictive) {
+            // (problem, step) a wavefront: the steps gridDim.y * kWaves apart where a problem owes more rows than the grid holds
+            int64_t owed = 0;
+            for (size_t b = 0; b < B; ++b) owed = std::max<int64_t>(owed, (int64_t)pd[b].T + 1 - (int64_t)pd[b].mfrom);
+            if (owed <= 0) return 0;
+            const unsigned gy = (unsigned)std::min<int64_t>((owed + kWaves - 1) / kWaves, kPredictiveGridMax);
+            hipLaunchKernelGGL(batch_predictive_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, fa);
+        } else {
+            const unsigned tiles = fa.traj ? (unsigned)((n_traj + kTile - 1) / kTile) : 0u;
+            if (hmm3) hipLaunchKernelGGL(batch_forecast_kernel<3>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), 0, c->stream, fa);
+            else hipLaunchKernelGGL(batch_forecast_kernel<8>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), 0, c->stream, fa);
+        }
+        HIP_TRY(c, hipGetLastError());
+        return 0;
     }
     if (lg && d_marg && items_top > 0) {
         // (problem, end step) a wavefront: the ends gridDim.y * kWaves apart where a problem has more than the grid holds
@@ -4748,6 +4778,121 @@ int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* c, const double* h_observes, s
     const BatchSmoothStats st{d_obs, d_stats};
     if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, &st)) return rc;
     HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- forecasts of a batch (csrc/batch_forecast.hpp) ---------------------------------------------------------------------------------
+// cpprob_hip_batch_forecast's arguments against the batch's state (batch_smooth_check first), then the totals against the capacities.
+static int batch_forecast_check(cpprob_hip_ctx* c, uint64_t horizon, uint64_t n_traj, uint64_t draw_index, bool with_marg, size_t n_doubles, bool with_traj,
+                                size_t n_entries, uint64_t& doubles, uint64_t& entries)
+{
+    uint64_t full_doubles = 0, full_entries = 0;
+    if (int rc = batch_smooth_check(c, n_traj, draw_index, false, 0, false, 0, full_doubles, full_entries)) return rc;
+    if (horizon == 0 || horizon >= (uint64_t)kForecastMaxH) return fail(c, CPPROB_HIP_EINVAL, "horizon must lie in 1 .. 2^24 - 1");
+    BatchState* bs = c->batch;
+    doubles = (uint64_t)bs->cfg.n_problems * horizon * (uint64_t)bs->K;
+    entries = (uint64_t)bs->cfg.n_problems * (horizon + 1) * n_traj;
+    if (with_marg && n_doubles < doubles) return fail(c, CPPROB_HIP_EINVAL, "the marginals buffer is too small: " + std::to_string(doubles) + " doubles (n_problems * horizon * stats_per_predict)");
+    if (with_traj && n_entries < entries) return fail(c, CPPROB_HIP_EINVAL, "the trajectories buffer is too small: " + std::to_string(entries) + " entries (n_problems * (horizon + 1) * n_traj)");
+    return 0;
+}
+
+// The device staging of a host call: the doubles (8-byte aligned) in front of the int8 entries.
+static int batch_forecast_stage(cpprob_hip_ctx* c, size_t doubles, size_t entries, double*& d_marg, int8_t*& d_traj)
+{
+    BatchState* bs = c->batch;
+    const size_t m_bytes = batch_round(doubles * sizeof(double)), need = m_bytes + entries;
+    if (need > bs->stage_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
+        bs->stage_cap = need;
+    }
+    d_marg = doubles ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
+    d_traj = entries ? reinterpret_cast<int8_t*>(bs->d_stage + m_bytes) : nullptr;
+    return 0;
+}
+
+int cpprob_hip_batch_forecast_device(cpprob_hip_ctx* c, uint64_t horizon, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles,
+                                     int8_t* d_traj, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_forecast_check(c, horizon, n_traj, draw_index, d_marginals != nullptr, n_doubles, d_traj != nullptr, n_entries, doubles, entries)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const BatchForecast fc{horizon, nullptr, 0};
+    return batch_smooth_enqueue(c, n_traj, draw_index, d_marginals, d_traj, nullptr, nullptr, &fc);
+}
+
+int cpprob_hip_batch_forecast(cpprob_hip_ctx* c, uint64_t horizon, uint64_t n_traj, uint64_t draw_index, double* h_marginals, size_t n_doubles,
+                              int32_t* h_traj, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_forecast_check(c, horizon, n_traj, draw_index, h_marginals != nullptr, n_doubles, h_traj != nullptr, n_entries, doubles, entries)) return rc;
+    const bool with_traj = h_traj && entries;
+    if (!h_marginals && !with_traj) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    double* d_marg = nullptr;
+    int8_t* d_traj = nullptr;
+    if (int rc = batch_forecast_stage(c, h_marginals ? (size_t)doubles : 0, with_traj ? (size_t)entries : 0, d_marg, d_traj)) return rc;
+    const BatchForecast fc{horizon, nullptr, 0};
+    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj, nullptr, nullptr, &fc)) return rc;
+    std::vector<int8_t> v(with_traj ? (size_t)entries : 0);
+    if (with_traj) HIP_TRY(c, hipMemcpyAsync(v.data(), d_traj, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
+    if (h_marginals) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
+    return 0;
+}
+
+// cpprob_hip_batch_predictive's arguments against the batch's state (batch_smooth_check first).
+static int batch_predictive_check(cpprob_hip_ctx* c, const uint32_t* h_from, uint64_t n_rows, const double* rows, size_t n_doubles, uint64_t& doubles)
+{
+    uint64_t full_doubles = 0, full_entries = 0;
+    if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, full_doubles, full_entries)) return rc;
+    if (!rows) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    for (size_t b = 0; b < bs->prob.size(); ++b) {
+        const uint64_t L = (uint64_t)bs->prob[b].T, from = h_from ? h_from[b] : 0;
+        if (from > L + 1) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": from = " + std::to_string(from) + " lies past its " + std::to_string(L + 1) + " predictive rows");
+        if (L + 1 - from > n_rows)
+            return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": " + std::to_string(L + 1 - from) + " rows asked for, n_rows = " + std::to_string(n_rows));
+    }
+    doubles = (uint64_t)bs->cfg.n_problems * n_rows * (uint64_t)bs->K;
+    if (n_doubles < doubles) return fail(c, CPPROB_HIP_EINVAL, "the rows buffer is too small: " + std::to_string(doubles) + " doubles (n_problems * n_rows * stats_per_predict)");
+    return 0;
+}
+
+int cpprob_hip_batch_predictive_device(cpprob_hip_ctx* c, const uint32_t* h_from, uint64_t n_rows, double* d_rows, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0;
+    if (int rc = batch_predictive_check(c, h_from, n_rows, d_rows, n_doubles, doubles)) return rc;
+    if (doubles == 0) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const BatchForecast fc{0, h_from, n_rows};
+    return batch_smooth_enqueue(c, 0, 0, d_rows, nullptr, nullptr, nullptr, &fc);
+}
+
+int cpprob_hip_batch_predictive(cpprob_hip_ctx* c, const uint32_t* h_from, uint64_t n_rows, double* h_rows, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0;
+    if (int rc = batch_predictive_check(c, h_from, n_rows, h_rows, n_doubles, doubles)) return rc;
+    if (doubles == 0) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    double* d_rows = nullptr;
+    int8_t* d_none = nullptr;
+    if (int rc = batch_forecast_stage(c, (size_t)doubles, 0, d_rows, d_none)) return rc;
+    const BatchForecast fc{0, h_from, n_rows};
+    if (int rc = batch_smooth_enqueue(c, 0, 0, d_rows, nullptr, nullptr, nullptr, &fc)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(h_rows, d_rows, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }

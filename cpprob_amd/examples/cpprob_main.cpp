@@ -85,6 +85,21 @@ void print_json(const cpprob::gpu::Result& r)
         }
     }
     std::cout << "]";
+    if (!r.forecast.empty()) {                                   // --forecast: row h - 1 the law of the state h steps past the last observe
+        std::cout << ", \"forecast\": [";
+        for (std::size_t h = 0; h < r.forecast.size(); ++h) {
+            std::cout << (h ? ", [" : "[");
+            for (std::size_t s = 0; s < r.forecast[h].size(); ++s) std::cout << (s ? ", " : "") << r.forecast[h][s];
+            std::cout << "]";
+        }
+        std::cout << "], \"futures\": [";
+        for (std::size_t j = 0; j < r.forecast_trajectories.size(); ++j) {
+            std::cout << (j ? ", [" : "[");
+            for (std::size_t h = 0; h < r.forecast_trajectories[j].size(); ++h) std::cout << (h ? ", " : "") << r.forecast_trajectories[j][h];
+            std::cout << "]";
+        }
+        std::cout << "]";
+    }
     if (r.n_replicates > 1) {
         std::cout << ", \"replicates\": " << r.n_replicates << ", \"log_evidence_mean\": " << r.log_evidence_mean << ", \"log_evidence_sd\": " << r.log_evidence_sd
                   << ", \"replicates_seconds\": " << r.replicates_seconds << ", \"predict_mean\": [";
@@ -94,6 +109,25 @@ void print_json(const cpprob::gpu::Result& r)
         std::cout << "]";
     }
     std::cout << "}" << std::endl;
+}
+
+// --forecast H [--forecast_trajectories M], after the statistics of the batch: problem b's rows "forecast b h p_0 .. p_{k-1}", the law
+// of the state h = 1 .. H steps past its last observe, then "future b j x_0 .. x_H", simulated future j from the present state x_0 on
+// (--json carries both inside the problem's object instead)
+void print_forecasts(const std::vector<cpprob::gpu::Result>& res)
+{
+    for (std::size_t b = 0; b < res.size(); ++b) {
+        for (std::size_t h = 0; h < res[b].forecast.size(); ++h) {
+            std::cout << "forecast " << b << " " << h + 1;
+            for (double v : res[b].forecast[h]) std::cout << " " << v;
+            std::cout << std::endl;
+        }
+        for (std::size_t j = 0; j < res[b].forecast_trajectories.size(); ++j) {
+            std::cout << "future " << b << " " << j;
+            for (std::int32_t x : res[b].forecast_trajectories[j]) std::cout << " " << x;
+            std::cout << std::endl;
+        }
+    }
 }
 
 // --batch_observes_file F: one observation sequence a line, all run as ONE batch (cpprob::gpu::inference_batch, smc, built-in HMMs);
@@ -123,6 +157,7 @@ int execute_batch(const F& model, const Args& a)
             for (double v : p.probabilities) std::cout << " " << v;
         std::cout << std::endl;
     }
+    if (!a.json) print_forecasts(res);
     cpprob::gpu::release_device_resources();
     return EXIT_SUCCESS;
 }
@@ -189,6 +224,7 @@ int execute_batch_tables(const Args& a)
             for (double v : p.probabilities) std::cout << " " << v;
         std::cout << std::endl;
     }
+    if (!a.json) print_forecasts(res);
     for (const cpprob::gpu::HmmTable& t : fitted) {
         std::cout << "[";
         for (std::size_t s = 0; s < t.means.size(); ++s) std::cout << (s ? " " : "") << t.means[s];
@@ -257,6 +293,8 @@ int main(int argc, char** argv)
         else if (f == "--batch_dump") a.batch_dump = true;                         // the batch modes: problem b's traces as <generated_file>_smc_<b>.int / .ids
         else if (f == "--backward_smoothing") opt.backward_smoothing = true;      // the batch modes: statistics from the backward smoother (cpprob_hip_batch_smooth)
         else if (f == "--smoothing_lag") opt.smoothing_lag = std::stol(next());    // the batch modes: fixed-lag marginals (cpprob_hip_batch_smooth_lag)
+        else if (f == "--forecast") opt.forecast_horizon = std::stoull(next());   // the batch modes: the state's laws this many steps ahead (cpprob_hip_batch_forecast)
+        else if (f == "--forecast_trajectories") opt.forecast_trajectories = std::stoull(next());   // ... and this many simulated futures a problem
         else if (f == "--backward_trajectories") opt.backward_trajectories = std::stoull(next());   // ... and --batch_dump writes this many backward-simulated trajectories
         else if (f == "--dump_max_particles") opt.dump_max_particles = std::stoull(next());   // the posterior files hold the first M traces only (0: all)
         else if (f == "--generated_file") a.generated_file = next();
@@ -285,6 +323,10 @@ int main(int argc, char** argv)
         else { std::cerr << "unknown option " << f << std::endl; return EXIT_FAILURE; }
     }
     if (a.sis == a.smc) { std::cerr << "exactly one of --sis / --smc has to be set" << std::endl; return EXIT_FAILURE; }
+    if ((opt.forecast_horizon || opt.forecast_trajectories) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
+        std::cerr << "--forecast serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;
+        return EXIT_FAILURE;
+    }
     try {
         if (!a.batch_tables_file.empty()) return execute_batch_tables(a);     // (the model is the table HMM: --model is not read)
         if (a.model == "gaussian_unknown_mean") return execute(models::gaussian_unknown_mean<double>, a);     // main.cpp:123-130

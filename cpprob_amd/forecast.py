@@ -1,0 +1,42 @@
+"""What to do with a batch's forecasts on the host (Engine.batch_forecast, Engine.batch_predictive): the forecast of the observe
+itself and the one-step predictive likelihood of a stream, under the emission y | x = s ~ N(means[s], 1) of the HMM models.  Pure
+numpy: the rows come from the device, the emission is restated here."""
+import numpy as np
+
+LOG_SQRT_2PI = 0.5 * np.log(2.0 * np.pi)
+
+
+def _means(means, k_max):
+    mu = np.asarray(means, np.float64).reshape(-1)
+    if mu.size == 0 or mu.size > k_max:
+        raise ValueError("%d means for rows of %d states" % (mu.size, k_max))
+    return mu
+
+
+def observation_forecast(marginals, means):
+    """(mean, variance) of y_{L-1+h} for every row of `marginals` ([..., spp], a law over the states in its last axis; the states
+    past len(means) carry no mass): mean = sum_s f[s] mu[s], variance = 1 + sum_s f[s] mu[s]^2 - mean^2."""
+    f = np.asarray(marginals, np.float64)
+    if f.ndim < 1:
+        raise ValueError("marginals must have the states in their last axis")
+    mu = _means(means, f.shape[-1])
+    fk = f[..., :mu.size]
+    mean = fk @ mu
+    return mean, 1.0 + fk @ (mu * mu) - mean * mean
+
+
+def predictive_log_likelihood(rows, means, observes):
+    """log p(y_t | y_0 .. y_{t-1}) = log sum_s r_t[s] N(y_t; mu[s], 1) for every observe, by log-sum-exp: rows [T', spp] with
+    T' >= len(observes) (row t the predictive law of step t, Engine.batch_predictive's rows of one problem; the rows past the observes
+    -- the forecast of the step to come -- are not read), observes [T].  Their sum is the log-evidence of the observes under the
+    rows."""
+    r = np.asarray(rows, np.float64)
+    y = np.asarray(observes, np.float64).reshape(-1)
+    if r.ndim != 2 or r.shape[0] < y.size:
+        raise ValueError("rows must be [T', spp] with a row for every observe")
+    mu = _means(means, r.shape[1])
+    r = r[:y.size, :mu.size]
+    with np.errstate(divide="ignore"):
+        a = np.log(r) - 0.5 * (y[:, None] - mu[None, :]) ** 2 - LOG_SQRT_2PI
+    top = a.max(axis=1) if y.size else np.zeros(0)
+    return top + np.log(np.exp(a - top[:, None]).sum(axis=1))

@@ -616,6 +616,37 @@ void dump_batch_backward(Context& ctx, const std::string& prefix, const std::vec
     }
 }
 
+// ---- forecasts of a batch (cpprob_hip_batch_forecast): Options::forecast_horizon, ::forecast_trajectories -----------------------------
+// What the C ABI would refuse, refused before a batch is begun.  stored: the batch keeps its history or its masses.
+inline void check_forecast_options(const std::string& who, std::size_t H, std::size_t M, bool stored)
+{
+    if (M && !H) throw std::runtime_error(who + ": options().forecast_trajectories simulates the steps of a forecast: set options().forecast_horizon");
+    if (!H) return;
+    if (H >= (std::size_t(1) << 24)) throw std::runtime_error(who + ": options().forecast_horizon must lie below 2^24");
+    if (M > (std::size_t(1) << 20)) throw std::runtime_error(who + ": options().forecast_trajectories must lie in 0 .. 2^20");
+    if (!stored)
+        throw std::runtime_error(who + ": a forecast reads the smoother's masses: a filtering-only run (options().keep_history = false) keeps none without options().keep_masses");
+}
+
+// The forecast of the batch last run or advanced on ctx into its results: H rows of the first k of K states, M futures a problem.
+inline void batch_forecast_results(Context& ctx, std::size_t H, std::size_t M, std::size_t K, std::size_t k, std::vector<Result>& out)
+{
+    if (!H) return;
+    const std::size_t B = out.size();
+    std::vector<double> marg(B * H * K);
+    std::vector<std::int32_t> traj(B * (H + 1) * M);
+    ctx.check(cpprob_hip_batch_forecast(ctx.get(), H, M, 0, marg.data(), marg.size(), M ? traj.data() : nullptr, traj.size()), "cpprob_hip_batch_forecast");
+    for (std::size_t b = 0; b < B; ++b) {
+        Result& r = out[b];
+        r.forecast.resize(H);
+        for (std::size_t h = 0; h < H; ++h)
+            r.forecast[h].assign(marg.begin() + static_cast<std::ptrdiff_t>((b * H + h) * K), marg.begin() + static_cast<std::ptrdiff_t>((b * H + h) * K + k));
+        r.forecast_trajectories.assign(M, std::vector<std::int32_t>(H + 1));
+        for (std::size_t h = 0; h <= H; ++h)
+            for (std::size_t j = 0; j < M; ++j) r.forecast_trajectories[j][h] = traj[(b * (H + 1) + h) * M + j];
+    }
+}
+
 // The trace structure of a table-HMM problem of T observes: one int predict per observe, "state[t]".
 inline detail::TraceStructure hmm_table_structure(std::size_t T)
 {
@@ -663,6 +694,7 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
         throw std::runtime_error("cpprob::gpu::inference_batch: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     if (!opt.keep_history && !masses && opt.smoothing_lag >= 0)
         throw std::runtime_error("cpprob::gpu::inference_batch: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
+    check_forecast_options("cpprob::gpu::inference_batch", opt.forecast_horizon, opt.forecast_trajectories, opt.keep_history || masses);
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -691,8 +723,9 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     else if (!opt.batch_dump_file.empty())
         dump_batch_posterior(ctx, opt.batch_dump_file, std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(T)), std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(n)),
                              opt.dump_max_particles, [&st](std::size_t) -> const detail::TraceStructure& { return st; });
-    lease.done();
     std::vector<Result> out(B);
+    batch_forecast_results(ctx, opt.forecast_horizon, opt.forecast_trajectories, K, K, out);
+    lease.done();
     for (std::size_t b = 0; b < B; ++b) {
         Result& r = out[b];
         const cpprob_hip_summary& s = sums[b];
@@ -751,6 +784,7 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
         throw std::runtime_error(who + ": backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     if (!opt.keep_history && !masses && opt.smoothing_lag >= 0)
         throw std::runtime_error(who + ": fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
+    check_forecast_options(who, opt.forecast_horizon, opt.forecast_trajectories, opt.keep_history || masses);
     return pk;
 }
 
@@ -800,6 +834,7 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
         }
         r.step_ess.assign(ess.begin() + b * T_max, ess.begin() + b * T_max + T[b]);
     }
+    batch_forecast_results(ctx, opt.forecast_horizon, opt.forecast_trajectories, K, k, out);
     return out;
 }
 
@@ -875,6 +910,8 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // advance whatever its readout.  An advance asks the device for the steps from max(0, L_before - lag) on -- those whose estimate the
 // new observes can still change -- and the object keeps the final rows on the host: the work of an advance is that of its new steps,
 // and the predicts depend on the lengths reached alone, never on how the observes were cut into advances.
+// options().forecast_horizon = H > 0: every advance's results carry the forecast from the lengths reached (Result::forecast, and
+// Result::forecast_trajectories for options().forecast_trajectories > 0); a problem without observes has rows of zeros.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -884,6 +921,7 @@ public:
         : B_(seeds.size()), k_(tables.empty() ? 0 : tables[0].means.size()), keep_(options().keep_history), masses_(!options().keep_history && options().keep_masses), lease_(options().device)
     {
         if (B_ == 0) throw std::runtime_error("cpprob::gpu::HmmTableStream: no problems (one seed per problem)");
+        check_forecast_options("cpprob::gpu::HmmTableStream", forecast_H_, forecast_M_, keep_ || masses_);
         if (!keep_ && !masses_ && backward_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         if (!keep_ && !masses_ && lag_ >= 0)
@@ -979,6 +1017,7 @@ public:
             }
             r.step_ess.assign(ess.begin() + b * T_max_, ess.begin() + b * T_max_ + L[b]);
         }
+        batch_forecast_results(ctx, forecast_H_, forecast_M_, K, k_, out);      // (after every advance, whatever its readout)
         return out;
     }
 
@@ -999,6 +1038,7 @@ private:
     bool backward_ = options().backward_smoothing;
     std::size_t backward_traj_ = options().backward_trajectories;
     long lag_ = options().smoothing_lag;
+    std::size_t forecast_H_ = options().forecast_horizon, forecast_M_ = options().forecast_trajectories;
     std::vector<double> lagged_;               // smoothing_lag: [B][T_max][8], the fixed-lag rows so far (rows below L - lag are final)
     std::vector<std::size_t> L_prev_;          // ... and the lengths they stand for
     std::size_t dump_max_ = options().dump_max_particles;

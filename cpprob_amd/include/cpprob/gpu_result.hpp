@@ -39,6 +39,10 @@ struct Options {
                                                       // P(x_t | y_0 .. y_min(t + lag, L - 1)) (cpprob_hip_batch_smooth_lag; it takes precedence over
                                                       // backward_smoothing).  HmmTableStream asks for the steps not yet final only: an advance costs its
                                                       // new steps, whatever length the stream has reached.  Negative: off
+    std::size_t forecast_horizon = 0;                 // batched runs (keep_history, or keep_masses): not 0 = every result carries Result::forecast, the laws of
+                                                      // the state 1 .. forecast_horizon steps past the last observe, P(x_{L-1+h} | y_0 .. y_{L-1})
+                                                      // (cpprob_hip_batch_forecast); HmmTableStream: after every advance.  0: off
+    std::size_t forecast_trajectories = 0;            // ... and, not 0, Result::forecast_trajectories: this many simulated futures (draw_index 0)
     bool markov_probe = true;                         // smc, unchanged-model path: test on the host whether a step depends on more than the last few
                                                       // sampled values; a model that does not is replayed from that window only (O(T) instead of O(T^2))
     bool markov_crosscheck = true;                    // ... and certify the probe's window on the device before using it: a pilot population under windowed
@@ -93,6 +97,8 @@ struct Result {
     double run_seconds = 0;                   // device work of the run (launch to synchronise), excluding allocation and dumps
     std::vector<PredictStats> predicts;       // real hits first (in trace order), then int hits
     std::vector<double> step_ess;             // smc: ESS after each observe
+    std::vector<std::vector<double>> forecast;                      // Options::forecast_horizon: [h - 1][s] = P(x_{L-1+h} = s | y_0 .. y_{L-1}), h = 1 .. horizon
+    std::vector<std::vector<std::int32_t>> forecast_trajectories;   // Options::forecast_trajectories: [j][h], future j's states; h = 0 is the present state
     // Options::replicates > 1: replicate 0 is what the fields above (and the dump) describe; across replicates:
     int n_replicates = 1;
     double log_evidence_mean = 0, log_evidence_sd = 0;        // log of the mean evidence (unbiased in Z); sd of the log estimates

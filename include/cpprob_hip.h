@@ -490,6 +490,45 @@ int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* ctx, const double* h_observes,
 /* The same between device buffers, enqueued on the context's stream after the run / advance, no host synchronisation. */
 int cpprob_hip_batch_smooth_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
 
+/* Forecasts of a batch (csrc/batch_forecast.hpp): what lies ahead of the last observe, from the smoother's m table and the transition
+ * law the device itself draws from.  Per problem b (L_b the length reached, k its states, m_t its rows of the m table, P[s][s'] the
+ * integer transition masses of cpprob_hip_batch_smooth):
+ *   p[s][s']           = double(P[s][s']) * 2^-32 (exact)
+ *   push(f)[s']        = sum over s = 0..k-1, in that order, of f[s] * p[s][s'] (every product one rounded operation, nothing
+ *                      contracted; the sum from 0.0, terms with f[s] = 0 left out)
+ *   forecast marginals f_0 = the last row of cpprob_hip_batch_smooth's marginals (the normalised filtering masses of step L_b - 1, the
+ *                      same device function); f_h = push(f_{h-1}) = P(x_{L_b-1+h} | y_0 .. y_{L_b-1}), h = 1 .. horizon
+ *   simulated futures  trajectory j: row 0, the present state, drawn from m_{L_b-1} by the backward simulation's start rule with the
+ *                      53-bit uniform of word pair j & 1 of Philox block (seed_b, group j >> 1, ordinal 2^42 + (draw_index << 24));
+ *                      row h >= 1: x_h = #{i < k-1 : w >= c[x_{h-1}][i]}, c the threshold words and w the 32-bit word 2 (j & 1) of
+ *                      block (seed_b, j >> 1, 2^42 + (draw_index << 24) + h): the forward draw's own statement, so the law is P
+ * Marginals: [B][horizon][stats_per_predict] doubles, row h - 1 is f_h, states >= k zero.  Trajectories: [B][horizon + 1][n_traj]
+ * (uniform, not packed: every problem has the same horizon).  A problem of length 0 has rows of zeros in both.  Either output may be
+ * NULL; n_traj may be 0 when the trajectories are NULL.  Needs the particle store (keep_history = 1) or CPPROB_HIP_BATCH_KEEP_MASSES,
+ * and a run or advance before it (else CPPROB_HIP_ESTATE).  CPPROB_HIP_EINVAL (nothing written): horizon 0 or >= 2^24,
+ * draw_index >= 2^16, n_traj > 2^20, a capacity too small, a problem longer than 2^24.
+ * Cost: horizon k^2 and horizon n_traj, whatever length the stream has reached.  The m table is the smoothing calls': a
+ * CPPROB_HIP_BATCH_KEEP_MASSES batch reads the rows its run kept, an online batch with history counts the rows that arrived since
+ * the last call that counted (none counts a row twice), a run batch counts row L_b - 1.  The call changes nothing any other entry
+ * point returns.  Host copies: h_traj int32.  Stages on the device and widens.  Synchronises. */
+int cpprob_hip_batch_forecast(cpprob_hip_ctx* ctx, uint64_t horizon, uint64_t n_traj, uint64_t draw_index, double* h_marginals, size_t n_doubles,
+                              int32_t* h_traj, size_t n_entries);
+/* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation: d_traj int8. */
+int cpprob_hip_batch_forecast_device(cpprob_hip_ctx* ctx, uint64_t horizon, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles,
+                                     int8_t* d_traj, size_t n_entries);
+/* One-step predictive rows: the law every observe was predicted from, r_t = P(x_t | y_0 .. y_{t-1}) for t = 0 .. L_b.
+ *   r_0[s] = 1.0 / double(k) for s < k (the uniform initial state);  r_t = push(normalised filtering masses of step t - 1), t >= 1
+ * r_{L_b} is row h = 1 of cpprob_hip_batch_forecast bit for bit; r_t reads row t - 1 of the m table alone, so it is final when it is
+ * first available and the same however an online batch was cut into advances.
+ * Output: [B][n_rows][stats_per_predict] doubles; row r of problem b is r_{from_b + r} for from_b + r <= L_b, every other row and the
+ * states >= k are zero.  h_from: [B] (a host array, read before the call returns), or NULL for all 0.  n_rows >= max over b of
+ * (L_b + 1 - from_b).  State and cost as above (a run batch counts rows max(from_b, 1) - 1 .. L_b - 1).  CPPROB_HIP_EINVAL (nothing
+ * written; the message names the problem where one is at fault): from_b > L_b + 1, n_rows too small, a capacity too small, a NULL
+ * output.  Synchronises. */
+int cpprob_hip_batch_predictive(cpprob_hip_ctx* ctx, const uint32_t* h_from, uint64_t n_rows, double* h_rows, size_t n_doubles);
+/* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation. */
+int cpprob_hip_batch_predictive_device(cpprob_hip_ctx* ctx, const uint32_t* h_from, uint64_t n_rows, double* d_rows, size_t n_doubles);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
