@@ -14,5 +14,7 @@ from . import em  # noqa: F401
 from .em import hmm_table_em, m_step  # noqa: F401
 from . import forecast  # noqa: F401
 from .forecast import observation_forecast, predictive_log_likelihood  # noqa: F401
+from . import decode  # noqa: F401
+from .decode import hmm_table_decode  # noqa: F401
 
 __version__ = "0.1.0"

@@ -45,6 +45,8 @@ SYMBOLS = [
     "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device", "cpprob_hip_batch_smooth_grid",
     "cpprob_hip_batch_smooth_stats", "cpprob_hip_batch_smooth_stats_device",
     "cpprob_hip_batch_forecast", "cpprob_hip_batch_forecast_device", "cpprob_hip_batch_predictive", "cpprob_hip_batch_predictive_device",
+    "cpprob_hip_batch_decode", "cpprob_hip_batch_decode_device", "cpprob_hip_batch_decode_lag", "cpprob_hip_batch_decode_lag_device",
+    "cpprob_hip_batch_decode_logp",
 ]
 
 
@@ -183,6 +185,7 @@ def batch_smooth_layout(T, n_traj):
 
 
 FORECAST_MAX_HORIZON, FORECAST_MAX_TRAJ, FORECAST_MAX_DRAWS = 1 << 24, 1 << 20, 1 << 16      # cpprob_hip_batch_forecast: horizon <, n_traj <=, draw_index <
+DECODE_MAX_LAG = 1 << 24                      # cpprob_hip_batch_decode_lag: lag <=
 STATS_PER_PROBLEM = 88                        # doubles a problem of cpprob_hip_batch_smooth_stats: xi[8][8], occ[8], occ_y[8], occ_yy[8]
 
 
@@ -345,6 +348,11 @@ def load_library(path=None):
         "cpprob_hip_batch_forecast_device": (C.c_int, [vp, u64, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_predictive": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, vp, sz]),
         "cpprob_hip_batch_predictive_device": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, vp, sz]),
+        "cpprob_hip_batch_decode": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_decode_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_decode_lag": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_decode_lag_device": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_decode_logp": (C.c_int, [vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -828,6 +836,66 @@ class Engine:
         h_from, _ = self._batch_predictive_shapes(from_steps)
         self._chk(self.L.cpprob_hip_batch_predictive_device(self.h, None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), int(rows.shape[1]),
                                                             _dptr(rows), rows.numel()))
+
+    def batch_decode(self):
+        """The most probable state path of every problem given its observes (cpprob_hip_batch_decode): (a list of int32 [L_b] arrays,
+        scores float64 [B]) -- dynamic programming over the states the particles occupy, under the transition law the device draws
+        from; the score is the log joint density of the path and the observes.  A problem of length 0 has an empty path and score 0."""
+        h_T, _ = self._batch_problem_shapes()
+        first = batch_smooth_layout(h_T, 1)
+        flat = np.zeros(int(first[-1]), np.int32)
+        score = np.zeros(self.batch_B)
+        self._chk(self.L.cpprob_hip_batch_decode(self.h, flat.ctypes.data if flat.size else None, flat.size, score.ctypes.data, score.size))
+        return [flat[int(first[b]):int(first[b + 1])] for b in range(self.batch_B)], score
+
+    def batch_decode_device(self, path_i8=None, score=None):
+        """The same left in device tensors, enqueued behind the run / advance without a host synchronisation: path_i8 torch int8
+        packed as batch_smooth_layout(T, 1) says or None, score torch float64 [B] or None (their numel() are the capacities)."""
+        self._chk(self.L.cpprob_hip_batch_decode_device(self.h, _dptr(path_i8), 0 if path_i8 is None else path_i8.numel(), _dptr(score), 0 if score is None else score.numel()))
+
+    def _batch_decode_lag_shapes(self, lag, from_steps):
+        """(from uint32 [B] or None, n_rows) of a fixed-lag decode on the batch last begun / advanced; the ranges the library refuses
+        are checked before anything is allocated."""
+        if not 0 <= int(lag) <= DECODE_MAX_LAG:
+            raise ValueError("lag must lie in 0 .. 2^24")
+        if from_steps is not None:
+            f = np.asarray(from_steps)
+            if f.size and (f.min() < 0 or f.max() >= 1 << 32):
+                raise ValueError("from_steps must be steps, 0 .. 2^32 - 1")
+        _, h_from, _, n_rows = self._batch_lag_shapes(lag, from_steps)
+        return h_from, n_rows
+
+    def batch_decode_lag(self, lag, from_steps=None):
+        """Fixed-lag decoding of every problem (cpprob_hip_batch_decode_lag): (states int32 [B, n_rows], scores float64 [B]).  Row r
+        of problem b is X_t at t = from_b + r, the state at t of the most probable path of steps 0 .. min(t + lag, L_b - 1) -- final
+        once lag more observes have arrived --, and -1 past its length; from_steps None: every problem from step 0;
+        n_rows = max(L_b - from_b).  The rows with t + lag >= L_b - 1 are batch_decode's."""
+        h_from, n_rows = self._batch_decode_lag_shapes(lag, from_steps)
+        states = np.full((self.batch_B, n_rows), -1, np.int32)
+        score = np.zeros(self.batch_B)
+        self._chk(self.L.cpprob_hip_batch_decode_lag(self.h, int(lag), None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows,
+                                                     states.ctypes.data if states.size else None, states.size, score.ctypes.data, score.size))
+        return states, score
+
+    def batch_decode_lag_device(self, lag, states_i8=None, score=None, from_steps=None):
+        """The same left in device tensors, enqueued behind the run / advance without a host synchronisation: states_i8 torch int8
+        [B, n_rows] (n_rows = its second dimension) or None, score torch float64 [B] or None."""
+        h_from, n_rows = self._batch_decode_lag_shapes(lag, from_steps)
+        if states_i8 is not None:
+            if states_i8.dim() != 2:
+                raise ValueError("states_i8 must be [B, n_rows]")
+            n_rows = int(states_i8.shape[1])
+        self._chk(self.L.cpprob_hip_batch_decode_lag_device(self.h, int(lag), None if h_from is None else h_from.ctypes.data_as(C.POINTER(C.c_uint32)), n_rows,
+                                                            _dptr(states_i8), 0 if states_i8 is None else states_i8.numel(), _dptr(score), 0 if score is None else score.numel()))
+
+    def batch_decode_logp(self, b):
+        """(lp float64 [8, 8], lp0) of problem b (cpprob_hip_batch_decode_logp): lp[s, s'] = log P(s -> s') under the transition law the
+        device realises (-inf where it is 0 or outside the k states), lp0 = log(1 / k): the doubles the decode kernels are given.
+        Host only."""
+        lp = np.zeros(64)
+        lp0 = C.c_double(0.0)
+        self._chk(self.L.cpprob_hip_batch_decode_logp(self.h, int(b), lp.ctypes.data_as(C.POINTER(C.c_double)), C.byref(lp0)))
+        return lp.reshape(8, 8), float(lp0.value)
 
     def batch_smooth_grid(self):
         """(gridDim.y of the counting launch, gridDim.y of the fixed-lag launch) of this context's last smoothing call

@@ -24,6 +24,7 @@
 #include "batch_smooth.hpp"
 #include "batch_suffstats.hpp"
 #include "batch_forecast.hpp"
+#include "batch_decode.hpp"
 
 using namespace cph;
 
@@ -1084,6 +1085,16 @@ struct BatchState {
     hipEvent_t sdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_smooth = 0;
     unsigned smooth_gy_count = 0, smooth_gy_lag = 0;        // gridDim.y of the last smoothing call's counting and lag launches (0: none)
+    // decoding (cpprob_hip_batch_decode*; csrc/batch_decode.hpp): the step words (addressed as the m table's rows: an online batch's by
+    // capacity, kept), the v rows [B][8] and the log tables ([tables][64], computed on the host at the first call after a begin and
+    // uploaded once), allocations of the context's own; decoded: [B], online batch: its words [0, decoded_b) and its v row are valid
+    // (any begin: none)
+    uint32_t* d_words = nullptr; size_t words_cap = 0;
+    double* d_v = nullptr; size_t v_cap = 0;
+    double* d_lp = nullptr; size_t lp_cap = 0;
+    std::vector<double> h_lp; double lp0 = 0.0;
+    bool lp_ready = false, lp_sent = false;
+    std::vector<uint32_t> decoded;
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -1098,6 +1109,7 @@ void batch_free(cpprob_hip_ctx* c)
     if (c->batch->pin_pdesc) (void)hipHostFree(c->batch->pin_pdesc);
     for (hipEvent_t e : c->batch->pdesc_done) if (e) (void)hipEventDestroy(e);
     dfree(c->batch->d_mass); dfree(c->batch->d_sdesc);
+    dfree(c->batch->d_words); dfree(c->batch->d_v); dfree(c->batch->d_lp);
     if (c->batch->pin_sdesc) (void)hipHostFree(c->batch->pin_sdesc);
     for (hipEvent_t e : c->batch->sdesc_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
@@ -1166,6 +1178,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->begun = false; bs->ran = false;
     const uint64_t B = cfg->n_problems;
     bs->counted.assign(B, 0);
+    bs->decoded.assign(B, 0); bs->lp_ready = false; bs->lp_sent = false;
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3, described = h_T != nullptr, own = h_means != nullptr;
     const int spp = hmm3 ? 3 : 8;
     const uint64_t tables = described ? B : 1;
@@ -4485,6 +4498,10 @@ struct BatchSmoothStats { const double* d_obs; double* d_stats; };
 // A forecast call's own (cpprob_hip_batch_forecast: horizon > 0; cpprob_hip_batch_predictive: horizon = 0, the first rows wanted and
 // the rows a problem of the output).
 struct BatchForecast { uint64_t horizon; const uint32_t* from; uint64_t n_rows; };
+// A decode call's own (cpprob_hip_batch_decode: full; cpprob_hip_batch_decode_lag: the lag, the first rows wanted and the rows a
+// problem of the output), and its outputs on the device (either may be nullptr).
+struct BatchDecode { bool full; uint64_t lag; const uint32_t* from; uint64_t n_rows; double* d_score; int8_t* d_path; };
+static int batch_decode_prepare(cpprob_hip_ctx* c, size_t word_rows);
 
 // Enqueues the descriptors' copy, the counting pass and the smoothing pass on the context's stream; waits for nothing but the pinned
 // slot it writes (the copy that read it kOnlineSlots calls ago) and, where a buffer of its own has to grow, for the calls before it.
@@ -4492,8 +4509,10 @@ struct BatchForecast { uint64_t horizon; const uint32_t* from; uint64_t n_rows; 
 // st: the smoothing pass is batch_smooth_stats_kernel (csrc/batch_suffstats.hpp) and nothing else is written.
 // fc: the pass after the counting is batch_forecast_kernel or batch_predictive_kernel (csrc/batch_forecast.hpp); a run batch counts
 // row L - 1 (the forecast) or rows max(from_b, 1) - 1 .. L - 1 (the predictive rows) only.
+// dc: the passes after the counting are batch_decode_forward_kernel and batch_decode_trace_kernel (csrc/batch_decode.hpp); an online
+// batch's words are kept as its m table is: the forward pass walks steps [decoded_b, L_b) and moves that watermark.
 static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr,
-                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr)
+                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr, const BatchDecode* dc = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
@@ -4510,7 +4529,11 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     if (st && reached == 0) HIP_TRY(c, hipMemsetAsync(st->d_stats, 0, B * (size_t)kSuffStats * sizeof(double), c->stream));
     // a forecast before the first observes: rows of zeros; the predictive row 0 needs no row of the table and goes on
     if (fc && !predictive && reached == 0 && with_traj) HIP_TRY(c, hipMemsetAsync(d_traj, 0, B * (size_t)(fc->horizon + 1) * (size_t)n_traj, c->stream));
-    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st)) return 0;   // (an online batch before its first observes, or nothing asked for)
+    // a decode: a problem of length 0 has score 0; the fixed-lag rows no step owns are -1 (0 is a state)
+    if (dc && dc->d_score) HIP_TRY(c, hipMemsetAsync(dc->d_score, 0, B * sizeof(double), c->stream));
+    if (dc && !dc->full && dc->d_path && dc->n_rows) HIP_TRY(c, hipMemsetAsync(dc->d_path, 0xff, B * (size_t)dc->n_rows, c->stream));
+    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st && !dc)) return 0;   // (an online batch before its first observes, or nothing asked for)
+    const size_t word_rows = kept ? B * (size_t)bs->T : rows;
     if (kept) rows = 0;
     if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
         // (earlier calls' copies and kernels may still read the buffers this replaces)
@@ -4530,6 +4553,7 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
             bs->mass_rows = rows;
         }
     }
+    if (dc) { if (int rc = batch_decode_prepare(c, word_rows)) return rc; }
     const int slot = (int)(bs->n_smooth % BatchState::kOnlineSlots);
     if (bs->n_smooth >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->sdesc_done[slot]));
     char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap;
@@ -4541,9 +4565,10 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     for (size_t b = 0; b < B; ++b) {
         const BatchProblem& pr = bs->prob[b];
         const int L = pr.T, W = lg ? (int)std::min<uint64_t>(lg->lag + 1, (uint64_t)L) : L;
-        const int mfrom = lg && lg->from ? (int)lg->from[b] : (fc && fc->from ? (int)fc->from[b] : 0);
+        const int mfrom = lg && lg->from ? (int)lg->from[b] : (fc && fc->from ? (int)fc->from[b] : (dc && dc->from ? (int)dc->from[b] : 0));
         pd[b].T = L; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at; pd[b].trows = at_traj;
         pd[b].lo = L - W; pd[b].mfrom = mfrom; pd[b].cto = L;
+        if (dc) pd[b].lo = bs->online ? (int)std::min<uint32_t>(bs->decoded[b], (uint32_t)L) : 0;   // the forward pass's first step
         // the rows the pass owes: an online batch's new ones; a run batch's -- nothing is kept -- those this call reads
         if (kept) { pd[b].rows = (int64_t)b * bs->T; pd[b].store = 0; pd[b].cfrom = L; }
         else if (bs->online) pd[b].cfrom = (int)bs->counted[b];
@@ -4581,6 +4606,25 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         HIP_TRY(c, hipGetLastError());
         bs->smooth_gy_count = gy;
         if (bs->online) for (size_t b = 0; b < B; ++b) bs->counted[b] = (uint32_t)bs->prob[b].T;
+    }
+    if (dc) {
+        BatchDecodeArgs da{};
+        da.desc = a.desc; da.mass = a.mass; da.tab = a.tab; da.lp = bs->d_lp; da.lp0 = bs->lp0; da.v = bs->d_v; da.words = bs->d_words;
+        da.score = dc->d_score; da.path = dc->d_path;
+        da.B = (int)B; da.T_max = a.T_max; da.k = a.k; da.lp_stride = bs->h_lp.size() > 64 ? 64 : 0;
+        da.full = dc->full ? 1 : 0; da.lag = (int)std::min<uint64_t>(dc->lag, (uint64_t)kBackwardMaxT); da.n_rows = (int)dc->n_rows;
+        // a wavefront a problem; it also leaves the score, so it runs where no step is new
+        hipLaunchKernelGGL(batch_decode_forward_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, da);
+        HIP_TRY(c, hipGetLastError());
+        if (bs->online) for (size_t b = 0; b < B; ++b) bs->decoded[b] = (uint32_t)bs->prob[b].T;
+        if (!dc->d_path) return 0;
+        // row 0 of the grid: the item of end L - 1; the ends before it a lane each, (gridDim.y - 1) * kThreads apart
+        int64_t lane_items = 0;
+        if (!dc->full) for (size_t b = 0; b < B; ++b) lane_items = std::max<int64_t>(lane_items, (int64_t)pd[b].T - 1 - (int64_t)pd[b].mfrom - (int64_t)da.lag);
+        const unsigned gy = 1u + (unsigned)std::min<int64_t>((lane_items + kThreads - 1) / kThreads, kDecodeTraceGridMax);
+        hipLaunchKernelGGL(batch_decode_trace_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, da);
+        HIP_TRY(c, hipGetLastError());
+        return 0;
     }
     if (fc) {
         BatchForecastArgs fa{};
@@ -4894,6 +4938,157 @@ int cpprob_hip_batch_predictive(cpprob_hip_ctx* c, const uint32_t* h_from, uint6
     if (int rc = batch_smooth_enqueue(c, 0, 0, d_rows, nullptr, nullptr, nullptr, &fc)) return rc;
     HIP_TRY(c, hipMemcpyAsync(h_rows, d_rows, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- decoding a batch (csrc/batch_decode.hpp) ---------------------------------------------------------------------------------------
+// The log tables of the batch last begun, on the host: one a problem (a described CPPROB_HIP_MODEL_HMM_TABLE batch) or one for all.
+static void batch_decode_table(BatchState* bs)
+{
+    if (bs->lp_ready) return;
+    const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
+    const size_t tables = hmm3 ? 1 : bs->h_thr.size() / 64;
+    bs->h_lp.assign(tables * 64, 0.0);
+    uint64_t h3[64];
+    for (int i = 0; i < 64; ++i) h3[i] = ~0ull;
+    for (int s2 = 0; s2 < 3; ++s2) for (int j = 0; j < 2; ++j) h3[s2 * 8 + j] = bs->mp.hmm_thr[s2][j];
+    for (size_t i = 0; i < tables; ++i) decode_log_table(hmm3 ? h3 : bs->h_thr.data() + i * 64, hmm3 ? 3 : bs->hk, bs->h_lp.data() + i * 64, &bs->lp0);
+    bs->lp_ready = true;
+}
+
+// The decode's own allocations for word_rows step words, and the log tables' upload (once a begin).  Where a buffer has to grow it
+// waits for the calls before it, and the words kept so far go with it.
+static int batch_decode_prepare(cpprob_hip_ctx* c, size_t word_rows)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    batch_decode_table(bs);
+    const size_t tables = bs->h_lp.size() / 64;
+    if (word_rows > bs->words_cap || B > bs->v_cap || tables > bs->lp_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (earlier calls' kernels may still read the buffers this replaces)
+        if (word_rows > bs->words_cap) {
+            dfree(bs->d_words); bs->words_cap = 0;
+            bs->decoded.assign(B, 0);
+            HIP_TRY(c, hipMalloc(&bs->d_words, word_rows * sizeof(uint32_t)));
+            bs->words_cap = word_rows;
+        }
+        if (B > bs->v_cap) {
+            dfree(bs->d_v); bs->v_cap = 0;
+            bs->decoded.assign(B, 0);
+            HIP_TRY(c, hipMalloc(&bs->d_v, B * 8 * sizeof(double)));
+            bs->v_cap = B;
+        }
+        if (tables > bs->lp_cap) {
+            dfree(bs->d_lp); bs->lp_cap = 0; bs->lp_sent = false;
+            HIP_TRY(c, hipMalloc(&bs->d_lp, tables * 64 * sizeof(double)));
+            bs->lp_cap = tables;
+        }
+    }
+    if (!bs->lp_sent) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lp, bs->h_lp.data(), bs->h_lp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        bs->lp_sent = true;
+    }
+    return 0;
+}
+
+// A decode call's arguments against the batch's state (batch_smooth_check first), then the totals against the capacities.
+static int batch_decode_check(cpprob_hip_ctx* c, bool full, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, bool with_path, size_t n_entries,
+                              bool with_score, size_t n_doubles, uint64_t& entries)
+{
+    uint64_t full_doubles = 0, full_entries = 0;
+    if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, full_doubles, full_entries)) return rc;
+    BatchState* bs = c->batch;
+    entries = 0;
+    if (full) {
+        for (const BatchProblem& pr : bs->prob) entries += (uint64_t)pr.T;
+        if (with_path && n_entries < entries) return fail(c, CPPROB_HIP_EINVAL, "the path buffer is too small: " + std::to_string(entries) + " entries (cpprob_hip_batch_smooth_layout with n_traj = 1)");
+    } else {
+        if (lag > (uint64_t)kBackwardMaxT) return fail(c, CPPROB_HIP_EINVAL, "lag must lie in 0 .. 2^24");
+        if (n_rows > (uint64_t)INT32_MAX) return fail(c, CPPROB_HIP_EINVAL, "n_rows must lie in 0 .. 2^31 - 1");
+        for (size_t b = 0; b < bs->prob.size(); ++b) {
+            const uint64_t L = (uint64_t)bs->prob[b].T, from = h_from ? h_from[b] : 0;
+            if (from > L) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": from = " + std::to_string(from) + " lies past its length of " + std::to_string(L));
+            if (with_path && L - from > n_rows)
+                return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": " + std::to_string(L - from) + " rows asked for, n_rows = " + std::to_string(n_rows));
+        }
+        entries = (uint64_t)bs->cfg.n_problems * n_rows;
+        if (with_path && n_entries < entries) return fail(c, CPPROB_HIP_EINVAL, "the states buffer is too small: " + std::to_string(entries) + " entries (n_problems * n_rows)");
+    }
+    if (with_score && n_doubles < (size_t)bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "the score buffer is too small: " + std::to_string(bs->cfg.n_problems) + " doubles (one a problem)");
+    return 0;
+}
+
+// Both calls' device forms (dc.d_score, dc.d_path: device buffers or nullptr).
+static int batch_decode_device(cpprob_hip_ctx* c, BatchDecode dc, size_t n_entries, size_t n_doubles)
+{
+    uint64_t entries = 0;
+    if (int rc = batch_decode_check(c, dc.full, dc.lag, dc.from, dc.n_rows, dc.d_path != nullptr, n_entries, dc.d_score != nullptr, n_doubles, entries)) return rc;
+    if (entries == 0) dc.d_path = nullptr;
+    if (!dc.d_path && !dc.d_score) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dc);
+}
+
+// Both calls' host forms: staged on the device, the int8 entries widened.
+static int batch_decode_host(cpprob_hip_ctx* c, BatchDecode dc, int32_t* h_path, size_t n_entries, double* h_score, size_t n_doubles)
+{
+    uint64_t entries = 0;
+    if (int rc = batch_decode_check(c, dc.full, dc.lag, dc.from, dc.n_rows, h_path != nullptr, n_entries, h_score != nullptr, n_doubles, entries)) return rc;
+    const bool with_path = h_path && entries;
+    if (!with_path && !h_score) return 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = c->batch->cfg.n_problems;
+    if (int rc = batch_forecast_stage(c, h_score ? B : 0, with_path ? (size_t)entries : 0, dc.d_score, dc.d_path)) return rc;
+    if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dc)) return rc;
+    std::vector<int8_t> v(with_path ? (size_t)entries : 0);
+    if (with_path) HIP_TRY(c, hipMemcpyAsync(v.data(), dc.d_path, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
+    if (h_score) HIP_TRY(c, hipMemcpyAsync(h_score, dc.d_score, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < v.size(); ++i) h_path[i] = v[i];
+    return 0;
+}
+
+int cpprob_hip_batch_decode_device(cpprob_hip_ctx* c, int8_t* d_path, size_t n_entries, double* d_score, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    return batch_decode_device(c, BatchDecode{true, 0, nullptr, 0, d_score, d_path}, n_entries, n_doubles);
+}
+
+int cpprob_hip_batch_decode(cpprob_hip_ctx* c, int32_t* h_path, size_t n_entries, double* h_score, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    return batch_decode_host(c, BatchDecode{true, 0, nullptr, 0, nullptr, nullptr}, h_path, n_entries, h_score, n_doubles);
+}
+
+int cpprob_hip_batch_decode_lag_device(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, int8_t* d_states, size_t n_entries,
+                                       double* d_score, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    return batch_decode_device(c, BatchDecode{false, lag, h_from, n_rows, d_score, d_states}, n_entries, n_doubles);
+}
+
+int cpprob_hip_batch_decode_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, int32_t* h_states, size_t n_entries,
+                                double* h_score, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    return batch_decode_host(c, BatchDecode{false, lag, h_from, n_rows, nullptr, nullptr}, h_states, n_entries, h_score, n_doubles);
+}
+
+int cpprob_hip_batch_decode_logp(cpprob_hip_ctx* c, uint64_t problem, double* h_lp, double* h_lp0)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch begun");
+    if (!h_lp || !h_lp0) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    batch_decode_table(bs);
+    const size_t tables = bs->h_lp.size() / 64;
+    std::memcpy(h_lp, bs->h_lp.data() + (tables > 1 ? (size_t)problem * 64 : 0), 64 * sizeof(double));
+    *h_lp0 = bs->lp0;
     return 0;
 }
 

@@ -28,9 +28,15 @@
 //                   --em_iterations N (with --batch_tables_file, not with --stream_chunk: particle EM -- N runs, each followed by the
 //                   backward smoother's expected sufficient statistics and an M-step on every problem's table; the usual output is the
 //                   last run's, then the fitted tables follow, one "[means] [transition]" line a problem in the input's grammar)
+//                   --decode (the batch modes and --stream_chunk, not with --filtering_only unless --keep_masses: after the statistics, a
+//                   line "decode b score x_0 .. x_{T-1}" a problem -- the single most probable state path given the observes, over the
+//                   states the particles occupy, and its log joint density; --json carries "map_path" and "map_score" instead; with
+//                   --em_iterations the decode is that of the fitted tables)   --decode_lag L (with --decode: x_t is the state at t of the
+//                   best path of steps 0 .. min(t + L, T - 1), what a stream would have labelled L observes later)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <fstream>
@@ -100,6 +106,13 @@ void print_json(const cpprob::gpu::Result& r)
         }
         std::cout << "]";
     }
+    if (r.map_decoded) {                                         // --decode: the most probable state path and its log joint density
+        std::cout << ", \"map_score\": ";
+        if (std::isfinite(r.map_score)) std::cout << r.map_score; else std::cout << "null";
+        std::cout << ", \"map_path\": [";
+        for (std::size_t t = 0; t < r.map_path.size(); ++t) std::cout << (t ? ", " : "") << r.map_path[t];
+        std::cout << "]";
+    }
     if (r.n_replicates > 1) {
         std::cout << ", \"replicates\": " << r.n_replicates << ", \"log_evidence_mean\": " << r.log_evidence_mean << ", \"log_evidence_sd\": " << r.log_evidence_sd
                   << ", \"replicates_seconds\": " << r.replicates_seconds << ", \"predict_mean\": [";
@@ -127,6 +140,18 @@ void print_forecasts(const std::vector<cpprob::gpu::Result>& res)
             for (std::int32_t x : res[b].forecast_trajectories[j]) std::cout << " " << x;
             std::cout << std::endl;
         }
+    }
+}
+
+// --decode [--decode_lag L], after the statistics (and the forecasts) of the batch: problem b's row "decode b score x_0 .. x_{T-1}"
+// (--json carries both inside the problem's object instead)
+void print_decodes(const std::vector<cpprob::gpu::Result>& res)
+{
+    for (std::size_t b = 0; b < res.size(); ++b) {
+        if (!res[b].map_decoded) continue;
+        std::cout << "decode " << b << " " << res[b].map_score;
+        for (std::int32_t x : res[b].map_path) std::cout << " " << x;
+        std::cout << std::endl;
     }
 }
 
@@ -158,6 +183,7 @@ int execute_batch(const F& model, const Args& a)
         std::cout << std::endl;
     }
     if (!a.json) print_forecasts(res);
+    if (!a.json) print_decodes(res);
     cpprob::gpu::release_device_resources();
     return EXIT_SUCCESS;
 }
@@ -225,6 +251,7 @@ int execute_batch_tables(const Args& a)
         std::cout << std::endl;
     }
     if (!a.json) print_forecasts(res);
+    if (!a.json) print_decodes(res);
     for (const cpprob::gpu::HmmTable& t : fitted) {
         std::cout << "[";
         for (std::size_t s = 0; s < t.means.size(); ++s) std::cout << (s ? " " : "") << t.means[s];
@@ -293,6 +320,8 @@ int main(int argc, char** argv)
         else if (f == "--batch_dump") a.batch_dump = true;                         // the batch modes: problem b's traces as <generated_file>_smc_<b>.int / .ids
         else if (f == "--backward_smoothing") opt.backward_smoothing = true;      // the batch modes: statistics from the backward smoother (cpprob_hip_batch_smooth)
         else if (f == "--smoothing_lag") opt.smoothing_lag = std::stol(next());    // the batch modes: fixed-lag marginals (cpprob_hip_batch_smooth_lag)
+        else if (f == "--decode") opt.map_decode = true;                           // the batch modes: the most probable state path (cpprob_hip_batch_decode)
+        else if (f == "--decode_lag") opt.decode_lag = std::stol(next());          // ... its fixed-lag rows instead (cpprob_hip_batch_decode_lag)
         else if (f == "--forecast") opt.forecast_horizon = std::stoull(next());   // the batch modes: the state's laws this many steps ahead (cpprob_hip_batch_forecast)
         else if (f == "--forecast_trajectories") opt.forecast_trajectories = std::stoull(next());   // ... and this many simulated futures a problem
         else if (f == "--backward_trajectories") opt.backward_trajectories = std::stoull(next());   // ... and --batch_dump writes this many backward-simulated trajectories
@@ -325,6 +354,15 @@ int main(int argc, char** argv)
     if (a.sis == a.smc) { std::cerr << "exactly one of --sis / --smc has to be set" << std::endl; return EXIT_FAILURE; }
     if ((opt.forecast_horizon || opt.forecast_trajectories) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
         std::cerr << "--forecast serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if ((opt.map_decode || opt.decode_lag >= 0) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
+        std::cerr << "--decode serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (opt.decode_lag >= 0 && !opt.map_decode) { std::cerr << "--decode_lag delays a decode: set --decode" << std::endl; return EXIT_FAILURE; }
+    if (opt.map_decode && !opt.keep_history && !opt.keep_masses) {
+        std::cerr << "--decode reads the smoother's masses: with --filtering_only set --keep_masses" << std::endl;
         return EXIT_FAILURE;
     }
     try {

@@ -647,6 +647,46 @@ inline void batch_forecast_results(Context& ctx, std::size_t H, std::size_t M, s
     }
 }
 
+// ---- decoding a batch (cpprob_hip_batch_decode, _decode_lag): Options::map_decode, ::decode_lag ---------------------------------------
+// What the C ABI would refuse, refused before a batch is begun.  stored: the batch keeps its history or its masses.
+inline void check_decode_options(const std::string& who, bool decode, long lag, bool stored)
+{
+    if (!decode) {
+        if (lag >= 0) throw std::runtime_error(who + ": options().decode_lag delays a decode: set options().map_decode");
+        return;
+    }
+    if (lag > (1l << 24)) throw std::runtime_error(who + ": options().decode_lag must lie in 0 .. 2^24");
+    if (!stored)
+        throw std::runtime_error(who + ": decoding reads the smoother's masses: a filtering-only run (options().keep_history = false) keeps none without options().keep_masses");
+}
+
+// The decode of the batch last run or advanced on ctx into its results (L: the lengths reached): Result::map_path the most probable
+// state path, or (lag >= 0) the fixed-lag rows from step 0 on, and Result::map_score.
+inline void batch_decode_results(Context& ctx, bool decode, long lag, const std::vector<std::uint32_t>& L, std::vector<Result>& out)
+{
+    if (!decode) return;
+    const std::size_t B = out.size();
+    std::vector<double> score(B);
+    std::size_t total = 0, n_rows = 0;
+    for (std::size_t b = 0; b < B; ++b) { total += L[b]; n_rows = std::max<std::size_t>(n_rows, L[b]); }
+    if (lag < 0) {
+        std::vector<std::int32_t> path(total);
+        ctx.check(cpprob_hip_batch_decode(ctx.get(), total ? path.data() : nullptr, path.size(), score.data(), score.size()), "cpprob_hip_batch_decode");
+        std::size_t at = 0;
+        for (std::size_t b = 0; b < B; ++b) {
+            out[b].map_path.assign(path.begin() + static_cast<std::ptrdiff_t>(at), path.begin() + static_cast<std::ptrdiff_t>(at + L[b]));
+            at += L[b];
+        }
+    } else {
+        std::vector<std::int32_t> st(B * n_rows);
+        ctx.check(cpprob_hip_batch_decode_lag(ctx.get(), static_cast<std::uint64_t>(lag), nullptr, n_rows, n_rows ? st.data() : nullptr, st.size(), score.data(), score.size()),
+                  "cpprob_hip_batch_decode_lag");
+        for (std::size_t b = 0; b < B; ++b)
+            out[b].map_path.assign(st.begin() + static_cast<std::ptrdiff_t>(b * n_rows), st.begin() + static_cast<std::ptrdiff_t>(b * n_rows + L[b]));
+    }
+    for (std::size_t b = 0; b < B; ++b) { out[b].map_decoded = true; out[b].map_score = score[b]; }
+}
+
 // The trace structure of a table-HMM problem of T observes: one int predict per observe, "state[t]".
 inline detail::TraceStructure hmm_table_structure(std::size_t T)
 {
@@ -695,6 +735,7 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     if (!opt.keep_history && !masses && opt.smoothing_lag >= 0)
         throw std::runtime_error("cpprob::gpu::inference_batch: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     check_forecast_options("cpprob::gpu::inference_batch", opt.forecast_horizon, opt.forecast_trajectories, opt.keep_history || masses);
+    check_decode_options("cpprob::gpu::inference_batch", opt.map_decode, opt.decode_lag, opt.keep_history || masses);
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -725,6 +766,7 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
                              opt.dump_max_particles, [&st](std::size_t) -> const detail::TraceStructure& { return st; });
     std::vector<Result> out(B);
     batch_forecast_results(ctx, opt.forecast_horizon, opt.forecast_trajectories, K, K, out);
+    batch_decode_results(ctx, opt.map_decode, opt.decode_lag, std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(T)), out);
     lease.done();
     for (std::size_t b = 0; b < B; ++b) {
         Result& r = out[b];
@@ -785,12 +827,14 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
     if (!opt.keep_history && !masses && opt.smoothing_lag >= 0)
         throw std::runtime_error(who + ": fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     check_forecast_options(who, opt.forecast_horizon, opt.forecast_trajectories, opt.keep_history || masses);
+    check_decode_options(who, opt.map_decode, opt.decode_lag, opt.keep_history || masses);
     return pk;
 }
 
 // One batch of the packed problems on ctx: begin, run, results (options().backward_smoothing / ::smoothing_lag as hmm_table_batch
-// states them) and, where dump is set, options().batch_dump_file.  The batch stays on ctx for the calls that read it.
-inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTableProblems& pk, const std::vector<std::uint64_t>& seeds, bool dump)
+// states them) and, where dump is set, options().batch_dump_file; decode: options().map_decode is served.  The batch stays on ctx for
+// the calls that read it.
+inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTableProblems& pk, const std::vector<std::uint64_t>& seeds, bool dump, bool decode = true)
 {
     const Options& opt = options();
     const std::size_t B = seeds.size(), k = pk.k, T_max = pk.T_max;
@@ -835,6 +879,7 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
         r.step_ess.assign(ess.begin() + b * T_max, ess.begin() + b * T_max + T[b]);
     }
     batch_forecast_results(ctx, opt.forecast_horizon, opt.forecast_trajectories, K, k, out);
+    batch_decode_results(ctx, decode && opt.map_decode, opt.decode_lag, T, out);
     return out;
 }
 
@@ -855,7 +900,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // (the M-step; a row or a state without mass keeps its value; the emission's sigma is 1 and not fitted).  Returns the fitted tables
 // and the results of the last run -- those of the tables that run began with.  options().keep_history must be set, or options().keep_masses
 // with it (the statistics then come from the masses the filtering-only runs keep);
-// options().batch_dump_file is written by the last run.
+// options().batch_dump_file is written by the last run.  options().map_decode: one more run, with the keys seeds[b] + iterations,
+// under the FITTED tables, and its decode (Result::map_path, ::map_score) in the results -- the labels a fit is made for.
 struct HmmTableFit { std::vector<HmmTable> tables; std::vector<Result> results; };
 
 inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes, const std::vector<std::size_t>& n,
@@ -873,7 +919,7 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
     std::vector<std::uint64_t> keys(B);
     for (std::size_t it = 0; it < iterations; ++it) {
         for (std::size_t b = 0; b < B; ++b) keys[b] = seeds[b] + it;
-        fit.results = run_hmm_table_problems(ctx, pk, keys, it + 1 == iterations);
+        fit.results = run_hmm_table_problems(ctx, pk, keys, it + 1 == iterations, false);
         ctx.check(cpprob_hip_batch_smooth_stats(ctx.get(), pk.flat.empty() ? nullptr : pk.flat.data(), pk.flat.size(), rec.data(), rec.size()),
                   "cpprob_hip_batch_smooth_stats");
         for (std::size_t b = 0; b < B; ++b) {
@@ -886,6 +932,12 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
                 if (r[64 + s] > 0.0) pk.means[b * k + s] = r[72 + s] / r[64 + s];
             }
         }
+    }
+    if (options().map_decode) {
+        for (std::size_t b = 0; b < B; ++b) keys[b] = seeds[b] + iterations;
+        std::vector<Result> fin = run_hmm_table_problems(ctx, pk, keys, false, true);
+        if (fit.results.empty()) fit.results = fin;
+        for (std::size_t b = 0; b < B; ++b) { fit.results[b].map_decoded = true; fit.results[b].map_path = fin[b].map_path; fit.results[b].map_score = fin[b].map_score; }
     }
     lease.done();
     fit.tables.resize(B);
@@ -912,6 +964,10 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // and the predicts depend on the lengths reached alone, never on how the observes were cut into advances.
 // options().forecast_horizon = H > 0: every advance's results carry the forecast from the lengths reached (Result::forecast, and
 // Result::forecast_trajectories for options().forecast_trajectories > 0); a problem without observes has rows of zeros.
+// options().map_decode: every advance's results carry the most probable state path of the lengths reached (Result::map_path,
+// ::map_score); with options().decode_lag = lag >= 0 the path holds the fixed-lag rows instead -- row t is final once lag more
+// observes have arrived --, an advance asks for the rows from max(0, L_before - lag) on and the object keeps the final ones.  The
+// forward work of an advance is that of its new steps either way.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -922,6 +978,7 @@ public:
     {
         if (B_ == 0) throw std::runtime_error("cpprob::gpu::HmmTableStream: no problems (one seed per problem)");
         check_forecast_options("cpprob::gpu::HmmTableStream", forecast_H_, forecast_M_, keep_ || masses_);
+        check_decode_options("cpprob::gpu::HmmTableStream", decode_, decode_lag_, keep_ || masses_);
         if (!keep_ && !masses_ && backward_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         if (!keep_ && !masses_ && lag_ >= 0)
@@ -960,6 +1017,7 @@ public:
                   "cpprob_hip_batch_begin_online");
         lease_.done();
         if (lag_ >= 0) { lagged_.assign(B_ * T_max_ * 8, 0.0); L_prev_.assign(B_, 0); }
+        if (decode_ && decode_lag_ >= 0) { decoded_.assign(B_ * T_max_, -1); dec_prev_.assign(B_, 0); }
     }
     HmmTableStream(const HmmTableStream&) = delete;
     HmmTableStream& operator=(const HmmTableStream&) = delete;
@@ -1018,6 +1076,26 @@ public:
             r.step_ess.assign(ess.begin() + b * T_max_, ess.begin() + b * T_max_ + L[b]);
         }
         batch_forecast_results(ctx, forecast_H_, forecast_M_, K, k_, out);      // (after every advance, whatever its readout)
+        if (decode_ && decode_lag_ >= 0) {
+            // the rows the new observes can still change: from max(0, L_before - lag) on; the rows before them are final and kept
+            std::vector<std::uint32_t> from(B_);
+            std::size_t n_rows = 0;
+            for (std::size_t b = 0; b < B_; ++b) {
+                from[b] = dec_prev_[b] > static_cast<std::size_t>(decode_lag_) ? static_cast<std::uint32_t>(dec_prev_[b] - static_cast<std::size_t>(decode_lag_)) : 0u;
+                n_rows = std::max<std::size_t>(n_rows, L[b] - from[b]);
+            }
+            std::vector<std::int32_t> st(B_ * n_rows);
+            std::vector<double> score(B_);
+            ctx.check(cpprob_hip_batch_decode_lag(ctx.get(), static_cast<std::uint64_t>(decode_lag_), from.data(), n_rows, n_rows ? st.data() : nullptr, st.size(),
+                                                  score.data(), score.size()), "cpprob_hip_batch_decode_lag");
+            for (std::size_t b = 0; b < B_; ++b) {
+                std::copy(st.begin() + static_cast<std::ptrdiff_t>(b * n_rows), st.begin() + static_cast<std::ptrdiff_t>(b * n_rows + (L[b] - from[b])),
+                          decoded_.begin() + static_cast<std::ptrdiff_t>(b * T_max_ + from[b]));
+                dec_prev_[b] = L[b];
+                out[b].map_decoded = true; out[b].map_score = score[b];
+                out[b].map_path.assign(decoded_.begin() + static_cast<std::ptrdiff_t>(b * T_max_), decoded_.begin() + static_cast<std::ptrdiff_t>(b * T_max_ + L[b]));
+            }
+        } else batch_decode_results(ctx, decode_, -1, L, out);
         return out;
     }
 
@@ -1041,6 +1119,10 @@ private:
     std::size_t forecast_H_ = options().forecast_horizon, forecast_M_ = options().forecast_trajectories;
     std::vector<double> lagged_;               // smoothing_lag: [B][T_max][8], the fixed-lag rows so far (rows below L - lag are final)
     std::vector<std::size_t> L_prev_;          // ... and the lengths they stand for
+    bool decode_ = options().map_decode;
+    long decode_lag_ = options().decode_lag;
+    std::vector<std::int32_t> decoded_;        // decode_lag: [B][T_max], the fixed-lag rows so far (rows below L - lag are final)
+    std::vector<std::size_t> dec_prev_;        // ... and the lengths they stand for
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

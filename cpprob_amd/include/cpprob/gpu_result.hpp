@@ -43,6 +43,12 @@ struct Options {
                                                       // the state 1 .. forecast_horizon steps past the last observe, P(x_{L-1+h} | y_0 .. y_{L-1})
                                                       // (cpprob_hip_batch_forecast); HmmTableStream: after every advance.  0: off
     std::size_t forecast_trajectories = 0;            // ... and, not 0, Result::forecast_trajectories: this many simulated futures (draw_index 0)
+    bool map_decode = false;                          // batched runs (keep_history, or keep_masses): every result carries Result::map_path, the single most
+                                                      // probable state sequence given the observes over the states the particles occupy, and
+                                                      // Result::map_score (cpprob_hip_batch_decode); hmm_table_fit decodes under the fitted tables
+    long decode_lag = -1;                             // ... not negative: Result::map_path holds the fixed-lag rows instead, row t the state at t of the
+                                                      // best path of steps 0 .. min(t + lag, L - 1) (cpprob_hip_batch_decode_lag): what a stream labels
+                                                      // with that delay.  HmmTableStream asks for the rows not yet final only
     bool markov_probe = true;                         // smc, unchanged-model path: test on the host whether a step depends on more than the last few
                                                       // sampled values; a model that does not is replayed from that window only (O(T) instead of O(T^2))
     bool markov_crosscheck = true;                    // ... and certify the probe's window on the device before using it: a pilot population under windowed
@@ -99,6 +105,9 @@ struct Result {
     std::vector<double> step_ess;             // smc: ESS after each observe
     std::vector<std::vector<double>> forecast;                      // Options::forecast_horizon: [h - 1][s] = P(x_{L-1+h} = s | y_0 .. y_{L-1}), h = 1 .. horizon
     std::vector<std::vector<std::int32_t>> forecast_trajectories;   // Options::forecast_trajectories: [j][h], future j's states; h = 0 is the present state
+    bool map_decoded = false;                 // Options::map_decode: the two fields below are set
+    std::vector<std::int32_t> map_path;       // [t]: the most probable state path (Options::decode_lag >= 0: the fixed-lag rows)
+    double map_score = 0;                     // the log joint density of the full decode's path and the observes; 0 without observes
     // Options::replicates > 1: replicate 0 is what the fields above (and the dump) describe; across replicates:
     int n_replicates = 1;
     double log_evidence_mean = 0, log_evidence_sd = 0;        // log of the mean evidence (unbiased in Z); sd of the log estimates

@@ -529,6 +529,55 @@ int cpprob_hip_batch_predictive(cpprob_hip_ctx* ctx, const uint32_t* h_from, uin
 /* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation. */
 int cpprob_hip_batch_predictive_device(cpprob_hip_ctx* ctx, const uint32_t* h_from, uint64_t n_rows, double* d_rows, size_t n_doubles);
 
+/* Decoding a batch (csrc/batch_decode.hpp): the single most probable state path of every problem given its observes, by dynamic
+ * programming over the states the particles occupy (the particle form of the MAP sequence estimate: Godsill, Doucet & West 2001).
+ * The per-step argmax of cpprob_hip_batch_smooth's marginals is a different estimator and may name a sequence the transition table
+ * forbids; this one cannot.  It reads the smoother's m table, the per-step log-likelihood rows and the threshold words, and touches no
+ * particle.  Per problem b (L_b the length reached, k its states, m_t its rows of the m table, ll_t[s] the log-likelihood of observe
+ * t in state s, P[s][s'] the integer transition masses of cpprob_hip_batch_smooth):
+ *   lp[s][s']  = log(double(P[s][s']) * 2^-32), -inf where P = 0;  lp0 = log(1.0 / double(k)): computed on the HOST (std::log), the
+ *                table cpprob_hip_batch_decode_logp returns; the device evaluates no logarithm
+ *   support      S_t = { s < k : m_t[s] > 0 }
+ *   v_0[s]     = lp0 + ll_0[s] for s in S_0, else -inf;  bp_0[.] = 0
+ *   t >= 1, s' < k: best = -inf, arg = 0; for s = 0 .. k-1 in that order c = v_{t-1}[s] + lp[s][s'], taken if c > best (strict: ties
+ *                go to the lowest s, an all -inf column keeps arg = 0);  bp_t[s'] = arg;  v_t[s'] = best + ll_t[s'] for s' in S_t,
+ *                else -inf.  Every sum is one IEEE addition.
+ *   end_t      = the first s of the same strict scan over v_t[0..k)
+ *   step word    w_t = sum over s' < 8 of bp_t[s'] << (3 s') | end_t << 24
+ *   full decode  x_{L-1} = end_{L-1};  x_{t-1} = (w_t >> 3 x_t) & 7;  score = v_{L-1}[end_{L-1}], the log joint density of the path
+ *                and the observes under the realised law
+ * On a store a run wrote every supported state has a finite candidate; the -inf rules are defensive.
+ * Path: problem b's L_b entries from h_first[b] on, exactly cpprob_hip_batch_smooth_layout with n_traj = 1.  h_score: [B]; a problem
+ * of length 0 owns no entries and has score 0.  Either output may be NULL.  State as for the smoothing calls: the particle store
+ * (keep_history = 1) or CPPROB_HIP_BATCH_KEEP_MASSES, and a run or advance before it (else CPPROB_HIP_ESTATE).  CPPROB_HIP_EINVAL
+ * (nothing written): a capacity too small, a problem longer than 2^24.
+ * Cost.  The step words (4 B a row of the m table, addressed as it is), a v row of 8 doubles a problem and the log tables are
+ * allocations of the context's own, made on first use.  An online batch keeps its words as it keeps the m table: a call walks the
+ * steps that arrived since the last decode call -- a stream fed one observe at a time does L steps of forward work in all, not
+ * L^2 / 2 -- and any batch begin forgets them.  A run batch caches nothing.  The counting pass and its watermark are the smoothing
+ * calls': no row is counted twice.  The call changes nothing any other entry point returns.
+ * Host copies: h_path int32.  Stages on the device and widens.  Synchronises. */
+int cpprob_hip_batch_decode(cpprob_hip_ctx* ctx, int32_t* h_path, size_t n_entries, double* h_score, size_t n_doubles);
+/* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation: d_path int8. */
+int cpprob_hip_batch_decode_device(cpprob_hip_ctx* ctx, int8_t* d_path, size_t n_entries, double* d_score, size_t n_doubles);
+/* Fixed-lag decoding on the same words: e(t) = min(t + lag, L_b - 1), X_t = the state at t of the traceback started at end_{e(t)}.
+ * X_t is FINAL once lag more observes have arrived -- it reads the words t + 1 .. e(t) alone and is the same at every later length,
+ * however an online batch was cut into advances; the rows with e(t) = L_b - 1 are cpprob_hip_batch_decode's.
+ * States: [B][n_rows]; row r of problem b is X_{from_b + r} for from_b + r < L_b, every other row is -1 (0 is a state).  h_from: [B]
+ * (a host array, read before the call returns), or NULL for all 0.  n_rows >= max over b of (L_b - from_b).  h_score as above (the
+ * full decode's).  Either output may be NULL.  State and cost as above; the traceback's own work is the rows asked for times lag.
+ * CPPROB_HIP_EINVAL (nothing written; the message names the problem where one is at fault): from_b > L_b, n_rows too small,
+ * lag > 2^24, a capacity too small, a problem longer than 2^24.  Host copies: h_states int32.  Synchronises. */
+int cpprob_hip_batch_decode_lag(cpprob_hip_ctx* ctx, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, int32_t* h_states, size_t n_entries,
+                                double* h_score, size_t n_doubles);
+/* The same left on the device, enqueued on the context's stream after the run / advance, no host synchronisation: d_states int8. */
+int cpprob_hip_batch_decode_lag_device(cpprob_hip_ctx* ctx, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, int8_t* d_states, size_t n_entries,
+                                       double* d_score, size_t n_doubles);
+/* The log table of `problem` in the batch last begun: h_lp[8 s + s'] = lp[s][s'] (-inf outside the k x k table), *h_lp0 = lp0 -- the
+ * doubles the decode kernels were or will be given, so that a restatement of a run depends on no second logarithm.  Host state only:
+ * no device work, no synchronisation.  CPPROB_HIP_ESTATE: no batch begun. */
+int cpprob_hip_batch_decode_logp(cpprob_hip_ctx* ctx, uint64_t problem, double h_lp[64], double* h_lp0);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
