@@ -46,7 +46,7 @@ SYMBOLS = [
     "cpprob_hip_batch_smooth_stats", "cpprob_hip_batch_smooth_stats_device",
     "cpprob_hip_batch_forecast", "cpprob_hip_batch_forecast_device", "cpprob_hip_batch_predictive", "cpprob_hip_batch_predictive_device",
     "cpprob_hip_batch_decode", "cpprob_hip_batch_decode_device", "cpprob_hip_batch_decode_lag", "cpprob_hip_batch_decode_lag_device",
-    "cpprob_hip_batch_decode_logp",
+    "cpprob_hip_batch_decode_logp", "cpprob_hip_batch_pass_grid",
 ]
 
 
@@ -353,6 +353,7 @@ def load_library(path=None):
         "cpprob_hip_batch_decode_lag": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_decode_lag_device": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_decode_logp": (C.c_int, [vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "cpprob_hip_batch_pass_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -903,6 +904,14 @@ class Engine:
         cy, ly = C.c_uint32(0), C.c_uint32(0)
         self._chk(self.L.cpprob_hip_batch_smooth_grid(self.h, C.byref(cy), C.byref(ly)))
         return int(cy.value), int(ly.value)
+
+    def batch_pass_grid(self):
+        """(gridDim.x of the decode's forward launch, gridDim.y of its traceback launch, gridDim.y of the forecast launch, gridDim.y of
+        the predictive launch) of this context's last decode / forecast / predictive call (cpprob_hip_batch_pass_grid); 0 where the
+        launch did not happen.  Host only."""
+        g = [C.c_uint32(0) for _ in range(4)]
+        self._chk(self.L.cpprob_hip_batch_pass_grid(self.h, *[C.byref(x) for x in g]))
+        return tuple(int(x.value) for x in g)
 
     # ---- sharded SMC ---------------------------------------------------------------------
     def step_begin(self, t, local_totals, run_index=0):

@@ -1085,6 +1085,8 @@ struct BatchState {
     hipEvent_t sdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t n_smooth = 0;
     unsigned smooth_gy_count = 0, smooth_gy_lag = 0;        // gridDim.y of the last smoothing call's counting and lag launches (0: none)
+    // of the last decode / forecast / predictive call: gridDim.x of the forward launch, gridDim.y of the trace, forecast and predictive launches (0: none)
+    unsigned decode_gx_forward = 0, decode_gy_trace = 0, forecast_gy = 0, predictive_gy = 0;
     // decoding (cpprob_hip_batch_decode*; csrc/batch_decode.hpp): the step words (addressed as the m table's rows: an online batch's by
     // capacity, kept), the v rows [B][8] and the log tables ([tables][64], computed on the host at the first call after a begin and
     // uploaded once), allocations of the context's own; decoded: [B], online batch: its words [0, decoded_b) and its v row are valid
@@ -4474,7 +4476,7 @@ int cpprob_hip_batch_smooth_layout(const uint32_t* h_T, uint64_t n_problems, uin
 static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, bool with_marg, size_t n_doubles, bool with_traj, size_t n_entries, uint64_t& doubles, uint64_t& entries)
 {
     BatchState* bs = c->batch;
-    if (bs) bs->smooth_gy_count = bs->smooth_gy_lag = 0;
+    if (bs) bs->smooth_gy_count = bs->smooth_gy_lag = bs->decode_gx_forward = bs->decode_gy_trace = bs->forecast_gy = bs->predictive_gy = 0;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
     if (bs->cfg.keep_history != 1 && !batch_masses(&bs->cfg)) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
     if (draw_index >= (uint64_t)kBackwardMaxDraws) return fail(c, CPPROB_HIP_EINVAL, "draw_index must lie in 0 .. 2^16 - 1");
@@ -4616,6 +4618,7 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         // a wavefront a problem; it also leaves the score, so it runs where no step is new
         hipLaunchKernelGGL(batch_decode_forward_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, da);
         HIP_TRY(c, hipGetLastError());
+        bs->decode_gx_forward = (unsigned)((B + kWaves - 1) / kWaves);
         if (bs->online) for (size_t b = 0; b < B; ++b) bs->decoded[b] = (uint32_t)bs->prob[b].T;
         if (!dc->d_path) return 0;
         // row 0 of the grid: the item of end L - 1; the ends before it a lane each, (gridDim.y - 1) * kThreads apart
@@ -4624,6 +4627,7 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         const unsigned gy = 1u + (unsigned)std::min<int64_t>((lane_items + kThreads - 1) / kThreads, kDecodeTraceGridMax);
         hipLaunchKernelGGL(batch_decode_trace_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, da);
         HIP_TRY(c, hipGetLastError());
+        bs->decode_gy_trace = gy;
         return 0;
     }
     if (fc) {
@@ -4638,12 +4642,15 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
             if (owed <= 0) return 0;
             const unsigned gy = (unsigned)std::min<int64_t>((owed + kWaves - 1) / kWaves, kPredictiveGridMax);
             hipLaunchKernelGGL(batch_predictive_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, fa);
+            HIP_TRY(c, hipGetLastError());
+            bs->predictive_gy = gy;
         } else {
             const unsigned tiles = fa.traj ? (unsigned)((n_traj + kTile - 1) / kTile) : 0u;
             if (hmm3) hipLaunchKernelGGL(batch_forecast_kernel<3>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), 0, c->stream, fa);
             else hipLaunchKernelGGL(batch_forecast_kernel<8>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), 0, c->stream, fa);
+            HIP_TRY(c, hipGetLastError());
+            bs->forecast_gy = 1 + tiles;
         }
-        HIP_TRY(c, hipGetLastError());
         return 0;
     }
     if (lg && d_marg && items_top > 0) {
@@ -5098,6 +5105,18 @@ int cpprob_hip_batch_smooth_grid(cpprob_hip_ctx* c, uint32_t* count_grid_y, uint
     if (!count_grid_y || !lag_grid_y) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     *count_grid_y = c->batch ? c->batch->smooth_gy_count : 0u;
     *lag_grid_y = c->batch ? c->batch->smooth_gy_lag : 0u;
+    return 0;
+}
+
+int cpprob_hip_batch_pass_grid(cpprob_hip_ctx* c, uint32_t* decode_forward_grid_x, uint32_t* decode_trace_grid_y, uint32_t* forecast_grid_y, uint32_t* predictive_grid_y)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    if (!decode_forward_grid_x || !decode_trace_grid_y || !forecast_grid_y || !predictive_grid_y) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const BatchState* bs = c->batch;
+    *decode_forward_grid_x = bs ? bs->decode_gx_forward : 0u;
+    *decode_trace_grid_y = bs ? bs->decode_gy_trace : 0u;
+    *forecast_grid_y = bs ? bs->forecast_gy : 0u;
+    *predictive_grid_y = bs ? bs->predictive_gy : 0u;
     return 0;
 }
 }  // extern "C"

@@ -577,6 +577,15 @@ int cpprob_hip_batch_decode_lag_device(cpprob_hip_ctx* ctx, uint64_t lag, const 
  * doubles the decode kernels were or will be given, so that a restatement of a run depends on no second logarithm.  Host state only:
  * no device work, no synchronisation.  CPPROB_HIP_ESTATE: no batch begun. */
 int cpprob_hip_batch_decode_logp(cpprob_hip_ctx* ctx, uint64_t problem, double h_lp[64], double* h_lp0);
+/* The grids of the context's last decode, forecast or predictive call (any form of them), host only, as cpprob_hip_batch_smooth_grid
+ * reports the smoother's: gridDim.x of the decode's forward launch -- a workgroup takes 4 problems, the problems 4 times that far
+ * apart --, gridDim.y of its traceback launch -- row 0 the end L - 1, a lane of the rows behind it an earlier end, the ends
+ * 256 (gridDim.y - 1) apart --, gridDim.y of the forecast launch -- 1 + the tiles of 1024 trajectories -- and gridDim.y of the
+ * predictive launch -- a wavefront takes the rows 4 times that far apart.  0 where the launch did not happen (or no batch is begun);
+ * every batch call that smooths, forecasts or decodes resets all four.  The results do not depend on them; tests read them to know
+ * how many trips a shape produced. */
+int cpprob_hip_batch_pass_grid(cpprob_hip_ctx* ctx, uint32_t* decode_forward_grid_x, uint32_t* decode_trace_grid_y, uint32_t* forecast_grid_y,
+                               uint32_t* predictive_grid_y);
 
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):

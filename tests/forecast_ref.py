@@ -71,12 +71,15 @@ def predictive_rows(m, P, frm, n_rows, spp):
     return out
 
 
-def trajectories(m, P_thr, seed, H, n_traj, draw_index=0):
+def trajectories(m, P_thr, seed, H, n_traj, draw_index=0, columns=None):
     """[H + 1, n_traj] int32.  P_thr: the threshold rows c[s][0 .. k-2] (R.thresholds).  Row 0 by the backward simulation's start
     rule on m_{L-1}; row h by the forward draw's statement on word 2 (j & 1) of the block of ordinal 2^42 + (draw_index << 24) + h.
-    A problem of length 0: zeros."""
-    out = np.zeros((H + 1, n_traj), np.int32)
-    if len(m) == 0 or n_traj == 0:
+    A problem of length 0: zeros.  columns: the trajectories wanted (indices below n_traj, any order); the result then holds those
+    columns of the full [H + 1, n_traj] only, and only their blocks are drawn (as backward_ref.trajectories_fast's argument)."""
+    cols = np.arange(n_traj, dtype=np.int64) if columns is None else np.asarray(columns, np.int64).reshape(-1)
+    assert cols.size == 0 or (0 <= int(cols.min()) and int(cols.max()) < n_traj)
+    out = np.zeros((H + 1, cols.size), np.int32)
+    if len(m) == 0 or cols.size == 0:
         return out
     k = len(m[-1])
     L = O.lib()
@@ -89,20 +92,24 @@ def trajectories(m, P_thr, seed, H, n_traj, draw_index=0):
     base = DRAW_BASE + (int(draw_index) << 24)
     blk = np.zeros(4, np.uint32)
     thr = [[int(v) for v in row] for row in P_thr]
-    for g in range((n_traj + 1) >> 1):
-        cols = [j for j in (2 * g, 2 * g + 1) if j < n_traj]
+    served = {}                                                    # block g serves trajectories 2 g and 2 g + 1: the places of each
+    for i, j in enumerate(cols.tolist()):
+        served.setdefault(j >> 1, []).append((i, j & 1))
+    for g, places in served.items():
         L.orc_draw_block(int(seed), int(g), base, blk)
         x = {}
-        for j in cols:
-            u = float(L.orc_u01_53(int(blk[2 * (j & 1)]), int(blk[2 * (j & 1) + 1])))
+        for half in set(h for _, h in places):
+            u = float(L.orc_u01_53(int(blk[2 * half]), int(blk[2 * half + 1])))
             target = u * c[k - 1]
             hit = [s for s in range(k) if c[s] > target]
-            x[j] = hit[0] if hit else last
-            out[0, j] = x[j]
+            x[half] = hit[0] if hit else last
+        for i, half in places:
+            out[0, i] = x[half]
         for h in range(1, H + 1):
             L.orc_draw_block(int(seed), int(g), base + h, blk)
-            for j in cols:
-                word = int(blk[2 * (j & 1)])
-                x[j] = sum(1 for i in range(k - 1) if word >= thr[x[j]][i])
-                out[h, j] = x[j]
+            for half in x:
+                word = int(blk[2 * half])
+                x[half] = sum(1 for i in range(k - 1) if word >= thr[x[half]][i])
+            for i, half in places:
+                out[h, i] = x[half]
     return out

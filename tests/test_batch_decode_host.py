@@ -15,7 +15,7 @@ import cpprob_amd.capi as cp
 EINVAL = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"cpprob_hip_batch_decode": 5, "cpprob_hip_batch_decode_device": 5, "cpprob_hip_batch_decode_lag": 8, "cpprob_hip_batch_decode_lag_device": 8,
-       "cpprob_hip_batch_decode_logp": 4}
+       "cpprob_hip_batch_decode_logp": 4, "cpprob_hip_batch_pass_grid": 5}
 
 
 def test_decode_symbols_are_declared_listed_and_bound():
@@ -27,7 +27,7 @@ def test_decode_symbols_are_declared_listed_and_bound():
         assert hasattr(L, s)
         assert getattr(L, s).argtypes is not None and len(getattr(L, s).argtypes) == n_args, s
     assert L.cpprob_hip_abi_version() == 3
-    for name in ("batch_decode", "batch_decode_device", "batch_decode_lag", "batch_decode_lag_device", "batch_decode_logp"):
+    for name in ("batch_decode", "batch_decode_device", "batch_decode_lag", "batch_decode_lag_device", "batch_decode_logp", "batch_pass_grid"):
         assert callable(getattr(cp.Engine, name)), name
     assert cpprob_amd.decode.hmm_table_decode is cpprob_amd.hmm_table_decode
 
@@ -46,6 +46,8 @@ def test_decode_refusals_without_a_device():
     assert L.cpprob_hip_batch_decode_logp(None, 0, lp.ctypes.data_as(C.POINTER(C.c_double)), C.byref(lp0)) == EINVAL
     assert b"ctx" in L.cpprob_hip_last_error(None)
     assert np.all(path == -5) and np.all(score == -5.0) and np.all(lp == -5.0) and lp0.value == -5.0
+    grid = [C.c_uint32(7) for _ in range(4)]
+    assert L.cpprob_hip_batch_pass_grid(None, *[C.byref(g) for g in grid]) == EINVAL and [g.value for g in grid] == [7] * 4
 
 
 def test_path_layout_is_the_smoothers_with_one_trajectory():

@@ -263,3 +263,31 @@ def test_zero_entry_is_never_taken(prog):
     _, v, path = bt.check_full(prog, bt.Ts)
     p = path[40:80]
     assert max(v[1]) > -math.inf and not np.any((p[:-1] == 0) & (p[1:] == 4))
+
+
+def test_forward_pass_resumes_across_chunk_borders(prog):
+    """A 150-step stream fed as 63 + 1 + 1 + 63 + 1 + 21 into tables addressed by capacity, decoded after every advance: the forward
+    pass resumes from the saved v row at 63, 64, 65, 128 and 129, and row 0 of the traceback walks chunks whose words were written by
+    different launches.  Problem 1 is never fed; problem 2's stream ends at 128."""
+    bt = Batch([150, 5, 128], [70, 1, 30], 5, False, 13, caps=[150, 9, 130])
+    v, words = bt.fresh()
+    lens, resumed = [0, 0, 0], []
+    for dT in (63, 1, 1, 63, 1, 21):
+        lo, lens = lens, [min(lens[0] + dT, 150), 0, min(lens[2] + dT, 128)]
+        resumed.append(lo[0])
+        words, v, sc, path = prog(bt, lens, lo, v, words, True, grid_x=1, trace=True, full=True)
+        ww, wv, ws = bt.want_words(lens)
+        assert np.array_equal(words, ww), "lengths %s: words differ" % lens
+        assert np.array_equal(v[[0, 2]], wv[[0, 2]]) and np.array_equal(sc, ws), "lengths %s" % lens
+        at = 0
+        for b, L in enumerate(lens):
+            wp, _ = D.decode(bt.m[b][:L], bt.ll[b][:L], bt.table(b), bt.lp0)
+            assert np.array_equal(path[at:at + L], wp), "problem %d resumed at %d, length %d: paths differ" % (b, lo[b], L)
+            at += L
+        for gy in (2, 3):
+            bt.check_lag(prog, lens, words, v, 3, gy)
+    assert resumed == [0, 63, 64, 65, 128, 129] and lens == [150, 0, 128]
+    one = bt.check_full(prog, lens)
+    assert np.array_equal(words, one[0]) and np.array_equal(v[[0, 2]], one[1][[0, 2]]) and np.array_equal(path, one[2])
+    carried = [int(x) for x in path[:150][[149 - 64, 149 - 128]]]
+    assert any(carried), "every state carried across a chunk border is zero: choose another seed"

@@ -12,7 +12,8 @@ import cpprob_amd.capi as cp
 
 EINVAL = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"cpprob_hip_batch_forecast": 8, "cpprob_hip_batch_forecast_device": 8, "cpprob_hip_batch_predictive": 5, "cpprob_hip_batch_predictive_device": 5}
+NEW = {"cpprob_hip_batch_forecast": 8, "cpprob_hip_batch_forecast_device": 8, "cpprob_hip_batch_predictive": 5, "cpprob_hip_batch_predictive_device": 5,
+       "cpprob_hip_batch_pass_grid": 5}
 
 
 def test_forecast_symbols_are_declared_listed_and_bound():

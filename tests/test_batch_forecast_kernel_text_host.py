@@ -205,3 +205,17 @@ def test_table_addressed_by_capacity(prog):
         bt.check_forecast(prog, lens, 3, 257)
         for gy in (1, 2):
             bt.check_predictive(prog, lens, gy)
+
+
+def test_predictive_rows_from_mid_table_in_several_trips(prog):
+    """A `from` list that starts inside the table on grids that hold fewer items than the problems owe: 131 rows from step 70 on one
+    and two grid rows (33 and 17 trips of a workgroup's four wavefronts), beside problems asked from 0, from L (one row) and from
+    L + 1 (none)."""
+    bt = Batch([200, 64, 65, 9], [70, 3, 300, 1], 5, False, 17)
+    frm = [70, 0, 65, 10]
+    one = bt.check_predictive(prog, bt.Ts, 64, frm=frm)               # (one trip: the grid holds 256 items a problem)
+    for gy in (1, 2, 5):
+        got = bt.check_predictive(prog, bt.Ts, gy, frm=frm)
+        assert np.array_equal(got, one), "gridDim.y = %d differs from the grid of one trip" % gy
+    full = bt.check_predictive(prog, bt.Ts, 3)
+    assert np.array_equal(one[0], full[0, 70:]) and np.array_equal(one[2, 0], full[2, 65]) and np.all(one[2, 1:] == 0.0) and np.all(one[3] == 0.0)

@@ -145,6 +145,10 @@ def test_fixed_lag_rows(k):
             final = [t for t in range(L) if t + lag <= L - 1]
             assert np.array_equal(short[final], rows[final])
         assert np.array_equal(D.decode_lag(words, lag, 2, 9), np.concatenate([rows[2:], np.full(4, -1, np.int32)]))
+        # the side-by-side walk is the plain one
+        assert np.array_equal(D.decode_lag_fast(words, lag), rows)
+        for frm, n_rows in ((2, 9), (0, 3), (T, 2), (T - 1, None)):
+            assert np.array_equal(D.decode_lag_fast(words, lag, frm, n_rows), D.decode_lag(words, lag, frm, n_rows))
 
 
 def test_forward_resumes_from_its_row():
@@ -155,3 +159,12 @@ def test_forward_resumes_from_its_row():
         w1, v1 = D.forward(m[:cut], ll[:cut], lp, lp0)
         w2, v2 = D.forward(m, ll, lp, lp0, v1, cut)
         assert np.array_equal(np.concatenate([w1, w2[cut:]]), words) and v2 == v
+
+
+def test_side_by_side_walk_on_long_rows():
+    """Random words of 300 steps (any word is a valid table of back pointers): lags across the 64-word chunk, rows from inside."""
+    rng = np.random.default_rng(77)
+    words = rng.integers(0, 1 << 27, 300).astype(np.uint32)
+    for lag in (0, 2, 63, 64, 65, 299, 300, 1000):
+        for frm, n_rows in ((0, None), (70, None), (0, 310), (299, 4)):
+            assert np.array_equal(D.decode_lag_fast(words, lag, frm, n_rows), D.decode_lag(words, lag, frm, n_rows)), (lag, frm, n_rows)

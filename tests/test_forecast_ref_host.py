@@ -98,6 +98,8 @@ def test_simulated_futures_follow_the_marginals(problem):
     assert np.all(np.abs(np.bincount(traj[0], minlength=k) / float(M) - np.array(F.start(m[-1]))) <= 0.05)
     assert not np.array_equal(traj, F.trajectories(m, thr, seed, H, M, draw_index=3))
     assert np.array_equal(traj[:, :33], F.trajectories(m, thr, seed, H, 33, draw_index=2))       # (n_traj is a bound only)
+    cols = [4095, 0, 1, 1023, 1024, 7, 6, 4094, 7]                 # (both halves of a block, one half alone, any order, one twice)
+    assert np.array_equal(traj[:, cols], F.trajectories(m, thr, seed, H, M, draw_index=2, columns=cols))
 
 
 def test_a_zero_transition_entry_is_never_taken():

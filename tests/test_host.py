@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, "include", "cpprob_hip.h")).read()
     declared = sorted(set(re.findall(r"\b(cpprob_hip_[a-z0-9_]+)\s*\(", hdr)))
     assert len(declared) >= 35
-    assert "cpprob_hip_batch_smooth_grid" in declared
+    assert "cpprob_hip_batch_smooth_grid" in declared and "cpprob_hip_batch_pass_grid" in declared
     assert sorted(cpprob_amd.capi.SYMBOLS) == declared
     out = subprocess.check_output(["nm", "-D", "--defined-only", cpprob_amd.capi.LIB_PATH]).decode()
     exported = set(re.findall(r" T (cpprob_hip_\w+)", out))
