@@ -44,6 +44,7 @@ SYMBOLS = [
     "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
     "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device", "cpprob_hip_batch_smooth_grid",
     "cpprob_hip_batch_smooth_stats", "cpprob_hip_batch_smooth_stats_device",
+    "cpprob_hip_batch_traj_stats", "cpprob_hip_batch_traj_stats_device", "cpprob_hip_batch_traj_stats_grid",
     "cpprob_hip_batch_forecast", "cpprob_hip_batch_forecast_device", "cpprob_hip_batch_predictive", "cpprob_hip_batch_predictive_device",
     "cpprob_hip_batch_decode", "cpprob_hip_batch_decode_device", "cpprob_hip_batch_decode_lag", "cpprob_hip_batch_decode_lag_device",
     "cpprob_hip_batch_decode_logp", "cpprob_hip_batch_pass_grid",
@@ -189,10 +190,22 @@ DECODE_MAX_LAG = 1 << 24                      # cpprob_hip_batch_decode_lag: lag
 STATS_PER_PROBLEM = 88                        # doubles a problem of cpprob_hip_batch_smooth_stats: xi[8][8], occ[8], occ_y[8], occ_yy[8]
 
 
+TRAJ_STATS_TILE = 256                         # trajectories a workgroup of cpprob_hip_batch_traj_stats: its grid holds ceil(n_traj / this) tiles a problem
+TRAJ_STATS_MAX_TRAJ, TRAJ_STATS_MAX_DRAWS = 1 << 20, 1 << 16     # cpprob_hip_batch_traj_stats: n_traj in 1 ..=, draw_index <
+
+
 def split_stats(rec):
     """The records [B, 88] of cpprob_hip_batch_smooth_stats as a dict of views: xi [B, 8, 8], occ, occ_y, occ_yy [B, 8]."""
     rec = np.asarray(rec).reshape(-1, STATS_PER_PROBLEM)
     return {"xi": rec[:, :64].reshape(-1, 8, 8), "occ": rec[:, 64:72], "occ_y": rec[:, 72:80], "occ_yy": rec[:, 80:88]}
+
+
+def split_traj_stats(rec):
+    """The records [B, n_traj, 88] of cpprob_hip_batch_traj_stats as a dict of views: xi [B, n_traj, 8, 8], occ, occ_y, occ_yy
+    [B, n_traj, 8]."""
+    rec = np.asarray(rec)
+    B, M = rec.shape[0], rec.shape[1]
+    return {"xi": rec[:, :, :64].reshape(B, M, 8, 8), "occ": rec[:, :, 64:72], "occ_y": rec[:, :, 72:80], "occ_yy": rec[:, :, 80:88]}
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -344,6 +357,9 @@ def load_library(path=None):
         "cpprob_hip_batch_smooth_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "cpprob_hip_batch_smooth_stats": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_traj_stats": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_traj_stats_device": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
+        "cpprob_hip_batch_traj_stats_grid": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "cpprob_hip_batch_forecast": (C.c_int, [vp, u64, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_forecast_device": (C.c_int, [vp, u64, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_predictive": (C.c_int, [vp, C.POINTER(C.c_uint32), u64, vp, sz]),
@@ -770,6 +786,43 @@ class Engine:
         """The same left in a device tensor, enqueued behind the run / advance without a host synchronisation: stats torch float64
         [B, 88] (split_stats names its columns), observes a torch float64 tensor packed as above or None."""
         self._chk(self.L.cpprob_hip_batch_smooth_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    @staticmethod
+    def _traj_stats_args(n_traj, draw_index):
+        """The ranges cpprob_hip_batch_traj_stats refuses, checked before anything is allocated."""
+        n_traj, draw_index = int(n_traj), int(draw_index)
+        if not 1 <= n_traj <= TRAJ_STATS_MAX_TRAJ:
+            raise ValueError("n_traj must lie in 1 .. 2^20")
+        if not 0 <= draw_index < TRAJ_STATS_MAX_DRAWS:
+            raise ValueError("draw_index must lie in 0 .. 2^16 - 1")
+        return n_traj, draw_index
+
+    def batch_traj_stats(self, n_traj, draw_index=0, observes=None):
+        """Complete-data sufficient statistics of backward-simulated trajectories (cpprob_hip_batch_traj_stats), counted on the
+        device: a dict of xi [B, n_traj, 8, 8] (transitions s -> s' of the trajectory), occ [B, n_traj, 8] (visits), occ_y and occ_yy
+        [B, n_traj, 8] (the sums of y_t and y_t^2 over the visits; zero without observes).  Trajectory j of problem b is column j of
+        batch_smooth(n_traj, draw_index)'s trajectories; it is not stored.  observes: as batch_smooth_stats takes them.
+        cpprob_amd.gibbs samples the tables from these records."""
+        n_traj, draw_index = self._traj_stats_args(n_traj, draw_index)
+        rec = np.zeros((self.batch_B, n_traj, STATS_PER_PROBLEM))
+        flat = None if observes is None else self._batch_packed_observes(observes)
+        self._chk(self.L.cpprob_hip_batch_traj_stats(self.h, n_traj, draw_index, None if flat is None or flat.size == 0 else flat.ctypes.data,
+                                                     0 if flat is None else flat.size, rec.ctypes.data, rec.size))
+        return split_traj_stats(rec)
+
+    def batch_traj_stats_device(self, stats, n_traj, draw_index=0, observes=None):
+        """The same left in a device tensor, enqueued behind the run / advance without a host synchronisation: stats torch float64
+        [B, n_traj, 88] (split_traj_stats names its columns), observes a torch float64 tensor packed as above or None."""
+        n_traj, draw_index = self._traj_stats_args(n_traj, draw_index)
+        self._chk(self.L.cpprob_hip_batch_traj_stats_device(self.h, n_traj, draw_index, _dptr(observes), 0 if observes is None else observes.numel(),
+                                                            _dptr(stats), stats.numel()))
+
+    def batch_traj_stats_grid(self):
+        """gridDim.y of the last trajectory statistics launch (cpprob_hip_batch_traj_stats_grid): the tiles of TRAJ_STATS_TILE
+        trajectories a problem, 0 where none happened."""
+        gy = C.c_uint32(0)
+        self._chk(self.L.cpprob_hip_batch_traj_stats_grid(self.h, C.byref(gy)))
+        return int(gy.value)
 
     @staticmethod
     def _forecast_args(horizon, n_traj, draw_index):

@@ -23,6 +23,7 @@
 #include "batch_paths.hpp"
 #include "batch_smooth.hpp"
 #include "batch_suffstats.hpp"
+#include "batch_trajstats.hpp"
 #include "batch_forecast.hpp"
 #include "batch_decode.hpp"
 
@@ -1087,6 +1088,7 @@ struct BatchState {
     unsigned smooth_gy_count = 0, smooth_gy_lag = 0;        // gridDim.y of the last smoothing call's counting and lag launches (0: none)
     // of the last decode / forecast / predictive call: gridDim.x of the forward launch, gridDim.y of the trace, forecast and predictive launches (0: none)
     unsigned decode_gx_forward = 0, decode_gy_trace = 0, forecast_gy = 0, predictive_gy = 0;
+    unsigned traj_stats_gy = 0;                             // gridDim.y of the last trajectory statistics launch (0: none)
     // decoding (cpprob_hip_batch_decode*; csrc/batch_decode.hpp): the step words (addressed as the m table's rows: an online batch's by
     // capacity, kept), the v rows [B][8] and the log tables ([tables][64], computed on the host at the first call after a begin and
     // uploaded once), allocations of the context's own; decoded: [B], online batch: its words [0, decoded_b) and its v row are valid
@@ -4476,7 +4478,7 @@ int cpprob_hip_batch_smooth_layout(const uint32_t* h_T, uint64_t n_problems, uin
 static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, bool with_marg, size_t n_doubles, bool with_traj, size_t n_entries, uint64_t& doubles, uint64_t& entries)
 {
     BatchState* bs = c->batch;
-    if (bs) bs->smooth_gy_count = bs->smooth_gy_lag = bs->decode_gx_forward = bs->decode_gy_trace = bs->forecast_gy = bs->predictive_gy = 0;
+    if (bs) bs->smooth_gy_count = bs->smooth_gy_lag = bs->decode_gx_forward = bs->decode_gy_trace = bs->forecast_gy = bs->predictive_gy = bs->traj_stats_gy = 0;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
     if (bs->cfg.keep_history != 1 && !batch_masses(&bs->cfg)) return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no particle store");
     if (draw_index >= (uint64_t)kBackwardMaxDraws) return fail(c, CPPROB_HIP_EINVAL, "draw_index must lie in 0 .. 2^16 - 1");
@@ -4497,6 +4499,9 @@ static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_
 struct BatchSmoothLag { uint64_t lag; const uint32_t* from; uint64_t n_rows; };
 // A statistics call's own (cpprob_hip_batch_smooth_stats): the observes (or nullptr) and the records, both on the device.
 struct BatchSmoothStats { const double* d_obs; double* d_stats; };
+// A trajectory statistics call's own (cpprob_hip_batch_traj_stats): the observes (or nullptr) and the records [B][n_traj][88], on the device.
+struct BatchTrajStats { const double* d_obs; double* d_stats; };
+static_assert(kTrajStats == kSuffStats, "a trajectory's record has the layout of a problem's expected statistics");
 // A forecast call's own (cpprob_hip_batch_forecast: horizon > 0; cpprob_hip_batch_predictive: horizon = 0, the first rows wanted and
 // the rows a problem of the output).
 struct BatchForecast { uint64_t horizon; const uint32_t* from; uint64_t n_rows; };
@@ -4509,12 +4514,14 @@ static int batch_decode_prepare(cpprob_hip_ctx* c, size_t word_rows);
 // slot it writes (the copy that read it kOnlineSlots calls ago) and, where a buffer of its own has to grow, for the calls before it.
 // An online batch's m table is addressed by capacity and kept: the pass counts rows [counted_b, L_b) and moves the watermark.
 // st: the smoothing pass is batch_smooth_stats_kernel (csrc/batch_suffstats.hpp) and nothing else is written.
+// ts: the smoothing pass is batch_traj_stats_kernel (csrc/batch_trajstats.hpp) and nothing else is written.
 // fc: the pass after the counting is batch_forecast_kernel or batch_predictive_kernel (csrc/batch_forecast.hpp); a run batch counts
 // row L - 1 (the forecast) or rows max(from_b, 1) - 1 .. L - 1 (the predictive rows) only.
 // dc: the passes after the counting are batch_decode_forward_kernel and batch_decode_trace_kernel (csrc/batch_decode.hpp); an online
 // batch's words are kept as its m table is: the forward pass walks steps [decoded_b, L_b) and moves that watermark.
 static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr,
-                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr, const BatchDecode* dc = nullptr)
+                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr, const BatchDecode* dc = nullptr,
+                                const BatchTrajStats* ts = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
@@ -4529,12 +4536,13 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     size_t rows = 0, reached = 0;
     for (size_t b = 0; b < B; ++b) { reached += (size_t)bs->prob[b].T; rows += bs->online ? (size_t)bs->cap_T[b] : (size_t)bs->prob[b].T; }
     if (st && reached == 0) HIP_TRY(c, hipMemsetAsync(st->d_stats, 0, B * (size_t)kSuffStats * sizeof(double), c->stream));
+    if (ts && reached == 0) HIP_TRY(c, hipMemsetAsync(ts->d_stats, 0, B * (size_t)n_traj * (size_t)kTrajStats * sizeof(double), c->stream));
     // a forecast before the first observes: rows of zeros; the predictive row 0 needs no row of the table and goes on
     if (fc && !predictive && reached == 0 && with_traj) HIP_TRY(c, hipMemsetAsync(d_traj, 0, B * (size_t)(fc->horizon + 1) * (size_t)n_traj, c->stream));
     // a decode: a problem of length 0 has score 0; the fixed-lag rows no step owns are -1 (0 is a state)
     if (dc && dc->d_score) HIP_TRY(c, hipMemsetAsync(dc->d_score, 0, B * sizeof(double), c->stream));
     if (dc && !dc->full && dc->d_path && dc->n_rows) HIP_TRY(c, hipMemsetAsync(dc->d_path, 0xff, B * (size_t)dc->n_rows, c->stream));
-    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st && !dc)) return 0;   // (an online batch before its first observes, or nothing asked for)
+    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st && !dc && !ts)) return 0;   // (an online batch before its first observes, or nothing asked for)
     const size_t word_rows = kept ? B * (size_t)bs->T : rows;
     if (kept) rows = 0;
     if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
@@ -4666,6 +4674,18 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         sa.B = (int)B; sa.k = a.k; sa.thr_stride = a.thr_stride;
         hipLaunchKernelGGL(batch_smooth_stats_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, sa);
         HIP_TRY(c, hipGetLastError());
+        return 0;
+    }
+    if (ts) {
+        BatchTrajStatsArgs ta{};
+        ta.desc = a.desc; ta.mass = a.mass; ta.thr = a.thr; ta.seeds = a.seeds; ta.obs = ts->d_obs; ta.stats = ts->d_stats;
+        ta.draw_base = a.draw_base; ta.k = a.k; ta.thr_stride = a.thr_stride; ta.n_traj = (int)n_traj; ta.lds_bytes = a.lds_bytes;
+        // a lane a trajectory: the tiles cover n_traj, a problem of length 0 writes its zero records
+        const unsigned gy = (unsigned)((n_traj + kTrajStatsTile - 1) / kTrajStatsTile);
+        if (hmm3) hipLaunchKernelGGL(batch_traj_stats_kernel<3>, dim3((unsigned)B, gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, ta);
+        else hipLaunchKernelGGL(batch_traj_stats_kernel<8>, dim3((unsigned)B, gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, ta);
+        HIP_TRY(c, hipGetLastError());
+        bs->traj_stats_gy = gy;
         return 0;
     }
     if (lg && !a.traj) return 0;
@@ -4828,6 +4848,62 @@ int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* c, const double* h_observes, s
     if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const BatchSmoothStats st{d_obs, d_stats};
     if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, &st)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// cpprob_hip_batch_traj_stats' arguments against the batch's state (batch_smooth_check first).
+static int batch_traj_stats_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, bool with_obs, size_t n_observes, const double* stats, size_t n_doubles,
+                                  uint64_t& rows, uint64_t& need)
+{
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, n_traj, draw_index, false, 0, false, 0, doubles, entries)) return rc;
+    if (n_traj == 0) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 1 .. 2^20");
+    if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    if (with_obs && (uint64_t)n_observes != rows)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    need = (uint64_t)bs->cfg.n_problems * n_traj * (uint64_t)kTrajStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a trajectory, n_problems * n_traj of them)");
+    return 0;
+}
+
+int cpprob_hip_batch_traj_stats_device(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, const double* d_observes, size_t n_observes, double* d_stats,
+                                       size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t rows = 0, need = 0;
+    if (int rc = batch_traj_stats_check(c, n_traj, draw_index, d_observes != nullptr, n_observes, d_stats, n_doubles, rows, need)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const BatchTrajStats ts{rows ? d_observes : nullptr, d_stats};
+    return batch_smooth_enqueue(c, n_traj, draw_index, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ts);
+}
+
+int cpprob_hip_batch_traj_stats(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t rows = 0, need = 0;
+    if (int rc = batch_traj_stats_check(c, n_traj, draw_index, h_observes != nullptr, n_observes, h_stats, n_doubles, rows, need)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchState* bs = c->batch;
+    // device staging: the records in front of the observes
+    const size_t s_bytes = (size_t)need * sizeof(double), bytes = s_bytes + (h_observes ? (size_t)rows * sizeof(double) : 0);
+    if (bytes > bs->stage_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, bytes));
+        bs->stage_cap = bytes;
+    }
+    double* d_stats = reinterpret_cast<double*>(bs->d_stage);
+    double* d_obs = h_observes && rows ? reinterpret_cast<double*>(bs->d_stage + s_bytes) : nullptr;
+    if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const BatchTrajStats ts{d_obs, d_stats};
+    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ts)) return rc;
     HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -5105,6 +5181,14 @@ int cpprob_hip_batch_smooth_grid(cpprob_hip_ctx* c, uint32_t* count_grid_y, uint
     if (!count_grid_y || !lag_grid_y) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     *count_grid_y = c->batch ? c->batch->smooth_gy_count : 0u;
     *lag_grid_y = c->batch ? c->batch->smooth_gy_lag : 0u;
+    return 0;
+}
+
+int cpprob_hip_batch_traj_stats_grid(cpprob_hip_ctx* c, uint32_t* grid_y)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    if (!grid_y) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    *grid_y = c->batch ? c->batch->traj_stats_gy : 0u;
     return 0;
 }
 

@@ -155,6 +155,23 @@ void print_decodes(const std::vector<cpprob::gpu::Result>& res)
     }
 }
 
+// --trajectory_stats M [--draw_index D], after everything else of the batch (in --json mode too): M lines a problem in problem order,
+// line j the record of its backward-simulated trajectory j, "[xi k x k row-major] [occ] [occ_y] [occ_yy]" over the first k states
+void print_trajectory_stats(const std::vector<cpprob::gpu::Result>& res, std::size_t k)
+{
+    for (const cpprob::gpu::Result& r : res)
+        for (const std::vector<double>& rec : r.trajectory_stats) {
+            std::cout << "[";
+            for (std::size_t s = 0; s < k; ++s)
+                for (std::size_t j = 0; j < k; ++j) std::cout << (s + j ? " " : "") << rec[8 * s + j];
+            for (std::size_t part = 0; part < 3; ++part) {
+                std::cout << "] [";
+                for (std::size_t s = 0; s < k; ++s) std::cout << (s ? " " : "") << rec[64 + 8 * part + s];
+            }
+            std::cout << "]" << std::endl;
+        }
+}
+
 // --batch_observes_file F: one observation sequence a line, all run as ONE batch (cpprob::gpu::inference_batch, smc, built-in HMMs);
 // problem i (line i) runs with seed --seed + i; one estimate a line: log-evidence, then P(x_t = s) row by row (--json: one JSON object a line)
 template <class F>
@@ -184,6 +201,7 @@ int execute_batch(const F& model, const Args& a)
     }
     if (!a.json) print_forecasts(res);
     if (!a.json) print_decodes(res);
+    print_trajectory_stats(res, res.empty() || res[0].predicts.empty() ? 8 : res[0].predicts[0].probabilities.size());
     cpprob::gpu::release_device_resources();
     return EXIT_SUCCESS;
 }
@@ -259,6 +277,7 @@ int execute_batch_tables(const Args& a)
         for (std::size_t i = 0; i < t.transition.size(); ++i) std::cout << (i ? " " : "") << t.transition[i];
         std::cout << "]" << std::endl;
     }
+    print_trajectory_stats(res, k);
     cpprob::gpu::release_device_resources();
     return EXIT_SUCCESS;
 }
@@ -322,6 +341,8 @@ int main(int argc, char** argv)
         else if (f == "--smoothing_lag") opt.smoothing_lag = std::stol(next());    // the batch modes: fixed-lag marginals (cpprob_hip_batch_smooth_lag)
         else if (f == "--decode") opt.map_decode = true;                           // the batch modes: the most probable state path (cpprob_hip_batch_decode)
         else if (f == "--decode_lag") opt.decode_lag = std::stol(next());          // ... its fixed-lag rows instead (cpprob_hip_batch_decode_lag)
+        else if (f == "--trajectory_stats") opt.trajectory_stats = std::stoull(next());   // the batch modes: the records of this many backward-simulated trajectories a problem (cpprob_hip_batch_traj_stats)
+        else if (f == "--draw_index") opt.trajectory_stats_draw_index = std::stoull(next());   // ... under this draw index
         else if (f == "--forecast") opt.forecast_horizon = std::stoull(next());   // the batch modes: the state's laws this many steps ahead (cpprob_hip_batch_forecast)
         else if (f == "--forecast_trajectories") opt.forecast_trajectories = std::stoull(next());   // ... and this many simulated futures a problem
         else if (f == "--backward_trajectories") opt.backward_trajectories = std::stoull(next());   // ... and --batch_dump writes this many backward-simulated trajectories
@@ -358,6 +379,14 @@ int main(int argc, char** argv)
     }
     if ((opt.map_decode || opt.decode_lag >= 0) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
         std::cerr << "--decode serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (opt.trajectory_stats && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
+        std::cerr << "--trajectory_stats serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (opt.trajectory_stats && !opt.keep_history && !opt.keep_masses) {
+        std::cerr << "--trajectory_stats reads the smoother's masses: with --filtering_only set --keep_masses" << std::endl;
         return EXIT_FAILURE;
     }
     if (opt.decode_lag >= 0 && !opt.map_decode) { std::cerr << "--decode_lag delays a decode: set --decode" << std::endl; return EXIT_FAILURE; }

@@ -1,0 +1,63 @@
+"""A batched Gibbs sampler for the tables of MODEL_HMM_TABLE problems, the Bayesian counterpart of cpprob_amd.em: one chain a problem.
+A sweep draws one state trajectory a chain on the device and reads only its complete-data sufficient statistics
+(Engine.batch_traj_stats, 88 doubles a chain); the tables are then drawn on the host from their conjugate posteriors.  The model fixes
+the emission's sigma at 1, so a table is its means and its transition rows; the initial state is uniform and not sampled."""
+import numpy as np
+
+from .capi import MODEL_HMM_TABLE, RESAMPLE_SYSTEMATIC
+
+
+def sample_tables(stats, k, rng, alpha=1.0, mu0=0.0, tau0=10.0):
+    """One draw of the tables given one trajectory's statistics a problem (`stats`: the dict Engine.batch_traj_stats returns with the
+    trajectory axis indexed away -- xi [B, 8, 8], occ, occ_y [B, 8]).  Priors: every transition row Dirichlet(alpha, .., alpha), every
+    mean N(mu0, tau0^2); sigma is 1 as the model fixes it, so both posteriors are conjugate:
+      G = rng.standard_gamma(alpha + xi[:, :k, :k]) (one call), trans = G / G.sum(-1, keepdims=True)
+      z = rng.standard_normal((B, k)) (one call, after G), prec = 1 / tau0^2 + occ[:, :k],
+      means = (mu0 / tau0^2 + occ_y[:, :k]) / prec + z / sqrt(prec)
+    Pure numpy; returns (means [B, k], trans [B, k, k])."""
+    k = int(k)
+    xi, occ, occ_y = (np.asarray(stats[f], np.float64) for f in ("xi", "occ", "occ_y"))
+    if xi.ndim != 3 or occ.ndim != 2 or occ_y.ndim != 2 or not xi.shape[0] == occ.shape[0] == occ_y.shape[0]:
+        raise ValueError("one record of statistics per problem: xi [B, 8, 8], occ and occ_y [B, 8]")
+    xi, occ, occ_y = xi[:, :k, :k], occ[:, :k], occ_y[:, :k]
+    G = rng.standard_gamma(alpha + xi)
+    trans = G / G.sum(-1, keepdims=True)
+    z = rng.standard_normal((xi.shape[0], k))
+    prec = 1 / tau0**2 + occ
+    means = (mu0 / tau0**2 + occ_y) / prec + z / np.sqrt(prec)
+    return means, trans
+
+
+def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps, rng, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, **prior):
+    """Batched Gibbs sampling of the tables, one chain a problem.  observes: a list of B 1-D sequences, or one sequence every chain
+    shares; means0 [B, k], trans0 [B, k, k] the chains' initial tables; seeds [B]; rng a numpy Generator; prior: sample_tables' alpha,
+    mu0, tau0.  Sweep i begins a batch with the current tables (batch_begin_problems), runs it with seeds + i, takes the statistics of
+    one backward-simulated trajectory a chain (batch_traj_stats(1, draw_index=i % 2^16, observes)) and draws the next tables with
+    sample_tables.  Returns (means [sweeps + 1, B, k], trans [sweeps + 1, B, k, k], log_evidence [sweeps, B]): the tables before every
+    sweep and after the last, and the log-evidence estimate of every sweep's run (of the tables it began with).  keep_history=False:
+    the batches are filtering-only and keep the smoother's masses (keep_masses) -- the same chain bit for bit, without a particle store.
+
+    The trajectory comes from the particle approximation of forward filtering / backward sampling: it is drawn from the n_particles
+    filtering approximations of the run, not from the exact smoothing law.  The chain's invariant law is therefore the posterior only
+    up to the particle filter's error in n_particles (it vanishes as n_particles grows).  This is NOT a particle-Gibbs kernel with a
+    retained path (conditional SMC): nothing here corrects that error at finite n_particles."""
+    means = np.array(means0, np.float64)
+    trans = np.array(trans0, np.float64)
+    B, k = means.shape
+    if isinstance(observes, np.ndarray) and observes.ndim == 1:
+        observes = [observes] * B
+    seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in observes]
+    if len(seqs) != B:
+        raise ValueError("one sequence per table (or one for all)")
+    sd = np.ascontiguousarray(seeds, np.uint64)
+    m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(sweeps), B))
+    for i in range(int(sweeps)):
+        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), resampler=resampler, keep_history=bool(keep_history),
+                                    keep_masses=not keep_history)
+        engine.batch_run(sd + np.uint64(i))
+        stats = engine.batch_traj_stats(1, draw_index=i % (1 << 16), observes=seqs)
+        ev[i] = [s["log_evidence"] for s in engine.batch_results()[0]]
+        means, trans = sample_tables({name: v[:, 0] for name, v in stats.items()}, k, rng, **prior)
+        m_hist.append(means.copy())
+        t_hist.append(trans.copy())
+    return np.array(m_hist), np.array(t_hist), ev

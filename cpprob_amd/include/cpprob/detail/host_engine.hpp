@@ -647,6 +647,33 @@ inline void batch_forecast_results(Context& ctx, std::size_t H, std::size_t M, s
     }
 }
 
+// ---- trajectory sufficient statistics of a batch (cpprob_hip_batch_traj_stats): Options::trajectory_stats, ::trajectory_stats_draw_index ----
+// What the C ABI would refuse, refused before a batch is begun.  stored: the batch keeps its history or its masses.
+inline void check_trajectory_stats_options(const std::string& who, std::size_t M, std::uint64_t draw_index, bool stored)
+{
+    if (!M) return;
+    if (M > (std::size_t(1) << 20)) throw std::runtime_error(who + ": options().trajectory_stats must lie in 0 .. 2^20");
+    if (draw_index >= (std::uint64_t(1) << 16)) throw std::runtime_error(who + ": options().trajectory_stats_draw_index must lie below 2^16");
+    if (!stored)
+        throw std::runtime_error(who + ": options().trajectory_stats reads the smoother's masses: a filtering-only run (options().keep_history = false) keeps none without options().keep_masses");
+}
+
+// The records of M trajectories a problem of the batch last run or advanced on ctx into its results; observes: the problems'
+// sequences packed by the lengths reached.
+inline void batch_trajectory_stats_results(Context& ctx, std::size_t M, std::uint64_t draw_index, const std::vector<double>& observes, std::vector<Result>& out)
+{
+    if (!M) return;
+    const std::size_t B = out.size(), R = 88;
+    std::vector<double> rec(B * M * R);
+    ctx.check(cpprob_hip_batch_traj_stats(ctx.get(), M, draw_index, observes.empty() ? nullptr : observes.data(), observes.size(), rec.data(), rec.size()),
+              "cpprob_hip_batch_traj_stats");
+    for (std::size_t b = 0; b < B; ++b) {
+        out[b].trajectory_stats.resize(M);
+        for (std::size_t j = 0; j < M; ++j)
+            out[b].trajectory_stats[j].assign(rec.begin() + static_cast<std::ptrdiff_t>((b * M + j) * R), rec.begin() + static_cast<std::ptrdiff_t>((b * M + j + 1) * R));
+    }
+}
+
 // ---- decoding a batch (cpprob_hip_batch_decode, _decode_lag): Options::map_decode, ::decode_lag ---------------------------------------
 // What the C ABI would refuse, refused before a batch is begun.  stored: the batch keeps its history or its masses.
 inline void check_decode_options(const std::string& who, bool decode, long lag, bool stored)
@@ -736,6 +763,7 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
         throw std::runtime_error("cpprob::gpu::inference_batch: fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     check_forecast_options("cpprob::gpu::inference_batch", opt.forecast_horizon, opt.forecast_trajectories, opt.keep_history || masses);
     check_decode_options("cpprob::gpu::inference_batch", opt.map_decode, opt.decode_lag, opt.keep_history || masses);
+    check_trajectory_stats_options("cpprob::gpu::inference_batch", opt.trajectory_stats, opt.trajectory_stats_draw_index, opt.keep_history || masses);
     ContextLease lease(opt.device);
     Context& ctx = *lease;
     cpprob_hip_batch_config bc{};
@@ -767,6 +795,7 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
     std::vector<Result> out(B);
     batch_forecast_results(ctx, opt.forecast_horizon, opt.forecast_trajectories, K, K, out);
     batch_decode_results(ctx, opt.map_decode, opt.decode_lag, std::vector<std::uint32_t>(B, static_cast<std::uint32_t>(T)), out);
+    batch_trajectory_stats_results(ctx, opt.trajectory_stats, opt.trajectory_stats_draw_index, flat, out);
     lease.done();
     for (std::size_t b = 0; b < B; ++b) {
         Result& r = out[b];
@@ -828,6 +857,7 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
         throw std::runtime_error(who + ": fixed-lag smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
     check_forecast_options(who, opt.forecast_horizon, opt.forecast_trajectories, opt.keep_history || masses);
     check_decode_options(who, opt.map_decode, opt.decode_lag, opt.keep_history || masses);
+    check_trajectory_stats_options(who, opt.trajectory_stats, opt.trajectory_stats_draw_index, opt.keep_history || masses);
     return pk;
 }
 
@@ -880,6 +910,7 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
     }
     batch_forecast_results(ctx, opt.forecast_horizon, opt.forecast_trajectories, K, k, out);
     batch_decode_results(ctx, decode && opt.map_decode, opt.decode_lag, T, out);
+    batch_trajectory_stats_results(ctx, opt.trajectory_stats, opt.trajectory_stats_draw_index, pk.flat, out);
     return out;
 }
 
@@ -968,6 +999,9 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // ::map_score); with options().decode_lag = lag >= 0 the path holds the fixed-lag rows instead -- row t is final once lag more
 // observes have arrived --, an advance asks for the rows from max(0, L_before - lag) on and the object keeps the final ones.  The
 // forward work of an advance is that of its new steps either way.
+// options().trajectory_stats = M > 0: every advance's results carry the records of M backward-simulated trajectories of the lengths
+// reached (Result::trajectory_stats; the object keeps the observes seen so far for their occ_y and occ_yy); a problem without
+// observes has zero records.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -979,6 +1013,7 @@ public:
         if (B_ == 0) throw std::runtime_error("cpprob::gpu::HmmTableStream: no problems (one seed per problem)");
         check_forecast_options("cpprob::gpu::HmmTableStream", forecast_H_, forecast_M_, keep_ || masses_);
         check_decode_options("cpprob::gpu::HmmTableStream", decode_, decode_lag_, keep_ || masses_);
+        check_trajectory_stats_options("cpprob::gpu::HmmTableStream", traj_stats_M_, traj_stats_draw_, keep_ || masses_);
         if (!keep_ && !masses_ && backward_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         if (!keep_ && !masses_ && lag_ >= 0)
@@ -1018,6 +1053,7 @@ public:
         lease_.done();
         if (lag_ >= 0) { lagged_.assign(B_ * T_max_ * 8, 0.0); L_prev_.assign(B_, 0); }
         if (decode_ && decode_lag_ >= 0) { decoded_.assign(B_ * T_max_, -1); dec_prev_.assign(B_, 0); }
+        if (traj_stats_M_) seen_.resize(B_);
     }
     HmmTableStream(const HmmTableStream&) = delete;
     HmmTableStream& operator=(const HmmTableStream&) = delete;
@@ -1096,6 +1132,14 @@ public:
                 out[b].map_path.assign(decoded_.begin() + static_cast<std::ptrdiff_t>(b * T_max_), decoded_.begin() + static_cast<std::ptrdiff_t>(b * T_max_ + L[b]));
             }
         } else batch_decode_results(ctx, decode_, -1, L, out);
+        if (traj_stats_M_) {
+            std::vector<double> seen;
+            for (std::size_t b = 0; b < B_; ++b) {
+                seen_[b].insert(seen_[b].end(), new_observes[b].begin(), new_observes[b].end());
+                seen.insert(seen.end(), seen_[b].begin(), seen_[b].end());
+            }
+            batch_trajectory_stats_results(ctx, traj_stats_M_, traj_stats_draw_, seen, out);
+        }
         return out;
     }
 
@@ -1123,6 +1167,9 @@ private:
     long decode_lag_ = options().decode_lag;
     std::vector<std::int32_t> decoded_;        // decode_lag: [B][T_max], the fixed-lag rows so far (rows below L - lag are final)
     std::vector<std::size_t> dec_prev_;        // ... and the lengths they stand for
+    std::size_t traj_stats_M_ = options().trajectory_stats;
+    std::uint64_t traj_stats_draw_ = options().trajectory_stats_draw_index;
+    std::vector<std::vector<double>> seen_;    // trajectory_stats: [b] = problem b's observes so far
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

@@ -43,6 +43,10 @@ struct Options {
                                                       // the state 1 .. forecast_horizon steps past the last observe, P(x_{L-1+h} | y_0 .. y_{L-1})
                                                       // (cpprob_hip_batch_forecast); HmmTableStream: after every advance.  0: off
     std::size_t forecast_trajectories = 0;            // ... and, not 0, Result::forecast_trajectories: this many simulated futures (draw_index 0)
+    std::size_t trajectory_stats = 0;                 // batched runs (keep_history, or keep_masses): not 0 = every result carries Result::trajectory_stats, the
+                                                      // complete-data sufficient statistics of this many backward-simulated trajectories, counted on the
+                                                      // device (cpprob_hip_batch_traj_stats); HmmTableStream: after every advance.  0: off
+    std::uint64_t trajectory_stats_draw_index = 0;    // ... under this draw_index (< 2^16): the trajectories are cpprob_hip_batch_smooth's for it
     bool map_decode = false;                          // batched runs (keep_history, or keep_masses): every result carries Result::map_path, the single most
                                                       // probable state sequence given the observes over the states the particles occupy, and
                                                       // Result::map_score (cpprob_hip_batch_decode); hmm_table_fit decodes under the fitted tables
@@ -105,6 +109,8 @@ struct Result {
     std::vector<double> step_ess;             // smc: ESS after each observe
     std::vector<std::vector<double>> forecast;                      // Options::forecast_horizon: [h - 1][s] = P(x_{L-1+h} = s | y_0 .. y_{L-1}), h = 1 .. horizon
     std::vector<std::vector<std::int32_t>> forecast_trajectories;   // Options::forecast_trajectories: [j][h], future j's states; h = 0 is the present state
+    std::vector<std::vector<double>> trajectory_stats;              // Options::trajectory_stats: [j] = trajectory j's record of 88 doubles -- xi at 8 s + s' (transitions
+                                                                    // s -> s'), then occ[8], occ_y[8], occ_yy[8]
     bool map_decoded = false;                 // Options::map_decode: the two fields below are set
     std::vector<std::int32_t> map_path;       // [t]: the most probable state path (Options::decode_lag >= 0: the fixed-lag rows)
     double map_score = 0;                     // the log joint density of the full decode's path and the observes; 0 without observes

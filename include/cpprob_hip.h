@@ -490,6 +490,35 @@ int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* ctx, const double* h_observes,
 /* The same between device buffers, enqueued on the context's stream after the run / advance, no host synchronisation. */
 int cpprob_hip_batch_smooth_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
 
+/* Trajectory sufficient statistics of a batch (csrc/batch_trajstats.hpp): the complete-data statistics of backward-simulated
+ * trajectories, counted on the device while they are drawn -- what a Gibbs sweep over a table, a stochastic EM step or a
+ * posterior-predictive check reads of a trajectory.  Trajectory j of problem b under draw_index is exactly column j of
+ * cpprob_hip_batch_smooth's trajectories for that draw_index (the same start rule, the same pick, the Philox block
+ * draw_block(seed_b, j >> 1, 2^41 + (draw_index << 24) + t), word pair j & 1) and does not depend on n_traj; it is not stored.  With
+ * x_0 .. x_{T-1} the trajectory, T = T_b the length reached and y_t the observes, walking t = T - 1 .. 0:
+ *   xi[s][s'] = #{t < T - 1 : x_t = s, x_{t+1} = s'}          occ[s] = #{t : x_t = s}
+ *   occ_y[x_t] = occ_y[x_t] + y_t,   occ_yy[x_t] = occ_yy[x_t] + (y_t * y_t)
+ * every accumulator from 0.0, one addition a step in that order of t, the product one rounded multiplication, nothing contracted;
+ * the counts are integers written as doubles.
+ * Record: 88 doubles a trajectory in cpprob_hip_batch_smooth_stats' layout -- xi at 8 s + s', then occ[8], occ_y[8], occ_yy[8];
+ * states >= k are zero, a problem of length 0 is all zero, a problem of length 1 has xi = 0.  Output [n_problems][n_traj][88],
+ * uniform and not packed; n_doubles >= 88 n_problems n_traj.
+ * Observes: as cpprob_hip_batch_smooth_stats takes them, packed by the lengths reached; NULL (n_observes is then not read): occ_y
+ * and occ_yy stay zero.
+ * keep_history = 1 or CPPROB_HIP_BATCH_KEEP_MASSES, and only after a run / advance (else CPPROB_HIP_ESTATE); CPPROB_HIP_EINVAL
+ * (nothing written): n_traj = 0 or above 2^20, draw_index >= 2^16, a capacity too small, n_observes not the sum of the lengths, a
+ * problem longer than 2^24.  A batch with nothing reached yet gets zeros.  The call shares the m table and its counting pass with
+ * the smoothing calls above (an online batch: none counts a row twice) and changes nothing any other entry point returns.
+ * Synchronises. */
+int cpprob_hip_batch_traj_stats(cpprob_hip_ctx* ctx, uint64_t n_traj, uint64_t draw_index, const double* h_observes, size_t n_observes, double* h_stats,
+                                size_t n_doubles);
+/* The same between device buffers, enqueued on the context's stream after the run / advance, no host synchronisation. */
+int cpprob_hip_batch_traj_stats_device(cpprob_hip_ctx* ctx, uint64_t n_traj, uint64_t draw_index, const double* d_observes, size_t n_observes, double* d_stats,
+                                       size_t n_doubles);
+/* gridDim.y of the context's last trajectory statistics launch, host only: the tiles of 256 trajectories a problem; 0 where none
+ * happened since the last smoothing, forecast, decode or statistics call (or no batch is begun).  The records do not depend on it. */
+int cpprob_hip_batch_traj_stats_grid(cpprob_hip_ctx* ctx, uint32_t* grid_y);
+
 /* Forecasts of a batch (csrc/batch_forecast.hpp): what lies ahead of the last observe, from the smoother's m table and the transition
  * law the device itself draws from.  Per problem b (L_b the length reached, k its states, m_t its rows of the m table, P[s][s'] the
  * integer transition masses of cpprob_hip_batch_smooth):
