@@ -14,6 +14,8 @@ from . import em  # noqa: F401
 from .em import hmm_table_em, m_step  # noqa: F401
 from . import gibbs  # noqa: F401
 from .gibbs import hmm_table_gibbs, sample_tables  # noqa: F401
+from . import pgibbs  # noqa: F401
+from .pgibbs import hmm_table_particle_gibbs  # noqa: F401
 from . import forecast  # noqa: F401
 from .forecast import observation_forecast, predictive_log_likelihood  # noqa: F401
 from . import decode  # noqa: F401

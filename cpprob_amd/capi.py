@@ -48,6 +48,7 @@ SYMBOLS = [
     "cpprob_hip_batch_forecast", "cpprob_hip_batch_forecast_device", "cpprob_hip_batch_predictive", "cpprob_hip_batch_predictive_device",
     "cpprob_hip_batch_decode", "cpprob_hip_batch_decode_device", "cpprob_hip_batch_decode_lag", "cpprob_hip_batch_decode_lag_device",
     "cpprob_hip_batch_decode_logp", "cpprob_hip_batch_pass_grid",
+    "cpprob_hip_batch_run_conditional", "cpprob_hip_batch_run_conditional_device",
 ]
 
 
@@ -370,6 +371,8 @@ def load_library(path=None):
         "cpprob_hip_batch_decode_lag_device": (C.c_int, [vp, u64, C.POINTER(C.c_uint32), u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_decode_logp": (C.c_int, [vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "cpprob_hip_batch_pass_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "cpprob_hip_batch_run_conditional": (C.c_int, [vp, C.POINTER(u64), vp, sz]),
+        "cpprob_hip_batch_run_conditional_device": (C.c_int, [vp, C.POINTER(u64), vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -640,6 +643,43 @@ class Engine:
         if sd.shape != (self.batch_B,):
             raise ValueError("one seed per problem")
         self._chk(self.L.cpprob_hip_batch_run(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+    def _conditional_seeds(self, seeds):
+        sd = np.ascontiguousarray(seeds, np.uint64)
+        if sd.shape != (self.batch_B,):
+            raise ValueError("one seed per problem")
+        return sd
+
+    def batch_run_conditional(self, seeds, ref):
+        """A conditional SMC run in place of batch_run (cpprob_hip_batch_run_conditional): slot 0 of problem b follows its reference
+        path.  ref: a list of B integer arrays of lengths T_b, or one packed array (problem after problem, as
+        batch_smooth_layout(T, 1) packs trajectories); every entry a state 0 .. k - 1.  The batch: MODEL_HMM_TABLE, keep_history=False,
+        keep_masses=True; the resampling is multinomial whatever the batch's resampler.  The run keeps the m table only:
+        batch_masses, batch_smooth*, batch_traj_stats*, batch_forecast*, batch_predictive* and batch_decode* serve it, batch_results
+        waits for the next batch_run."""
+        sd = self._conditional_seeds(seeds)
+        h_T, _ = self._batch_problem_shapes()
+        if isinstance(ref, np.ndarray) and ref.ndim == 1:
+            flat = np.ascontiguousarray(ref, np.int32)
+        else:
+            paths = [np.ascontiguousarray(r, np.int32).reshape(-1) for r in ref]
+            if len(paths) != self.batch_B:
+                raise ValueError("one reference path per problem")
+            if any(len(r) != int(T) for r, T in zip(paths, h_T)):
+                raise ValueError("problem b's reference path holds T_b states")
+            flat = np.ascontiguousarray(np.concatenate(paths), np.int32)
+        if flat.size != int(np.sum(h_T, dtype=np.int64)):
+            raise ValueError("the reference paths hold one state per problem and step: %d entries" % int(np.sum(h_T, dtype=np.int64)))
+        self._chk(self.L.cpprob_hip_batch_run_conditional(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), flat.ctypes.data, flat.size))
+
+    def batch_run_conditional_device(self, seeds, ref_i8):
+        """The same with the reference paths in a torch int8 device tensor packed as batch_smooth_layout(T, 1) says -- what
+        batch_smooth_device(traj_i8=..., n_traj=1) writes --, enqueued without a host synchronisation."""
+        sd = self._conditional_seeds(seeds)
+        h_T, _ = self._batch_problem_shapes()
+        if ref_i8 is None or ref_i8.numel() != int(np.sum(h_T, dtype=np.int64)):
+            raise ValueError("the reference paths hold one state per problem and step: %d entries" % int(np.sum(h_T, dtype=np.int64)))
+        self._chk(self.L.cpprob_hip_batch_run_conditional_device(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), _dptr(ref_i8), ref_i8.numel()))
 
     def batch_results(self, with_stats=True):
         """[summary dict] * B, stats [B, T, spp], ess [B, T], resampled [B, T] in one call and one synchronisation.  with_stats=False:

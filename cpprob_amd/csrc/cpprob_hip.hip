@@ -26,6 +26,7 @@
 #include "batch_trajstats.hpp"
 #include "batch_forecast.hpp"
 #include "batch_decode.hpp"
+#include "batch_csmc.hpp"
 
 using namespace cph;
 
@@ -1099,6 +1100,12 @@ struct BatchState {
     std::vector<double> h_lp; double lp0 = 0.0;
     bool lp_ready = false, lp_sent = false;
     std::vector<uint32_t> decoded;
+    // conditional runs (cpprob_hip_batch_run_conditional*; csrc/batch_csmc.hpp): conditional: the last run was one -- it keeps masses, not
+    // books, and cpprob_hip_batch_results is refused until the next cpprob_hip_batch_run; a described batch's first entries in the
+    // reference paths ([B] int64, the lengths are fixed at begin: written and uploaded at the first conditional run after it) with
+    // their pinned source, allocations of the context's own
+    bool conditional = false, cfirst_ready = false;
+    int64_t* d_cfirst = nullptr; int64_t* pin_cfirst = nullptr; size_t cfirst_cap = 0;
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -1115,6 +1122,8 @@ void batch_free(cpprob_hip_ctx* c)
     dfree(c->batch->d_mass); dfree(c->batch->d_sdesc);
     dfree(c->batch->d_words); dfree(c->batch->d_v); dfree(c->batch->d_lp);
     if (c->batch->pin_sdesc) (void)hipHostFree(c->batch->pin_sdesc);
+    dfree(c->batch->d_cfirst);
+    if (c->batch->pin_cfirst) (void)hipHostFree(c->batch->pin_cfirst);
     for (hipEvent_t e : c->batch->sdesc_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
     c->batch = nullptr;
@@ -1179,7 +1188,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->batch) c->batch = new BatchState();
     BatchState* bs = c->batch;
-    bs->begun = false; bs->ran = false;
+    bs->begun = false; bs->ran = false; bs->conditional = false; bs->cfirst_ready = false;
     const uint64_t B = cfg->n_problems;
     bs->counted.assign(B, 0);
     bs->decoded.assign(B, 0); bs->lp_ready = false; bs->lp_sent = false;
@@ -4133,7 +4142,98 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, bs->cfg.n_problems * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     if (int rc = batch_launch(c, bs, true)) return rc;
-    bs->ran = true;
+    bs->ran = true; bs->conditional = false;
+    return 0;
+}
+
+// ---- conditional runs of a batch (csrc/batch_csmc.hpp) ----------------------------------------------------------------------------
+// The state a conditional run needs and the total of its reference paths; nothing is enqueued before it has passed.
+static int batch_conditional_check(cpprob_hip_ctx* c, const void* seeds, const void* ref, size_t n_entries)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    if (!seeds || !ref) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
+    if (bs->online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "conditional runs serve batches begun by cpprob_hip_batch_begin or _begin_problems: an online batch is advanced (cpprob_hip_batch_advance)");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "conditional runs serve CPPROB_HIP_MODEL_HMM_TABLE");
+    if (bs->cfg.keep_history != 0 || !batch_masses(&bs->cfg))
+        return fail(c, CPPROB_HIP_ESTATE, "a conditional run keeps masses, not a particle store: begin the batch with keep_history = 0 and CPPROB_HIP_BATCH_KEEP_MASSES");
+    uint64_t rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    if ((uint64_t)n_entries != rows) return fail(c, CPPROB_HIP_EINVAL, "the reference paths hold " + std::to_string(n_entries) + " entries: the batch's lengths sum to " + std::to_string(rows));
+    return 0;
+}
+
+// Enqueues the seeds' copy, a described batch's first entries (once a begin) and the launch; waits for nothing, but where the buffer
+// of first entries has to grow, for the calls before it.
+static int batch_conditional_enqueue(cpprob_hip_ctx* c, const uint64_t* h_seeds, const int8_t* d_ref)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    if (bs->described && !bs->cfirst_ready) {
+        if (B > bs->cfirst_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (earlier runs may still read the buffer this replaces)
+            dfree(bs->d_cfirst); bs->cfirst_cap = 0;
+            if (bs->pin_cfirst) { (void)hipHostFree(bs->pin_cfirst); bs->pin_cfirst = nullptr; }
+            HIP_TRY(c, hipMalloc(&bs->d_cfirst, B * sizeof(int64_t)));
+            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_cfirst), B * sizeof(int64_t), hipHostMallocDefault));
+            bs->cfirst_cap = B;
+        }
+        // (the pinned source is written once a begin, and a begin ends with the stream drained: no copy still reads it)
+        int64_t at = 0;
+        for (size_t b = 0; b < B; ++b) { bs->pin_cfirst[b] = at; at += (int64_t)bs->prob[b].T; }
+        HIP_TRY(c, hipMemcpyAsync(bs->d_cfirst, bs->pin_cfirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        bs->cfirst_ready = true;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    BatchCsmcArgs a{};
+    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
+    a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
+    a.thr = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+    a.thr_stride = bs->described ? 64 : 0;
+    a.prob = bs->described ? reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob) : nullptr;
+    a.order = bs->described ? reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.order) : nullptr;
+    a.ref = d_ref;
+    a.first = bs->described ? bs->d_cfirst : nullptr;
+    a.mass = reinterpret_cast<double*>(bs->d_ws + bs->lay.mass);
+    a.T_max = bs->T; a.n = (int)bs->cfg.n_particles; a.k = bs->hk;
+    hipLaunchKernelGGL(batch_csmc_kernel, dim3((unsigned)B), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    bs->ran = true; bs->conditional = true;
+    return 0;
+}
+
+int cpprob_hip_batch_run_conditional_device(cpprob_hip_ctx* c, const uint64_t* h_seeds, const int8_t* d_ref, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (int rc = batch_conditional_check(c, h_seeds, d_ref, n_entries)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_conditional_enqueue(c, h_seeds, d_ref);
+}
+
+int cpprob_hip_batch_run_conditional(cpprob_hip_ctx* c, const uint64_t* h_seeds, const int32_t* h_ref, size_t n_entries)
+{
+    LANES_OWN(c);
+    if (int rc = batch_conditional_check(c, h_seeds, h_ref, n_entries)) return rc;
+    BatchState* bs = c->batch;
+    std::vector<int8_t> v(n_entries);
+    size_t at = 0;
+    for (size_t b = 0; b < bs->prob.size(); ++b)
+        for (int t = 0; t < bs->prob[b].T; ++t, ++at) {
+            if (h_ref[at] < 0 || h_ref[at] >= bs->hk)
+                return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ", step " + std::to_string(t) + ": the reference state " + std::to_string(h_ref[at]) +
+                                                  " lies outside 0 .. " + std::to_string(bs->hk - 1));
+            v[at] = (int8_t)h_ref[at];
+        }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n_entries > bs->stage_cap) {
+        dfree(bs->d_stage); bs->stage_cap = 0;                  // (hipFree waits for the device: no call still reads the staging)
+        HIP_TRY(c, hipMalloc(&bs->d_stage, n_entries));
+        bs->stage_cap = n_entries;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_stage, v.data(), n_entries, hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_conditional_enqueue(c, h_seeds, reinterpret_cast<const int8_t*>(bs->d_stage))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));               // (the staged copy has read v; a later host call may take the staging over)
     return 0;
 }
 
@@ -4249,6 +4349,7 @@ int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, doubl
     if (!c || !h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->conditional) return fail(c, CPPROB_HIP_ESTATE, "a conditional run keeps masses, not books: the results wait for the next cpprob_hip_batch_run");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, T = (size_t)bs->T, need = B * T * (size_t)bs->K;
     if (h_stats && !bs->walked) return fail(c, CPPROB_HIP_ESTATE, "the statistics wait for an advance with readout = 1 (cpprob_hip_batch_advance)");
@@ -4286,6 +4387,7 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_d
     if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->conditional) return fail(c, CPPROB_HIP_ESTATE, "a conditional run keeps masses, not books: the results wait for the next cpprob_hip_batch_run");
     if (!bs->walked) return fail(c, CPPROB_HIP_ESTATE, "the statistics wait for an advance with readout = 1 (cpprob_hip_batch_advance)");
     const int64_t B = (int64_t)bs->cfg.n_problems, per = (int64_t)bs->T * bs->K;
     if (n_doubles < (size_t)(B * (4 + per))) return fail(c, CPPROB_HIP_EINVAL, "d_out too small: n_problems * (4 + n_predict * stats_per_predict) doubles");

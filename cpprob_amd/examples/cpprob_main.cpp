@@ -33,6 +33,9 @@
 //                   states the particles occupy, and its log joint density; --json carries "map_path" and "map_score" instead; with
 //                   --em_iterations the decode is that of the fitted tables)   --decode_lag L (with --decode: x_t is the state at t of the
 //                   best path of steps 0 .. min(t + L, T - 1), what a stream would have labelled L observes later)
+//                   --conditional_paths FILE (with --batch_tables_file --filtering_only --keep_masses: the run is the conditional SMC run,
+//                   problem b's retained particle following line b of FILE, T_b states; the estimates print as 0 -- such a run keeps
+//                   masses, not books -- and --trajectory_stats, --backward_smoothing, --forecast and --decode read its masses as usual)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <algorithm>
 #include <array>
@@ -41,6 +44,7 @@
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <tuple>
 #include <utility>
@@ -60,6 +64,7 @@ struct Args {
     std::size_t n_samples = 10000;            // src/main.cpp:166
     std::size_t stream_chunk = 0;             // --batch_tables_file: feed every problem's observes this many at a time (0: all at once)
     std::size_t em_iterations = 0;            // --batch_tables_file: fit the tables by this many iterations of particle EM (0: none)
+    std::string conditional_paths_file;       // --batch_tables_file: the reference paths of a conditional run, one line a problem (empty: none)
 };
 
 void print_json(const cpprob::gpu::Result& r)
@@ -232,6 +237,21 @@ int execute_batch_tables(const Args& a)
         seeds.push_back(cpprob::gpu::options().seed + at);
     }
     if (tables.empty()) { std::cerr << "no problems in " << a.batch_tables_file << std::endl; return EXIT_FAILURE; }
+    if (!a.conditional_paths_file.empty()) {
+        if (a.em_iterations || a.stream_chunk) { std::cerr << "--conditional_paths replaces the run of one batch: not with --em_iterations or --stream_chunk" << std::endl; return EXIT_FAILURE; }
+        std::ifstream pin(a.model_folder + "/" + a.conditional_paths_file);
+        if (!pin) { std::cerr << "cannot open " << a.model_folder << "/" << a.conditional_paths_file << std::endl; return EXIT_FAILURE; }
+        std::vector<std::vector<int>>& paths = cpprob::gpu::options().conditional_paths;
+        paths.clear();
+        while (std::getline(pin, line)) {
+            std::istringstream ls(line);
+            std::vector<int> path;
+            for (int s2; ls >> s2;) path.push_back(s2);
+            if (!ls.eof()) { std::cerr << "--conditional_paths: line " << paths.size() << " holds something that is no integer." << std::endl; return EXIT_FAILURE; }
+            paths.push_back(path);
+        }
+        if (paths.size() != tables.size()) { std::cerr << "--conditional_paths: " << paths.size() << " lines for " << tables.size() << " problems." << std::endl; return EXIT_FAILURE; }
+    }
     if (a.em_iterations && a.stream_chunk) { std::cerr << "--em_iterations begins a fresh batch an iteration: not with --stream_chunk" << std::endl; return EXIT_FAILURE; }
     std::vector<cpprob::gpu::Result> res;
     std::vector<cpprob::gpu::HmmTable> fitted;
@@ -352,6 +372,7 @@ int main(int argc, char** argv)
         else if (f == "--ess_threshold") opt.ess_threshold = std::stod(next());
         else if (f == "--resampler") { const std::string r = next(); opt.resampler = r == "multinomial" ? 2 : (r == "stratified" ? 1 : 0); }
         else if (f == "--generic") opt.prefer_builtin = false;
+        else if (f == "--conditional_paths") a.conditional_paths_file = next();     // --batch_tables_file --filtering_only --keep_masses: the run is the conditional SMC run; FILE: one line of T_b states a problem
         else if (f == "--keep_masses") opt.keep_masses = true;                     // the batch modes, with --filtering_only: CPPROB_HIP_BATCH_KEEP_MASSES
         else if (f == "--filtering_only") { opt.keep_history = false; opt.dump = false; }   // smc, built-in models: O(N) particle store, filtering statistics
         else if (f == "--islands") opt.islands = true;                          // unchanged-model smc over several ranks: independent runs combined by evidence

@@ -864,7 +864,9 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
 // One batch of the packed problems on ctx: begin, run, results (options().backward_smoothing / ::smoothing_lag as hmm_table_batch
 // states them) and, where dump is set, options().batch_dump_file; decode: options().map_decode is served.  The batch stays on ctx for
 // the calls that read it.
-inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTableProblems& pk, const std::vector<std::uint64_t>& seeds, bool dump, bool decode = true)
+// conditional: the run is cpprob_hip_batch_run_conditional on these paths (one a problem); what cpprob_hip_batch_results returns stays default.
+inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTableProblems& pk, const std::vector<std::uint64_t>& seeds, bool dump, bool decode = true,
+                                                  const std::vector<std::vector<int>>* conditional = nullptr)
 {
     const Options& opt = options();
     const std::size_t B = seeds.size(), k = pk.k, T_max = pk.T_max;
@@ -881,11 +883,17 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
     const auto t0 = std::chrono::steady_clock::now();
     ctx.check(cpprob_hip_batch_begin_problems(ctx.get(), &bc, T.data(), pk.np.data(), pk.flat.data(), static_cast<std::int32_t>(k), pk.means.data(), pk.trans.data()),
               "cpprob_hip_batch_begin_problems");
-    ctx.check(cpprob_hip_batch_run(ctx.get(), seeds.data()), "cpprob_hip_batch_run");
     std::vector<cpprob_hip_summary> sums(B);
     const std::size_t K = 8;
     std::vector<double> stats(B * T_max * K), ess(B * T_max);
-    ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+    if (conditional) {
+        std::vector<std::int32_t> ref;
+        for (const std::vector<int>& path : *conditional) ref.insert(ref.end(), path.begin(), path.end());
+        ctx.check(cpprob_hip_batch_run_conditional(ctx.get(), seeds.data(), ref.data(), ref.size()), "cpprob_hip_batch_run_conditional");
+    } else {
+        ctx.check(cpprob_hip_batch_run(ctx.get(), seeds.data()), "cpprob_hip_batch_run");
+        ctx.check(cpprob_hip_batch_results(ctx.get(), sums.data(), stats.data(), stats.size(), ess.data(), nullptr), "cpprob_hip_batch_results");
+    }
     if (opt.smoothing_lag >= 0) batch_lag_marginals(ctx, static_cast<std::size_t>(opt.smoothing_lag), nullptr, T_max, stats);
     else if (opt.backward_smoothing) batch_backward_marginals(ctx, stats);
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -899,6 +907,9 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
         const cpprob_hip_summary& s = sums[b];
         r.n_particles = pk.np[b]; r.log_evidence = s.log_evidence; r.ess = s.ess_final; r.log_norm = s.log_norm; r.n_resampled = s.n_resampled;
         r.used_builtin = true; r.step_form = s.step_form; r.run_seconds = seconds;
+        // (a conditional run: the predicts hold the smoother's marginals where they were asked for, else nothing)
+        if (conditional) { r = Result(); r.n_particles = pk.np[b]; r.used_builtin = true; r.run_seconds = seconds; }
+        if (conditional && opt.smoothing_lag < 0 && !opt.backward_smoothing) continue;
         r.predicts.resize(T[b]);
         for (std::size_t t = 0; t < T[b]; ++t) {
             PredictStats& p = r.predicts[t];
@@ -906,7 +917,7 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
             p.is_int = true;
             p.probabilities.assign(stats.begin() + (b * T_max + t) * K, stats.begin() + (b * T_max + t) * K + k);
         }
-        r.step_ess.assign(ess.begin() + b * T_max, ess.begin() + b * T_max + T[b]);
+        if (!conditional) r.step_ess.assign(ess.begin() + b * T_max, ess.begin() + b * T_max + T[b]);
     }
     batch_forecast_results(ctx, opt.forecast_horizon, opt.forecast_trajectories, K, k, out);
     batch_decode_results(ctx, decode && opt.map_decode, opt.decode_lag, T, out);
@@ -917,9 +928,24 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
 inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes,
                                            const std::vector<std::size_t>& n, const std::vector<std::uint64_t>& seeds)
 {
-    const HmmTableProblems pk = pack_hmm_table_problems("cpprob::gpu::hmm_table_batch", tables, observes, n, seeds.size());
+    const std::string who = "cpprob::gpu::hmm_table_batch";
+    const HmmTableProblems pk = pack_hmm_table_problems(who, tables, observes, n, seeds.size());
+    const Options& opt = options();
+    const std::vector<std::vector<int>>* conditional = opt.conditional_paths.empty() ? nullptr : &opt.conditional_paths;
+    if (conditional) {
+        if (opt.keep_history || !opt.keep_masses)
+            throw std::runtime_error(who + ": a conditional run (options().conditional_paths) keeps masses, not a particle store: set options().keep_history = false and options().keep_masses");
+        if (conditional->size() != seeds.size()) throw std::runtime_error(who + ": options().conditional_paths holds one path per problem");
+        for (std::size_t b = 0; b < seeds.size(); ++b) {
+            if ((*conditional)[b].size() != pk.T[b])
+                throw std::runtime_error(who + ": problem " + std::to_string(b) + ": options().conditional_paths holds one state per observe");
+            for (int s : (*conditional)[b])
+                if (s < 0 || static_cast<std::size_t>(s) >= pk.k)
+                    throw std::runtime_error(who + ": problem " + std::to_string(b) + ": options().conditional_paths holds states 0 .. k - 1");
+        }
+    }
     ContextLease lease(options().device);
-    std::vector<Result> out = run_hmm_table_problems(*lease, pk, seeds, true);
+    std::vector<Result> out = run_hmm_table_problems(*lease, pk, seeds, true, true, conditional);
     lease.done();
     return out;
 }

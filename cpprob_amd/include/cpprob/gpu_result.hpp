@@ -64,6 +64,11 @@ struct Options {
     bool keep_masses = false;                         // batched runs with keep_history = false: the run keeps the backward smoother's masses (64 bytes a
                                                       // problem and step, CPPROB_HIP_BATCH_KEEP_MASSES), so backward_smoothing, backward_trajectories,
                                                       // smoothing_lag and hmm_table_fit serve the filtering-only batch; lineage dumps stay refused
+    std::vector<std::vector<int>> conditional_paths;  // hmm_table_batch with keep_history = false and keep_masses: not empty = the run is the conditional
+                                                      // SMC run (cpprob_hip_batch_run_conditional), problem b's retained particle following
+                                                      // conditional_paths[b] (one state a step).  It keeps masses, not books: what comes from
+                                                      // cpprob_hip_batch_results stays default in the results; the smoothing, trajectory statistics,
+                                                      // forecast and decode outputs asked for are filled as usual.  Empty: off
     std::uint64_t particle_offset = 0;                // (set by the engine when it shards a population: global id of this shard's first particle)
     bool progress = false;
     bool islands = false;                             // smc over several ranks, unchanged models: independent SMC runs combined by their evidence instead of

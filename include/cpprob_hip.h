@@ -519,6 +519,35 @@ int cpprob_hip_batch_traj_stats_device(cpprob_hip_ctx* ctx, uint64_t n_traj, uin
  * happened since the last smoothing, forecast, decode or statistics call (or no batch is begun).  The records do not depend on it. */
 int cpprob_hip_batch_traj_stats_grid(cpprob_hip_ctx* ctx, uint32_t* grid_y);
 
+/* Conditional SMC runs of a batch (csrc/batch_csmc.hpp): the forward pass of particle Gibbs with backward sampling.  Either call
+ * takes the place of cpprob_hip_batch_run on a batch begun by cpprob_hip_batch_begin or _begin_problems with model
+ * CPPROB_HIP_MODEL_HMM_TABLE, keep_history = 0 and CPPROB_HIP_BATCH_KEEP_MASSES.  Problem b runs with Philox key h_seeds[b] and with
+ * one particle, slot 0, pinned to its reference path r_0 .. r_{T_b - 1}: the paths are packed problem after problem, problem b's
+ * entries from first[b] of cpprob_hip_batch_smooth_layout(T, B, 1) on -- what cpprob_hip_batch_smooth_device writes with
+ * n_traj = 1 -- and n_entries is their total, the sum of the T_b.  The run writes the batch's m table (the counts of a row include
+ * slot 0) and nothing else.  A sweep "conditional run on the previous trajectory, then one backward-simulated trajectory" leaves
+ * the smoothing law invariant at every n_particles >= 1, up to the 32-bit quantisation of weights and thresholds.
+ * The resampling of a conditional run is multinomial whatever cfg.resampler says: conditional SMC with multinomial resampling
+ * followed by backward sampling is the form whose invariance is proven (Whiteley 2010; Lindsten & Schon 2013), and on discrete states
+ * it is the cheap one -- a particle's ancestor matters through the ancestor's state alone, a draw from the k masses of the previous
+ * row, so there is no comb, no ancestor array and no particle store.  Per slot i >= 1: t = 0: x = smallint_from_word(w, 0, k - 1), w
+ * word i & 3 of draw_block(seed, i >> 2, 0); t >= 1: C_s the inclusive sums of the integer masses of row t - 1, S = C_{k-1},
+ * W = (hi << 32) | lo from words 2 (i & 1), 2 (i & 1) + 1 of draw_block(seed, i >> 1, 2^43 + t), V = the high 64 bits of W S,
+ * a = #{s < k-1 : V >= C_s}, x = #{j < k-1 : w >= c[a][j]} with w word i & 3 of draw_block(seed, i >> 2, t) and c the thresholds.
+ * After a conditional run every entry point that serves a CPPROB_HIP_BATCH_KEEP_MASSES batch from its m table, tables and seeds serves
+ * this one unchanged, the run's seeds its Philox keys: cpprob_hip_batch_copy_masses, _smooth*, _smooth_lag*, _smooth_stats*,
+ * _traj_stats*, _forecast*, _predictive* and _decode* (none of them reads anything else of a run).  A conditional run keeps masses,
+ * not books: cpprob_hip_batch_results and _results_device return CPPROB_HIP_ESTATE until the next cpprob_hip_batch_run, which
+ * returns exactly what it returns without the conditional run before it.
+ * The host form validates every entry (0 <= r < k) and stages the paths as int8; it synchronises.  CPPROB_HIP_ESTATE: no batch begun,
+ * keep_history = 1, no CPPROB_HIP_BATCH_KEEP_MASSES; CPPROB_HIP_EUNSUPPORTED: CPPROB_HIP_MODEL_HMM3, an online batch;
+ * CPPROB_HIP_EINVAL (nothing enqueued): a NULL pointer, n_entries not the sum of the T_b, an entry out of range. */
+int cpprob_hip_batch_run_conditional(cpprob_hip_ctx* ctx, const uint64_t* h_seeds, const int32_t* h_ref, size_t n_entries);
+/* The same with the paths in a device buffer of int8, enqueued on the context's stream, no host synchronisation.  The entries are not
+ * validated: the low three bits of one count, and a value >= k is taken as k - 1.  d_ref is read by the run, in stream order; the caller
+ * keeps it alive and unchanged by other streams until the run has finished. */
+int cpprob_hip_batch_run_conditional_device(cpprob_hip_ctx* ctx, const uint64_t* h_seeds, const int8_t* d_ref, size_t n_entries);
+
 /* Forecasts of a batch (csrc/batch_forecast.hpp): what lies ahead of the last observe, from the smoother's m table and the transition
  * law the device itself draws from.  Per problem b (L_b the length reached, k its states, m_t its rows of the m table, P[s][s'] the
  * integer transition masses of cpprob_hip_batch_smooth):
