@@ -107,27 +107,43 @@ class Batch:
 
     def __init__(self, Ts, ns, k, described, seed, zero_entry=False):
         rng = np.random.default_rng(seed)
-        self.Ts, self.ns, self.k, self.B, self.described = list(Ts), list(ns), k, len(Ts), described
-        self.T_max, self.n_max = max(Ts), max(ns)
-        assert described or (len(set(Ts)) == 1 and len(set(ns)) == 1)
-        self.seeds = np.array([(7 << 40) + 1000 + 77 * b for b in range(self.B)], np.uint64)
-        trans = rng.uniform(0.05, 1.0, (self.B if described else 1, k, k))
+        seeds = np.array([(7 << 40) + 1000 + 77 * b for b in range(len(Ts))], np.uint64)
+        trans = rng.uniform(0.05, 1.0, (len(Ts) if described else 1, k, k))
         if zero_entry:
             trans[-1, 0, k - 1] = 0.0
             trans[-1, 1 % k, 0] = 0.0
-        self.rows = [R.thresholds(tr) for tr in trans]
-        self.thr = np.full((trans.shape[0], 8, 8), np.iinfo(np.uint64).max, np.uint64)      # (words behind a row's k - 1 entries: all ones)
-        for i, rows in enumerate(self.rows):
-            for s, row in enumerate(rows):
+        ll, paths = [], []
+        for T in Ts:
+            ll.append((-rng.uniform(0.0, 12.0, (T, k))).tolist())
+            paths.append(rng.integers(0, k, T).astype(np.int8))
+        self._fill(Ts, ns, k, described, seeds, [R.thresholds(tr) for tr in trans], ll, paths)
+
+    @classmethod
+    def given(cls, Ts, ns, k, described, seeds, rows, ll, paths):
+        """A batch over tables, log-likelihoods and reference bytes the caller states: rows[i] = backward_ref.thresholds of table i (one
+        a problem, or one for all), ll[b] = [T_b][k] floats, paths[b] = T_b reference bytes (any int8 values)."""
+        bt = cls.__new__(cls)
+        bt._fill(Ts, ns, k, described, np.array(seeds, np.uint64), [list(r) for r in rows], [[list(map(float, r)) for r in x] for x in ll],
+                 [np.asarray(p).astype(np.int8) for p in paths])
+        return bt
+
+    def _fill(self, Ts, ns, k, described, seeds, rows, ll, paths):
+        self.Ts, self.ns, self.k, self.B, self.described = list(Ts), list(ns), k, len(Ts), described
+        self.T_max, self.n_max = max(Ts), max(ns)
+        assert described or (len(set(Ts)) == 1 and len(set(ns)) == 1)
+        assert len(rows) == (self.B if described else 1) and len(ll) == len(paths) == len(seeds) == self.B
+        self.seeds = seeds
+        self.rows = rows
+        self.thr = np.full((len(rows), 8, 8), np.iinfo(np.uint64).max, np.uint64)           # (words behind a row's k - 1 entries: all ones)
+        for i, rows_i in enumerate(self.rows):
+            for s, row in enumerate(rows_i):
                 self.thr[i, s, :k - 1] = row
         self.thr_stride = 64 if described else 0
         self.tab = np.zeros((self.B, self.T_max, 8))
-        self.ll, self.paths = [], []
+        self.ll, self.paths = ll, paths
         for b, T in enumerate(self.Ts):
-            ll = -rng.uniform(0.0, 12.0, (T, k))
-            self.tab[b, :T, :k] = ll
-            self.ll.append(ll.tolist())
-            self.paths.append(rng.integers(0, k, T).astype(np.int8))
+            assert len(ll[b]) == len(paths[b]) == T
+            self.tab[b, :T, :k] = np.array(ll[b])
         self.ref = np.concatenate(self.paths)
         self.first = np.concatenate([[0], np.cumsum(self.Ts)])[:-1].astype(np.int64)
         self.prob = np.zeros(self.B, PROB)
