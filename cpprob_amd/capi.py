@@ -44,6 +44,7 @@ SYMBOLS = [
     "cpprob_hip_batch_smooth_layout", "cpprob_hip_batch_smooth", "cpprob_hip_batch_smooth_device",
     "cpprob_hip_batch_smooth_lag", "cpprob_hip_batch_smooth_lag_device", "cpprob_hip_batch_smooth_grid",
     "cpprob_hip_batch_smooth_stats", "cpprob_hip_batch_smooth_stats_device",
+    "cpprob_hip_batch_online_stats", "cpprob_hip_batch_online_stats_device", "cpprob_hip_batch_online_stats_progress",
     "cpprob_hip_batch_traj_stats", "cpprob_hip_batch_traj_stats_device", "cpprob_hip_batch_traj_stats_grid",
     "cpprob_hip_batch_forecast", "cpprob_hip_batch_forecast_device", "cpprob_hip_batch_predictive", "cpprob_hip_batch_predictive_device",
     "cpprob_hip_batch_decode", "cpprob_hip_batch_decode_device", "cpprob_hip_batch_decode_lag", "cpprob_hip_batch_decode_lag_device",
@@ -358,6 +359,9 @@ def load_library(path=None):
         "cpprob_hip_batch_smooth_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "cpprob_hip_batch_smooth_stats": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_smooth_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_online_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_online_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_online_stats_progress": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
         "cpprob_hip_batch_traj_stats": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_traj_stats_device": (C.c_int, [vp, u64, u64, vp, sz, vp, sz]),
         "cpprob_hip_batch_traj_stats_grid": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
@@ -826,6 +830,38 @@ class Engine:
         """The same left in a device tensor, enqueued behind the run / advance without a host synchronisation: stats torch float64
         [B, 88] (split_stats names its columns), observes a torch float64 tensor packed as above or None."""
         self._chk(self.L.cpprob_hip_batch_smooth_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    def batch_online_stats(self, new_observes=None):
+        """Running sufficient statistics of an online batch (cpprob_hip_batch_online_stats), forward-only: batch_smooth_stats' dict
+        -- xi [B, 8, 8], occ, occ_y, occ_yy [B, 8] -- at the lengths reached, for the cost of the steps that arrived since the last
+        call (the backward walk of batch_smooth_stats pays every step on every call; in exact arithmetic the two records are equal,
+        in doubles they differ by rounding).  new_observes: the observes of the steps the call consumes -- called after every
+        batch_advance, that advance's own list of 1-D arrays (or one packed array); None: those steps take y = 0 and add nothing to
+        occ_y, occ_yy.  The bits do not depend on how the stream was cut into advances and calls; a call without new steps returns
+        the same record again.  cpprob_amd.em.m_step on the result is the running M-step estimate of the tables:
+
+            eng.batch_begin_online(MODEL_HMM_TABLE, capacity, n, seeds, tables=(means, trans))
+            for piece in stream:                                   # piece: a list of B arrays
+                eng.batch_advance(piece)
+                means_now, trans_now = em.m_step(eng.batch_online_stats(piece), means, trans)
+        """
+        rec = np.zeros((self.batch_B, STATS_PER_PROBLEM))
+        flat = None if new_observes is None else self._batch_packed_observes(new_observes)
+        self._chk(self.L.cpprob_hip_batch_online_stats(self.h, None if flat is None or flat.size == 0 else flat.ctypes.data, 0 if flat is None else flat.size,
+                                                       rec.ctypes.data, rec.size))
+        return split_stats(rec)
+
+    def batch_online_stats_device(self, stats, new_observes=None):
+        """The same left in a device tensor, enqueued behind the advance without a host synchronisation: stats torch float64 [B, 88]
+        (split_stats names its columns), new_observes a torch float64 tensor packed as above or None."""
+        self._chk(self.L.cpprob_hip_batch_online_stats_device(self.h, _dptr(new_observes), 0 if new_observes is None else new_observes.numel(), _dptr(stats),
+                                                              0 if stats is None else stats.numel()))
+
+    def batch_online_stats_progress(self):
+        """The steps of every problem the running statistics have consumed (uint32 [B]); 0 after any begin."""
+        out = np.zeros(self.batch_B, np.uint32)
+        self._chk(self.L.cpprob_hip_batch_online_stats_progress(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     @staticmethod
     def _traj_stats_args(n_traj, draw_index):

@@ -24,6 +24,7 @@
 #include "batch_smooth.hpp"
 #include "batch_suffstats.hpp"
 #include "batch_trajstats.hpp"
+#include "batch_onlinestats.hpp"
 #include "batch_forecast.hpp"
 #include "batch_decode.hpp"
 #include "batch_csmc.hpp"
@@ -1100,6 +1101,10 @@ struct BatchState {
     std::vector<double> h_lp; double lp0 = 0.0;
     bool lp_ready = false, lp_sent = false;
     std::vector<uint32_t> decoded;
+    // running statistics (cpprob_hip_batch_online_stats*; csrc/batch_onlinestats.hpp): tau [B][8][88], an allocation of the context's
+    // own; ostats_done: [B], online batch: the steps [0, ostats_done_b) are in its tau (any begin: none -- a problem at 0 never reads tau)
+    double* d_tau = nullptr; size_t tau_cap = 0;
+    std::vector<uint32_t> ostats_done;
     // conditional runs (cpprob_hip_batch_run_conditional*; csrc/batch_csmc.hpp): conditional: the last run was one -- it keeps masses, not
     // books, and cpprob_hip_batch_results is refused until the next cpprob_hip_batch_run; a described batch's first entries in the
     // reference paths ([B] int64, the lengths are fixed at begin: written and uploaded at the first conditional run after it) with
@@ -1120,7 +1125,7 @@ void batch_free(cpprob_hip_ctx* c)
     if (c->batch->pin_pdesc) (void)hipHostFree(c->batch->pin_pdesc);
     for (hipEvent_t e : c->batch->pdesc_done) if (e) (void)hipEventDestroy(e);
     dfree(c->batch->d_mass); dfree(c->batch->d_sdesc);
-    dfree(c->batch->d_words); dfree(c->batch->d_v); dfree(c->batch->d_lp);
+    dfree(c->batch->d_words); dfree(c->batch->d_v); dfree(c->batch->d_lp); dfree(c->batch->d_tau);
     if (c->batch->pin_sdesc) (void)hipHostFree(c->batch->pin_sdesc);
     dfree(c->batch->d_cfirst);
     if (c->batch->pin_cfirst) (void)hipHostFree(c->batch->pin_cfirst);
@@ -1192,6 +1197,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     const uint64_t B = cfg->n_problems;
     bs->counted.assign(B, 0);
     bs->decoded.assign(B, 0); bs->lp_ready = false; bs->lp_sent = false;
+    bs->ostats_done.assign(B, 0);
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3, described = h_T != nullptr, own = h_means != nullptr;
     const int spp = hmm3 ? 3 : 8;
     const uint64_t tables = described ? B : 1;
@@ -4604,6 +4610,9 @@ struct BatchSmoothStats { const double* d_obs; double* d_stats; };
 // A trajectory statistics call's own (cpprob_hip_batch_traj_stats): the observes (or nullptr) and the records [B][n_traj][88], on the device.
 struct BatchTrajStats { const double* d_obs; double* d_stats; };
 static_assert(kTrajStats == kSuffStats, "a trajectory's record has the layout of a problem's expected statistics");
+// A running statistics call's own (cpprob_hip_batch_online_stats): the observes of the steps it consumes (or nullptr) and the records, on the device.
+struct BatchOnlineStats { const double* d_obs; double* d_stats; };
+static_assert(kOnlineStats == kSuffStats, "the running record has the layout of a problem's expected statistics");
 // A forecast call's own (cpprob_hip_batch_forecast: horizon > 0; cpprob_hip_batch_predictive: horizon = 0, the first rows wanted and
 // the rows a problem of the output).
 struct BatchForecast { uint64_t horizon; const uint32_t* from; uint64_t n_rows; };
@@ -4621,9 +4630,11 @@ static int batch_decode_prepare(cpprob_hip_ctx* c, size_t word_rows);
 // row L - 1 (the forecast) or rows max(from_b, 1) - 1 .. L - 1 (the predictive rows) only.
 // dc: the passes after the counting are batch_decode_forward_kernel and batch_decode_trace_kernel (csrc/batch_decode.hpp); an online
 // batch's words are kept as its m table is: the forward pass walks steps [decoded_b, L_b) and moves that watermark.
-static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr,
-                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr, const BatchDecode* dc = nullptr,
-                                const BatchTrajStats* ts = nullptr)
+// os: the pass after the counting is batch_online_stats_kernel (csrc/batch_onlinestats.hpp): an online batch's tau is kept as its m
+// table is, the kernel walks steps [ostats_done_b, L_b) -- its observes packed by those counts -- and moves that watermark.
+static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg,
+                                const BatchSmoothStats* st, const BatchForecast* fc, const BatchDecode* dc, const BatchTrajStats* ts,
+                                const BatchOnlineStats* os)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
@@ -4638,13 +4649,14 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     size_t rows = 0, reached = 0;
     for (size_t b = 0; b < B; ++b) { reached += (size_t)bs->prob[b].T; rows += bs->online ? (size_t)bs->cap_T[b] : (size_t)bs->prob[b].T; }
     if (st && reached == 0) HIP_TRY(c, hipMemsetAsync(st->d_stats, 0, B * (size_t)kSuffStats * sizeof(double), c->stream));
+    if (os && reached == 0) HIP_TRY(c, hipMemsetAsync(os->d_stats, 0, B * (size_t)kOnlineStats * sizeof(double), c->stream));
     if (ts && reached == 0) HIP_TRY(c, hipMemsetAsync(ts->d_stats, 0, B * (size_t)n_traj * (size_t)kTrajStats * sizeof(double), c->stream));
     // a forecast before the first observes: rows of zeros; the predictive row 0 needs no row of the table and goes on
     if (fc && !predictive && reached == 0 && with_traj) HIP_TRY(c, hipMemsetAsync(d_traj, 0, B * (size_t)(fc->horizon + 1) * (size_t)n_traj, c->stream));
     // a decode: a problem of length 0 has score 0; the fixed-lag rows no step owns are -1 (0 is a state)
     if (dc && dc->d_score) HIP_TRY(c, hipMemsetAsync(dc->d_score, 0, B * sizeof(double), c->stream));
     if (dc && !dc->full && dc->d_path && dc->n_rows) HIP_TRY(c, hipMemsetAsync(dc->d_path, 0xff, B * (size_t)dc->n_rows, c->stream));
-    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st && !dc && !ts)) return 0;   // (an online batch before its first observes, or nothing asked for)
+    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st && !dc && !ts && !os)) return 0;   // (an online batch before its first observes, or nothing asked for)
     const size_t word_rows = kept ? B * (size_t)bs->T : rows;
     if (kept) rows = 0;
     if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
@@ -4666,12 +4678,19 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         }
     }
     if (dc) { if (int rc = batch_decode_prepare(c, word_rows)) return rc; }
+    if (os && B > bs->tau_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (earlier calls' kernels may still read the buffer this replaces)
+        dfree(bs->d_tau); bs->tau_cap = 0;
+        bs->ostats_done.assign(B, 0);
+        HIP_TRY(c, hipMalloc(&bs->d_tau, B * (size_t)kOnlineTau * sizeof(double)));
+        bs->tau_cap = B;
+    }
     const int slot = (int)(bs->n_smooth % BatchState::kOnlineSlots);
     if (bs->n_smooth >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->sdesc_done[slot]));
     char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap;
     BatchSmoothProblem* pd = reinterpret_cast<BatchSmoothProblem*>(sl);
     const size_t thr_at = bs->sdesc_cap - thr_bytes;
-    int64_t at = 0, at_traj = 0;
+    int64_t at = 0, at_traj = 0, at_fresh = 0;
     int range_top = 0, W_top = 0;
     int64_t items_top = 0;
     for (size_t b = 0; b < B; ++b) {
@@ -4681,6 +4700,11 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         pd[b].T = L; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at; pd[b].trows = at_traj;
         pd[b].lo = L - W; pd[b].mfrom = mfrom; pd[b].cto = L;
         if (dc) pd[b].lo = bs->online ? (int)std::min<uint32_t>(bs->decoded[b], (uint32_t)L) : 0;   // the forward pass's first step
+        if (os) {                                                           // the first step to consume and its observe
+            pd[b].lo = (int)std::min<uint32_t>(bs->ostats_done[b], (uint32_t)L);
+            pd[b].trows = at_fresh;
+            at_fresh += L - pd[b].lo;
+        }
         // the rows the pass owes: an online batch's new ones; a run batch's -- nothing is kept -- those this call reads
         if (kept) { pd[b].rows = (int64_t)b * bs->T; pd[b].store = 0; pd[b].cfrom = L; }
         else if (bs->online) pd[b].cfrom = (int)bs->counted[b];
@@ -4718,6 +4742,16 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
         HIP_TRY(c, hipGetLastError());
         bs->smooth_gy_count = gy;
         if (bs->online) for (size_t b = 0; b < B; ++b) bs->counted[b] = (uint32_t)bs->prob[b].T;
+    }
+    if (os) {
+        BatchOnlineStatsArgs oa{};
+        oa.desc = a.desc; oa.mass = a.mass; oa.thr = a.thr; oa.obs = os->d_obs; oa.tau = bs->d_tau; oa.stats = os->d_stats;
+        oa.B = (int)B; oa.k = a.k; oa.thr_stride = a.thr_stride;
+        // a wavefront a problem; a problem without new steps is read out of its tau
+        hipLaunchKernelGGL(batch_online_stats_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, oa);
+        HIP_TRY(c, hipGetLastError());
+        for (size_t b = 0; b < B; ++b) bs->ostats_done[b] = (uint32_t)bs->prob[b].T;
+        return 0;
     }
     if (dc) {
         BatchDecodeArgs da{};
@@ -4797,6 +4831,14 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     else hipLaunchKernelGGL(batch_smooth_kernel<8>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return 0;
+}
+
+// The modes that were there before os, each optional (the running statistics pass all eleven arguments).
+static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr,
+                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr, const BatchDecode* dc = nullptr,
+                                const BatchTrajStats* ts = nullptr)
+{
+    return batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj, lg, st, fc, dc, ts, nullptr);
 }
 
 int cpprob_hip_batch_smooth_device(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries)
@@ -4952,6 +4994,74 @@ int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* c, const double* h_observes, s
     if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, &st)) return rc;
     HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- running statistics of an online batch (csrc/batch_onlinestats.hpp) -------------------------------------------------------------
+// cpprob_hip_batch_online_stats' arguments against the batch's state; fresh: the steps the call consumes.  It writes nothing.
+static int batch_online_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& fresh)
+{
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->online) return fail(c, CPPROB_HIP_ESTATE, "running statistics serve a batch begun by cpprob_hip_batch_begin_online");
+    if (bs->cfg.keep_history != 1 && !batch_masses(&bs->cfg))
+        return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no masses: begin it with CPPROB_HIP_BATCH_KEEP_MASSES");
+    if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    fresh = 0;
+    for (size_t b = 0; b < bs->prob.size(); ++b) fresh += (uint64_t)bs->prob[b].T - std::min<uint64_t>(bs->ostats_done[b], (uint64_t)bs->prob[b].T);
+    if ((observes || n_observes) && (uint64_t)n_observes != fresh)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the call consumes " + std::to_string(fresh) + " steps (the lengths reached less the steps consumed)");
+    if (!observes && n_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const uint64_t need = (uint64_t)bs->cfg.n_problems * (uint64_t)kOnlineStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
+    return 0;
+}
+
+int cpprob_hip_batch_online_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t fresh = 0;
+    if (int rc = batch_online_stats_check(c, d_observes, n_observes, d_stats, n_doubles, fresh)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const BatchOnlineStats os{fresh ? d_observes : nullptr, d_stats};
+    return batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &os);
+}
+
+int cpprob_hip_batch_online_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t fresh = 0;
+    if (int rc = batch_online_stats_check(c, h_observes, n_observes, h_stats, n_doubles, fresh)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchState* bs = c->batch;
+    // device staging: the records in front of the observes
+    const bool with_obs = h_observes && fresh;
+    const size_t s_bytes = (size_t)bs->cfg.n_problems * kOnlineStats * sizeof(double), need = s_bytes + (with_obs ? (size_t)fresh * sizeof(double) : 0);
+    if (need > bs->stage_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
+        bs->stage_cap = need;
+    }
+    double* d_stats = reinterpret_cast<double*>(bs->d_stage);
+    double* d_obs = with_obs ? reinterpret_cast<double*>(bs->d_stage + s_bytes) : nullptr;
+    if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, (size_t)fresh * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const BatchOnlineStats os{d_obs, d_stats};
+    if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &os)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int cpprob_hip_batch_online_stats_progress(cpprob_hip_ctx* c, uint32_t* h_done)
+{
+    LANES_OWN(c);
+    if (!c || !h_done) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->online) return fail(c, CPPROB_HIP_ESTATE, "running statistics serve a batch begun by cpprob_hip_batch_begin_online");
+    for (uint64_t b = 0; b < bs->cfg.n_problems; ++b) h_done[b] = bs->ostats_done[b];
     return 0;
 }
 

@@ -36,6 +36,9 @@
 //                   --conditional_paths FILE (with --batch_tables_file --filtering_only --keep_masses: the run is the conditional SMC run,
 //                   problem b's retained particle following line b of FILE, T_b states; the estimates print as 0 -- such a run keeps
 //                   masses, not books -- and --trajectory_stats, --backward_smoothing, --forecast and --decode read its masses as usual)
+//                   --running_stats (with --batch_tables_file --stream_chunk K: every chunk is followed by the forward-only update of the
+//                   expected sufficient statistics, at the cost of the chunk's steps; after everything else one line a problem, the
+//                   record of the lengths reached in --trajectory_stats' format)
 // This file never touches HIP: it calls cpprob::inference exactly as the reference's main does.
 #include <algorithm>
 #include <array>
@@ -162,19 +165,30 @@ void print_decodes(const std::vector<cpprob::gpu::Result>& res)
 
 // --trajectory_stats M [--draw_index D], after everything else of the batch (in --json mode too): M lines a problem in problem order,
 // line j the record of its backward-simulated trajectory j, "[xi k x k row-major] [occ] [occ_y] [occ_yy]" over the first k states
+void print_stats_record(const std::vector<double>& rec, std::size_t k)
+{
+    std::cout << "[";
+    for (std::size_t s = 0; s < k; ++s)
+        for (std::size_t j = 0; j < k; ++j) std::cout << (s + j ? " " : "") << rec[8 * s + j];
+    for (std::size_t part = 0; part < 3; ++part) {
+        std::cout << "] [";
+        for (std::size_t s = 0; s < k; ++s) std::cout << (s ? " " : "") << rec[64 + 8 * part + s];
+    }
+    std::cout << "]" << std::endl;
+}
+
 void print_trajectory_stats(const std::vector<cpprob::gpu::Result>& res, std::size_t k)
 {
     for (const cpprob::gpu::Result& r : res)
-        for (const std::vector<double>& rec : r.trajectory_stats) {
-            std::cout << "[";
-            for (std::size_t s = 0; s < k; ++s)
-                for (std::size_t j = 0; j < k; ++j) std::cout << (s + j ? " " : "") << rec[8 * s + j];
-            for (std::size_t part = 0; part < 3; ++part) {
-                std::cout << "] [";
-                for (std::size_t s = 0; s < k; ++s) std::cout << (s ? " " : "") << rec[64 + 8 * part + s];
-            }
-            std::cout << "]" << std::endl;
-        }
+        for (const std::vector<double>& rec : r.trajectory_stats) print_stats_record(rec, k);
+}
+
+// --running_stats (with --stream_chunk), after the trajectory statistics (in --json mode too): one line a problem in problem order,
+// its running record of the lengths reached in the same format
+void print_running_stats(const std::vector<cpprob::gpu::Result>& res, std::size_t k)
+{
+    for (const cpprob::gpu::Result& r : res)
+        if (!r.running_stats.empty()) print_stats_record(r.running_stats, k);
 }
 
 // --batch_observes_file F: one observation sequence a line, all run as ONE batch (cpprob::gpu::inference_batch, smc, built-in HMMs);
@@ -298,6 +312,7 @@ int execute_batch_tables(const Args& a)
         std::cout << "]" << std::endl;
     }
     print_trajectory_stats(res, k);
+    print_running_stats(res, k);
     cpprob::gpu::release_device_resources();
     return EXIT_SUCCESS;
 }
@@ -362,6 +377,7 @@ int main(int argc, char** argv)
         else if (f == "--decode") opt.map_decode = true;                           // the batch modes: the most probable state path (cpprob_hip_batch_decode)
         else if (f == "--decode_lag") opt.decode_lag = std::stol(next());          // ... its fixed-lag rows instead (cpprob_hip_batch_decode_lag)
         else if (f == "--trajectory_stats") opt.trajectory_stats = std::stoull(next());   // the batch modes: the records of this many backward-simulated trajectories a problem (cpprob_hip_batch_traj_stats)
+        else if (f == "--running_stats") opt.running_stats = true;                 // --batch_tables_file --stream_chunk: the expected statistics kept forward-only (cpprob_hip_batch_online_stats)
         else if (f == "--draw_index") opt.trajectory_stats_draw_index = std::stoull(next());   // ... under this draw index
         else if (f == "--forecast") opt.forecast_horizon = std::stoull(next());   // the batch modes: the state's laws this many steps ahead (cpprob_hip_batch_forecast)
         else if (f == "--forecast_trajectories") opt.forecast_trajectories = std::stoull(next());   // ... and this many simulated futures a problem
@@ -408,6 +424,14 @@ int main(int argc, char** argv)
     }
     if (opt.trajectory_stats && !opt.keep_history && !opt.keep_masses) {
         std::cerr << "--trajectory_stats reads the smoother's masses: with --filtering_only set --keep_masses" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (opt.running_stats && (a.batch_tables_file.empty() || a.stream_chunk == 0)) {
+        std::cerr << "--running_stats follows a stream: set --batch_tables_file and --stream_chunk" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (opt.running_stats && !opt.keep_history && !opt.keep_masses) {
+        std::cerr << "--running_stats reads the smoother's masses: with --filtering_only set --keep_masses" << std::endl;
         return EXIT_FAILURE;
     }
     if (opt.decode_lag >= 0 && !opt.map_decode) { std::cerr << "--decode_lag delays a decode: set --decode" << std::endl; return EXIT_FAILURE; }

@@ -1028,6 +1028,9 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // options().trajectory_stats = M > 0: every advance's results carry the records of M backward-simulated trajectories of the lengths
 // reached (Result::trajectory_stats; the object keeps the observes seen so far for their occ_y and occ_yy); a problem without
 // observes has zero records.
+// options().running_stats: every advance's results carry the expected sufficient statistics of the lengths reached
+// (Result::running_stats), kept forward-only on the device (cpprob_hip_batch_online_stats): the call consumes the advance's own
+// observes and costs its new steps, whatever length the stream has reached; a problem without observes has a zero record.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -1040,6 +1043,8 @@ public:
         check_forecast_options("cpprob::gpu::HmmTableStream", forecast_H_, forecast_M_, keep_ || masses_);
         check_decode_options("cpprob::gpu::HmmTableStream", decode_, decode_lag_, keep_ || masses_);
         check_trajectory_stats_options("cpprob::gpu::HmmTableStream", traj_stats_M_, traj_stats_draw_, keep_ || masses_);
+        if (!keep_ && !masses_ && running_stats_)
+            throw std::runtime_error("cpprob::gpu::HmmTableStream: options().running_stats reads the smoother's masses: a filtering-only run (options().keep_history = false) keeps none without options().keep_masses");
         if (!keep_ && !masses_ && backward_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         if (!keep_ && !masses_ && lag_ >= 0)
@@ -1166,6 +1171,13 @@ public:
             }
             batch_trajectory_stats_results(ctx, traj_stats_M_, traj_stats_draw_, seen, out);
         }
+        if (running_stats_) {
+            // (the steps the call consumes are this advance's: every advance is followed by the call)
+            const std::size_t R = 88;
+            std::vector<double> rec(B_ * R);
+            ctx.check(cpprob_hip_batch_online_stats(ctx.get(), flat.empty() ? nullptr : flat.data(), flat.size(), rec.data(), rec.size()), "cpprob_hip_batch_online_stats");
+            for (std::size_t b = 0; b < B_; ++b) out[b].running_stats.assign(rec.begin() + static_cast<std::ptrdiff_t>(b * R), rec.begin() + static_cast<std::ptrdiff_t>((b + 1) * R));
+        }
         return out;
     }
 
@@ -1196,6 +1208,7 @@ private:
     std::size_t traj_stats_M_ = options().trajectory_stats;
     std::uint64_t traj_stats_draw_ = options().trajectory_stats_draw_index;
     std::vector<std::vector<double>> seen_;    // trajectory_stats: [b] = problem b's observes so far
+    bool running_stats_ = options().running_stats;
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

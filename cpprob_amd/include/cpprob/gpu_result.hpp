@@ -47,6 +47,9 @@ struct Options {
                                                       // complete-data sufficient statistics of this many backward-simulated trajectories, counted on the
                                                       // device (cpprob_hip_batch_traj_stats); HmmTableStream: after every advance.  0: off
     std::uint64_t trajectory_stats_draw_index = 0;    // ... under this draw_index (< 2^16): the trajectories are cpprob_hip_batch_smooth's for it
+    bool running_stats = false;                       // HmmTableStream (keep_history, or keep_masses): every advance's results carry Result::running_stats, the
+                                                      // expected sufficient statistics of the lengths reached, kept forward-only on the device
+                                                      // (cpprob_hip_batch_online_stats): an advance costs its new steps, whatever length the stream has reached
     bool map_decode = false;                          // batched runs (keep_history, or keep_masses): every result carries Result::map_path, the single most
                                                       // probable state sequence given the observes over the states the particles occupy, and
                                                       // Result::map_score (cpprob_hip_batch_decode); hmm_table_fit decodes under the fitted tables
@@ -116,6 +119,7 @@ struct Result {
     std::vector<std::vector<std::int32_t>> forecast_trajectories;   // Options::forecast_trajectories: [j][h], future j's states; h = 0 is the present state
     std::vector<std::vector<double>> trajectory_stats;              // Options::trajectory_stats: [j] = trajectory j's record of 88 doubles -- xi at 8 s + s' (transitions
                                                                     // s -> s'), then occ[8], occ_y[8], occ_yy[8]
+    std::vector<double> running_stats;                              // Options::running_stats: the problem's record of 88 doubles in that layout, the expected statistics
     bool map_decoded = false;                 // Options::map_decode: the two fields below are set
     std::vector<std::int32_t> map_path;       // [t]: the most probable state path (Options::decode_lag >= 0: the fixed-lag rows)
     double map_score = 0;                     // the log joint density of the full decode's path and the observes; 0 without observes

@@ -490,6 +490,41 @@ int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* ctx, const double* h_observes,
 /* The same between device buffers, enqueued on the context's stream after the run / advance, no host synchronisation. */
 int cpprob_hip_batch_smooth_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
 
+/* Running sufficient statistics of an online batch, forward-only (csrc/batch_onlinestats.hpp): the 88 numbers of
+ * cpprob_hip_batch_smooth_stats at the lengths the stream has reached, for the cost of the steps that arrived since the last call --
+ * the backward walk above pays every row of the m table on every call.  The forward-only smoothing of additive functionals (Cappe
+ * 2011; Del Moral, Doucet & Singh 2010): for every current state s' the batch keeps
+ *   tau_t[s'][.] = E[statistics of steps 0..t | x_t = s', y_0..y_t]                 ([8][88] doubles a problem, on the device)
+ * and pushes it one step with the backward kernel the smoother forms from row t - 1 of the m table.  In exact arithmetic the record
+ * equals cpprob_hip_batch_smooth_stats'; in doubles the two differ by rounding (a few T 2^-52, relative to max(1, |value|)).
+ * State, for the life of an online batch: tau and, a problem, done_b = the steps consumed (host state).  Any batch begin resets both.
+ * Per problem (k states; m_t its rows of the m table, states >= k zero; p[s][s'] = double(P[s][s']) as above; column j of a row of tau
+ * as the record's: 8 s + s'' for xi[s][s''], 64 + s occ, 72 + s occ_y, 80 + s occ_yy), consuming step t = done_b with observe y:
+ *   t = 0:   tau'[s'][.] = 0.0
+ *   t >= 1, m = m_{t-1}:  a[s'][s] = m[s] * p[s][s'] (one rounded product);  D[s'] = sum of a[s'][s] in the order s = 0..7 from 0.0;
+ *            Dm the same sum of m[s];  w[s'][s] = m[s] / Dm where D[s'] == 0.0 (the defensive rule), else a[s'][s] / D[s']
+ *            tau'[s'][j] = sum over s = 0..k-1 ascending, from 0.0, of w[s'][s] * v (one rounded product),
+ *            v = tau[s][j] + 1.0 (one rounded addition) where j == 8 s + s', else tau[s][j]
+ *   then     tau'[s'][64 + s'] += 1.0,  tau'[s'][72 + s'] += y,  tau'[s'][80 + s'] += y * y;  rows s' >= k stay 0.0
+ * Read-out at length L_b (tau unchanged): L_b = 0: 88 zeros; else g[s'] = double(m_{L_b-1}[s']) / double(sum of m_{L_b-1}) and
+ *   out[j] = sum over s' = 0..k-1 ascending, from 0.0, of g[s'] * tau[s'][j];  states >= k of the record are zero.
+ * Nothing is contracted: the record is a pure function of integers and IEEE operations, the same bits however the stream was cut into
+ * advances and calls.  After the call done_b = L_b; a call without new steps returns the same record again.
+ * Observes: those of the steps the call consumes -- problem b's L_b - done_b values, packed in problem order; called after every
+ * advance, the advance's own h_observes.  n_observes must equal that total exactly.  NULL with n_observes = 0: every consumed step
+ * takes y = 0.0 (its occ_y, occ_yy terms are zero).  h_stats: [n_problems][88], n_doubles >= 88 n_problems.
+ * CPPROB_HIP_ESTATE: no batch is begun; the batch was not begun by cpprob_hip_batch_begin_online; a filtering-only batch
+ * (keep_history = 0) without CPPROB_HIP_BATCH_KEEP_MASSES.  CPPROB_HIP_EINVAL: n_observes not the steps consumed (or nonzero with
+ * NULL observes), n_doubles < 88 n_problems, a NULL stats.  After any refusal nothing has changed: the next correct call returns the
+ * bits it would have returned.  The call shares the m table and its counting pass with the smoothing calls above (none counts a row
+ * twice) and changes nothing any other entry point returns.  Stages the observes and the records on the device.  Synchronises. */
+int cpprob_hip_batch_online_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+/* The same between device buffers, enqueued on the context's stream after the advance, no host synchronisation. */
+int cpprob_hip_batch_online_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+/* done_b of every problem ([n_problems]), host only: the steps the running statistics have consumed.  CPPROB_HIP_ESTATE without an
+ * online batch. */
+int cpprob_hip_batch_online_stats_progress(cpprob_hip_ctx* ctx, uint32_t* h_done);
+
 /* Trajectory sufficient statistics of a batch (csrc/batch_trajstats.hpp): the complete-data statistics of backward-simulated
  * trajectories, counted on the device while they are drawn -- what a Gibbs sweep over a table, a stochastic EM step or a
  * posterior-predictive check reads of a trajectory.  Trajectory j of problem b under draw_index is exactly column j of
