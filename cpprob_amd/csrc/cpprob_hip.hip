@@ -28,6 +28,7 @@
 #include "batch_forecast.hpp"
 #include "batch_decode.hpp"
 #include "batch_csmc.hpp"
+#include "batch_pass_plan.hpp"
 
 using namespace cph;
 
@@ -4541,6 +4542,36 @@ int cpprob_hip_batch_paths_device(cpprob_hip_ctx* c, uint64_t max_particles, int
     return batch_paths_enqueue(c, max_particles, d_paths, d_logw);
 }
 
+// The device staging of a host call: front_bytes of the block in front of back_bytes (the caller rounds the former where the latter
+// needs the alignment); a part of 0 bytes is nullptr.  Where the block has to grow, it waits first for the calls before it, whose
+// copies and kernels may still read the block this replaces.
+extern "C++" template <class F, class K> int batch_stage(cpprob_hip_ctx* c, size_t front_bytes, size_t back_bytes, F*& front, K*& back)
+{
+    BatchState* bs = c->batch;
+    const size_t need = front_bytes + back_bytes;
+    if (need > bs->stage_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        dfree(bs->d_stage); bs->stage_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
+        bs->stage_cap = need;
+    }
+    front = front_bytes ? reinterpret_cast<F*>(bs->d_stage) : nullptr;
+    back = back_bytes ? reinterpret_cast<K*>(bs->d_stage + front_bytes) : nullptr;
+    return 0;
+}
+
+// A host call's results: the int8 entries and the doubles copied back (either count may be 0), the stream waited for, the entries
+// widened to int32.
+static int batch_fetch(cpprob_hip_ctx* c, int32_t* h_int32, const int8_t* d_int8, size_t entries, double* h_doubles, const double* d_doubles, size_t n_doubles)
+{
+    std::vector<int8_t> v(entries);
+    if (entries) HIP_TRY(c, hipMemcpyAsync(v.data(), d_int8, entries, hipMemcpyDeviceToHost, c->stream));
+    if (n_doubles) HIP_TRY(c, hipMemcpyAsync(h_doubles, d_doubles, n_doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < entries; ++i) h_int32[i] = v[i];
+    return 0;
+}
+
 int cpprob_hip_batch_paths(cpprob_hip_ctx* c, uint64_t max_particles, int32_t* h_paths, size_t n_entries, double* h_logw, size_t n_weights)
 {
     LANES_OWN(c);
@@ -4550,23 +4581,13 @@ int cpprob_hip_batch_paths(cpprob_hip_ctx* c, uint64_t max_particles, int32_t* h
     if (!h_paths && entries) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (entries == 0) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    BatchState* bs = c->batch;
     // device staging: the weights (8-byte aligned) in front of the int8 entries
-    const size_t w_bytes = batch_round((h_logw ? (size_t)weights : 0) * sizeof(double)), need = w_bytes + (size_t)entries;
-    if (need > bs->stage_cap) {
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
-        bs->stage_cap = need;
-    }
-    double* d_logw = h_logw ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
-    int8_t* d_paths = reinterpret_cast<int8_t*>(bs->d_stage + w_bytes);
+    const size_t n_logw = h_logw ? (size_t)weights : 0;
+    double* d_logw = nullptr;
+    int8_t* d_paths = nullptr;
+    if (int rc = batch_stage(c, batch_round(n_logw * sizeof(double)), (size_t)entries, d_logw, d_paths)) return rc;
     if (int rc = batch_paths_enqueue(c, max_particles, d_paths, d_logw)) return rc;
-    std::vector<int8_t> v((size_t)entries);
-    HIP_TRY(c, hipMemcpyAsync(v.data(), d_paths, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
-    if (h_logw) HIP_TRY(c, hipMemcpyAsync(h_logw, d_logw, (size_t)weights * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < (size_t)entries; ++i) h_paths[i] = v[i];
-    return 0;
+    return batch_fetch(c, h_paths, d_paths, (size_t)entries, h_logw, d_logw, n_logw);
 }
 // ---- backward smoothing of a batch (csrc/batch_smooth.hpp) ------------------------------------------------------------------------
 int cpprob_hip_batch_smooth_layout(const uint32_t* h_T, uint64_t n_problems, uint64_t n_traj, uint64_t* h_first)
@@ -4603,64 +4624,36 @@ static int batch_smooth_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_
     return 0;
 }
 
-// A fixed-lag call's own arguments (cpprob_hip_batch_smooth_lag); the full calls pass none.
-struct BatchSmoothLag { uint64_t lag; const uint32_t* from; uint64_t n_rows; };
-// A statistics call's own (cpprob_hip_batch_smooth_stats): the observes (or nullptr) and the records, both on the device.
-struct BatchSmoothStats { const double* d_obs; double* d_stats; };
-// A trajectory statistics call's own (cpprob_hip_batch_traj_stats): the observes (or nullptr) and the records [B][n_traj][88], on the device.
-struct BatchTrajStats { const double* d_obs; double* d_stats; };
-static_assert(kTrajStats == kSuffStats, "a trajectory's record has the layout of a problem's expected statistics");
-// A running statistics call's own (cpprob_hip_batch_online_stats): the observes of the steps it consumes (or nullptr) and the records, on the device.
-struct BatchOnlineStats { const double* d_obs; double* d_stats; };
-static_assert(kOnlineStats == kSuffStats, "the running record has the layout of a problem's expected statistics");
-// A forecast call's own (cpprob_hip_batch_forecast: horizon > 0; cpprob_hip_batch_predictive: horizon = 0, the first rows wanted and
-// the rows a problem of the output).
-struct BatchForecast { uint64_t horizon; const uint32_t* from; uint64_t n_rows; };
-// A decode call's own (cpprob_hip_batch_decode: full; cpprob_hip_batch_decode_lag: the lag, the first rows wanted and the rows a
-// problem of the output), and its outputs on the device (either may be nullptr).
-struct BatchDecode { bool full; uint64_t lag; const uint32_t* from; uint64_t n_rows; double* d_score; int8_t* d_path; };
+static_assert(kTrajStats == kSuffStats && kOnlineStats == kSuffStats, "a trajectory's record and the running record have the layout of a problem's expected statistics");
+// csrc/batch_pass_plan.hpp includes no kernel header: the constants it states are the kernels'
+namespace bpl = batch_pass_limits;
+static_assert(bpl::kThreads == kThreads && bpl::kWaves == kWaves && bpl::kTile == kTile && bpl::kTrajStatsTile == kTrajStatsTile && bpl::kStats == kSuffStats &&
+              bpl::kBackwardMaxT == kBackwardMaxT && bpl::kBackwardLdsMax == kBackwardLdsMax && bpl::kSmoothCountGroups == kSmoothCountGroups &&
+              bpl::kSmoothLagGridMax == kSmoothLagGridMax && bpl::kPredictiveGridMax == kPredictiveGridMax && bpl::kDecodeTraceGridMax == kDecodeTraceGridMax, "the plan's limits are the kernels'");
 static int batch_decode_prepare(cpprob_hip_ctx* c, size_t word_rows);
+static bool batch_hmm3(const BatchState* bs) { return bs->cfg.model == CPPROB_HIP_MODEL_HMM3; }
+static BatchPassBatch<BatchProblem> batch_pass_batch(const BatchState* bs)
+{
+    return {(size_t)bs->cfg.n_problems, bs->prob.data(), bs->cap_T.data(), bs->counted.data(), bs->decoded.data(), bs->ostats_done.data(), bs->online, batch_masses(&bs->cfg) != 0, bs->T, bs->K};
+}
 
-// Enqueues the descriptors' copy, the counting pass and the smoothing pass on the context's stream; waits for nothing but the pinned
-// slot it writes (the copy that read it kOnlineSlots calls ago) and, where a buffer of its own has to grow, for the calls before it.
-// An online batch's m table is addressed by capacity and kept: the pass counts rows [counted_b, L_b) and moves the watermark.
-// st: the smoothing pass is batch_smooth_stats_kernel (csrc/batch_suffstats.hpp) and nothing else is written.
-// ts: the smoothing pass is batch_traj_stats_kernel (csrc/batch_trajstats.hpp) and nothing else is written.
-// fc: the pass after the counting is batch_forecast_kernel or batch_predictive_kernel (csrc/batch_forecast.hpp); a run batch counts
-// row L - 1 (the forecast) or rows max(from_b, 1) - 1 .. L - 1 (the predictive rows) only.
-// dc: the passes after the counting are batch_decode_forward_kernel and batch_decode_trace_kernel (csrc/batch_decode.hpp); an online
-// batch's words are kept as its m table is: the forward pass walks steps [decoded_b, L_b) and moves that watermark.
-// os: the pass after the counting is batch_online_stats_kernel (csrc/batch_onlinestats.hpp): an online batch's tau is kept as its m
-// table is, the kernel walks steps [ostats_done_b, L_b) -- its observes packed by those counts -- and moves that watermark.
-static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg,
-                                const BatchSmoothStats* st, const BatchForecast* fc, const BatchDecode* dc, const BatchTrajStats* ts,
-                                const BatchOnlineStats* os)
+// What every pass shares, in stream order: the output memsets; the growth of the context's own buffers, each after a wait for the
+// calls before it (their copies and kernels may still read what it replaces); the wait for the pinned slot (the copy that read it
+// kOnlineSlots calls ago); the plan's descriptors with the HMM3 thresholds behind them, their copy and its event; the shared arguments;
+// the counting pass (an online batch's m table is addressed by capacity and kept: rows [counted_b, L_b), and the watermark moves).
+static int batch_pass_prologue(cpprob_hip_ctx* c, const BatchPass& p, BatchPassPlan& pl, BatchSmoothArgs& a)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
-    const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
-    const bool predictive = fc && fc->horizon == 0;
-    const size_t marg_rows = fc ? (size_t)(predictive ? fc->n_rows : fc->horizon) : lg ? (size_t)lg->n_rows : (size_t)bs->T;
-    if (d_marg && marg_rows) HIP_TRY(c, hipMemsetAsync(d_marg, 0, B * marg_rows * (size_t)bs->K * sizeof(double), c->stream));   // rows past the problem's, states >= k
-    const bool with_traj = d_traj && n_traj;
-    // a filtering batch with masses: the run wrote the m table into the workspace, rows by T_max as the per-step tables'; nothing to
-    // count, no table of the context's own
-    const bool kept = batch_masses(&bs->cfg);
-    size_t rows = 0, reached = 0;
-    for (size_t b = 0; b < B; ++b) { reached += (size_t)bs->prob[b].T; rows += bs->online ? (size_t)bs->cap_T[b] : (size_t)bs->prob[b].T; }
-    if (st && reached == 0) HIP_TRY(c, hipMemsetAsync(st->d_stats, 0, B * (size_t)kSuffStats * sizeof(double), c->stream));
-    if (os && reached == 0) HIP_TRY(c, hipMemsetAsync(os->d_stats, 0, B * (size_t)kOnlineStats * sizeof(double), c->stream));
-    if (ts && reached == 0) HIP_TRY(c, hipMemsetAsync(ts->d_stats, 0, B * (size_t)n_traj * (size_t)kTrajStats * sizeof(double), c->stream));
-    // a forecast before the first observes: rows of zeros; the predictive row 0 needs no row of the table and goes on
-    if (fc && !predictive && reached == 0 && with_traj) HIP_TRY(c, hipMemsetAsync(d_traj, 0, B * (size_t)(fc->horizon + 1) * (size_t)n_traj, c->stream));
-    // a decode: a problem of length 0 has score 0; the fixed-lag rows no step owns are -1 (0 is a state)
-    if (dc && dc->d_score) HIP_TRY(c, hipMemsetAsync(dc->d_score, 0, B * sizeof(double), c->stream));
-    if (dc && !dc->full && dc->d_path && dc->n_rows) HIP_TRY(c, hipMemsetAsync(dc->d_path, 0xff, B * (size_t)dc->n_rows, c->stream));
-    if ((reached == 0 && !predictive) || (!d_marg && !with_traj && !st && !dc && !ts && !os)) return 0;   // (an online batch before its first observes, or nothing asked for)
-    const size_t word_rows = kept ? B * (size_t)bs->T : rows;
-    if (kept) rows = 0;
-    if (bytes > bs->sdesc_cap || rows > bs->mass_rows) {
-        // (earlier calls' copies and kernels may still read the buffers this replaces)
+    const bool hmm3 = batch_hmm3(bs), kept = batch_masses(&bs->cfg);
+    pl = batch_pass_plan(batch_pass_batch(bs), p);
+    if (pl.marg_bytes) HIP_TRY(c, hipMemsetAsync(p.d_marg, 0, pl.marg_bytes, c->stream));
+    if (pl.stats_bytes) HIP_TRY(c, hipMemsetAsync(p.d_stats, 0, pl.stats_bytes, c->stream));
+    if (pl.traj_bytes) HIP_TRY(c, hipMemsetAsync(p.d_traj, 0, pl.traj_bytes, c->stream));
+    if (pl.score_bytes) HIP_TRY(c, hipMemsetAsync(p.d_score, 0, pl.score_bytes, c->stream));
+    if (pl.path_bytes) HIP_TRY(c, hipMemsetAsync(p.d_path, 0xff, pl.path_bytes, c->stream));
+    if (pl.done) return 0;
+    if (bytes > bs->sdesc_cap || pl.mass_rows > bs->mass_rows) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (bytes > bs->sdesc_cap) {
             dfree(bs->d_sdesc); bs->sdesc_cap = 0;
@@ -4670,16 +4663,16 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
             for (hipEvent_t& e : bs->sdesc_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
             bs->sdesc_cap = bytes; bs->n_smooth = 0;
         }
-        if (rows > bs->mass_rows) {
+        if (pl.mass_rows > bs->mass_rows) {
             dfree(bs->d_mass); bs->mass_rows = 0;
             bs->counted.assign(B, 0);                                       // (the rows counted so far went with the table)
-            HIP_TRY(c, hipMalloc(&bs->d_mass, rows * 8 * sizeof(double)));
-            bs->mass_rows = rows;
+            HIP_TRY(c, hipMalloc(&bs->d_mass, pl.mass_rows * 8 * sizeof(double)));
+            bs->mass_rows = pl.mass_rows;
         }
     }
-    if (dc) { if (int rc = batch_decode_prepare(c, word_rows)) return rc; }
-    if (os && B > bs->tau_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (earlier calls' kernels may still read the buffer this replaces)
+    if (p.decodes()) { if (int rc = batch_decode_prepare(c, pl.word_rows)) return rc; }
+    if (p.kind == BatchPass::OnlineStats && B > bs->tau_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         dfree(bs->d_tau); bs->tau_cap = 0;
         bs->ostats_done.assign(B, 0);
         HIP_TRY(c, hipMalloc(&bs->d_tau, B * (size_t)kOnlineTau * sizeof(double)));
@@ -4687,35 +4680,8 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     }
     const int slot = (int)(bs->n_smooth % BatchState::kOnlineSlots);
     if (bs->n_smooth >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->sdesc_done[slot]));
-    char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap;
-    BatchSmoothProblem* pd = reinterpret_cast<BatchSmoothProblem*>(sl);
-    const size_t thr_at = bs->sdesc_cap - thr_bytes;
-    int64_t at = 0, at_traj = 0, at_fresh = 0;
-    int range_top = 0, W_top = 0;
-    int64_t items_top = 0;
-    for (size_t b = 0; b < B; ++b) {
-        const BatchProblem& pr = bs->prob[b];
-        const int L = pr.T, W = lg ? (int)std::min<uint64_t>(lg->lag + 1, (uint64_t)L) : L;
-        const int mfrom = lg && lg->from ? (int)lg->from[b] : (fc && fc->from ? (int)fc->from[b] : (dc && dc->from ? (int)dc->from[b] : 0));
-        pd[b].T = L; pd[b].n = pr.n; pd[b].store = pr.store; pd[b].rows = at; pd[b].trows = at_traj;
-        pd[b].lo = L - W; pd[b].mfrom = mfrom; pd[b].cto = L;
-        if (dc) pd[b].lo = bs->online ? (int)std::min<uint32_t>(bs->decoded[b], (uint32_t)L) : 0;   // the forward pass's first step
-        if (os) {                                                           // the first step to consume and its observe
-            pd[b].lo = (int)std::min<uint32_t>(bs->ostats_done[b], (uint32_t)L);
-            pd[b].trows = at_fresh;
-            at_fresh += L - pd[b].lo;
-        }
-        // the rows the pass owes: an online batch's new ones; a run batch's -- nothing is kept -- those this call reads
-        if (kept) { pd[b].rows = (int64_t)b * bs->T; pd[b].store = 0; pd[b].cfrom = L; }
-        else if (bs->online) pd[b].cfrom = (int)bs->counted[b];
-        else if (fc) pd[b].cfrom = predictive ? std::min(std::max(mfrom, 1) - 1, L) : std::max(L - 1, 0);
-        else pd[b].cfrom = lg ? std::min(d_marg ? mfrom : L, with_traj ? L - W : L) : 0;
-        at += bs->online ? (int64_t)bs->cap_T[b] : (int64_t)L;
-        at_traj += W;
-        range_top = std::max(range_top, pd[b].cto - pd[b].cfrom);
-        W_top = std::max(W_top, W);
-        if (lg && mfrom < L) items_top = std::max<int64_t>(items_top, std::max<int64_t>(1, (int64_t)L - mfrom - (int64_t)lg->lag));
-    }
+    char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap; const size_t thr_at = bs->sdesc_cap - thr_bytes;
+    batch_pass_describe(batch_pass_batch(bs), p, reinterpret_cast<BatchSmoothProblem*>(sl), pl);      // (after the growth: it reads the watermarks)
     // CPPROB_HIP_MODEL_HMM3: its thresholds as a table row set of CPPROB_HIP_MODEL_HMM_TABLE ([k][8], entries 0..k-2), behind the descriptors
     uint64_t* h3 = reinterpret_cast<uint64_t*>(sl + thr_at);
     for (int i = 0; i < 64; ++i) h3[i] = ~0ull;
@@ -4723,122 +4689,143 @@ static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     HIP_TRY(c, hipMemcpyAsync(bs->d_sdesc, sl, bs->sdesc_cap, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(bs->sdesc_done[slot], c->stream));
     ++bs->n_smooth;
-    BatchSmoothArgs a{};
     a.desc = reinterpret_cast<const BatchSmoothProblem*>(bs->d_sdesc);
     a.values = kept ? nullptr : reinterpret_cast<const int8_t*>(bs->d_ws + bs->lay.values);
     a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
     a.thr = hmm3 ? reinterpret_cast<const uint64_t*>(bs->d_sdesc + thr_at) : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
     a.thr_stride = !hmm3 && bs->described ? 64 : 0;
     a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
-    a.mass = kept ? reinterpret_cast<double*>(bs->d_ws + bs->lay.mass) : bs->d_mass; a.marg = d_marg; a.traj = with_traj ? d_traj : nullptr;
-    a.draw_base = kBackwardDrawBase + (draw_index << 24);
-    a.T_max = bs->T; a.k = hmm3 ? 3 : bs->hk; a.spp = bs->K; a.n_traj = (int)n_traj;
-    a.marg_rows = (int)marg_rows; a.lag = lg ? (int)lg->lag : 0;
-    a.lds_bytes = (int)std::min<int64_t>((int64_t)W_top * 64, kBackwardLdsMax);
-    // the counting pass: at least ~kSmoothCountGroups workgroups where the batch owes that many rows, a workgroup walking the rows gridDim.y apart
-    if (range_top > 0 && !kept) {
-        const unsigned gy = (unsigned)std::min<uint64_t>((uint64_t)range_top, std::max<uint64_t>(8, ((uint64_t)kSmoothCountGroups + B - 1) / B));
-        hipLaunchKernelGGL(batch_smooth_count_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
+    a.mass = kept ? reinterpret_cast<double*>(bs->d_ws + bs->lay.mass) : bs->d_mass; a.marg = p.d_marg; a.traj = p.with_traj() ? p.d_traj : nullptr;
+    a.draw_base = kBackwardDrawBase + (p.draw_index << 24);
+    a.T_max = bs->T; a.k = hmm3 ? 3 : bs->hk; a.spp = bs->K; a.n_traj = (int)p.n_traj;
+    a.marg_rows = (int)pl.marg_rows; a.lag = p.lagged() ? pl.lag : 0; a.lds_bytes = pl.lds_bytes;
+    if (pl.count_gy) {
+        hipLaunchKernelGGL(batch_smooth_count_kernel, dim3((unsigned)B, pl.count_gy), dim3(kThreads), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());
-        bs->smooth_gy_count = gy;
+        bs->smooth_gy_count = pl.count_gy;
         if (bs->online) for (size_t b = 0; b < B; ++b) bs->counted[b] = (uint32_t)bs->prob[b].T;
     }
-    if (os) {
-        BatchOnlineStatsArgs oa{};
-        oa.desc = a.desc; oa.mass = a.mass; oa.thr = a.thr; oa.obs = os->d_obs; oa.tau = bs->d_tau; oa.stats = os->d_stats;
-        oa.B = (int)B; oa.k = a.k; oa.thr_stride = a.thr_stride;
-        // a wavefront a problem; a problem without new steps is read out of its tau
-        hipLaunchKernelGGL(batch_online_stats_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, oa);
+    return 0;
+}
+
+// The launchers, one a pass family: each builds its own arguments from the shared ones, launches with the plan's grid, records the
+// grid where a call reads it back (cpprob_hip_batch_smooth_grid, _traj_stats_grid, _pass_grid) and moves its watermark.
+static int batch_pass_smooth(cpprob_hip_ctx* c, const BatchPass& p, const BatchPassPlan& pl, BatchSmoothArgs a)
+{
+    BatchState* bs = c->batch; const unsigned B = (unsigned)bs->cfg.n_problems;
+    if (pl.lag_gy) {
+        hipLaunchKernelGGL(batch_smooth_lag_kernel, dim3(B, pl.lag_gy), dim3(kThreads), 0, c->stream, a);
         HIP_TRY(c, hipGetLastError());
-        for (size_t b = 0; b < B; ++b) bs->ostats_done[b] = (uint32_t)bs->prob[b].T;
-        return 0;
+        bs->smooth_gy_lag = pl.lag_gy;
     }
-    if (dc) {
-        BatchDecodeArgs da{};
-        da.desc = a.desc; da.mass = a.mass; da.tab = a.tab; da.lp = bs->d_lp; da.lp0 = bs->lp0; da.v = bs->d_v; da.words = bs->d_words;
-        da.score = dc->d_score; da.path = dc->d_path;
-        da.B = (int)B; da.T_max = a.T_max; da.k = a.k; da.lp_stride = bs->h_lp.size() > 64 ? 64 : 0;
-        da.full = dc->full ? 1 : 0; da.lag = (int)std::min<uint64_t>(dc->lag, (uint64_t)kBackwardMaxT); da.n_rows = (int)dc->n_rows;
-        // a wavefront a problem; it also leaves the score, so it runs where no step is new
-        hipLaunchKernelGGL(batch_decode_forward_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, da);
-        HIP_TRY(c, hipGetLastError());
-        bs->decode_gx_forward = (unsigned)((B + kWaves - 1) / kWaves);
-        if (bs->online) for (size_t b = 0; b < B; ++b) bs->decoded[b] = (uint32_t)bs->prob[b].T;
-        if (!dc->d_path) return 0;
-        // row 0 of the grid: the item of end L - 1; the ends before it a lane each, (gridDim.y - 1) * kThreads apart
-        int64_t lane_items = 0;
-        if (!dc->full) for (size_t b = 0; b < B; ++b) lane_items = std::max<int64_t>(lane_items, (int64_t)pd[b].T - 1 - (int64_t)pd[b].mfrom - (int64_t)da.lag);
-        const unsigned gy = 1u + (unsigned)std::min<int64_t>((lane_items + kThreads - 1) / kThreads, kDecodeTraceGridMax);
-        hipLaunchKernelGGL(batch_decode_trace_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, da);
-        HIP_TRY(c, hipGetLastError());
-        bs->decode_gy_trace = gy;
-        return 0;
-    }
-    if (fc) {
-        BatchForecastArgs fa{};
-        fa.desc = a.desc; fa.mass = a.mass; fa.thr = a.thr; fa.seeds = a.seeds; fa.marg = d_marg; fa.traj = a.traj;
-        fa.draw_base = kForecastDrawBase + (draw_index << 24);
-        fa.k = a.k; fa.spp = a.spp; fa.thr_stride = a.thr_stride; fa.n_traj = (int)n_traj; fa.H = (int)fc->horizon; fa.rows = (int)marg_rows;
-        if (predictive) {
-            // (problem, step) a wavefront: the steps gridDim.y * kWaves apart where a problem owes more rows than the grid holds
-            int64_t owed = 0;
-            for (size_t b = 0; b < B; ++b) owed = std::max<int64_t>(owed, (int64_t)pd[b].T + 1 - (int64_t)pd[b].mfrom);
-            if (owed <= 0) return 0;
-            const unsigned gy = (unsigned)std::min<int64_t>((owed + kWaves - 1) / kWaves, kPredictiveGridMax);
-            hipLaunchKernelGGL(batch_predictive_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, fa);
-            HIP_TRY(c, hipGetLastError());
-            bs->predictive_gy = gy;
-        } else {
-            const unsigned tiles = fa.traj ? (unsigned)((n_traj + kTile - 1) / kTile) : 0u;
-            if (hmm3) hipLaunchKernelGGL(batch_forecast_kernel<3>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), 0, c->stream, fa);
-            else hipLaunchKernelGGL(batch_forecast_kernel<8>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), 0, c->stream, fa);
-            HIP_TRY(c, hipGetLastError());
-            bs->forecast_gy = 1 + tiles;
-        }
-        return 0;
-    }
-    if (lg && d_marg && items_top > 0) {
-        // (problem, end step) a wavefront: the ends gridDim.y * kWaves apart where a problem has more than the grid holds
-        const unsigned gy = (unsigned)std::min<int64_t>((items_top + kWaves - 1) / kWaves, kSmoothLagGridMax);
-        hipLaunchKernelGGL(batch_smooth_lag_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
-        HIP_TRY(c, hipGetLastError());
-        bs->smooth_gy_lag = gy;
-    }
-    if (st) {
-        BatchSmoothStatsArgs sa{};
-        sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = st->d_obs; sa.stats = st->d_stats;
-        sa.B = (int)B; sa.k = a.k; sa.thr_stride = a.thr_stride;
-        hipLaunchKernelGGL(batch_smooth_stats_kernel, dim3((unsigned)((B + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, sa);
-        HIP_TRY(c, hipGetLastError());
-        return 0;
-    }
-    if (ts) {
-        BatchTrajStatsArgs ta{};
-        ta.desc = a.desc; ta.mass = a.mass; ta.thr = a.thr; ta.seeds = a.seeds; ta.obs = ts->d_obs; ta.stats = ts->d_stats;
-        ta.draw_base = a.draw_base; ta.k = a.k; ta.thr_stride = a.thr_stride; ta.n_traj = (int)n_traj; ta.lds_bytes = a.lds_bytes;
-        // a lane a trajectory: the tiles cover n_traj, a problem of length 0 writes its zero records
-        const unsigned gy = (unsigned)((n_traj + kTrajStatsTile - 1) / kTrajStatsTile);
-        if (hmm3) hipLaunchKernelGGL(batch_traj_stats_kernel<3>, dim3((unsigned)B, gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, ta);
-        else hipLaunchKernelGGL(batch_traj_stats_kernel<8>, dim3((unsigned)B, gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, ta);
-        HIP_TRY(c, hipGetLastError());
-        bs->traj_stats_gy = gy;
-        return 0;
-    }
-    if (lg && !a.traj) return 0;
-    if (lg) a.marg = nullptr;                                               // (the pass below: the window's trajectories only)
-    const unsigned tiles = a.traj ? (unsigned)((n_traj + kTile - 1) / kTile) : 0u;
-    if (hmm3) hipLaunchKernelGGL(batch_smooth_kernel<3>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
-    else hipLaunchKernelGGL(batch_smooth_kernel<8>, dim3((unsigned)B, 1 + tiles), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
+    if (!pl.smooth_gy) return 0;
+    if (p.lagged()) a.marg = nullptr;                                       // (the pass below: the window's trajectories only)
+    if (batch_hmm3(bs)) hipLaunchKernelGGL(batch_smooth_kernel<3>, dim3(B, pl.smooth_gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
+    else hipLaunchKernelGGL(batch_smooth_kernel<8>, dim3(B, pl.smooth_gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }
 
-// The modes that were there before os, each optional (the running statistics pass all eleven arguments).
-static int batch_smooth_enqueue(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marg, int8_t* d_traj, const BatchSmoothLag* lg = nullptr,
-                                const BatchSmoothStats* st = nullptr, const BatchForecast* fc = nullptr, const BatchDecode* dc = nullptr,
-                                const BatchTrajStats* ts = nullptr)
+static int batch_pass_stats(cpprob_hip_ctx* c, const BatchPass& p, const BatchPassPlan& pl, const BatchSmoothArgs& a)
 {
-    return batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj, lg, st, fc, dc, ts, nullptr);
+    BatchSmoothStatsArgs sa{};
+    sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = p.d_obs; sa.stats = p.d_stats;
+    sa.B = (int)c->batch->cfg.n_problems; sa.k = a.k; sa.thr_stride = a.thr_stride;
+    hipLaunchKernelGGL(batch_smooth_stats_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, sa);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+static int batch_pass_traj_stats(cpprob_hip_ctx* c, const BatchPass& p, const BatchPassPlan& pl, const BatchSmoothArgs& a)
+{
+    BatchState* bs = c->batch; const unsigned B = (unsigned)bs->cfg.n_problems;
+    BatchTrajStatsArgs ta{};
+    ta.desc = a.desc; ta.mass = a.mass; ta.thr = a.thr; ta.seeds = a.seeds; ta.obs = p.d_obs; ta.stats = p.d_stats;
+    ta.draw_base = a.draw_base; ta.k = a.k; ta.thr_stride = a.thr_stride; ta.n_traj = (int)p.n_traj; ta.lds_bytes = a.lds_bytes;
+    if (batch_hmm3(bs)) hipLaunchKernelGGL(batch_traj_stats_kernel<3>, dim3(B, pl.traj_stats_gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, ta);
+    else hipLaunchKernelGGL(batch_traj_stats_kernel<8>, dim3(B, pl.traj_stats_gy), dim3(kThreads), (size_t)a.lds_bytes, c->stream, ta);
+    HIP_TRY(c, hipGetLastError());
+    bs->traj_stats_gy = pl.traj_stats_gy;
+    return 0;
+}
+
+// (a problem without new steps is read out of its tau)
+static int batch_pass_online_stats(cpprob_hip_ctx* c, const BatchPass& p, const BatchPassPlan& pl, const BatchSmoothArgs& a)
+{
+    BatchState* bs = c->batch; const size_t B = bs->cfg.n_problems;
+    BatchOnlineStatsArgs oa{};
+    oa.desc = a.desc; oa.mass = a.mass; oa.thr = a.thr; oa.obs = p.d_obs; oa.tau = bs->d_tau; oa.stats = p.d_stats;
+    oa.B = (int)B; oa.k = a.k; oa.thr_stride = a.thr_stride;
+    hipLaunchKernelGGL(batch_online_stats_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, oa);
+    HIP_TRY(c, hipGetLastError());
+    for (size_t b = 0; b < B; ++b) bs->ostats_done[b] = (uint32_t)bs->prob[b].T;
+    return 0;
+}
+
+// (a run batch counts row L - 1 -- the forecast -- or rows max(from_b, 1) - 1 .. L - 1 -- the predictive rows -- only)
+static int batch_pass_forecast(cpprob_hip_ctx* c, const BatchPass& p, const BatchPassPlan& pl, const BatchSmoothArgs& a)
+{
+    BatchState* bs = c->batch; const unsigned B = (unsigned)bs->cfg.n_problems;
+    BatchForecastArgs fa{};
+    fa.desc = a.desc; fa.mass = a.mass; fa.thr = a.thr; fa.seeds = a.seeds; fa.marg = p.d_marg; fa.traj = a.traj;
+    fa.draw_base = kForecastDrawBase + (p.draw_index << 24);
+    fa.k = a.k; fa.spp = a.spp; fa.thr_stride = a.thr_stride; fa.n_traj = (int)p.n_traj; fa.H = (int)p.horizon; fa.rows = (int)pl.marg_rows;
+    if (p.kind == BatchPass::Predictive) {
+        if (!pl.predictive_gy) return 0;                                    // (nothing owed anywhere)
+        hipLaunchKernelGGL(batch_predictive_kernel, dim3(B, pl.predictive_gy), dim3(kThreads), 0, c->stream, fa);
+    }
+    else if (batch_hmm3(bs)) hipLaunchKernelGGL(batch_forecast_kernel<3>, dim3(B, pl.forecast_gy), dim3(kThreads), 0, c->stream, fa);
+    else hipLaunchKernelGGL(batch_forecast_kernel<8>, dim3(B, pl.forecast_gy), dim3(kThreads), 0, c->stream, fa);
+    HIP_TRY(c, hipGetLastError());
+    bs->predictive_gy = pl.predictive_gy; bs->forecast_gy = pl.forecast_gy;
+    return 0;
+}
+
+// (an online batch's forward pass walks steps [decoded_b, L_b) and moves that watermark)
+static int batch_pass_decode(cpprob_hip_ctx* c, const BatchPass& p, const BatchPassPlan& pl, const BatchSmoothArgs& a)
+{
+    BatchState* bs = c->batch; const size_t B = bs->cfg.n_problems;
+    BatchDecodeArgs da{};
+    da.desc = a.desc; da.mass = a.mass; da.tab = a.tab; da.lp = bs->d_lp; da.lp0 = bs->lp0; da.v = bs->d_v; da.words = bs->d_words;
+    da.score = p.d_score; da.path = p.d_path;
+    da.B = (int)B; da.T_max = a.T_max; da.k = a.k; da.lp_stride = bs->h_lp.size() > 64 ? 64 : 0;
+    da.full = p.kind == BatchPass::Decode ? 1 : 0; da.lag = pl.lag; da.n_rows = (int)p.n_rows;
+    hipLaunchKernelGGL(batch_decode_forward_kernel, dim3(pl.decode_gx), dim3(kThreads), 0, c->stream, da);
+    HIP_TRY(c, hipGetLastError());
+    bs->decode_gx_forward = pl.decode_gx;
+    if (bs->online) for (size_t b = 0; b < B; ++b) bs->decoded[b] = (uint32_t)bs->prob[b].T;
+    if (!pl.trace_gy) return 0;
+    hipLaunchKernelGGL(batch_decode_trace_kernel, dim3((unsigned)B, pl.trace_gy), dim3(kThreads), 0, c->stream, da);
+    HIP_TRY(c, hipGetLastError());
+    bs->decode_gy_trace = pl.trace_gy;
+    return 0;
+}
+
+// Enqueues one pass of the batch on the context's stream: the prologue, then the pass's own launches.  It waits for nothing but the
+// pinned slot it writes and, where a buffer of its own has to grow, for the calls before it.
+static int batch_smooth_enqueue(cpprob_hip_ctx* c, const BatchPass& p)
+{
+    BatchPassPlan pl; BatchSmoothArgs a{};
+    if (int rc = batch_pass_prologue(c, p, pl, a)) return rc;
+    if (pl.done) return 0;
+    switch (p.kind) {
+    case BatchPass::Smooth: case BatchPass::SmoothLag: return batch_pass_smooth(c, p, pl, a);
+    case BatchPass::Stats: return batch_pass_stats(c, p, pl, a);
+    case BatchPass::TrajStats: return batch_pass_traj_stats(c, p, pl, a);
+    case BatchPass::OnlineStats: return batch_pass_online_stats(c, p, pl, a);
+    case BatchPass::Forecast: case BatchPass::Predictive: return batch_pass_forecast(c, p, pl, a);
+    case BatchPass::Decode: case BatchPass::DecodeLag: return batch_pass_decode(c, p, pl, a);
+    }
+    return 0;
+}
+
+// The host form of a pass that leaves rows of doubles (p.d_marg) and int8 entries (p.d_traj), either count may be 0: staged on the
+// device, the doubles in front of the entries, enqueued and read back.
+static int batch_pass_rows_host(cpprob_hip_ctx* c, BatchPass p, double* h_doubles, size_t n_doubles, int32_t* h_entries, size_t n_entries)
+{
+    if (int rc = batch_stage(c, batch_round(n_doubles * sizeof(double)), n_entries, p.d_marg, p.d_traj)) return rc;
+    if (int rc = batch_smooth_enqueue(c, p)) return rc;
+    return batch_fetch(c, h_entries, p.d_traj, n_entries, h_doubles, p.d_marg, n_doubles);
 }
 
 int cpprob_hip_batch_smooth_device(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles, int8_t* d_traj, size_t n_entries)
@@ -4848,7 +4835,7 @@ int cpprob_hip_batch_smooth_device(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t 
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_check(c, n_traj, draw_index, d_marginals != nullptr, n_doubles, d_traj != nullptr, n_entries, doubles, entries)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    return batch_smooth_enqueue(c, n_traj, draw_index, d_marginals, d_traj);
+    return batch_smooth_enqueue(c, BatchPass::smooth(n_traj, draw_index, d_marginals, d_traj));
 }
 
 int cpprob_hip_batch_smooth(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, double* h_marginals, size_t n_doubles, int32_t* h_traj, size_t n_entries)
@@ -4860,23 +4847,7 @@ int cpprob_hip_batch_smooth(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_in
     const bool with_traj = h_traj && entries;
     if (!h_marginals && !with_traj) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    BatchState* bs = c->batch;
-    // device staging: the marginals (8-byte aligned) in front of the int8 entries
-    const size_t m_bytes = batch_round((h_marginals ? (size_t)doubles : 0) * sizeof(double)), need = m_bytes + (with_traj ? (size_t)entries : 0);
-    if (need > bs->stage_cap) {
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
-        bs->stage_cap = need;
-    }
-    double* d_marg = h_marginals ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
-    int8_t* d_traj = with_traj ? reinterpret_cast<int8_t*>(bs->d_stage + m_bytes) : nullptr;
-    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj)) return rc;
-    std::vector<int8_t> v(with_traj ? (size_t)entries : 0);
-    if (with_traj) HIP_TRY(c, hipMemcpyAsync(v.data(), d_traj, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
-    if (h_marginals) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
-    return 0;
+    return batch_pass_rows_host(c, BatchPass::smooth(n_traj, draw_index, nullptr, nullptr), h_marginals, h_marginals ? (size_t)doubles : 0, h_traj, with_traj ? (size_t)entries : 0);
 }
 
 // cpprob_hip_batch_smooth_lag's arguments against the batch's state (batch_smooth_check first), then the totals against the capacities.
@@ -4910,8 +4881,7 @@ int cpprob_hip_batch_smooth_lag_device(cpprob_hip_ctx* c, uint64_t lag, const ui
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_lag_check(c, lag, h_from, n_rows, n_traj, draw_index, d_marginals != nullptr, n_doubles, d_traj != nullptr, n_entries, doubles, entries)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const BatchSmoothLag lg{lag, h_from, n_rows};
-    return batch_smooth_enqueue(c, n_traj, draw_index, d_marginals, d_traj, &lg);
+    return batch_smooth_enqueue(c, BatchPass::smooth_lag(lag, h_from, n_rows, n_traj, draw_index, d_marginals, d_traj));
 }
 
 int cpprob_hip_batch_smooth_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, uint64_t n_traj, uint64_t draw_index,
@@ -4924,24 +4894,8 @@ int cpprob_hip_batch_smooth_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t*
     const bool with_marg = h_marginals && doubles, with_traj = h_traj && entries;
     if (!with_marg && !with_traj) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    BatchState* bs = c->batch;
-    // device staging: the marginals (8-byte aligned) in front of the int8 entries
-    const size_t m_bytes = batch_round((with_marg ? (size_t)doubles : 0) * sizeof(double)), need = m_bytes + (with_traj ? (size_t)entries : 0);
-    if (need > bs->stage_cap) {
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
-        bs->stage_cap = need;
-    }
-    double* d_marg = with_marg ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
-    int8_t* d_traj = with_traj ? reinterpret_cast<int8_t*>(bs->d_stage + m_bytes) : nullptr;
-    const BatchSmoothLag lg{lag, h_from, n_rows};
-    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj, &lg)) return rc;
-    std::vector<int8_t> v(with_traj ? (size_t)entries : 0);
-    if (with_traj) HIP_TRY(c, hipMemcpyAsync(v.data(), d_traj, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
-    if (with_marg) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
-    return 0;
+    return batch_pass_rows_host(c, BatchPass::smooth_lag(lag, h_from, n_rows, n_traj, draw_index, nullptr, nullptr), h_marginals, with_marg ? (size_t)doubles : 0, h_traj,
+                                with_traj ? (size_t)entries : 0);
 }
 
 // cpprob_hip_batch_smooth_stats' arguments against the batch's state (batch_smooth_check first).
@@ -4960,6 +4914,14 @@ static int batch_smooth_stats_check(cpprob_hip_ctx* c, bool with_obs, size_t n_o
     return 0;
 }
 
+// A statistics call's device staging: the records in front of the observes, which it uploads (none of them: d_obs = nullptr).
+static int batch_stage_observes(cpprob_hip_ctx* c, size_t n_stats, const double* h_observes, size_t n_observes, double*& d_stats, double*& d_obs)
+{
+    if (int rc = batch_stage(c, n_stats * sizeof(double), (h_observes ? n_observes : 0) * sizeof(double), d_stats, d_obs)) return rc;
+    if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
 int cpprob_hip_batch_smooth_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
 {
     LANES_OWN(c);
@@ -4967,8 +4929,7 @@ int cpprob_hip_batch_smooth_stats_device(cpprob_hip_ctx* c, const double* d_obse
     uint64_t rows = 0;
     if (int rc = batch_smooth_stats_check(c, d_observes != nullptr, n_observes, d_stats, n_doubles, rows)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const BatchSmoothStats st{d_observes, d_stats};
-    return batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, &st);
+    return batch_smooth_enqueue(c, BatchPass::stats(d_observes, d_stats));
 }
 
 int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
@@ -4978,23 +4939,11 @@ int cpprob_hip_batch_smooth_stats(cpprob_hip_ctx* c, const double* h_observes, s
     uint64_t rows = 0;
     if (int rc = batch_smooth_stats_check(c, h_observes != nullptr, n_observes, h_stats, n_doubles, rows)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    BatchState* bs = c->batch;
-    // device staging: the records in front of the observes
-    const size_t s_bytes = (size_t)bs->cfg.n_problems * kSuffStats * sizeof(double), need = s_bytes + (h_observes ? (size_t)rows * sizeof(double) : 0);
-    if (need > bs->stage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
-        bs->stage_cap = need;
-    }
-    double* d_stats = reinterpret_cast<double*>(bs->d_stage);
-    double* d_obs = h_observes && rows ? reinterpret_cast<double*>(bs->d_stage + s_bytes) : nullptr;
-    if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const BatchSmoothStats st{d_obs, d_stats};
-    if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, &st)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kSuffStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)rows, d_stats, d_obs)) return rc;
+    if (int rc = batch_smooth_enqueue(c, BatchPass::stats(d_obs, d_stats))) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
 }
 
 // ---- running statistics of an online batch (csrc/batch_onlinestats.hpp) -------------------------------------------------------------
@@ -5024,8 +4973,7 @@ int cpprob_hip_batch_online_stats_device(cpprob_hip_ctx* c, const double* d_obse
     uint64_t fresh = 0;
     if (int rc = batch_online_stats_check(c, d_observes, n_observes, d_stats, n_doubles, fresh)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const BatchOnlineStats os{fresh ? d_observes : nullptr, d_stats};
-    return batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &os);
+    return batch_smooth_enqueue(c, BatchPass::online_stats(fresh ? d_observes : nullptr, d_stats));
 }
 
 int cpprob_hip_batch_online_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
@@ -5035,24 +4983,11 @@ int cpprob_hip_batch_online_stats(cpprob_hip_ctx* c, const double* h_observes, s
     uint64_t fresh = 0;
     if (int rc = batch_online_stats_check(c, h_observes, n_observes, h_stats, n_doubles, fresh)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    BatchState* bs = c->batch;
-    // device staging: the records in front of the observes
-    const bool with_obs = h_observes && fresh;
-    const size_t s_bytes = (size_t)bs->cfg.n_problems * kOnlineStats * sizeof(double), need = s_bytes + (with_obs ? (size_t)fresh * sizeof(double) : 0);
-    if (need > bs->stage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
-        bs->stage_cap = need;
-    }
-    double* d_stats = reinterpret_cast<double*>(bs->d_stage);
-    double* d_obs = with_obs ? reinterpret_cast<double*>(bs->d_stage + s_bytes) : nullptr;
-    if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, (size_t)fresh * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const BatchOnlineStats os{d_obs, d_stats};
-    if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &os)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kOnlineStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)fresh, d_stats, d_obs)) return rc;
+    if (int rc = batch_smooth_enqueue(c, BatchPass::online_stats(d_obs, d_stats))) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
 }
 
 int cpprob_hip_batch_online_stats_progress(cpprob_hip_ctx* c, uint32_t* h_done)
@@ -5091,8 +5026,7 @@ int cpprob_hip_batch_traj_stats_device(cpprob_hip_ctx* c, uint64_t n_traj, uint6
     uint64_t rows = 0, need = 0;
     if (int rc = batch_traj_stats_check(c, n_traj, draw_index, d_observes != nullptr, n_observes, d_stats, n_doubles, rows, need)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const BatchTrajStats ts{rows ? d_observes : nullptr, d_stats};
-    return batch_smooth_enqueue(c, n_traj, draw_index, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ts);
+    return batch_smooth_enqueue(c, BatchPass::traj_stats(n_traj, draw_index, rows ? d_observes : nullptr, d_stats));
 }
 
 int cpprob_hip_batch_traj_stats(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t draw_index, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
@@ -5102,23 +5036,10 @@ int cpprob_hip_batch_traj_stats(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t dra
     uint64_t rows = 0, need = 0;
     if (int rc = batch_traj_stats_check(c, n_traj, draw_index, h_observes != nullptr, n_observes, h_stats, n_doubles, rows, need)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    BatchState* bs = c->batch;
-    // device staging: the records in front of the observes
-    const size_t s_bytes = (size_t)need * sizeof(double), bytes = s_bytes + (h_observes ? (size_t)rows * sizeof(double) : 0);
-    if (bytes > bs->stage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, bytes));
-        bs->stage_cap = bytes;
-    }
-    double* d_stats = reinterpret_cast<double*>(bs->d_stage);
-    double* d_obs = h_observes && rows ? reinterpret_cast<double*>(bs->d_stage + s_bytes) : nullptr;
-    if (d_obs) HIP_TRY(c, hipMemcpyAsync(d_obs, h_observes, (size_t)rows * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const BatchTrajStats ts{d_obs, d_stats};
-    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &ts)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(h_stats, d_stats, s_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, (size_t)need, h_observes, (size_t)rows, d_stats, d_obs)) return rc;
+    if (int rc = batch_smooth_enqueue(c, BatchPass::traj_stats(n_traj, draw_index, d_obs, d_stats))) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, (size_t)need);
 }
 
 // ---- forecasts of a batch (csrc/batch_forecast.hpp) ---------------------------------------------------------------------------------
@@ -5137,22 +5058,6 @@ static int batch_forecast_check(cpprob_hip_ctx* c, uint64_t horizon, uint64_t n_
     return 0;
 }
 
-// The device staging of a host call: the doubles (8-byte aligned) in front of the int8 entries.
-static int batch_forecast_stage(cpprob_hip_ctx* c, size_t doubles, size_t entries, double*& d_marg, int8_t*& d_traj)
-{
-    BatchState* bs = c->batch;
-    const size_t m_bytes = batch_round(doubles * sizeof(double)), need = m_bytes + entries;
-    if (need > bs->stage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (an earlier call's kernels may still read the block this replaces)
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
-        bs->stage_cap = need;
-    }
-    d_marg = doubles ? reinterpret_cast<double*>(bs->d_stage) : nullptr;
-    d_traj = entries ? reinterpret_cast<int8_t*>(bs->d_stage + m_bytes) : nullptr;
-    return 0;
-}
-
 int cpprob_hip_batch_forecast_device(cpprob_hip_ctx* c, uint64_t horizon, uint64_t n_traj, uint64_t draw_index, double* d_marginals, size_t n_doubles,
                                      int8_t* d_traj, size_t n_entries)
 {
@@ -5161,8 +5066,7 @@ int cpprob_hip_batch_forecast_device(cpprob_hip_ctx* c, uint64_t horizon, uint64
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_forecast_check(c, horizon, n_traj, draw_index, d_marginals != nullptr, n_doubles, d_traj != nullptr, n_entries, doubles, entries)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const BatchForecast fc{horizon, nullptr, 0};
-    return batch_smooth_enqueue(c, n_traj, draw_index, d_marginals, d_traj, nullptr, nullptr, &fc);
+    return batch_smooth_enqueue(c, BatchPass::forecast(horizon, n_traj, draw_index, d_marginals, d_traj));
 }
 
 int cpprob_hip_batch_forecast(cpprob_hip_ctx* c, uint64_t horizon, uint64_t n_traj, uint64_t draw_index, double* h_marginals, size_t n_doubles,
@@ -5175,17 +5079,8 @@ int cpprob_hip_batch_forecast(cpprob_hip_ctx* c, uint64_t horizon, uint64_t n_tr
     const bool with_traj = h_traj && entries;
     if (!h_marginals && !with_traj) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    double* d_marg = nullptr;
-    int8_t* d_traj = nullptr;
-    if (int rc = batch_forecast_stage(c, h_marginals ? (size_t)doubles : 0, with_traj ? (size_t)entries : 0, d_marg, d_traj)) return rc;
-    const BatchForecast fc{horizon, nullptr, 0};
-    if (int rc = batch_smooth_enqueue(c, n_traj, draw_index, d_marg, d_traj, nullptr, nullptr, &fc)) return rc;
-    std::vector<int8_t> v(with_traj ? (size_t)entries : 0);
-    if (with_traj) HIP_TRY(c, hipMemcpyAsync(v.data(), d_traj, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
-    if (h_marginals) HIP_TRY(c, hipMemcpyAsync(h_marginals, d_marg, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < v.size(); ++i) h_traj[i] = v[i];
-    return 0;
+    return batch_pass_rows_host(c, BatchPass::forecast(horizon, n_traj, draw_index, nullptr, nullptr), h_marginals, h_marginals ? (size_t)doubles : 0, h_traj,
+                                with_traj ? (size_t)entries : 0);
 }
 
 // cpprob_hip_batch_predictive's arguments against the batch's state (batch_smooth_check first).
@@ -5214,8 +5109,7 @@ int cpprob_hip_batch_predictive_device(cpprob_hip_ctx* c, const uint32_t* h_from
     if (int rc = batch_predictive_check(c, h_from, n_rows, d_rows, n_doubles, doubles)) return rc;
     if (doubles == 0) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    const BatchForecast fc{0, h_from, n_rows};
-    return batch_smooth_enqueue(c, 0, 0, d_rows, nullptr, nullptr, nullptr, &fc);
+    return batch_smooth_enqueue(c, BatchPass::predictive(h_from, n_rows, d_rows));
 }
 
 int cpprob_hip_batch_predictive(cpprob_hip_ctx* c, const uint32_t* h_from, uint64_t n_rows, double* h_rows, size_t n_doubles)
@@ -5226,14 +5120,7 @@ int cpprob_hip_batch_predictive(cpprob_hip_ctx* c, const uint32_t* h_from, uint6
     if (int rc = batch_predictive_check(c, h_from, n_rows, h_rows, n_doubles, doubles)) return rc;
     if (doubles == 0) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    double* d_rows = nullptr;
-    int8_t* d_none = nullptr;
-    if (int rc = batch_forecast_stage(c, (size_t)doubles, 0, d_rows, d_none)) return rc;
-    const BatchForecast fc{0, h_from, n_rows};
-    if (int rc = batch_smooth_enqueue(c, 0, 0, d_rows, nullptr, nullptr, nullptr, &fc)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(h_rows, d_rows, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
+    return batch_pass_rows_host(c, BatchPass::predictive(h_from, n_rows, nullptr), h_rows, (size_t)doubles, nullptr, 0);
 }
 
 // ---- decoding a batch (csrc/batch_decode.hpp) ---------------------------------------------------------------------------------------
@@ -5314,47 +5201,42 @@ static int batch_decode_check(cpprob_hip_ctx* c, bool full, uint64_t lag, const 
 }
 
 // Both calls' device forms (dc.d_score, dc.d_path: device buffers or nullptr).
-static int batch_decode_device(cpprob_hip_ctx* c, BatchDecode dc, size_t n_entries, size_t n_doubles)
+static int batch_decode_device(cpprob_hip_ctx* c, BatchPass dc, size_t n_entries, size_t n_doubles)
 {
     uint64_t entries = 0;
-    if (int rc = batch_decode_check(c, dc.full, dc.lag, dc.from, dc.n_rows, dc.d_path != nullptr, n_entries, dc.d_score != nullptr, n_doubles, entries)) return rc;
+    if (int rc = batch_decode_check(c, dc.kind == BatchPass::Decode, dc.lag, dc.from, dc.n_rows, dc.d_path != nullptr, n_entries, dc.d_score != nullptr, n_doubles, entries)) return rc;
     if (entries == 0) dc.d_path = nullptr;
     if (!dc.d_path && !dc.d_score) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    return batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dc);
+    return batch_smooth_enqueue(c, dc);
 }
 
-// Both calls' host forms: staged on the device, the int8 entries widened.
-static int batch_decode_host(cpprob_hip_ctx* c, BatchDecode dc, int32_t* h_path, size_t n_entries, double* h_score, size_t n_doubles)
+// Both calls' host forms: staged on the device (the scores in front of the int8 entries), the entries widened.
+static int batch_decode_host(cpprob_hip_ctx* c, BatchPass dc, int32_t* h_path, size_t n_entries, double* h_score, size_t n_doubles)
 {
     uint64_t entries = 0;
-    if (int rc = batch_decode_check(c, dc.full, dc.lag, dc.from, dc.n_rows, h_path != nullptr, n_entries, h_score != nullptr, n_doubles, entries)) return rc;
+    if (int rc = batch_decode_check(c, dc.kind == BatchPass::Decode, dc.lag, dc.from, dc.n_rows, h_path != nullptr, n_entries, h_score != nullptr, n_doubles, entries)) return rc;
     const bool with_path = h_path && entries;
     if (!with_path && !h_score) return 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t B = c->batch->cfg.n_problems;
-    if (int rc = batch_forecast_stage(c, h_score ? B : 0, with_path ? (size_t)entries : 0, dc.d_score, dc.d_path)) return rc;
-    if (int rc = batch_smooth_enqueue(c, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &dc)) return rc;
-    std::vector<int8_t> v(with_path ? (size_t)entries : 0);
-    if (with_path) HIP_TRY(c, hipMemcpyAsync(v.data(), dc.d_path, (size_t)entries, hipMemcpyDeviceToHost, c->stream));
-    if (h_score) HIP_TRY(c, hipMemcpyAsync(h_score, dc.d_score, B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t i = 0; i < v.size(); ++i) h_path[i] = v[i];
-    return 0;
+    const size_t n_score = h_score ? (size_t)c->batch->cfg.n_problems : 0, n_path = with_path ? (size_t)entries : 0;
+    if (int rc = batch_stage(c, batch_round(n_score * sizeof(double)), n_path, dc.d_score, dc.d_path)) return rc;
+    if (int rc = batch_smooth_enqueue(c, dc)) return rc;
+    return batch_fetch(c, h_path, dc.d_path, n_path, h_score, dc.d_score, n_score);
 }
 
 int cpprob_hip_batch_decode_device(cpprob_hip_ctx* c, int8_t* d_path, size_t n_entries, double* d_score, size_t n_doubles)
 {
     LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
-    return batch_decode_device(c, BatchDecode{true, 0, nullptr, 0, d_score, d_path}, n_entries, n_doubles);
+    return batch_decode_device(c, BatchPass::decode(d_score, d_path), n_entries, n_doubles);
 }
 
 int cpprob_hip_batch_decode(cpprob_hip_ctx* c, int32_t* h_path, size_t n_entries, double* h_score, size_t n_doubles)
 {
     LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
-    return batch_decode_host(c, BatchDecode{true, 0, nullptr, 0, nullptr, nullptr}, h_path, n_entries, h_score, n_doubles);
+    return batch_decode_host(c, BatchPass::decode(nullptr, nullptr), h_path, n_entries, h_score, n_doubles);
 }
 
 int cpprob_hip_batch_decode_lag_device(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, int8_t* d_states, size_t n_entries,
@@ -5362,7 +5244,7 @@ int cpprob_hip_batch_decode_lag_device(cpprob_hip_ctx* c, uint64_t lag, const ui
 {
     LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
-    return batch_decode_device(c, BatchDecode{false, lag, h_from, n_rows, d_score, d_states}, n_entries, n_doubles);
+    return batch_decode_device(c, BatchPass::decode_lag(lag, h_from, n_rows, d_score, d_states), n_entries, n_doubles);
 }
 
 int cpprob_hip_batch_decode_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t* h_from, uint64_t n_rows, int32_t* h_states, size_t n_entries,
@@ -5370,7 +5252,7 @@ int cpprob_hip_batch_decode_lag(cpprob_hip_ctx* c, uint64_t lag, const uint32_t*
 {
     LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
-    return batch_decode_host(c, BatchDecode{false, lag, h_from, n_rows, nullptr, nullptr}, h_states, n_entries, h_score, n_doubles);
+    return batch_decode_host(c, BatchPass::decode_lag(lag, h_from, n_rows, nullptr, nullptr), h_states, n_entries, h_score, n_doubles);
 }
 
 int cpprob_hip_batch_decode_logp(cpprob_hip_ctx* c, uint64_t problem, double* h_lp, double* h_lp0)

@@ -78,7 +78,11 @@ def test_records_keep_their_names():
 def test_kernel_is_built_into_the_library():
     hip = open(os.path.join(ROOT, "cpprob_amd", "csrc", "cpprob_hip.hip")).read()
     assert "batch_traj_stats_kernel<3>" in hip and "batch_traj_stats_kernel<8>" in hip
-    assert re.search(r"const BatchDecode\* dc = nullptr,\s*const BatchTrajStats\* ts = nullptr\)", hip)      # (taken as st, fc and dc are)
+    # both calls reach them through the one batch_smooth_enqueue (as every other pass does)
+    assert len(re.findall(r"^static int batch_smooth_enqueue\(", hip, re.M)) == 1 and hip.count("static int batch_smooth_enqueue(") == 1
+    for name in ("cpprob_hip_batch_traj_stats", "cpprob_hip_batch_traj_stats_device"):
+        body = re.search(r"^int %s\(.*?^\}" % name, hip, re.M | re.S)
+        assert body and "batch_smooth_enqueue(" in body.group(0), name
 
 
 _OPTIONS_TU = r"""
