@@ -50,6 +50,8 @@ SYMBOLS = [
     "cpprob_hip_batch_decode", "cpprob_hip_batch_decode_device", "cpprob_hip_batch_decode_lag", "cpprob_hip_batch_decode_lag_device",
     "cpprob_hip_batch_decode_logp", "cpprob_hip_batch_pass_grid",
     "cpprob_hip_batch_run_conditional", "cpprob_hip_batch_run_conditional_device",
+    "cpprob_hip_batch_retable", "cpprob_hip_batch_retable_device", "cpprob_hip_batch_retable_status", "cpprob_hip_batch_retable_grid",
+    "cpprob_hip_batch_mstep_device", "cpprob_hip_batch_copy_step_tables", "cpprob_hip_batch_summaries_device",
 ]
 
 
@@ -377,6 +379,13 @@ def load_library(path=None):
         "cpprob_hip_batch_pass_grid": (C.c_int, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "cpprob_hip_batch_run_conditional": (C.c_int, [vp, C.POINTER(u64), vp, sz]),
         "cpprob_hip_batch_run_conditional_device": (C.c_int, [vp, C.POINTER(u64), vp, sz]),
+        "cpprob_hip_batch_retable": (C.c_int, [vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_device": (C.c_int, [vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_status": (C.c_int, [vp, C.POINTER(i32)]),
+        "cpprob_hip_batch_retable_grid": (C.c_int, [vp, C.POINTER(C.c_uint32)]),
+        "cpprob_hip_batch_mstep_device": (C.c_int, [vp, vp, sz, vp, vp]),
+        "cpprob_hip_batch_copy_step_tables": (C.c_int, [vp, u64, vp, sz, vp]),
+        "cpprob_hip_batch_summaries_device": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -684,6 +693,61 @@ class Engine:
         if ref_i8 is None or ref_i8.numel() != int(np.sum(h_T, dtype=np.int64)):
             raise ValueError("the reference paths hold one state per problem and step: %d entries" % int(np.sum(h_T, dtype=np.int64)))
         self._chk(self.L.cpprob_hip_batch_run_conditional_device(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), _dptr(ref_i8), ref_i8.numel()))
+
+    # ---- re-tabling a begun batch (include/cpprob_hip.h: cpprob_hip_batch_retable*) ----------------------------------
+    def batch_retable(self, tables, observes=None):
+        """New tables for the begun MODEL_HMM_TABLE batch of problems where it stands (cpprob_hip_batch_retable): tables = (means
+        [B, k], transition [B, k, k]) on the host, validated as batch_begin_problems validates them.  observes: the problems'
+        sequences as batch_begin_problems took them, or None once a previous batch_retable of this begun batch has staged them.
+        Everything the batch returns afterwards is what a fresh batch_begin_problems with these tables returns, bit for bit; like a
+        begin, the read-outs wait for the next batch_run / batch_run_conditional."""
+        means = np.ascontiguousarray(tables[0], np.float64)
+        trans = np.ascontiguousarray(tables[1], np.float64)
+        if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != self.batch_B:
+            raise ValueError("tables = (means [B, k], transition [B, k, k])")
+        h_T, _ = self._batch_problem_shapes()
+        flat = None if observes is None else self._batch_packed_observes(observes)
+        self._chk(self.L.cpprob_hip_batch_retable(self.h, means.ctypes.data, trans.ctypes.data, None if flat is None or flat.size == 0 else flat.ctypes.data,
+                                                  int(np.sum(h_T, dtype=np.int64)) if flat is None else flat.size))
+
+    def batch_retable_device(self, means, trans, observes):
+        """The same between torch float64 device tensors (means [B, k], trans [B, k, k], observes packed problem after problem),
+        enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status)."""
+        self._chk(self.L.cpprob_hip_batch_retable_device(self.h, _dptr(means), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+
+    def batch_retable_status(self):
+        """int32 [B] of the last re-table: 0, or bits 1 (a weight not finite or < 0), 2 (a transition row without mass), 4 (a mean
+        not finite) -- such a problem kept its previous table.  Synchronises."""
+        out = np.zeros(self.batch_B, np.int32)
+        self._chk(self.L.cpprob_hip_batch_retable_status(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def batch_retable_grid(self):
+        """gridDim.y of the last re-table launch (0: none)."""
+        g = C.c_uint32()
+        self._chk(self.L.cpprob_hip_batch_retable_grid(self.h, C.byref(g)))
+        return int(g.value)
+
+    def batch_mstep_device(self, stats, means, trans):
+        """em.m_step on the device (cpprob_hip_batch_mstep_device): stats torch float64 [B, 88] as batch_smooth_stats_device leaves
+        them; means [B, k] and trans [B, k, k] torch float64, updated in place.  Enqueued without a host synchronisation."""
+        self._chk(self.L.cpprob_hip_batch_mstep_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans)))
+
+    def batch_step_tables(self, b):
+        """Problem b's per-step table as the device holds it: (rows float64 [T_b, 8], threshold words uint64 [64] -- None for
+        MODEL_HMM3).  Synchronises."""
+        inside = 0 <= int(b) < self.batch_B                  # (an index out of range: the library's own refusal)
+        T = self.batch_T if self.batch_shapes is None or not inside else int(self.batch_shapes[0][int(b)])
+        rows = np.zeros((T, 8))
+        thr = np.zeros(64, np.uint64) if self.batch_K == 8 else None
+        self._chk(self.L.cpprob_hip_batch_copy_step_tables(self.h, int(b), rows.ctypes.data, rows.size, None if thr is None else thr.ctypes.data))
+        return rows, thr
+
+    def batch_summaries_device(self, out):
+        """[B, 4] = {log_evidence, ess_final, log_norm, max_logw} per problem into a torch float64 device tensor; no host sync."""
+        if out is None or out.numel() < 4 * self.batch_B:
+            raise ValueError("out holds 4 doubles a problem")
+        self._chk(self.L.cpprob_hip_batch_summaries_device(self.h, _dptr(out)))
 
     def batch_results(self, with_stats=True):
         """[summary dict] * B, stats [B, T, spp], ess [B, T], resampled [B, T] in one call and one synchronisation.  with_stats=False:

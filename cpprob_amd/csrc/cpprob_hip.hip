@@ -28,6 +28,7 @@
 #include "batch_forecast.hpp"
 #include "batch_decode.hpp"
 #include "batch_csmc.hpp"
+#include "batch_retable.hpp"
 #include "batch_pass_plan.hpp"
 
 using namespace cph;
@@ -1112,6 +1113,13 @@ struct BatchState {
     // their pinned source, allocations of the context's own
     bool conditional = false, cfirst_ready = false;
     int64_t* d_cfirst = nullptr; int64_t* pin_cfirst = nullptr; size_t cfirst_cap = 0;
+    // re-tabling (cpprob_hip_batch_retable*; csrc/batch_retable.hpp): the status words [B] and the observes the host form staged, allocations
+    // of the context's own; retabled: the begun batch has been re-tabled (its status words are those of the last one); robs_ready: d_robs
+    // holds this begun batch's observes; tab_stale / thr_stale: the device holds rows / thresholds the host mirrors (h_tab, h_thr) do not
+    int32_t* d_rstatus = nullptr; size_t rstatus_cap = 0;
+    double* d_robs = nullptr; size_t robs_cap = 0;
+    bool retabled = false, robs_ready = false, tab_stale = false, thr_stale = false;
+    unsigned retable_gy = 0;                                // gridDim.y of the last re-table launch (0: none)
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -1129,6 +1137,7 @@ void batch_free(cpprob_hip_ctx* c)
     dfree(c->batch->d_words); dfree(c->batch->d_v); dfree(c->batch->d_lp); dfree(c->batch->d_tau);
     if (c->batch->pin_sdesc) (void)hipHostFree(c->batch->pin_sdesc);
     dfree(c->batch->d_cfirst);
+    dfree(c->batch->d_rstatus); dfree(c->batch->d_robs);
     if (c->batch->pin_cfirst) (void)hipHostFree(c->batch->pin_cfirst);
     for (hipEvent_t e : c->batch->sdesc_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
@@ -1199,6 +1208,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->counted.assign(B, 0);
     bs->decoded.assign(B, 0); bs->lp_ready = false; bs->lp_sent = false;
     bs->ostats_done.assign(B, 0);
+    bs->retabled = false; bs->robs_ready = false; bs->tab_stale = false; bs->thr_stale = false; bs->retable_gy = 0;
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3, described = h_T != nullptr, own = h_means != nullptr;
     const int spp = hmm3 ? 3 : 8;
     const uint64_t tables = described ? B : 1;
@@ -4171,27 +4181,37 @@ static int batch_conditional_check(cpprob_hip_ctx* c, const void* seeds, const v
     return 0;
 }
 
+// A described batch's first entries ([B] int64: the sums of the lengths before each problem -- where its reference path and its observes
+// begin in a packed array) on the device, written and uploaded once a begin; waits for nothing, but where the buffer has to grow, for
+// the calls before it.
+static int batch_first_entries(cpprob_hip_ctx* c)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    if (!bs->described || bs->cfirst_ready) return 0;
+    if (B > bs->cfirst_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));       // (earlier runs may still read the buffer this replaces)
+        dfree(bs->d_cfirst); bs->cfirst_cap = 0;
+        if (bs->pin_cfirst) { (void)hipHostFree(bs->pin_cfirst); bs->pin_cfirst = nullptr; }
+        HIP_TRY(c, hipMalloc(&bs->d_cfirst, B * sizeof(int64_t)));
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_cfirst), B * sizeof(int64_t), hipHostMallocDefault));
+        bs->cfirst_cap = B;
+    }
+    // (the pinned source is written once a begin, and a begin ends with the stream drained: no copy still reads it)
+    int64_t at = 0;
+    for (size_t b = 0; b < B; ++b) { bs->pin_cfirst[b] = at; at += (int64_t)bs->prob[b].T; }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_cfirst, bs->pin_cfirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    bs->cfirst_ready = true;
+    return 0;
+}
+
 // Enqueues the seeds' copy, a described batch's first entries (once a begin) and the launch; waits for nothing, but where the buffer
 // of first entries has to grow, for the calls before it.
 static int batch_conditional_enqueue(cpprob_hip_ctx* c, const uint64_t* h_seeds, const int8_t* d_ref)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
-    if (bs->described && !bs->cfirst_ready) {
-        if (B > bs->cfirst_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (earlier runs may still read the buffer this replaces)
-            dfree(bs->d_cfirst); bs->cfirst_cap = 0;
-            if (bs->pin_cfirst) { (void)hipHostFree(bs->pin_cfirst); bs->pin_cfirst = nullptr; }
-            HIP_TRY(c, hipMalloc(&bs->d_cfirst, B * sizeof(int64_t)));
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_cfirst), B * sizeof(int64_t), hipHostMallocDefault));
-            bs->cfirst_cap = B;
-        }
-        // (the pinned source is written once a begin, and a begin ends with the stream drained: no copy still reads it)
-        int64_t at = 0;
-        for (size_t b = 0; b < B; ++b) { bs->pin_cfirst[b] = at; at += (int64_t)bs->prob[b].T; }
-        HIP_TRY(c, hipMemcpyAsync(bs->d_cfirst, bs->pin_cfirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        bs->cfirst_ready = true;
-    }
+    if (int rc = batch_first_entries(c)) return rc;
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     BatchCsmcArgs a{};
     a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
@@ -4419,13 +4439,17 @@ int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_
     // the problem's own [T_b][n_b] from its first entry in the store on; its table rows are bs->T apart
     const size_t T = (size_t)bs->prob[problem].T, n = (size_t)bs->prob[problem].n, first = (size_t)bs->prob[problem].store;
     std::vector<int8_t> v(T * n);
+    double fetched[kBatchTab];                                 // a re-tabled batch's rows are on the device only: the last step's, 64 bytes
+    const size_t last = ((size_t)problem * (size_t)bs->T + (T ? T - 1 : 0)) * kBatchTab;
+    if (h_logw && T > 0 && bs->tab_stale)
+        HIP_TRY(c, hipMemcpyAsync(fetched, bs->d_ws + bs->lay.tab + last * sizeof(double), sizeof fetched, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(v.data(), bs->d_ws + bs->lay.values + first, T * n, hipMemcpyDeviceToHost, c->stream));
     if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->d_ws + bs->lay.anc + first * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (h_values) for (size_t i = 0; i < T * n; ++i) h_values[i] = v[i];
     if (h_logw && T > 0) {
         // the final weights are table values: ll of the last step at the particle's state (what cpprob_hip_copy_logw returns)
-        const double* row = bs->tab_host() + ((size_t)problem * (size_t)bs->T + (T - 1)) * kBatchTab;
+        const double* row = bs->tab_stale ? fetched : bs->tab_host() + last;
         for (size_t i = 0; i < n; ++i) h_logw[i] = row[(int)v[(T - 1) * n + i]];
     }
     return 0;
@@ -5125,9 +5149,17 @@ int cpprob_hip_batch_predictive(cpprob_hip_ctx* c, const uint32_t* h_from, uint6
 
 // ---- decoding a batch (csrc/batch_decode.hpp) ---------------------------------------------------------------------------------------
 // The log tables of the batch last begun, on the host: one a problem (a described CPPROB_HIP_MODEL_HMM_TABLE batch) or one for all.
-static void batch_decode_table(BatchState* bs)
+// (After a device-form re-table the thresholds are the device's: fetched once, which waits for the stream.)
+static int batch_decode_table(cpprob_hip_ctx* c)
 {
-    if (bs->lp_ready) return;
+    BatchState* bs = c->batch;
+    if (bs->lp_ready) return 0;
+    if (bs->thr_stale) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipMemcpyAsync(bs->h_thr.data(), bs->d_ws + bs->lay.thr, bs->h_thr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        bs->thr_stale = false;
+    }
     const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
     const size_t tables = hmm3 ? 1 : bs->h_thr.size() / 64;
     bs->h_lp.assign(tables * 64, 0.0);
@@ -5136,6 +5168,7 @@ static void batch_decode_table(BatchState* bs)
     for (int s2 = 0; s2 < 3; ++s2) for (int j = 0; j < 2; ++j) h3[s2 * 8 + j] = bs->mp.hmm_thr[s2][j];
     for (size_t i = 0; i < tables; ++i) decode_log_table(hmm3 ? h3 : bs->h_thr.data() + i * 64, hmm3 ? 3 : bs->hk, bs->h_lp.data() + i * 64, &bs->lp0);
     bs->lp_ready = true;
+    return 0;
 }
 
 // The decode's own allocations for word_rows step words, and the log tables' upload (once a begin).  Where a buffer has to grow it
@@ -5144,7 +5177,7 @@ static int batch_decode_prepare(cpprob_hip_ctx* c, size_t word_rows)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
-    batch_decode_table(bs);
+    if (int rc = batch_decode_table(c)) return rc;
     const size_t tables = bs->h_lp.size() / 64;
     if (word_rows > bs->words_cap || B > bs->v_cap || tables > bs->lp_cap) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (earlier calls' kernels may still read the buffers this replaces)
@@ -5262,7 +5295,7 @@ int cpprob_hip_batch_decode_logp(cpprob_hip_ctx* c, uint64_t problem, double* h_
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch begun");
     if (!h_lp || !h_lp0) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
-    batch_decode_table(bs);
+    if (int rc = batch_decode_table(c)) return rc;
     const size_t tables = bs->h_lp.size() / 64;
     std::memcpy(h_lp, bs->h_lp.data() + (tables > 1 ? (size_t)problem * 64 : 0), 64 * sizeof(double));
     *h_lp0 = bs->lp0;
@@ -5295,6 +5328,168 @@ int cpprob_hip_batch_pass_grid(cpprob_hip_ctx* c, uint32_t* decode_forward_grid_
     *decode_trace_grid_y = bs ? bs->decode_gy_trace : 0u;
     *forecast_grid_y = bs ? bs->forecast_gy : 0u;
     *predictive_grid_y = bs ? bs->predictive_gy : 0u;
+    return 0;
+}
+// ---- re-tabling a begun batch (csrc/batch_retable.hpp) -----------------------------------------------------------------------------
+static_assert(kRetableStats == kSuffStats, "the M-step reads the record of cpprob_hip_batch_smooth_stats");
+// What a re-table needs of the batch's state, then n_observes against the lengths; nothing is enqueued before it has passed.
+static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "an online batch is not re-tabled: its advances evaluate their rows from the host's means");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "re-tabling serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
+    if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
+    uint64_t rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    if ((uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    return 0;
+}
+
+// Enqueues the first entries (once a begin) and the launch; the batch then stands as after a begin.  Waits for nothing but, where the
+// status words have to grow, for the calls before it.
+static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    if (B > bs->rstatus_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        dfree(bs->d_rstatus); bs->rstatus_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_rstatus, B * sizeof(int32_t)));
+        bs->rstatus_cap = B;
+    }
+    if (int rc = batch_first_entries(c)) return rc;
+    BatchRetableArgs a{};
+    a.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+    a.first = bs->d_cfirst;
+    a.means = d_means; a.trans = d_trans; a.obs = d_obs;
+    a.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+    a.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
+    a.status = bs->d_rstatus;
+    a.log_norm = std::log(2 * kPi * 1.0 * 1.0);               // (normal_logpdf's own expression at sigma = 1.0)
+    a.T_max = bs->T; a.k = bs->hk;
+    const unsigned gy = retable_grid_y(bs->T, (int64_t)B);
+    hipLaunchKernelGGL(batch_retable_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    bs->retable_gy = gy; bs->retabled = true;
+    // a begin as far as results go: the read-outs wait for the next run; the decode's log tables come from the thresholds
+    bs->ran = false; bs->conditional = false;
+    bs->lp_ready = false; bs->lp_sent = false;
+    bs->tab_stale = true; bs->thr_stale = true;
+    return 0;
+}
+
+int cpprob_hip_batch_retable_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes)) return rc;
+    if (!d_means || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_means, d_transition, d_observes);
+}
+
+int cpprob_hip_batch_retable(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_means || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    int k = 0;
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
+    if (h_observes) {
+        if (n_observes > bs->robs_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (an earlier re-table may still read the buffer this replaces)
+            dfree(bs->d_robs); bs->robs_cap = 0; bs->robs_ready = false;
+            HIP_TRY(c, hipMalloc(&bs->d_robs, n_observes * sizeof(double)));
+            bs->robs_cap = n_observes;
+        }
+        HIP_TRY(c, hipMemcpyAsync(bs->d_robs, h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        bs->robs_ready = true;
+    }
+    double *d_means = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(B * (size_t)k * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs)) return rc;
+    // the host knows the tables: the thresholds' mirror is current again (the rows' is not: cpprob_hip_batch_copy_store fetches its row)
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    bs->thr_stale = false;
+    return 0;
+}
+
+int cpprob_hip_batch_retable_status(cpprob_hip_ctx* c, int32_t* h_status)
+{
+    LANES_OWN(c);
+    if (!c || !h_status) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->retabled) return fail(c, CPPROB_HIP_ESTATE, "the begun batch has not been re-tabled");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(h_status, bs->d_rstatus, bs->cfg.n_problems * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int cpprob_hip_batch_retable_grid(cpprob_hip_ctx* c, uint32_t* grid_y)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    if (!grid_y) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    *grid_y = c->batch ? c->batch->retable_gy : 0u;
+    return 0;
+}
+
+int cpprob_hip_batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!d_stats || !d_means || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kRetableStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepArgs a{};
+    a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.B = (int64_t)B; a.k = bs->hk;
+    hipLaunchKernelGGL(batch_mstep_kernel, dim3((unsigned)((B * (uint64_t)bs->hk + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_step_tables(cpprob_hip_ctx* c, uint64_t problem, double* h_rows, size_t n_doubles, uint64_t* h_thr)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
+    if (hmm3 && h_thr) return fail(c, CPPROB_HIP_EINVAL, "CPPROB_HIP_MODEL_HMM3 keeps no threshold words on the device: h_thr must be NULL");
+    const size_t T = (size_t)bs->prob[problem].T;
+    if (n_doubles < T * kBatchTab) return fail(c, CPPROB_HIP_EINVAL, "h_rows too small: " + std::to_string(T * kBatchTab) + " doubles (8 a step of the problem)");
+    if (T && !h_rows) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (T) HIP_TRY(c, hipMemcpyAsync(h_rows, bs->d_ws + bs->lay.tab + (size_t)problem * (size_t)bs->T * kBatchTab * sizeof(double), T * kBatchTab * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_thr) HIP_TRY(c, hipMemcpyAsync(h_thr, bs->d_ws + bs->lay.thr + (bs->described ? (size_t)problem : 0) * 64 * sizeof(uint64_t), 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int cpprob_hip_batch_summaries_device(cpprob_hip_ctx* c, double* d_out)
+{
+    LANES_OWN(c);
+    if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->conditional) return fail(c, CPPROB_HIP_ESTATE, "a conditional run keeps masses and no books: the summaries wait for the next cpprob_hip_batch_run");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t B = (int64_t)bs->cfg.n_problems, total = B * 4;
+    hipLaunchKernelGGL(batch_pack_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
+                       (const char*)(bs->d_ws + bs->lay.ctrl), (const double*)(bs->d_ws + bs->lay.stats), 0, B, d_out);
+    HIP_TRY(c, hipGetLastError());
     return 0;
 }
 }  // extern "C"

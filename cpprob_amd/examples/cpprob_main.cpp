@@ -28,6 +28,8 @@
 //                   --em_iterations N (with --batch_tables_file, not with --stream_chunk: particle EM -- N runs, each followed by the
 //                   backward smoother's expected sufficient statistics and an M-step on every problem's table; the usual output is the
 //                   last run's, then the fitted tables follow, one "[means] [transition]" line a problem in the input's grammar)
+//                   --em_on_device (with --em_iterations: the batch is begun once and re-tabled on the device between the iterations,
+//                   cpprob::gpu::Options::fit_on_device; the same output)
 //                   --decode (the batch modes and --stream_chunk, not with --filtering_only unless --keep_masses: after the statistics, a
 //                   line "decode b score x_0 .. x_{T-1}" a problem -- the single most probable state path given the observes, over the
 //                   states the particles occupy, and its log joint density; --json carries "map_path" and "map_score" instead; with
@@ -370,6 +372,7 @@ int main(int argc, char** argv)
         else if (f == "--batch_observes_file") a.batch_observes_file = next();   // one problem a line, one batched launch (built-in HMMs, smc)
         else if (f == "--batch_tables_file") a.batch_tables_file = next();       // one table-HMM problem a line: [means] [transition] [observes]
         else if (f == "--stream_chunk") a.stream_chunk = std::stoull(next());    // --batch_tables_file: the observes arrive this many at a time
+        else if (f == "--em_on_device") opt.fit_on_device = true;                  // --em_iterations: one begin, then cpprob_hip_batch_retable an iteration
         else if (f == "--em_iterations") a.em_iterations = std::stoull(next());  // --batch_tables_file: particle EM on the tables (cpprob::gpu::hmm_table_fit)
         else if (f == "--batch_dump") a.batch_dump = true;                         // the batch modes: problem b's traces as <generated_file>_smc_<b>.int / .ids
         else if (f == "--backward_smoothing") opt.backward_smoothing = true;      // the batch modes: statistics from the backward smoother (cpprob_hip_batch_smooth)
@@ -410,6 +413,7 @@ int main(int argc, char** argv)
         else { std::cerr << "unknown option " << f << std::endl; return EXIT_FAILURE; }
     }
     if (a.sis == a.smc) { std::cerr << "exactly one of --sis / --smc has to be set" << std::endl; return EXIT_FAILURE; }
+    if (opt.fit_on_device && a.em_iterations == 0) { std::cerr << "--em_on_device re-tables the batch of a fit: set --em_iterations" << std::endl; return EXIT_FAILURE; }
     if ((opt.forecast_horizon || opt.forecast_trajectories) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
         std::cerr << "--forecast serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;
         return EXIT_FAILURE;

@@ -28,7 +28,7 @@ def sample_tables(stats, k, rng, alpha=1.0, mu0=0.0, tau0=10.0):
     return means, trans
 
 
-def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps, rng, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, **prior):
+def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps, rng, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, retable=False, **prior):
     """Batched Gibbs sampling of the tables, one chain a problem.  observes: a list of B 1-D sequences, or one sequence every chain
     shares; means0 [B, k], trans0 [B, k, k] the chains' initial tables; seeds [B]; rng a numpy Generator; prior: sample_tables' alpha,
     mu0, tau0.  Sweep i begins a batch with the current tables (batch_begin_problems), runs it with seeds + i, takes the statistics of
@@ -36,6 +36,8 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
     sample_tables.  Returns (means [sweeps + 1, B, k], trans [sweeps + 1, B, k, k], log_evidence [sweeps, B]): the tables before every
     sweep and after the last, and the log-evidence estimate of every sweep's run (of the tables it began with).  keep_history=False:
     the batches are filtering-only and keep the smoother's masses (keep_masses) -- the same chain bit for bit, without a particle store.
+    retable=True: sweep 0 begins the batch; every later sweep gives it its new tables where it stands (batch_retable: the tables drawn
+    on the host, the observes uploaded once) in place of a fresh begin -- the same chain bit for bit.
 
     The trajectory comes from the particle approximation of forward filtering / backward sampling: it is drawn from the n_particles
     filtering approximations of the run, not from the exact smoothing law.  The chain's invariant law is therefore the posterior only
@@ -52,8 +54,11 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
     sd = np.ascontiguousarray(seeds, np.uint64)
     m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(sweeps), B))
     for i in range(int(sweeps)):
-        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), resampler=resampler, keep_history=bool(keep_history),
-                                    keep_masses=not keep_history)
+        if retable and i > 0:
+            engine.batch_retable((means, trans), seqs if i == 1 else None)
+        else:
+            engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), resampler=resampler, keep_history=bool(keep_history),
+                                        keep_masses=not keep_history)
         engine.batch_run(sd + np.uint64(i))
         stats = engine.batch_traj_stats(1, draw_index=i % (1 << 16), observes=seqs)
         ev[i] = [s["log_evidence"] for s in engine.batch_results()[0]]

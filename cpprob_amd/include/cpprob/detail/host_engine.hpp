@@ -865,8 +865,10 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
 // states them) and, where dump is set, options().batch_dump_file; decode: options().map_decode is served.  The batch stays on ctx for
 // the calls that read it.
 // conditional: the run is cpprob_hip_batch_run_conditional on these paths (one a problem); what cpprob_hip_batch_results returns stays default.
+// retable: ctx holds this batch begun with other tables -- it is given pk's tables where it stands (cpprob_hip_batch_retable; with_observes:
+// the first such call of the batch, which uploads them) in place of a begin.
 inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTableProblems& pk, const std::vector<std::uint64_t>& seeds, bool dump, bool decode = true,
-                                                  const std::vector<std::vector<int>>* conditional = nullptr)
+                                                  const std::vector<std::vector<int>>* conditional = nullptr, bool retable = false, bool with_observes = true)
 {
     const Options& opt = options();
     const std::size_t B = seeds.size(), k = pk.k, T_max = pk.T_max;
@@ -881,8 +883,11 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
     bc.n_particles = pk.n_max;
     bc.n_problems = B;
     const auto t0 = std::chrono::steady_clock::now();
-    ctx.check(cpprob_hip_batch_begin_problems(ctx.get(), &bc, T.data(), pk.np.data(), pk.flat.data(), static_cast<std::int32_t>(k), pk.means.data(), pk.trans.data()),
-              "cpprob_hip_batch_begin_problems");
+    if (retable)
+        ctx.check(cpprob_hip_batch_retable(ctx.get(), pk.means.data(), pk.trans.data(), with_observes ? pk.flat.data() : nullptr, pk.flat.size()), "cpprob_hip_batch_retable");
+    else
+        ctx.check(cpprob_hip_batch_begin_problems(ctx.get(), &bc, T.data(), pk.np.data(), pk.flat.data(), static_cast<std::int32_t>(k), pk.means.data(), pk.trans.data()),
+                  "cpprob_hip_batch_begin_problems");
     std::vector<cpprob_hip_summary> sums(B);
     const std::size_t K = 8;
     std::vector<double> stats(B * T_max * K), ess(B * T_max);
@@ -959,6 +964,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // with it (the statistics then come from the masses the filtering-only runs keep);
 // options().batch_dump_file is written by the last run.  options().map_decode: one more run, with the keys seeds[b] + iterations,
 // under the FITTED tables, and its decode (Result::map_path, ::map_score) in the results -- the labels a fit is made for.
+// options().fit_on_device: the first run begins the batch, every later one re-tables it on the device (cpprob_hip_batch_retable) -- the
+// same HmmTableFit bit for bit without a begin's host work an iteration.
 struct HmmTableFit { std::vector<HmmTable> tables; std::vector<Result> results; };
 
 inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes, const std::vector<std::size_t>& n,
@@ -974,9 +981,12 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
     Context& ctx = *lease;
     std::vector<double> rec(B * R);
     std::vector<std::uint64_t> keys(B);
+    const bool kept = options().fit_on_device;                 // the batch of iteration 0 is re-tabled from then on
+    std::size_t runs = 0;
     for (std::size_t it = 0; it < iterations; ++it) {
         for (std::size_t b = 0; b < B; ++b) keys[b] = seeds[b] + it;
-        fit.results = run_hmm_table_problems(ctx, pk, keys, it + 1 == iterations, false);
+        fit.results = run_hmm_table_problems(ctx, pk, keys, it + 1 == iterations, false, nullptr, kept && runs > 0, runs == 1);
+        ++runs;
         ctx.check(cpprob_hip_batch_smooth_stats(ctx.get(), pk.flat.empty() ? nullptr : pk.flat.data(), pk.flat.size(), rec.data(), rec.size()),
                   "cpprob_hip_batch_smooth_stats");
         for (std::size_t b = 0; b < B; ++b) {
@@ -992,7 +1002,7 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
     }
     if (options().map_decode) {
         for (std::size_t b = 0; b < B; ++b) keys[b] = seeds[b] + iterations;
-        std::vector<Result> fin = run_hmm_table_problems(ctx, pk, keys, false, true);
+        std::vector<Result> fin = run_hmm_table_problems(ctx, pk, keys, false, true, nullptr, kept && runs > 0, runs == 1);
         if (fit.results.empty()) fit.results = fin;
         for (std::size_t b = 0; b < B; ++b) { fit.results[b].map_decoded = true; fit.results[b].map_path = fin[b].map_path; fit.results[b].map_score = fin[b].map_score; }
     }

@@ -67,6 +67,12 @@ struct Options {
     bool keep_masses = false;                         // batched runs with keep_history = false: the run keeps the backward smoother's masses (64 bytes a
                                                       // problem and step, CPPROB_HIP_BATCH_KEEP_MASSES), so backward_smoothing, backward_trajectories,
                                                       // smoothing_lag and hmm_table_fit serve the filtering-only batch; lineage dumps stay refused
+    bool fit_on_device = false;                       // hmm_table_fit: the batch is begun once and every later iteration gives it its new tables
+                                                      // where it stands on the device (cpprob_hip_batch_retable: rows and thresholds rewritten by a
+                                                      // kernel, the observes uploaded once) in place of a fresh begin; the same HmmTableFit bit for
+                                                      // bit.  This host layer owns no device memory, so an iteration's record (88 doubles a problem)
+                                                      // and its M-step still cross the host; cpprob_amd.hmm_table_em(resident=True) keeps both on the
+                                                      // device (cpprob_hip_batch_mstep_device, _retable_device)
     std::vector<std::vector<int>> conditional_paths;  // hmm_table_batch with keep_history = false and keep_masses: not empty = the run is the conditional
                                                       // SMC run (cpprob_hip_batch_run_conditional), problem b's retained particle following
                                                       // conditional_paths[b] (one state a step).  It keeps masses, not books: what comes from

@@ -17,7 +17,8 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     other of two device buffers (batch_smooth_device(traj_i8=..., n_traj=1, draw_index=i % 2^16)), takes that trajectory's statistics
     (batch_traj_stats(1, draw_index=i % 2^16, observes): the same trajectory) and draws the next tables with sample_tables.  No
     trajectory crosses to the host.  Returns (means [sweeps + 1, B, k], trans [sweeps + 1, B, k, k]): the tables before every sweep
-    and after the last.
+    and after the last.  retable=True (a keyword beside the prior's, default False): sweep 0 begins the batch; every later sweep gives it its new tables where it stands
+    (batch_retable: the tables drawn on the host, the observes uploaded once) in place of a fresh begin -- the same chain bit for bit.
 
     This is particle Gibbs with backward sampling: a conditional SMC run with multinomial resampling, its retained particle the
     previous trajectory, followed by backward simulation.  That kernel leaves the smoothing law of the states given the tables
@@ -25,6 +26,7 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     n_particles >= 1, up to the 32-bit quantisation of weights and thresholds; n_particles moves how fast the chain mixes, not where
     it settles.  (hmm_table_gibbs draws its trajectory from an unconditional filter and is exact only as n_particles grows.)"""
     import torch
+    retable = bool(prior.pop("retable", False))
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
     B, k = means.shape
@@ -38,7 +40,10 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     traj = [torch.empty(total, dtype=torch.int8, device="cuda:%d" % engine.device) for _ in range(2)]
     m_hist, t_hist = [means.copy()], [trans.copy()]
     for i in range(int(sweeps)):
-        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), keep_history=False, keep_masses=True)
+        if retable and i > 0:
+            engine.batch_retable((means, trans), seqs if i == 1 else None)
+        else:
+            engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), keep_history=False, keep_masses=True)
         if i == 0:
             engine.batch_run(sd)
         else:

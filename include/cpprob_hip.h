@@ -668,7 +668,8 @@ int cpprob_hip_batch_decode_lag_device(cpprob_hip_ctx* ctx, uint64_t lag, const 
                                        double* d_score, size_t n_doubles);
 /* The log table of `problem` in the batch last begun: h_lp[8 s + s'] = lp[s][s'] (-inf outside the k x k table), *h_lp0 = lp0 -- the
  * doubles the decode kernels were or will be given, so that a restatement of a run depends on no second logarithm.  Host state only:
- * no device work, no synchronisation.  CPPROB_HIP_ESTATE: no batch begun. */
+ * no device work, no synchronisation -- but after cpprob_hip_batch_retable_device, whose thresholds the first call fetches (it waits
+ * for the stream once).  CPPROB_HIP_ESTATE: no batch begun. */
 int cpprob_hip_batch_decode_logp(cpprob_hip_ctx* ctx, uint64_t problem, double h_lp[64], double* h_lp0);
 /* The grids of the context's last decode, forecast or predictive call (any form of them), host only, as cpprob_hip_batch_smooth_grid
  * reports the smoother's: gridDim.x of the decode's forward launch -- a workgroup takes 4 problems, the problems 4 times that far
@@ -679,6 +680,58 @@ int cpprob_hip_batch_decode_logp(cpprob_hip_ctx* ctx, uint64_t problem, double h
  * how many trips a shape produced. */
 int cpprob_hip_batch_pass_grid(cpprob_hip_ctx* ctx, uint32_t* decode_forward_grid_x, uint32_t* decode_trace_grid_y, uint32_t* forecast_grid_y,
                                uint32_t* predictive_grid_y);
+
+/* Re-tabling a begun batch (csrc/batch_retable.hpp): new tables for a batch of CPPROB_HIP_MODEL_HMM_TABLE problems where it stands --
+ * what a fitting loop changes between two sweeps (72 doubles a problem) without the begin's host work.  The launch rewrites, from the
+ * observes and the new tables, what a begin derives from a table: the rows log N(y_t; mean[s], 1) of every step t < T_b (-inf for
+ * s >= k) and the 64 threshold words of every problem.  The row's logarithm, log(2 pi), is evaluated once on the host with the begin's
+ * own expression; the device performs a subtraction, a product, a sum and a product by -0.5, none contracted, and the thresholds'
+ * division, product and ceil: EVERYTHING the batch returns afterwards is, bit for bit, what cpprob_hip_batch_begin_problems with these
+ * tables and the same observes returns.  Lengths, particle counts, dispatch order, descriptors and workspace stay; no workspace region
+ * is added (the status words, and the host form's copy of the observes, are allocations of the context's own).
+ * d_means [B][k], d_transition [B][k][k], k the batch's; d_observes packed as cpprob_hip_batch_begin_problems packs them, n_observes
+ * the sum of the lengths (else CPPROB_HIP_EINVAL).  A re-table is a begin as far as results go: until the next cpprob_hip_batch_run or
+ * cpprob_hip_batch_run_conditional* every read-out returns CPPROB_HIP_ESTATE.
+ * The tables are checked on the device (status bits: 1 a weight not finite or not >= 0, 2 a transition row without mass, 4 a mean not
+ * finite): a problem with a bit set keeps its previous rows and thresholds -- its next run is the old table's run -- and
+ * cpprob_hip_batch_retable_status names it.
+ * Serves a batch begun by cpprob_hip_batch_begin_problems with CPPROB_HIP_MODEL_HMM_TABLE (per-problem tables or the context's),
+ * keep_history 1 or 0, with or without CPPROB_HIP_BATCH_KEEP_MASSES, before or after runs.  CPPROB_HIP_EUNSUPPORTED, the message saying
+ * why: CPPROB_HIP_MODEL_HMM3 (its table is the model's), a cpprob_hip_batch_begin batch (one shared table), an online batch (its
+ * advances evaluate rows from host means).  CPPROB_HIP_ESTATE: no batch begun.  After any refusal nothing has changed.
+ * Enqueued on the context's stream, no host synchronisation (stream contract as cpprob_hip_batch_smooth_stats_device: the caller's
+ * buffers are complete before the call and live until the stream has passed it).  After this form the host's mirrors of the tables
+ * are stale: cpprob_hip_batch_copy_store fetches the one row it needs, and the first decode call (or cpprob_hip_batch_decode_logp)
+ * after it fetches the threshold words, which waits for the stream once. */
+int cpprob_hip_batch_retable_device(cpprob_hip_ctx* ctx, const double* d_means, const double* d_transition, const double* d_observes, size_t n_observes);
+/* The same from host arrays.  The tables are validated on the host as cpprob_hip_batch_begin_problems validates them (the same codes,
+ * the same messages naming the problem; nothing changes on a refusal), staged on the device and enqueued; the observes are copied into
+ * a buffer of the context's own.  h_observes may be NULL when the context still holds the copy a previous cpprob_hip_batch_retable of
+ * THIS begun batch staged (any begin forgets it; NULL without one: CPPROB_HIP_EINVAL) -- a loop that draws its tables on the host
+ * uploads the observes once.  n_observes is checked either way.  The host arrays may be reused when the call returns. */
+int cpprob_hip_batch_retable(cpprob_hip_ctx* ctx, const double* h_means, const double* h_transition, const double* h_observes, size_t n_observes);
+/* The status words of the last re-table of the begun batch, [n_problems]: 0, or the bits above.  Synchronises.  CPPROB_HIP_ESTATE: the
+ * begun batch has not been re-tabled. */
+int cpprob_hip_batch_retable_status(cpprob_hip_ctx* ctx, int32_t* h_status);
+/* gridDim.y of the last re-table launch, host only, as cpprob_hip_batch_smooth_grid: a workgroup writes 32 rows a trip, the grid holds
+ * min(ceil(T_max / 32), 64, max(1, 4096 / n_problems)) of them a problem and strides beyond.  0: none since the begin (or no batch). */
+int cpprob_hip_batch_retable_grid(cpprob_hip_ctx* ctx, uint32_t* grid_y);
+/* The M-step of particle EM on the device: from the records of cpprob_hip_batch_smooth_stats (d_stats [n_problems][88], n_doubles >=
+ * 88 n_problems) d_means [B][k] and d_transition [B][k][k] are updated in place, a state s < k of a problem:
+ *   row = ((0.0 + xi[s][0]) + xi[s][1]) + ... in that order;  row > 0: trans[s][j] = xi[s][j] / row;  occ[s] > 0: means[s] = occ_y[s] / occ[s]
+ * a row or a state without mass keeps its value -- cpprob_amd.em.m_step and cpprob::gpu::hmm_table_fit bit for bit.  k and
+ * n_problems are the begun batch's (CPPROB_HIP_MODEL_HMM_TABLE, else CPPROB_HIP_EUNSUPPORTED; none begun: CPPROB_HIP_ESTATE).
+ * Enqueued on the context's stream, no host synchronisation. */
+int cpprob_hip_batch_mstep_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition);
+/* Problem `problem`'s rows of the per-step table as the device holds them, h_rows [T_b][8] (n_doubles >= 8 T_b; an online batch: the
+ * length reached), and its 64 threshold words (h_thr, or NULL; a cpprob_hip_batch_begin batch: the shared table's).  Any begun batch;
+ * CPPROB_HIP_MODEL_HMM3 keeps no threshold words on the device: h_thr must be NULL (CPPROB_HIP_EINVAL).  Synchronises.  A test
+ * compares a re-tabled batch with a freshly begun one through it. */
+int cpprob_hip_batch_copy_step_tables(cpprob_hip_ctx* ctx, uint64_t problem, double* h_rows, size_t n_doubles, uint64_t* h_thr);
+/* {log_evidence, ess_final, log_norm, max_logw} of every problem into d_out [n_problems][4]: the head of
+ * cpprob_hip_batch_results_device's rows without the statistics behind it, so that a loop resident on the device keeps every
+ * iteration's evidence for 4 doubles a problem.  State as cpprob_hip_batch_results_device.  Enqueued, no host synchronisation. */
+int cpprob_hip_batch_summaries_device(cpprob_hip_ctx* ctx, double* d_out);
 
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
