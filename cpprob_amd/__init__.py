@@ -12,6 +12,8 @@ from .capi import (ALG_SIS, ALG_SMC, MODEL_GAUSSIAN_README, MODEL_GAUSSIAN_UNKNO
 
 from . import em  # noqa: F401
 from .em import hmm_table_em, m_step  # noqa: F401
+from . import online_em  # noqa: F401
+from .online_em import hmm_table_online_em  # noqa: F401
 from . import gibbs  # noqa: F401
 from .gibbs import hmm_table_gibbs, sample_tables  # noqa: F401
 from . import pgibbs  # noqa: F401

@@ -52,6 +52,8 @@ SYMBOLS = [
     "cpprob_hip_batch_run_conditional", "cpprob_hip_batch_run_conditional_device",
     "cpprob_hip_batch_retable", "cpprob_hip_batch_retable_device", "cpprob_hip_batch_retable_status", "cpprob_hip_batch_retable_grid",
     "cpprob_hip_batch_mstep_device", "cpprob_hip_batch_copy_step_tables", "cpprob_hip_batch_summaries_device",
+    "cpprob_hip_batch_learn_begin", "cpprob_hip_batch_advance_learn", "cpprob_hip_batch_advance_learn_device", "cpprob_hip_batch_online_tables",
+    "cpprob_hip_batch_learn_tables", "cpprob_hip_batch_learn_tables_device", "cpprob_hip_batch_learn_record",
 ]
 
 
@@ -386,6 +388,13 @@ def load_library(path=None):
         "cpprob_hip_batch_mstep_device": (C.c_int, [vp, vp, sz, vp, vp]),
         "cpprob_hip_batch_copy_step_tables": (C.c_int, [vp, u64, vp, sz, vp]),
         "cpprob_hip_batch_summaries_device": (C.c_int, [vp, vp]),
+        "cpprob_hip_batch_learn_begin": (C.c_int, [vp, vp, sz, C.c_uint32]),
+        "cpprob_hip_batch_advance_learn": (C.c_int, [vp, C.POINTER(C.c_uint32), vp]),
+        "cpprob_hip_batch_advance_learn_device": (C.c_int, [vp, C.POINTER(C.c_uint32), vp, sz]),
+        "cpprob_hip_batch_online_tables": (C.c_int, [vp, vp, vp]),
+        "cpprob_hip_batch_learn_tables": (C.c_int, [vp, vp, vp, C.POINTER(i32)]),
+        "cpprob_hip_batch_learn_tables_device": (C.c_int, [vp, vp, vp]),
+        "cpprob_hip_batch_learn_record": (C.c_int, [vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -434,6 +443,7 @@ class Engine:
         self.is_int = False
         self.K = 0
         self.batch_shapes = None              # (h_T, h_n) of a batch begun by batch_begin_problems
+        self.batch_k = 0                      # the states of the tables batch_begin_online / batch_online_tables took last
 
     def close(self):
         if getattr(self, "h", None):
@@ -624,6 +634,7 @@ class Engine:
             if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != h_T.size:
                 raise ValueError("tables = (means [B, k], transition [B, k, k])")
             k = means.shape[1]
+        self.batch_k = k
         self._chk(self.L.cpprob_hip_batch_begin_online(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), k,
                                                        None if means is None else means.ctypes.data, None if trans is None else trans.ctypes.data,
                                                        sd.ctypes.data_as(C.POINTER(C.c_uint64))))
@@ -732,6 +743,70 @@ class Engine:
         """em.m_step on the device (cpprob_hip_batch_mstep_device): stats torch float64 [B, 88] as batch_smooth_stats_device leaves
         them; means [B, k] and trans [B, k, k] torch float64, updated in place.  Enqueued without a host synchronisation."""
         self._chk(self.L.cpprob_hip_batch_mstep_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans)))
+
+    # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
+    def _batch_tables(self, tables):
+        means = np.ascontiguousarray(tables[0], np.float64)
+        trans = np.ascontiguousarray(tables[1], np.float64)
+        if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != self.batch_B:
+            raise ValueError("tables = (means [B, k], transition [B, k, k])")
+        self.batch_k = means.shape[1]
+        return means, trans
+
+    def batch_learn_begin(self, gamma, t_min):
+        """Arms the online MODEL_HMM_TABLE batch just begun (per-problem tables; before its first advance) for online EM
+        (cpprob_hip_batch_learn_begin): gamma[t] in (0, 1], the step size of a problem's absolute step t, at least as long as the
+        largest capacity; t_min: the length a problem must have reached before its first M-step."""
+        g = np.ascontiguousarray(gamma, np.float64).reshape(-1)
+        self._chk(self.L.cpprob_hip_batch_learn_begin(self.h, g.ctypes.data if g.size else None, g.size, int(t_min)))
+
+    def _batch_new_observes(self, new_observes):
+        seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in new_observes]
+        if len(seqs) != self.batch_B:
+            raise ValueError("one (possibly empty) sequence per problem")
+        return np.array([len(o) for o in seqs], np.uint32), (np.ascontiguousarray(np.concatenate(seqs)) if seqs else np.zeros(0))
+
+    def batch_advance_learn(self, new_observes):
+        """batch_advance on an armed batch (cpprob_hip_batch_advance_learn): the new rows are written on the device from the tables
+        in force, the new steps run, and the learn step pushes the discounted statistics, stores the record and -- where a problem
+        received observes and has reached t_min -- replaces its table and threshold words by the M-step's.  Enqueued without waiting."""
+        h_dT, flat = self._batch_new_observes(new_observes)
+        self._chk(self.L.cpprob_hip_batch_advance_learn(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), flat.ctypes.data if flat.size else None))
+        self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
+
+    def batch_advance_learn_device(self, dT, observes):
+        """The same with the new observes in a torch float64 device tensor, packed problem after problem (dT: how many each problem
+        receives); no host synchronisation."""
+        h_dT = np.ascontiguousarray(dT, np.uint32)
+        if h_dT.shape != (self.batch_B,):
+            raise ValueError("one count per problem")
+        self._chk(self.L.cpprob_hip_batch_advance_learn_device(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), _dptr(observes), 0 if observes is None else observes.numel()))
+        self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
+
+    def batch_online_tables(self, tables):
+        """New tables (means [B, k], transition [B, k, k]) for the FUTURE steps of an online MODEL_HMM_TABLE batch, armed or not
+        (cpprob_hip_batch_online_tables): validated as the begin validates them; past rows stay."""
+        means, trans = self._batch_tables(tables)
+        self._chk(self.L.cpprob_hip_batch_online_tables(self.h, means.ctypes.data, trans.ctypes.data))
+
+    def batch_learn_tables(self, k=None):
+        """(means [B, k], transition [B, k, k], status int32 [B]) of an armed batch as the device holds them: status 0, or the bits
+        of batch_retable_status of the last M-step that was dropped.  k: the batch's states (default: those of the last
+        batch_begin_online of this engine).  Synchronises."""
+        k = int(k if k is not None else self.batch_k)
+        means, trans, status = np.zeros((self.batch_B, k)), np.zeros((self.batch_B, k, k)), np.zeros(self.batch_B, np.int32)
+        self._chk(self.L.cpprob_hip_batch_learn_tables(self.h, means.ctypes.data, trans.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return means, trans, status
+
+    def batch_learn_tables_device(self, means, trans):
+        """The same tables into torch float64 device tensors (means [B, k], trans [B, k, k]): a stream-ordered copy."""
+        self._chk(self.L.cpprob_hip_batch_learn_tables_device(self.h, _dptr(means), _dptr(trans)))
+
+    def batch_learn_record(self):
+        """float64 [B, 88]: the records of the last learning advance (cpprob_hip_batch_learn_record).  Synchronises."""
+        out = np.zeros((self.batch_B, 88))
+        self._chk(self.L.cpprob_hip_batch_learn_record(self.h, out.ctypes.data, out.size))
+        return out
 
     def batch_step_tables(self, b):
         """Problem b's per-step table as the device holds it: (rows float64 [T_b, 8], threshold words uint64 [64] -- None for

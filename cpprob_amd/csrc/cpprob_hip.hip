@@ -29,6 +29,7 @@
 #include "batch_decode.hpp"
 #include "batch_csmc.hpp"
 #include "batch_retable.hpp"
+#include "batch_learn.hpp"
 #include "batch_pass_plan.hpp"
 
 using namespace cph;
@@ -1065,6 +1066,7 @@ struct BatchState {
     std::vector<char> walked_b;                // [B]: ... problem b's (keep_history = 1: the lineage walk has run over its rows)
     std::vector<uint32_t> cap_T;               // [B]
     std::vector<double> means;                 // HMM_TABLE: [tables][hk], the rows an advance evaluates its steps' tables with
+    std::vector<double> trans;                 // HMM_TABLE with per-problem tables: [B][hk][hk], what cpprob_hip_batch_learn_begin uploads
     double* pin_tab = nullptr; size_t pin_tab_cap = 0;      // pinned mirror of the table region: an advance writes its new rows only
     // pinned descriptors of an advance in flight, kOnlineSlots in turn: {BatchProblem[B], first[B], order[B]}; a slot is written
     // again once the copies that read it have run (its event)
@@ -1120,12 +1122,32 @@ struct BatchState {
     double* d_robs = nullptr; size_t robs_cap = 0;
     bool retabled = false, robs_ready = false, tab_stale = false, thr_stale = false;
     unsigned retable_gy = 0;                                // gridDim.y of the last re-table launch (0: none)
+    // online EM (cpprob_hip_batch_learn_*; csrc/batch_learn.hpp): own_tables: the batch was begun with per-problem tables; armed: the
+    // begun online batch learns its tables -- the step sizes [n_gamma], the device-resident tables (means [B][k], transition [B][k][k]),
+    // the learner's tau [B][8][88], the records [B][88], the status words [B], the first new observes of an advance ([B] int64, with
+    // their pinned sources, kOnlineSlots in turn as an advance's descriptors) and the host form's copy of an advance's observes,
+    // allocations of the context's own
+    bool own_tables = false, armed = false;
+    uint32_t learn_t_min = 0;
+    double *d_gamma = nullptr, *d_lmeans = nullptr, *d_ltrans = nullptr, *d_ltau = nullptr, *d_lrec = nullptr, *d_lobs = nullptr;
+    int32_t* d_lstatus = nullptr;
+    int64_t *d_lfirst = nullptr, *pin_lfirst = nullptr;
+    size_t lobs_cap = 0;
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
+
+// Disarms: the learner's allocations go (hipFree waits for the device: no kernel still reads them).
+void batch_learn_free(BatchState* bs)
+{
+    dfree(bs->d_gamma); dfree(bs->d_lmeans); dfree(bs->d_ltrans); dfree(bs->d_ltau); dfree(bs->d_lrec); dfree(bs->d_lobs); dfree(bs->d_lstatus); dfree(bs->d_lfirst);
+    if (bs->pin_lfirst) { (void)hipHostFree(bs->pin_lfirst); bs->pin_lfirst = nullptr; }
+    bs->lobs_cap = 0; bs->armed = false;
+}
 
 void batch_free(cpprob_hip_ctx* c)
 {
     if (!c->batch) return;
+    batch_learn_free(c->batch);
     dfree(c->batch->d_ws);                     // (hipFree waits for the device: no copy still reads the pinned buffers)
     if (c->batch->pin_tab) (void)hipHostFree(c->batch->pin_tab);
     if (c->batch->pin_desc) (void)hipHostFree(c->batch->pin_desc);
@@ -1209,6 +1231,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->decoded.assign(B, 0); bs->lp_ready = false; bs->lp_sent = false;
     bs->ostats_done.assign(B, 0);
     bs->retabled = false; bs->robs_ready = false; bs->tab_stale = false; bs->thr_stale = false; bs->retable_gy = 0;
+    if (bs->armed) batch_learn_free(bs);
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3, described = h_T != nullptr, own = h_means != nullptr;
     const int spp = hmm3 ? 3 : 8;
     const uint64_t tables = described ? B : 1;
@@ -1236,7 +1259,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         for (hipEvent_t& e : bs->slot_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         bs->cap_T.assign(h_T, h_T + B);
         bs->walked_b.assign(B, 1);
-        bs->means.clear();
+        bs->means.clear(); bs->trans.clear();
         bs->n_advance = 0;
         bs->h_tab.clear();
     } else bs->h_tab.assign((size_t)B * T_max * kBatchTab, 0.0);
@@ -1251,7 +1274,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     for (uint64_t b = 0; b < B; ++b) {
         const size_t T_b = described ? h_T[b] : T_max, n_b = described ? h_n[b] : (size_t)cfg->n_particles;
         if (own) { mean.assign(h_means + b * (size_t)k, h_means + (b + 1) * (size_t)k); trans.assign(h_transition + b * (size_t)k * k, h_transition + (b + 1) * (size_t)k * k); }
-        if (online && own) bs->means.insert(bs->means.end(), mean.begin(), mean.end());
+        if (online && own) { bs->means.insert(bs->means.end(), mean.begin(), mean.end()); bs->trans.insert(bs->trans.end(), trans.begin(), trans.end()); }
         for (size_t t = 0; t < (online ? 0 : T_b); ++t) {
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
@@ -1307,7 +1330,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
-    bs->online = online; bs->walked = true;
+    bs->online = online; bs->walked = true; bs->own_tables = own;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -4288,12 +4311,20 @@ int cpprob_hip_batch_begin_online(cpprob_hip_ctx* c, const cpprob_hip_batch_conf
     return batch_begin(c, cfg, (size_t)sh.T_max, h_Tcap, h_n, nullptr, k, h_means, h_transition, h_seeds);
 }
 
-int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs, int32_t readout)
+static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs);
+
+// One advance of the begun online batch.  Plain (cpprob_hip_batch_advance): the new rows are evaluated on the host from bs->means and
+// copied.  Learning (cpprob_hip_batch_advance_learn*, learn: the batch is armed): the rows are written on the device from the
+// device-resident tables and the observes (d_obs, or h_obs copied into a buffer of the context's own), and the learn step follows the
+// launch (csrc/batch_learn.hpp).  Nothing changes before every check has passed.
+static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs, const double* d_obs, size_t n_observes, int32_t readout, bool learn)
 {
-    LANES_OWN(c);
     if (!c || !h_dT) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
-    if (!bs || !bs->begun || !bs->online) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_advance serves a batch begun by cpprob_hip_batch_begin_online");
+    if (!bs || !bs->begun || !bs->online)
+        return fail(c, CPPROB_HIP_ESTATE, std::string(learn ? "cpprob_hip_batch_advance_learn" : "cpprob_hip_batch_advance") + " serves a batch begun by cpprob_hip_batch_begin_online");
+    if (learn && !bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the online batch is not armed: call cpprob_hip_batch_learn_begin before its first advance");
+    if (!learn && bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the online batch learns its tables (cpprob_hip_batch_learn_begin): it is advanced by cpprob_hip_batch_advance_learn");
     const uint64_t B = bs->cfg.n_problems;
     uint64_t total = 0;
     for (uint64_t b = 0; b < B; ++b) {
@@ -4302,8 +4333,21 @@ int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const doub
                                               " exceed its capacity of " + std::to_string(bs->cap_T[b]));
         total += h_dT[b];
     }
-    if (total && !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (total && !h_obs && !d_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (learn && !h_obs && (uint64_t)n_observes != total)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the advance hands over " + std::to_string(total) + " observes (the sum of h_dT)");
     HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<uint32_t> before;                              // (learning: the lengths the learn step resumes from)
+    if (learn) {
+        before.resize(B);
+        for (uint64_t b = 0; b < B; ++b) before[b] = (uint32_t)bs->prob[b].T;
+        if (h_obs && total > bs->lobs_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (the advance before may still read the buffer this replaces)
+            dfree(bs->d_lobs); bs->lobs_cap = 0;
+            HIP_TRY(c, hipMalloc(&bs->d_lobs, (size_t)total * sizeof(double)));
+            bs->lobs_cap = (size_t)total;
+        }
+    }
     // this advance's descriptors: its slot is free once the copies of the advance that used it last have run
     const int slot = (int)(bs->n_advance % BatchState::kOnlineSlots);
     if (bs->n_advance >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->slot_done[slot]));
@@ -4311,6 +4355,7 @@ int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const doub
     BatchProblem* pr = reinterpret_cast<BatchProblem*>(sl);
     int32_t* first = reinterpret_cast<int32_t*>(sl + B * sizeof(BatchProblem));
     int32_t* order = first + B;
+    int64_t* ofirst = learn ? bs->pin_lfirst + (size_t)slot * B : nullptr;
     const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3, keep = bs->cfg.keep_history == 1;
     const size_t hk = (size_t)bs->hk, T_max = (size_t)bs->T, row_bytes = kBatchTab * sizeof(double);
     const bool own = !hmm3 && bs->means.size() > hk;
@@ -4319,8 +4364,9 @@ int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const doub
     size_t at_obs = 0;
     for (uint64_t b = 0; b < B; ++b) {
         const size_t L = (size_t)bs->prob[b].T;
-        if (own && h_dT[b]) mean.assign(bs->means.begin() + (ptrdiff_t)(b * hk), bs->means.begin() + (ptrdiff_t)((b + 1) * hk));
-        for (size_t t = L; t < L + h_dT[b]; ++t) {
+        if (learn) { ofirst[b] = (int64_t)at_obs; at_obs += h_dT[b]; }
+        if (own && h_dT[b] && !learn) mean.assign(bs->means.begin() + (ptrdiff_t)(b * hk), bs->means.begin() + (ptrdiff_t)((b + 1) * hk));
+        for (size_t t = L; !learn && t < L + h_dT[b]; ++t) {
             const double y = h_obs[at_obs++];
             double* row = bs->pin_tab + (b * T_max + t) * kBatchTab;
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
@@ -4338,7 +4384,7 @@ int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const doub
     auto cost = [&](int32_t b) { return (uint64_t)h_dT[b] * (((uint64_t)bs->prob[b].n + kTile - 1) / kTile); };
     std::stable_sort(order, order + B, [&](int32_t x, int32_t y) { return cost(x) > cost(y); });
     // the new rows: one strided copy per run of problems that share first step and piece length
-    for (uint64_t b = 0; b < B;) {
+    for (uint64_t b = 0; !learn && b < B;) {
         uint64_t e = b + 1;
         while (e < B && bs->prob[e].T == bs->prob[b].T && h_dT[e] == h_dT[b]) ++e;
         if (h_dT[b]) {
@@ -4351,13 +4397,49 @@ int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const doub
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.prob, pr, B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.first, first, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.order, order, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (learn) HIP_TRY(c, hipMemcpyAsync(bs->d_lfirst, ofirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(bs->slot_done[slot], c->stream));
     ++bs->n_advance;
+    if (learn && total) {
+        // the new rows, on the device: from the observes and the tables in force
+        if (h_obs) { HIP_TRY(c, hipMemcpyAsync(bs->d_lobs, h_obs, (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream)); d_obs = bs->d_lobs; }
+        uint32_t top = 0;
+        for (uint64_t b = 0; b < B; ++b) top = std::max(top, h_dT[b]);
+        BatchLearnRowsArgs ra{};
+        ra.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+        ra.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
+        ra.ofirst = bs->d_lfirst; ra.means = bs->d_lmeans; ra.obs = d_obs;
+        ra.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+        ra.log_norm = std::log(2 * kPi * 1.0 * 1.0);              // (normal_logpdf's own expression at sigma = 1.0)
+        ra.T_max = bs->T; ra.k = bs->hk;
+        hipLaunchKernelGGL(batch_learn_rows_kernel, dim3((unsigned)B, retable_grid_y(top, (int64_t)B)), dim3(kThreads), 0, c->stream, ra);
+        HIP_TRY(c, hipGetLastError());
+        bs->tab_stale = true;
+    }
     bool work = false, walked = true;
     for (uint64_t b = 0; b < B; ++b) { work = work || first[b] >= 0; walked = walked && bs->walked_b[b]; }
     if (work) if (int rc = batch_launch(c, bs, readout != 0)) return rc;
     bs->walked = walked;
+    if (learn) return batch_learn_enqueue(c, before.data(), total ? d_obs : nullptr);
     return 0;
+}
+
+int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs, int32_t readout)
+{
+    LANES_OWN(c);
+    return batch_advance(c, h_dT, h_obs, nullptr, 0, readout, false);
+}
+
+int cpprob_hip_batch_advance_learn(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs)
+{
+    LANES_OWN(c);
+    return batch_advance(c, h_dT, h_obs, nullptr, 0, 1, true);
+}
+
+int cpprob_hip_batch_advance_learn_device(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* d_obs, size_t n_observes)
+{
+    LANES_OWN(c);
+    return batch_advance(c, h_dT, nullptr, d_obs, n_observes, 1, true);
 }
 
 int cpprob_hip_batch_lengths(cpprob_hip_ctx* c, uint32_t* h_L)
@@ -4665,12 +4747,15 @@ static BatchPassBatch<BatchProblem> batch_pass_batch(const BatchState* bs)
 // calls before it (their copies and kernels may still read what it replaces); the wait for the pinned slot (the copy that read it
 // kOnlineSlots calls ago); the plan's descriptors with the HMM3 thresholds behind them, their copy and its event; the shared arguments;
 // the counting pass (an online batch's m table is addressed by capacity and kept: rows [counted_b, L_b), and the watermark moves).
-static int batch_pass_prologue(cpprob_hip_ctx* c, const BatchPass& p, BatchPassPlan& pl, BatchSmoothArgs& a)
+// (done: a learning advance's OnlineStats pass -- the steps consumed are the lengths before the advance, and tau is the learner's)
+static int batch_pass_prologue(cpprob_hip_ctx* c, const BatchPass& p, BatchPassPlan& pl, BatchSmoothArgs& a, const uint32_t* done = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, thr_bytes = 64 * sizeof(uint64_t), bytes = batch_round(B * sizeof(BatchSmoothProblem)) + thr_bytes;
     const bool hmm3 = batch_hmm3(bs), kept = batch_masses(&bs->cfg);
-    pl = batch_pass_plan(batch_pass_batch(bs), p);
+    BatchPassBatch<BatchProblem> bt = batch_pass_batch(bs);
+    if (done) bt.ostats_done = done;
+    pl = batch_pass_plan(bt, p);
     if (pl.marg_bytes) HIP_TRY(c, hipMemsetAsync(p.d_marg, 0, pl.marg_bytes, c->stream));
     if (pl.stats_bytes) HIP_TRY(c, hipMemsetAsync(p.d_stats, 0, pl.stats_bytes, c->stream));
     if (pl.traj_bytes) HIP_TRY(c, hipMemsetAsync(p.d_traj, 0, pl.traj_bytes, c->stream));
@@ -4695,7 +4780,7 @@ static int batch_pass_prologue(cpprob_hip_ctx* c, const BatchPass& p, BatchPassP
         }
     }
     if (p.decodes()) { if (int rc = batch_decode_prepare(c, pl.word_rows)) return rc; }
-    if (p.kind == BatchPass::OnlineStats && B > bs->tau_cap) {
+    if (p.kind == BatchPass::OnlineStats && !done && B > bs->tau_cap) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         dfree(bs->d_tau); bs->tau_cap = 0;
         bs->ostats_done.assign(B, 0);
@@ -4705,7 +4790,7 @@ static int batch_pass_prologue(cpprob_hip_ctx* c, const BatchPass& p, BatchPassP
     const int slot = (int)(bs->n_smooth % BatchState::kOnlineSlots);
     if (bs->n_smooth >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->sdesc_done[slot]));
     char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap; const size_t thr_at = bs->sdesc_cap - thr_bytes;
-    batch_pass_describe(batch_pass_batch(bs), p, reinterpret_cast<BatchSmoothProblem*>(sl), pl);      // (after the growth: it reads the watermarks)
+    batch_pass_describe(bt, p, reinterpret_cast<BatchSmoothProblem*>(sl), pl);      // (after the growth: it reads the watermarks)
     // CPPROB_HIP_MODEL_HMM3: its thresholds as a table row set of CPPROB_HIP_MODEL_HMM_TABLE ([k][8], entries 0..k-2), behind the descriptors
     uint64_t* h3 = reinterpret_cast<uint64_t*>(sl + thr_at);
     for (int i = 0; i < 64; ++i) h3[i] = ~0ull;
@@ -5456,6 +5541,140 @@ int cpprob_hip_batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size
     a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.B = (int64_t)B; a.k = bs->hk;
     hipLaunchKernelGGL(batch_mstep_kernel, dim3((unsigned)((B * (uint64_t)bs->hk + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// ---- online EM of an online batch (csrc/batch_learn.hpp) ----------------------------------------------------------------------------
+// What the host route and the arming share: an online CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables.
+static int batch_learn_check(cpprob_hip_ctx* c, const char* who)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->online) return fail(c, CPPROB_HIP_ESTATE, std::string(who) + " serves a batch begun by cpprob_hip_batch_begin_online");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, std::string(who) + " serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
+    if (!bs->own_tables) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the batch was begun with the context's shared table: begin it with per-problem tables to change them");
+    return 0;
+}
+
+int cpprob_hip_batch_learn_begin(cpprob_hip_ctx* c, const double* h_gamma, size_t n_gamma, uint32_t t_min)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_check(c, "cpprob_hip_batch_learn_begin")) return rc;
+    BatchState* bs = c->batch;
+    if (bs->cfg.keep_history != 1 && !batch_masses(&bs->cfg))
+        return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no masses: begin it with CPPROB_HIP_BATCH_KEEP_MASSES");
+    if (bs->n_advance) return fail(c, CPPROB_HIP_ESTATE, "the online batch has been advanced: cpprob_hip_batch_learn_begin comes before the first advance");
+    if (!h_gamma) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (n_gamma < (size_t)bs->T) return fail(c, CPPROB_HIP_EINVAL, "n_gamma = " + std::to_string(n_gamma) + " lies below the largest capacity, " + std::to_string(bs->T));
+    for (size_t t = 0; t < n_gamma; ++t)
+        if (!(h_gamma[t] > 0.0) || !(h_gamma[t] <= 1.0)) return fail(c, CPPROB_HIP_EINVAL, "gamma[" + std::to_string(t) + "] lies outside (0, 1]");
+    HIP_TRY(c, hipSetDevice(c->device));
+    batch_learn_free(bs);
+    const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
+    HIP_TRY(c, hipMalloc(&bs->d_gamma, n_gamma * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&bs->d_lmeans, B * k * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&bs->d_ltrans, B * k * k * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&bs->d_ltau, B * (size_t)kOnlineTau * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&bs->d_lrec, B * (size_t)kOnlineStats * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&bs->d_lstatus, B * sizeof(int32_t)));
+    HIP_TRY(c, hipMalloc(&bs->d_lfirst, B * sizeof(int64_t)));
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_lfirst), B * BatchState::kOnlineSlots * sizeof(int64_t), hipHostMallocDefault));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_gamma, h_gamma, n_gamma * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_lmeans, bs->means.data(), B * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ltrans, bs->trans.data(), B * k * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->d_ltau, 0, B * (size_t)kOnlineTau * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->d_lrec, 0, B * (size_t)kOnlineStats * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->d_lstatus, 0, B * sizeof(int32_t), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));               // (h_gamma may be reused when the call returns)
+    bs->learn_t_min = t_min; bs->armed = true;
+    return 0;
+}
+
+// The learn step of a learning advance, behind its launch: the prologue of a running-statistics pass that resumes from the lengths
+// before the advance (a batch with a particle store: the counting pass over the new rows first), then batch_learn_kernel.  The
+// thresholds and, through them, the decode's log tables and step words are the device's from here on.
+static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs)
+{
+    BatchState* bs = c->batch; const size_t B = bs->cfg.n_problems;
+    BatchPassPlan pl; BatchSmoothArgs a{};
+    if (int rc = batch_pass_prologue(c, BatchPass::online_stats(d_obs, bs->d_lrec), pl, a, before)) return rc;
+    if (pl.done) return 0;
+    BatchLearnArgs la{};
+    la.desc = a.desc; la.mass = a.mass; la.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr); la.obs = d_obs; la.gamma = bs->d_gamma;
+    la.tau = bs->d_ltau; la.stats = bs->d_lrec; la.means = bs->d_lmeans; la.trans = bs->d_ltrans; la.status = bs->d_lstatus;
+    la.B = (int)B; la.k = bs->hk; la.t_min = (int)std::min<uint32_t>(bs->learn_t_min, (uint32_t)INT32_MAX);
+    hipLaunchKernelGGL(batch_learn_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, la);
+    HIP_TRY(c, hipGetLastError());
+    bs->thr_stale = true; bs->lp_ready = false; bs->lp_sent = false;
+    bs->decoded.assign(B, 0);
+    return 0;
+}
+
+int cpprob_hip_batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const double* h_transition)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_check(c, "cpprob_hip_batch_online_tables")) return rc;
+    BatchState* bs = c->batch;
+    if (!h_means || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    int k = 0;
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
+    bs->means.assign(h_means, h_means + B * (size_t)k);
+    bs->trans.assign(h_transition, h_transition + B * kk);
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    if (bs->armed) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lmeans, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_ltrans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    // the host knows the words again; the decode's log tables and step words follow them
+    bs->thr_stale = false; bs->lp_ready = false; bs->lp_sent = false;
+    bs->decoded.assign(B, 0);
+    return 0;
+}
+
+int cpprob_hip_batch_learn_tables(cpprob_hip_ctx* c, double* h_means, double* h_transition, int32_t* h_status)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the begun batch is not armed (cpprob_hip_batch_learn_begin)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
+    if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_lmeans, B * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_transition) HIP_TRY(c, hipMemcpyAsync(h_transition, bs->d_ltrans, B * k * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_status) HIP_TRY(c, hipMemcpyAsync(h_status, bs->d_lstatus, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int cpprob_hip_batch_learn_tables_device(cpprob_hip_ctx* c, double* d_means, double* d_transition)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the begun batch is not armed (cpprob_hip_batch_learn_begin)");
+    if (!d_means || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
+    HIP_TRY(c, hipMemcpyAsync(d_means, bs->d_lmeans, B * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_transition, bs->d_ltrans, B * k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+int cpprob_hip_batch_learn_record(cpprob_hip_ctx* c, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the begun batch is not armed (cpprob_hip_batch_learn_begin)");
+    if (!h_stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const size_t need = (size_t)bs->cfg.n_problems * kOnlineStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(h_stats, bs->d_lrec, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 

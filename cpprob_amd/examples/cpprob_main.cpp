@@ -38,6 +38,10 @@
 //                   --conditional_paths FILE (with --batch_tables_file --filtering_only --keep_masses: the run is the conditional SMC run,
 //                   problem b's retained particle following line b of FILE, T_b states; the estimates print as 0 -- such a run keeps
 //                   masses, not books -- and --trajectory_stats, --backward_smoothing, --forecast and --decode read its masses as usual)
+//                   --online_em [--em_step_exponent A] [--em_burn_in T] (with --batch_tables_file --stream_chunk K: online EM -- after every
+//                   chunk the stream's tables are refitted on the device from the discounted running statistics, step sizes (t + 1)^-A
+//                   (0.6), no M-step before T observes (20), and the next chunk is filtered under them; the final tables are printed as
+//                   --em_iterations prints them)
 //                   --running_stats (with --batch_tables_file --stream_chunk K: every chunk is followed by the forward-only update of the
 //                   expected sufficient statistics, at the cost of the chunk's steps; after everything else one line a problem, the
 //                   record of the lengths reached in --trajectory_stats' format)
@@ -295,6 +299,7 @@ int execute_batch_tables(const Args& a)
             res = stream.advance(piece, at + a.stream_chunk >= longest);
         }
         if (a.batch_dump) stream.dump(dump_prefix);
+        if (cpprob::gpu::options().learn_tables) fitted = stream.tables();      // --online_em: the tables the stream has learned
     }
     std::cout.precision(17);
     for (const cpprob::gpu::Result& r : res) {
@@ -380,6 +385,9 @@ int main(int argc, char** argv)
         else if (f == "--decode") opt.map_decode = true;                           // the batch modes: the most probable state path (cpprob_hip_batch_decode)
         else if (f == "--decode_lag") opt.decode_lag = std::stol(next());          // ... its fixed-lag rows instead (cpprob_hip_batch_decode_lag)
         else if (f == "--trajectory_stats") opt.trajectory_stats = std::stoull(next());   // the batch modes: the records of this many backward-simulated trajectories a problem (cpprob_hip_batch_traj_stats)
+        else if (f == "--online_em") opt.learn_tables = true;                      // --batch_tables_file --stream_chunk: the stream learns its tables on the device (cpprob_hip_batch_advance_learn)
+        else if (f == "--em_step_exponent") opt.learn_step_exponent = std::stod(next());   // ... with the step sizes (t + 1) ^ -A
+        else if (f == "--em_burn_in") opt.learn_burn_in = std::stoull(next());      // ... and no M-step before a problem has this many observes
         else if (f == "--running_stats") opt.running_stats = true;                 // --batch_tables_file --stream_chunk: the expected statistics kept forward-only (cpprob_hip_batch_online_stats)
         else if (f == "--draw_index") opt.trajectory_stats_draw_index = std::stoull(next());   // ... under this draw index
         else if (f == "--forecast") opt.forecast_horizon = std::stoull(next());   // the batch modes: the state's laws this many steps ahead (cpprob_hip_batch_forecast)
@@ -432,6 +440,14 @@ int main(int argc, char** argv)
     }
     if (opt.running_stats && (a.batch_tables_file.empty() || a.stream_chunk == 0)) {
         std::cerr << "--running_stats follows a stream: set --batch_tables_file and --stream_chunk" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (opt.learn_tables && (a.batch_tables_file.empty() || a.stream_chunk == 0)) {
+        std::cerr << "--online_em learns the tables of a stream: set --batch_tables_file and --stream_chunk" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (opt.learn_tables && !opt.keep_history && !opt.keep_masses) {
+        std::cerr << "--online_em reads the smoother's masses: with --filtering_only set --keep_masses" << std::endl;
         return EXIT_FAILURE;
     }
     if (opt.running_stats && !opt.keep_history && !opt.keep_masses) {

@@ -1041,6 +1041,10 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // options().running_stats: every advance's results carry the expected sufficient statistics of the lengths reached
 // (Result::running_stats), kept forward-only on the device (cpprob_hip_batch_online_stats): the call consumes the advance's own
 // observes and costs its new steps, whatever length the stream has reached; a problem without observes has a zero record.
+// options().learn_tables: online EM -- the stream is armed (cpprob_hip_batch_learn_begin, step sizes (t + 1) ^ -options().learn_step_exponent,
+// burn-in options().learn_burn_in) and every advance is a learning advance (cpprob_hip_batch_advance_learn, with the read-out walk):
+// the tables change between advances, the chunk is the update period, log_evidence is the prequential likelihood under the tables in
+// force at each step; tables() reads what the stream has learned.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -1055,6 +1059,8 @@ public:
         check_trajectory_stats_options("cpprob::gpu::HmmTableStream", traj_stats_M_, traj_stats_draw_, keep_ || masses_);
         if (!keep_ && !masses_ && running_stats_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: options().running_stats reads the smoother's masses: a filtering-only run (options().keep_history = false) keeps none without options().keep_masses");
+        if (!keep_ && !masses_ && learn_)
+            throw std::runtime_error("cpprob::gpu::HmmTableStream: options().learn_tables reads the smoother's masses: a filtering-only run (options().keep_history = false) keeps none without options().keep_masses");
         if (!keep_ && !masses_ && backward_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: backward smoothing reads the particle store: a filtering-only run (options().keep_history = false) keeps none");
         if (!keep_ && !masses_ && lag_ >= 0)
@@ -1091,6 +1097,13 @@ public:
         Context& ctx = *lease_;
         ctx.check(cpprob_hip_batch_begin_online(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), seeds.data()),
                   "cpprob_hip_batch_begin_online");
+        if (learn_) {
+            // the step sizes, evaluated here: the device takes no power
+            std::vector<double> gamma(T_max_);
+            for (std::size_t t = 0; t < T_max_; ++t) gamma[t] = std::pow(static_cast<double>(t) + 1.0, -opt.learn_step_exponent);
+            ctx.check(cpprob_hip_batch_learn_begin(ctx.get(), gamma.data(), gamma.size(), static_cast<std::uint32_t>(std::min<std::size_t>(opt.learn_burn_in, 0xffffffffu))),
+                      "cpprob_hip_batch_learn_begin");
+        }
         lease_.done();
         if (lag_ >= 0) { lagged_.assign(B_ * T_max_ * 8, 0.0); L_prev_.assign(B_, 0); }
         if (decode_ && decode_lag_ >= 0) { decoded_.assign(B_ * T_max_, -1); dec_prev_.assign(B_, 0); }
@@ -1111,7 +1124,9 @@ public:
         }
         Context& ctx = *lease_;
         const auto t0 = std::chrono::steady_clock::now();
-        ctx.check(cpprob_hip_batch_advance(ctx.get(), dT.data(), flat.empty() ? nullptr : flat.data(), readout ? 1 : 0), "cpprob_hip_batch_advance");
+        // (a learning stream's advance does the read-out walk every time)
+        if (learn_) ctx.check(cpprob_hip_batch_advance_learn(ctx.get(), dT.data(), flat.empty() ? nullptr : flat.data()), "cpprob_hip_batch_advance_learn");
+        else ctx.check(cpprob_hip_batch_advance(ctx.get(), dT.data(), flat.empty() ? nullptr : flat.data(), readout ? 1 : 0), "cpprob_hip_batch_advance");
         ctx.check(cpprob_hip_batch_lengths(ctx.get(), L.data()), "cpprob_hip_batch_lengths");
         // (the backward smoother reads the store, not the read-out: its marginals are there after every advance)
         const bool lagged = lag_ >= 0, with_stats = readout || !keep_ || backward_ || lagged;
@@ -1191,6 +1206,21 @@ public:
         return out;
     }
 
+    // options().learn_tables: the tables the stream has learned so far, one a problem, as the device holds them (synchronises).
+    std::vector<HmmTable> tables()
+    {
+        if (!learn_) throw std::runtime_error("cpprob::gpu::HmmTableStream: tables() reads the tables of a learning stream: set options().learn_tables");
+        Context& ctx = *lease_;
+        std::vector<double> means(B_ * k_), trans(B_ * k_ * k_);
+        ctx.check(cpprob_hip_batch_learn_tables(ctx.get(), means.data(), trans.data(), nullptr), "cpprob_hip_batch_learn_tables");
+        std::vector<HmmTable> out(B_);
+        for (std::size_t b = 0; b < B_; ++b) {
+            out[b].means.assign(means.begin() + static_cast<std::ptrdiff_t>(b * k_), means.begin() + static_cast<std::ptrdiff_t>((b + 1) * k_));
+            out[b].transition.assign(trans.begin() + static_cast<std::ptrdiff_t>(b * k_ * k_), trans.begin() + static_cast<std::ptrdiff_t>((b + 1) * k_ * k_));
+        }
+        return out;
+    }
+
     // Problem b's posterior as <prefix>_<b>.int / .ids for the lengths reached: the first dump_max_ traces (0 = all).
     void dump(const std::string& prefix)
     {
@@ -1219,6 +1249,7 @@ private:
     std::uint64_t traj_stats_draw_ = options().trajectory_stats_draw_index;
     std::vector<std::vector<double>> seen_;    // trajectory_stats: [b] = problem b's observes so far
     bool running_stats_ = options().running_stats;
+    bool learn_ = options().learn_tables;
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

@@ -50,6 +50,11 @@ struct Options {
     bool running_stats = false;                       // HmmTableStream (keep_history, or keep_masses): every advance's results carry Result::running_stats, the
                                                       // expected sufficient statistics of the lengths reached, kept forward-only on the device
                                                       // (cpprob_hip_batch_online_stats): an advance costs its new steps, whatever length the stream has reached
+    bool learn_tables = false;                        // HmmTableStream (keep_history, or keep_masses): online EM -- the stream learns its tables on the device while
+                                                      // its observes arrive (cpprob_hip_batch_learn_begin, _advance_learn): after every advance the M-step on the
+                                                      // discounted running statistics gives the tables the next observes are filtered under; tables() reads them
+    double learn_step_exponent = 0.6;                 // ... with the step sizes gamma[t] = (t + 1) ^ -this, evaluated on the host (0.5 < exponent <= 1)
+    std::size_t learn_burn_in = 20;                   // ... and no M-step before a problem has reached this length
     bool map_decode = false;                          // batched runs (keep_history, or keep_masses): every result carries Result::map_path, the single most
                                                       // probable state sequence given the observes over the states the particles occupy, and
                                                       // Result::map_score (cpprob_hip_batch_decode); hmm_table_fit decodes under the fitted tables

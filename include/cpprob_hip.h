@@ -733,6 +733,54 @@ int cpprob_hip_batch_copy_step_tables(cpprob_hip_ctx* ctx, uint64_t problem, dou
  * iteration's evidence for 4 doubles a problem.  State as cpprob_hip_batch_results_device.  Enqueued, no host synchronisation. */
 int cpprob_hip_batch_summaries_device(cpprob_hip_ctx* ctx, double* d_out);
 
+/* ---- online EM: an online batch whose tables are learned on the device while its observes arrive (csrc/batch_learn.hpp) --
+ * The stochastic-approximation form of Cappe 2011, Alg. 1: every step discounts the running statistics by 1 - gamma[t] and adds the
+ * new ones with weight gamma[t]; the M-step on the running record gives new tables; the next observes are filtered under them.
+ * cpprob_hip_batch_learn_begin arms the batch begun by cpprob_hip_batch_begin_online (CPPROB_HIP_MODEL_HMM_TABLE with per-problem
+ * tables; keep_history = 1, or keep_history = 0 with CPPROB_HIP_BATCH_KEEP_MASSES): the step sizes h_gamma[t], 0 < gamma <= 1,
+ * indexed by a problem's absolute step (n_gamma >= the largest capacity; the host evaluates them, the device takes no power), the
+ * burn-in t_min -- the length a problem must have reached before its first M-step -- and a device-resident copy of every problem's
+ * table (means [B][k], transition [B][k][k]; allocations of the context's own, no workspace region is added).
+ * CPPROB_HIP_ESTATE: no online batch begun, a filtering-only batch without the masses bit, or an advance has been made.
+ * CPPROB_HIP_EUNSUPPORTED: CPPROB_HIP_MODEL_HMM3, or a batch begun with the context's shared table.  CPPROB_HIP_EINVAL: n_gamma below
+ * the largest capacity, a gamma outside (0, 1].  Any begin disarms.  After any refusal nothing has changed. */
+int cpprob_hip_batch_learn_begin(cpprob_hip_ctx* ctx, const double* h_gamma, size_t n_gamma, uint32_t t_min);
+/* A learning advance: problem b receives h_dT[b] >= 0 new observes (packed problem after problem, as cpprob_hip_batch_advance takes
+ * them; the capacity check and its message are that call's).  Three steps are enqueued and the call returns without waiting:
+ *   rows   the rows of the steps [L_b, L_b + dT_b) from the observes and the device tables in force, the statements of a begin's
+ *          rows (log(2 pi) from the host, nothing contracted); rows a problem has taken before are not touched
+ *   run    the launch cpprob_hip_batch_advance makes over the new steps (keep_history = 1: with the read-out walk, readout = 1)
+ *   learn  a wavefront a problem: for every new step t, with g = gamma[t] and om = 1.0 - g, the discounted forward recursion
+ *            tau'[s'][j] = sum over s ascending of w[s'][s] (om tau[s][j] + g [j == 8 s + s']),  w as cpprob_hip_batch_online_stats',
+ *            tau'[s'][64 + s'] += g,  tau'[s'][72 + s'] += g y,  tau'[s'][80 + s'] += g (y y)      (step 0: from zeros)
+ *          on a tau of the learner's own (cpprob_hip_batch_online_stats keeps its sums); the record [88] at the new length, read out
+ *          as that call reads its own; and, where dT_b > 0 and the new length is >= t_min, cpprob_hip_batch_mstep_device's M-step on
+ *          the record: the new table is checked (the status bits of cpprob_hip_batch_retable_device) and either replaces the device
+ *          table and the problem's 64 threshold words (status 0) or is dropped (the old table and words stay, status = the bits).
+ * With gamma[t] = 1 / (t + 1) the record is the running mean of cpprob_hip_batch_online_stats' sums.
+ * Tables change only between advances: the chunk is the caller's update period.  The summaries' log_evidence is the prequential
+ * likelihood under the tables in force at each step.  Smoothing, forecast, decode and statistics calls read the m table with the
+ * CURRENT threshold words for every row.  The host's mirrors of rows and thresholds are stale afterwards, exactly as after
+ * cpprob_hip_batch_retable_device: cpprob_hip_batch_copy_store and the decode calls fetch what they need.
+ * CPPROB_HIP_ESTATE: the batch is not armed.  On an armed batch a plain cpprob_hip_batch_advance returns CPPROB_HIP_ESTATE: the two
+ * routes do not mix.  After any refusal nothing has changed. */
+int cpprob_hip_batch_advance_learn(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const double* h_observes);
+/* The same with the observes in device memory (n_observes = the sum of h_dT, else CPPROB_HIP_EINVAL); stream contract as
+ * cpprob_hip_batch_online_stats_device. */
+int cpprob_hip_batch_advance_learn_device(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const double* d_observes, size_t n_observes);
+/* The host route: new tables for the FUTURE steps of an online CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables, armed or
+ * not.  The tables are validated as the begin validates them (the same codes and messages naming the problem); they replace the host
+ * means the next cpprob_hip_batch_advance evaluates its rows from, the threshold words are uploaded stream-ordered, and on an armed
+ * batch the device tables are replaced too.  Past rows stay.  (cpprob_hip_batch_retable* keeps refusing online batches.) */
+int cpprob_hip_batch_online_tables(cpprob_hip_ctx* ctx, const double* h_means, const double* h_transition);
+/* The device-resident tables of an armed batch, h_means [B][k], h_transition [B][k][k], and the status words [B] (any may be NULL):
+ * 0, or the bits of the last M-step that was dropped (a problem no M-step has visited: 0).  Synchronises. */
+int cpprob_hip_batch_learn_tables(cpprob_hip_ctx* ctx, double* h_means, double* h_transition, int32_t* h_status);
+/* The same tables into device buffers, a stream-ordered copy. */
+int cpprob_hip_batch_learn_tables_device(cpprob_hip_ctx* ctx, double* d_means, double* d_transition);
+/* The records [n_problems][88] of the last learning advance (n_doubles >= 88 n_problems; none yet: zeros).  Synchronises. */
+int cpprob_hip_batch_learn_record(cpprob_hip_ctx* ctx, double* h_stats, size_t n_doubles);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
