@@ -54,6 +54,10 @@ SYMBOLS = [
     "cpprob_hip_batch_mstep_device", "cpprob_hip_batch_copy_step_tables", "cpprob_hip_batch_summaries_device",
     "cpprob_hip_batch_learn_begin", "cpprob_hip_batch_advance_learn", "cpprob_hip_batch_advance_learn_device", "cpprob_hip_batch_online_tables",
     "cpprob_hip_batch_learn_tables", "cpprob_hip_batch_learn_tables_device", "cpprob_hip_batch_learn_record",
+    "cpprob_hip_table_log", "cpprob_hip_batch_begin_problems_scaled", "cpprob_hip_batch_begin_online_scaled",
+    "cpprob_hip_batch_retable_scaled", "cpprob_hip_batch_retable_scaled_device", "cpprob_hip_batch_mstep_scaled_device",
+    "cpprob_hip_batch_online_tables_scaled", "cpprob_hip_batch_copy_scales",
+    "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
 ]
 
 
@@ -395,6 +399,17 @@ def load_library(path=None):
         "cpprob_hip_batch_learn_tables": (C.c_int, [vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_device": (C.c_int, [vp, vp, vp]),
         "cpprob_hip_batch_learn_record": (C.c_int, [vp, vp, sz]),
+        "cpprob_hip_table_log": (dbl, [dbl]),
+        "cpprob_hip_batch_begin_problems_scaled": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, vp, vp, vp]),
+        "cpprob_hip_batch_begin_online_scaled": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, vp, vp, vp, C.POINTER(u64)]),
+        "cpprob_hip_batch_retable_scaled": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_scaled_device": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_mstep_scaled_device": (C.c_int, [vp, vp, sz, vp, vp, vp, vp, dbl]),
+        "cpprob_hip_batch_online_tables_scaled": (C.c_int, [vp, vp, vp, vp]),
+        "cpprob_hip_batch_copy_scales": (C.c_int, [vp, u64, vp, vp]),
+        "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
+        "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
+        "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -593,51 +608,73 @@ class Engine:
                              max_particles=None, keep_masses=False):
         """A batch whose problems differ.  observes: a list of 1-D arrays, problem b's own sequence (any lengths); n_particles: an int
         or one count a problem; tables (MODEL_HMM_TABLE): None (the set_hmm table for every problem) or (means [B, k], transition
-        [B, k, k]), problem b's own table.  batch_results() then returns arrays padded to the longest problem (rows t >= T_b zero) and
-        batch_store(b) problem b's own [T_b, n_b]."""
+        [B, k, k]), problem b's own table, or (means, transition, sigmas [B, k]): state s of problem b emits N(means[b, s],
+        sigmas[b, s]) (cpprob_hip_batch_begin_problems_scaled).  batch_results() then returns arrays padded to the longest problem
+        (rows t >= T_b zero) and batch_store(b) problem b's own [T_b, n_b]."""
         seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in observes]
         h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
         flat = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0))
         top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
         cfg = self.batch_config(model, top, len(seqs), resampler, ess_threshold, keep_history, algorithm, _batch_flags(flags, keep_masses))
-        k, means, trans = 0, None, None
+        k, means, trans, sigmas = 0, None, None, None
         if tables is not None:
             means = np.ascontiguousarray(tables[0], np.float64)
             trans = np.ascontiguousarray(tables[1], np.float64)
             if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != len(seqs):
                 raise ValueError("tables = (means [B, k], transition [B, k, k])")
             k = means.shape[1]
-        self._chk(self.L.cpprob_hip_batch_begin_problems(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                         flat.ctypes.data_as(C.POINTER(C.c_double)), k, None if means is None else means.ctypes.data,
-                                                         None if trans is None else trans.ctypes.data))
+            sigmas = self._batch_sigmas(tables, means)
+        if sigmas is not None:
+            self._chk(self.L.cpprob_hip_batch_begin_problems_scaled(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                    flat.ctypes.data_as(C.POINTER(C.c_double)), k, means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data))
+            self.batch_k = k                                 # (batch_scales reads it)
+        else:
+            self._chk(self.L.cpprob_hip_batch_begin_problems(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                             flat.ctypes.data_as(C.POINTER(C.c_double)), k, None if means is None else means.ctypes.data,
+                                                             None if trans is None else trans.ctypes.data))
         self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
         self.batch_K = 3 if model == MODEL_HMM3 else 8
         self.batch_shapes = (h_T, h_n)
         return self
+
+    @staticmethod
+    def _batch_sigmas(tables, means):
+        """The third array of a tables tuple, [B, k] as the means, or None for a 2-tuple."""
+        if len(tables) < 3 or tables[2] is None:
+            return None
+        sigmas = np.ascontiguousarray(tables[2], np.float64)
+        if sigmas.shape != means.shape:
+            raise ValueError("tables = (means [B, k], transition [B, k, k], sigmas [B, k])")
+        return sigmas
 
     def batch_begin_online(self, model, capacity, n_particles, seeds, tables=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC,
                            flags=0, max_particles=None, keep_masses=False):
         """A batch whose observes arrive over time.  capacity: the most observes problem b may reach, one a problem; n_particles and
         tables as for batch_begin_problems; seeds: one Philox key a problem, for the life of the batch.  Every problem starts at
         length 0; batch_advance() feeds it.  batch_results() returns arrays padded to the largest capacity and batch_store(b) the
-        [L_b, n_b] rows reached."""
+        [L_b, n_b] rows reached.  A 3-tuple of tables carries the emission scales (cpprob_hip_batch_begin_online_scaled)."""
         h_T, h_n = _problem_shapes(capacity, n_particles)
         sd = np.ascontiguousarray(seeds, np.uint64)
         if sd.shape != h_T.shape:
             raise ValueError("one seed per problem")
         top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
         cfg = self.batch_config(model, top, h_T.size, resampler, ess_threshold, keep_history, algorithm, _batch_flags(flags, keep_masses))
-        k, means, trans = 0, None, None
+        k, means, trans, sigmas = 0, None, None, None
         if tables is not None:
             means = np.ascontiguousarray(tables[0], np.float64)
             trans = np.ascontiguousarray(tables[1], np.float64)
             if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != h_T.size:
                 raise ValueError("tables = (means [B, k], transition [B, k, k])")
             k = means.shape[1]
+            sigmas = self._batch_sigmas(tables, means)
         self.batch_k = k
-        self._chk(self.L.cpprob_hip_batch_begin_online(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), k,
-                                                       None if means is None else means.ctypes.data, None if trans is None else trans.ctypes.data,
-                                                       sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        if sigmas is not None:
+            self._chk(self.L.cpprob_hip_batch_begin_online_scaled(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), k,
+                                                                  means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        else:
+            self._chk(self.L.cpprob_hip_batch_begin_online(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), k,
+                                                           None if means is None else means.ctypes.data, None if trans is None else trans.ctypes.data,
+                                                           sd.ctypes.data_as(C.POINTER(C.c_uint64))))
         self.batch_B, self.batch_T, self.batch_n = int(h_T.size), int(h_T.max()), top
         self.batch_K = 3 if model == MODEL_HMM3 else 8
         self.batch_shapes = (np.zeros(h_T.size, np.uint32), h_n)
@@ -711,24 +748,35 @@ class Engine:
         [B, k], transition [B, k, k]) on the host, validated as batch_begin_problems validates them.  observes: the problems'
         sequences as batch_begin_problems took them, or None once a previous batch_retable of this begun batch has staged them.
         Everything the batch returns afterwards is what a fresh batch_begin_problems with these tables returns, bit for bit; like a
-        begin, the read-outs wait for the next batch_run / batch_run_conditional."""
+        begin, the read-outs wait for the next batch_run / batch_run_conditional.  A 3-tuple (means, transition, sigmas [B, k])
+        re-tables a batch begun with emission scales (cpprob_hip_batch_retable_scaled)."""
         means = np.ascontiguousarray(tables[0], np.float64)
         trans = np.ascontiguousarray(tables[1], np.float64)
         if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != self.batch_B:
             raise ValueError("tables = (means [B, k], transition [B, k, k])")
         h_T, _ = self._batch_problem_shapes()
         flat = None if observes is None else self._batch_packed_observes(observes)
-        self._chk(self.L.cpprob_hip_batch_retable(self.h, means.ctypes.data, trans.ctypes.data, None if flat is None or flat.size == 0 else flat.ctypes.data,
-                                                  int(np.sum(h_T, dtype=np.int64)) if flat is None else flat.size))
+        sigmas = self._batch_sigmas(tables, means)
+        h_obs, n_obs = None if flat is None or flat.size == 0 else flat.ctypes.data, int(np.sum(h_T, dtype=np.int64)) if flat is None else flat.size
+        if sigmas is not None:
+            self._chk(self.L.cpprob_hip_batch_retable_scaled(self.h, means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data, h_obs, n_obs))
+        else:
+            self._chk(self.L.cpprob_hip_batch_retable(self.h, means.ctypes.data, trans.ctypes.data, h_obs, n_obs))
 
-    def batch_retable_device(self, means, trans, observes):
+    def batch_retable_device(self, means, trans, observes, sigmas=None):
         """The same between torch float64 device tensors (means [B, k], trans [B, k, k], observes packed problem after problem),
-        enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status)."""
-        self._chk(self.L.cpprob_hip_batch_retable_device(self.h, _dptr(means), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+        enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status).  sigmas [B, k]: the
+        emission scales of a batch begun with them (cpprob_hip_batch_retable_scaled_device)."""
+        n_obs = 0 if observes is None else observes.numel()
+        if sigmas is not None:
+            self._chk(self.L.cpprob_hip_batch_retable_scaled_device(self.h, _dptr(means), _dptr(trans), _dptr(sigmas), _dptr(observes), n_obs))
+        else:
+            self._chk(self.L.cpprob_hip_batch_retable_device(self.h, _dptr(means), _dptr(trans), _dptr(observes), n_obs))
 
     def batch_retable_status(self):
         """int32 [B] of the last re-table: 0, or bits 1 (a weight not finite or < 0), 2 (a transition row without mass), 4 (a mean
-        not finite) -- such a problem kept its previous table.  Synchronises."""
+        not finite), 8 (a scaled re-table: a sigma not finite, not > 0, or with a 2 pi sigma^2 that is not a normal number) -- such a
+        problem kept its previous table.  Synchronises."""
         out = np.zeros(self.batch_B, np.int32)
         self._chk(self.L.cpprob_hip_batch_retable_status(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
@@ -739,10 +787,24 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_retable_grid(self.h, C.byref(g)))
         return int(g.value)
 
-    def batch_mstep_device(self, stats, means, trans):
+    def batch_mstep_device(self, stats, means, trans, sigmas=None, sigma_floor=1e-3, log_norms=None):
         """em.m_step on the device (cpprob_hip_batch_mstep_device): stats torch float64 [B, 88] as batch_smooth_stats_device leaves
-        them; means [B, k] and trans [B, k, k] torch float64, updated in place.  Enqueued without a host synchronisation."""
-        self._chk(self.L.cpprob_hip_batch_mstep_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans)))
+        them; means [B, k] and trans [B, k, k] torch float64, updated in place.  Enqueued without a host synchronisation.
+        sigmas [B, k]: the emission scales, updated in place too, none below sigma_floor (cpprob_hip_batch_mstep_scaled_device);
+        log_norms [B, k], if given, takes the new sigmas' log(2 pi sigma^2): for tests, a fitting loop has no use for it."""
+        if sigmas is not None:
+            self._chk(self.L.cpprob_hip_batch_mstep_scaled_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans), _dptr(sigmas), _dptr(log_norms),
+                                                                  float(sigma_floor)))
+        else:
+            self._chk(self.L.cpprob_hip_batch_mstep_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans)))
+
+    def batch_scales(self, b, k=None):
+        """(sigmas [k], log_norms [k]) of problem b of a batch begun with emission scales, as the device holds them
+        (cpprob_hip_batch_copy_scales).  Synchronises.  For tests."""
+        k = int(k if k is not None else self.batch_k)
+        sg, ln = np.zeros(k), np.zeros(k)
+        self._chk(self.L.cpprob_hip_batch_copy_scales(self.h, int(b), sg.ctypes.data, ln.ctypes.data))
+        return sg, ln
 
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):
@@ -753,12 +815,17 @@ class Engine:
         self.batch_k = means.shape[1]
         return means, trans
 
-    def batch_learn_begin(self, gamma, t_min):
+    def batch_learn_begin(self, gamma, t_min, sigma_floor=None):
         """Arms the online MODEL_HMM_TABLE batch just begun (per-problem tables; before its first advance) for online EM
         (cpprob_hip_batch_learn_begin): gamma[t] in (0, 1], the step size of a problem's absolute step t, at least as long as the
-        largest capacity; t_min: the length a problem must have reached before its first M-step."""
+        largest capacity; t_min: the length a problem must have reached before its first M-step.  sigma_floor (a batch begun with
+        emission scales): the learner fits the sigmas too, none below it (cpprob_hip_batch_learn_begin_scaled); None on such a batch:
+        means and transition rows are learned and the sigmas stay."""
         g = np.ascontiguousarray(gamma, np.float64).reshape(-1)
-        self._chk(self.L.cpprob_hip_batch_learn_begin(self.h, g.ctypes.data if g.size else None, g.size, int(t_min)))
+        if sigma_floor is not None:
+            self._chk(self.L.cpprob_hip_batch_learn_begin_scaled(self.h, g.ctypes.data if g.size else None, g.size, int(t_min), float(sigma_floor)))
+        else:
+            self._chk(self.L.cpprob_hip_batch_learn_begin(self.h, g.ctypes.data if g.size else None, g.size, int(t_min)))
 
     def _batch_new_observes(self, new_observes):
         seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in new_observes]
@@ -787,20 +854,33 @@ class Engine:
         """New tables (means [B, k], transition [B, k, k]) for the FUTURE steps of an online MODEL_HMM_TABLE batch, armed or not
         (cpprob_hip_batch_online_tables): validated as the begin validates them; past rows stay."""
         means, trans = self._batch_tables(tables)
-        self._chk(self.L.cpprob_hip_batch_online_tables(self.h, means.ctypes.data, trans.ctypes.data))
+        sigmas = self._batch_sigmas(tables, means)
+        if sigmas is not None:                               # (a batch begun with emission scales: cpprob_hip_batch_online_tables_scaled)
+            self._chk(self.L.cpprob_hip_batch_online_tables_scaled(self.h, means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data))
+        else:
+            self._chk(self.L.cpprob_hip_batch_online_tables(self.h, means.ctypes.data, trans.ctypes.data))
 
-    def batch_learn_tables(self, k=None):
+    def batch_learn_tables(self, k=None, scales=False):
         """(means [B, k], transition [B, k, k], status int32 [B]) of an armed batch as the device holds them: status 0, or the bits
         of batch_retable_status of the last M-step that was dropped.  k: the batch's states (default: those of the last
-        batch_begin_online of this engine).  Synchronises."""
+        batch_begin_online of this engine).  Synchronises.  scales=True (a batch with emission scales): (means, transition, sigmas
+        [B, k], status) (cpprob_hip_batch_learn_tables_scaled)."""
         k = int(k if k is not None else self.batch_k)
         means, trans, status = np.zeros((self.batch_B, k)), np.zeros((self.batch_B, k, k)), np.zeros(self.batch_B, np.int32)
+        if scales:
+            sigmas = np.zeros((self.batch_B, k))
+            self._chk(self.L.cpprob_hip_batch_learn_tables_scaled(self.h, means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
+            return means, trans, sigmas, status
         self._chk(self.L.cpprob_hip_batch_learn_tables(self.h, means.ctypes.data, trans.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_int32))))
         return means, trans, status
 
-    def batch_learn_tables_device(self, means, trans):
-        """The same tables into torch float64 device tensors (means [B, k], trans [B, k, k]): a stream-ordered copy."""
-        self._chk(self.L.cpprob_hip_batch_learn_tables_device(self.h, _dptr(means), _dptr(trans)))
+    def batch_learn_tables_device(self, means, trans, sigmas=None):
+        """The same tables into torch float64 device tensors (means [B, k], trans [B, k, k]; sigmas [B, k] of a batch with emission
+        scales): a stream-ordered copy."""
+        if sigmas is not None:
+            self._chk(self.L.cpprob_hip_batch_learn_tables_scaled_device(self.h, _dptr(means), _dptr(trans), _dptr(sigmas)))
+        else:
+            self._chk(self.L.cpprob_hip_batch_learn_tables_device(self.h, _dptr(means), _dptr(trans)))
 
     def batch_learn_record(self):
         """float64 [B, 88]: the records of the last learning advance (cpprob_hip_batch_learn_record).  Synchronises."""

@@ -30,6 +30,8 @@
 #include "batch_csmc.hpp"
 #include "batch_retable.hpp"
 #include "batch_learn.hpp"
+#include "batch_scale.hpp"
+#include "batch_learn_scaled.hpp"
 #include "batch_pass_plan.hpp"
 
 using namespace cph;
@@ -991,6 +993,11 @@ void hmmk_step_ll(double y, const std::vector<double>& mean, int k, double* ll)
 {
     for (int s2 = 0; s2 < 8; ++s2) ll[s2] = s2 < k ? normal_logpdf(y, mean[(size_t)s2], 1.0) : -INFINITY;
 }
+// a scaled table's row (csrc/batch_scale.hpp): the statements the device's re-table writes it with, not normal_logpdf's logarithm
+void scale_step_ll(double y, const double* mean, const double* sigma, const double* log_norm, int k, double* ll)
+{
+    for (int s2 = 0; s2 < 8; ++s2) ll[s2] = s2 < k ? scale_entry(y, mean[s2], sigma[s2], log_norm[s2]) : -INFINITY;
+}
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
 {
     std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
@@ -1133,6 +1140,15 @@ struct BatchState {
     int32_t* d_lstatus = nullptr;
     int64_t *d_lfirst = nullptr, *pin_lfirst = nullptr;
     size_t lobs_cap = 0;
+    // per-state emission scales (cpprob_hip_batch_begin_problems_scaled, _begin_online_scaled; csrc/batch_scale.hpp): scaled: the begun
+    // batch has them; the sigmas and log_norms in force, [B][8] (states >= k zero), on the host as the last begin or host call
+    // (cpprob_hip_batch_retable_scaled, _online_tables_scaled) left them and on the device (allocations of the context's own) as the
+    // last re-table or learn step left them; learn_scales / learn_floor: the armed batch's learner fits the scales
+    // (cpprob_hip_batch_learn_begin_scaled) -- the host mirrors are stale from its first advance on, and nothing reads them then
+    bool scaled = false, learn_scales = false;
+    double learn_floor = 0.0;
+    std::vector<double> sigmas, log_norms;
+    double *d_sigma = nullptr, *d_lognorm = nullptr; size_t scale_cap = 0;
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -1160,6 +1176,7 @@ void batch_free(cpprob_hip_ctx* c)
     if (c->batch->pin_sdesc) (void)hipHostFree(c->batch->pin_sdesc);
     dfree(c->batch->d_cfirst);
     dfree(c->batch->d_rstatus); dfree(c->batch->d_robs);
+    dfree(c->batch->d_sigma); dfree(c->batch->d_lognorm);
     if (c->batch->pin_cfirst) (void)hipHostFree(c->batch->pin_cfirst);
     for (hipEvent_t e : c->batch->sdesc_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
@@ -1219,9 +1236,9 @@ int batch_check_problems(const cpprob_hip_batch_config* cfg, const uint32_t* h_T
 // Online (h_T = the capacities, h_obs NULL, h_seeds given): every problem starts without observes; cpprob_hip_batch_advance evaluates
 // its rows, with the statements below, as they arrive.
 int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_max, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
-                int k, const double* h_means, const double* h_transition, const uint64_t* h_seeds = nullptr)
+                int k, const double* h_means, const double* h_transition, const uint64_t* h_seeds = nullptr, const double* h_sigmas = nullptr)
 {
-    const bool online = h_seeds != nullptr;
+    const bool online = h_seeds != nullptr, scaled = h_sigmas != nullptr;
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->batch) c->batch = new BatchState();
     BatchState* bs = c->batch;
@@ -1265,6 +1282,22 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     } else bs->h_tab.assign((size_t)B * T_max * kBatchTab, 0.0);
     bs->h_thr.assign((size_t)tables * 64, ~0ull);
     bs->prob.resize(B);
+    bs->scaled = false; bs->sigmas.clear(); bs->log_norms.clear();
+    if (scaled) {
+        // the scales in force and their logarithms, with the statements the device's re-table evaluates (csrc/batch_scale.hpp)
+        bs->sigmas.assign((size_t)B * 8, 0.0); bs->log_norms.assign((size_t)B * 8, 0.0);
+        for (uint64_t b = 0; b < B; ++b)
+            for (int s2 = 0; s2 < k; ++s2) {
+                bs->sigmas[b * 8 + (size_t)s2] = h_sigmas[b * (size_t)k + (size_t)s2];
+                bs->log_norms[b * 8 + (size_t)s2] = scale_log_norm(h_sigmas[b * (size_t)k + (size_t)s2]);
+            }
+        if (B > bs->scale_cap) {
+            dfree(bs->d_sigma); dfree(bs->d_lognorm); bs->scale_cap = 0;      // (hipFree waits for the device: no kernel still writes them)
+            HIP_TRY(c, hipMalloc(&bs->d_sigma, B * 8 * sizeof(double)));
+            HIP_TRY(c, hipMalloc(&bs->d_lognorm, B * 8 * sizeof(double)));
+            bs->scale_cap = B;
+        }
+    }
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
@@ -1279,6 +1312,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
+            else if (scaled) scale_step_ll(y, mean.data(), &bs->sigmas[b * 8], &bs->log_norms[b * 8], k, row);
             else hmmk_step_ll(y, mean, k, row);
         }
         if (!hmm3 && b < tables) {
@@ -1301,6 +1335,10 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     if (online) HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.tab, 0, (size_t)B * T_max * kBatchTab * sizeof(double), c->stream));
     else HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    if (scaled) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_sigma, bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm, bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
     if (online) {
@@ -1330,7 +1368,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
-    bs->online = online; bs->walked = true; bs->own_tables = own;
+    bs->online = online; bs->walked = true; bs->own_tables = own; bs->scaled = scaled;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -4110,6 +4148,32 @@ int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_co
     return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition);
 }
 
+// The scales of a batch of problems (cpprob_hip_batch_begin_problems_scaled, _begin_online_scaled, _retable_scaled, _online_tables_scaled):
+// per problem and state what scale_check's bit 8 demands (csrc/batch_scale.hpp).
+static int batch_check_scales(cpprob_hip_ctx* c, uint64_t B, int k, const double* h_sigmas)
+{
+    for (uint64_t b = 0; b < B; ++b)
+        for (int s2 = 0; s2 < k; ++s2)
+            if (scale_bad(h_sigmas[b * (size_t)k + (size_t)s2]))
+                return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": emission scales must be finite and > 0, with a normal finite 2 pi sigma^2");
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems_scaled(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                           const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition, const double* h_sigmas)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "emission scales serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    int k = 0;
+    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
+    if (int rc = batch_check_scales(c, cfg->n_problems, k, h_sigmas)) return rc;
+    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition, nullptr, h_sigmas);
+}
+
 // The tables of a batch of problems (cpprob_hip_batch_begin_problems, _begin_online): per problem, or the context's; k = the states.
 static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, int32_t k_in, const double* h_means, const double* h_transition, int& k)
 {
@@ -4311,6 +4375,21 @@ int cpprob_hip_batch_begin_online(cpprob_hip_ctx* c, const cpprob_hip_batch_conf
     return batch_begin(c, cfg, (size_t)sh.T_max, h_Tcap, h_n, nullptr, k, h_means, h_transition, h_seeds);
 }
 
+int cpprob_hip_batch_begin_online_scaled(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
+                                         int32_t k_in, const double* h_means, const double* h_transition, const double* h_sigmas, const uint64_t* h_seeds)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_Tcap || !h_n || !h_seeds || !h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "emission scales serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_Tcap, h_n, sh, msg)) return fail(c, rc, msg);
+    int k = 0;
+    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
+    if (int rc = batch_check_scales(c, cfg->n_problems, k, h_sigmas)) return rc;
+    return batch_begin(c, cfg, (size_t)sh.T_max, h_Tcap, h_n, nullptr, k, h_means, h_transition, h_seeds, h_sigmas);
+}
+
 static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs);
 
 // One advance of the begun online batch.  Plain (cpprob_hip_batch_advance): the new rows are evaluated on the host from bs->means and
@@ -4370,6 +4449,7 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
             const double y = h_obs[at_obs++];
             double* row = bs->pin_tab + (b * T_max + t) * kBatchTab;
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
+            else if (bs->scaled) scale_step_ll(y, mean.data(), &bs->sigmas[b * 8], &bs->log_norms[b * 8], (int)hk, row);
             else hmmk_step_ll(y, mean, (int)hk, row);
         }
         // (a problem without observes, or without new ones and with its read-out done, has nothing to do)
@@ -4405,14 +4485,24 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
         if (h_obs) { HIP_TRY(c, hipMemcpyAsync(bs->d_lobs, h_obs, (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream)); d_obs = bs->d_lobs; }
         uint32_t top = 0;
         for (uint64_t b = 0; b < B; ++b) top = std::max(top, h_dT[b]);
-        BatchLearnRowsArgs ra{};
-        ra.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-        ra.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
-        ra.ofirst = bs->d_lfirst; ra.means = bs->d_lmeans; ra.obs = d_obs;
-        ra.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
-        ra.log_norm = std::log(2 * kPi * 1.0 * 1.0);              // (normal_logpdf's own expression at sigma = 1.0)
-        ra.T_max = bs->T; ra.k = bs->hk;
-        hipLaunchKernelGGL(batch_learn_rows_kernel, dim3((unsigned)B, retable_grid_y(top, (int64_t)B)), dim3(kThreads), 0, c->stream, ra);
+        if (bs->scaled) {
+            BatchLearnRowsScaledArgs rs{};
+            rs.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+            rs.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
+            rs.ofirst = bs->d_lfirst; rs.means = bs->d_lmeans; rs.sigmas = bs->d_sigma; rs.log_norms = bs->d_lognorm; rs.obs = d_obs;
+            rs.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+            rs.T_max = bs->T; rs.k = bs->hk;
+            hipLaunchKernelGGL(batch_learn_rows_scaled_kernel, dim3((unsigned)B, retable_grid_y(top, (int64_t)B)), dim3(kThreads), 0, c->stream, rs);
+        } else {
+            BatchLearnRowsArgs ra{};
+            ra.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+            ra.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
+            ra.ofirst = bs->d_lfirst; ra.means = bs->d_lmeans; ra.obs = d_obs;
+            ra.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+            ra.log_norm = std::log(2 * kPi * 1.0 * 1.0);              // (normal_logpdf's own expression at sigma = 1.0)
+            ra.T_max = bs->T; ra.k = bs->hk;
+            hipLaunchKernelGGL(batch_learn_rows_kernel, dim3((unsigned)B, retable_grid_y(top, (int64_t)B)), dim3(kThreads), 0, c->stream, ra);
+        }
         HIP_TRY(c, hipGetLastError());
         bs->tab_stale = true;
     }
@@ -5418,7 +5508,7 @@ int cpprob_hip_batch_pass_grid(cpprob_hip_ctx* c, uint32_t* decode_forward_grid_
 // ---- re-tabling a begun batch (csrc/batch_retable.hpp) -----------------------------------------------------------------------------
 static_assert(kRetableStats == kSuffStats, "the M-step reads the record of cpprob_hip_batch_smooth_stats");
 // What a re-table needs of the batch's state, then n_observes against the lengths; nothing is enqueued before it has passed.
-static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes)
+static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, bool scaled = false)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
@@ -5426,6 +5516,8 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes)
     if (bs->online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "an online batch is not re-tabled: its advances evaluate their rows from the host's means");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "re-tabling serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
+    if (bs->scaled && !scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: it is re-tabled by cpprob_hip_batch_retable_scaled / _retable_scaled_device");
+    if (!bs->scaled && scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_problems_scaled, or re-table it with cpprob_hip_batch_retable / _retable_device");
     uint64_t rows = 0;
     for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
     if ((uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
@@ -5434,7 +5526,7 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes)
 
 // Enqueues the first entries (once a begin) and the launch; the batch then stands as after a begin.  Waits for nothing but, where the
 // status words have to grow, for the calls before it.
-static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs)
+static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs, const double* d_sigmas = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
@@ -5445,17 +5537,31 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
         bs->rstatus_cap = B;
     }
     if (int rc = batch_first_entries(c)) return rc;
-    BatchRetableArgs a{};
-    a.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-    a.first = bs->d_cfirst;
-    a.means = d_means; a.trans = d_trans; a.obs = d_obs;
-    a.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
-    a.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
-    a.status = bs->d_rstatus;
-    a.log_norm = std::log(2 * kPi * 1.0 * 1.0);               // (normal_logpdf's own expression at sigma = 1.0)
-    a.T_max = bs->T; a.k = bs->hk;
     const unsigned gy = retable_grid_y(bs->T, (int64_t)B);
-    hipLaunchKernelGGL(batch_retable_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
+    if (d_sigmas) {
+        // (a scaled batch; the sigmas and log_norms in force are the device's from here on)
+        BatchRetableScaledArgs sa{};
+        sa.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+        sa.first = bs->d_cfirst;
+        sa.means = d_means; sa.sigmas = d_sigmas; sa.trans = d_trans; sa.obs = d_obs;
+        sa.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+        sa.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
+        sa.status = bs->d_rstatus;
+        sa.sigma_out = bs->d_sigma; sa.log_norm_out = bs->d_lognorm;
+        sa.T_max = bs->T; sa.k = bs->hk;
+        hipLaunchKernelGGL(batch_retable_scaled_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, sa);
+    } else {
+        BatchRetableArgs a{};
+        a.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+        a.first = bs->d_cfirst;
+        a.means = d_means; a.trans = d_trans; a.obs = d_obs;
+        a.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+        a.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
+        a.status = bs->d_rstatus;
+        a.log_norm = std::log(2 * kPi * 1.0 * 1.0);               // (normal_logpdf's own expression at sigma = 1.0)
+        a.T_max = bs->T; a.k = bs->hk;
+        hipLaunchKernelGGL(batch_retable_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
+    }
     HIP_TRY(c, hipGetLastError());
     bs->retable_gy = gy; bs->retabled = true;
     // a begin as far as results go: the read-outs wait for the next run; the decode's log tables come from the thresholds
@@ -5544,6 +5650,124 @@ int cpprob_hip_batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size
     return 0;
 }
 
+// ---- per-state emission scales (csrc/batch_scale.hpp) -----------------------------------------------------------------------------
+static int batch_learn_check(cpprob_hip_ctx* c, const char* who);
+
+double cpprob_hip_table_log(double x) { return table_log(x); }
+
+int cpprob_hip_batch_retable_scaled_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_sigmas, const double* d_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, true)) return rc;
+    if (!d_means || !d_transition || !d_sigmas || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_means, d_transition, d_observes, d_sigmas);
+}
+
+int cpprob_hip_batch_retable_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, true)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    int k = 0;
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
+    if (h_observes) {
+        if (n_observes > bs->robs_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (an earlier re-table may still read the buffer this replaces)
+            dfree(bs->d_robs); bs->robs_cap = 0; bs->robs_ready = false;
+            HIP_TRY(c, hipMalloc(&bs->d_robs, n_observes * sizeof(double)));
+            bs->robs_cap = n_observes;
+        }
+        HIP_TRY(c, hipMemcpyAsync(bs->d_robs, h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        bs->robs_ready = true;
+    }
+    // the means with the sigmas behind them in front, the transition rows at the back
+    double *d_means = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(2 * B * (size_t)k * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
+    double* d_sigmas = d_means + B * (size_t)k;
+    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs, d_sigmas)) return rc;
+    for (size_t b = 0; b < B; ++b) {
+        retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+        for (size_t s2 = 0; s2 < (size_t)k; ++s2) { bs->sigmas[b * 8 + s2] = h_sigmas[b * (size_t)k + s2]; bs->log_norms[b * 8 + s2] = scale_log_norm(h_sigmas[b * (size_t)k + s2]); }
+    }
+    bs->thr_stale = false;
+    return 0;
+}
+
+int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition, double* d_sigmas,
+                                         double* d_log_norm, double sigma_floor)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!d_stats || !d_means || !d_transition || !d_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor)) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kRetableStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepScaledArgs a{};
+    a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.sigmas = d_sigmas; a.log_norms = d_log_norm; a.floor = sigma_floor; a.B = (int64_t)B; a.k = bs->hk;
+    hipLaunchKernelGGL(batch_mstep_scaled_kernel, dim3((unsigned)((B * (uint64_t)bs->hk + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* c, uint64_t problem, double* h_sigmas, double* h_log_norm)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales (cpprob_hip_batch_begin_problems_scaled, _begin_online_scaled)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t k = (size_t)bs->hk;
+    if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_sigma + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_log_norm) HIP_TRY(c, hipMemcpyAsync(h_log_norm, bs->d_lognorm + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int cpprob_hip_batch_online_tables_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_check(c, "cpprob_hip_batch_online_tables_scaled")) return rc;
+    BatchState* bs = c->batch;
+    if (!bs->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_online_scaled, or call cpprob_hip_batch_online_tables");
+    if (!h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    int k = 0;
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
+    bs->means.assign(h_means, h_means + B * (size_t)k);
+    bs->trans.assign(h_transition, h_transition + B * kk);
+    for (size_t b = 0; b < B; ++b) {
+        retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+        for (size_t s2 = 0; s2 < (size_t)k; ++s2) { bs->sigmas[b * 8 + s2] = h_sigmas[b * (size_t)k + s2]; bs->log_norms[b * 8 + s2] = scale_log_norm(h_sigmas[b * (size_t)k + s2]); }
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_sigma, bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm, bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (bs->armed) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lmeans, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_ltrans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    bs->thr_stale = false; bs->lp_ready = false; bs->lp_sent = false;
+    bs->decoded.assign(B, 0);
+    return 0;
+}
+
 // ---- online EM of an online batch (csrc/batch_learn.hpp) ----------------------------------------------------------------------------
 // What the host route and the arming share: an online CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables.
 static int batch_learn_check(cpprob_hip_ctx* c, const char* who)
@@ -5586,7 +5810,21 @@ int cpprob_hip_batch_learn_begin(cpprob_hip_ctx* c, const double* h_gamma, size_
     HIP_TRY(c, hipMemsetAsync(bs->d_lrec, 0, B * (size_t)kOnlineStats * sizeof(double), c->stream));
     HIP_TRY(c, hipMemsetAsync(bs->d_lstatus, 0, B * sizeof(int32_t), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));               // (h_gamma may be reused when the call returns)
-    bs->learn_t_min = t_min; bs->armed = true;
+    bs->learn_t_min = t_min; bs->armed = true; bs->learn_scales = false; bs->learn_floor = 0.0;
+    return 0;
+}
+
+// The same arming for a batch with emission scales, whose learner then fits them: its own two checks, then cpprob_hip_batch_learn_begin's
+// checks, allocations and uploads; the two words that tell the learn step to fit the scales are set once that has succeeded.  (A
+// context serves one thread at a time -- include/cpprob_hip.h --, and LANES_OWN waits for the run lanes, it holds nothing.)
+int cpprob_hip_batch_learn_begin_scaled(cpprob_hip_ctx* c, const double* h_gamma, size_t n_gamma, uint32_t t_min, double sigma_floor)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_check(c, "cpprob_hip_batch_learn_begin_scaled")) return rc;
+    if (!c->batch->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_online_scaled, or arm it with cpprob_hip_batch_learn_begin");
+    if (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor)) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
+    if (int rc = cpprob_hip_batch_learn_begin(c, h_gamma, n_gamma, t_min)) return rc;
+    c->batch->learn_scales = true; c->batch->learn_floor = sigma_floor;
     return 0;
 }
 
@@ -5603,7 +5841,12 @@ static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const 
     la.desc = a.desc; la.mass = a.mass; la.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr); la.obs = d_obs; la.gamma = bs->d_gamma;
     la.tau = bs->d_ltau; la.stats = bs->d_lrec; la.means = bs->d_lmeans; la.trans = bs->d_ltrans; la.status = bs->d_lstatus;
     la.B = (int)B; la.k = bs->hk; la.t_min = (int)std::min<uint32_t>(bs->learn_t_min, (uint32_t)INT32_MAX);
-    hipLaunchKernelGGL(batch_learn_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, la);
+    if (bs->scaled) {
+        BatchLearnScaledArgs ls{};
+        ls.base = la; ls.sigmas = bs->d_sigma; ls.log_norms = bs->d_lognorm; ls.floor = bs->learn_floor; ls.fit = bs->learn_scales ? 1 : 0;
+        hipLaunchKernelGGL(batch_learn_scaled_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, ls);
+    } else
+        hipLaunchKernelGGL(batch_learn_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, la);
     HIP_TRY(c, hipGetLastError());
     bs->thr_stale = true; bs->lp_ready = false; bs->lp_sent = false;
     bs->decoded.assign(B, 0);
@@ -5615,6 +5858,7 @@ int cpprob_hip_batch_online_tables(cpprob_hip_ctx* c, const double* h_means, con
     LANES_OWN(c);
     if (int rc = batch_learn_check(c, "cpprob_hip_batch_online_tables")) return rc;
     BatchState* bs = c->batch;
+    if (bs->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its tables are replaced by cpprob_hip_batch_online_tables_scaled");
     if (!h_means || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     int k = 0;
     if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
@@ -5634,14 +5878,13 @@ int cpprob_hip_batch_online_tables(cpprob_hip_ctx* c, const double* h_means, con
     return 0;
 }
 
-int cpprob_hip_batch_learn_tables(cpprob_hip_ctx* c, double* h_means, double* h_transition, int32_t* h_status)
+// The armed batch's tables, status words and -- h_sigmas given: a scaled batch -- scales to the host; waits for the stream.
+static int batch_learn_tables_fetch(cpprob_hip_ctx* c, double* h_means, double* h_transition, double* h_sigmas, int32_t* h_status)
 {
-    LANES_OWN(c);
-    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
-    if (!bs || !bs->begun || !bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the begun batch is not armed (cpprob_hip_batch_learn_begin)");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
+    if (h_sigmas) HIP_TRY(c, hipMemcpy2DAsync(h_sigmas, k * sizeof(double), bs->d_sigma, 8 * sizeof(double), k * sizeof(double), B, hipMemcpyDeviceToHost, c->stream));
     if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_lmeans, B * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_transition) HIP_TRY(c, hipMemcpyAsync(h_transition, bs->d_ltrans, B * k * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_status) HIP_TRY(c, hipMemcpyAsync(h_status, bs->d_lstatus, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -5649,18 +5892,56 @@ int cpprob_hip_batch_learn_tables(cpprob_hip_ctx* c, double* h_means, double* h_
     return 0;
 }
 
-int cpprob_hip_batch_learn_tables_device(cpprob_hip_ctx* c, double* d_means, double* d_transition)
+// What the four read-outs of the learner's tables share; scaled: the call is one of the two that read the scales.
+static int batch_learn_tables_check(cpprob_hip_ctx* c, bool scaled)
 {
-    LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
     if (!bs || !bs->begun || !bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the begun batch is not armed (cpprob_hip_batch_learn_begin)");
-    if (!d_means || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (scaled && !bs->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: call cpprob_hip_batch_learn_tables / _learn_tables_device");
+    return 0;
+}
+
+int cpprob_hip_batch_learn_tables(cpprob_hip_ctx* c, double* h_means, double* h_transition, int32_t* h_status)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_tables_check(c, false)) return rc;
+    return batch_learn_tables_fetch(c, h_means, h_transition, nullptr, h_status);
+}
+
+// The same tables and -- d_sigmas given -- scales into device buffers, stream-ordered.
+static int batch_learn_tables_copy(cpprob_hip_ctx* c, double* d_means, double* d_transition, double* d_sigmas)
+{
+    BatchState* bs = c->batch;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
+    if (d_sigmas) HIP_TRY(c, hipMemcpy2DAsync(d_sigmas, k * sizeof(double), bs->d_sigma, 8 * sizeof(double), k * sizeof(double), B, hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_means, bs->d_lmeans, B * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_transition, bs->d_ltrans, B * k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return 0;
+}
+
+int cpprob_hip_batch_learn_tables_device(cpprob_hip_ctx* c, double* d_means, double* d_transition)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_tables_check(c, false)) return rc;
+    if (!d_means || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    return batch_learn_tables_copy(c, d_means, d_transition, nullptr);
+}
+
+int cpprob_hip_batch_learn_tables_scaled(cpprob_hip_ctx* c, double* h_means, double* h_transition, double* h_sigmas, int32_t* h_status)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_tables_check(c, true)) return rc;
+    return batch_learn_tables_fetch(c, h_means, h_transition, h_sigmas, h_status);
+}
+
+int cpprob_hip_batch_learn_tables_scaled_device(cpprob_hip_ctx* c, double* d_means, double* d_transition, double* d_sigmas)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_tables_check(c, true)) return rc;
+    if (!d_means || !d_transition || !d_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    return batch_learn_tables_copy(c, d_means, d_transition, d_sigmas);
 }
 
 int cpprob_hip_batch_learn_record(cpprob_hip_ctx* c, double* h_stats, size_t n_doubles)

@@ -1,16 +1,20 @@
 """Particle EM for the tables of MODEL_HMM_TABLE problems: the E-step is Engine.batch_smooth_stats (the backward smoother's expected
-sufficient statistics, one record a problem, computed on the device), the M-step below is 88 doubles a problem on the host.  The
-model fixes the emission's sigma at 1, so a table is its means and its transition rows; the initial state is uniform and not fitted."""
+sufficient statistics, one record a problem, computed on the device), the M-step below is 88 doubles a problem on the host.  A
+table is its means and its transition rows and, where the caller passes them, its per-state emission scales (without them the
+emission's sigma is 1 and stays so); the initial state is uniform and not fitted."""
 import numpy as np
 
 from .capi import MODEL_HMM_TABLE, RESAMPLE_SYSTEMATIC, STATS_PER_PROBLEM
 
 
-def m_step(stats, means, trans):
+def m_step(stats, means, trans, sigmas=None, sigma_floor=1e-3):
     """The tables that maximise the expected complete-data log-likelihood under `stats` (a dict as Engine.batch_smooth_stats returns:
     xi [B, 8, 8], occ, occ_y [B, 8]): trans[b, s, :] = xi[b, s, :k] / its sum, means[b, s] = occ_y[b, s] / occ[b, s], k =
     means.shape[1].  A transition row or a state with no mass keeps its previous value; states >= k of the statistics are not read.
-    Pure numpy; returns new (means [B, k], trans [B, k, k])."""
+    Pure numpy; returns new (means [B, k], trans [B, k, k]).
+    sigmas [B, k]: the emission scales are fitted too, and returned as a third array -- a state with mass takes v = occ_yy / occ -
+    mean' mean' (mean' its new mean) and sigma' = sqrt(v) where v >= sigma_floor^2, else sigma_floor (a NaN v too); a state without
+    mass keeps its sigma.  The statements of csrc/batch_scale.hpp, which cpprob_hip_batch_mstep_scaled_device runs bit for bit."""
     means = np.array(means, np.float64)
     trans = np.array(trans, np.float64)
     if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]):
@@ -28,10 +32,25 @@ def m_step(stats, means, trans):
     trans[fit] = xi[fit] / row[fit][:, None]
     seen = occ > 0.0
     means[seen] = occ_y[seen] / occ[seen]
-    return means, trans
+    if sigmas is None:
+        return means, trans
+    sigmas = np.array(sigmas, np.float64)
+    if sigmas.shape != means.shape:
+        raise ValueError("sigmas [B, k]")
+    floor = np.float64(sigma_floor)
+    if not (floor > 0.0) or not np.isfinite(floor):
+        raise ValueError("sigma_floor must be finite and > 0")
+    occ_yy = np.asarray(stats["occ_yy"], np.float64)[:, :k]
+    with np.errstate(all="ignore"):
+        v = occ_yy[seen] / occ[seen]
+        v = v - means[seen] * means[seen]
+        root = np.sqrt(np.where(v >= floor * floor, v, 1.0))
+    sigmas[seen] = np.where(v >= floor * floor, root, floor)
+    return means, trans, sigmas
 
 
-def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iterations, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, resident=False):
+def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iterations, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, resident=False,
+                 sigmas0=None, sigma_floor=1e-3):
     """Batched particle EM.  observes: a list of B 1-D sequences, or one sequence every problem shares (restarts: one sequence under
     B initial tables); means0 [B, k], trans0 [B, k, k] the initial tables; seeds [B].  Iteration i begins a batch with the current
     tables (batch_begin_problems), runs it with seeds + i, takes the statistics and the M-step.  Returns (means [iterations + 1, B, k],
@@ -40,7 +59,9 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
     and keep the smoother's masses (keep_masses) -- the same arrays bit for bit, without a particle store.
     resident=True: one batch_begin_problems, then the whole loop is enqueued on the engine's stream -- per iteration batch_run,
     batch_smooth_stats_device, batch_summaries_device, batch_mstep_device and batch_retable_device on tensors that stay on the device
-    -- and the tables of every iteration and the evidences are read once after it.  The same arrays bit for bit."""
+    -- and the tables of every iteration and the evidences are read once after it.  The same arrays bit for bit.
+    sigmas0 [B, k]: the problems carry per-state emission scales, fitted with the rest (m_step with sigmas, none below sigma_floor); a
+    fourth array, sigmas [iterations + 1, B, k], is returned behind the three.  Both routes, the same arrays bit for bit."""
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
     B = means.shape[0]
@@ -50,33 +71,49 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
     if len(seqs) != B:
         raise ValueError("one sequence per table (or one for all)")
     sd = np.ascontiguousarray(seeds, np.uint64)
+    sigmas = None if sigmas0 is None else np.array(sigmas0, np.float64)
+    if sigmas is not None and sigmas.shape != means.shape:
+        raise ValueError("sigmas0 [B, k]")
     if resident and int(iterations) > 0:
-        return _em_resident(engine, seqs, means, trans, n_particles, sd, int(iterations), resampler, bool(keep_history))
+        return _em_resident(engine, seqs, means, trans, n_particles, sd, int(iterations), resampler, bool(keep_history), sigmas, float(sigma_floor))
     m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(iterations), B))
+    s_hist = None if sigmas is None else [sigmas.copy()]
     for it in range(int(iterations)):
-        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), resampler=resampler, keep_history=bool(keep_history),
+        tables = (means, trans) if sigmas is None else (means, trans, sigmas)
+        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, resampler=resampler, keep_history=bool(keep_history),
                                     keep_masses=not keep_history)
         engine.batch_run(sd + np.uint64(it))
         stats = engine.batch_smooth_stats(seqs)
         ev[it] = [s["log_evidence"] for s in engine.batch_results()[0]]
-        means, trans = m_step(stats, means, trans)
+        if sigmas is None:
+            means, trans = m_step(stats, means, trans)
+        else:
+            means, trans, sigmas = m_step(stats, means, trans, sigmas, sigma_floor)
+            s_hist.append(sigmas.copy())
         m_hist.append(means.copy())
         t_hist.append(trans.copy())
-    return np.array(m_hist), np.array(t_hist), ev
+    if sigmas is None:
+        return np.array(m_hist), np.array(t_hist), ev
+    return np.array(m_hist), np.array(t_hist), ev, np.array(s_hist)
 
 
-def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resampler, keep_history):
+def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resampler, keep_history, sigmas=None, sigma_floor=1e-3):
     """hmm_table_em's loop with the tables, the observes, the records and the evidences in device tensors; the host enqueues and
     looks at nothing until the loop is over."""
     import torch
     B, k = means.shape
     dev = torch.device("cuda", engine.device)
-    engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), resampler=resampler, keep_history=keep_history, keep_masses=not keep_history)
+    tables = (means, trans) if sigmas is None else (means, trans, sigmas)
+    engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, resampler=resampler, keep_history=keep_history, keep_masses=not keep_history)
     obs = torch.from_numpy(np.ascontiguousarray(np.concatenate(seqs))).to(dev)
     m_all = torch.zeros((iterations + 1, B, k), dtype=torch.float64, device=dev)
     t_all = torch.zeros((iterations + 1, B, k, k), dtype=torch.float64, device=dev)
     m_all[0].copy_(torch.from_numpy(means))
     t_all[0].copy_(torch.from_numpy(trans))
+    s_all = None
+    if sigmas is not None:
+        s_all = torch.zeros((iterations + 1, B, k), dtype=torch.float64, device=dev)
+        s_all[0].copy_(torch.from_numpy(sigmas))
     stats = torch.zeros((B, STATS_PER_PROBLEM), dtype=torch.float64, device=dev)
     ev = torch.zeros((iterations, B, 4), dtype=torch.float64, device=dev)
     torch.cuda.current_stream(dev).synchronize()            # (the engine's stream is not ordered behind torch's: the tensors are complete first)
@@ -88,8 +125,15 @@ def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resamp
         with torch.cuda.stream(stream):                     # (the next tables start as these: a copy on the engine's stream)
             m_all[it + 1].copy_(m_all[it])
             t_all[it + 1].copy_(t_all[it])
-        engine.batch_mstep_device(stats, m_all[it + 1], t_all[it + 1])
+            if s_all is not None:
+                s_all[it + 1].copy_(s_all[it])
+        if s_all is None:
+            engine.batch_mstep_device(stats, m_all[it + 1], t_all[it + 1])
+        else:
+            engine.batch_mstep_device(stats, m_all[it + 1], t_all[it + 1], sigmas=s_all[it + 1], sigma_floor=sigma_floor)
         if it + 1 < iterations:
-            engine.batch_retable_device(m_all[it + 1], t_all[it + 1], obs)
+            engine.batch_retable_device(m_all[it + 1], t_all[it + 1], obs, sigmas=None if s_all is None else s_all[it + 1])
     engine.sync()
-    return m_all.cpu().numpy(), t_all.cpu().numpy(), np.ascontiguousarray(ev[:, :, 0].cpu().numpy())
+    if s_all is None:
+        return m_all.cpu().numpy(), t_all.cpu().numpy(), np.ascontiguousarray(ev[:, :, 0].cpu().numpy())
+    return m_all.cpu().numpy(), t_all.cpu().numpy(), np.ascontiguousarray(ev[:, :, 0].cpu().numpy()), s_all.cpu().numpy()

@@ -42,6 +42,10 @@
 //                   chunk the stream's tables are refitted on the device from the discounted running statistics, step sizes (t + 1)^-A
 //                   (0.6), no M-step before T observes (20), and the next chunk is filtered under them; the final tables are printed as
 //                   --em_iterations prints them)
+//                   --emission_scales (with --batch_tables_file: every line carries four lists, [means] [sigmas] [transition] [observes]:
+//                   state s emits N(means[s], sigmas[s]); the fitted tables are printed with their sigmas as a third list)
+//                   --learn_scales [--scale_floor F] (with --emission_scales and --em_iterations or --online_em: the sigmas are fitted
+//                   too, none below F (0.001); without it they stay)
 //                   --running_stats (with --batch_tables_file --stream_chunk K: every chunk is followed by the forward-only update of the
 //                   expected sufficient statistics, at the cost of the chunk's steps; after everything else one line a problem, the
 //                   record of the lengths reached in --trajectory_stats' format)
@@ -73,6 +77,7 @@ struct Args {
     std::size_t n_samples = 10000;            // src/main.cpp:166
     std::size_t stream_chunk = 0;             // --batch_tables_file: feed every problem's observes this many at a time (0: all at once)
     std::size_t em_iterations = 0;            // --batch_tables_file: fit the tables by this many iterations of particle EM (0: none)
+    bool emission_scales = false;             // --batch_tables_file: every line carries [sigmas] behind [means]: per-state emission scales
     std::string conditional_paths_file;       // --batch_tables_file: the reference paths of a conditional run, one line a problem (empty: none)
 };
 
@@ -247,12 +252,21 @@ int execute_batch_tables(const Args& a)
     while (std::getline(in, line)) {
         const std::size_t at = tables.size();
         std::tuple<std::vector<double>, std::vector<double>, std::vector<double>> p;
-        if (!cpprob::parse_string(line, p)) { std::cerr << "Could not parse line " << at << ": expected [means] [transition] [observes]." << std::endl; return EXIT_FAILURE; }
+        std::vector<double> sigmas;
+        if (a.emission_scales) {
+            // --emission_scales: four lists a line, [means] [sigmas] [transition] [observes]
+            std::tuple<std::vector<double>, std::vector<double>, std::vector<double>, std::vector<double>> q;
+            if (!cpprob::parse_string(line, q)) { std::cerr << "Could not parse line " << at << ": expected [means] [sigmas] [transition] [observes]." << std::endl; return EXIT_FAILURE; }
+            sigmas = std::get<1>(q);
+            if (sigmas.size() != std::get<0>(q).size()) { std::cerr << "line " << at << ": " << sigmas.size() << " sigmas for " << std::get<0>(q).size() << " means." << std::endl; return EXIT_FAILURE; }
+            p = std::make_tuple(std::get<0>(q), std::get<2>(q), std::get<3>(q));
+        }
+        else if (!cpprob::parse_string(line, p)) { std::cerr << "Could not parse line " << at << ": expected [means] [transition] [observes]." << std::endl; return EXIT_FAILURE; }
         if (at == 0) k = std::get<0>(p).size();
         if (std::get<0>(p).size() != k) { std::cerr << "line " << at << ": " << std::get<0>(p).size() << " means, but the first line has " << k << "." << std::endl; return EXIT_FAILURE; }
         if (std::get<1>(p).size() != k * k) { std::cerr << "line " << at << ": the transition list holds " << std::get<1>(p).size() << " weights, not k x k = " << k * k << "." << std::endl; return EXIT_FAILURE; }
         if (std::get<2>(p).empty()) { std::cerr << "line " << at << ": no observes." << std::endl; return EXIT_FAILURE; }
-        tables.push_back(cpprob::gpu::HmmTable{std::get<0>(p), std::get<1>(p)});
+        tables.push_back(cpprob::gpu::HmmTable{std::get<0>(p), std::get<1>(p), sigmas});
         observes.push_back(std::get<2>(p));
         seeds.push_back(cpprob::gpu::options().seed + at);
     }
@@ -316,7 +330,14 @@ int execute_batch_tables(const Args& a)
         for (std::size_t s = 0; s < t.means.size(); ++s) std::cout << (s ? " " : "") << t.means[s];
         std::cout << "] [";
         for (std::size_t i = 0; i < t.transition.size(); ++i) std::cout << (i ? " " : "") << t.transition[i];
-        std::cout << "]" << std::endl;
+        std::cout << "]";
+        if (!t.sigmas.empty()) {
+            // (tables with emission scales: the fitted sigmas behind the table)
+            std::cout << " [";
+            for (std::size_t s = 0; s < t.sigmas.size(); ++s) std::cout << (s ? " " : "") << t.sigmas[s];
+            std::cout << "]";
+        }
+        std::cout << std::endl;
     }
     print_trajectory_stats(res, k);
     print_running_stats(res, k);
@@ -387,6 +408,9 @@ int main(int argc, char** argv)
         else if (f == "--trajectory_stats") opt.trajectory_stats = std::stoull(next());   // the batch modes: the records of this many backward-simulated trajectories a problem (cpprob_hip_batch_traj_stats)
         else if (f == "--online_em") opt.learn_tables = true;                      // --batch_tables_file --stream_chunk: the stream learns its tables on the device (cpprob_hip_batch_advance_learn)
         else if (f == "--em_step_exponent") opt.learn_step_exponent = std::stod(next());   // ... with the step sizes (t + 1) ^ -A
+        else if (f == "--emission_scales") a.emission_scales = true;              // --batch_tables_file: every line is [means] [sigmas] [transition] [observes]
+        else if (f == "--learn_scales") opt.learn_scales = true;                   // --em_iterations / --online_em with --emission_scales: the sigmas are fitted too
+        else if (f == "--scale_floor") opt.scale_floor = std::stod(next());        // ... none below this
         else if (f == "--em_burn_in") opt.learn_burn_in = std::stoull(next());      // ... and no M-step before a problem has this many observes
         else if (f == "--running_stats") opt.running_stats = true;                 // --batch_tables_file --stream_chunk: the expected statistics kept forward-only (cpprob_hip_batch_online_stats)
         else if (f == "--draw_index") opt.trajectory_stats_draw_index = std::stoull(next());   // ... under this draw index
@@ -421,6 +445,11 @@ int main(int argc, char** argv)
         else { std::cerr << "unknown option " << f << std::endl; return EXIT_FAILURE; }
     }
     if (a.sis == a.smc) { std::cerr << "exactly one of --sis / --smc has to be set" << std::endl; return EXIT_FAILURE; }
+    if (a.emission_scales && a.batch_tables_file.empty()) { std::cerr << "--emission_scales reads the sigmas of --batch_tables_file" << std::endl; return EXIT_FAILURE; }
+    if (opt.learn_scales && (!a.emission_scales || (a.em_iterations == 0 && !opt.learn_tables))) {
+        std::cerr << "--learn_scales fits the sigmas of --emission_scales: set it with --em_iterations or --online_em" << std::endl;
+        return EXIT_FAILURE;
+    }
     if (opt.fit_on_device && a.em_iterations == 0) { std::cerr << "--em_on_device re-tables the batch of a fit: set --em_iterations" << std::endl; return EXIT_FAILURE; }
     if ((opt.forecast_horizon || opt.forecast_trajectories) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
         std::cerr << "--forecast serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;

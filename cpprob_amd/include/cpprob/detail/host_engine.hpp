@@ -815,12 +815,19 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
 // table computes: log_evidence, ess, one predict per observe ("state[t]": P(x_t = s), s < k) and the per-step ESS.  tables, observes
 // and n of size 1 are shared by all problems; the number of problems is seeds.size().  Resampler, keep_history (false: filtering
 // statistics), ess_threshold (must be > 1: every step) and device come from options(), as for inference_batch.
-struct HmmTable { std::vector<double> means, transition; };
+// sigmas: empty (the emission of state s is N(means[s], 1)) or k per-state emission scales (N(means[s], sigmas[s]); include/cpprob_hip.h:
+// cpprob_hip_batch_begin_problems_scaled) -- every table of a call with them, or none.
+struct HmmTable {
+    std::vector<double> means, transition, sigmas;
+    HmmTable() = default;
+    HmmTable(std::vector<double> m, std::vector<double> t, std::vector<double> s = std::vector<double>()) : means(std::move(m)), transition(std::move(t)), sigmas(std::move(s)) {}
+};
 
 // The problems of hmm_table_batch / hmm_table_fit as cpprob_hip_batch_begin_problems takes them.
 struct HmmTableProblems {
     std::size_t k = 0, T_max = 0, n_max = 0;
     std::vector<double> means, trans, flat;     // [B][k], [B][k][k], the observes packed problem after problem
+    std::vector<double> sigmas;                 // [B][k], or empty: the tables carry no emission scales
     std::vector<std::uint32_t> T, np;           // [B]
 };
 
@@ -838,8 +845,11 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
         const HmmTable& tb = tables[tables.size() == 1 ? 0 : b];
         if (tb.means.size() != pk.k || tb.transition.size() != pk.k * pk.k)
             throw std::runtime_error(who + ": problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
+        if (tb.sigmas.size() != (tables[0].sigmas.empty() ? 0 : pk.k))
+            throw std::runtime_error(who + ": problem " + std::to_string(b) + ": every table holds k emission scales, or none does");
         pk.means.insert(pk.means.end(), tb.means.begin(), tb.means.end());
         pk.trans.insert(pk.trans.end(), tb.transition.begin(), tb.transition.end());
+        pk.sigmas.insert(pk.sigmas.end(), tb.sigmas.begin(), tb.sigmas.end());
         const std::vector<double>& o = observes[observes.size() == 1 ? 0 : b];
         pk.flat.insert(pk.flat.end(), o.begin(), o.end());
         const std::size_t nb = n[n.size() == 1 ? 0 : b];
@@ -883,8 +893,15 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
     bc.n_particles = pk.n_max;
     bc.n_problems = B;
     const auto t0 = std::chrono::steady_clock::now();
-    if (retable)
+    const bool scaled = !pk.sigmas.empty();
+    if (retable && scaled)
+        ctx.check(cpprob_hip_batch_retable_scaled(ctx.get(), pk.means.data(), pk.trans.data(), pk.sigmas.data(), with_observes ? pk.flat.data() : nullptr, pk.flat.size()),
+                  "cpprob_hip_batch_retable_scaled");
+    else if (retable)
         ctx.check(cpprob_hip_batch_retable(ctx.get(), pk.means.data(), pk.trans.data(), with_observes ? pk.flat.data() : nullptr, pk.flat.size()), "cpprob_hip_batch_retable");
+    else if (scaled)
+        ctx.check(cpprob_hip_batch_begin_problems_scaled(ctx.get(), &bc, T.data(), pk.np.data(), pk.flat.data(), static_cast<std::int32_t>(k), pk.means.data(), pk.trans.data(),
+                                                         pk.sigmas.data()), "cpprob_hip_batch_begin_problems_scaled");
     else
         ctx.check(cpprob_hip_batch_begin_problems(ctx.get(), &bc, T.data(), pk.np.data(), pk.flat.data(), static_cast<std::int32_t>(k), pk.means.data(), pk.trans.data()),
                   "cpprob_hip_batch_begin_problems");
@@ -966,6 +983,9 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // under the FITTED tables, and its decode (Result::map_path, ::map_score) in the results -- the labels a fit is made for.
 // options().fit_on_device: the first run begins the batch, every later one re-tables it on the device (cpprob_hip_batch_retable) -- the
 // same HmmTableFit bit for bit without a begin's host work an iteration.
+// Tables with emission scales (HmmTable::sigmas): the batches are scaled; options().learn_scales: the M-step fits the scales too -- a
+// state with mass takes v = occ_yy[s] / occ[s] - means[s] means[s] (its new mean) and sigmas[s] = sqrt(v) where v >= scale_floor^2, else
+// options().scale_floor (a NaN v too), the statements of cpprob_hip_batch_mstep_scaled_device.  Without it the scales stay.
 struct HmmTableFit { std::vector<HmmTable> tables; std::vector<Result> results; };
 
 inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes, const std::vector<std::size_t>& n,
@@ -982,6 +1002,10 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
     std::vector<double> rec(B * R);
     std::vector<std::uint64_t> keys(B);
     const bool kept = options().fit_on_device;                 // the batch of iteration 0 is re-tabled from then on
+    const bool fit_scales = options().learn_scales;
+    const double floor = options().scale_floor;
+    if (fit_scales && pk.sigmas.empty()) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().learn_scales fits emission scales: give every table its sigmas");
+    if (fit_scales && (!(floor > 0.0) || !std::isfinite(floor))) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().scale_floor must be finite and > 0");
     std::size_t runs = 0;
     for (std::size_t it = 0; it < iterations; ++it) {
         for (std::size_t b = 0; b < B; ++b) keys[b] = seeds[b] + it;
@@ -997,6 +1021,12 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
                 if (row > 0.0)
                     for (std::size_t j = 0; j < k; ++j) pk.trans[(b * k + s) * k + j] = r[8 * s + j] / row;
                 if (r[64 + s] > 0.0) pk.means[b * k + s] = r[72 + s] / r[64 + s];
+                if (fit_scales && r[64 + s] > 0.0) {
+                    const double mean = pk.means[b * k + s], mm = mean * mean, ff = floor * floor;
+                    double v = r[80 + s] / r[64 + s];
+                    v = v - mm;
+                    pk.sigmas[b * k + s] = v >= ff ? std::sqrt(v) : floor;
+                }
             }
         }
     }
@@ -1011,6 +1041,7 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
     for (std::size_t b = 0; b < B; ++b) {
         fit.tables[b].means.assign(pk.means.begin() + static_cast<std::ptrdiff_t>(b * k), pk.means.begin() + static_cast<std::ptrdiff_t>((b + 1) * k));
         fit.tables[b].transition.assign(pk.trans.begin() + static_cast<std::ptrdiff_t>(b * k * k), pk.trans.begin() + static_cast<std::ptrdiff_t>((b + 1) * k * k));
+        if (!pk.sigmas.empty()) fit.tables[b].sigmas.assign(pk.sigmas.begin() + static_cast<std::ptrdiff_t>(b * k), pk.sigmas.begin() + static_cast<std::ptrdiff_t>((b + 1) * k));
     }
     return fit;
 }
@@ -1045,6 +1076,9 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // burn-in options().learn_burn_in) and every advance is a learning advance (cpprob_hip_batch_advance_learn, with the read-out walk):
 // the tables change between advances, the chunk is the update period, log_evidence is the prequential likelihood under the tables in
 // force at each step; tables() reads what the stream has learned.
+// Tables with emission scales (HmmTable::sigmas): the stream is a scaled one (cpprob_hip_batch_begin_online_scaled); with
+// options().learn_tables and options().learn_scales the learner fits the scales too, none below options().scale_floor
+// (cpprob_hip_batch_learn_begin_scaled) -- without learn_scales it learns means and transition rows and keeps them; tables() returns them.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -1069,7 +1103,10 @@ public:
         auto fits = [B](std::size_t have) { return have == B || have == 1; };
         if (!fits(tables.size()) || !fits(capacities.size()) || !fits(n.size()))
             throw std::runtime_error("cpprob::gpu::HmmTableStream: tables, capacities and n hold one entry per seed, or one entry shared by all problems");
-        std::vector<double> means, trans;
+        std::vector<double> means, trans, sigmas;
+        scaled_ = !tables[0].sigmas.empty();
+        if (options().learn_scales && learn_ && !scaled_)
+            throw std::runtime_error("cpprob::gpu::HmmTableStream: options().learn_scales fits emission scales: give every table its sigmas");
         std::vector<std::uint32_t> cap(B_);
         np_.resize(B_);
         std::size_t n_max = 0;
@@ -1077,8 +1114,11 @@ public:
             const HmmTable& tb = tables[tables.size() == 1 ? 0 : b];
             if (tb.means.size() != k_ || tb.transition.size() != k_ * k_)
                 throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
+            if (tb.sigmas.size() != (scaled_ ? k_ : 0))
+                throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": every table holds k emission scales, or none does");
             means.insert(means.end(), tb.means.begin(), tb.means.end());
             trans.insert(trans.end(), tb.transition.begin(), tb.transition.end());
+            sigmas.insert(sigmas.end(), tb.sigmas.begin(), tb.sigmas.end());
             const std::size_t cb = capacities[capacities.size() == 1 ? 0 : b], nb = n[n.size() == 1 ? 0 : b];
             if (cb > 0x7fffffffu || nb > 0x7fffffffu) throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": too large for a batch");
             cap[b] = static_cast<std::uint32_t>(cb); np_[b] = static_cast<std::uint32_t>(nb);
@@ -1095,14 +1135,21 @@ public:
         bc.n_particles = n_max;
         bc.n_problems = B_;
         Context& ctx = *lease_;
-        ctx.check(cpprob_hip_batch_begin_online(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), seeds.data()),
-                  "cpprob_hip_batch_begin_online");
+        if (scaled_)
+            ctx.check(cpprob_hip_batch_begin_online_scaled(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), sigmas.data(),
+                                                           seeds.data()), "cpprob_hip_batch_begin_online_scaled");
+        else
+            ctx.check(cpprob_hip_batch_begin_online(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), seeds.data()),
+                      "cpprob_hip_batch_begin_online");
         if (learn_) {
             // the step sizes, evaluated here: the device takes no power
             std::vector<double> gamma(T_max_);
             for (std::size_t t = 0; t < T_max_; ++t) gamma[t] = std::pow(static_cast<double>(t) + 1.0, -opt.learn_step_exponent);
-            ctx.check(cpprob_hip_batch_learn_begin(ctx.get(), gamma.data(), gamma.size(), static_cast<std::uint32_t>(std::min<std::size_t>(opt.learn_burn_in, 0xffffffffu))),
-                      "cpprob_hip_batch_learn_begin");
+            const std::uint32_t burn_in = static_cast<std::uint32_t>(std::min<std::size_t>(opt.learn_burn_in, 0xffffffffu));
+            if (scaled_ && opt.learn_scales)
+                ctx.check(cpprob_hip_batch_learn_begin_scaled(ctx.get(), gamma.data(), gamma.size(), burn_in, opt.scale_floor), "cpprob_hip_batch_learn_begin_scaled");
+            else
+                ctx.check(cpprob_hip_batch_learn_begin(ctx.get(), gamma.data(), gamma.size(), burn_in), "cpprob_hip_batch_learn_begin");
         }
         lease_.done();
         if (lag_ >= 0) { lagged_.assign(B_ * T_max_ * 8, 0.0); L_prev_.assign(B_, 0); }
@@ -1211,10 +1258,14 @@ public:
     {
         if (!learn_) throw std::runtime_error("cpprob::gpu::HmmTableStream: tables() reads the tables of a learning stream: set options().learn_tables");
         Context& ctx = *lease_;
-        std::vector<double> means(B_ * k_), trans(B_ * k_ * k_);
-        ctx.check(cpprob_hip_batch_learn_tables(ctx.get(), means.data(), trans.data(), nullptr), "cpprob_hip_batch_learn_tables");
+        std::vector<double> means(B_ * k_), trans(B_ * k_ * k_), sigmas(scaled_ ? B_ * k_ : 0);
+        if (scaled_)
+            ctx.check(cpprob_hip_batch_learn_tables_scaled(ctx.get(), means.data(), trans.data(), sigmas.data(), nullptr), "cpprob_hip_batch_learn_tables_scaled");
+        else
+            ctx.check(cpprob_hip_batch_learn_tables(ctx.get(), means.data(), trans.data(), nullptr), "cpprob_hip_batch_learn_tables");
         std::vector<HmmTable> out(B_);
         for (std::size_t b = 0; b < B_; ++b) {
+            if (scaled_) out[b].sigmas.assign(sigmas.begin() + static_cast<std::ptrdiff_t>(b * k_), sigmas.begin() + static_cast<std::ptrdiff_t>((b + 1) * k_));
             out[b].means.assign(means.begin() + static_cast<std::ptrdiff_t>(b * k_), means.begin() + static_cast<std::ptrdiff_t>((b + 1) * k_));
             out[b].transition.assign(trans.begin() + static_cast<std::ptrdiff_t>(b * k_ * k_), trans.begin() + static_cast<std::ptrdiff_t>((b + 1) * k_ * k_));
         }
@@ -1250,6 +1301,7 @@ private:
     std::vector<std::vector<double>> seen_;    // trajectory_stats: [b] = problem b's observes so far
     bool running_stats_ = options().running_stats;
     bool learn_ = options().learn_tables;
+    bool scaled_ = false;                      // the tables carry emission scales
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

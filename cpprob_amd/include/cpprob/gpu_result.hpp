@@ -54,6 +54,9 @@ struct Options {
                                                       // its observes arrive (cpprob_hip_batch_learn_begin, _advance_learn): after every advance the M-step on the
                                                       // discounted running statistics gives the tables the next observes are filtered under; tables() reads them
     double learn_step_exponent = 0.6;                 // ... with the step sizes gamma[t] = (t + 1) ^ -this, evaluated on the host (0.5 < exponent <= 1)
+    bool learn_scales = false;                        // hmm_table_fit and HmmTableStream with learn_tables, tables with HmmTable::sigmas: the per-state emission
+                                                      // scales are fitted too (the M-step's sigma' = sqrt(occ_yy / occ - mean'^2)), none below scale_floor
+    double scale_floor = 1e-3;                        // ... finite and > 0
     std::size_t learn_burn_in = 20;                   // ... and no M-step before a problem has reached this length
     bool map_decode = false;                          // batched runs (keep_history, or keep_masses): every result carries Result::map_path, the single most
                                                       // probable state sequence given the observes over the states the particles occupy, and

@@ -19,6 +19,8 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     trajectory crosses to the host.  Returns (means [sweeps + 1, B, k], trans [sweeps + 1, B, k, k]): the tables before every sweep
     and after the last.  retable=True (a keyword beside the prior's, default False): sweep 0 begins the batch; every later sweep gives it its new tables where it stands
     (batch_retable: the tables drawn on the host, the observes uploaded once) in place of a fresh begin -- the same chain bit for bit.
+    sigmas0 [B, k] (a keyword likewise, default None): the chains carry per-state emission scales, sampled with the rest
+    (sample_tables with sigmas; prior: its a0, b0), and a third array, sigmas [sweeps + 1, B, k], is returned behind the two.
 
     This is particle Gibbs with backward sampling: a conditional SMC run with multinomial resampling, its retained particle the
     previous trajectory, followed by backward simulation.  That kernel leaves the smoothing law of the states given the tables
@@ -27,6 +29,9 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     it settles.  (hmm_table_gibbs draws its trajectory from an unconditional filter and is exact only as n_particles grows.)"""
     import torch
     retable = bool(prior.pop("retable", False))
+    sigmas0 = prior.pop("sigmas0", None)
+    sigmas = None if sigmas0 is None else np.array(sigmas0, np.float64)
+    s_hist = None if sigmas is None else [sigmas.copy()]
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
     B, k = means.shape
@@ -40,17 +45,25 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     traj = [torch.empty(total, dtype=torch.int8, device="cuda:%d" % engine.device) for _ in range(2)]
     m_hist, t_hist = [means.copy()], [trans.copy()]
     for i in range(int(sweeps)):
+        tables = (means, trans) if sigmas is None else (means, trans, sigmas)
         if retable and i > 0:
-            engine.batch_retable((means, trans), seqs if i == 1 else None)
+            engine.batch_retable(tables, seqs if i == 1 else None)
         else:
-            engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=(means, trans), keep_history=False, keep_masses=True)
+            engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, keep_history=False, keep_masses=True)
         if i == 0:
             engine.batch_run(sd)
         else:
             engine.batch_run_conditional_device(sd + np.uint64(i), traj[(i - 1) & 1])
         engine.batch_smooth_device(traj_i8=traj[i & 1], n_traj=1, draw_index=i % (1 << 16))
         stats = engine.batch_traj_stats(1, draw_index=i % (1 << 16), observes=seqs)
-        means, trans = sample_tables({name: v[:, 0] for name, v in stats.items()}, k, rng, **prior)
+        one = {name: v[:, 0] for name, v in stats.items()}
+        if sigmas is None:
+            means, trans = sample_tables(one, k, rng, **prior)
+        else:
+            means, trans, sigmas = sample_tables(one, k, rng, sigmas=sigmas, **prior)
+            s_hist.append(sigmas.copy())
         m_hist.append(means.copy())
         t_hist.append(trans.copy())
-    return np.array(m_hist), np.array(t_hist)
+    if sigmas is None:
+        return np.array(m_hist), np.array(t_hist)
+    return np.array(m_hist), np.array(t_hist), np.array(s_hist)

@@ -781,6 +781,64 @@ int cpprob_hip_batch_learn_tables_device(cpprob_hip_ctx* ctx, double* d_means, d
 /* The records [n_problems][88] of the last learning advance (n_doubles >= 88 n_problems; none yet: zeros).  Synchronises. */
 int cpprob_hip_batch_learn_record(cpprob_hip_ctx* ctx, double* h_stats, size_t n_doubles);
 
+/* ---- per-state emission scales of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_scale.hpp) --
+ * State s of problem b emits N(mean[b][s], sigma[b][s]) in place of N(mean[b][s], 1).  The step kernel and every pass behind it read
+ * the emission through the per-step rows alone, so a scaled batch is run, advanced, smoothed, counted, forecast and decoded by the
+ * calls above as they are; what differs is who writes the rows.  Every scaled row, on the host and on the device, is
+ *   r = (y - mean) / sigma;  r *= r;  r += log_norm;  r *= -0.5          (-inf for an infinite y and for s >= k)
+ * with log_norm = table_log(((2 pi) sigma) sigma), and table_log is a logarithm of the library's own in uncontracted IEEE operations
+ * (exponent and mantissa by bit operations, the mantissa folded to [sqrt(1/2), sqrt(2)), twelve terms of the odd series in
+ * f = (m - 1) / (m + 1), e ln2_hi + (e ln2_lo + r)): host and device perform the same operations, so that a re-tabled batch is bit
+ * for bit a freshly begun one.  table_log(2 pi) has the bits of the C library's log(2 pi): a scaled batch whose sigmas are all 1.0
+ * returns, bit for bit, what the unit batch returns.  cpprob_hip_table_log exports the function for tests (x normal, positive,
+ * finite; host only). */
+double cpprob_hip_table_log(double x);
+/* cpprob_hip_batch_begin_problems / _begin_online with h_sigmas [B][k] behind the tables, which must be given (k_in states, h_means,
+ * h_transition: CPPROB_HIP_EINVAL where one is NULL; another model: CPPROB_HIP_EUNSUPPORTED).  Validated as those calls validate, and
+ * every sigma must be finite and > 0 with a normal finite 2 pi sigma^2 (CPPROB_HIP_EINVAL naming the problem; after a refusal nothing
+ * has changed).  The batch remembers that it is scaled: cpprob_hip_batch_advance writes its rows with the statements above. */
+int cpprob_hip_batch_begin_problems_scaled(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                           const double* h_observes, int32_t k, const double* h_means, const double* h_transition, const double* h_sigmas);
+int cpprob_hip_batch_begin_online_scaled(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
+                                         int32_t k, const double* h_means, const double* h_transition, const double* h_sigmas, const uint64_t* h_seeds);
+/* cpprob_hip_batch_retable_device / _retable with d_sigmas / h_sigmas [B][k], for a batch begun by
+ * cpprob_hip_batch_begin_problems_scaled (a batch without scales: CPPROB_HIP_ESTATE; cpprob_hip_batch_retable* likewise returns
+ * CPPROB_HIP_ESTATE on a scaled batch).  The device checks the table as those calls do and sets status bit 8 where a sigma is not
+ * finite, not > 0, or has a 2 pi sigma^2 that is not a normal finite number: such a problem keeps its rows, threshold words, sigmas
+ * and log_norms.  The launch takes one logarithm a state (table_log) and stores the sigmas and log_norms in force in arrays of the
+ * context's own; no workspace region is added.  Everything else as the unit calls. */
+int cpprob_hip_batch_retable_scaled_device(cpprob_hip_ctx* ctx, const double* d_means, const double* d_transition, const double* d_sigmas,
+                                           const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_scaled(cpprob_hip_ctx* ctx, const double* h_means, const double* h_transition, const double* h_sigmas,
+                                    const double* h_observes, size_t n_observes);
+/* cpprob_hip_batch_mstep_device with the scales: after that call's statements, a state with occ[s] > 0 takes
+ *   v = occ_yy[s] / occ[s] - means'[s] means'[s];   sigmas[s] = v >= sigma_floor sigma_floor ? sqrt(v) : sigma_floor      (a NaN v: the floor)
+ * (means' the new mean; a division, a product, a subtraction and the correctly rounded square root, none contracted) -- d_sigmas
+ * [B][k] updated in place, and where d_log_norm [B][k] is not NULL, log_norm[s] of the new sigma (NaN for a sigma the check above
+ * refuses).  A state without mass keeps mean, sigma and log_norm.  sigma_floor finite and > 0 (else CPPROB_HIP_EINVAL).
+ * cpprob_amd.em.m_step with sigmas, bit for bit.  Enqueued, no host synchronisation. */
+int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition,
+                                         double* d_sigmas, double* d_log_norm, double sigma_floor);
+/* cpprob_hip_batch_online_tables with h_sigmas [B][k], for a batch begun by cpprob_hip_batch_begin_online_scaled, armed or not (a
+ * batch without scales: CPPROB_HIP_ESTATE; cpprob_hip_batch_online_tables likewise returns CPPROB_HIP_ESTATE on a scaled batch). */
+int cpprob_hip_batch_online_tables_scaled(cpprob_hip_ctx* ctx, const double* h_means, const double* h_transition, const double* h_sigmas);
+/* Online EM of a scaled online batch (csrc/batch_learn_scaled.hpp).  cpprob_hip_batch_learn_begin_scaled is
+ * cpprob_hip_batch_learn_begin for a batch begun by cpprob_hip_batch_begin_online_scaled (a batch without scales: CPPROB_HIP_ESTATE;
+ * sigma_floor not finite or not > 0: CPPROB_HIP_EINVAL): the learner then fits the sigmas too.  cpprob_hip_batch_advance_learn* are
+ * the unchanged calls; on a scaled batch the rows of the new steps are written on the device from the device-resident means, sigmas
+ * and log_norms (no logarithm is taken there), and the learn step's M-step is cpprob_hip_batch_mstep_scaled_device's on the record, a
+ * state with mass taking sigma' as there and log_norm' = table_log(2 pi sigma'^2); the check adds status bit 8; a table that passes
+ * replaces the device table, the sigmas, the log_norms and the 64 threshold words, one that fails leaves all of them.  A plain
+ * cpprob_hip_batch_learn_begin on a scaled batch learns means and transition rows and keeps the sigmas: they are read, checked and
+ * never written.  cpprob_hip_batch_learn_tables_scaled / _device are cpprob_hip_batch_learn_tables / _device with the sigmas in force,
+ * [B][k] (h_sigmas may be NULL); a batch without scales: CPPROB_HIP_ESTATE. */
+int cpprob_hip_batch_learn_begin_scaled(cpprob_hip_ctx* ctx, const double* h_gamma, size_t n_gamma, uint32_t t_min, double sigma_floor);
+int cpprob_hip_batch_learn_tables_scaled(cpprob_hip_ctx* ctx, double* h_means, double* h_transition, double* h_sigmas, int32_t* h_status);
+int cpprob_hip_batch_learn_tables_scaled_device(cpprob_hip_ctx* ctx, double* d_means, double* d_transition, double* d_sigmas);
+/* Problem `problem`'s sigmas and log_norms in force as the device holds them, [k] each (either may be NULL).  Synchronises.
+ * CPPROB_HIP_ESTATE: no batch begun, or a batch without scales.  For tests. */
+int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* ctx, uint64_t problem, double* h_sigmas, double* h_log_norm);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
