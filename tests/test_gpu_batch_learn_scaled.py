@@ -5,7 +5,8 @@ M-step, check and rows of tests/scale_ref.py, batch_online_tables with the sigma
 of 24 steps fed in chunks of 1 and 5: problem 2 sits one advance out; problem 1 observes the constant 0.0, so that every state's
 variance is 0, its sigma the floor of 1e-160, 2 pi sigma^2 subnormal and every one of its M-steps dropped with bit 8.  Frozen (a
 burn-in above every capacity) the stream is the plain scaled online batch; armed by the plain batch_learn_begin it learns means and
-transition rows and leaves the sigmas."""
+transition rows and leaves the sigmas.  The same two routes on tests/test_gpu_batch_learn.py's ragged schedule: seven problems of 1
+to 300 particles and ragged capacities, a piece of 40 observes, a problem that never receives an observe."""
 import numpy as np
 import pytest
 
@@ -13,7 +14,7 @@ import cpprob_amd as cp
 import learn_ref as G
 import retable_ref as R
 import scale_ref as S
-from test_gpu_batch_learn import assert_same, new_masses, snapshot
+from test_gpu_batch_learn import CAPS, NS, SCHEDULE, assert_same, new_masses, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -24,30 +25,32 @@ B, T, N, T_MIN, FLOOR = 3, 24, 64, 3, 1e-160
 ScaledLearner = S.ScaledLearner
 
 
-def _seeds():
-    return np.array([77 + 7919 * b for b in range(B)], np.uint64)
+def _seeds(nb=B):
+    return np.array([77 + 7919 * b for b in range(nb)], np.uint64)
 
 
-def _gamma():
-    return (np.arange(T) + 1.0) ** -0.6
+def _gamma(n=T):
+    return (np.arange(n) + 1.0) ** -0.6
 
 
-def _tables(k, seed):
+def _tables(k, seed, nb=B):
     rng = np.random.default_rng(seed)
-    means = np.sort(rng.uniform(-3.0, 3.0, (B, k)), axis=1) + 0.5 * np.arange(k)
-    trans = rng.uniform(0.05, 1.0, (B, k, k))
-    sigmas = rng.uniform(0.4, 2.0, (B, k))
+    means = np.sort(rng.uniform(-3.0, 3.0, (nb, k)), axis=1) + 0.5 * np.arange(k)
+    trans = rng.uniform(0.05, 1.0, (nb, k, k))
+    sigmas = rng.uniform(0.4, 2.0, (nb, k))
     return means, trans, sigmas
 
 
-def _observes(tables, seed):
+def _observes(tables, seed, caps=None):
+    """Problem b's observes up to its capacity (caps None: B streams of T steps, problem 1 observing the constant 0.0)."""
     rng = np.random.default_rng(seed)
     k = tables[0].shape[1]
     obs = []
-    for b in range(B):
-        x = rng.integers(0, k, T)
-        obs.append(tables[0][b][x] + tables[2][b][x] * rng.standard_normal(T))
-    obs[1] = np.zeros(T)
+    for b, cap in enumerate([T] * B if caps is None else caps):
+        x = rng.integers(0, k, cap)
+        obs.append(tables[0][b][x] + tables[2][b][x] * rng.standard_normal(cap))
+    if caps is None:
+        obs[1] = np.zeros(T)
     return obs
 
 
@@ -61,24 +64,28 @@ def _schedule(chunk):
     return out
 
 
-def _begin(eng, tables, history, resampler):
-    eng.batch_begin_online(cp.MODEL_HMM_TABLE, [T] * B, N, _seeds(), tables=tables, resampler=resampler, keep_history=history, keep_masses=not history)
+def _begin(eng, tables, history, resampler, caps=None, ns=N):
+    """caps None: B streams of capacity T; ns: one particle count, or one a problem."""
+    caps = [T] * B if caps is None else caps
+    eng.batch_begin_online(cp.MODEL_HMM_TABLE, caps, ns, _seeds(len(caps)), tables=tables, resampler=resampler, keep_history=history, keep_masses=not history)
 
 
-def _resident(eng, k, tables, obs, schedule, history, resampler, t_min, floor):
-    _begin(eng, tables, history, resampler)
-    eng.batch_learn_begin(_gamma(), t_min, sigma_floor=floor)
-    lens, out = [0] * B, []
+def _resident(eng, k, tables, obs, schedule, history, resampler, t_min, floor, caps=None, ns=N):
+    _begin(eng, tables, history, resampler, caps, ns)
+    nb = len(obs)
+    eng.batch_learn_begin(_gamma(max(len(o) for o in obs)), t_min, sigma_floor=floor)
+    lens, out = [0] * nb, []
     for dT in schedule:
-        eng.batch_advance_learn([obs[b][lens[b]:lens[b] + dT[b]] for b in range(B)])
-        lens = [lens[b] + dT[b] for b in range(B)]
-        out.append((snapshot(eng, history, not history), eng.batch_learn_tables(k, scales=True), [eng.batch_scales(b, k) for b in range(B)], eng.batch_learn_record()))
+        eng.batch_advance_learn([obs[b][lens[b]:lens[b] + dT[b]] for b in range(nb)])
+        lens = [lens[b] + dT[b] for b in range(nb)]
+        out.append((snapshot(eng, history, not history), eng.batch_learn_tables(k, scales=True), [eng.batch_scales(b, k) for b in range(nb)], eng.batch_learn_record()))
     return out
 
 
-def _host_stepped(eng, k, tables, obs, schedule, history, resampler, floor, got):
-    _begin(eng, tables, history, resampler)
-    learners = [ScaledLearner(tables[0][b], tables[1][b], tables[2][b], k, _gamma(), T_MIN, floor) for b in range(B)]
+def _host_stepped(eng, k, tables, obs, schedule, history, resampler, floor, got, caps=None, ns=N):
+    _begin(eng, tables, history, resampler, caps, ns)
+    B = len(obs)
+    learners = [ScaledLearner(tables[0][b], tables[1][b], tables[2][b], k, _gamma(max(len(o) for o in obs)), T_MIN, floor) for b in range(B)]
     lens = [0] * B
     for a, dT in enumerate(schedule):
         piece = [obs[b][lens[b]:lens[b] + dT[b]] for b in range(B)]
@@ -119,6 +126,36 @@ def test_the_resident_scaled_stream_is_the_host_stepped_one(engine, chunk, k, hi
     assert learners[1].status == S.BAD_SCALE and learners[1].changed == 0 and got[-1][1][3][1] == S.BAD_SCALE
     assert np.array_equal(got[-1][1][2][1], tables[2][1]) and np.array_equal(got[-1][1][0][1], tables[0][1])
     assert learners[0].changed >= 3 and learners[2].changed >= 3 and not np.array_equal(got[-1][1][2][0], tables[2][0])
+
+
+RAGGED = [(k, history, floor) for k in (2, 8) for history in (True, False) for floor in (1e-3, None)]
+
+
+@pytest.mark.parametrize("k,history,floor", RAGGED, ids=["k%d-%s-%s" % (k, "history" if h else "masses", "floor" if f else "plain") for k, h, f in RAGGED])
+def test_the_resident_scaled_stream_on_the_ragged_schedule(engine, k, history, floor):
+    """tests/test_gpu_batch_learn.py's CAPS, NS and SCHEDULE under the scaled learner: seven problems (two workgroups of the learn
+    kernel) of 1 to 300 particles; a piece of 40 observes, so that the rows kernel's grid is 2; problem 2 never receives an observe
+    (the learn kernel's T <= 0 branch), problem 6 receives one and never reaches the burn-in.  floor None: the plain arming on a
+    scaled batch.  This is also where the learn kernel's own copy of table_log runs at sigmas nobody chose: every log_norm of every
+    advance is held to tests/scale_ref.py's."""
+    nb = len(CAPS)
+    assert nb == 7 and max(max(dT) for dT in SCHEDULE) == 40 and R.grid_y(40, nb) == 2 and (min(NS), max(NS)) == (1, 300)
+    assert all(dT[2] == 0 for dT in SCHEDULE) and sum(dT[6] for dT in SCHEDULE) == 1 < T_MIN
+    resampler = cp.RESAMPLE_SYSTEMATIC if history else cp.RESAMPLE_STRATIFIED
+    tables = _tables(k, 60 + k, nb)
+    obs = _observes(tables, 70 + k, CAPS)
+    got = _resident(engine, k, tables, obs, SCHEDULE, history, resampler, T_MIN, floor, CAPS, NS)
+    learners = _host_stepped(engine, k, tables, obs, SCHEDULE, history, resampler, floor, got, CAPS, NS)
+    for a in range(len(SCHEDULE)):
+        _, (m, t, sg, st), scales, rec = got[a]
+        assert not rec[2].any() and np.array_equal(m[2], tables[0][2]) and np.array_equal(t[2], tables[1][2]) and np.array_equal(sg[2], tables[2][2]) and st[2] == 0
+        assert np.array_equal(scales[2][0], tables[2][2]) and np.array_equal(scales[2][1], [S.log_norm(s) for s in tables[2][2]])
+        assert np.array_equal(m[6], tables[0][6]) and np.array_equal(sg[6], tables[2][6])
+        if floor is None:
+            assert np.array_equal(sg, tables[2]), "advance %d: the sigmas moved" % a
+    assert learners[2].changed == 0 and learners[2].done == 0 and learners[6].changed == 0 and learners[6].done == 1
+    assert learners[3].changed >= 3 and not np.array_equal(got[-1][1][0][3], tables[0][3])
+    assert (floor is None) == np.array_equal(got[-1][1][2][3], tables[2][3])
 
 
 @pytest.mark.parametrize("history", [True, False], ids=["history", "masses"])
