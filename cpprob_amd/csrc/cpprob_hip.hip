@@ -29,9 +29,8 @@
 #include "batch_decode.hpp"
 #include "batch_csmc.hpp"
 #include "batch_retable.hpp"
-#include "batch_learn.hpp"
 #include "batch_scale.hpp"
-#include "batch_learn_scaled.hpp"
+#include "batch_learn.hpp"
 #include "batch_pass_plan.hpp"
 
 using namespace cph;
@@ -1230,6 +1229,17 @@ int batch_check_problems(const cpprob_hip_batch_config* cfg, const uint32_t* h_T
     return 0;
 }
 
+// The host mirrors of a scaled batch ([B][8]): the scales in force and their logarithms, with the statements the device's re-table
+// evaluates (csrc/batch_scale.hpp).
+void batch_mirror_scales(BatchState* bs, size_t B, int k, const double* h_sigmas)
+{
+    for (size_t b = 0; b < B; ++b)
+        for (size_t s = 0; s < (size_t)k; ++s) {
+            bs->sigmas[b * 8 + s] = h_sigmas[b * (size_t)k + s];
+            bs->log_norms[b * 8 + s] = scale_log_norm(h_sigmas[b * (size_t)k + s]);
+        }
+}
+
 // Begins a checked batch.  Described (h_T, h_n given): problem b has h_T[b] observes, consecutive in h_obs, and h_n[b] particles;
 // uniform (both NULL): every problem has T_max observes and cfg->n_particles particles.  HMM_TABLE of k states: problem b's own table
 // (h_means [B][k], h_transition [B][k][k]) or, both NULL, the table of cpprob_hip_set_hmm.
@@ -1284,13 +1294,8 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->prob.resize(B);
     bs->scaled = false; bs->sigmas.clear(); bs->log_norms.clear();
     if (scaled) {
-        // the scales in force and their logarithms, with the statements the device's re-table evaluates (csrc/batch_scale.hpp)
         bs->sigmas.assign((size_t)B * 8, 0.0); bs->log_norms.assign((size_t)B * 8, 0.0);
-        for (uint64_t b = 0; b < B; ++b)
-            for (int s2 = 0; s2 < k; ++s2) {
-                bs->sigmas[b * 8 + (size_t)s2] = h_sigmas[b * (size_t)k + (size_t)s2];
-                bs->log_norms[b * 8 + (size_t)s2] = scale_log_norm(h_sigmas[b * (size_t)k + (size_t)s2]);
-            }
+        batch_mirror_scales(bs, (size_t)B, k, h_sigmas);
         if (B > bs->scale_cap) {
             dfree(bs->d_sigma); dfree(bs->d_lognorm); bs->scale_cap = 0;      // (hipFree waits for the device: no kernel still writes them)
             HIP_TRY(c, hipMalloc(&bs->d_sigma, B * 8 * sizeof(double)));
@@ -4485,23 +4490,24 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
         if (h_obs) { HIP_TRY(c, hipMemcpyAsync(bs->d_lobs, h_obs, (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream)); d_obs = bs->d_lobs; }
         uint32_t top = 0;
         for (uint64_t b = 0; b < B; ++b) top = std::max(top, h_dT[b]);
+        const dim3 grid((unsigned)B, retable_grid_y(top, (int64_t)B));
+        auto common = [&](auto& r) {                            // (what the two forms' arguments share)
+            r.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+            r.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
+            r.ofirst = bs->d_lfirst; r.means = bs->d_lmeans; r.obs = d_obs;
+            r.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+            r.T_max = bs->T; r.k = bs->hk;
+        };
         if (bs->scaled) {
             BatchLearnRowsScaledArgs rs{};
-            rs.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-            rs.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
-            rs.ofirst = bs->d_lfirst; rs.means = bs->d_lmeans; rs.sigmas = bs->d_sigma; rs.log_norms = bs->d_lognorm; rs.obs = d_obs;
-            rs.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
-            rs.T_max = bs->T; rs.k = bs->hk;
-            hipLaunchKernelGGL(batch_learn_rows_scaled_kernel, dim3((unsigned)B, retable_grid_y(top, (int64_t)B)), dim3(kThreads), 0, c->stream, rs);
+            common(rs);
+            rs.sigmas = bs->d_sigma; rs.log_norms = bs->d_lognorm;
+            hipLaunchKernelGGL(batch_learn_rows_scaled_kernel, grid, dim3(kThreads), 0, c->stream, rs);
         } else {
             BatchLearnRowsArgs ra{};
-            ra.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-            ra.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
-            ra.ofirst = bs->d_lfirst; ra.means = bs->d_lmeans; ra.obs = d_obs;
-            ra.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+            common(ra);
             ra.log_norm = std::log(2 * kPi * 1.0 * 1.0);              // (normal_logpdf's own expression at sigma = 1.0)
-            ra.T_max = bs->T; ra.k = bs->hk;
-            hipLaunchKernelGGL(batch_learn_rows_kernel, dim3((unsigned)B, retable_grid_y(top, (int64_t)B)), dim3(kThreads), 0, c->stream, ra);
+            hipLaunchKernelGGL(batch_learn_rows_kernel, grid, dim3(kThreads), 0, c->stream, ra);
         }
         HIP_TRY(c, hipGetLastError());
         bs->tab_stale = true;
@@ -5632,22 +5638,44 @@ int cpprob_hip_batch_retable_grid(cpprob_hip_ctx* c, uint32_t* grid_y)
     return 0;
 }
 
-int cpprob_hip_batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition)
+// cpprob_hip_batch_mstep_device and -- scaled: the sigmas (and, where given, the log_norms) are fitted too, above sigma_floor --
+// cpprob_hip_batch_mstep_scaled_device.
+static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition, bool scaled, double* d_sigmas,
+                              double* d_log_norm, double sigma_floor)
 {
     LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
-    if (!d_stats || !d_means || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!d_stats || !d_means || !d_transition || (scaled && !d_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (scaled && (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor))) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
     const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kRetableStats;
     if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
     HIP_TRY(c, hipSetDevice(c->device));
-    BatchMstepArgs a{};
-    a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.B = (int64_t)B; a.k = bs->hk;
-    hipLaunchKernelGGL(batch_mstep_kernel, dim3((unsigned)((B * (uint64_t)bs->hk + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    const dim3 grid((unsigned)((B * (uint64_t)bs->hk + kThreads - 1) / kThreads));
+    if (scaled) {
+        BatchMstepScaledArgs a{};
+        a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.sigmas = d_sigmas; a.log_norms = d_log_norm; a.floor = sigma_floor; a.B = (int64_t)B; a.k = bs->hk;
+        hipLaunchKernelGGL(batch_mstep_scaled_kernel, grid, dim3(kThreads), 0, c->stream, a);
+    } else {
+        BatchMstepArgs a{};
+        a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.B = (int64_t)B; a.k = bs->hk;
+        hipLaunchKernelGGL(batch_mstep_kernel, grid, dim3(kThreads), 0, c->stream, a);
+    }
     HIP_TRY(c, hipGetLastError());
     return 0;
+}
+
+int cpprob_hip_batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition)
+{
+    return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, false, nullptr, nullptr, 0.0);
+}
+
+int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition, double* d_sigmas,
+                                         double* d_log_norm, double sigma_floor)
+{
+    return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, true, d_sigmas, d_log_norm, sigma_floor);
 }
 
 // ---- per-state emission scales (csrc/batch_scale.hpp) -----------------------------------------------------------------------------
@@ -5694,31 +5722,9 @@ int cpprob_hip_batch_retable_scaled(cpprob_hip_ctx* c, const double* h_means, co
     HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs, d_sigmas)) return rc;
-    for (size_t b = 0; b < B; ++b) {
-        retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
-        for (size_t s2 = 0; s2 < (size_t)k; ++s2) { bs->sigmas[b * 8 + s2] = h_sigmas[b * (size_t)k + s2]; bs->log_norms[b * 8 + s2] = scale_log_norm(h_sigmas[b * (size_t)k + s2]); }
-    }
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    batch_mirror_scales(bs, B, k, h_sigmas);
     bs->thr_stale = false;
-    return 0;
-}
-
-int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition, double* d_sigmas,
-                                         double* d_log_norm, double sigma_floor)
-{
-    LANES_OWN(c);
-    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
-    BatchState* bs = c->batch;
-    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
-    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
-    if (!d_stats || !d_means || !d_transition || !d_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    if (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor)) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
-    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kRetableStats;
-    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    BatchMstepScaledArgs a{};
-    a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.sigmas = d_sigmas; a.log_norms = d_log_norm; a.floor = sigma_floor; a.B = (int64_t)B; a.k = bs->hk;
-    hipLaunchKernelGGL(batch_mstep_scaled_kernel, dim3((unsigned)((B * (uint64_t)bs->hk + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
-    HIP_TRY(c, hipGetLastError());
     return 0;
 }
 
@@ -5752,10 +5758,8 @@ int cpprob_hip_batch_online_tables_scaled(cpprob_hip_ctx* c, const double* h_mea
     const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
     bs->means.assign(h_means, h_means + B * (size_t)k);
     bs->trans.assign(h_transition, h_transition + B * kk);
-    for (size_t b = 0; b < B; ++b) {
-        retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
-        for (size_t s2 = 0; s2 < (size_t)k; ++s2) { bs->sigmas[b * 8 + s2] = h_sigmas[b * (size_t)k + s2]; bs->log_norms[b * 8 + s2] = scale_log_norm(h_sigmas[b * (size_t)k + s2]); }
-    }
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    batch_mirror_scales(bs, B, k, h_sigmas);
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->d_sigma, bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm, bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));

@@ -822,7 +822,7 @@ int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* ctx, const double* d_st
 /* cpprob_hip_batch_online_tables with h_sigmas [B][k], for a batch begun by cpprob_hip_batch_begin_online_scaled, armed or not (a
  * batch without scales: CPPROB_HIP_ESTATE; cpprob_hip_batch_online_tables likewise returns CPPROB_HIP_ESTATE on a scaled batch). */
 int cpprob_hip_batch_online_tables_scaled(cpprob_hip_ctx* ctx, const double* h_means, const double* h_transition, const double* h_sigmas);
-/* Online EM of a scaled online batch (csrc/batch_learn_scaled.hpp).  cpprob_hip_batch_learn_begin_scaled is
+/* Online EM of a scaled online batch (csrc/batch_learn.hpp).  cpprob_hip_batch_learn_begin_scaled is
  * cpprob_hip_batch_learn_begin for a batch begun by cpprob_hip_batch_begin_online_scaled (a batch without scales: CPPROB_HIP_ESTATE;
  * sigma_floor not finite or not > 0: CPPROB_HIP_EINVAL): the learner then fits the sigmas too.  cpprob_hip_batch_advance_learn* are
  * the unchanged calls; on a scaled batch the rows of the new steps are written on the device from the device-resident means, sigmas

@@ -1,9 +1,9 @@
-// batch_learn_rows_scaled_kernel and batch_learn_scaled_kernel (csrc/batch_learn_scaled.hpp) run as host code over grids given in a
+// batch_learn_rows_scaled_kernel and batch_learn_scaled_kernel (csrc/batch_learn.hpp) run as host code over grids given in a
 // case file (tests/test_batch_learn_scaled_kernel_text_host.py writes it and states the format): every buffer is a heap block of
 // exactly the size the host code would hand the kernels, a launch is a loop over its blocks, a block 256 threads.
-// "batch_learn_scaled_host.hpp" is the kernels' text on top of batch_learn.hpp's and batch_scale.hpp's, with the shims in place of
+// "batch_learn_host.hpp" is the kernels' text on top of batch_onlinestats.hpp's and batch_scale.hpp's, with the shims in place of
 // batch_smc.hpp.  batch_learn_main.cpp with the scales: the sigmas and log_norms [B][8] in and out, the floor and the fit flag.
-#include "batch_learn_scaled_host.hpp"
+#include "batch_learn_host.hpp"
 
 #include <vector>
 

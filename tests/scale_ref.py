@@ -1,7 +1,7 @@
 """csrc/batch_scale.hpp restated in plain Python: the table logarithm, the scaled rows, the scaled check and the scaled M-step.  Every
 operation is one IEEE float64 operation on Python floats (or numpy elementwise), a bit operation, or math.sqrt (correctly rounded); no
 library logarithm is taken.  ScaledLearner is tests/learn_ref.py's Learner with the scaled rows, M-step and check: one problem of a scaled
-learning stream (csrc/batch_learn_scaled.hpp)."""
+learning stream (csrc/batch_learn.hpp)."""
 import math
 import struct
 

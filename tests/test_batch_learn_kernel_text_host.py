@@ -1,7 +1,7 @@
 """batch_learn_rows_kernel and batch_learn_kernel (csrc/batch_learn.hpp) as host code: the translation unit is formed here from the
-text of csrc/batch_smooth.hpp, csrc/batch_onlinestats.hpp, csrc/batch_retable.hpp (as their own kernel-text tests form them) and
-csrc/batch_learn.hpp (its include lines naming those texts), built against tests/host_kernels/batch_smooth_shim.hpp and
-batch_retable_shim.hpp as a stand-alone program with g++ -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined
+text of csrc/batch_smooth.hpp, csrc/batch_onlinestats.hpp, csrc/batch_retable.hpp (as their own kernel-text tests form them),
+csrc/batch_scale.hpp and csrc/batch_learn.hpp (their include lines naming those texts), built against
+tests/host_kernels/batch_smooth_shim.hpp and batch_retable_shim.hpp as a stand-alone program with g++ -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined
 -ffp-contract=off (tests/host_kernels/batch_learn_main.cpp).  Every buffer has exactly the size the host code hands the kernels, the rows
 of the m table no problem has reached AT THAT CALL are NaN, the table region starts as NaN, tau of a problem that has consumed nothing
 is NaN on the way in, and records, tau, tables, threshold words, status words and rows must equal tests/learn_ref.py's (host division
@@ -39,23 +39,28 @@ POISON = 64                                     # a status word nobody has writt
 def _texts():
     smooth, online = KO._texts()
     retable = KR._text()[1]
+    scale = open(os.path.join(CSRC, "batch_scale.hpp")).read()
+    inc = '#include "batch_retable.hpp"'
+    assert scale.count(inc) == 1 and scale.count("#include") == 1
+    scale = scale.replace(inc, '#include "batch_retable_host.hpp"')
     text = open(os.path.join(CSRC, "batch_learn.hpp")).read()
-    incs = ('#include "batch_onlinestats.hpp"', '#include "batch_retable.hpp"')
+    incs = ('#include "batch_onlinestats.hpp"', '#include "batch_scale.hpp"')
     assert all(text.count(i) == 1 for i in incs) and text.count("#include") == 2
-    text = text.replace(incs[0], '#include "batch_onlinestats_host.hpp"').replace(incs[1], '#include "batch_retable_host.hpp"')
-    return {"batch_smooth_host.hpp": smooth, "batch_onlinestats_host.hpp": online, "batch_retable_host.hpp": retable, "batch_learn_host.hpp": text}
+    text = text.replace(incs[0], '#include "batch_onlinestats_host.hpp"').replace(incs[1], '#include "batch_scale_host.hpp"')
+    return {"batch_smooth_host.hpp": smooth, "batch_onlinestats_host.hpp": online, "batch_retable_host.hpp": retable, "batch_scale_host.hpp": scale,
+            "batch_learn_host.hpp": text}
 
 
 def test_text():
-    """fp contract off in every function, no power, no logarithm, no LDS, no barrier, no atomics; the library launches both kernels
-    and leaves batch_smc_kernel's launch to batch_launch."""
+    """fp contract off in every function (the two bodies, learn_row_bits and the four kernels over them), no power, no logarithm, no
+    LDS, no barrier, no atomics; the library launches both kernels and leaves batch_smc_kernel's launch to batch_launch."""
     text = open(os.path.join(CSRC, "batch_learn.hpp")).read()
     code = re.sub(r"//[^\n]*", "", text)
     for word in ("__shared__", "__syncthreads", "atomic", "pow(", "exp("):
         assert word not in code, word
     assert re.search(r"[^_\w]log\s*\(", code) is None and re.search(r"[^_\w]fma\s*\(", code) is None
     bodies = re.findall(r"\n(?:__device__ __forceinline__|__global__)[^\n]*\)\n\{\n(.*?)\n\}\n", code, re.S)
-    assert len(bodies) == 3
+    assert len(bodies) == 7
     for body in bodies:
         assert body.lstrip().startswith("#pragma clang fp contract(off)"), body[:80]
     hip = open(os.path.join(CSRC, "cpprob_hip.hip")).read()

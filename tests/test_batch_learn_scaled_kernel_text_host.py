@@ -1,7 +1,6 @@
-"""batch_learn_rows_scaled_kernel and batch_learn_scaled_kernel (csrc/batch_learn_scaled.hpp) as host code: the translation unit of
-tests/test_batch_learn_kernel_text_host.py with the texts of csrc/batch_scale.hpp and csrc/batch_learn_scaled.hpp on top (their include
-lines naming those texts), built as a stand-alone program with g++ -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined
--ffp-contract=off (tests/host_kernels/batch_learn_scaled_main.cpp).  Records, tau, tables, sigmas, log_norms, threshold words, status
+"""batch_learn_rows_scaled_kernel and batch_learn_scaled_kernel (csrc/batch_learn.hpp: the kScaled instantiations of its two bodies) as
+host code: the translation unit of tests/test_batch_learn_kernel_text_host.py, built as a stand-alone program with g++ -O1
+-fsanitize=address,undefined -fno-sanitize-recover=undefined -ffp-contract=off (tests/host_kernels/batch_learn_scaled_main.cpp).  Records, tau, tables, sigmas, log_norms, threshold words, status
 words and rows must equal tests/scale_ref.py's ScaledLearner on every grid, call after call: the learner's step (c) -- the scale of a
 state with mass, its logarithm only where the scale passes, bit 8 gathered on the rows' lanes -- and the rows from the resident
 scales.  Nothing is loaded into python and nothing runs on a GPU.
@@ -27,36 +26,25 @@ TAU, PROB, POISON, SCHEDULE, T_MIN = KL.TAU, KL.PROB, KL.POISON, KL.SCHEDULE, KL
 FLOOR = 1e-3
 
 
-def _texts():
-    texts = KL._texts()
-    scale = open(os.path.join(CSRC, "batch_scale.hpp")).read()
-    inc = '#include "batch_retable.hpp"'
-    assert scale.count(inc) == 1 and scale.count("#include") == 1
-    texts["batch_scale_host.hpp"] = scale.replace(inc, '#include "batch_retable_host.hpp"')
-    text = open(os.path.join(CSRC, "batch_learn_scaled.hpp")).read()
-    incs = ('#include "batch_learn.hpp"', '#include "batch_scale.hpp"')
-    assert all(text.count(i) == 1 for i in incs) and text.count("#include") == 2
-    texts["batch_learn_scaled_host.hpp"] = text.replace(incs[0], '#include "batch_learn_host.hpp"').replace(incs[1], '#include "batch_scale_host.hpp"')
-    return texts
+_texts = KL._texts
 
 
 def test_text():
-    """fp contract off in both kernels, no power, no library logarithm, no LDS, no barrier, no atomics; steps (a) and (b) are
-    batch_learn_kernel's text; the library launches both kernels."""
-    text = open(os.path.join(CSRC, "batch_learn_scaled.hpp")).read()
+    """fp contract off in every function, no power, no library logarithm, no LDS, no barrier, no atomics; the unit and the scaled
+    learner are one text -- one loop over the problems and one walk over the steps in the file, and each of the four kernels is the
+    pragma and a single call of its body --; the library launches both kernels."""
+    text = open(os.path.join(CSRC, "batch_learn.hpp")).read()
     code = re.sub(r"//[^\n]*", "", text)
     for word in ("__shared__", "__syncthreads", "atomic", "pow(", "exp("):
         assert word not in code, word
     assert re.search(r"[^_\w]log\s*\(", code) is None and re.search(r"[^_\w]fma\s*\(", code) is None
-    bodies = re.findall(r"\n__global__[^\n]*\)\n\{\n(.*?)\n\}\n", code, re.S)
-    assert len(bodies) == 2
-    for body in bodies:
-        assert body.lstrip().startswith("#pragma clang fp contract(off)"), body[:80]
-    unit = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "batch_learn.hpp")).read())
-    cut = lambda c: re.sub(r"[ \t]+\n", "\n", c.split("for (int b = online_uniform(")[1].split("if (done >= T || T < a.t_min) continue;")[0])
-    assert cut(code) == cut(unit), "steps (a) and (b) are the unit learner's statements"
+    assert code.count("for (int b = online_uniform(") == 1 and code.count("for (int t = done; t < T; ++t)") == 1
+    kernels = re.findall(r"\n__global__[^\n]* void (\w+)\([^\n]*\)\n\{\n(.*?)\n\}\n", code, re.S)
+    assert [name for name, _ in kernels] == ["batch_learn_rows_kernel", "batch_learn_rows_scaled_kernel", "batch_learn_kernel", "batch_learn_scaled_kernel"]
+    for (name, body), call in zip(kernels, ("batch_learn_rows_body<false>", "batch_learn_rows_body<true>", "batch_learn_body<false>", "batch_learn_body<true>")):
+        assert re.fullmatch(r"#pragma clang fp contract\(off\)\n\s*" + re.escape(call) + r"\(\w+\);", body.strip()), (name, body)
     hip = open(os.path.join(CSRC, "cpprob_hip.hip")).read()
-    assert '#include "batch_learn_scaled.hpp"' in hip and "hipLaunchKernelGGL(batch_learn_scaled_kernel" in hip and "hipLaunchKernelGGL(batch_learn_rows_scaled_kernel" in hip
+    assert '#include "batch_learn.hpp"' in hip and "hipLaunchKernelGGL(batch_learn_scaled_kernel" in hip and "hipLaunchKernelGGL(batch_learn_rows_scaled_kernel" in hip
 
 
 @pytest.fixture(scope="module")
