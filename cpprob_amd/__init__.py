@@ -11,7 +11,7 @@ from .capi import (ALG_SIS, ALG_SMC, MODEL_GAUSSIAN_README, MODEL_GAUSSIAN_UNKNO
                    SCOPE_GLOBAL, SCOPE_ISLAND, SCOPE_EXCHANGE, Engine, Group, CpprobHipError, load_library)
 
 from . import em  # noqa: F401
-from .em import hmm_table_em, m_step  # noqa: F401
+from .em import hmm_table_em, m_step, pool_stats  # noqa: F401
 from . import online_em  # noqa: F401
 from .online_em import hmm_table_online_em  # noqa: F401
 from . import gibbs  # noqa: F401

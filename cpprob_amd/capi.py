@@ -58,6 +58,7 @@ SYMBOLS = [
     "cpprob_hip_batch_retable_scaled", "cpprob_hip_batch_retable_scaled_device", "cpprob_hip_batch_mstep_scaled_device",
     "cpprob_hip_batch_online_tables_scaled", "cpprob_hip_batch_copy_scales",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
+    "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
 ]
 
 
@@ -410,6 +411,10 @@ def load_library(path=None):
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
+        "cpprob_hip_batch_tie": (C.c_int, [vp, C.POINTER(i32), sz]),
+        "cpprob_hip_batch_tie_get": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32)]),
+        "cpprob_hip_batch_pool_stats": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_int, vp, sz]),
+        "cpprob_hip_batch_pool_stats_device": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_int, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -797,6 +802,42 @@ class Engine:
                                                                   float(sigma_floor)))
         else:
             self._chk(self.L.cpprob_hip_batch_mstep_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans)))
+
+    # ---- tied tables (include/cpprob_hip.h: cpprob_hip_batch_tie, _pool_stats*) --------------------------------------
+    def batch_tie(self, groups):
+        """Partitions the begun batch's problems into groups that share one table (cpprob_hip_batch_tie): groups int [B], ids in
+        0 .. G-1, every id used.  A re-table keeps the tie, any begin forgets it, a second call replaces it."""
+        g = np.ascontiguousarray(groups, np.int32).reshape(-1)
+        self._chk(self.L.cpprob_hip_batch_tie(self.h, g.ctypes.data_as(C.POINTER(C.c_int32)), g.size))
+
+    def batch_tie_get(self):
+        """(groups int32 [B], G) of the begun batch's tie (cpprob_hip_batch_tie_get); without one the call raises (ESTATE)."""
+        G = C.c_int32()
+        self._chk(self.L.cpprob_hip_batch_tie_get(self.h, None, C.byref(G)))
+        g = np.zeros(self.batch_B, np.int32)
+        self._chk(self.L.cpprob_hip_batch_tie_get(self.h, g.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(G)))
+        return g, int(G.value)
+
+    def batch_pool_stats(self, records, per_problem=1, broadcast=True, out=None):
+        """The tied groups' pooled records (cpprob_hip_batch_pool_stats; cpprob_amd.em.pool_stats states the sum): records float64
+        [B, 88] or [B, per_problem, 88] on the host, staged and pooled by the device's kernel.  broadcast=True: the records' shape,
+        every member holding its group's sum; False: [G, ...].  out: a contiguous float64 array to fill (default: a new one).
+        Synchronises."""
+        rec = np.ascontiguousarray(records, np.float64)
+        R = int(per_problem)
+        if out is None:
+            rows = self.batch_B if broadcast else self.batch_tie_get()[1]
+            out = np.zeros((rows, STATS_PER_PROBLEM) if rec.ndim == 2 and R == 1 else (rows, R, STATS_PER_PROBLEM))
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous):
+            raise ValueError("out: a contiguous float64 array")
+        self._chk(self.L.cpprob_hip_batch_pool_stats(self.h, rec.ctypes.data, rec.size, R, 1 if broadcast else 0, out.ctypes.data, out.size))
+        return out
+
+    def batch_pool_stats_device(self, records, out, per_problem=1, broadcast=True):
+        """batch_pool_stats on torch float64 tensors of the engine's device (cpprob_hip_batch_pool_stats_device), enqueued without a
+        host synchronisation: records [B, per_problem, 88] (or [B, 88]), out [B, ...] (broadcast; may be records itself: the pooling
+        is then in place) or [G, ...]."""
+        self._chk(self.L.cpprob_hip_batch_pool_stats_device(self.h, _dptr(records), records.numel(), int(per_problem), 1 if broadcast else 0, _dptr(out), out.numel()))
 
     def batch_scales(self, b, k=None):
         """(sigmas [k], log_norms [k]) of problem b of a batch begun with emission scales, as the device holds them

@@ -32,6 +32,7 @@
 #include "batch_scale.hpp"
 #include "batch_learn.hpp"
 #include "batch_pass_plan.hpp"
+#include "batch_pool.hpp"
 
 using namespace cph;
 
@@ -1148,6 +1149,13 @@ struct BatchState {
     double learn_floor = 0.0;
     std::vector<double> sigmas, log_norms;
     double *d_sigma = nullptr, *d_lognorm = nullptr; size_t scale_cap = 0;
+    // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
+    // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
+    // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
+    bool tied = false;
+    int32_t tie_groups = 0;
+    std::vector<int32_t> tie_map;
+    int32_t* d_tie = nullptr; size_t tie_cap = 0;
     const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
 };
 
@@ -1176,6 +1184,7 @@ void batch_free(cpprob_hip_ctx* c)
     dfree(c->batch->d_cfirst);
     dfree(c->batch->d_rstatus); dfree(c->batch->d_robs);
     dfree(c->batch->d_sigma); dfree(c->batch->d_lognorm);
+    dfree(c->batch->d_tie);
     if (c->batch->pin_cfirst) (void)hipHostFree(c->batch->pin_cfirst);
     for (hipEvent_t e : c->batch->sdesc_done) if (e) (void)hipEventDestroy(e);
     delete c->batch;
@@ -1258,6 +1267,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->decoded.assign(B, 0); bs->lp_ready = false; bs->lp_sent = false;
     bs->ostats_done.assign(B, 0);
     bs->retabled = false; bs->robs_ready = false; bs->tab_stale = false; bs->thr_stale = false; bs->retable_gy = 0;
+    bs->tied = false; bs->tie_groups = 0; bs->tie_map.clear();              // (any begin forgets the tie)
     if (bs->armed) batch_learn_free(bs);
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3, described = h_T != nullptr, own = h_means != nullptr;
     const int spp = hmm3 ? 3 : 8;
@@ -5676,6 +5686,120 @@ int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* c, const double* d_stat
                                          double* d_log_norm, double sigma_floor)
 {
     return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, true, d_sigmas, d_log_norm, sigma_floor);
+}
+
+// ---- tied tables: a partition of the begun batch's problems and the pooled records of its groups (csrc/batch_pool.hpp) -------------
+static_assert(kPoolStats == kSuffStats, "the pooling kernel sums the record of cpprob_hip_batch_smooth_stats");
+
+int cpprob_hip_batch_tie(cpprob_hip_ctx* c, const int32_t* h_group, size_t n)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!h_group) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const size_t B = bs->cfg.n_problems;
+    if (n != B) return fail(c, CPPROB_HIP_EINVAL, "n = " + std::to_string(n) + ", the begun batch has " + std::to_string(B) + " problems");
+    int64_t G = 0;
+    for (size_t b = 0; b < B; ++b) {
+        if (h_group[b] < 0) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + " has the negative group id " + std::to_string(h_group[b]));
+        G = std::max<int64_t>(G, (int64_t)h_group[b] + 1);
+    }
+    if (G > (int64_t)B) return fail(c, CPPROB_HIP_EINVAL, "a group id in 0 .. " + std::to_string(G - 1) + " is unused: every id must occur");
+    // a counting sort by group: within a group the members stay in ascending problem order
+    std::vector<int32_t> h((size_t)B + (size_t)G + 1 + (size_t)B, 0);
+    int32_t *members = h.data(), *first = h.data() + B, *map = first + G + 1;
+    for (size_t b = 0; b < B; ++b) ++first[h_group[b] + 1];
+    for (int64_t g = 0; g < G; ++g) {
+        if (first[g + 1] == 0) return fail(c, CPPROB_HIP_EINVAL, "the group id " + std::to_string(g) + " is unused: every id in 0 .. " + std::to_string(G - 1) + " must occur");
+        first[g + 1] += first[g];
+    }
+    std::vector<int32_t> at(first, first + G);
+    for (size_t b = 0; b < B; ++b) { members[at[(size_t)h_group[b]]++] = (int32_t)b; map[b] = h_group[b]; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    // (a pooling launch of the tie this one replaces may still read the arrays)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bs->tied = false;
+    if (h.size() > bs->tie_cap) {
+        dfree(bs->d_tie); bs->tie_cap = 0;
+        HIP_TRY(c, hipMalloc(&bs->d_tie, h.size() * sizeof(int32_t)));
+        bs->tie_cap = h.size();
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_tie, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bs->tie_map.assign(map, map + B);
+    bs->tie_groups = (int32_t)G;
+    bs->tied = true;
+    return 0;
+}
+
+int cpprob_hip_batch_tie_get(cpprob_hip_ctx* c, int32_t* h_group, int32_t* n_groups)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->tied) return fail(c, CPPROB_HIP_ESTATE, "the begun batch has no tie");
+    if (!n_groups) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (h_group) std::copy(bs->tie_map.begin(), bs->tie_map.end(), h_group);
+    *n_groups = bs->tie_groups;
+    return 0;
+}
+
+// cpprob_hip_batch_pool_stats' arguments against the batch's state; doubles: the records' size, out_doubles: the output's.  It writes nothing.
+static int batch_pool_check(cpprob_hip_ctx* c, const double* records, size_t n_doubles, uint32_t per_problem, int broadcast, const double* out, size_t n_out,
+                            uint64_t& doubles, uint64_t& out_doubles)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->tied) return fail(c, CPPROB_HIP_ESTATE, "the begun batch has no tie: cpprob_hip_batch_tie sets one");
+    if (!records || !out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (per_problem == 0) return fail(c, CPPROB_HIP_EINVAL, "per_problem must be >= 1");
+    const uint64_t B = bs->cfg.n_problems, G = (uint64_t)bs->tie_groups, R = per_problem, per = (uint64_t)kPoolStats * R;
+    if (G * R > (uint64_t)INT32_MAX) return fail(c, CPPROB_HIP_EINVAL, "groups x per_problem = " + std::to_string(G * R) + " is beyond one launch's grid");
+    doubles = B * per;
+    out_doubles = (broadcast ? B : G) * per;
+    if ((uint64_t)n_doubles < doubles) return fail(c, CPPROB_HIP_EINVAL, "the records are too small: " + std::to_string(doubles) + " doubles (88 a problem and record)");
+    if ((uint64_t)n_out < out_doubles) return fail(c, CPPROB_HIP_EINVAL, "the output is too small: " + std::to_string(out_doubles) + " doubles");
+    if (out == records) {
+        if (!broadcast) return fail(c, CPPROB_HIP_EINVAL, "the compact form does not pool in place");
+    } else if (out < records + doubles && records < out + out_doubles)
+        return fail(c, CPPROB_HIP_EINVAL, "the output overlaps the records: in place (d_out == d_records, broadcast) or apart");
+    return 0;
+}
+
+static int batch_pool_enqueue(cpprob_hip_ctx* c, const double* d_records, uint32_t per_problem, int broadcast, double* d_out)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    BatchPoolArgs a{};
+    a.members = bs->d_tie; a.first = bs->d_tie + B;
+    a.rec = d_records; a.out = d_out;
+    a.pairs = (int64_t)bs->tie_groups * (int64_t)per_problem; a.R = (int)per_problem; a.broadcast = broadcast ? 1 : 0;
+    hipLaunchKernelGGL(batch_pool_stats_kernel, dim3((unsigned)((a.pairs + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_pool_stats_device(cpprob_hip_ctx* c, const double* d_records, size_t n_doubles, uint32_t per_problem, int broadcast, double* d_out, size_t n_out)
+{
+    LANES_OWN(c);
+    uint64_t doubles = 0, out_doubles = 0;
+    if (int rc = batch_pool_check(c, d_records, n_doubles, per_problem, broadcast, d_out, n_out, doubles, out_doubles)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_pool_enqueue(c, d_records, per_problem, broadcast, d_out);
+}
+
+int cpprob_hip_batch_pool_stats(cpprob_hip_ctx* c, const double* h_records, size_t n_doubles, uint32_t per_problem, int broadcast, double* h_out, size_t n_out)
+{
+    LANES_OWN(c);
+    uint64_t doubles = 0, out_doubles = 0;
+    if (int rc = batch_pool_check(c, h_records, n_doubles, per_problem, broadcast, h_out, n_out, doubles, out_doubles)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    double *d_rec = nullptr, *d_out = nullptr;
+    if (int rc = batch_stage(c, (size_t)doubles * sizeof(double), (size_t)out_doubles * sizeof(double), d_rec, d_out)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_rec, h_records, (size_t)doubles * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_pool_enqueue(c, d_rec, per_problem, broadcast, d_out)) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_out, d_out, (size_t)out_doubles);
 }
 
 // ---- per-state emission scales (csrc/batch_scale.hpp) -----------------------------------------------------------------------------

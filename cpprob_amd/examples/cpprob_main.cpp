@@ -46,6 +46,10 @@
 //                   state s emits N(means[s], sigmas[s]); the fitted tables are printed with their sigmas as a third list)
 //                   --learn_scales [--scale_floor F] (with --emission_scales and --em_iterations or --online_em: the sigmas are fitted
 //                   too, none below F (0.001); without it they stay)
+//                   --tie_tables / --tie_groups "[g_0 g_1 ..]" (with --em_iterations: tied tables -- all problems, or the problems with
+//                   one group id (ids 0 .. G-1, every id used, one a problem), share one table fitted to all of their observes,
+//                   cpprob::gpu::Options::tie_groups; their input tables must be equal; the output format is unchanged, the members of
+//                   a group print the same fitted table)
 //                   --running_stats (with --batch_tables_file --stream_chunk K: every chunk is followed by the forward-only update of the
 //                   expected sufficient statistics, at the cost of the chunk's steps; after everything else one line a problem, the
 //                   record of the lengths reached in --trajectory_stats' format)
@@ -79,6 +83,8 @@ struct Args {
     std::size_t em_iterations = 0;            // --batch_tables_file: fit the tables by this many iterations of particle EM (0: none)
     bool emission_scales = false;             // --batch_tables_file: every line carries [sigmas] behind [means]: per-state emission scales
     std::string conditional_paths_file;       // --batch_tables_file: the reference paths of a conditional run, one line a problem (empty: none)
+    bool tie_tables = false;                  // --em_iterations: all problems share one fitted table
+    std::string tie_groups;                   // --em_iterations: "[g_0 g_1 ..]", the problems with one id share one fitted table (empty: none)
 };
 
 void print_json(const cpprob::gpu::Result& r)
@@ -291,6 +297,17 @@ int execute_batch_tables(const Args& a)
     std::vector<cpprob::gpu::HmmTable> fitted;
     const std::string dump_prefix = a.model_folder + "/" + a.generated_file + "_smc";
     if (a.batch_dump && a.stream_chunk == 0) cpprob::gpu::options().batch_dump_file = dump_prefix;
+    if (a.tie_tables) cpprob::gpu::options().tie_groups.assign(tables.size(), 0);
+    else if (!a.tie_groups.empty()) {
+        std::string ids = a.tie_groups;
+        for (char& ch : ids) if (ch == '[' || ch == ']' || ch == ',') ch = ' ';
+        std::istringstream gs(ids);
+        std::vector<std::int32_t>& tie = cpprob::gpu::options().tie_groups;
+        tie.clear();
+        for (long g; gs >> g;) tie.push_back(static_cast<std::int32_t>(g));
+        if (!gs.eof()) { std::cerr << "--tie_groups: the list holds something that is no integer." << std::endl; return EXIT_FAILURE; }
+        if (tie.size() != tables.size()) { std::cerr << "--tie_groups: " << tie.size() << " ids for " << tables.size() << " problems." << std::endl; return EXIT_FAILURE; }
+    }
     if (a.em_iterations) {
         cpprob::gpu::HmmTableFit fit = cpprob::gpu::hmm_table_fit(tables, observes, std::vector<std::size_t>{a.n_samples}, seeds, a.em_iterations);
         res = std::move(fit.results);
@@ -400,6 +417,8 @@ int main(int argc, char** argv)
         else if (f == "--stream_chunk") a.stream_chunk = std::stoull(next());    // --batch_tables_file: the observes arrive this many at a time
         else if (f == "--em_on_device") opt.fit_on_device = true;                  // --em_iterations: one begin, then cpprob_hip_batch_retable an iteration
         else if (f == "--em_iterations") a.em_iterations = std::stoull(next());  // --batch_tables_file: particle EM on the tables (cpprob::gpu::hmm_table_fit)
+        else if (f == "--tie_tables") a.tie_tables = true;                         // --em_iterations: every problem in one group (cpprob::gpu::Options::tie_groups)
+        else if (f == "--tie_groups") a.tie_groups = next();                       // --em_iterations: "[0 0 1 1]", one group id a problem
         else if (f == "--batch_dump") a.batch_dump = true;                         // the batch modes: problem b's traces as <generated_file>_smc_<b>.int / .ids
         else if (f == "--backward_smoothing") opt.backward_smoothing = true;      // the batch modes: statistics from the backward smoother (cpprob_hip_batch_smooth)
         else if (f == "--smoothing_lag") opt.smoothing_lag = std::stol(next());    // the batch modes: fixed-lag marginals (cpprob_hip_batch_smooth_lag)
@@ -450,6 +469,11 @@ int main(int argc, char** argv)
         std::cerr << "--learn_scales fits the sigmas of --emission_scales: set it with --em_iterations or --online_em" << std::endl;
         return EXIT_FAILURE;
     }
+    if ((a.tie_tables || !a.tie_groups.empty()) && a.em_iterations == 0) {
+        std::cerr << "--tie_tables / --tie_groups tie the tables of a fit: set --em_iterations" << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (a.tie_tables && !a.tie_groups.empty()) { std::cerr << "--tie_tables is --tie_groups of all zeros: set one of them" << std::endl; return EXIT_FAILURE; }
     if (opt.fit_on_device && a.em_iterations == 0) { std::cerr << "--em_on_device re-tables the batch of a fit: set --em_iterations" << std::endl; return EXIT_FAILURE; }
     if ((opt.forecast_horizon || opt.forecast_trajectories) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {
         std::cerr << "--forecast serves the batch modes: set --batch_observes_file or --batch_tables_file" << std::endl;

@@ -43,8 +43,22 @@ def sample_tables(stats, k, rng, alpha=1.0, mu0=0.0, tau0=10.0, sigmas=None, a0=
     return means, trans, np.sqrt(rate / rng.standard_gamma(a0 + occ / 2))
 
 
+def draw_tables(one, k, rng, sigmas, tie, prior):
+    """A sweep's draw of the tables from the chains' records `one` (trajectory axis indexed away).  tie: None, or
+    em.check_tied_start's (groups, G, first members) -- the records are then pooled over each group (em.pool_stats, compact), one
+    sample_tables call on the G records draws one table a group, so the generator is consumed at shape [G, ...], and the draw is
+    expanded to the members.  Returns sample_tables' tuple at shape [B, ...]."""
+    if tie is None:
+        return sample_tables(one, k, rng, **prior) if sigmas is None else sample_tables(one, k, rng, sigmas=sigmas, **prior)
+    from .em import pool_stats
+    groups, _, lead = tie
+    pooled = pool_stats(one, groups, broadcast=False)
+    drawn = sample_tables(pooled, k, rng, **prior) if sigmas is None else sample_tables(pooled, k, rng, sigmas=sigmas[lead], **prior)
+    return tuple(a[groups] for a in drawn)
+
+
 def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps, rng, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, retable=False, sigmas0=None,
-                    **prior):
+                    groups=None, **prior):
     """Batched Gibbs sampling of the tables, one chain a problem.  observes: a list of B 1-D sequences, or one sequence every chain
     shares; means0 [B, k], trans0 [B, k, k] the chains' initial tables; seeds [B]; rng a numpy Generator; prior: sample_tables' alpha,
     mu0, tau0.  Sweep i begins a batch with the current tables (batch_begin_problems), runs it with seeds + i, takes the statistics of
@@ -61,7 +75,12 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
     retained path (conditional SMC): nothing here corrects that error at finite n_particles.
 
     sigmas0 [B, k]: the chains carry per-state emission scales, sampled with the rest (sample_tables with sigmas; prior: its a0, b0);
-    a fourth array, sigmas [sweeps + 1, B, k], is returned behind the three."""
+    a fourth array, sigmas [sweeps + 1, B, k], is returned behind the three.
+
+    groups int [B]: tied tables -- the chains of a group share one table, drawn from the posterior given all of their trajectories
+    (draw_tables: the sweep's records pooled over each group, G tables drawn, expanded to the members).  The members' initial tables
+    must be equal bit for bit (ValueError naming the group); every member keeps its own trajectory; the returned shapes stay, with
+    and without retable=True."""
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
     B, k = means.shape
@@ -72,6 +91,10 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
         raise ValueError("one sequence per table (or one for all)")
     sd = np.ascontiguousarray(seeds, np.uint64)
     sigmas = None if sigmas0 is None else np.array(sigmas0, np.float64)
+    tie = None
+    if groups is not None:
+        from .em import check_tied_start
+        tie = check_tied_start(groups, means, trans, sigmas)
     m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(sweeps), B))
     s_hist = None if sigmas is None else [sigmas.copy()]
     for i in range(int(sweeps)):
@@ -86,9 +109,9 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
         ev[i] = [s["log_evidence"] for s in engine.batch_results()[0]]
         one = {name: v[:, 0] for name, v in stats.items()}
         if sigmas is None:
-            means, trans = sample_tables(one, k, rng, **prior)
+            means, trans = draw_tables(one, k, rng, None, tie, prior)
         else:
-            means, trans, sigmas = sample_tables(one, k, rng, sigmas=sigmas, **prior)
+            means, trans, sigmas = draw_tables(one, k, rng, sigmas, tie, prior)
             s_hist.append(sigmas.copy())
         m_hist.append(means.copy())
         t_hist.append(trans.copy())

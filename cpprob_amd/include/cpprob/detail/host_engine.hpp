@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <iomanip>
 #include <limits>
@@ -986,6 +987,10 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // Tables with emission scales (HmmTable::sigmas): the batches are scaled; options().learn_scales: the M-step fits the scales too -- a
 // state with mass takes v = occ_yy[s] / occ[s] - means[s] means[s] (its new mean) and sigmas[s] = sqrt(v) where v >= scale_floor^2, else
 // options().scale_floor (a NaN v too), the statements of cpprob_hip_batch_mstep_scaled_device.  Without it the scales stay.
+// options().tie_groups (one group id a problem): tied tables -- every begun batch is tied (cpprob_hip_batch_tie; once with
+// fit_on_device, a re-table keeps the tie) and an iteration's records go through cpprob_hip_batch_pool_stats (broadcast) in front of
+// the M-step's statements, which are unchanged: the members of a group, which must start from one table bit for bit (else
+// std::runtime_error naming the group), hold one table throughout, fitted to all of their observes.
 struct HmmTableFit { std::vector<HmmTable> tables; std::vector<Result> results; };
 
 inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std::vector<std::vector<double>>& observes, const std::vector<std::size_t>& n,
@@ -999,20 +1004,46 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
     HmmTableFit fit;
     ContextLease lease(options().device);
     Context& ctx = *lease;
-    std::vector<double> rec(B * R);
+    std::vector<double> rec(B * R), pooled(options().tie_groups.empty() ? 0 : B * R);
     std::vector<std::uint64_t> keys(B);
     const bool kept = options().fit_on_device;                 // the batch of iteration 0 is re-tabled from then on
     const bool fit_scales = options().learn_scales;
     const double floor = options().scale_floor;
     if (fit_scales && pk.sigmas.empty()) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().learn_scales fits emission scales: give every table its sigmas");
     if (fit_scales && (!(floor > 0.0) || !std::isfinite(floor))) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().scale_floor must be finite and > 0");
+    const std::vector<std::int32_t>& tie = options().tie_groups;
+    if (!tie.empty()) {
+        // a group's members start from one table, bit for bit; lead[g]: the group's first member
+        if (tie.size() != B) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().tie_groups holds " + std::to_string(tie.size()) + " ids for " + std::to_string(B) + " problems");
+        std::vector<std::size_t> lead;
+        for (std::size_t b = 0; b < B; ++b) {
+            if (tie[b] < 0) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().tie_groups: the group id of problem " + std::to_string(b) + " is negative");
+            const std::size_t g = static_cast<std::size_t>(tie[b]);
+            if (g >= lead.size()) lead.resize(g + 1, B);
+            if (lead[g] == B) { lead[g] = b; continue; }
+            const std::size_t a = lead[g];
+            const bool same = std::memcmp(&pk.means[a * k], &pk.means[b * k], k * sizeof(double)) == 0 &&
+                              std::memcmp(&pk.trans[a * k * k], &pk.trans[b * k * k], k * k * sizeof(double)) == 0 &&
+                              (pk.sigmas.empty() || std::memcmp(&pk.sigmas[a * k], &pk.sigmas[b * k], k * sizeof(double)) == 0);
+            if (!same)
+                throw std::runtime_error("cpprob::gpu::hmm_table_fit: group " + std::to_string(g) + ": the initial table of problem " + std::to_string(b) +
+                                         " differs from that of problem " + std::to_string(a) + "; a group's members start from one table");
+        }
+    }
     std::size_t runs = 0;
     for (std::size_t it = 0; it < iterations; ++it) {
         for (std::size_t b = 0; b < B; ++b) keys[b] = seeds[b] + it;
         fit.results = run_hmm_table_problems(ctx, pk, keys, it + 1 == iterations, false, nullptr, kept && runs > 0, runs == 1);
+        // (a fresh begin has forgotten the tie, a re-table keeps it)
+        if (!tie.empty() && (!kept || runs == 0)) ctx.check(cpprob_hip_batch_tie(ctx.get(), tie.data(), tie.size()), "cpprob_hip_batch_tie");
         ++runs;
         ctx.check(cpprob_hip_batch_smooth_stats(ctx.get(), pk.flat.empty() ? nullptr : pk.flat.data(), pk.flat.size(), rec.data(), rec.size()),
                   "cpprob_hip_batch_smooth_stats");
+        if (!tie.empty()) {
+            // every member's record becomes its group's pooled record: the M-step below then gives the members one table
+            ctx.check(cpprob_hip_batch_pool_stats(ctx.get(), rec.data(), rec.size(), 1, 1, pooled.data(), pooled.size()), "cpprob_hip_batch_pool_stats");
+            rec.swap(pooled);
+        }
         for (std::size_t b = 0; b < B; ++b) {
             const double* r = rec.data() + b * R;
             for (std::size_t s = 0; s < k; ++s) {

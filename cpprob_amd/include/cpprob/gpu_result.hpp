@@ -81,6 +81,10 @@ struct Options {
                                                       // bit.  This host layer owns no device memory, so an iteration's record (88 doubles a problem)
                                                       // and its M-step still cross the host; cpprob_amd.hmm_table_em(resident=True) keeps both on the
                                                       // device (cpprob_hip_batch_mstep_device, _retable_device)
+    std::vector<std::int32_t> tie_groups;             // hmm_table_fit: not empty = tied tables -- tie_groups[b] in 0 .. G-1 is problem b's group (every id
+                                                      // used), the problems of a group share one table fitted to all of their observes: an iteration's
+                                                      // records are pooled over each group on the device (cpprob_hip_batch_tie, _pool_stats) in front of
+                                                      // the unchanged M-step.  A group's members must start from one table, bit for bit.  Empty: off
     std::vector<std::vector<int>> conditional_paths;  // hmm_table_batch with keep_history = false and keep_masses: not empty = the run is the conditional
                                                       // SMC run (cpprob_hip_batch_run_conditional), problem b's retained particle following
                                                       // conditional_paths[b] (one state a step).  It keeps masses, not books: what comes from

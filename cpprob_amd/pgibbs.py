@@ -5,7 +5,7 @@ the device, in one of two buffers, and only its complete-data sufficient statist
 import numpy as np
 
 from .capi import MODEL_HMM_TABLE, batch_smooth_layout
-from .gibbs import sample_tables
+from .gibbs import draw_tables
 
 
 def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps, rng, **prior):
@@ -21,6 +21,9 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     (batch_retable: the tables drawn on the host, the observes uploaded once) in place of a fresh begin -- the same chain bit for bit.
     sigmas0 [B, k] (a keyword likewise, default None): the chains carry per-state emission scales, sampled with the rest
     (sample_tables with sigmas; prior: its a0, b0), and a third array, sigmas [sweeps + 1, B, k], is returned behind the two.
+    groups int [B] (a keyword likewise, default None): tied tables -- the chains of a group share one table, drawn given all of
+    their trajectories (gibbs.draw_tables); the members' initial tables must be equal bit for bit (ValueError naming the group), and
+    every member keeps its own trajectory and its own retained path.
 
     This is particle Gibbs with backward sampling: a conditional SMC run with multinomial resampling, its retained particle the
     previous trajectory, followed by backward simulation.  That kernel leaves the smoothing law of the states given the tables
@@ -30,6 +33,7 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     import torch
     retable = bool(prior.pop("retable", False))
     sigmas0 = prior.pop("sigmas0", None)
+    groups = prior.pop("groups", None)
     sigmas = None if sigmas0 is None else np.array(sigmas0, np.float64)
     s_hist = None if sigmas is None else [sigmas.copy()]
     means = np.array(means0, np.float64)
@@ -41,6 +45,10 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     if len(seqs) != B:
         raise ValueError("one sequence per table (or one for all)")
     sd = np.ascontiguousarray(seeds, np.uint64)
+    tie = None
+    if groups is not None:
+        from .em import check_tied_start
+        tie = check_tied_start(groups, means, trans, sigmas)
     total = int(batch_smooth_layout([len(o) for o in seqs], 1)[-1])
     traj = [torch.empty(total, dtype=torch.int8, device="cuda:%d" % engine.device) for _ in range(2)]
     m_hist, t_hist = [means.copy()], [trans.copy()]
@@ -58,9 +66,9 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
         stats = engine.batch_traj_stats(1, draw_index=i % (1 << 16), observes=seqs)
         one = {name: v[:, 0] for name, v in stats.items()}
         if sigmas is None:
-            means, trans = sample_tables(one, k, rng, **prior)
+            means, trans = draw_tables(one, k, rng, None, tie, prior)
         else:
-            means, trans, sigmas = sample_tables(one, k, rng, sigmas=sigmas, **prior)
+            means, trans, sigmas = draw_tables(one, k, rng, sigmas, tie, prior)
             s_hist.append(sigmas.copy())
         m_hist.append(means.copy())
         t_hist.append(trans.copy())

@@ -839,6 +839,32 @@ int cpprob_hip_batch_learn_tables_scaled_device(cpprob_hip_ctx* ctx, double* d_m
  * CPPROB_HIP_ESTATE: no batch begun, or a batch without scales.  For tests. */
 int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* ctx, uint64_t problem, double* h_sigmas, double* h_log_norm);
 
+/* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
+ * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
+ * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
+ * tie on the device in arrays of its own -- the members sorted by (group, problem), the groups' first positions [G + 1], the map [B] --;
+ * no workspace region is added.  A re-table keeps the tie, any begin forgets it, a second call replaces it.  CPPROB_HIP_ESTATE: no
+ * batch is begun; CPPROB_HIP_EINVAL with nothing changed: n is not the batch's number of problems, an id is negative, an id in
+ * 0 .. G-1 is unused.  Synchronises. */
+int cpprob_hip_batch_tie(cpprob_hip_ctx* ctx, const int32_t* h_group, size_t n);
+/* The tie in force: h_group [B] (may be NULL) and the number of groups.  CPPROB_HIP_ESTATE without a tie.  Host only. */
+int cpprob_hip_batch_tie_get(cpprob_hip_ctx* ctx, int32_t* h_group, int32_t* n_groups);
+/* The groups' pooled records.  d_records [B][R][88], R = per_problem >= 1 (R = 1: the records of cpprob_hip_batch_smooth_stats and
+ * _online_stats; R = n_traj: those of _traj_stats).  For a group g with the members b_0 < b_1 < ..., every r < R and entry e < 88:
+ *   pooled[g][r][e] = (((0.0 + rec[b_0][r][e]) + rec[b_1][r][e]) + ...)
+ * one addition a member, in ascending problem order, from 0.0, nothing contracted; all 88 entries whatever the batch's k.
+ * broadcast = 0: d_out is [G][R][88]; broadcast = 1: d_out is [B][R][88] and every member of g receives pooled[g] -- the record
+ * cpprob_hip_batch_mstep_device then turns into one table a group, held by every member alike.  d_out == d_records is allowed with
+ * broadcast = 1 (a resident fit pools in place); any other overlap is CPPROB_HIP_EINVAL.  CPPROB_HIP_EINVAL with nothing written:
+ * n_doubles < 88 B R, n_out too small, R == 0, G R beyond what one launch's grid holds.  CPPROB_HIP_ESTATE: no begun batch, or no
+ * tie.  It needs no run: it reads the caller's records and the tie.  The device form is enqueued on the context's stream without a
+ * host synchronisation, under cpprob_hip_batch_smooth_stats_device's stream contract; the host form stages h_records, runs the same
+ * kernel and synchronises.  cpprob_amd.em.pool_stats states the sum in numpy. */
+int cpprob_hip_batch_pool_stats_device(cpprob_hip_ctx* ctx, const double* d_records, size_t n_doubles, uint32_t per_problem, int broadcast,
+                                       double* d_out, size_t n_out);
+int cpprob_hip_batch_pool_stats(cpprob_hip_ctx* ctx, const double* h_records, size_t n_doubles, uint32_t per_problem, int broadcast,
+                                double* h_out, size_t n_out);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
