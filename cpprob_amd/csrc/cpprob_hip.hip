@@ -4148,48 +4148,7 @@ int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg
     return 0;
 }
 
-static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, int32_t k_in, const double* h_means, const double* h_transition, int& k);
-
-int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
-                                    const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition)
-{
-    LANES_OWN(c);
-    if (!c || !cfg || !h_T || !h_n || !h_obs) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    std::string msg;
-    BatchProblemsShape sh;
-    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
-    int k = 0;
-    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
-    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition);
-}
-
-// The scales of a batch of problems (cpprob_hip_batch_begin_problems_scaled, _begin_online_scaled, _retable_scaled, _online_tables_scaled):
-// per problem and state what scale_check's bit 8 demands (csrc/batch_scale.hpp).
-static int batch_check_scales(cpprob_hip_ctx* c, uint64_t B, int k, const double* h_sigmas)
-{
-    for (uint64_t b = 0; b < B; ++b)
-        for (int s2 = 0; s2 < k; ++s2)
-            if (scale_bad(h_sigmas[b * (size_t)k + (size_t)s2]))
-                return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": emission scales must be finite and > 0, with a normal finite 2 pi sigma^2");
-    return 0;
-}
-
-int cpprob_hip_batch_begin_problems_scaled(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
-                                           const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition, const double* h_sigmas)
-{
-    LANES_OWN(c);
-    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "emission scales serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
-    std::string msg;
-    BatchProblemsShape sh;
-    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
-    int k = 0;
-    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
-    if (int rc = batch_check_scales(c, cfg->n_problems, k, h_sigmas)) return rc;
-    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition, nullptr, h_sigmas);
-}
-
-// The tables of a batch of problems (cpprob_hip_batch_begin_problems, _begin_online): per problem, or the context's; k = the states.
+// The tables of a batch of problems (the described begins, re-table and online tables): per problem, or the context's; k = the states.
 static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, int32_t k_in, const double* h_means, const double* h_transition, int& k)
 {
     const uint64_t B = cfg->n_problems;
@@ -4214,6 +4173,48 @@ static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* 
         }
     }
     return 0;
+}
+
+// The scales of a batch of problems (the scaled begins, re-table and online tables): per problem and state what scale_check's bit 8
+// demands (csrc/batch_scale.hpp).
+static int batch_check_scales(cpprob_hip_ctx* c, uint64_t B, int k, const double* h_sigmas)
+{
+    for (uint64_t b = 0; b < B; ++b)
+        for (int s2 = 0; s2 < k; ++s2)
+            if (scale_bad(h_sigmas[b * (size_t)k + (size_t)s2]))
+                return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": emission scales must be finite and > 0, with a normal finite 2 pi sigma^2");
+    return 0;
+}
+
+// The four begins over described problems (cpprob_hip_batch_begin_problems, _begin_online and their _scaled forms).  h_obs given: a begin
+// over problems of h_T observes each; h_seeds given: an online begin of capacities h_T.  scaled: the call carries emission scales, which
+// serve per-problem tables alone.
+static int batch_begin_described(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs, int32_t k_in,
+                                 const double* h_means, const double* h_transition, const double* h_sigmas, const uint64_t* h_seeds, bool scaled)
+{
+    if (!c || !cfg || !h_T || !h_n || (!h_obs && !h_seeds) || (scaled && (!h_means || !h_transition || !h_sigmas))) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (scaled && cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "emission scales serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    int k = 0;
+    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
+    if (scaled) if (int rc = batch_check_scales(c, cfg->n_problems, k, h_sigmas)) return rc;
+    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition, h_seeds, h_sigmas);
+}
+
+int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                    const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition)
+{
+    LANES_OWN(c);
+    return batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, h_means, h_transition, nullptr, nullptr, false);
+}
+
+int cpprob_hip_batch_begin_problems_scaled(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                           const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition, const double* h_sigmas)
+{
+    LANES_OWN(c);
+    return batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, h_means, h_transition, h_sigmas, nullptr, true);
 }
 
 // One launch over the begun batch: every problem from step 0 (cpprob_hip_batch_run), or its piece (cpprob_hip_batch_advance).
@@ -4381,28 +4382,14 @@ int cpprob_hip_batch_begin_online(cpprob_hip_ctx* c, const cpprob_hip_batch_conf
                                   int32_t k_in, const double* h_means, const double* h_transition, const uint64_t* h_seeds)
 {
     LANES_OWN(c);
-    if (!c || !cfg || !h_Tcap || !h_n || !h_seeds) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    std::string msg;
-    BatchProblemsShape sh;
-    if (int rc = batch_check_problems(cfg, h_Tcap, h_n, sh, msg)) return fail(c, rc, msg);
-    int k = 0;
-    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
-    return batch_begin(c, cfg, (size_t)sh.T_max, h_Tcap, h_n, nullptr, k, h_means, h_transition, h_seeds);
+    return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_means, h_transition, nullptr, h_seeds, false);
 }
 
 int cpprob_hip_batch_begin_online_scaled(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
                                          int32_t k_in, const double* h_means, const double* h_transition, const double* h_sigmas, const uint64_t* h_seeds)
 {
     LANES_OWN(c);
-    if (!c || !cfg || !h_Tcap || !h_n || !h_seeds || !h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "emission scales serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
-    std::string msg;
-    BatchProblemsShape sh;
-    if (int rc = batch_check_problems(cfg, h_Tcap, h_n, sh, msg)) return fail(c, rc, msg);
-    int k = 0;
-    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
-    if (int rc = batch_check_scales(c, cfg->n_problems, k, h_sigmas)) return rc;
-    return batch_begin(c, cfg, (size_t)sh.T_max, h_Tcap, h_n, nullptr, k, h_means, h_transition, h_seeds, h_sigmas);
+    return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_means, h_transition, h_sigmas, h_seeds, true);
 }
 
 static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs);
@@ -5524,7 +5511,7 @@ int cpprob_hip_batch_pass_grid(cpprob_hip_ctx* c, uint32_t* decode_forward_grid_
 // ---- re-tabling a begun batch (csrc/batch_retable.hpp) -----------------------------------------------------------------------------
 static_assert(kRetableStats == kSuffStats, "the M-step reads the record of cpprob_hip_batch_smooth_stats");
 // What a re-table needs of the batch's state, then n_observes against the lengths; nothing is enqueued before it has passed.
-static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, bool scaled = false)
+static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, bool scaled)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
@@ -5540,9 +5527,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, bool scaled
     return 0;
 }
 
-// Enqueues the first entries (once a begin) and the launch; the batch then stands as after a begin.  Waits for nothing but, where the
-// status words have to grow, for the calls before it.
-static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs, const double* d_sigmas = nullptr)
+// Enqueues the first entries (once a begin) and the launch (d_sigmas given: a scaled batch's); the batch then stands as after a begin.
+// Waits for nothing but, where the status words have to grow, for the calls before it.
+static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs, const double* d_sigmas)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
@@ -5554,28 +5541,25 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
     }
     if (int rc = batch_first_entries(c)) return rc;
     const unsigned gy = retable_grid_y(bs->T, (int64_t)B);
+    auto common = [&](auto& r) {                                // (what the two forms' arguments share)
+        r.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
+        r.first = bs->d_cfirst;
+        r.means = d_means; r.trans = d_trans; r.obs = d_obs;
+        r.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+        r.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
+        r.status = bs->d_rstatus;
+        r.T_max = bs->T; r.k = bs->hk;
+    };
     if (d_sigmas) {
         // (a scaled batch; the sigmas and log_norms in force are the device's from here on)
         BatchRetableScaledArgs sa{};
-        sa.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-        sa.first = bs->d_cfirst;
-        sa.means = d_means; sa.sigmas = d_sigmas; sa.trans = d_trans; sa.obs = d_obs;
-        sa.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
-        sa.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
-        sa.status = bs->d_rstatus;
-        sa.sigma_out = bs->d_sigma; sa.log_norm_out = bs->d_lognorm;
-        sa.T_max = bs->T; sa.k = bs->hk;
+        common(sa);
+        sa.sigmas = d_sigmas; sa.sigma_out = bs->d_sigma; sa.log_norm_out = bs->d_lognorm;
         hipLaunchKernelGGL(batch_retable_scaled_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, sa);
     } else {
         BatchRetableArgs a{};
-        a.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-        a.first = bs->d_cfirst;
-        a.means = d_means; a.trans = d_trans; a.obs = d_obs;
-        a.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
-        a.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
-        a.status = bs->d_rstatus;
+        common(a);
         a.log_norm = std::log(2 * kPi * 1.0 * 1.0);               // (normal_logpdf's own expression at sigma = 1.0)
-        a.T_max = bs->T; a.k = bs->hk;
         hipLaunchKernelGGL(batch_retable_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
     }
     HIP_TRY(c, hipGetLastError());
@@ -5587,45 +5571,82 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
     return 0;
 }
 
+// The two device forms (scaled: cpprob_hip_batch_retable_scaled_device, whose d_sigmas a unit call does not have): enqueued, no wait.
+static int batch_retable_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_sigmas, const double* d_observes, size_t n_observes,
+                                bool scaled)
+{
+    if (int rc = batch_retable_check(c, n_observes, scaled)) return rc;
+    if (!d_means || !d_transition || (scaled && !d_sigmas) || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_means, d_transition, d_observes, d_sigmas);
+}
+
+// The observes of a host re-table in the buffer of the context's own, where a later re-table without observes finds them.
+static int batch_retable_observes(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes)
+{
+    BatchState* bs = c->batch;
+    if (n_observes > bs->robs_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));           // (an earlier re-table may still read the buffer this replaces)
+        dfree(bs->d_robs); bs->robs_cap = 0; bs->robs_ready = false;
+        HIP_TRY(c, hipMalloc(&bs->d_robs, n_observes * sizeof(double)));
+        bs->robs_cap = n_observes;
+    }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_robs, h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    bs->robs_ready = true;
+    return 0;
+}
+
+// The two host forms (scaled: cpprob_hip_batch_retable_scaled): the tables are validated with the begin's own statements, staged -- the
+// means, a scaled batch's sigmas behind them, in front; the transition rows at the back -- and re-tabled as by the device form.
+static int batch_retable_host(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, const double* h_observes, size_t n_observes,
+                              bool scaled)
+{
+    if (int rc = batch_retable_check(c, n_observes, scaled)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_means || !h_transition || (scaled && !h_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    int k = 0;
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    if (scaled) if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
+    if (h_observes) if (int rc = batch_retable_observes(c, h_observes, n_observes)) return rc;
+    double *d_means = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round((scaled ? 2 : 1) * B * (size_t)k * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
+    double* d_sigmas = scaled ? d_means + B * (size_t)k : nullptr;
+    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (scaled) HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs, d_sigmas)) return rc;
+    // the host knows the tables: the thresholds' mirror is current again (the rows' is not: cpprob_hip_batch_copy_store fetches its row)
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    if (scaled) batch_mirror_scales(bs, B, k, h_sigmas);
+    bs->thr_stale = false;
+    return 0;
+}
+
 int cpprob_hip_batch_retable_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_observes, size_t n_observes)
 {
     LANES_OWN(c);
-    if (int rc = batch_retable_check(c, n_observes)) return rc;
-    if (!d_means || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return batch_retable_enqueue(c, d_means, d_transition, d_observes);
+    return batch_retable_device(c, d_means, d_transition, nullptr, d_observes, n_observes, false);
+}
+
+int cpprob_hip_batch_retable_scaled_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_sigmas, const double* d_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    return batch_retable_device(c, d_means, d_transition, d_sigmas, d_observes, n_observes, true);
 }
 
 int cpprob_hip_batch_retable(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_observes, size_t n_observes)
 {
     LANES_OWN(c);
-    if (int rc = batch_retable_check(c, n_observes)) return rc;
-    BatchState* bs = c->batch;
-    if (!h_means || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
-    int k = 0;
-    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
-    if (h_observes) {
-        if (n_observes > bs->robs_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (an earlier re-table may still read the buffer this replaces)
-            dfree(bs->d_robs); bs->robs_cap = 0; bs->robs_ready = false;
-            HIP_TRY(c, hipMalloc(&bs->d_robs, n_observes * sizeof(double)));
-            bs->robs_cap = n_observes;
-        }
-        HIP_TRY(c, hipMemcpyAsync(bs->d_robs, h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        bs->robs_ready = true;
-    }
-    double *d_means = nullptr, *d_trans = nullptr;
-    if (int rc = batch_stage(c, batch_round(B * (size_t)k * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs)) return rc;
-    // the host knows the tables: the thresholds' mirror is current again (the rows' is not: cpprob_hip_batch_copy_store fetches its row)
-    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
-    bs->thr_stale = false;
-    return 0;
+    return batch_retable_host(c, h_means, h_transition, nullptr, h_observes, n_observes, false);
+}
+
+int cpprob_hip_batch_retable_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    return batch_retable_host(c, h_means, h_transition, h_sigmas, h_observes, n_observes, true);
 }
 
 int cpprob_hip_batch_retable_status(cpprob_hip_ctx* c, int32_t* h_status)
@@ -5802,55 +5823,8 @@ int cpprob_hip_batch_pool_stats(cpprob_hip_ctx* c, const double* h_records, size
     return batch_fetch(c, nullptr, nullptr, 0, h_out, d_out, (size_t)out_doubles);
 }
 
-// ---- per-state emission scales (csrc/batch_scale.hpp) -----------------------------------------------------------------------------
-static int batch_learn_check(cpprob_hip_ctx* c, const char* who);
-
+// ---- emission scales: the logarithm their tables are built with, and the scales in force (csrc/batch_scale.hpp) --------------------
 double cpprob_hip_table_log(double x) { return table_log(x); }
-
-int cpprob_hip_batch_retable_scaled_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_sigmas, const double* d_observes, size_t n_observes)
-{
-    LANES_OWN(c);
-    if (int rc = batch_retable_check(c, n_observes, true)) return rc;
-    if (!d_means || !d_transition || !d_sigmas || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return batch_retable_enqueue(c, d_means, d_transition, d_observes, d_sigmas);
-}
-
-int cpprob_hip_batch_retable_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, const double* h_observes, size_t n_observes)
-{
-    LANES_OWN(c);
-    if (int rc = batch_retable_check(c, n_observes, true)) return rc;
-    BatchState* bs = c->batch;
-    if (!h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
-    int k = 0;
-    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
-    if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
-    if (h_observes) {
-        if (n_observes > bs->robs_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (an earlier re-table may still read the buffer this replaces)
-            dfree(bs->d_robs); bs->robs_cap = 0; bs->robs_ready = false;
-            HIP_TRY(c, hipMalloc(&bs->d_robs, n_observes * sizeof(double)));
-            bs->robs_cap = n_observes;
-        }
-        HIP_TRY(c, hipMemcpyAsync(bs->d_robs, h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        bs->robs_ready = true;
-    }
-    // the means with the sigmas behind them in front, the transition rows at the back
-    double *d_means = nullptr, *d_trans = nullptr;
-    if (int rc = batch_stage(c, batch_round(2 * B * (size_t)k * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
-    double* d_sigmas = d_means + B * (size_t)k;
-    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs, d_sigmas)) return rc;
-    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
-    batch_mirror_scales(bs, B, k, h_sigmas);
-    bs->thr_stale = false;
-    return 0;
-}
 
 int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* c, uint64_t problem, double* h_sigmas, double* h_log_norm)
 {
@@ -5865,34 +5839,6 @@ int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* c, uint64_t problem, double* h_
     if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_sigma + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_log_norm) HIP_TRY(c, hipMemcpyAsync(h_log_norm, bs->d_lognorm + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int cpprob_hip_batch_online_tables_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas)
-{
-    LANES_OWN(c);
-    if (int rc = batch_learn_check(c, "cpprob_hip_batch_online_tables_scaled")) return rc;
-    BatchState* bs = c->batch;
-    if (!bs->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_online_scaled, or call cpprob_hip_batch_online_tables");
-    if (!h_means || !h_transition || !h_sigmas) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
-    int k = 0;
-    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
-    if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
-    bs->means.assign(h_means, h_means + B * (size_t)k);
-    bs->trans.assign(h_transition, h_transition + B * kk);
-    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
-    batch_mirror_scales(bs, B, k, h_sigmas);
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_sigma, bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm, bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (bs->armed) {
-        HIP_TRY(c, hipMemcpyAsync(bs->d_lmeans, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(bs->d_ltrans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    }
-    bs->thr_stale = false; bs->lp_ready = false; bs->lp_sent = false;
-    bs->decoded.assign(B, 0);
     return 0;
 }
 
@@ -5981,21 +5927,29 @@ static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const 
     return 0;
 }
 
-int cpprob_hip_batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const double* h_transition)
+// New tables for the begun online batch from the host (scaled: cpprob_hip_batch_online_tables_scaled, with the scales), validated with
+// the begin's own statements before anything changes; an armed batch's device tables follow.
+static int batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, bool scaled, const char* who)
 {
-    LANES_OWN(c);
-    if (int rc = batch_learn_check(c, "cpprob_hip_batch_online_tables")) return rc;
+    if (int rc = batch_learn_check(c, who)) return rc;
     BatchState* bs = c->batch;
-    if (bs->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its tables are replaced by cpprob_hip_batch_online_tables_scaled");
-    if (!h_means || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (bs->scaled && !scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its tables are replaced by cpprob_hip_batch_online_tables_scaled");
+    if (!bs->scaled && scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_online_scaled, or call cpprob_hip_batch_online_tables");
+    if (!h_means || !h_transition || (scaled && !h_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     int k = 0;
     if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    if (scaled) if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
     bs->means.assign(h_means, h_means + B * (size_t)k);
     bs->trans.assign(h_transition, h_transition + B * kk);
     for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
     HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    if (scaled) {
+        batch_mirror_scales(bs, B, k, h_sigmas);
+        HIP_TRY(c, hipMemcpyAsync(bs->d_sigma, bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm, bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     if (bs->armed) {
         HIP_TRY(c, hipMemcpyAsync(bs->d_lmeans, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_ltrans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -6004,6 +5958,18 @@ int cpprob_hip_batch_online_tables(cpprob_hip_ctx* c, const double* h_means, con
     bs->thr_stale = false; bs->lp_ready = false; bs->lp_sent = false;
     bs->decoded.assign(B, 0);
     return 0;
+}
+
+int cpprob_hip_batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const double* h_transition)
+{
+    LANES_OWN(c);
+    return batch_online_tables(c, h_means, h_transition, nullptr, false, "cpprob_hip_batch_online_tables");
+}
+
+int cpprob_hip_batch_online_tables_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas)
+{
+    LANES_OWN(c);
+    return batch_online_tables(c, h_means, h_transition, h_sigmas, true, "cpprob_hip_batch_online_tables_scaled");
 }
 
 // The armed batch's tables, status words and -- h_sigmas given: a scaled batch -- scales to the host; waits for the stream.

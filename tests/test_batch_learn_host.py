@@ -118,9 +118,17 @@ def test_the_library_words_every_refusal_with_its_code():
                        ("cpprob_hip_batch_advance_learn_device", "batch_advance(c, h_dT, nullptr, d_obs, n_observes, 1, true)")):
         assert call in _body(hip, "int " + name), name
     # the host route validates with the begin's own statements before it changes anything
-    host = _body(hip, "int cpprob_hip_batch_online_tables")
+    host = _body(hip, "static int batch_online_tables")
     assert host.index("batch_learn_check(") < host.index("batch_check_tables(") < host.index("bs->means.assign(") < host.index("hipMemcpyAsync")
     assert "bs->thr_stale = false; bs->lp_ready = false; bs->lp_sent = false;" in host and "if (bs->armed)" in host
+    # ... and is the body of the unit and of the scaled entry point, which name themselves for the state's refusal
+    for name, call in (("cpprob_hip_batch_online_tables", 'batch_online_tables(c, h_means, h_transition, nullptr, false, "cpprob_hip_batch_online_tables")'),
+                       ("cpprob_hip_batch_online_tables_scaled", 'batch_online_tables(c, h_means, h_transition, h_sigmas, true, "cpprob_hip_batch_online_tables_scaled")')):
+        entry = _body(hip, "int " + name)
+        assert [line.strip() for line in entry.splitlines()[2:-1]] == ["LANES_OWN(c);", "return %s;" % call], name
+    # the state is judged after batch_learn_check and before the arguments
+    assert host.index("batch_learn_check(") < host.index('"the batch has emission scales: its tables are replaced by') < host.index('"the batch has no emission scales: begin it with') \
+        < host.index('"NULL argument"') < host.index("batch_check_tables(")
     # re-tabling an online batch answers as before
     retable = _body(hip, "static int batch_retable_check")
     assert 'if (bs->online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "an online batch is not re-tabled: its advances evaluate their rows from the host\'s means");' in retable

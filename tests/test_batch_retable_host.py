@@ -87,13 +87,25 @@ def test_the_library_words_every_refusal_and_resets_the_state_of_a_begin():
                         ("CPPROB_HIP_EUNSUPPORTED", "a batch begun by cpprob_hip_batch_begin shares one table"),
                         ("CPPROB_HIP_EINVAL", "the problems' lengths sum to")):
         assert re.search(r"fail\(c, %s, \"[^\n]*%s" % (code, re.escape(words)), check), words
+    # the unit and the scaled entry points are one shared body each: the device forms', the host forms'
+    for name, call in (("cpprob_hip_batch_retable_device", "batch_retable_device(c, d_means, d_transition, nullptr, d_observes, n_observes, false)"),
+                       ("cpprob_hip_batch_retable_scaled_device", "batch_retable_device(c, d_means, d_transition, d_sigmas, d_observes, n_observes, true)"),
+                       ("cpprob_hip_batch_retable", "batch_retable_host(c, h_means, h_transition, nullptr, h_observes, n_observes, false)"),
+                       ("cpprob_hip_batch_retable_scaled", "batch_retable_host(c, h_means, h_transition, h_sigmas, h_observes, n_observes, true)")):
+        entry = re.search(r"^int %s\([^;{}]*\)\n\{\n(.*?)^\}" % name, hip, re.M | re.S).group(1)
+        assert [line.strip() for line in entry.splitlines()] == ["LANES_OWN(c);", "return %s;" % call], name
     # nothing is enqueued before the check has passed, in either form; the host form validates with the begin's own statements
-    for name in ("cpprob_hip_batch_retable_device", "cpprob_hip_batch_retable"):
-        body = re.search(r"^int %s\(.*?^\}" % name, hip, re.M | re.S).group(0)
+    observes = re.search(r"^static int batch_retable_observes\(.*?^\}", hip, re.M | re.S).group(0)
+    for name in ("batch_retable_device", "batch_retable_host"):
+        body = re.search(r"^static int %s\(.*?^\}" % name, hip, re.M | re.S).group(0)
         assert body.index("batch_retable_check(") < body.index("batch_retable_enqueue(")
-        assert body.count("hipStreamSynchronize") == (1 if name == "cpprob_hip_batch_retable" else 0)      # (the observes' buffer, where it has to grow)
-    host = re.search(r"^int cpprob_hip_batch_retable\(.*?^\}", hip, re.M | re.S).group(0)
-    assert host.index("batch_check_tables(") < host.index("hipMemcpyAsync") and "batch_stage(" in host and "bs->thr_stale = false;" in host
+        sync = body.count("hipStreamSynchronize") + (observes.count("hipStreamSynchronize") if name == "batch_retable_host" else 0)
+        assert sync == (1 if name == "batch_retable_host" else 0)                                          # (the observes' buffer, where it has to grow)
+        assert ("batch_retable_observes(" in body) == (name == "batch_retable_host")
+    host = re.search(r"^static int batch_retable_host\(.*?^\}", hip, re.M | re.S).group(0)
+    assert "hipMemcpyAsync" in observes and host.count("batch_retable_observes(") == 1
+    assert host.index("batch_check_tables(") < host.index("batch_check_scales(") < host.index("batch_retable_observes(") < host.index("hipMemcpyAsync")
+    assert "batch_stage(" in host and "bs->thr_stale = false;" in host
     enq = re.search(r"^static int batch_retable_enqueue\(.*?^\}", hip, re.M | re.S).group(0)
     for line in ("bs->ran = false; bs->conditional = false;", "bs->lp_ready = false; bs->lp_sent = false;", "bs->tab_stale = true; bs->thr_stale = true;"):
         assert line in enq, line

@@ -84,7 +84,8 @@ def test_the_entry_points_text():
     assert "bs->tied = false; bs->tie_groups = 0; bs->tie_map.clear();" in begin
     assert begin.index("bs->tied = false;") < begin.index("hipMalloc")
     for name in ("static int batch_retable_enqueue", "int cpprob_hip_batch_retable", "int cpprob_hip_batch_retable_device", "int cpprob_hip_batch_retable_scaled",
-                 "int cpprob_hip_batch_retable_scaled_device", "static int batch_retable_check"):
+                 "int cpprob_hip_batch_retable_scaled_device", "static int batch_retable_check", "static int batch_retable_device", "static int batch_retable_host",
+                 "static int batch_retable_observes"):
         assert re.search(r"\btied\b|tie_", _fn(hip, name)) is None, name
     # arrays of the context's own: no workspace region is added
     layout = re.search(r"^struct BatchLayout \{[^\n]*\};", hip, re.M).group(0)
