@@ -32,6 +32,7 @@
 #include "batch_scale.hpp"
 #include "batch_learn.hpp"
 #include "batch_pass_plan.hpp"
+#include "batch_buffers.hpp"
 #include "batch_pool.hpp"
 
 using namespace cph;
@@ -1065,7 +1066,8 @@ struct BatchState {
     BatchLayout lay{};
     std::vector<double> h_tab;                 // [B][T][kBatchTab]: the per-step tables the kernel reads (also the final log-weights' source)
     std::vector<uint64_t> h_thr;               // HMM_TABLE: the rows' thresholds at begin
-    char* d_ws = nullptr; size_t cap = 0;
+    DeviceBuffer d_ws;
+    char* ws() const { return d_ws.as<char>(); }
     ModelParams mp{};
     // a batch advanced in pieces (cpprob_hip_batch_begin_online): prob[b].T is the length reached, prob[b].store the problem's first
     // entry in a store sized by the capacities (keep_history = 1) or its first byte in the carry region (keep_history = 0)
@@ -1074,30 +1076,24 @@ struct BatchState {
     std::vector<uint32_t> cap_T;               // [B]
     std::vector<double> means;                 // HMM_TABLE: [tables][hk], the rows an advance evaluates its steps' tables with
     std::vector<double> trans;                 // HMM_TABLE with per-problem tables: [B][hk][hk], what cpprob_hip_batch_learn_begin uploads
-    double* pin_tab = nullptr; size_t pin_tab_cap = 0;      // pinned mirror of the table region: an advance writes its new rows only
+    PinnedBuffer pin_tab;                      // pinned mirror of the table region: an advance writes its new rows only
     // pinned descriptors of an advance in flight, kOnlineSlots in turn: {BatchProblem[B], first[B], order[B]}; a slot is written
-    // again once the copies that read it have run (its event)
+    // again once the copies that read it have run (its event); the ring's count is the advances since the begin
     static constexpr int kOnlineSlots = 4;
-    char* pin_desc = nullptr; size_t pin_desc_cap = 0, slot_bytes = 0;
-    hipEvent_t slot_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t n_advance = 0;
+    SlotRing<kOnlineSlots> advance_ring;
     // posterior traces (cpprob_hip_batch_paths, _paths_device; csrc/batch_paths.hpp): the problems' descriptors on the device, their
     // pinned sources (kOnlineSlots in turn, as an advance's) and the host variant's device staging; none of it in the workspace
-    char* d_pdesc = nullptr; size_t pdesc_cap = 0;
-    char* pin_pdesc = nullptr;
-    hipEvent_t pdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t n_paths = 0;
-    char* d_stage = nullptr; size_t stage_cap = 0;
+    DeviceBuffer d_pdesc;
+    SlotRing<kOnlineSlots> paths_ring;
+    DeviceBuffer d_stage;
     // backward smoothing (cpprob_hip_batch_smooth*, _smooth_lag*; csrc/batch_smooth.hpp): the m table ([sum of T_b][8] doubles -- an
     // online batch: of its capacities, rows never move --, grown lazily), the problems' descriptors with the HMM3 thresholds behind
     // them, and their pinned sources, kOnlineSlots in turn
-    double* d_mass = nullptr; size_t mass_rows = 0;
+    DeviceBuffer d_mass;
     // (a filtering batch with CPPROB_HIP_BATCH_KEEP_MASSES has its m table in the workspace, written by the run: none of these three)
     std::vector<uint32_t> counted;             // [B], online batch: its rows [0, counted_b) of the m table are valid (any begin: none)
-    char* d_sdesc = nullptr; size_t sdesc_cap = 0;
-    char* pin_sdesc = nullptr;
-    hipEvent_t sdesc_done[kOnlineSlots] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t n_smooth = 0;
+    DeviceBuffer d_sdesc;                      // (as large as a slot of the ring: a call copies the whole slot)
+    SlotRing<kOnlineSlots> smooth_ring;
     unsigned smooth_gy_count = 0, smooth_gy_lag = 0;        // gridDim.y of the last smoothing call's counting and lag launches (0: none)
     // of the last decode / forecast / predictive call: gridDim.x of the forward launch, gridDim.y of the trace, forecast and predictive launches (0: none)
     unsigned decode_gx_forward = 0, decode_gy_trace = 0, forecast_gy = 0, predictive_gy = 0;
@@ -1106,40 +1102,38 @@ struct BatchState {
     // capacity, kept), the v rows [B][8] and the log tables ([tables][64], computed on the host at the first call after a begin and
     // uploaded once), allocations of the context's own; decoded: [B], online batch: its words [0, decoded_b) and its v row are valid
     // (any begin: none)
-    uint32_t* d_words = nullptr; size_t words_cap = 0;
-    double* d_v = nullptr; size_t v_cap = 0;
-    double* d_lp = nullptr; size_t lp_cap = 0;
+    DeviceBuffer d_words, d_v, d_lp;
     std::vector<double> h_lp; double lp0 = 0.0;
     bool lp_ready = false, lp_sent = false;
     std::vector<uint32_t> decoded;
     // running statistics (cpprob_hip_batch_online_stats*; csrc/batch_onlinestats.hpp): tau [B][8][88], an allocation of the context's
     // own; ostats_done: [B], online batch: the steps [0, ostats_done_b) are in its tau (any begin: none -- a problem at 0 never reads tau)
-    double* d_tau = nullptr; size_t tau_cap = 0;
+    DeviceBuffer d_tau;
     std::vector<uint32_t> ostats_done;
     // conditional runs (cpprob_hip_batch_run_conditional*; csrc/batch_csmc.hpp): conditional: the last run was one -- it keeps masses, not
     // books, and cpprob_hip_batch_results is refused until the next cpprob_hip_batch_run; a described batch's first entries in the
     // reference paths ([B] int64, the lengths are fixed at begin: written and uploaded at the first conditional run after it) with
     // their pinned source, allocations of the context's own
     bool conditional = false, cfirst_ready = false;
-    int64_t* d_cfirst = nullptr; int64_t* pin_cfirst = nullptr; size_t cfirst_cap = 0;
+    DeviceBuffer d_cfirst; PinnedBuffer pin_cfirst;
     // re-tabling (cpprob_hip_batch_retable*; csrc/batch_retable.hpp): the status words [B] and the observes the host form staged, allocations
     // of the context's own; retabled: the begun batch has been re-tabled (its status words are those of the last one); robs_ready: d_robs
     // holds this begun batch's observes; tab_stale / thr_stale: the device holds rows / thresholds the host mirrors (h_tab, h_thr) do not
-    int32_t* d_rstatus = nullptr; size_t rstatus_cap = 0;
-    double* d_robs = nullptr; size_t robs_cap = 0;
+    DeviceBuffer d_rstatus, d_robs;
     bool retabled = false, robs_ready = false, tab_stale = false, thr_stale = false;
     unsigned retable_gy = 0;                                // gridDim.y of the last re-table launch (0: none)
     // online EM (cpprob_hip_batch_learn_*; csrc/batch_learn.hpp): own_tables: the batch was begun with per-problem tables; armed: the
     // begun online batch learns its tables -- the step sizes [n_gamma], the device-resident tables (means [B][k], transition [B][k][k]),
     // the learner's tau [B][8][88], the records [B][88], the status words [B], the first new observes of an advance ([B] int64, with
     // their pinned sources, kOnlineSlots in turn as an advance's descriptors) and the host form's copy of an advance's observes,
-    // allocations of the context's own
+    // allocations of the context's own, in the order above
     bool own_tables = false, armed = false;
     uint32_t learn_t_min = 0;
-    double *d_gamma = nullptr, *d_lmeans = nullptr, *d_ltrans = nullptr, *d_ltau = nullptr, *d_lrec = nullptr, *d_lobs = nullptr;
-    int32_t* d_lstatus = nullptr;
-    int64_t *d_lfirst = nullptr, *pin_lfirst = nullptr;
-    size_t lobs_cap = 0;
+    struct Learner {
+        DeviceBuffer gamma, means, trans, tau, rec, obs, status, first;
+        PinnedBuffer pin_first;
+        void release() { for (DeviceBuffer* b : {&gamma, &means, &trans, &tau, &rec, &obs, &status, &first}) b->release(); pin_first.release(); }
+    } learn;
     // per-state emission scales (cpprob_hip_batch_begin_problems_scaled, _begin_online_scaled; csrc/batch_scale.hpp): scaled: the begun
     // batch has them; the sigmas and log_norms in force, [B][8] (states >= k zero), on the host as the last begin or host call
     // (cpprob_hip_batch_retable_scaled, _online_tables_scaled) left them and on the device (allocations of the context's own) as the
@@ -1148,45 +1142,30 @@ struct BatchState {
     bool scaled = false, learn_scales = false;
     double learn_floor = 0.0;
     std::vector<double> sigmas, log_norms;
-    double *d_sigma = nullptr, *d_lognorm = nullptr; size_t scale_cap = 0;
+    DeviceBuffer d_sigma, d_lognorm;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
     bool tied = false;
     int32_t tie_groups = 0;
     std::vector<int32_t> tie_map;
-    int32_t* d_tie = nullptr; size_t tie_cap = 0;
-    const double* tab_host() const { return online ? pin_tab : h_tab.data(); }
+    DeviceBuffer d_tie;
+    const double* tab_host() const { return online ? pin_tab.as<double>() : h_tab.data(); }
 };
 
 // Disarms: the learner's allocations go (hipFree waits for the device: no kernel still reads them).
 void batch_learn_free(BatchState* bs)
 {
-    dfree(bs->d_gamma); dfree(bs->d_lmeans); dfree(bs->d_ltrans); dfree(bs->d_ltau); dfree(bs->d_lrec); dfree(bs->d_lobs); dfree(bs->d_lstatus); dfree(bs->d_lfirst);
-    if (bs->pin_lfirst) { (void)hipHostFree(bs->pin_lfirst); bs->pin_lfirst = nullptr; }
-    bs->lobs_cap = 0; bs->armed = false;
+    bs->learn.release();
+    bs->armed = false;
 }
 
+// The state goes with everything it owns.  The workspace first: hipFree waits for the device, so no copy still reads a pinned buffer
+// when the members' destructors free them.
 void batch_free(cpprob_hip_ctx* c)
 {
     if (!c->batch) return;
-    batch_learn_free(c->batch);
-    dfree(c->batch->d_ws);                     // (hipFree waits for the device: no copy still reads the pinned buffers)
-    if (c->batch->pin_tab) (void)hipHostFree(c->batch->pin_tab);
-    if (c->batch->pin_desc) (void)hipHostFree(c->batch->pin_desc);
-    for (hipEvent_t e : c->batch->slot_done) if (e) (void)hipEventDestroy(e);
-    dfree(c->batch->d_pdesc); dfree(c->batch->d_stage);
-    if (c->batch->pin_pdesc) (void)hipHostFree(c->batch->pin_pdesc);
-    for (hipEvent_t e : c->batch->pdesc_done) if (e) (void)hipEventDestroy(e);
-    dfree(c->batch->d_mass); dfree(c->batch->d_sdesc);
-    dfree(c->batch->d_words); dfree(c->batch->d_v); dfree(c->batch->d_lp); dfree(c->batch->d_tau);
-    if (c->batch->pin_sdesc) (void)hipHostFree(c->batch->pin_sdesc);
-    dfree(c->batch->d_cfirst);
-    dfree(c->batch->d_rstatus); dfree(c->batch->d_robs);
-    dfree(c->batch->d_sigma); dfree(c->batch->d_lognorm);
-    dfree(c->batch->d_tie);
-    if (c->batch->pin_cfirst) (void)hipHostFree(c->batch->pin_cfirst);
-    for (hipEvent_t e : c->batch->sdesc_done) if (e) (void)hipEventDestroy(e);
+    c->batch->d_ws.release();
     delete c->batch;
     c->batch = nullptr;
 }
@@ -1281,23 +1260,13 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         // (advances of the batch this one replaces may still read the pinned buffers)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         const size_t tab_bytes = (size_t)B * T_max * kBatchTab * sizeof(double);
-        if (tab_bytes > bs->pin_tab_cap) {
-            if (bs->pin_tab) { (void)hipHostFree(bs->pin_tab); bs->pin_tab = nullptr; bs->pin_tab_cap = 0; }
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_tab), tab_bytes, hipHostMallocDefault));
-            bs->pin_tab_cap = tab_bytes;
-        }
-        std::memset(bs->pin_tab, 0, tab_bytes);
-        bs->slot_bytes = batch_round((size_t)B * (sizeof(BatchProblem) + 2 * sizeof(int32_t)));
-        if (bs->slot_bytes * BatchState::kOnlineSlots > bs->pin_desc_cap) {
-            if (bs->pin_desc) { (void)hipHostFree(bs->pin_desc); bs->pin_desc = nullptr; bs->pin_desc_cap = 0; }
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_desc), bs->slot_bytes * BatchState::kOnlineSlots, hipHostMallocDefault));
-            bs->pin_desc_cap = bs->slot_bytes * BatchState::kOnlineSlots;
-        }
-        for (hipEvent_t& e : bs->slot_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIP_TRY(c, bs->pin_tab.grow(c->stream, tab_bytes));
+        std::memset(bs->pin_tab.as<double>(), 0, tab_bytes);
+        HIP_TRY(c, bs->advance_ring.reserve(c->stream, batch_round((size_t)B * (sizeof(BatchProblem) + 2 * sizeof(int32_t)))));
+        bs->advance_ring.restart();
         bs->cap_T.assign(h_T, h_T + B);
         bs->walked_b.assign(B, 1);
         bs->means.clear(); bs->trans.clear();
-        bs->n_advance = 0;
         bs->h_tab.clear();
     } else bs->h_tab.assign((size_t)B * T_max * kBatchTab, 0.0);
     bs->h_thr.assign((size_t)tables * 64, ~0ull);
@@ -1306,12 +1275,8 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     if (scaled) {
         bs->sigmas.assign((size_t)B * 8, 0.0); bs->log_norms.assign((size_t)B * 8, 0.0);
         batch_mirror_scales(bs, (size_t)B, k, h_sigmas);
-        if (B > bs->scale_cap) {
-            dfree(bs->d_sigma); dfree(bs->d_lognorm); bs->scale_cap = 0;      // (hipFree waits for the device: no kernel still writes them)
-            HIP_TRY(c, hipMalloc(&bs->d_sigma, B * 8 * sizeof(double)));
-            HIP_TRY(c, hipMalloc(&bs->d_lognorm, B * 8 * sizeof(double)));
-            bs->scale_cap = B;
-        }
+        HIP_TRY(c, bs->d_sigma.grow(c->stream, B * 8 * sizeof(double)));
+        HIP_TRY(c, bs->d_lognorm.grow(c->stream, B * 8 * sizeof(double)));
     }
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
@@ -1341,18 +1306,13 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         at_carry += (int64_t)n_b;
     }
     bs->lay = batch_layout(B, T_max, tables, described, (uint64_t)at_store, spp, cfg->keep_history == 1, online, (uint64_t)at_carry, batch_masses(cfg));
-    if (bs->lay.total > bs->cap) {
-        // (the previous workspace may still be read by a batch in flight: hipFree waits for the device)
-        dfree(bs->d_ws); bs->cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_ws, bs->lay.total));
-        bs->cap = bs->lay.total;
-    }
-    if (online) HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.tab, 0, (size_t)B * T_max * kBatchTab * sizeof(double), c->stream));
-    else HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, bs->d_ws.grow(c->stream, bs->lay.total));        // (the previous workspace may still be read by a batch in flight)
+    if (online) HIP_TRY(c, hipMemsetAsync(bs->ws() + bs->lay.tab, 0, (size_t)B * T_max * kBatchTab * sizeof(double), c->stream));
+    else HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     if (scaled) {
-        HIP_TRY(c, hipMemcpyAsync(bs->d_sigma, bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm, bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_sigma.as<double>(), bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm.as<double>(), bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
@@ -1362,10 +1322,10 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         StepCtrl z{};
         z.W = 1.0;
         for (uint64_t b = 0; b < B; ++b) std::memcpy(ctrl0.data() + b * kBatchCtrlBytes, &z, sizeof z);
-        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.ctrl, ctrl0.data(), ctrl0.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.nreq, 0, B * sizeof(int32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.snap, 0, B * sizeof(BatchSnap), c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.ctrl, ctrl0.data(), ctrl0.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->ws() + bs->lay.nreq, 0, B * sizeof(int32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->ws() + bs->lay.snap, 0, B * sizeof(BatchSnap), c->stream));
     }
     if (described) {
         // the longest chains first (steps x LDS passes a step), ties by index: the launch's tail is made of short problems; no result
@@ -1374,12 +1334,12 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         for (uint64_t b = 0; b < B; ++b) order[b] = (int32_t)b;
         auto cost = [&](int32_t b) { return (uint64_t)h_T[b] * ((h_n[b] + (uint64_t)kTile - 1) / kTile); };
         std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cost(x) > cost(y); });
-        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.prob, bs->prob.data(), B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.order, order.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.prob, bs->prob.data(), B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.order, order.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         // the padded rows t >= T_b are never written by a run: zero once (the workspace may have held another batch)
-        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.stats, 0, B * T_max * (size_t)spp * sizeof(double), c->stream));
-        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.ess, 0, B * T_max * sizeof(double), c->stream));
-        HIP_TRY(c, hipMemsetAsync(bs->d_ws + bs->lay.res, 0, B * T_max * sizeof(int32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->ws() + bs->lay.stats, 0, B * T_max * (size_t)spp * sizeof(double), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->ws() + bs->lay.ess, 0, B * T_max * sizeof(double), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->ws() + bs->lay.res, 0, B * T_max * sizeof(int32_t), c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
@@ -4224,26 +4184,26 @@ static int batch_launch(cpprob_hip_ctx* c, BatchState* bs, bool readout)
     const bool keep = bs->cfg.keep_history == 1;
     BatchArgs a{};
     if (bs->online) {
-        a.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
-        a.snap = reinterpret_cast<BatchSnap*>(bs->d_ws + bs->lay.snap);
-        a.carry = keep ? nullptr : reinterpret_cast<uint8_t*>(bs->d_ws + bs->lay.carry);
+        a.first = reinterpret_cast<const int32_t*>(bs->ws() + bs->lay.first);
+        a.snap = reinterpret_cast<BatchSnap*>(bs->ws() + bs->lay.snap);
+        a.carry = keep ? nullptr : reinterpret_cast<uint8_t*>(bs->ws() + bs->lay.carry);
         a.skip_readout = keep && !readout ? 1 : 0;
     }
     a.mp = bs->mp;
-    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
-    a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
-    a.thr = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+    a.tab = reinterpret_cast<const double*>(bs->ws() + bs->lay.tab);
+    a.seeds = reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.seeds);
+    a.thr = reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.thr);
     a.thr_stride = bs->described ? 64 : 0;
-    a.prob = bs->described ? reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob) : nullptr;
-    a.order = bs->described ? reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.order) : nullptr;
-    a.values = keep ? reinterpret_cast<int8_t*>(bs->d_ws + bs->lay.values) : nullptr;
-    a.anc = keep ? reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.anc) : nullptr;
-    a.ctrl = bs->d_ws + bs->lay.ctrl;
-    a.stats = reinterpret_cast<double*>(bs->d_ws + bs->lay.stats);
-    a.ess = reinterpret_cast<double*>(bs->d_ws + bs->lay.ess);
-    a.resampled = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.res);
-    a.n_requant = reinterpret_cast<int32_t*>(bs->d_ws + bs->lay.nreq);
-    a.mass = batch_masses(&bs->cfg) ? reinterpret_cast<double*>(bs->d_ws + bs->lay.mass) : nullptr;
+    a.prob = bs->described ? reinterpret_cast<const BatchProblem*>(bs->ws() + bs->lay.prob) : nullptr;
+    a.order = bs->described ? reinterpret_cast<const int32_t*>(bs->ws() + bs->lay.order) : nullptr;
+    a.values = keep ? reinterpret_cast<int8_t*>(bs->ws() + bs->lay.values) : nullptr;
+    a.anc = keep ? reinterpret_cast<int32_t*>(bs->ws() + bs->lay.anc) : nullptr;
+    a.ctrl = bs->ws() + bs->lay.ctrl;
+    a.stats = reinterpret_cast<double*>(bs->ws() + bs->lay.stats);
+    a.ess = reinterpret_cast<double*>(bs->ws() + bs->lay.ess);
+    a.resampled = reinterpret_cast<int32_t*>(bs->ws() + bs->lay.res);
+    a.n_requant = reinterpret_cast<int32_t*>(bs->ws() + bs->lay.nreq);
+    a.mass = batch_masses(&bs->cfg) ? reinterpret_cast<double*>(bs->ws() + bs->lay.mass) : nullptr;
     a.T_max = bs->T; a.n = (int)bs->cfg.n_particles; a.spp = bs->K; a.ess_frac = bs->cfg.ess_threshold;
     const bool strat = bs->cfg.resampler == CPPROB_HIP_RESAMPLE_STRATIFIED;
     const BatchKernel kern = bs->cfg.model == CPPROB_HIP_MODEL_HMM3 ? batch_kernel<ModelHmm3>(strat, keep, bs->online, a.mass != nullptr) : batch_kernel<ModelHmmK>(strat, keep, bs->online, a.mass != nullptr);
@@ -4260,9 +4220,21 @@ int cpprob_hip_batch_run(cpprob_hip_ctx* c, const uint64_t* h_seeds)
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
     if (bs->online) return fail(c, CPPROB_HIP_ESTATE, "a batch begun by cpprob_hip_batch_begin_online is advanced (cpprob_hip_batch_advance), not run");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, bs->cfg.n_problems * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.seeds, h_seeds, bs->cfg.n_problems * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     if (int rc = batch_launch(c, bs, true)) return rc;
     bs->ran = true; bs->conditional = false;
+    return 0;
+}
+
+// The device staging of a host call: front_bytes of the block in front of back_bytes (the caller rounds the former where the latter
+// needs the alignment); a part of 0 bytes is nullptr.  Where the block has to grow, it waits first for the calls before it, whose
+// copies and kernels may still read the block this replaces.
+extern "C++" template <class F, class K> int batch_stage(cpprob_hip_ctx* c, size_t front_bytes, size_t back_bytes, F*& front, K*& back)
+{
+    BatchState* bs = c->batch;
+    HIP_TRY(c, bs->d_stage.grow(c->stream, front_bytes + back_bytes));
+    front = front_bytes ? reinterpret_cast<F*>(bs->d_stage.as<char>()) : nullptr;
+    back = back_bytes ? reinterpret_cast<K*>(bs->d_stage.as<char>() + front_bytes) : nullptr;
     return 0;
 }
 
@@ -4292,18 +4264,12 @@ static int batch_first_entries(cpprob_hip_ctx* c)
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
     if (!bs->described || bs->cfirst_ready) return 0;
-    if (B > bs->cfirst_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));       // (earlier runs may still read the buffer this replaces)
-        dfree(bs->d_cfirst); bs->cfirst_cap = 0;
-        if (bs->pin_cfirst) { (void)hipHostFree(bs->pin_cfirst); bs->pin_cfirst = nullptr; }
-        HIP_TRY(c, hipMalloc(&bs->d_cfirst, B * sizeof(int64_t)));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_cfirst), B * sizeof(int64_t), hipHostMallocDefault));
-        bs->cfirst_cap = B;
-    }
+    HIP_TRY(c, bs->d_cfirst.grow(c->stream, B * sizeof(int64_t)));
+    HIP_TRY(c, bs->pin_cfirst.grow(c->stream, B * sizeof(int64_t)));
     // (the pinned source is written once a begin, and a begin ends with the stream drained: no copy still reads it)
     int64_t at = 0;
-    for (size_t b = 0; b < B; ++b) { bs->pin_cfirst[b] = at; at += (int64_t)bs->prob[b].T; }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_cfirst, bs->pin_cfirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    for (size_t b = 0; b < B; ++b) { bs->pin_cfirst.as<int64_t>()[b] = at; at += (int64_t)bs->prob[b].T; }
+    HIP_TRY(c, hipMemcpyAsync(bs->d_cfirst.as<int64_t>(), bs->pin_cfirst.as<int64_t>(), B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     bs->cfirst_ready = true;
     return 0;
 }
@@ -4315,17 +4281,17 @@ static int batch_conditional_enqueue(cpprob_hip_ctx* c, const uint64_t* h_seeds,
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
     if (int rc = batch_first_entries(c)) return rc;
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.seeds, h_seeds, B * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     BatchCsmcArgs a{};
-    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
-    a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
-    a.thr = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+    a.tab = reinterpret_cast<const double*>(bs->ws() + bs->lay.tab);
+    a.seeds = reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.seeds);
+    a.thr = reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.thr);
     a.thr_stride = bs->described ? 64 : 0;
-    a.prob = bs->described ? reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob) : nullptr;
-    a.order = bs->described ? reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.order) : nullptr;
+    a.prob = bs->described ? reinterpret_cast<const BatchProblem*>(bs->ws() + bs->lay.prob) : nullptr;
+    a.order = bs->described ? reinterpret_cast<const int32_t*>(bs->ws() + bs->lay.order) : nullptr;
     a.ref = d_ref;
-    a.first = bs->described ? bs->d_cfirst : nullptr;
-    a.mass = reinterpret_cast<double*>(bs->d_ws + bs->lay.mass);
+    a.first = bs->described ? bs->d_cfirst.as<int64_t>() : nullptr;
+    a.mass = reinterpret_cast<double*>(bs->ws() + bs->lay.mass);
     a.T_max = bs->T; a.n = (int)bs->cfg.n_particles; a.k = bs->hk;
     hipLaunchKernelGGL(batch_csmc_kernel, dim3((unsigned)B), dim3(kThreads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
@@ -4356,13 +4322,10 @@ int cpprob_hip_batch_run_conditional(cpprob_hip_ctx* c, const uint64_t* h_seeds,
             v[at] = (int8_t)h_ref[at];
         }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (n_entries > bs->stage_cap) {
-        dfree(bs->d_stage); bs->stage_cap = 0;                  // (hipFree waits for the device: no call still reads the staging)
-        HIP_TRY(c, hipMalloc(&bs->d_stage, n_entries));
-        bs->stage_cap = n_entries;
-    }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_stage, v.data(), n_entries, hipMemcpyHostToDevice, c->stream));
-    if (int rc = batch_conditional_enqueue(c, h_seeds, reinterpret_cast<const int8_t*>(bs->d_stage))) return rc;
+    int8_t *d_ref = nullptr, *none = nullptr;
+    if (int rc = batch_stage(c, n_entries, 0, d_ref, none)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_ref, v.data(), n_entries, hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_conditional_enqueue(c, h_seeds, d_ref)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));               // (the staged copy has read v; a later host call may take the staging over)
     return 0;
 }
@@ -4422,21 +4385,16 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
     if (learn) {
         before.resize(B);
         for (uint64_t b = 0; b < B; ++b) before[b] = (uint32_t)bs->prob[b].T;
-        if (h_obs && total > bs->lobs_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));       // (the advance before may still read the buffer this replaces)
-            dfree(bs->d_lobs); bs->lobs_cap = 0;
-            HIP_TRY(c, hipMalloc(&bs->d_lobs, (size_t)total * sizeof(double)));
-            bs->lobs_cap = (size_t)total;
-        }
+        if (h_obs) HIP_TRY(c, bs->learn.obs.grow(c->stream, (size_t)total * sizeof(double)));      // (the advance before may still read the buffer this replaces)
     }
     // this advance's descriptors: its slot is free once the copies of the advance that used it last have run
-    const int slot = (int)(bs->n_advance % BatchState::kOnlineSlots);
-    if (bs->n_advance >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->slot_done[slot]));
-    char* sl = bs->pin_desc + (size_t)slot * bs->slot_bytes;
+    const int slot = bs->advance_ring.slot_index();
+    char* sl = nullptr;
+    HIP_TRY(c, bs->advance_ring.acquire(sl));
     BatchProblem* pr = reinterpret_cast<BatchProblem*>(sl);
     int32_t* first = reinterpret_cast<int32_t*>(sl + B * sizeof(BatchProblem));
     int32_t* order = first + B;
-    int64_t* ofirst = learn ? bs->pin_lfirst + (size_t)slot * B : nullptr;
+    int64_t* ofirst = learn ? bs->learn.pin_first.as<int64_t>() + (size_t)slot * B : nullptr;
     const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3, keep = bs->cfg.keep_history == 1;
     const size_t hk = (size_t)bs->hk, T_max = (size_t)bs->T, row_bytes = kBatchTab * sizeof(double);
     const bool own = !hmm3 && bs->means.size() > hk;
@@ -4449,7 +4407,7 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
         if (own && h_dT[b] && !learn) mean.assign(bs->means.begin() + (ptrdiff_t)(b * hk), bs->means.begin() + (ptrdiff_t)((b + 1) * hk));
         for (size_t t = L; !learn && t < L + h_dT[b]; ++t) {
             const double y = h_obs[at_obs++];
-            double* row = bs->pin_tab + (b * T_max + t) * kBatchTab;
+            double* row = bs->pin_tab.as<double>() + (b * T_max + t) * kBatchTab;
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
             else if (bs->scaled) scale_step_ll(y, mean.data(), &bs->sigmas[b * 8], &bs->log_norms[b * 8], (int)hk, row);
             else hmmk_step_ll(y, mean, (int)hk, row);
@@ -4471,34 +4429,33 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
         while (e < B && bs->prob[e].T == bs->prob[b].T && h_dT[e] == h_dT[b]) ++e;
         if (h_dT[b]) {
             const size_t at = ((size_t)b * T_max + (size_t)first[b]) * row_bytes;      // (h_dT[b] > 0: first[b] is its length before)
-            HIP_TRY(c, hipMemcpy2DAsync(bs->d_ws + bs->lay.tab + at, T_max * row_bytes, reinterpret_cast<const char*>(bs->pin_tab) + at, T_max * row_bytes,
+            HIP_TRY(c, hipMemcpy2DAsync(bs->ws() + bs->lay.tab + at, T_max * row_bytes, reinterpret_cast<const char*>(bs->pin_tab.as<double>()) + at, T_max * row_bytes,
                                         (size_t)h_dT[b] * row_bytes, (size_t)(e - b), hipMemcpyHostToDevice, c->stream));
         }
         b = e;
     }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.prob, pr, B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.first, first, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.order, order, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (learn) HIP_TRY(c, hipMemcpyAsync(bs->d_lfirst, ofirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(bs->slot_done[slot], c->stream));
-    ++bs->n_advance;
+    HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.prob, pr, B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.first, first, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.order, order, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (learn) HIP_TRY(c, hipMemcpyAsync(bs->learn.first.as<int64_t>(), ofirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, bs->advance_ring.commit(c->stream));
     if (learn && total) {
         // the new rows, on the device: from the observes and the tables in force
-        if (h_obs) { HIP_TRY(c, hipMemcpyAsync(bs->d_lobs, h_obs, (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream)); d_obs = bs->d_lobs; }
+        if (h_obs) { HIP_TRY(c, hipMemcpyAsync(bs->learn.obs.as<double>(), h_obs, (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream)); d_obs = bs->learn.obs.as<double>(); }
         uint32_t top = 0;
         for (uint64_t b = 0; b < B; ++b) top = std::max(top, h_dT[b]);
         const dim3 grid((unsigned)B, retable_grid_y(top, (int64_t)B));
         auto common = [&](auto& r) {                            // (what the two forms' arguments share)
-            r.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-            r.first = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.first);
-            r.ofirst = bs->d_lfirst; r.means = bs->d_lmeans; r.obs = d_obs;
-            r.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
+            r.prob = reinterpret_cast<const BatchProblem*>(bs->ws() + bs->lay.prob);
+            r.first = reinterpret_cast<const int32_t*>(bs->ws() + bs->lay.first);
+            r.ofirst = bs->learn.first.as<int64_t>(); r.means = bs->learn.means.as<double>(); r.obs = d_obs;
+            r.tab = reinterpret_cast<double*>(bs->ws() + bs->lay.tab);
             r.T_max = bs->T; r.k = bs->hk;
         };
         if (bs->scaled) {
             BatchLearnRowsScaledArgs rs{};
             common(rs);
-            rs.sigmas = bs->d_sigma; rs.log_norms = bs->d_lognorm;
+            rs.sigmas = bs->d_sigma.as<double>(); rs.log_norms = bs->d_lognorm.as<double>();
             hipLaunchKernelGGL(batch_learn_rows_scaled_kernel, grid, dim3(kThreads), 0, c->stream, rs);
         } else {
             BatchLearnRowsArgs ra{};
@@ -4558,11 +4515,11 @@ int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, doubl
     if (h_stats && n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "h_stats too small");
     std::vector<char> ctrl(B * kBatchCtrlBytes);
     std::vector<int32_t> nreq(B);
-    HIP_TRY(c, hipMemcpyAsync(ctrl.data(), bs->d_ws + bs->lay.ctrl, ctrl.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(nreq.data(), bs->d_ws + bs->lay.nreq, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (h_stats) HIP_TRY(c, hipMemcpyAsync(h_stats, bs->d_ws + bs->lay.stats, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (h_ess) HIP_TRY(c, hipMemcpyAsync(h_ess, bs->d_ws + bs->lay.ess, B * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (h_resampled) HIP_TRY(c, hipMemcpyAsync(h_resampled, bs->d_ws + bs->lay.res, B * T * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ctrl.data(), bs->ws() + bs->lay.ctrl, ctrl.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(nreq.data(), bs->ws() + bs->lay.nreq, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (h_stats) HIP_TRY(c, hipMemcpyAsync(h_stats, bs->ws() + bs->lay.stats, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_ess) HIP_TRY(c, hipMemcpyAsync(h_ess, bs->ws() + bs->lay.ess, B * T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_resampled) HIP_TRY(c, hipMemcpyAsync(h_resampled, bs->ws() + bs->lay.res, B * T * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3;
     for (size_t b = 0; b < B; ++b) {
@@ -4597,7 +4554,7 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_d
     const int64_t total = B * (4 + per);
     // (a batch of problems: per = T_max spp; rows t >= T_b are zero -- begin cleared them and no run writes them)
     hipLaunchKernelGGL(batch_pack_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
-                       (const char*)(bs->d_ws + bs->lay.ctrl), (const double*)(bs->d_ws + bs->lay.stats), (int)per, B, d_out);
+                       (const char*)(bs->ws() + bs->lay.ctrl), (const double*)(bs->ws() + bs->lay.stats), (int)per, B, d_out);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }
@@ -4617,9 +4574,9 @@ int cpprob_hip_batch_copy_store(cpprob_hip_ctx* c, uint64_t problem, int32_t* h_
     double fetched[kBatchTab];                                 // a re-tabled batch's rows are on the device only: the last step's, 64 bytes
     const size_t last = ((size_t)problem * (size_t)bs->T + (T ? T - 1 : 0)) * kBatchTab;
     if (h_logw && T > 0 && bs->tab_stale)
-        HIP_TRY(c, hipMemcpyAsync(fetched, bs->d_ws + bs->lay.tab + last * sizeof(double), sizeof fetched, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(v.data(), bs->d_ws + bs->lay.values + first, T * n, hipMemcpyDeviceToHost, c->stream));
-    if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->d_ws + bs->lay.anc + first * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(fetched, bs->ws() + bs->lay.tab + last * sizeof(double), sizeof fetched, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v.data(), bs->ws() + bs->lay.values + first, T * n, hipMemcpyDeviceToHost, c->stream));
+    if (h_anc) HIP_TRY(c, hipMemcpyAsync(h_anc, bs->ws() + bs->lay.anc + first * sizeof(int32_t), T * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (h_values) for (size_t i = 0; i < T * n; ++i) h_values[i] = v[i];
     if (h_logw && T > 0) {
@@ -4643,7 +4600,7 @@ int cpprob_hip_batch_copy_masses(cpprob_hip_ctx* c, uint64_t problem, double* h_
     if (T == 0) return 0;
     if (!h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(h_out, bs->d_ws + bs->lay.mass + (size_t)problem * (size_t)bs->T * 8 * sizeof(double), T * 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_out, bs->ws() + bs->lay.mass + (size_t)problem * (size_t)bs->T * 8 * sizeof(double), T * 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -4692,19 +4649,11 @@ static int batch_paths_enqueue(cpprob_hip_ctx* c, uint64_t max_particles, int8_t
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems, bytes = batch_round(B * sizeof(BatchPathsProblem));
-    if (bytes > bs->pdesc_cap) {
-        // (earlier calls' copies may still read the buffers this replaces)
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        dfree(bs->d_pdesc); bs->pdesc_cap = 0;
-        if (bs->pin_pdesc) { (void)hipHostFree(bs->pin_pdesc); bs->pin_pdesc = nullptr; }
-        HIP_TRY(c, hipMalloc(&bs->d_pdesc, bytes));
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_pdesc), bytes * BatchState::kOnlineSlots, hipHostMallocDefault));
-        for (hipEvent_t& e : bs->pdesc_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        bs->pdesc_cap = bytes; bs->n_paths = 0;
-    }
-    const int slot = (int)(bs->n_paths % BatchState::kOnlineSlots);
-    if (bs->n_paths >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->pdesc_done[slot]));
-    BatchPathsProblem* pd = reinterpret_cast<BatchPathsProblem*>(bs->pin_pdesc + (size_t)slot * bs->pdesc_cap);
+    HIP_TRY(c, bs->paths_ring.reserve(c->stream, bytes));       // (earlier calls' copies may still read the buffers these replace)
+    HIP_TRY(c, bs->d_pdesc.grow(c->stream, bytes));
+    char* sl = nullptr;
+    HIP_TRY(c, bs->paths_ring.acquire(sl));
+    BatchPathsProblem* pd = reinterpret_cast<BatchPathsProblem*>(sl);
     int64_t first = 0, wfirst = 0;
     int m_top = 0;
     for (size_t b = 0; b < B; ++b) {
@@ -4716,14 +4665,13 @@ static int batch_paths_enqueue(cpprob_hip_ctx* c, uint64_t max_particles, int8_t
         if (pr.T) { wfirst += m; m_top = std::max(m_top, m); }
     }
     if (m_top == 0) return 0;                                  // (an online batch before its first observes: nothing to resolve)
-    HIP_TRY(c, hipMemcpyAsync(bs->d_pdesc, pd, B * sizeof(BatchPathsProblem), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(bs->pdesc_done[slot], c->stream));
-    ++bs->n_paths;
+    HIP_TRY(c, hipMemcpyAsync(bs->d_pdesc.as<char>(), pd, B * sizeof(BatchPathsProblem), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, bs->paths_ring.commit(c->stream));
     BatchPathsArgs a{};
-    a.desc = reinterpret_cast<const BatchPathsProblem*>(bs->d_pdesc);
-    a.values = reinterpret_cast<const int8_t*>(bs->d_ws + bs->lay.values);
-    a.anc = reinterpret_cast<const int32_t*>(bs->d_ws + bs->lay.anc);
-    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
+    a.desc = reinterpret_cast<const BatchPathsProblem*>(bs->d_pdesc.as<char>());
+    a.values = reinterpret_cast<const int8_t*>(bs->ws() + bs->lay.values);
+    a.anc = reinterpret_cast<const int32_t*>(bs->ws() + bs->lay.anc);
+    a.tab = reinterpret_cast<const double*>(bs->ws() + bs->lay.tab);
     a.paths = d_paths; a.logw = d_logw; a.T_max = bs->T;
     hipLaunchKernelGGL(batch_paths_kernel, dim3((unsigned)B, (unsigned)((m_top + kTile - 1) / kTile)), dim3(kThreads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
@@ -4739,24 +4687,6 @@ int cpprob_hip_batch_paths_device(cpprob_hip_ctx* c, uint64_t max_particles, int
     if (!d_paths && entries) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     HIP_TRY(c, hipSetDevice(c->device));
     return batch_paths_enqueue(c, max_particles, d_paths, d_logw);
-}
-
-// The device staging of a host call: front_bytes of the block in front of back_bytes (the caller rounds the former where the latter
-// needs the alignment); a part of 0 bytes is nullptr.  Where the block has to grow, it waits first for the calls before it, whose
-// copies and kernels may still read the block this replaces.
-extern "C++" template <class F, class K> int batch_stage(cpprob_hip_ctx* c, size_t front_bytes, size_t back_bytes, F*& front, K*& back)
-{
-    BatchState* bs = c->batch;
-    const size_t need = front_bytes + back_bytes;
-    if (need > bs->stage_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        dfree(bs->d_stage); bs->stage_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_stage, need));
-        bs->stage_cap = need;
-    }
-    front = front_bytes ? reinterpret_cast<F*>(bs->d_stage) : nullptr;
-    back = back_bytes ? reinterpret_cast<K*>(bs->d_stage + front_bytes) : nullptr;
-    return 0;
 }
 
 // A host call's results: the int8 entries and the doubles copied back (either count may be 0), the stream waited for, the entries
@@ -4855,49 +4785,36 @@ static int batch_pass_prologue(cpprob_hip_ctx* c, const BatchPass& p, BatchPassP
     if (pl.score_bytes) HIP_TRY(c, hipMemsetAsync(p.d_score, 0, pl.score_bytes, c->stream));
     if (pl.path_bytes) HIP_TRY(c, hipMemsetAsync(p.d_path, 0xff, pl.path_bytes, c->stream));
     if (pl.done) return 0;
-    if (bytes > bs->sdesc_cap || pl.mass_rows > bs->mass_rows) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (bytes > bs->sdesc_cap) {
-            dfree(bs->d_sdesc); bs->sdesc_cap = 0;
-            if (bs->pin_sdesc) { (void)hipHostFree(bs->pin_sdesc); bs->pin_sdesc = nullptr; }
-            HIP_TRY(c, hipMalloc(&bs->d_sdesc, bytes));
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_sdesc), bytes * BatchState::kOnlineSlots, hipHostMallocDefault));
-            for (hipEvent_t& e : bs->sdesc_done) if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            bs->sdesc_cap = bytes; bs->n_smooth = 0;
-        }
-        if (pl.mass_rows > bs->mass_rows) {
-            dfree(bs->d_mass); bs->mass_rows = 0;
-            bs->counted.assign(B, 0);                                       // (the rows counted so far went with the table)
-            HIP_TRY(c, hipMalloc(&bs->d_mass, pl.mass_rows * 8 * sizeof(double)));
-            bs->mass_rows = pl.mass_rows;
-        }
-    }
+    bool grew = false;                                                      // (what went with a block is forgotten before a failed allocation returns)
+    HIP_TRY(c, bs->smooth_ring.reserve(c->stream, bytes));
+    HIP_TRY(c, bs->d_sdesc.grow(c->stream, bs->smooth_ring.stride()));      // (a call copies a whole slot)
+    const hipError_t mass_grow = bs->d_mass.grow(c->stream, pl.mass_rows * 8 * sizeof(double), &grew);
+    if (grew) bs->counted.assign(B, 0);                                     // (the rows counted so far went with the table)
+    HIP_TRY(c, mass_grow);
     if (p.decodes()) { if (int rc = batch_decode_prepare(c, pl.word_rows)) return rc; }
-    if (p.kind == BatchPass::OnlineStats && !done && B > bs->tau_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        dfree(bs->d_tau); bs->tau_cap = 0;
-        bs->ostats_done.assign(B, 0);
-        HIP_TRY(c, hipMalloc(&bs->d_tau, B * (size_t)kOnlineTau * sizeof(double)));
-        bs->tau_cap = B;
+    if (p.kind == BatchPass::OnlineStats && !done) {
+        const hipError_t tau_grow = bs->d_tau.grow(c->stream, B * (size_t)kOnlineTau * sizeof(double), &grew);
+        if (grew) bs->ostats_done.assign(B, 0);
+        HIP_TRY(c, tau_grow);
     }
-    const int slot = (int)(bs->n_smooth % BatchState::kOnlineSlots);
-    if (bs->n_smooth >= (uint64_t)BatchState::kOnlineSlots) HIP_TRY(c, hipEventSynchronize(bs->sdesc_done[slot]));
-    char* sl = bs->pin_sdesc + (size_t)slot * bs->sdesc_cap; const size_t thr_at = bs->sdesc_cap - thr_bytes;
+    // the slot's stride, the copy below and the thresholds' place are those of the ring's last growth, not of this call's bytes
+    const size_t slot_bytes = bs->smooth_ring.stride(), thr_at = slot_bytes - thr_bytes;
+    char* sl = nullptr;
+    HIP_TRY(c, bs->smooth_ring.acquire(sl));
     batch_pass_describe(bt, p, reinterpret_cast<BatchSmoothProblem*>(sl), pl);      // (after the growth: it reads the watermarks)
     // CPPROB_HIP_MODEL_HMM3: its thresholds as a table row set of CPPROB_HIP_MODEL_HMM_TABLE ([k][8], entries 0..k-2), behind the descriptors
     uint64_t* h3 = reinterpret_cast<uint64_t*>(sl + thr_at);
     for (int i = 0; i < 64; ++i) h3[i] = ~0ull;
     for (int s2 = 0; s2 < 3; ++s2) for (int j = 0; j < 2; ++j) h3[s2 * 8 + j] = bs->mp.hmm_thr[s2][j];
-    HIP_TRY(c, hipMemcpyAsync(bs->d_sdesc, sl, bs->sdesc_cap, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(bs->sdesc_done[slot], c->stream));
-    ++bs->n_smooth;
-    a.desc = reinterpret_cast<const BatchSmoothProblem*>(bs->d_sdesc);
-    a.values = kept ? nullptr : reinterpret_cast<const int8_t*>(bs->d_ws + bs->lay.values);
-    a.tab = reinterpret_cast<const double*>(bs->d_ws + bs->lay.tab);
-    a.thr = hmm3 ? reinterpret_cast<const uint64_t*>(bs->d_sdesc + thr_at) : reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.thr);
+    HIP_TRY(c, hipMemcpyAsync(bs->d_sdesc.as<char>(), sl, slot_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, bs->smooth_ring.commit(c->stream));
+    a.desc = reinterpret_cast<const BatchSmoothProblem*>(bs->d_sdesc.as<char>());
+    a.values = kept ? nullptr : reinterpret_cast<const int8_t*>(bs->ws() + bs->lay.values);
+    a.tab = reinterpret_cast<const double*>(bs->ws() + bs->lay.tab);
+    a.thr = hmm3 ? reinterpret_cast<const uint64_t*>(bs->d_sdesc.as<char>() + thr_at) : reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.thr);
     a.thr_stride = !hmm3 && bs->described ? 64 : 0;
-    a.seeds = reinterpret_cast<const uint64_t*>(bs->d_ws + bs->lay.seeds);
-    a.mass = kept ? reinterpret_cast<double*>(bs->d_ws + bs->lay.mass) : bs->d_mass; a.marg = p.d_marg; a.traj = p.with_traj() ? p.d_traj : nullptr;
+    a.seeds = reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.seeds);
+    a.mass = kept ? reinterpret_cast<double*>(bs->ws() + bs->lay.mass) : bs->d_mass.as<double>(); a.marg = p.d_marg; a.traj = p.with_traj() ? p.d_traj : nullptr;
     a.draw_base = kBackwardDrawBase + (p.draw_index << 24);
     a.T_max = bs->T; a.k = hmm3 ? 3 : bs->hk; a.spp = bs->K; a.n_traj = (int)p.n_traj;
     a.marg_rows = (int)pl.marg_rows; a.lag = p.lagged() ? pl.lag : 0; a.lds_bytes = pl.lds_bytes;
@@ -4956,7 +4873,7 @@ static int batch_pass_online_stats(cpprob_hip_ctx* c, const BatchPass& p, const 
 {
     BatchState* bs = c->batch; const size_t B = bs->cfg.n_problems;
     BatchOnlineStatsArgs oa{};
-    oa.desc = a.desc; oa.mass = a.mass; oa.thr = a.thr; oa.obs = p.d_obs; oa.tau = bs->d_tau; oa.stats = p.d_stats;
+    oa.desc = a.desc; oa.mass = a.mass; oa.thr = a.thr; oa.obs = p.d_obs; oa.tau = bs->d_tau.as<double>(); oa.stats = p.d_stats;
     oa.B = (int)B; oa.k = a.k; oa.thr_stride = a.thr_stride;
     hipLaunchKernelGGL(batch_online_stats_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, oa);
     HIP_TRY(c, hipGetLastError());
@@ -4988,7 +4905,7 @@ static int batch_pass_decode(cpprob_hip_ctx* c, const BatchPass& p, const BatchP
 {
     BatchState* bs = c->batch; const size_t B = bs->cfg.n_problems;
     BatchDecodeArgs da{};
-    da.desc = a.desc; da.mass = a.mass; da.tab = a.tab; da.lp = bs->d_lp; da.lp0 = bs->lp0; da.v = bs->d_v; da.words = bs->d_words;
+    da.desc = a.desc; da.mass = a.mass; da.tab = a.tab; da.lp = bs->d_lp.as<double>(); da.lp0 = bs->lp0; da.v = bs->d_v.as<double>(); da.words = bs->d_words.as<uint32_t>();
     da.score = p.d_score; da.path = p.d_path;
     da.B = (int)B; da.T_max = a.T_max; da.k = a.k; da.lp_stride = bs->h_lp.size() > 64 ? 64 : 0;
     da.full = p.kind == BatchPass::Decode ? 1 : 0; da.lag = pl.lag; da.n_rows = (int)p.n_rows;
@@ -5334,7 +5251,7 @@ static int batch_decode_table(cpprob_hip_ctx* c)
     if (bs->lp_ready) return 0;
     if (bs->thr_stale) {
         HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipMemcpyAsync(bs->h_thr.data(), bs->d_ws + bs->lay.thr, bs->h_thr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->h_thr.data(), bs->ws() + bs->lay.thr, bs->h_thr.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         bs->thr_stale = false;
     }
@@ -5357,28 +5274,18 @@ static int batch_decode_prepare(cpprob_hip_ctx* c, size_t word_rows)
     const size_t B = bs->cfg.n_problems;
     if (int rc = batch_decode_table(c)) return rc;
     const size_t tables = bs->h_lp.size() / 64;
-    if (word_rows > bs->words_cap || B > bs->v_cap || tables > bs->lp_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));                        // (earlier calls' kernels may still read the buffers this replaces)
-        if (word_rows > bs->words_cap) {
-            dfree(bs->d_words); bs->words_cap = 0;
-            bs->decoded.assign(B, 0);
-            HIP_TRY(c, hipMalloc(&bs->d_words, word_rows * sizeof(uint32_t)));
-            bs->words_cap = word_rows;
-        }
-        if (B > bs->v_cap) {
-            dfree(bs->d_v); bs->v_cap = 0;
-            bs->decoded.assign(B, 0);
-            HIP_TRY(c, hipMalloc(&bs->d_v, B * 8 * sizeof(double)));
-            bs->v_cap = B;
-        }
-        if (tables > bs->lp_cap) {
-            dfree(bs->d_lp); bs->lp_cap = 0; bs->lp_sent = false;
-            HIP_TRY(c, hipMalloc(&bs->d_lp, tables * 64 * sizeof(double)));
-            bs->lp_cap = tables;
-        }
-    }
+    bool grew = false;                                                      // (what went with a block is forgotten before a failed allocation returns)
+    const hipError_t words_grow = bs->d_words.grow(c->stream, word_rows * sizeof(uint32_t), &grew);
+    if (grew) bs->decoded.assign(B, 0);
+    HIP_TRY(c, words_grow);
+    const hipError_t v_grow = bs->d_v.grow(c->stream, B * 8 * sizeof(double), &grew);
+    if (grew) bs->decoded.assign(B, 0);
+    HIP_TRY(c, v_grow);
+    const hipError_t lp_grow = bs->d_lp.grow(c->stream, tables * 64 * sizeof(double), &grew);
+    if (grew) bs->lp_sent = false;
+    HIP_TRY(c, lp_grow);
     if (!bs->lp_sent) {
-        HIP_TRY(c, hipMemcpyAsync(bs->d_lp, bs->h_lp.data(), bs->h_lp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lp.as<double>(), bs->h_lp.data(), bs->h_lp.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         bs->lp_sent = true;
     }
     return 0;
@@ -5533,28 +5440,23 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
-    if (B > bs->rstatus_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        dfree(bs->d_rstatus); bs->rstatus_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_rstatus, B * sizeof(int32_t)));
-        bs->rstatus_cap = B;
-    }
+    HIP_TRY(c, bs->d_rstatus.grow(c->stream, B * sizeof(int32_t)));
     if (int rc = batch_first_entries(c)) return rc;
     const unsigned gy = retable_grid_y(bs->T, (int64_t)B);
     auto common = [&](auto& r) {                                // (what the two forms' arguments share)
-        r.prob = reinterpret_cast<const BatchProblem*>(bs->d_ws + bs->lay.prob);
-        r.first = bs->d_cfirst;
+        r.prob = reinterpret_cast<const BatchProblem*>(bs->ws() + bs->lay.prob);
+        r.first = bs->d_cfirst.as<int64_t>();
         r.means = d_means; r.trans = d_trans; r.obs = d_obs;
-        r.tab = reinterpret_cast<double*>(bs->d_ws + bs->lay.tab);
-        r.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr);
-        r.status = bs->d_rstatus;
+        r.tab = reinterpret_cast<double*>(bs->ws() + bs->lay.tab);
+        r.thr = reinterpret_cast<uint64_t*>(bs->ws() + bs->lay.thr);
+        r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
     if (d_sigmas) {
         // (a scaled batch; the sigmas and log_norms in force are the device's from here on)
         BatchRetableScaledArgs sa{};
         common(sa);
-        sa.sigmas = d_sigmas; sa.sigma_out = bs->d_sigma; sa.log_norm_out = bs->d_lognorm;
+        sa.sigmas = d_sigmas; sa.sigma_out = bs->d_sigma.as<double>(); sa.log_norm_out = bs->d_lognorm.as<double>();
         hipLaunchKernelGGL(batch_retable_scaled_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, sa);
     } else {
         BatchRetableArgs a{};
@@ -5585,13 +5487,11 @@ static int batch_retable_device(cpprob_hip_ctx* c, const double* d_means, const 
 static int batch_retable_observes(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes)
 {
     BatchState* bs = c->batch;
-    if (n_observes > bs->robs_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));           // (an earlier re-table may still read the buffer this replaces)
-        dfree(bs->d_robs); bs->robs_cap = 0; bs->robs_ready = false;
-        HIP_TRY(c, hipMalloc(&bs->d_robs, n_observes * sizeof(double)));
-        bs->robs_cap = n_observes;
-    }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_robs, h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    bool grew = false;
+    const hipError_t robs_grow = bs->d_robs.grow(c->stream, n_observes * sizeof(double), &grew);      // (an earlier re-table may still read the buffer this replaces)
+    if (grew) bs->robs_ready = false;                          // (before a failed allocation returns: the observes went with the block)
+    HIP_TRY(c, robs_grow);
+    HIP_TRY(c, hipMemcpyAsync(bs->d_robs.as<double>(), h_observes, n_observes * sizeof(double), hipMemcpyHostToDevice, c->stream));
     bs->robs_ready = true;
     return 0;
 }
@@ -5617,7 +5517,7 @@ static int batch_retable_host(cpprob_hip_ctx* c, const double* h_means, const do
     HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (scaled) HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs, d_sigmas)) return rc;
+    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs.as<double>(), d_sigmas)) return rc;
     // the host knows the tables: the thresholds' mirror is current again (the rows' is not: cpprob_hip_batch_copy_store fetches its row)
     for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
     if (scaled) batch_mirror_scales(bs, B, k, h_sigmas);
@@ -5656,7 +5556,7 @@ int cpprob_hip_batch_retable_status(cpprob_hip_ctx* c, int32_t* h_status)
     BatchState* bs = c->batch;
     if (!bs || !bs->begun || !bs->retabled) return fail(c, CPPROB_HIP_ESTATE, "the begun batch has not been re-tabled");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(h_status, bs->d_rstatus, bs->cfg.n_problems * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_status, bs->d_rstatus.as<int32_t>(), bs->cfg.n_problems * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -5741,12 +5641,8 @@ int cpprob_hip_batch_tie(cpprob_hip_ctx* c, const int32_t* h_group, size_t n)
     // (a pooling launch of the tie this one replaces may still read the arrays)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->tied = false;
-    if (h.size() > bs->tie_cap) {
-        dfree(bs->d_tie); bs->tie_cap = 0;
-        HIP_TRY(c, hipMalloc(&bs->d_tie, h.size() * sizeof(int32_t)));
-        bs->tie_cap = h.size();
-    }
-    HIP_TRY(c, hipMemcpyAsync(bs->d_tie, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, bs->d_tie.grow(c->stream, h.size() * sizeof(int32_t)));
+    HIP_TRY(c, hipMemcpyAsync(bs->d_tie.as<int32_t>(), h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->tie_map.assign(map, map + B);
     bs->tie_groups = (int32_t)G;
@@ -5793,7 +5689,7 @@ static int batch_pool_enqueue(cpprob_hip_ctx* c, const double* d_records, uint32
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
     BatchPoolArgs a{};
-    a.members = bs->d_tie; a.first = bs->d_tie + B;
+    a.members = bs->d_tie.as<int32_t>(); a.first = bs->d_tie.as<int32_t>() + B;
     a.rec = d_records; a.out = d_out;
     a.pairs = (int64_t)bs->tie_groups * (int64_t)per_problem; a.R = (int)per_problem; a.broadcast = broadcast ? 1 : 0;
     hipLaunchKernelGGL(batch_pool_stats_kernel, dim3((unsigned)((a.pairs + kWaves - 1) / kWaves)), dim3(kThreads), 0, c->stream, a);
@@ -5836,8 +5732,8 @@ int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* c, uint64_t problem, double* h_
     if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t k = (size_t)bs->hk;
-    if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_sigma + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (h_log_norm) HIP_TRY(c, hipMemcpyAsync(h_log_norm, bs->d_lognorm + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_sigma.as<double>() + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_log_norm) HIP_TRY(c, hipMemcpyAsync(h_log_norm, bs->d_lognorm.as<double>() + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -5861,7 +5757,7 @@ int cpprob_hip_batch_learn_begin(cpprob_hip_ctx* c, const double* h_gamma, size_
     BatchState* bs = c->batch;
     if (bs->cfg.keep_history != 1 && !batch_masses(&bs->cfg))
         return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no masses: begin it with CPPROB_HIP_BATCH_KEEP_MASSES");
-    if (bs->n_advance) return fail(c, CPPROB_HIP_ESTATE, "the online batch has been advanced: cpprob_hip_batch_learn_begin comes before the first advance");
+    if (bs->advance_ring.count()) return fail(c, CPPROB_HIP_ESTATE, "the online batch has been advanced: cpprob_hip_batch_learn_begin comes before the first advance");
     if (!h_gamma) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (n_gamma < (size_t)bs->T) return fail(c, CPPROB_HIP_EINVAL, "n_gamma = " + std::to_string(n_gamma) + " lies below the largest capacity, " + std::to_string(bs->T));
     for (size_t t = 0; t < n_gamma; ++t)
@@ -5869,20 +5765,20 @@ int cpprob_hip_batch_learn_begin(cpprob_hip_ctx* c, const double* h_gamma, size_
     HIP_TRY(c, hipSetDevice(c->device));
     batch_learn_free(bs);
     const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
-    HIP_TRY(c, hipMalloc(&bs->d_gamma, n_gamma * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&bs->d_lmeans, B * k * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&bs->d_ltrans, B * k * k * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&bs->d_ltau, B * (size_t)kOnlineTau * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&bs->d_lrec, B * (size_t)kOnlineStats * sizeof(double)));
-    HIP_TRY(c, hipMalloc(&bs->d_lstatus, B * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc(&bs->d_lfirst, B * sizeof(int64_t)));
-    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&bs->pin_lfirst), B * BatchState::kOnlineSlots * sizeof(int64_t), hipHostMallocDefault));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_gamma, h_gamma, n_gamma * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_lmeans, bs->means.data(), B * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ltrans, bs->trans.data(), B * k * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(bs->d_ltau, 0, B * (size_t)kOnlineTau * sizeof(double), c->stream));
-    HIP_TRY(c, hipMemsetAsync(bs->d_lrec, 0, B * (size_t)kOnlineStats * sizeof(double), c->stream));
-    HIP_TRY(c, hipMemsetAsync(bs->d_lstatus, 0, B * sizeof(int32_t), c->stream));
+    HIP_TRY(c, bs->learn.gamma.grow(c->stream, n_gamma * sizeof(double)));
+    HIP_TRY(c, bs->learn.means.grow(c->stream, B * k * sizeof(double)));
+    HIP_TRY(c, bs->learn.trans.grow(c->stream, B * k * k * sizeof(double)));
+    HIP_TRY(c, bs->learn.tau.grow(c->stream, B * (size_t)kOnlineTau * sizeof(double)));
+    HIP_TRY(c, bs->learn.rec.grow(c->stream, B * (size_t)kOnlineStats * sizeof(double)));
+    HIP_TRY(c, bs->learn.status.grow(c->stream, B * sizeof(int32_t)));
+    HIP_TRY(c, bs->learn.first.grow(c->stream, B * sizeof(int64_t)));
+    HIP_TRY(c, bs->learn.pin_first.grow(c->stream, B * BatchState::kOnlineSlots * sizeof(int64_t)));
+    HIP_TRY(c, hipMemcpyAsync(bs->learn.gamma.as<double>(), h_gamma, n_gamma * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->learn.means.as<double>(), bs->means.data(), B * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->learn.trans.as<double>(), bs->trans.data(), B * k * k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->learn.tau.as<double>(), 0, B * (size_t)kOnlineTau * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->learn.rec.as<double>(), 0, B * (size_t)kOnlineStats * sizeof(double), c->stream));
+    HIP_TRY(c, hipMemsetAsync(bs->learn.status.as<int32_t>(), 0, B * sizeof(int32_t), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));               // (h_gamma may be reused when the call returns)
     bs->learn_t_min = t_min; bs->armed = true; bs->learn_scales = false; bs->learn_floor = 0.0;
     return 0;
@@ -5909,15 +5805,15 @@ static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const 
 {
     BatchState* bs = c->batch; const size_t B = bs->cfg.n_problems;
     BatchPassPlan pl; BatchSmoothArgs a{};
-    if (int rc = batch_pass_prologue(c, BatchPass::online_stats(d_obs, bs->d_lrec), pl, a, before)) return rc;
+    if (int rc = batch_pass_prologue(c, BatchPass::online_stats(d_obs, bs->learn.rec.as<double>()), pl, a, before)) return rc;
     if (pl.done) return 0;
     BatchLearnArgs la{};
-    la.desc = a.desc; la.mass = a.mass; la.thr = reinterpret_cast<uint64_t*>(bs->d_ws + bs->lay.thr); la.obs = d_obs; la.gamma = bs->d_gamma;
-    la.tau = bs->d_ltau; la.stats = bs->d_lrec; la.means = bs->d_lmeans; la.trans = bs->d_ltrans; la.status = bs->d_lstatus;
+    la.desc = a.desc; la.mass = a.mass; la.thr = reinterpret_cast<uint64_t*>(bs->ws() + bs->lay.thr); la.obs = d_obs; la.gamma = bs->learn.gamma.as<double>();
+    la.tau = bs->learn.tau.as<double>(); la.stats = bs->learn.rec.as<double>(); la.means = bs->learn.means.as<double>(); la.trans = bs->learn.trans.as<double>(); la.status = bs->learn.status.as<int32_t>();
     la.B = (int)B; la.k = bs->hk; la.t_min = (int)std::min<uint32_t>(bs->learn_t_min, (uint32_t)INT32_MAX);
     if (bs->scaled) {
         BatchLearnScaledArgs ls{};
-        ls.base = la; ls.sigmas = bs->d_sigma; ls.log_norms = bs->d_lognorm; ls.floor = bs->learn_floor; ls.fit = bs->learn_scales ? 1 : 0;
+        ls.base = la; ls.sigmas = bs->d_sigma.as<double>(); ls.log_norms = bs->d_lognorm.as<double>(); ls.floor = bs->learn_floor; ls.fit = bs->learn_scales ? 1 : 0;
         hipLaunchKernelGGL(batch_learn_scaled_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, ls);
     } else
         hipLaunchKernelGGL(batch_learn_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, la);
@@ -5944,15 +5840,15 @@ static int batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const d
     bs->means.assign(h_means, h_means + B * (size_t)k);
     bs->trans.assign(h_transition, h_transition + B * kk);
     for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
-    HIP_TRY(c, hipMemcpyAsync(bs->d_ws + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     if (scaled) {
         batch_mirror_scales(bs, B, k, h_sigmas);
-        HIP_TRY(c, hipMemcpyAsync(bs->d_sigma, bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm, bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_sigma.as<double>(), bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm.as<double>(), bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     if (bs->armed) {
-        HIP_TRY(c, hipMemcpyAsync(bs->d_lmeans, h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(bs->d_ltrans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->learn.means.as<double>(), h_means, B * (size_t)k * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->learn.trans.as<double>(), h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     // the host knows the words again; the decode's log tables and step words follow them
     bs->thr_stale = false; bs->lp_ready = false; bs->lp_sent = false;
@@ -5978,10 +5874,10 @@ static int batch_learn_tables_fetch(cpprob_hip_ctx* c, double* h_means, double* 
     BatchState* bs = c->batch;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
-    if (h_sigmas) HIP_TRY(c, hipMemcpy2DAsync(h_sigmas, k * sizeof(double), bs->d_sigma, 8 * sizeof(double), k * sizeof(double), B, hipMemcpyDeviceToHost, c->stream));
-    if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_lmeans, B * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (h_transition) HIP_TRY(c, hipMemcpyAsync(h_transition, bs->d_ltrans, B * k * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (h_status) HIP_TRY(c, hipMemcpyAsync(h_status, bs->d_lstatus, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (h_sigmas) HIP_TRY(c, hipMemcpy2DAsync(h_sigmas, k * sizeof(double), bs->d_sigma.as<double>(), 8 * sizeof(double), k * sizeof(double), B, hipMemcpyDeviceToHost, c->stream));
+    if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->learn.means.as<double>(), B * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_transition) HIP_TRY(c, hipMemcpyAsync(h_transition, bs->learn.trans.as<double>(), B * k * k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_status) HIP_TRY(c, hipMemcpyAsync(h_status, bs->learn.status.as<int32_t>(), B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -6009,9 +5905,9 @@ static int batch_learn_tables_copy(cpprob_hip_ctx* c, double* d_means, double* d
     BatchState* bs = c->batch;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
-    if (d_sigmas) HIP_TRY(c, hipMemcpy2DAsync(d_sigmas, k * sizeof(double), bs->d_sigma, 8 * sizeof(double), k * sizeof(double), B, hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_means, bs->d_lmeans, B * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_transition, bs->d_ltrans, B * k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (d_sigmas) HIP_TRY(c, hipMemcpy2DAsync(d_sigmas, k * sizeof(double), bs->d_sigma.as<double>(), 8 * sizeof(double), k * sizeof(double), B, hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_means, bs->learn.means.as<double>(), B * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_transition, bs->learn.trans.as<double>(), B * k * k * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return 0;
 }
 
@@ -6048,7 +5944,7 @@ int cpprob_hip_batch_learn_record(cpprob_hip_ctx* c, double* h_stats, size_t n_d
     const size_t need = (size_t)bs->cfg.n_problems * kOnlineStats;
     if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(h_stats, bs->d_lrec, need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_stats, bs->learn.rec.as<double>(), need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -6066,8 +5962,8 @@ int cpprob_hip_batch_copy_step_tables(cpprob_hip_ctx* c, uint64_t problem, doubl
     if (n_doubles < T * kBatchTab) return fail(c, CPPROB_HIP_EINVAL, "h_rows too small: " + std::to_string(T * kBatchTab) + " doubles (8 a step of the problem)");
     if (T && !h_rows) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     HIP_TRY(c, hipSetDevice(c->device));
-    if (T) HIP_TRY(c, hipMemcpyAsync(h_rows, bs->d_ws + bs->lay.tab + (size_t)problem * (size_t)bs->T * kBatchTab * sizeof(double), T * kBatchTab * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (h_thr) HIP_TRY(c, hipMemcpyAsync(h_thr, bs->d_ws + bs->lay.thr + (bs->described ? (size_t)problem : 0) * 64 * sizeof(uint64_t), 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (T) HIP_TRY(c, hipMemcpyAsync(h_rows, bs->ws() + bs->lay.tab + (size_t)problem * (size_t)bs->T * kBatchTab * sizeof(double), T * kBatchTab * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_thr) HIP_TRY(c, hipMemcpyAsync(h_thr, bs->ws() + bs->lay.thr + (bs->described ? (size_t)problem : 0) * 64 * sizeof(uint64_t), 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -6082,7 +5978,7 @@ int cpprob_hip_batch_summaries_device(cpprob_hip_ctx* c, double* d_out)
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t B = (int64_t)bs->cfg.n_problems, total = B * 4;
     hipLaunchKernelGGL(batch_pack_kernel, dim3((unsigned)((total + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
-                       (const char*)(bs->d_ws + bs->lay.ctrl), (const double*)(bs->d_ws + bs->lay.stats), 0, B, d_out);
+                       (const char*)(bs->ws() + bs->lay.ctrl), (const double*)(bs->ws() + bs->lay.stats), 0, B, d_out);
     HIP_TRY(c, hipGetLastError());
     return 0;
 }

@@ -104,7 +104,7 @@ def test_the_library_words_every_refusal_with_its_code():
                         ("CPPROB_HIP_EINVAL", "lies outside \\(0, 1\\]")):
         assert re.search(r"fail\(c, %s, [^\n]*%s" % (code, words), arm), words
     # nothing is allocated, freed or enqueued before every check has passed
-    assert arm.index("lies outside") < arm.index("batch_learn_free(") < arm.index("hipMalloc")
+    assert arm.index("lies outside") < arm.index("batch_learn_free(") < arm.index(".grow(") and "hipMalloc" not in arm
     adv = _body(hip, "static int batch_advance")
     for code, words in (("CPPROB_HIP_ESTATE", "the online batch is not armed"),
                         ("CPPROB_HIP_ESTATE", "it is advanced by cpprob_hip_batch_advance_learn"),
@@ -140,11 +140,17 @@ def test_a_learning_advance_leaves_the_mirrors_stale_and_a_begin_disarms():
     assert "bs->tab_stale = true;" in adv and adv.index("hipLaunchKernelGGL(batch_learn_rows_kernel") < adv.index("batch_launch(c, bs, readout != 0)") < adv.index("batch_learn_enqueue(")
     enq = _body(hip, "static int batch_learn_enqueue")
     assert "bs->thr_stale = true; bs->lp_ready = false; bs->lp_sent = false;" in enq and "bs->decoded.assign(B, 0);" in enq
-    assert "hipStreamSynchronize" not in enq and "batch_pass_prologue(" in enq
+    assert "hipStreamSynchronize" not in enq and ".grow(" not in enq and "batch_pass_prologue(" in enq
     begin = _body(hip, "int batch_begin")
     assert "if (bs->armed) batch_learn_free(bs);" in begin
+    # the learner's allocations are owning members of the state: disarming releases them, batch_free deletes the state
+    state = re.search(r"^struct BatchState \{.*?^\};", hip, re.M | re.S).group(0)
+    learner = re.search(r"struct Learner \{.*?\} learn;", state, re.S).group(0)
+    assert "DeviceBuffer gamma, means, trans, tau, rec, obs, status, first;" in learner and "PinnedBuffer pin_first;" in learner
+    disarm = _body(hip, "void batch_learn_free")
+    assert "bs->learn.release();" in disarm and "bs->armed = false;" in disarm
     free = _body(hip, "void batch_free")
-    assert "batch_learn_free(c->batch);" in free
+    assert "delete c->batch;" in free and "dfree(" not in free
     # batch_smc_kernel is launched where it was: by batch_launch alone
     assert hip.count("hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kThreads), (size_t)batch_lds_bytes(a.n), c->stream, a);") == 1
 

@@ -99,17 +99,21 @@ def test_the_library_words_every_refusal_and_resets_the_state_of_a_begin():
     for name in ("batch_retable_device", "batch_retable_host"):
         body = re.search(r"^static int %s\(.*?^\}" % name, hip, re.M | re.S).group(0)
         assert body.index("batch_retable_check(") < body.index("batch_retable_enqueue(")
-        sync = body.count("hipStreamSynchronize") + (observes.count("hipStreamSynchronize") if name == "batch_retable_host" else 0)
-        assert sync == (1 if name == "batch_retable_host" else 0)                                          # (the observes' buffer, where it has to grow)
+        # no wait of its own; one growth -- the observes' buffer -- in the host form, none in the device form (a growth waits for the
+        # stream: csrc/batch_buffers.hpp, tests/test_batch_buffers_host.py)
+        assert "hipStreamSynchronize" not in body and "hipStreamSynchronize" not in observes and "hipMalloc" not in body + observes
+        grows = body.count(".grow(") + (observes.count(".grow(") if name == "batch_retable_host" else 0)
+        assert grows == (1 if name == "batch_retable_host" else 0)
         assert ("batch_retable_observes(" in body) == (name == "batch_retable_host")
     host = re.search(r"^static int batch_retable_host\(.*?^\}", hip, re.M | re.S).group(0)
-    assert "hipMemcpyAsync" in observes and host.count("batch_retable_observes(") == 1
+    assert "hipMemcpyAsync" in observes and host.count("batch_retable_observes(") == 1 and "bs->d_robs.grow(c->stream, " in observes
     assert host.index("batch_check_tables(") < host.index("batch_check_scales(") < host.index("batch_retable_observes(") < host.index("hipMemcpyAsync")
     assert "batch_stage(" in host and "bs->thr_stale = false;" in host
     enq = re.search(r"^static int batch_retable_enqueue\(.*?^\}", hip, re.M | re.S).group(0)
     for line in ("bs->ran = false; bs->conditional = false;", "bs->lp_ready = false; bs->lp_sent = false;", "bs->tab_stale = true; bs->thr_stale = true;"):
         assert line in enq, line
-    assert "cfirst_ready = false" not in enq and "hipStreamSynchronize" in enq and enq.count("hipStreamSynchronize") == 1      # (the status words' growth alone)
+    assert "cfirst_ready = false" not in enq and "hipStreamSynchronize" not in enq and "hipMalloc" not in enq
+    assert enq.count(".grow(") == 1 and "bs->d_rstatus.grow(c->stream, " in enq                              # (the status words' growth alone)
     # the two host paths that read the mirrors fetch from the device when they are stale; nothing else names the mirrors
     store = re.search(r"^int cpprob_hip_batch_copy_store\(.*?^\}", hip, re.M | re.S).group(0)
     assert "bs->tab_stale ? fetched" in store

@@ -61,10 +61,10 @@ def test_the_entry_points_text():
     hip = _hip()
     # the device form is enqueued: it waits for nothing, and nothing is enqueued before the check has passed
     dev = _fn(hip, "int cpprob_hip_batch_pool_stats_device")
-    assert "hipStreamSynchronize" not in dev and "hipDeviceSynchronize" not in dev and "hipMalloc" not in dev
+    assert "hipStreamSynchronize" not in dev and "hipDeviceSynchronize" not in dev and "hipMalloc" not in dev and ".grow(" not in dev
     assert dev.index("batch_pool_check(") < dev.index("batch_pool_enqueue(")
     enq = _fn(hip, "static int batch_pool_enqueue")
-    assert "hipStreamSynchronize" not in enq and "hipMalloc" not in enq and "hipLaunchKernelGGL(batch_pool_stats_kernel" in enq and "c->stream" in enq
+    assert "hipStreamSynchronize" not in enq and "hipMalloc" not in enq and ".grow(" not in enq and "hipLaunchKernelGGL(batch_pool_stats_kernel" in enq and "c->stream" in enq
     host = _fn(hip, "int cpprob_hip_batch_pool_stats")
     assert host.index("batch_pool_check(") < host.index("batch_stage(") < host.index("hipMemcpyAsync") < host.index("batch_pool_enqueue(") < host.index("batch_fetch(")
     check = _fn(hip, "static int batch_pool_check")
@@ -75,14 +75,16 @@ def test_the_entry_points_text():
     assert "hipMemcpy" not in check and "hipLaunch" not in check
     # the tie: validated before anything changes; any begin forgets it; a re-table does not name it
     tie = _fn(hip, "int cpprob_hip_batch_tie")
-    assert tie.rindex("return fail(") < tie.index("hipStreamSynchronize") < tie.index("bs->tied = false;") < tie.index("hipMemcpyAsync") < tie.index("bs->tied = true;")
+    assert tie.rindex("return fail(") < tie.index("hipStreamSynchronize") < tie.index("bs->tied = false;") < tie.index("bs->d_tie.grow(c->stream, ") < tie.index("hipMemcpyAsync") \
+        < tie.index("bs->tied = true;")
+    assert tie.count(".grow(") == 1 and "hipMalloc" not in tie
     for code, words in (("CPPROB_HIP_ESTATE", "no batch is begun"), ("CPPROB_HIP_EINVAL", "the begun batch has"), ("CPPROB_HIP_EINVAL", "negative group id"), ("CPPROB_HIP_EINVAL", "is unused")):
         assert re.search(r"fail\(c, %s, \"[^\n]*%s" % (code, re.escape(words)), tie), words
     get = _fn(hip, "int cpprob_hip_batch_tie_get")
     assert "hip" not in get.replace("cpprob_hip", "").replace("CPPROB_HIP", "")          # host only
     begin = _fn(hip, "int batch_begin")
     assert "bs->tied = false; bs->tie_groups = 0; bs->tie_map.clear();" in begin
-    assert begin.index("bs->tied = false;") < begin.index("hipMalloc")
+    assert begin.index("bs->tied = false;") < begin.index(".grow(") and begin.index("bs->tied = false;") < begin.index(".reserve(") and "hipMalloc" not in begin
     for name in ("static int batch_retable_enqueue", "int cpprob_hip_batch_retable", "int cpprob_hip_batch_retable_device", "int cpprob_hip_batch_retable_scaled",
                  "int cpprob_hip_batch_retable_scaled_device", "static int batch_retable_check", "static int batch_retable_device", "static int batch_retable_host",
                  "static int batch_retable_observes"):
@@ -90,7 +92,11 @@ def test_the_entry_points_text():
     # arrays of the context's own: no workspace region is added
     layout = re.search(r"^struct BatchLayout \{[^\n]*\};", hip, re.M).group(0)
     assert layout == "struct BatchLayout { size_t tab, seeds, thr, ctrl, stats, ess, res, nreq, prob, order, values, anc, first, snap, carry, mass, total; };"
-    assert "dfree(c->batch->d_tie);" in _fn(hip, "void batch_free")
+    # ... one the state owns: declared an owning buffer in BatchState, freed when batch_free deletes the state
+    state = re.search(r"^struct BatchState \{.*?^\};", hip, re.M | re.S).group(0)
+    assert re.search(r"^    DeviceBuffer d_tie;$", state, re.M) and "int32_t* d_tie" not in state
+    free = _fn(hip, "void batch_free")
+    assert "delete c->batch;" in free and "dfree(" not in free and "hipFree" not in free
 
 
 def test_drivers_take_groups_and_default_to_the_untied_loops():
