@@ -59,6 +59,7 @@ SYMBOLS = [
     "cpprob_hip_batch_online_tables_scaled", "cpprob_hip_batch_copy_scales",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
+    "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
 ]
 
 
@@ -415,6 +416,8 @@ def load_library(path=None):
         "cpprob_hip_batch_tie_get": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32)]),
         "cpprob_hip_batch_pool_stats": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_int, vp, sz]),
         "cpprob_hip_batch_pool_stats_device": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_int, vp, sz]),
+        "cpprob_hip_batch_learn_tie": (C.c_int, [vp]),
+        "cpprob_hip_batch_learn_pooled_record": (C.c_int, [vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -856,17 +859,20 @@ class Engine:
         self.batch_k = means.shape[1]
         return means, trans
 
-    def batch_learn_begin(self, gamma, t_min, sigma_floor=None):
+    def batch_learn_begin(self, gamma, t_min, sigma_floor=None, tied=False):
         """Arms the online MODEL_HMM_TABLE batch just begun (per-problem tables; before its first advance) for online EM
         (cpprob_hip_batch_learn_begin): gamma[t] in (0, 1], the step size of a problem's absolute step t, at least as long as the
         largest capacity; t_min: the length a problem must have reached before its first M-step.  sigma_floor (a batch begun with
         emission scales): the learner fits the sigmas too, none below it (cpprob_hip_batch_learn_begin_scaled); None on such a batch:
-        means and transition rows are learned and the sigmas stay."""
+        means and transition rows are learned and the sigmas stay.  tied=True (a batch with a tie, batch_tie): the learner pools over
+        the tie -- the streams of a group learn one table, t_min counts the group's observes (cpprob_hip_batch_learn_tie)."""
         g = np.ascontiguousarray(gamma, np.float64).reshape(-1)
         if sigma_floor is not None:
             self._chk(self.L.cpprob_hip_batch_learn_begin_scaled(self.h, g.ctypes.data if g.size else None, g.size, int(t_min), float(sigma_floor)))
         else:
             self._chk(self.L.cpprob_hip_batch_learn_begin(self.h, g.ctypes.data if g.size else None, g.size, int(t_min)))
+        if tied:
+            self._chk(self.L.cpprob_hip_batch_learn_tie(self.h))
 
     def _batch_new_observes(self, new_observes):
         seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in new_observes]
@@ -927,6 +933,13 @@ class Engine:
         """float64 [B, 88]: the records of the last learning advance (cpprob_hip_batch_learn_record).  Synchronises."""
         out = np.zeros((self.batch_B, 88))
         self._chk(self.L.cpprob_hip_batch_learn_record(self.h, out.ctypes.data, out.size))
+        return out
+
+    def batch_learn_pooled_record(self):
+        """float64 [G, 88]: the groups' pooled records of the last tied learning advance (cpprob_hip_batch_learn_pooled_record).
+        Synchronises."""
+        out = np.zeros((self.batch_tie_get()[1], 88))
+        self._chk(self.L.cpprob_hip_batch_learn_pooled_record(self.h, out.ctypes.data, out.size))
         return out
 
     def batch_step_tables(self, b):

@@ -31,6 +31,7 @@
 #include "batch_retable.hpp"
 #include "batch_scale.hpp"
 #include "batch_learn.hpp"
+#include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
 #include "batch_buffers.hpp"
 #include "batch_pool.hpp"
@@ -1127,12 +1128,15 @@ struct BatchState {
     // the learner's tau [B][8][88], the records [B][88], the status words [B], the first new observes of an advance ([B] int64, with
     // their pinned sources, kOnlineSlots in turn as an advance's descriptors) and the host form's copy of an advance's observes,
     // allocations of the context's own, in the order above
-    bool own_tables = false, armed = false;
+    // learn_tied: the armed batch's learner pools over the tie in force (cpprob_hip_batch_learn_tie; csrc/batch_learn_tied.hpp): the streams
+    // of a group learn one table; arming again or any begin clears it
+    bool own_tables = false, armed = false, learn_tied = false;
     uint32_t learn_t_min = 0;
     struct Learner {
         DeviceBuffer gamma, means, trans, tau, rec, obs, status, first;
         PinnedBuffer pin_first;
-        void release() { for (DeviceBuffer* b : {&gamma, &means, &trans, &tau, &rec, &obs, &status, &first}) b->release(); pin_first.release(); }
+        DeviceBuffer pooled;                                // tied online EM (cpprob_hip_batch_learn_tie): the groups' pooled records [G][88]
+        void release() { for (DeviceBuffer* b : {&gamma, &means, &trans, &tau, &rec, &obs, &status, &first, &pooled}) b->release(); pin_first.release(); }
     } learn;
     // per-state emission scales (cpprob_hip_batch_begin_problems_scaled, _begin_online_scaled; csrc/batch_scale.hpp): scaled: the begun
     // batch has them; the sigmas and log_norms in force, [B][8] (states >= k zero), on the host as the last begin or host call
@@ -1157,7 +1161,7 @@ struct BatchState {
 void batch_learn_free(BatchState* bs)
 {
     bs->learn.release();
-    bs->armed = false;
+    bs->armed = false; bs->learn_tied = false;
 }
 
 // The state goes with everything it owns.  The workspace first: hipFree waits for the device, so no copy still reads a pinned buffer
@@ -5618,6 +5622,7 @@ int cpprob_hip_batch_tie(cpprob_hip_ctx* c, const int32_t* h_group, size_t n)
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->learn_tied) return fail(c, CPPROB_HIP_ESTATE, "the batch's learner pools over the tie in force (cpprob_hip_batch_learn_tie): arm it again before a new tie");
     if (!h_group) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     const size_t B = bs->cfg.n_problems;
     if (n != B) return fail(c, CPPROB_HIP_EINVAL, "n = " + std::to_string(n) + ", the begun batch has " + std::to_string(B) + " problems");
@@ -5798,6 +5803,64 @@ int cpprob_hip_batch_learn_begin_scaled(cpprob_hip_ctx* c, const double* h_gamma
     return 0;
 }
 
+// Tied online EM: the members of every group of the tie in force hold one table bit for bit (sigmas: given on a scaled batch), or
+// CPPROB_HIP_EINVAL naming the first problem that differs.  It writes nothing.
+static int batch_tied_tables_check(cpprob_hip_ctx* c, const double* means, const double* trans, const double* sigmas, size_t k)
+{
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    std::vector<size_t> lead((size_t)bs->tie_groups, B);
+    for (size_t b = 0; b < B; ++b) {
+        const size_t g = (size_t)bs->tie_map[b];
+        if (lead[g] == B) { lead[g] = b; continue; }
+        const size_t a = lead[g];
+        const bool same = std::memcmp(means + a * k, means + b * k, k * sizeof(double)) == 0 &&
+                          std::memcmp(trans + a * k * k, trans + b * k * k, k * k * sizeof(double)) == 0 &&
+                          (!sigmas || std::memcmp(sigmas + a * k, sigmas + b * k, k * sizeof(double)) == 0);
+        if (!same)
+            return fail(c, CPPROB_HIP_EINVAL, "group " + std::to_string(g) + ": the table of problem " + std::to_string(b) + " differs from that of problem " + std::to_string(a) +
+                                                  "; under tied online EM a group's members hold one table");
+    }
+    return 0;
+}
+
+// Tied online EM: the armed batch's learner pools over the tie in force from its first advance on (csrc/batch_learn_tied.hpp).
+int cpprob_hip_batch_learn_tie(cpprob_hip_ctx* c)
+{
+    LANES_OWN(c);
+    if (int rc = batch_learn_check(c, "cpprob_hip_batch_learn_tie")) return rc;
+    BatchState* bs = c->batch;
+    if (!bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the online batch is not armed: call cpprob_hip_batch_learn_begin before cpprob_hip_batch_learn_tie");
+    if (!bs->tied) return fail(c, CPPROB_HIP_ESTATE, "the begun batch has no tie: call cpprob_hip_batch_tie before cpprob_hip_batch_learn_tie");
+    if (bs->advance_ring.count()) return fail(c, CPPROB_HIP_ESTATE, "the online batch has been advanced: cpprob_hip_batch_learn_tie comes before the first advance");
+    const size_t B = bs->cfg.n_problems, k = (size_t)bs->hk;
+    std::vector<double> sg;                                     // (the mirror keeps 8 sigmas a problem)
+    if (bs->scaled) { sg.resize(B * k); for (size_t b = 0; b < B; ++b) std::copy(bs->sigmas.begin() + (ptrdiff_t)(b * 8), bs->sigmas.begin() + (ptrdiff_t)(b * 8 + k), sg.begin() + (ptrdiff_t)(b * k)); }
+    if (int rc = batch_tied_tables_check(c, bs->means.data(), bs->trans.data(), bs->scaled ? sg.data() : nullptr, k)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)bs->tie_groups * kPoolStats * sizeof(double);
+    HIP_TRY(c, bs->learn.pooled.grow(c->stream, bytes));
+    HIP_TRY(c, hipMemsetAsync(bs->learn.pooled.as<double>(), 0, bytes, c->stream));
+    bs->learn_tied = true;
+    return 0;
+}
+
+// The groups' pooled records [G][88] of the last tied learning advance (none yet: zeros).  Synchronises.
+int cpprob_hip_batch_learn_pooled_record(cpprob_hip_ctx* c, double* h_out, size_t n_doubles)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun || !bs->armed || !bs->learn_tied) return fail(c, CPPROB_HIP_ESTATE, "the begun batch's learner does not pool: call cpprob_hip_batch_learn_tie");
+    if (!h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const size_t need = (size_t)bs->tie_groups * kPoolStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the output is too small: " + std::to_string(need) + " doubles (88 a group)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(h_out, bs->learn.pooled.as<double>(), need * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 // The learn step of a learning advance, behind its launch: the prologue of a running-statistics pass that resumes from the lengths
 // before the advance (a batch with a particle store: the counting pass over the new rows first), then batch_learn_kernel.  The
 // thresholds and, through them, the decode's log tables and step words are the device's from here on.
@@ -5810,14 +5873,30 @@ static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const 
     BatchLearnArgs la{};
     la.desc = a.desc; la.mass = a.mass; la.thr = reinterpret_cast<uint64_t*>(bs->ws() + bs->lay.thr); la.obs = d_obs; la.gamma = bs->learn.gamma.as<double>();
     la.tau = bs->learn.tau.as<double>(); la.stats = bs->learn.rec.as<double>(); la.means = bs->learn.means.as<double>(); la.trans = bs->learn.trans.as<double>(); la.status = bs->learn.status.as<int32_t>();
-    la.B = (int)B; la.k = bs->hk; la.t_min = (int)std::min<uint32_t>(bs->learn_t_min, (uint32_t)INT32_MAX);
-    if (bs->scaled) {
-        BatchLearnScaledArgs ls{};
-        ls.base = la; ls.sigmas = bs->d_sigma.as<double>(); ls.log_norms = bs->d_lognorm.as<double>(); ls.floor = bs->learn_floor; ls.fit = bs->learn_scales ? 1 : 0;
+    la.B = (int)B; la.k = bs->hk; la.t_min = bs->learn_tied ? INT32_MAX : (int)std::min<uint32_t>(bs->learn_t_min, (uint32_t)INT32_MAX);
+    BatchLearnScaledArgs ls{};
+    ls.base = la; ls.sigmas = bs->d_sigma.as<double>(); ls.log_norms = bs->d_lognorm.as<double>(); ls.floor = bs->learn_floor; ls.fit = bs->learn_scales ? 1 : 0;
+    if (bs->scaled)
         hipLaunchKernelGGL(batch_learn_scaled_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, ls);
-    } else
+    else
         hipLaunchKernelGGL(batch_learn_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, la);
     HIP_TRY(c, hipGetLastError());
+    if (bs->learn_tied) {
+        // tied: step (c) never fired above; the groups' pooled records, then one M-step a group and its broadcast (csrc/batch_learn_tied.hpp)
+        if (int rc = batch_pool_enqueue(c, bs->learn.rec.as<double>(), 1, 0, bs->learn.pooled.as<double>())) return rc;
+        BatchLearnTiedScaledArgs ts{};
+        BatchLearnTiedArgs& ta = ts.base;
+        ta.members = bs->d_tie.as<int32_t>(); ta.first = bs->d_tie.as<int32_t>() + B; ta.desc = a.desc; ta.pooled = bs->learn.pooled.as<double>();
+        ta.thr = la.thr; ta.means = la.means; ta.trans = la.trans; ta.status = la.status;
+        ta.t_min = (int64_t)bs->learn_t_min; ta.G = (int)bs->tie_groups; ta.k = bs->hk;
+        ts.sigmas = ls.sigmas; ts.log_norms = ls.log_norms; ts.floor = ls.floor; ts.fit = ls.fit;
+        const dim3 tied_grid((unsigned)((bs->tie_groups + kWaves - 1) / kWaves));
+        if (bs->scaled)
+            hipLaunchKernelGGL(batch_learn_tied_scaled_kernel, tied_grid, dim3(kThreads), 0, c->stream, ts);
+        else
+            hipLaunchKernelGGL(batch_learn_tied_kernel, tied_grid, dim3(kThreads), 0, c->stream, ta);
+        HIP_TRY(c, hipGetLastError());
+    }
     bs->thr_stale = true; bs->lp_ready = false; bs->lp_sent = false;
     bs->decoded.assign(B, 0);
     return 0;
@@ -5835,6 +5914,7 @@ static int batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const d
     int k = 0;
     if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
     if (scaled) if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
+    if (bs->learn_tied) if (int rc = batch_tied_tables_check(c, h_means, h_transition, scaled ? h_sigmas : nullptr, (size_t)k)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
     bs->means.assign(h_means, h_means + B * (size_t)k);

@@ -49,7 +49,9 @@
 //                   --tie_tables / --tie_groups "[g_0 g_1 ..]" (with --em_iterations: tied tables -- all problems, or the problems with
 //                   one group id (ids 0 .. G-1, every id used, one a problem), share one table fitted to all of their observes,
 //                   cpprob::gpu::Options::tie_groups; their input tables must be equal; the output format is unchanged, the members of
-//                   a group print the same fitted table)
+//                   a group print the same fitted table; with --online_em --stream_chunk K: tied online EM -- the streams of a group
+//                   learn one table on the device from their pooled records, cpprob::gpu::Options::learn_tied, and --em_burn_in counts
+//                   the observes a group has seen)
 //                   --running_stats (with --batch_tables_file --stream_chunk K: every chunk is followed by the forward-only update of the
 //                   expected sufficient statistics, at the cost of the chunk's steps; after everything else one line a problem, the
 //                   record of the lengths reached in --trajectory_stats' format)
@@ -469,10 +471,11 @@ int main(int argc, char** argv)
         std::cerr << "--learn_scales fits the sigmas of --emission_scales: set it with --em_iterations or --online_em" << std::endl;
         return EXIT_FAILURE;
     }
-    if ((a.tie_tables || !a.tie_groups.empty()) && a.em_iterations == 0) {
-        std::cerr << "--tie_tables / --tie_groups tie the tables of a fit: set --em_iterations" << std::endl;
+    if ((a.tie_tables || !a.tie_groups.empty()) && a.em_iterations == 0 && !opt.learn_tables) {
+        std::cerr << "--tie_tables / --tie_groups tie the tables of a fit: set --em_iterations, or --online_em with --stream_chunk" << std::endl;
         return EXIT_FAILURE;
     }
+    if ((a.tie_tables || !a.tie_groups.empty()) && opt.learn_tables) opt.learn_tied = true;      // --online_em: the streams of a group learn one table
     if (a.tie_tables && !a.tie_groups.empty()) { std::cerr << "--tie_tables is --tie_groups of all zeros: set one of them" << std::endl; return EXIT_FAILURE; }
     if (opt.fit_on_device && a.em_iterations == 0) { std::cerr << "--em_on_device re-tables the batch of a fit: set --em_iterations" << std::endl; return EXIT_FAILURE; }
     if ((opt.forecast_horizon || opt.forecast_trajectories) && a.batch_tables_file.empty() && a.batch_observes_file.empty()) {

@@ -1110,6 +1110,10 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // Tables with emission scales (HmmTable::sigmas): the stream is a scaled one (cpprob_hip_batch_begin_online_scaled); with
 // options().learn_tables and options().learn_scales the learner fits the scales too, none below options().scale_floor
 // (cpprob_hip_batch_learn_begin_scaled) -- without learn_scales it learns means and transition rows and keeps them; tables() returns them.
+// options().learn_tables with options().tie_groups (one group id a problem; options().learn_tied asks for them): tied online EM -- the
+// stream is tied and its learner pools over the tie (cpprob_hip_batch_tie, _learn_tie): the streams of a group, which must start from one
+// table bit for bit, learn ONE table from their pooled records, every stream weighing equally whatever its length; the burn-in counts the
+// observes the group has seen; tables() returns equal tables for the members of a group.
 // Options are read once, by the constructor.  The object holds
 // one context until it is destroyed.
 class HmmTableStream {
@@ -1181,6 +1185,13 @@ public:
                 ctx.check(cpprob_hip_batch_learn_begin_scaled(ctx.get(), gamma.data(), gamma.size(), burn_in, opt.scale_floor), "cpprob_hip_batch_learn_begin_scaled");
             else
                 ctx.check(cpprob_hip_batch_learn_begin(ctx.get(), gamma.data(), gamma.size(), burn_in), "cpprob_hip_batch_learn_begin");
+            if (opt.learn_tied || !opt.tie_groups.empty()) {
+                // tied online EM: the streams of a group learn one table (the library checks that they start from one, bit for bit)
+                if (opt.tie_groups.size() != B_)
+                    throw std::runtime_error("cpprob::gpu::HmmTableStream: options().tie_groups holds " + std::to_string(opt.tie_groups.size()) + " ids for " + std::to_string(B_) + " problems");
+                ctx.check(cpprob_hip_batch_tie(ctx.get(), opt.tie_groups.data(), opt.tie_groups.size()), "cpprob_hip_batch_tie");
+                ctx.check(cpprob_hip_batch_learn_tie(ctx.get()), "cpprob_hip_batch_learn_tie");
+            }
         }
         lease_.done();
         if (lag_ >= 0) { lagged_.assign(B_ * T_max_ * 8, 0.0); L_prev_.assign(B_, 0); }

@@ -58,6 +58,10 @@ struct Options {
                                                       // scales are fitted too (the M-step's sigma' = sqrt(occ_yy / occ - mean'^2)), none below scale_floor
     double scale_floor = 1e-3;                        // ... finite and > 0
     std::size_t learn_burn_in = 20;                   // ... and no M-step before a problem has reached this length
+    bool learn_tied = false;                          // HmmTableStream with learn_tables: tied online EM -- tie_groups (then required) partitions the streams,
+                                                      // and the streams of a group learn ONE table on the device from their pooled records
+                                                      // (cpprob_hip_batch_learn_tie); learn_burn_in then counts the observes a group has seen.  A
+                                                      // non-empty tie_groups asks for the same
     bool map_decode = false;                          // batched runs (keep_history, or keep_masses): every result carries Result::map_path, the single most
                                                       // probable state sequence given the observes over the states the particles occupy, and
                                                       // Result::map_score (cpprob_hip_batch_decode); hmm_table_fit decodes under the fitted tables

@@ -865,6 +865,27 @@ int cpprob_hip_batch_pool_stats_device(cpprob_hip_ctx* ctx, const double* d_reco
 int cpprob_hip_batch_pool_stats(cpprob_hip_ctx* ctx, const double* h_records, size_t n_doubles, uint32_t per_problem, int broadcast,
                                 double* h_out, size_t n_out);
 
+/* ---- tied online EM: the streams of a group learn one table on the device (csrc/batch_learn_tied.hpp) --
+ * cpprob_hip_batch_learn_tie tells the learner of a begun, armed (cpprob_hip_batch_learn_begin*) and tied (cpprob_hip_batch_tie) online
+ * batch to pool over the tie in force, before its first advance.  A learning advance then runs, stream-ordered and without a look from
+ * the host: the rows and the run as before; every problem's discounted push and record (tau and the record of
+ * cpprob_hip_batch_learn_record are what an untied learner would hold under the same tables); the pooled records, compact and with R = 1
+ * (pooled[g][e] = ((0.0 + rec[b_0][e]) + rec[b_1][e]) + ... over the members b_0 < b_1 < ...; a member of length 0 contributes zeros);
+ * and one M-step a group.  Group g fires in an advance iff some member received observes in it AND the members' lengths reached, summed,
+ * are >= t_min.  A firing group runs the M-step on pooled[g] from the table of its first member (with the sigmas on a scaled learner
+ * that fits them) and checks it (the bits of cpprob_hip_batch_learn_tables): no bit set -- every member receives the new table, the
+ * scales where fitted, its 64 threshold words and status 0; a bit set -- every member's status word receives the bits and nothing else
+ * changes.  A group that does not fire keeps tables, words and status words.  Every stream's record is a convex running average, so the
+ * streams of a group weigh equally whatever their lengths; weighting by length is not built.  With every problem its own group this is
+ * the untied learner.
+ * CPPROB_HIP_ESTATE, naming the missing call: the batch is not armed, has no tie, or has been advanced.  CPPROB_HIP_EINVAL naming the
+ * first problem that differs: the members of a group do not hold one table (and, on a scaled batch, one set of sigmas) bit for bit.
+ * While the learner pools, cpprob_hip_batch_tie is CPPROB_HIP_ESTATE and cpprob_hip_batch_online_tables* is CPPROB_HIP_EINVAL for tables
+ * that differ within a group; arming again, or any begin, ends it. */
+int cpprob_hip_batch_learn_tie(cpprob_hip_ctx* ctx);
+/* The groups' pooled records [G][88] of the last tied learning advance (n_doubles >= 88 G; none yet: zeros).  Synchronises. */
+int cpprob_hip_batch_learn_pooled_record(cpprob_hip_ctx* ctx, double* h_out, size_t n_doubles);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
