@@ -57,6 +57,9 @@ SYMBOLS = [
     "cpprob_hip_table_log", "cpprob_hip_batch_begin_problems_scaled", "cpprob_hip_batch_begin_online_scaled",
     "cpprob_hip_batch_retable_scaled", "cpprob_hip_batch_retable_scaled_device", "cpprob_hip_batch_mstep_scaled_device",
     "cpprob_hip_batch_online_tables_scaled", "cpprob_hip_batch_copy_scales",
+    "cpprob_hip_batch_begin_problems_poisson", "cpprob_hip_batch_begin_online_poisson", "cpprob_hip_batch_retable_poisson",
+    "cpprob_hip_batch_retable_poisson_device", "cpprob_hip_batch_mstep_poisson_device", "cpprob_hip_batch_online_tables_poisson",
+    "cpprob_hip_batch_copy_rates",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
@@ -97,6 +100,15 @@ BATCH_KEEP_MASSES = 2                         # cpprob_hip_batch_config::flags: 
 
 def _batch_flags(flags, keep_masses):
     return int(flags) | (BATCH_KEEP_MASSES if keep_masses else 0)
+
+
+def _poisson(emission, tables):
+    """True for emission="poisson", whose tables are (rates [B, k], transition [B, k, k]); False for "normal"."""
+    if emission not in ("normal", "poisson"):
+        raise ValueError('emission is "normal" or "poisson"')
+    if emission == "poisson" and (tables is None or len(tables) != 2 or tables[0] is None or tables[1] is None):
+        raise ValueError('emission="poisson" takes tables = (rates [B, k], transition [B, k, k]): a batch is unit, scaled or Poisson')
+    return emission == "poisson"
 
 
 def batch_workspace_bytes(model, n_particles, n_problems, T, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
@@ -409,6 +421,13 @@ def load_library(path=None):
         "cpprob_hip_batch_mstep_scaled_device": (C.c_int, [vp, vp, sz, vp, vp, vp, vp, dbl]),
         "cpprob_hip_batch_online_tables_scaled": (C.c_int, [vp, vp, vp, vp]),
         "cpprob_hip_batch_copy_scales": (C.c_int, [vp, u64, vp, vp]),
+        "cpprob_hip_batch_begin_problems_poisson": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, vp, vp]),
+        "cpprob_hip_batch_begin_online_poisson": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int32, vp, vp, C.POINTER(u64)]),
+        "cpprob_hip_batch_retable_poisson": (C.c_int, [vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_poisson_device": (C.c_int, [vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_mstep_poisson_device": (C.c_int, [vp, vp, sz, vp, vp, vp, dbl]),
+        "cpprob_hip_batch_online_tables_poisson": (C.c_int, [vp, vp, vp]),
+        "cpprob_hip_batch_copy_rates": (C.c_int, [vp, u64, vp, vp]),
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
@@ -613,12 +632,15 @@ class Engine:
         return self
 
     def batch_begin_problems(self, model, observes, n_particles, tables=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC, flags=0,
-                             max_particles=None, keep_masses=False):
+                             max_particles=None, keep_masses=False, emission="normal"):
         """A batch whose problems differ.  observes: a list of 1-D arrays, problem b's own sequence (any lengths); n_particles: an int
         or one count a problem; tables (MODEL_HMM_TABLE): None (the set_hmm table for every problem) or (means [B, k], transition
         [B, k, k]), problem b's own table, or (means, transition, sigmas [B, k]): state s of problem b emits N(means[b, s],
-        sigmas[b, s]) (cpprob_hip_batch_begin_problems_scaled).  batch_results() then returns arrays padded to the longest problem
-        (rows t >= T_b zero) and batch_store(b) problem b's own [T_b, n_b]."""
+        sigmas[b, s]) (cpprob_hip_batch_begin_problems_scaled).  emission="poisson": tables = (rates [B, k], transition), state s of
+        problem b emits Poisson(rates[b, s]) and the observes are counts 0 .. 4095 (cpprob_hip_batch_begin_problems_poisson).
+        batch_results() then returns arrays padded to the longest problem (rows t >= T_b zero) and batch_store(b) problem b's own
+        [T_b, n_b]."""
+        poisson = _poisson(emission, tables)
         seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in observes]
         h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
         flat = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0))
@@ -632,7 +654,11 @@ class Engine:
                 raise ValueError("tables = (means [B, k], transition [B, k, k])")
             k = means.shape[1]
             sigmas = self._batch_sigmas(tables, means)
-        if sigmas is not None:
+        if poisson:
+            self._chk(self.L.cpprob_hip_batch_begin_problems_poisson(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                     flat.ctypes.data_as(C.POINTER(C.c_double)), k, means.ctypes.data, trans.ctypes.data))
+            self.batch_k = k                                 # (batch_copy_rates reads it)
+        elif sigmas is not None:
             self._chk(self.L.cpprob_hip_batch_begin_problems_scaled(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
                                                                     flat.ctypes.data_as(C.POINTER(C.c_double)), k, means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data))
             self.batch_k = k                                 # (batch_scales reads it)
@@ -656,11 +682,13 @@ class Engine:
         return sigmas
 
     def batch_begin_online(self, model, capacity, n_particles, seeds, tables=None, resampler=RESAMPLE_SYSTEMATIC, ess_threshold=2.0, keep_history=True, algorithm=ALG_SMC,
-                           flags=0, max_particles=None, keep_masses=False):
+                           flags=0, max_particles=None, keep_masses=False, emission="normal"):
         """A batch whose observes arrive over time.  capacity: the most observes problem b may reach, one a problem; n_particles and
         tables as for batch_begin_problems; seeds: one Philox key a problem, for the life of the batch.  Every problem starts at
         length 0; batch_advance() feeds it.  batch_results() returns arrays padded to the largest capacity and batch_store(b) the
-        [L_b, n_b] rows reached.  A 3-tuple of tables carries the emission scales (cpprob_hip_batch_begin_online_scaled)."""
+        [L_b, n_b] rows reached.  A 3-tuple of tables carries the emission scales (cpprob_hip_batch_begin_online_scaled);
+        emission="poisson": tables = (rates, transition) (cpprob_hip_batch_begin_online_poisson)."""
+        poisson = _poisson(emission, tables)
         h_T, h_n = _problem_shapes(capacity, n_particles)
         sd = np.ascontiguousarray(seeds, np.uint64)
         if sd.shape != h_T.shape:
@@ -676,7 +704,10 @@ class Engine:
             k = means.shape[1]
             sigmas = self._batch_sigmas(tables, means)
         self.batch_k = k
-        if sigmas is not None:
+        if poisson:
+            self._chk(self.L.cpprob_hip_batch_begin_online_poisson(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), k,
+                                                                   means.ctypes.data, trans.ctypes.data, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
+        elif sigmas is not None:
             self._chk(self.L.cpprob_hip_batch_begin_online_scaled(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)), k,
                                                                   means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data, sd.ctypes.data_as(C.POINTER(C.c_uint64))))
         else:
@@ -751,13 +782,15 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_run_conditional_device(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), _dptr(ref_i8), ref_i8.numel()))
 
     # ---- re-tabling a begun batch (include/cpprob_hip.h: cpprob_hip_batch_retable*) ----------------------------------
-    def batch_retable(self, tables, observes=None):
+    def batch_retable(self, tables, observes=None, emission="normal"):
         """New tables for the begun MODEL_HMM_TABLE batch of problems where it stands (cpprob_hip_batch_retable): tables = (means
         [B, k], transition [B, k, k]) on the host, validated as batch_begin_problems validates them.  observes: the problems'
         sequences as batch_begin_problems took them, or None once a previous batch_retable of this begun batch has staged them.
         Everything the batch returns afterwards is what a fresh batch_begin_problems with these tables returns, bit for bit; like a
         begin, the read-outs wait for the next batch_run / batch_run_conditional.  A 3-tuple (means, transition, sigmas [B, k])
-        re-tables a batch begun with emission scales (cpprob_hip_batch_retable_scaled)."""
+        re-tables a batch begun with emission scales (cpprob_hip_batch_retable_scaled); emission="poisson": tables = (rates,
+        transition) re-table a batch begun with Poisson emissions (cpprob_hip_batch_retable_poisson)."""
+        poisson = _poisson(emission, tables)
         means = np.ascontiguousarray(tables[0], np.float64)
         trans = np.ascontiguousarray(tables[1], np.float64)
         if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]) or means.shape[0] != self.batch_B:
@@ -766,25 +799,31 @@ class Engine:
         flat = None if observes is None else self._batch_packed_observes(observes)
         sigmas = self._batch_sigmas(tables, means)
         h_obs, n_obs = None if flat is None or flat.size == 0 else flat.ctypes.data, int(np.sum(h_T, dtype=np.int64)) if flat is None else flat.size
-        if sigmas is not None:
+        if poisson:
+            self._chk(self.L.cpprob_hip_batch_retable_poisson(self.h, means.ctypes.data, trans.ctypes.data, h_obs, n_obs))
+        elif sigmas is not None:
             self._chk(self.L.cpprob_hip_batch_retable_scaled(self.h, means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data, h_obs, n_obs))
         else:
             self._chk(self.L.cpprob_hip_batch_retable(self.h, means.ctypes.data, trans.ctypes.data, h_obs, n_obs))
 
-    def batch_retable_device(self, means, trans, observes, sigmas=None):
+    def batch_retable_device(self, means, trans, observes, sigmas=None, emission="normal"):
         """The same between torch float64 device tensors (means [B, k], trans [B, k, k], observes packed problem after problem),
         enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status).  sigmas [B, k]: the
-        emission scales of a batch begun with them (cpprob_hip_batch_retable_scaled_device)."""
+        emission scales of a batch begun with them (cpprob_hip_batch_retable_scaled_device).  emission="poisson": means holds the
+        rates of a batch begun with Poisson emissions (cpprob_hip_batch_retable_poisson_device)."""
         n_obs = 0 if observes is None else observes.numel()
-        if sigmas is not None:
+        if _poisson(emission, (means, trans) if sigmas is None else (means, trans, sigmas)):
+            self._chk(self.L.cpprob_hip_batch_retable_poisson_device(self.h, _dptr(means), _dptr(trans), _dptr(observes), n_obs))
+        elif sigmas is not None:
             self._chk(self.L.cpprob_hip_batch_retable_scaled_device(self.h, _dptr(means), _dptr(trans), _dptr(sigmas), _dptr(observes), n_obs))
         else:
             self._chk(self.L.cpprob_hip_batch_retable_device(self.h, _dptr(means), _dptr(trans), _dptr(observes), n_obs))
 
     def batch_retable_status(self):
         """int32 [B] of the last re-table: 0, or bits 1 (a weight not finite or < 0), 2 (a transition row without mass), 4 (a mean
-        not finite), 8 (a scaled re-table: a sigma not finite, not > 0, or with a 2 pi sigma^2 that is not a normal number) -- such a
-        problem kept its previous table.  Synchronises."""
+        not finite), 8 (a scaled re-table: a sigma not finite, not > 0, or with a 2 pi sigma^2 that is not a normal number), 16 (a
+        Poisson re-table: a rate not > 0, not finite or not a normal number; bit 4 is not used there) -- such a problem kept its
+        previous table.  Synchronises."""
         out = np.zeros(self.batch_B, np.int32)
         self._chk(self.L.cpprob_hip_batch_retable_status(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
@@ -795,12 +834,16 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_retable_grid(self.h, C.byref(g)))
         return int(g.value)
 
-    def batch_mstep_device(self, stats, means, trans, sigmas=None, sigma_floor=1e-3, log_norms=None):
+    def batch_mstep_device(self, stats, means, trans, sigmas=None, sigma_floor=1e-3, log_norms=None, emission="normal", rate_floor=1e-6, log_rates=None):
         """em.m_step on the device (cpprob_hip_batch_mstep_device): stats torch float64 [B, 88] as batch_smooth_stats_device leaves
         them; means [B, k] and trans [B, k, k] torch float64, updated in place.  Enqueued without a host synchronisation.
         sigmas [B, k]: the emission scales, updated in place too, none below sigma_floor (cpprob_hip_batch_mstep_scaled_device);
-        log_norms [B, k], if given, takes the new sigmas' log(2 pi sigma^2): for tests, a fitting loop has no use for it."""
-        if sigmas is not None:
+        log_norms [B, k], if given, takes the new sigmas' log(2 pi sigma^2): for tests, a fitting loop has no use for it.
+        emission="poisson": means holds the rates, none left below rate_floor (cpprob_hip_batch_mstep_poisson_device); log_rates
+        [B, k], if given, takes the new rates' logarithms, for tests."""
+        if _poisson(emission, (means, trans) if sigmas is None else (means, trans, sigmas)):
+            self._chk(self.L.cpprob_hip_batch_mstep_poisson_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans), _dptr(log_rates), float(rate_floor)))
+        elif sigmas is not None:
             self._chk(self.L.cpprob_hip_batch_mstep_scaled_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans), _dptr(sigmas), _dptr(log_norms),
                                                                   float(sigma_floor)))
         else:
@@ -850,6 +893,14 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_copy_scales(self.h, int(b), sg.ctypes.data, ln.ctypes.data))
         return sg, ln
 
+    def batch_copy_rates(self, b, k=None):
+        """(rates [k], log_rates [k]) of problem b of a batch begun with Poisson emissions, as the device holds them
+        (cpprob_hip_batch_copy_rates).  Synchronises.  For tests."""
+        k = int(k if k is not None else self.batch_k)
+        rt, lr = np.zeros(k), np.zeros(k)
+        self._chk(self.L.cpprob_hip_batch_copy_rates(self.h, int(b), rt.ctypes.data, lr.ctypes.data))
+        return rt, lr
+
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):
         means = np.ascontiguousarray(tables[0], np.float64)
@@ -897,12 +948,16 @@ class Engine:
         self._chk(self.L.cpprob_hip_batch_advance_learn_device(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), _dptr(observes), 0 if observes is None else observes.numel()))
         self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
 
-    def batch_online_tables(self, tables):
+    def batch_online_tables(self, tables, emission="normal"):
         """New tables (means [B, k], transition [B, k, k]) for the FUTURE steps of an online MODEL_HMM_TABLE batch, armed or not
-        (cpprob_hip_batch_online_tables): validated as the begin validates them; past rows stay."""
+        (cpprob_hip_batch_online_tables): validated as the begin validates them; past rows stay.  emission="poisson": (rates,
+        transition) for a batch begun with Poisson emissions (cpprob_hip_batch_online_tables_poisson)."""
+        poisson = _poisson(emission, tables)
         means, trans = self._batch_tables(tables)
         sigmas = self._batch_sigmas(tables, means)
-        if sigmas is not None:                               # (a batch begun with emission scales: cpprob_hip_batch_online_tables_scaled)
+        if poisson:
+            self._chk(self.L.cpprob_hip_batch_online_tables_poisson(self.h, means.ctypes.data, trans.ctypes.data))
+        elif sigmas is not None:                               # (a batch begun with emission scales: cpprob_hip_batch_online_tables_scaled)
             self._chk(self.L.cpprob_hip_batch_online_tables_scaled(self.h, means.ctypes.data, trans.ctypes.data, sigmas.ctypes.data))
         else:
             self._chk(self.L.cpprob_hip_batch_online_tables(self.h, means.ctypes.data, trans.ctypes.data))

@@ -30,6 +30,7 @@
 #include "batch_csmc.hpp"
 #include "batch_retable.hpp"
 #include "batch_scale.hpp"
+#include "batch_poisson.hpp"
 #include "batch_learn.hpp"
 #include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
@@ -1000,6 +1001,13 @@ void scale_step_ll(double y, const double* mean, const double* sigma, const doub
 {
     for (int s2 = 0; s2 < 8; ++s2) ll[s2] = s2 < k ? scale_entry(y, mean[s2], sigma[s2], log_norm[s2]) : -INFINITY;
 }
+// a Poisson table's row (csrc/batch_poisson.hpp), with the statements the device's re-table writes it with
+void poisson_step_ll(double y, const double* rate, const double* log_rate, const double* lf, int k, double* ll)
+{
+    for (int s2 = 0; s2 < 8; ++s2) ll[s2] = s2 < k ? poisson_entry(y, rate[s2], log_rate[s2], lf) : -INFINITY;
+}
+// The emission family of a table batch and of a call that hands tables over: N(mean, 1), N(mean, sigma) or Poisson(rate).
+enum EmissionFamily { kFamilyUnit = 0, kFamilyScaled = 1, kFamilyPoisson = 2 };
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
 {
     std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
@@ -1147,6 +1155,13 @@ struct BatchState {
     double learn_floor = 0.0;
     std::vector<double> sigmas, log_norms;
     DeviceBuffer d_sigma, d_lognorm;
+    // Poisson emissions (cpprob_hip_batch_begin_problems_poisson, _begin_online_poisson; csrc/batch_poisson.hpp): poisson: the begun batch
+    // has them, and is then not scaled.  The rates in force and their logarithms stand where a scaled batch's sigmas and log_norms stand
+    // (sigmas / log_norms on the host, d_sigma / d_lognorm on the device, [B][8]), under the same mirror rules; the log-factorials
+    // (lfact, kPoissonMaxCount + 1 doubles) are filled at the context's first Poisson begin and uploaded once
+    bool poisson = false;
+    std::vector<double> lfact;
+    DeviceBuffer d_lfact;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
@@ -1232,15 +1247,27 @@ void batch_mirror_scales(BatchState* bs, size_t B, int k, const double* h_sigmas
         }
 }
 
+// The same mirrors of a Poisson batch: the rates in force and their logarithms (csrc/batch_poisson.hpp).
+void batch_mirror_rates(BatchState* bs, size_t B, int k, const double* h_rates)
+{
+    for (size_t b = 0; b < B; ++b)
+        for (size_t s = 0; s < (size_t)k; ++s) {
+            bs->sigmas[b * 8 + s] = h_rates[b * (size_t)k + s];
+            bs->log_norms[b * 8 + s] = table_log(h_rates[b * (size_t)k + s]);
+        }
+}
+
 // Begins a checked batch.  Described (h_T, h_n given): problem b has h_T[b] observes, consecutive in h_obs, and h_n[b] particles;
 // uniform (both NULL): every problem has T_max observes and cfg->n_particles particles.  HMM_TABLE of k states: problem b's own table
 // (h_means [B][k], h_transition [B][k][k]) or, both NULL, the table of cpprob_hip_set_hmm.
 // Online (h_T = the capacities, h_obs NULL, h_seeds given): every problem starts without observes; cpprob_hip_batch_advance evaluates
 // its rows, with the statements below, as they arrive.
 int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_max, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
-                int k, const double* h_means, const double* h_transition, const uint64_t* h_seeds = nullptr, const double* h_sigmas = nullptr)
+                int k, const double* h_means, const double* h_transition, const uint64_t* h_seeds = nullptr, const double* h_sigmas = nullptr,
+                EmissionFamily family = kFamilyUnit)
 {
-    const bool online = h_seeds != nullptr, scaled = h_sigmas != nullptr;
+    // (a Poisson begin: h_means are the rates)
+    const bool online = h_seeds != nullptr, scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->batch) c->batch = new BatchState();
     BatchState* bs = c->batch;
@@ -1275,12 +1302,22 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     } else bs->h_tab.assign((size_t)B * T_max * kBatchTab, 0.0);
     bs->h_thr.assign((size_t)tables * 64, ~0ull);
     bs->prob.resize(B);
-    bs->scaled = false; bs->sigmas.clear(); bs->log_norms.clear();
-    if (scaled) {
+    bs->scaled = false; bs->poisson = false; bs->sigmas.clear(); bs->log_norms.clear();
+    if (scaled || poisson) {
         bs->sigmas.assign((size_t)B * 8, 0.0); bs->log_norms.assign((size_t)B * 8, 0.0);
-        batch_mirror_scales(bs, (size_t)B, k, h_sigmas);
+        if (scaled) batch_mirror_scales(bs, (size_t)B, k, h_sigmas);
+        else batch_mirror_rates(bs, (size_t)B, k, h_means);
         HIP_TRY(c, bs->d_sigma.grow(c->stream, B * 8 * sizeof(double)));
         HIP_TRY(c, bs->d_lognorm.grow(c->stream, B * 8 * sizeof(double)));
+    }
+    if (poisson && bs->lfact.empty()) {
+        // the context's first Poisson begin: the log-factorials, once (hipMemcpy of pageable memory has read them when it returns)
+        std::vector<double> lf((size_t)kPoissonMaxCount + 1);
+        poisson_log_fact_table(lf.data());
+        HIP_TRY(c, bs->d_lfact.grow(c->stream, lf.size() * sizeof(double)));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_lfact.as<double>(), lf.data(), lf.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        bs->lfact.swap(lf);
     }
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
@@ -1297,6 +1334,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
             else if (scaled) scale_step_ll(y, mean.data(), &bs->sigmas[b * 8], &bs->log_norms[b * 8], k, row);
+            else if (poisson) poisson_step_ll(y, &bs->sigmas[b * 8], &bs->log_norms[b * 8], bs->lfact.data(), k, row);
             else hmmk_step_ll(y, mean, k, row);
         }
         if (!hmm3 && b < tables) {
@@ -1314,7 +1352,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     if (online) HIP_TRY(c, hipMemsetAsync(bs->ws() + bs->lay.tab, 0, (size_t)B * T_max * kBatchTab * sizeof(double), c->stream));
     else HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.tab, bs->h_tab.data(), bs->h_tab.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    if (scaled) {
+    if (scaled || poisson) {
         HIP_TRY(c, hipMemcpyAsync(bs->d_sigma.as<double>(), bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm.as<double>(), bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
@@ -1347,7 +1385,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
-    bs->online = online; bs->walked = true; bs->own_tables = own; bs->scaled = scaled;
+    bs->online = online; bs->walked = true; bs->own_tables = own; bs->scaled = scaled; bs->poisson = poisson;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -4113,7 +4151,9 @@ int cpprob_hip_batch_problems_workspace_bytes(const cpprob_hip_batch_config* cfg
 }
 
 // The tables of a batch of problems (the described begins, re-table and online tables): per problem, or the context's; k = the states.
-static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, int32_t k_in, const double* h_means, const double* h_transition, int& k)
+// rates: a Poisson call's, whose h_means are rates and pass what poisson_check's bit 16 demands (csrc/batch_poisson.hpp).
+static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, int32_t k_in, const double* h_means, const double* h_transition, int& k,
+                              bool rates = false)
 {
     const uint64_t B = cfg->n_problems;
     const bool hmm3 = cfg->model == CPPROB_HIP_MODEL_HMM3;
@@ -4132,7 +4172,8 @@ static int batch_check_tables(cpprob_hip_ctx* c, const cpprob_hip_batch_config* 
                 double tot = 0.0;
                 for (int j = 0; j < k; ++j) { const double w = tr[(size_t)s2 * k + j]; if (!(w >= 0.0) || !std::isfinite(w)) return fail(c, CPPROB_HIP_EINVAL, at + "transition weights must be finite and >= 0"); tot += w; }
                 if (!(tot > 0.0)) return fail(c, CPPROB_HIP_EINVAL, at + "a transition row without mass");
-                if (!std::isfinite(h_means[b * (size_t)k + s2])) return fail(c, CPPROB_HIP_EINVAL, at + "state means must be finite");
+                if (rates ? poisson_bad(h_means[b * (size_t)k + s2]) : !std::isfinite(h_means[b * (size_t)k + s2]))
+                    return fail(c, CPPROB_HIP_EINVAL, at + (rates ? "emission rates must be > 0, finite and normal numbers" : "state means must be finite"));
             }
         }
     }
@@ -4151,34 +4192,43 @@ static int batch_check_scales(cpprob_hip_ctx* c, uint64_t B, int k, const double
 }
 
 // The four begins over described problems (cpprob_hip_batch_begin_problems, _begin_online and their _scaled forms).  h_obs given: a begin
-// over problems of h_T observes each; h_seeds given: an online begin of capacities h_T.  scaled: the call carries emission scales, which
-// serve per-problem tables alone.
+// over problems of h_T observes each; h_seeds given: an online begin of capacities h_T.  family: scaled: the call carries emission
+// scales; Poisson: its h_means are rates (cpprob_hip_batch_begin_problems_poisson, _begin_online_poisson).  Both serve per-problem tables alone.
 static int batch_begin_described(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs, int32_t k_in,
-                                 const double* h_means, const double* h_transition, const double* h_sigmas, const uint64_t* h_seeds, bool scaled)
+                                 const double* h_means, const double* h_transition, const double* h_sigmas, const uint64_t* h_seeds, EmissionFamily family)
 {
-    if (!c || !cfg || !h_T || !h_n || (!h_obs && !h_seeds) || (scaled && (!h_means || !h_transition || !h_sigmas))) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
+    if (!c || !cfg || !h_T || !h_n || (!h_obs && !h_seeds) || (family != kFamilyUnit && (!h_means || !h_transition)) || (scaled && !h_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (scaled && cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "emission scales serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    if (poisson && cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "Poisson emissions serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
     std::string msg;
     BatchProblemsShape sh;
     if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
     int k = 0;
-    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k)) return rc;
+    if (int rc = batch_check_tables(c, cfg, k_in, h_means, h_transition, k, poisson)) return rc;
     if (scaled) if (int rc = batch_check_scales(c, cfg->n_problems, k, h_sigmas)) return rc;
-    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition, h_seeds, h_sigmas);
+    return batch_begin(c, cfg, (size_t)sh.T_max, h_T, h_n, h_obs, k, h_means, h_transition, h_seeds, h_sigmas, family);
 }
 
 int cpprob_hip_batch_begin_problems(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
                                     const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition)
 {
     LANES_OWN(c);
-    return batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, h_means, h_transition, nullptr, nullptr, false);
+    return batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, h_means, h_transition, nullptr, nullptr, kFamilyUnit);
+}
+
+int cpprob_hip_batch_begin_problems_poisson(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                            const double* h_obs, int32_t k_in, const double* h_rates, const double* h_transition)
+{
+    LANES_OWN(c);
+    return batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, h_rates, h_transition, nullptr, nullptr, kFamilyPoisson);
 }
 
 int cpprob_hip_batch_begin_problems_scaled(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
                                            const double* h_obs, int32_t k_in, const double* h_means, const double* h_transition, const double* h_sigmas)
 {
     LANES_OWN(c);
-    return batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, h_means, h_transition, h_sigmas, nullptr, true);
+    return batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, h_means, h_transition, h_sigmas, nullptr, kFamilyScaled);
 }
 
 // One launch over the begun batch: every problem from step 0 (cpprob_hip_batch_run), or its piece (cpprob_hip_batch_advance).
@@ -4349,14 +4399,21 @@ int cpprob_hip_batch_begin_online(cpprob_hip_ctx* c, const cpprob_hip_batch_conf
                                   int32_t k_in, const double* h_means, const double* h_transition, const uint64_t* h_seeds)
 {
     LANES_OWN(c);
-    return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_means, h_transition, nullptr, h_seeds, false);
+    return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_means, h_transition, nullptr, h_seeds, kFamilyUnit);
+}
+
+int cpprob_hip_batch_begin_online_poisson(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
+                                          int32_t k_in, const double* h_rates, const double* h_transition, const uint64_t* h_seeds)
+{
+    LANES_OWN(c);
+    return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_rates, h_transition, nullptr, h_seeds, kFamilyPoisson);
 }
 
 int cpprob_hip_batch_begin_online_scaled(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
                                          int32_t k_in, const double* h_means, const double* h_transition, const double* h_sigmas, const uint64_t* h_seeds)
 {
     LANES_OWN(c);
-    return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_means, h_transition, h_sigmas, h_seeds, true);
+    return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_means, h_transition, h_sigmas, h_seeds, kFamilyScaled);
 }
 
 static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs);
@@ -4414,6 +4471,7 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
             double* row = bs->pin_tab.as<double>() + (b * T_max + t) * kBatchTab;
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
             else if (bs->scaled) scale_step_ll(y, mean.data(), &bs->sigmas[b * 8], &bs->log_norms[b * 8], (int)hk, row);
+            else if (bs->poisson) poisson_step_ll(y, &bs->sigmas[b * 8], &bs->log_norms[b * 8], bs->lfact.data(), (int)hk, row);
             else hmmk_step_ll(y, mean, (int)hk, row);
         }
         // (a problem without observes, or without new ones and with its read-out done, has nothing to do)
@@ -5422,7 +5480,7 @@ int cpprob_hip_batch_pass_grid(cpprob_hip_ctx* c, uint32_t* decode_forward_grid_
 // ---- re-tabling a begun batch (csrc/batch_retable.hpp) -----------------------------------------------------------------------------
 static_assert(kRetableStats == kSuffStats, "the M-step reads the record of cpprob_hip_batch_smooth_stats");
 // What a re-table needs of the batch's state, then n_observes against the lengths; nothing is enqueued before it has passed.
-static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, bool scaled)
+static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFamily family)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
@@ -5430,6 +5488,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, bool scaled
     if (bs->online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "an online batch is not re-tabled: its advances evaluate their rows from the host's means");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "re-tabling serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
+    const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
+    if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: it is re-tabled by cpprob_hip_batch_retable_poisson / _retable_poisson_device");
+    if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: begin it with cpprob_hip_batch_begin_problems_poisson, or re-table it with its own family's calls");
     if (bs->scaled && !scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: it is re-tabled by cpprob_hip_batch_retable_scaled / _retable_scaled_device");
     if (!bs->scaled && scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_problems_scaled, or re-table it with cpprob_hip_batch_retable / _retable_device");
     uint64_t rows = 0;
@@ -5438,7 +5499,8 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, bool scaled
     return 0;
 }
 
-// Enqueues the first entries (once a begin) and the launch (d_sigmas given: a scaled batch's); the batch then stands as after a begin.
+// Enqueues the first entries (once a begin) and the launch (d_sigmas given: a scaled batch's; a Poisson batch: its own, d_means the
+// rates); the batch then stands as after a begin.
 // Waits for nothing but, where the status words have to grow, for the calls before it.
 static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs, const double* d_sigmas)
 {
@@ -5450,21 +5512,28 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
     auto common = [&](auto& r) {                                // (what the two forms' arguments share)
         r.prob = reinterpret_cast<const BatchProblem*>(bs->ws() + bs->lay.prob);
         r.first = bs->d_cfirst.as<int64_t>();
-        r.means = d_means; r.trans = d_trans; r.obs = d_obs;
+        r.trans = d_trans; r.obs = d_obs;
         r.tab = reinterpret_cast<double*>(bs->ws() + bs->lay.tab);
         r.thr = reinterpret_cast<uint64_t*>(bs->ws() + bs->lay.thr);
         r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
-    if (d_sigmas) {
+    if (bs->poisson) {
+        // (a Poisson batch: d_means are its rates; the rates and log-rates in force are the device's from here on)
+        BatchRetablePoissonArgs pa{};
+        common(pa);
+        pa.rates = d_means; pa.lfact = bs->d_lfact.as<double>(); pa.rate_out = bs->d_sigma.as<double>(); pa.log_rate_out = bs->d_lognorm.as<double>();
+        hipLaunchKernelGGL(batch_retable_poisson_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, pa);
+    } else if (d_sigmas) {
         // (a scaled batch; the sigmas and log_norms in force are the device's from here on)
         BatchRetableScaledArgs sa{};
         common(sa);
-        sa.sigmas = d_sigmas; sa.sigma_out = bs->d_sigma.as<double>(); sa.log_norm_out = bs->d_lognorm.as<double>();
+        sa.means = d_means; sa.sigmas = d_sigmas; sa.sigma_out = bs->d_sigma.as<double>(); sa.log_norm_out = bs->d_lognorm.as<double>();
         hipLaunchKernelGGL(batch_retable_scaled_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, sa);
     } else {
         BatchRetableArgs a{};
         common(a);
+        a.means = d_means;
         a.log_norm = std::log(2 * kPi * 1.0 * 1.0);               // (normal_logpdf's own expression at sigma = 1.0)
         hipLaunchKernelGGL(batch_retable_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, a);
     }
@@ -5477,11 +5546,14 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
     return 0;
 }
 
-// The two device forms (scaled: cpprob_hip_batch_retable_scaled_device, whose d_sigmas a unit call does not have): enqueued, no wait.
+// The three device forms (scaled: cpprob_hip_batch_retable_scaled_device, whose d_sigmas the others do not have; Poisson:
+// cpprob_hip_batch_retable_poisson_device, whose d_means are rates): enqueued, no wait.  The unit and the scaled entry points pass
+// their flag as they always did; the Poisson one passes poisson behind it.
 static int batch_retable_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_sigmas, const double* d_observes, size_t n_observes,
-                                bool scaled)
+                                bool scaled, bool poisson = false)
 {
-    if (int rc = batch_retable_check(c, n_observes, scaled)) return rc;
+    const EmissionFamily family = poisson ? kFamilyPoisson : scaled ? kFamilyScaled : kFamilyUnit;
+    if (int rc = batch_retable_check(c, n_observes, family)) return rc;
     if (!d_means || !d_transition || (scaled && !d_sigmas) || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     HIP_TRY(c, hipSetDevice(c->device));
     return batch_retable_enqueue(c, d_means, d_transition, d_observes, d_sigmas);
@@ -5500,17 +5572,19 @@ static int batch_retable_observes(cpprob_hip_ctx* c, const double* h_observes, s
     return 0;
 }
 
-// The two host forms (scaled: cpprob_hip_batch_retable_scaled): the tables are validated with the begin's own statements, staged -- the
-// means, a scaled batch's sigmas behind them, in front; the transition rows at the back -- and re-tabled as by the device form.
+// The three host forms (scaled: cpprob_hip_batch_retable_scaled; Poisson: cpprob_hip_batch_retable_poisson, h_means its rates): the
+// tables are validated with the begin's own statements, staged -- the means, a scaled batch's sigmas behind them, in front; the
+// transition rows at the back -- and re-tabled as by the device form.
 static int batch_retable_host(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, const double* h_observes, size_t n_observes,
-                              bool scaled)
+                              bool scaled, bool poisson = false)
 {
-    if (int rc = batch_retable_check(c, n_observes, scaled)) return rc;
+    const EmissionFamily family = poisson ? kFamilyPoisson : scaled ? kFamilyScaled : kFamilyUnit;
+    if (int rc = batch_retable_check(c, n_observes, family)) return rc;
     BatchState* bs = c->batch;
     if (!h_means || !h_transition || (scaled && !h_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
     int k = 0;
-    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k, poisson)) return rc;
     if (scaled) if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, kk = (size_t)k * k;
@@ -5525,6 +5599,7 @@ static int batch_retable_host(cpprob_hip_ctx* c, const double* h_means, const do
     // the host knows the tables: the thresholds' mirror is current again (the rows' is not: cpprob_hip_batch_copy_store fetches its row)
     for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
     if (scaled) batch_mirror_scales(bs, B, k, h_sigmas);
+    if (poisson) batch_mirror_rates(bs, B, k, h_means);
     bs->thr_stale = false;
     return 0;
 }
@@ -5533,6 +5608,12 @@ int cpprob_hip_batch_retable_device(cpprob_hip_ctx* c, const double* d_means, co
 {
     LANES_OWN(c);
     return batch_retable_device(c, d_means, d_transition, nullptr, d_observes, n_observes, false);
+}
+
+int cpprob_hip_batch_retable_poisson_device(cpprob_hip_ctx* c, const double* d_rates, const double* d_transition, const double* d_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    return batch_retable_device(c, d_rates, d_transition, nullptr, d_observes, n_observes, false, true);
 }
 
 int cpprob_hip_batch_retable_scaled_device(cpprob_hip_ctx* c, const double* d_means, const double* d_transition, const double* d_sigmas, const double* d_observes, size_t n_observes)
@@ -5545,6 +5626,12 @@ int cpprob_hip_batch_retable(cpprob_hip_ctx* c, const double* h_means, const dou
 {
     LANES_OWN(c);
     return batch_retable_host(c, h_means, h_transition, nullptr, h_observes, n_observes, false);
+}
+
+int cpprob_hip_batch_retable_poisson(cpprob_hip_ctx* c, const double* h_rates, const double* h_transition, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    return batch_retable_host(c, h_rates, h_transition, nullptr, h_observes, n_observes, false, true);
 }
 
 int cpprob_hip_batch_retable_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, const double* h_observes, size_t n_observes)
@@ -5574,17 +5661,22 @@ int cpprob_hip_batch_retable_grid(cpprob_hip_ctx* c, uint32_t* grid_y)
 }
 
 // cpprob_hip_batch_mstep_device and -- scaled: the sigmas (and, where given, the log_norms) are fitted too, above sigma_floor --
-// cpprob_hip_batch_mstep_scaled_device.
-static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition, bool scaled, double* d_sigmas,
+// cpprob_hip_batch_mstep_scaled_device; Poisson: d_means are rates, kept at or above sigma_floor (the call's rate_floor), d_log_norm
+// their logarithms where given -- cpprob_hip_batch_mstep_poisson_device.
+static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition, EmissionFamily family, double* d_sigmas,
                               double* d_log_norm, double sigma_floor)
 {
+    const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
     LANES_OWN(c);
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its M-step is cpprob_hip_batch_mstep_poisson_device");
+    if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: its M-step is cpprob_hip_batch_mstep_device / _mstep_scaled_device");
     if (!d_stats || !d_means || !d_transition || (scaled && !d_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     if (scaled && (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor))) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
+    if (poisson && (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor))) return fail(c, CPPROB_HIP_EINVAL, "rate_floor must be finite and > 0");
     const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kRetableStats;
     if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -5593,6 +5685,10 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
         BatchMstepScaledArgs a{};
         a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.sigmas = d_sigmas; a.log_norms = d_log_norm; a.floor = sigma_floor; a.B = (int64_t)B; a.k = bs->hk;
         hipLaunchKernelGGL(batch_mstep_scaled_kernel, grid, dim3(kThreads), 0, c->stream, a);
+    } else if (poisson) {
+        BatchMstepPoissonArgs a{};
+        a.stats = d_stats; a.rates = d_means; a.trans = d_transition; a.log_rates = d_log_norm; a.floor = sigma_floor; a.B = (int64_t)B; a.k = bs->hk;
+        hipLaunchKernelGGL(batch_mstep_poisson_kernel, grid, dim3(kThreads), 0, c->stream, a);
     } else {
         BatchMstepArgs a{};
         a.stats = d_stats; a.means = d_means; a.trans = d_transition; a.B = (int64_t)B; a.k = bs->hk;
@@ -5604,13 +5700,19 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
 
 int cpprob_hip_batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition)
 {
-    return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, false, nullptr, nullptr, 0.0);
+    return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, kFamilyUnit, nullptr, nullptr, 0.0);
+}
+
+int cpprob_hip_batch_mstep_poisson_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_rates, double* d_transition, double* d_log_rates,
+                                          double rate_floor)
+{
+    return batch_mstep_device(c, d_stats, n_doubles, d_rates, d_transition, kFamilyPoisson, nullptr, d_log_rates, rate_floor);
 }
 
 int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_transition, double* d_sigmas,
                                          double* d_log_norm, double sigma_floor)
 {
-    return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, true, d_sigmas, d_log_norm, sigma_floor);
+    return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, kFamilyScaled, d_sigmas, d_log_norm, sigma_floor);
 }
 
 // ---- tied tables: a partition of the begun batch's problems and the pooled records of its groups (csrc/batch_pool.hpp) -------------
@@ -5743,6 +5845,22 @@ int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* c, uint64_t problem, double* h_
     return 0;
 }
 
+int cpprob_hip_batch_copy_rates(cpprob_hip_ctx* c, uint64_t problem, double* h_rates, double* h_log_rates)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions (cpprob_hip_batch_begin_problems_poisson, _begin_online_poisson)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t k = (size_t)bs->hk;
+    if (h_rates) HIP_TRY(c, hipMemcpyAsync(h_rates, bs->d_sigma.as<double>() + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_log_rates) HIP_TRY(c, hipMemcpyAsync(h_log_rates, bs->d_lognorm.as<double>() + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 // ---- online EM of an online batch (csrc/batch_learn.hpp) ----------------------------------------------------------------------------
 // What the host route and the arming share: an online CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables.
 static int batch_learn_check(cpprob_hip_ctx* c, const char* who)
@@ -5760,6 +5878,7 @@ int cpprob_hip_batch_learn_begin(cpprob_hip_ctx* c, const double* h_gamma, size_
     LANES_OWN(c);
     if (int rc = batch_learn_check(c, "cpprob_hip_batch_learn_begin")) return rc;
     BatchState* bs = c->batch;
+    if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: online EM serves the unit and the scaled batches");
     if (bs->cfg.keep_history != 1 && !batch_masses(&bs->cfg))
         return fail(c, CPPROB_HIP_ESTATE, "a filtering-only batch (keep_history = 0) keeps no masses: begin it with CPPROB_HIP_BATCH_KEEP_MASSES");
     if (bs->advance_ring.count()) return fail(c, CPPROB_HIP_ESTATE, "the online batch has been advanced: cpprob_hip_batch_learn_begin comes before the first advance");
@@ -5796,6 +5915,7 @@ int cpprob_hip_batch_learn_begin_scaled(cpprob_hip_ctx* c, const double* h_gamma
 {
     LANES_OWN(c);
     if (int rc = batch_learn_check(c, "cpprob_hip_batch_learn_begin_scaled")) return rc;
+    if (c->batch->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: online EM serves the unit and the scaled batches");
     if (!c->batch->scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_online_scaled, or arm it with cpprob_hip_batch_learn_begin");
     if (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor)) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
     if (int rc = cpprob_hip_batch_learn_begin(c, h_gamma, n_gamma, t_min)) return rc;
@@ -5902,17 +6022,20 @@ static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const 
     return 0;
 }
 
-// New tables for the begun online batch from the host (scaled: cpprob_hip_batch_online_tables_scaled, with the scales), validated with
+// New tables for the begun online batch from the host (scaled: cpprob_hip_batch_online_tables_scaled, with the scales; Poisson:
+// cpprob_hip_batch_online_tables_poisson, h_means its rates), validated with
 // the begin's own statements before anything changes; an armed batch's device tables follow.
-static int batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, bool scaled, const char* who)
+static int batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas, bool scaled, const char* who, bool poisson = false)
 {
     if (int rc = batch_learn_check(c, who)) return rc;
     BatchState* bs = c->batch;
+    if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its tables are replaced by cpprob_hip_batch_online_tables_poisson");
+    if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: begin it with cpprob_hip_batch_begin_online_poisson, or call its own family's cpprob_hip_batch_online_tables");
     if (bs->scaled && !scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its tables are replaced by cpprob_hip_batch_online_tables_scaled");
     if (!bs->scaled && scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_online_scaled, or call cpprob_hip_batch_online_tables");
     if (!h_means || !h_transition || (scaled && !h_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     int k = 0;
-    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k)) return rc;
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, h_means, h_transition, k, poisson)) return rc;
     if (scaled) if (int rc = batch_check_scales(c, bs->cfg.n_problems, k, h_sigmas)) return rc;
     if (bs->learn_tied) if (int rc = batch_tied_tables_check(c, h_means, h_transition, scaled ? h_sigmas : nullptr, (size_t)k)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -5921,8 +6044,9 @@ static int batch_online_tables(cpprob_hip_ctx* c, const double* h_means, const d
     bs->trans.assign(h_transition, h_transition + B * kk);
     for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
     HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.thr, bs->h_thr.data(), bs->h_thr.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    if (scaled) {
-        batch_mirror_scales(bs, B, k, h_sigmas);
+    if (scaled || poisson) {
+        if (scaled) batch_mirror_scales(bs, B, k, h_sigmas);
+        else batch_mirror_rates(bs, B, k, h_means);
         HIP_TRY(c, hipMemcpyAsync(bs->d_sigma.as<double>(), bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm.as<double>(), bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
@@ -5940,6 +6064,12 @@ int cpprob_hip_batch_online_tables(cpprob_hip_ctx* c, const double* h_means, con
 {
     LANES_OWN(c);
     return batch_online_tables(c, h_means, h_transition, nullptr, false, "cpprob_hip_batch_online_tables");
+}
+
+int cpprob_hip_batch_online_tables_poisson(cpprob_hip_ctx* c, const double* h_rates, const double* h_transition)
+{
+    LANES_OWN(c);
+    return batch_online_tables(c, h_rates, h_transition, nullptr, false, "cpprob_hip_batch_online_tables_poisson", true);
 }
 
 int cpprob_hip_batch_online_tables_scaled(cpprob_hip_ctx* c, const double* h_means, const double* h_transition, const double* h_sigmas)

@@ -1,21 +1,29 @@
 """Particle EM for the tables of MODEL_HMM_TABLE problems: the E-step is Engine.batch_smooth_stats (the backward smoother's expected
 sufficient statistics, one record a problem, computed on the device), the M-step below is 88 doubles a problem on the host.  A
 table is its means and its transition rows and, where the caller passes them, its per-state emission scales (without them the
-emission's sigma is 1 and stays so); the initial state is uniform and not fitted.  Problems may be tied (groups): the problems of a
+emission's sigma is 1 and stays so); with emission="poisson" the means are the rates of Poisson emissions (csrc/batch_poisson.hpp);
+the initial state is uniform and not fitted.  Problems may be tied (groups): the problems of a
 group share one table, fitted to their pooled records (pool_stats; on the device cpprob_hip_batch_pool_stats)."""
 import numpy as np
 
 from .capi import MODEL_HMM_TABLE, RESAMPLE_SYSTEMATIC, STATS_PER_PROBLEM
 
 
-def m_step(stats, means, trans, sigmas=None, sigma_floor=1e-3):
+def m_step(stats, means, trans, sigmas=None, sigma_floor=1e-3, emission="normal", rate_floor=1e-6):
     """The tables that maximise the expected complete-data log-likelihood under `stats` (a dict as Engine.batch_smooth_stats returns:
     xi [B, 8, 8], occ, occ_y [B, 8]): trans[b, s, :] = xi[b, s, :k] / its sum, means[b, s] = occ_y[b, s] / occ[b, s], k =
     means.shape[1].  A transition row or a state with no mass keeps its previous value; states >= k of the statistics are not read.
     Pure numpy; returns new (means [B, k], trans [B, k, k]).
     sigmas [B, k]: the emission scales are fitted too, and returned as a third array -- a state with mass takes v = occ_yy / occ -
     mean' mean' (mean' its new mean) and sigma' = sqrt(v) where v >= sigma_floor^2, else sigma_floor (a NaN v too); a state without
-    mass keeps its sigma.  The statements of csrc/batch_scale.hpp, which cpprob_hip_batch_mstep_scaled_device runs bit for bit."""
+    mass keeps its sigma.  The statements of csrc/batch_scale.hpp, which cpprob_hip_batch_mstep_scaled_device runs bit for bit.
+    emission="poisson": means are the rates of Poisson emissions; a state with mass takes occ_y / occ where that is >= rate_floor,
+    else rate_floor (a NaN too), a state without mass keeps its rate.  The statements of csrc/batch_poisson.hpp, which
+    cpprob_hip_batch_mstep_poisson_device runs bit for bit."""
+    if emission not in ("normal", "poisson"):
+        raise ValueError('emission is "normal" or "poisson"')
+    if emission == "poisson" and sigmas is not None:
+        raise ValueError("a Poisson emission has no scales: a table is unit, scaled or Poisson")
     means = np.array(means, np.float64)
     trans = np.array(trans, np.float64)
     if means.ndim != 2 or trans.shape != (means.shape[0], means.shape[1], means.shape[1]):
@@ -33,6 +41,13 @@ def m_step(stats, means, trans, sigmas=None, sigma_floor=1e-3):
     trans[fit] = xi[fit] / row[fit][:, None]
     seen = occ > 0.0
     means[seen] = occ_y[seen] / occ[seen]
+    if emission == "poisson":
+        floor = np.float64(rate_floor)
+        if not (floor > 0.0) or not np.isfinite(floor):
+            raise ValueError("rate_floor must be finite and > 0")
+        with np.errstate(all="ignore"):
+            means[seen] = np.where(means[seen] >= floor, means[seen], floor)
+        return means, trans
     if sigmas is None:
         return means, trans
     sigmas = np.array(sigmas, np.float64)
@@ -102,7 +117,7 @@ def check_tied_start(groups, means, trans, sigmas=None):
 
 
 def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iterations, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, resident=False,
-                 sigmas0=None, sigma_floor=1e-3, groups=None):
+                 sigmas0=None, sigma_floor=1e-3, groups=None, emission="normal", rate_floor=1e-6):
     """Batched particle EM.  observes: a list of B 1-D sequences, or one sequence every problem shares (restarts: one sequence under
     B initial tables); means0 [B, k], trans0 [B, k, k] the initial tables; seeds [B].  Iteration i begins a batch with the current
     tables (batch_begin_problems), runs it with seeds + i, takes the statistics and the M-step.  Returns (means [iterations + 1, B, k],
@@ -119,7 +134,13 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
     ascending problem order (pool_stats on the host route; resident: one Engine.batch_tie after the begin and one
     batch_pool_stats_device, in place, in front of the unchanged M-step), so the members hold bit-identical tables throughout.  The
     returned shapes stay: members repeat their group's table, log_evidence stays per problem (a group's log-likelihood is its
-    members' sum).  Both routes, the same arrays bit for bit."""
+    members' sum).  Both routes, the same arrays bit for bit.
+    emission="poisson": the observes are counts 0 .. 4095 and means0 [B, k] the initial rates of Poisson emissions, none fitted below
+    rate_floor; the means returned are the rates.  Host loop and resident=True, untied and tied, the same arrays bit for bit."""
+    if emission not in ("normal", "poisson"):
+        raise ValueError('emission is "normal" or "poisson"')
+    if emission == "poisson" and sigmas0 is not None:
+        raise ValueError("a Poisson emission has no scales: a table is unit, scaled or Poisson")
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
     B = means.shape[0]
@@ -135,20 +156,21 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
     if groups is not None:
         groups = check_tied_start(groups, means, trans, sigmas)[0]
     if resident and int(iterations) > 0:
-        return _em_resident(engine, seqs, means, trans, n_particles, sd, int(iterations), resampler, bool(keep_history), sigmas, float(sigma_floor), groups)
+        return _em_resident(engine, seqs, means, trans, n_particles, sd, int(iterations), resampler, bool(keep_history), sigmas, float(sigma_floor), groups,
+                            emission, float(rate_floor))
     m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(iterations), B))
     s_hist = None if sigmas is None else [sigmas.copy()]
     for it in range(int(iterations)):
         tables = (means, trans) if sigmas is None else (means, trans, sigmas)
         engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, resampler=resampler, keep_history=bool(keep_history),
-                                    keep_masses=not keep_history)
+                                    keep_masses=not keep_history, emission=emission)
         engine.batch_run(sd + np.uint64(it))
         stats = engine.batch_smooth_stats(seqs)
         ev[it] = [s["log_evidence"] for s in engine.batch_results()[0]]
         if groups is not None:
             stats = pool_stats(stats, groups)
         if sigmas is None:
-            means, trans = m_step(stats, means, trans)
+            means, trans = m_step(stats, means, trans, emission=emission, rate_floor=rate_floor)
         else:
             means, trans, sigmas = m_step(stats, means, trans, sigmas, sigma_floor)
             s_hist.append(sigmas.copy())
@@ -159,14 +181,16 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
     return np.array(m_hist), np.array(t_hist), ev, np.array(s_hist)
 
 
-def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resampler, keep_history, sigmas=None, sigma_floor=1e-3, groups=None):
+def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resampler, keep_history, sigmas=None, sigma_floor=1e-3, groups=None,
+                 emission="normal", rate_floor=1e-6):
     """hmm_table_em's loop with the tables, the observes, the records and the evidences in device tensors; the host enqueues and
     looks at nothing until the loop is over."""
     import torch
     B, k = means.shape
     dev = torch.device("cuda", engine.device)
     tables = (means, trans) if sigmas is None else (means, trans, sigmas)
-    engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, resampler=resampler, keep_history=keep_history, keep_masses=not keep_history)
+    engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, resampler=resampler, keep_history=keep_history, keep_masses=not keep_history,
+                                emission=emission)
     if groups is not None:
         engine.batch_tie(groups)                            # (once: the re-tables keep it)
     obs = torch.from_numpy(np.ascontiguousarray(np.concatenate(seqs))).to(dev)
@@ -194,11 +218,11 @@ def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resamp
             if s_all is not None:
                 s_all[it + 1].copy_(s_all[it])
         if s_all is None:
-            engine.batch_mstep_device(stats, m_all[it + 1], t_all[it + 1])
+            engine.batch_mstep_device(stats, m_all[it + 1], t_all[it + 1], emission=emission, rate_floor=rate_floor)
         else:
             engine.batch_mstep_device(stats, m_all[it + 1], t_all[it + 1], sigmas=s_all[it + 1], sigma_floor=sigma_floor)
         if it + 1 < iterations:
-            engine.batch_retable_device(m_all[it + 1], t_all[it + 1], obs, sigmas=None if s_all is None else s_all[it + 1])
+            engine.batch_retable_device(m_all[it + 1], t_all[it + 1], obs, sigmas=None if s_all is None else s_all[it + 1], emission=emission)
     engine.sync()
     if s_all is None:
         return m_all.cpu().numpy(), t_all.cpu().numpy(), np.ascontiguousarray(ev[:, :, 0].cpu().numpy())

@@ -46,6 +46,10 @@
 //                   state s emits N(means[s], sigmas[s]); the fitted tables are printed with their sigmas as a third list)
 //                   --learn_scales [--scale_floor F] (with --emission_scales and --em_iterations or --online_em: the sigmas are fitted
 //                   too, none below F (0.001); without it they stay)
+//                   --poisson_emissions [--rate_floor F] (with --batch_tables_file: state s emits Poisson(rate[s]) -- every line carries
+//                   the rates where it carries the means, [rates] [transition] [observes], and the observes are counts 0 .. 4095; with
+//                   --em_iterations, --em_on_device, --tie_tables / --tie_groups and --stream_chunk, not with --emission_scales or
+//                   --online_em; no rate is fitted below F (1e-6); the fitted rates are printed where the means are)
 //                   --tie_tables / --tie_groups "[g_0 g_1 ..]" (with --em_iterations: tied tables -- all problems, or the problems with
 //                   one group id (ids 0 .. G-1, every id used, one a problem), share one table fitted to all of their observes,
 //                   cpprob::gpu::Options::tie_groups; their input tables must be equal; the output format is unchanged, the members of
@@ -84,6 +88,7 @@ struct Args {
     std::size_t stream_chunk = 0;             // --batch_tables_file: feed every problem's observes this many at a time (0: all at once)
     std::size_t em_iterations = 0;            // --batch_tables_file: fit the tables by this many iterations of particle EM (0: none)
     bool emission_scales = false;             // --batch_tables_file: every line carries [sigmas] behind [means]: per-state emission scales
+    bool poisson_emissions = false;           // --batch_tables_file: the first list of every line holds the rates of Poisson emissions
     std::string conditional_paths_file;       // --batch_tables_file: the reference paths of a conditional run, one line a problem (empty: none)
     bool tie_tables = false;                  // --em_iterations: all problems share one fitted table
     std::string tie_groups;                   // --em_iterations: "[g_0 g_1 ..]", the problems with one id share one fitted table (empty: none)
@@ -275,6 +280,7 @@ int execute_batch_tables(const Args& a)
         if (std::get<1>(p).size() != k * k) { std::cerr << "line " << at << ": the transition list holds " << std::get<1>(p).size() << " weights, not k x k = " << k * k << "." << std::endl; return EXIT_FAILURE; }
         if (std::get<2>(p).empty()) { std::cerr << "line " << at << ": no observes." << std::endl; return EXIT_FAILURE; }
         tables.push_back(cpprob::gpu::HmmTable{std::get<0>(p), std::get<1>(p), sigmas});
+        if (a.poisson_emissions) tables.back().emission = cpprob::gpu::Emission::poisson;
         observes.push_back(std::get<2>(p));
         seeds.push_back(cpprob::gpu::options().seed + at);
     }
@@ -430,6 +436,8 @@ int main(int argc, char** argv)
         else if (f == "--online_em") opt.learn_tables = true;                      // --batch_tables_file --stream_chunk: the stream learns its tables on the device (cpprob_hip_batch_advance_learn)
         else if (f == "--em_step_exponent") opt.learn_step_exponent = std::stod(next());   // ... with the step sizes (t + 1) ^ -A
         else if (f == "--emission_scales") a.emission_scales = true;              // --batch_tables_file: every line is [means] [sigmas] [transition] [observes]
+        else if (f == "--poisson_emissions") a.poisson_emissions = true;          // --batch_tables_file: every line is [rates] [transition] [observes], the observes counts
+        else if (f == "--rate_floor") opt.rate_floor = std::stod(next());          // ... --em_iterations fits no rate below this
         else if (f == "--learn_scales") opt.learn_scales = true;                   // --em_iterations / --online_em with --emission_scales: the sigmas are fitted too
         else if (f == "--scale_floor") opt.scale_floor = std::stod(next());        // ... none below this
         else if (f == "--em_burn_in") opt.learn_burn_in = std::stoull(next());      // ... and no M-step before a problem has this many observes
@@ -466,6 +474,9 @@ int main(int argc, char** argv)
         else { std::cerr << "unknown option " << f << std::endl; return EXIT_FAILURE; }
     }
     if (a.sis == a.smc) { std::cerr << "exactly one of --sis / --smc has to be set" << std::endl; return EXIT_FAILURE; }
+    if (a.poisson_emissions && a.batch_tables_file.empty()) { std::cerr << "--poisson_emissions reads the rates of --batch_tables_file" << std::endl; return EXIT_FAILURE; }
+    if (a.poisson_emissions && a.emission_scales) { std::cerr << "--poisson_emissions and --emission_scales name two emission families: a batch has one" << std::endl; return EXIT_FAILURE; }
+    if (a.poisson_emissions && opt.learn_tables) { std::cerr << "--online_em serves Gaussian emissions: fit Poisson tables with --em_iterations" << std::endl; return EXIT_FAILURE; }
     if (a.emission_scales && a.batch_tables_file.empty()) { std::cerr << "--emission_scales reads the sigmas of --batch_tables_file" << std::endl; return EXIT_FAILURE; }
     if (opt.learn_scales && (!a.emission_scales || (a.em_iterations == 0 && !opt.learn_tables))) {
         std::cerr << "--learn_scales fits the sigmas of --emission_scales: set it with --em_iterations or --online_em" << std::endl;

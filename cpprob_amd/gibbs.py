@@ -2,13 +2,23 @@
 A sweep draws one state trajectory a chain on the device and reads only its complete-data sufficient statistics
 (Engine.batch_traj_stats, 88 doubles a chain); the tables are then drawn on the host from their conjugate posteriors.  A table is
 its means and its transition rows and, where the caller passes them, its per-state emission scales (without them the emission's
-sigma is 1 and stays so); the initial state is uniform and not sampled."""
+sigma is 1 and stays so); the initial state is uniform and not sampled.  The emission is Gaussian: for emission="poisson" every
+sampler here raises NotImplementedError (poisson_refusal) -- the rates have no conjugate draw here yet."""
 import numpy as np
 
 from .capi import MODEL_HMM_TABLE, RESAMPLE_SYSTEMATIC
 
 
-def sample_tables(stats, k, rng, alpha=1.0, mu0=0.0, tau0=10.0, sigmas=None, a0=2.0, b0=1.0):
+def poisson_refusal(emission):
+    """The samplers' answer to an emission family: nothing for "normal", a clear error for "poisson"."""
+    if emission == "poisson":
+        raise NotImplementedError('the Gibbs samplers draw the tables of Gaussian emissions: emission="poisson" has no conjugate (gamma) draw of '
+                                  "the rates yet -- fit Poisson tables with cpprob_amd.em.hmm_table_em")
+    if emission != "normal":
+        raise ValueError('emission is "normal" or "poisson"')
+
+
+def sample_tables(stats, k, rng, alpha=1.0, mu0=0.0, tau0=10.0, sigmas=None, a0=2.0, b0=1.0, emission="normal"):
     """One draw of the tables given one trajectory's statistics a problem (`stats`: the dict Engine.batch_traj_stats returns with the
     trajectory axis indexed away -- xi [B, 8, 8], occ, occ_y [B, 8]).  Priors: every transition row Dirichlet(alpha, .., alpha), every
     mean N(mu0, tau0^2); sigma is 1 as the model fixes it, so both posteriors are conjugate:
@@ -21,6 +31,7 @@ def sample_tables(stats, k, rng, alpha=1.0, mu0=0.0, tau0=10.0, sigmas=None, a0=
     an inverse-gamma(a0, b0) prior at the mean just drawn: shape = a0 + occ / 2, rate = b0 + (occ_yy - 2 mu occ_y + mu^2 occ) / 2,
     variance = rate / rng.standard_gamma(shape) (one call, after the draws above: a call without sigmas consumes the generator as it
     did).  Returns (means, trans, sigmas [B, k])."""
+    poisson_refusal(emission)
     k = int(k)
     xi, occ, occ_y = (np.asarray(stats[f], np.float64) for f in ("xi", "occ", "occ_y"))
     if xi.ndim != 3 or occ.ndim != 2 or occ_y.ndim != 2 or not xi.shape[0] == occ.shape[0] == occ_y.shape[0]:
@@ -81,6 +92,7 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
     (draw_tables: the sweep's records pooled over each group, G tables drawn, expanded to the members).  The members' initial tables
     must be equal bit for bit (ValueError naming the group); every member keeps its own trajectory; the returned shapes stay, with
     and without retable=True."""
+    poisson_refusal(prior.pop("emission", "normal"))
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
     B, k = means.shape

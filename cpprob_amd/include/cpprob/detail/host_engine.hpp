@@ -818,8 +818,12 @@ std::vector<Result> inference_batch(StateType algorithm, const Func& f, const st
 // statistics), ess_threshold (must be > 1: every step) and device come from options(), as for inference_batch.
 // sigmas: empty (the emission of state s is N(means[s], 1)) or k per-state emission scales (N(means[s], sigmas[s]); include/cpprob_hip.h:
 // cpprob_hip_batch_begin_problems_scaled) -- every table of a call with them, or none.
+// emission: the family -- Emission::poisson: state s emits Poisson(means[s]), the means are rates and the observes counts 0 .. 4095
+// (cpprob_hip_batch_begin_problems_poisson); such a table has no sigmas, and every table of a call has the first one's family.
+enum class Emission { normal, poisson };
 struct HmmTable {
     std::vector<double> means, transition, sigmas;
+    Emission emission = Emission::normal;
     HmmTable() = default;
     HmmTable(std::vector<double> m, std::vector<double> t, std::vector<double> s = std::vector<double>()) : means(std::move(m)), transition(std::move(t)), sigmas(std::move(s)) {}
 };
@@ -829,6 +833,7 @@ struct HmmTableProblems {
     std::size_t k = 0, T_max = 0, n_max = 0;
     std::vector<double> means, trans, flat;     // [B][k], [B][k][k], the observes packed problem after problem
     std::vector<double> sigmas;                 // [B][k], or empty: the tables carry no emission scales
+    bool poisson = false;                       // the tables' emission is Poisson: means holds the rates
     std::vector<std::uint32_t> T, np;           // [B]
 };
 
@@ -841,6 +846,7 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
         throw std::runtime_error(who + ": tables, observes and n hold one entry per seed, or one entry shared by all problems");
     HmmTableProblems pk;
     pk.k = tables[0].means.size();
+    pk.poisson = tables[0].emission == Emission::poisson;
     pk.T.resize(B); pk.np.resize(B);
     for (std::size_t b = 0; b < B; ++b) {
         const HmmTable& tb = tables[tables.size() == 1 ? 0 : b];
@@ -848,6 +854,8 @@ inline HmmTableProblems pack_hmm_table_problems(const std::string& who, const st
             throw std::runtime_error(who + ": problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
         if (tb.sigmas.size() != (tables[0].sigmas.empty() ? 0 : pk.k))
             throw std::runtime_error(who + ": problem " + std::to_string(b) + ": every table holds k emission scales, or none does");
+        if ((tb.emission == Emission::poisson) != pk.poisson || (pk.poisson && !tb.sigmas.empty()))
+            throw std::runtime_error(who + ": problem " + std::to_string(b) + ": every table has one emission family, and a Poisson table has no emission scales");
         pk.means.insert(pk.means.end(), tb.means.begin(), tb.means.end());
         pk.trans.insert(pk.trans.end(), tb.transition.begin(), tb.transition.end());
         pk.sigmas.insert(pk.sigmas.end(), tb.sigmas.begin(), tb.sigmas.end());
@@ -895,7 +903,12 @@ inline std::vector<Result> run_hmm_table_problems(Context& ctx, const HmmTablePr
     bc.n_problems = B;
     const auto t0 = std::chrono::steady_clock::now();
     const bool scaled = !pk.sigmas.empty();
-    if (retable && scaled)
+    if (retable && pk.poisson)
+        ctx.check(cpprob_hip_batch_retable_poisson(ctx.get(), pk.means.data(), pk.trans.data(), with_observes ? pk.flat.data() : nullptr, pk.flat.size()), "cpprob_hip_batch_retable_poisson");
+    else if (pk.poisson)
+        ctx.check(cpprob_hip_batch_begin_problems_poisson(ctx.get(), &bc, T.data(), pk.np.data(), pk.flat.data(), static_cast<std::int32_t>(k), pk.means.data(), pk.trans.data()),
+                  "cpprob_hip_batch_begin_problems_poisson");
+    else if (retable && scaled)
         ctx.check(cpprob_hip_batch_retable_scaled(ctx.get(), pk.means.data(), pk.trans.data(), pk.sigmas.data(), with_observes ? pk.flat.data() : nullptr, pk.flat.size()),
                   "cpprob_hip_batch_retable_scaled");
     else if (retable)
@@ -987,6 +1000,8 @@ inline std::vector<Result> hmm_table_batch(const std::vector<HmmTable>& tables, 
 // Tables with emission scales (HmmTable::sigmas): the batches are scaled; options().learn_scales: the M-step fits the scales too -- a
 // state with mass takes v = occ_yy[s] / occ[s] - means[s] means[s] (its new mean) and sigmas[s] = sqrt(v) where v >= scale_floor^2, else
 // options().scale_floor (a NaN v too), the statements of cpprob_hip_batch_mstep_scaled_device.  Without it the scales stay.
+// Poisson tables (HmmTable::emission): the batches are Poisson ones and the M-step's means[s] = occ_y[s] / occ[s] is the rate's, kept at or
+// above options().rate_floor (a NaN too), the statements of cpprob_hip_batch_mstep_poisson_device.
 // options().tie_groups (one group id a problem): tied tables -- every begun batch is tied (cpprob_hip_batch_tie; once with
 // fit_on_device, a re-table keeps the tie) and an iteration's records go through cpprob_hip_batch_pool_stats (broadcast) in front of
 // the M-step's statements, which are unchanged: the members of a group, which must start from one table bit for bit (else
@@ -1011,6 +1026,9 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
     const double floor = options().scale_floor;
     if (fit_scales && pk.sigmas.empty()) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().learn_scales fits emission scales: give every table its sigmas");
     if (fit_scales && (!(floor > 0.0) || !std::isfinite(floor))) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().scale_floor must be finite and > 0");
+    const double rate_floor = options().rate_floor;
+    if (pk.poisson && fit_scales) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().learn_scales fits emission scales: a Poisson table has none");
+    if (pk.poisson && (!(rate_floor > 0.0) || !std::isfinite(rate_floor))) throw std::runtime_error("cpprob::gpu::hmm_table_fit: options().rate_floor must be finite and > 0");
     const std::vector<std::int32_t>& tie = options().tie_groups;
     if (!tie.empty()) {
         // a group's members start from one table, bit for bit; lead[g]: the group's first member
@@ -1052,6 +1070,7 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
                 if (row > 0.0)
                     for (std::size_t j = 0; j < k; ++j) pk.trans[(b * k + s) * k + j] = r[8 * s + j] / row;
                 if (r[64 + s] > 0.0) pk.means[b * k + s] = r[72 + s] / r[64 + s];
+                if (pk.poisson && r[64 + s] > 0.0 && !(pk.means[b * k + s] >= rate_floor)) pk.means[b * k + s] = rate_floor;
                 if (fit_scales && r[64 + s] > 0.0) {
                     const double mean = pk.means[b * k + s], mm = mean * mean, ff = floor * floor;
                     double v = r[80 + s] / r[64 + s];
@@ -1073,6 +1092,7 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
         fit.tables[b].means.assign(pk.means.begin() + static_cast<std::ptrdiff_t>(b * k), pk.means.begin() + static_cast<std::ptrdiff_t>((b + 1) * k));
         fit.tables[b].transition.assign(pk.trans.begin() + static_cast<std::ptrdiff_t>(b * k * k), pk.trans.begin() + static_cast<std::ptrdiff_t>((b + 1) * k * k));
         if (!pk.sigmas.empty()) fit.tables[b].sigmas.assign(pk.sigmas.begin() + static_cast<std::ptrdiff_t>(b * k), pk.sigmas.begin() + static_cast<std::ptrdiff_t>((b + 1) * k));
+        if (pk.poisson) fit.tables[b].emission = Emission::poisson;
     }
     return fit;
 }
@@ -1110,6 +1130,8 @@ inline HmmTableFit hmm_table_fit(const std::vector<HmmTable>& tables, const std:
 // Tables with emission scales (HmmTable::sigmas): the stream is a scaled one (cpprob_hip_batch_begin_online_scaled); with
 // options().learn_tables and options().learn_scales the learner fits the scales too, none below options().scale_floor
 // (cpprob_hip_batch_learn_begin_scaled) -- without learn_scales it learns means and transition rows and keeps them; tables() returns them.
+// Poisson tables (HmmTable::emission): the stream is a Poisson one (cpprob_hip_batch_begin_online_poisson); options().learn_tables is
+// refused for it (std::runtime_error): online EM serves the Gaussian families.
 // options().learn_tables with options().tie_groups (one group id a problem; options().learn_tied asks for them): tied online EM -- the
 // stream is tied and its learner pools over the tie (cpprob_hip_batch_tie, _learn_tie): the streams of a group, which must start from one
 // table bit for bit, learn ONE table from their pooled records, every stream weighing equally whatever its length; the burn-in counts the
@@ -1140,6 +1162,9 @@ public:
             throw std::runtime_error("cpprob::gpu::HmmTableStream: tables, capacities and n hold one entry per seed, or one entry shared by all problems");
         std::vector<double> means, trans, sigmas;
         scaled_ = !tables[0].sigmas.empty();
+        poisson_ = tables[0].emission == Emission::poisson;
+        if (poisson_ && learn_)
+            throw std::runtime_error("cpprob::gpu::HmmTableStream: options().learn_tables (online EM) serves Gaussian emissions: a Poisson stream is fitted by cpprob::gpu::hmm_table_fit");
         if (options().learn_scales && learn_ && !scaled_)
             throw std::runtime_error("cpprob::gpu::HmmTableStream: options().learn_scales fits emission scales: give every table its sigmas");
         std::vector<std::uint32_t> cap(B_);
@@ -1151,6 +1176,8 @@ public:
                 throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": every table holds k means and k x k transition weights, k that of the first table");
             if (tb.sigmas.size() != (scaled_ ? k_ : 0))
                 throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": every table holds k emission scales, or none does");
+            if ((tb.emission == Emission::poisson) != poisson_ || (poisson_ && scaled_))
+                throw std::runtime_error("cpprob::gpu::HmmTableStream: problem " + std::to_string(b) + ": every table has one emission family, and a Poisson table has no emission scales");
             means.insert(means.end(), tb.means.begin(), tb.means.end());
             trans.insert(trans.end(), tb.transition.begin(), tb.transition.end());
             sigmas.insert(sigmas.end(), tb.sigmas.begin(), tb.sigmas.end());
@@ -1170,7 +1197,10 @@ public:
         bc.n_particles = n_max;
         bc.n_problems = B_;
         Context& ctx = *lease_;
-        if (scaled_)
+        if (poisson_)
+            ctx.check(cpprob_hip_batch_begin_online_poisson(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), seeds.data()),
+                      "cpprob_hip_batch_begin_online_poisson");
+        else if (scaled_)
             ctx.check(cpprob_hip_batch_begin_online_scaled(ctx.get(), &bc, cap.data(), np_.data(), static_cast<std::int32_t>(k_), means.data(), trans.data(), sigmas.data(),
                                                            seeds.data()), "cpprob_hip_batch_begin_online_scaled");
         else
@@ -1344,6 +1374,7 @@ private:
     bool running_stats_ = options().running_stats;
     bool learn_ = options().learn_tables;
     bool scaled_ = false;                      // the tables carry emission scales
+    bool poisson_ = false;                     // the tables' emission is Poisson
     std::size_t dump_max_ = options().dump_max_particles;
     std::vector<std::uint32_t> np_;
     ContextLease lease_;

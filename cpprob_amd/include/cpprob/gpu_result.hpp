@@ -57,6 +57,7 @@ struct Options {
     bool learn_scales = false;                        // hmm_table_fit and HmmTableStream with learn_tables, tables with HmmTable::sigmas: the per-state emission
                                                       // scales are fitted too (the M-step's sigma' = sqrt(occ_yy / occ - mean'^2)), none below scale_floor
     double scale_floor = 1e-3;                        // ... finite and > 0
+    double rate_floor = 1e-6;                         // hmm_table_fit, tables with HmmTable::emission = Emission::poisson: no rate is fitted below it; finite and > 0
     std::size_t learn_burn_in = 20;                   // ... and no M-step before a problem has reached this length
     bool learn_tied = false;                          // HmmTableStream with learn_tables: tied online EM -- tie_groups (then required) partitions the streams,
                                                       // and the streams of a group learn ONE table on the device from their pooled records

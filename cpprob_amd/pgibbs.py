@@ -31,6 +31,8 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     n_particles >= 1, up to the 32-bit quantisation of weights and thresholds; n_particles moves how fast the chain mixes, not where
     it settles.  (hmm_table_gibbs draws its trajectory from an unconditional filter and is exact only as n_particles grows.)"""
     import torch
+    from .gibbs import poisson_refusal
+    poisson_refusal(prior.pop("emission", "normal"))
     retable = bool(prior.pop("retable", False))
     sigmas0 = prior.pop("sigmas0", None)
     groups = prior.pop("groups", None)

@@ -839,6 +839,42 @@ int cpprob_hip_batch_learn_tables_scaled_device(cpprob_hip_ctx* ctx, double* d_m
  * CPPROB_HIP_ESTATE: no batch begun, or a batch without scales.  For tests. */
 int cpprob_hip_batch_copy_scales(cpprob_hip_ctx* ctx, uint64_t problem, double* h_sigmas, double* h_log_norm);
 
+/* ---- Poisson emissions of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_poisson.hpp) --
+ * State s of problem b emits Poisson(rate[b][s]); the rates stand where the means stand ([B][k]).  A batch is unit, scaled or Poisson,
+ * never two of them: every call of one family on a batch of another returns CPPROB_HIP_ESTATE and leaves the batch as it was.  The
+ * step kernel and every pass behind it read the emission through the per-step rows alone, so a Poisson batch is run, advanced,
+ * smoothed, counted, forecast and decoded by the calls above as they are.  Every Poisson row, on the host and on the device, is
+ *   r = y * log_rate;  r = r - rate;  r = r - lf[y]                      (-inf for s >= k and for a y that is no count)
+ * with log_rate = table_log(rate) and lf[c] = lf[c - 1] + table_log(c), lf[0] = lf[1] = 0, a table of 4096 doubles the host fills once
+ * a context and uploads (an allocation of the context's own); a count is an integer 0 .. 4095 held in a double -- NaN, infinities,
+ * negatives, non-integers and larger values have the row of an infinite observe under the Gaussian routes.  The operations are not
+ * contracted: host and device write the same bits.
+ * The begins: cpprob_hip_batch_begin_problems / _begin_online with h_rates in place of h_means, which must be given with h_transition
+ * (CPPROB_HIP_EINVAL where one is NULL; another model: CPPROB_HIP_EUNSUPPORTED).  Every rate must be > 0, finite and a normal number
+ * (CPPROB_HIP_EINVAL naming the problem; after a refusal nothing has changed).  cpprob_hip_batch_advance writes a Poisson batch's rows
+ * with the statements above.
+ * The re-tables: cpprob_hip_batch_retable_device / _retable with rates.  The device checks the transition rows as those calls do and
+ * sets status bit 16 where a rate is not > 0, not finite or not normal (bit 4 is not used): such a problem keeps its rows, threshold
+ * words, rates and log-rates.
+ * The M-step: cpprob_hip_batch_mstep_device's statements on d_rates (rate = occ_y / occ), then a state with occ[s] > 0 takes
+ *   rates[s] = rates[s] >= rate_floor ? rates[s] : rate_floor            (a NaN: the floor)
+ * and, where d_log_rates [B][k] is not NULL, log_rates[s] = table_log of it (NaN for a rate the check refuses).  A state without mass
+ * keeps both.  rate_floor finite and > 0 (else CPPROB_HIP_EINVAL).  cpprob_amd.em.m_step(emission="poisson"), bit for bit.  Enqueued.
+ * cpprob_hip_batch_online_tables_poisson: cpprob_hip_batch_online_tables with rates.  cpprob_hip_batch_learn_begin* on a Poisson batch:
+ * CPPROB_HIP_ESTATE (online EM serves the Gaussian families).
+ * cpprob_hip_batch_copy_rates: problem `problem`'s rates and log-rates in force as the device holds them, [k] each (either may be
+ * NULL); synchronises; CPPROB_HIP_ESTATE: no batch begun, or no Poisson batch.  For tests. */
+int cpprob_hip_batch_begin_problems_poisson(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                            const double* h_observes, int32_t k, const double* h_rates, const double* h_transition);
+int cpprob_hip_batch_begin_online_poisson(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_Tcap, const uint32_t* h_n,
+                                          int32_t k, const double* h_rates, const double* h_transition, const uint64_t* h_seeds);
+int cpprob_hip_batch_retable_poisson_device(cpprob_hip_ctx* ctx, const double* d_rates, const double* d_transition, const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_poisson(cpprob_hip_ctx* ctx, const double* h_rates, const double* h_transition, const double* h_observes, size_t n_observes);
+int cpprob_hip_batch_mstep_poisson_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_rates, double* d_transition,
+                                          double* d_log_rates, double rate_floor);
+int cpprob_hip_batch_online_tables_poisson(cpprob_hip_ctx* ctx, const double* h_rates, const double* h_transition);
+int cpprob_hip_batch_copy_rates(cpprob_hip_ctx* ctx, uint64_t problem, double* h_rates, double* h_log_rates);
+
 /* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
  * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
  * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
