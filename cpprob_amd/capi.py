@@ -63,6 +63,7 @@ SYMBOLS = [
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
+    "cpprob_hip_batch_draw_tables_device",
 ]
 
 
@@ -92,6 +93,10 @@ FORM_FLOAT, FORM_COUNTS, FORM_FIXED = 0, 1, 2
 class BatchConfig(C.Structure):
     _fields_ = [("algorithm", C.c_int32), ("model", C.c_int32), ("resampler", C.c_int32), ("keep_history", C.c_int32),
                 ("flags", C.c_uint32), ("ess_threshold", C.c_double), ("n_particles", C.c_uint64), ("n_problems", C.c_uint64)]
+
+
+class GibbsPrior(C.Structure):
+    _fields_ = [("alpha", C.c_double), ("mu0", C.c_double), ("tau0", C.c_double), ("a0", C.c_double), ("b0", C.c_double)]
 
 
 BATCH_MAX_PARTICLES = 8192
@@ -437,6 +442,7 @@ def load_library(path=None):
         "cpprob_hip_batch_pool_stats_device": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_int, vp, sz]),
         "cpprob_hip_batch_learn_tie": (C.c_int, [vp]),
         "cpprob_hip_batch_learn_pooled_record": (C.c_int, [vp, vp, sz]),
+        "cpprob_hip_batch_draw_tables_device": (C.c_int, [vp, vp, sz, vp, u64, C.POINTER(GibbsPrior), i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -848,6 +854,22 @@ class Engine:
                                                                   float(sigma_floor)))
         else:
             self._chk(self.L.cpprob_hip_batch_mstep_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(trans)))
+
+    def batch_draw_tables_device(self, stats, seeds, sweep, means, trans, sigmas=None, status=None, alpha=1.0, mu0=0.0, tau0=10.0, a0=2.0, b0=1.0, max_attempts=64):
+        """gibbs.sample_tables' posteriors drawn on the device (cpprob_hip_batch_draw_tables_device; csrc/batch_gibbs.hpp), from the
+        device's own generator -- Marsaglia-Tsang gammas on polar normals over Philox blocks, not numpy's stream: stats torch float64
+        [B, 88] as batch_traj_stats_device leaves them with n_traj = 1; seeds a torch tensor of B 64-bit words on the device (the
+        bits of uint64 keys); sweep < 2^16 picks the sweep's words; means [B, k], trans [B, k, k] and -- a batch with emission
+        scales -- sigmas [B, k] torch float64, updated in place; status int32 [B], if given: 0, batch_retable_status' bits of the
+        drawn table, or 32 where a variate found no draw within max_attempts (1 .. 64) -- such a problem keeps its table.  alpha >= 1,
+        a0 >= 1.  Enqueued without a host synchronisation; batch_retable_device then gives the batch the tables."""
+        if seeds is None or seeds.numel() != self.batch_B or seeds.element_size() != 8:
+            raise ValueError("seeds: a device tensor of one 64-bit word per problem")
+        if status is not None and (status.numel() < self.batch_B or status.element_size() != 4):
+            raise ValueError("status: a device tensor of one int32 per problem")
+        prior = GibbsPrior(float(alpha), float(mu0), float(tau0), float(a0), float(b0))
+        self._chk(self.L.cpprob_hip_batch_draw_tables_device(self.h, _dptr(stats), stats.numel(), _dptr(seeds), int(sweep), C.byref(prior), int(max_attempts),
+                                                             _dptr(means), _dptr(trans), _dptr(sigmas), _dptr(status)))
 
     # ---- tied tables (include/cpprob_hip.h: cpprob_hip_batch_tie, _pool_stats*) --------------------------------------
     def batch_tie(self, groups):

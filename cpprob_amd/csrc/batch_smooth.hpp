@@ -45,6 +45,7 @@ constexpr int kBackwardMaxT = 1 << 24;              // steps a problem may have:
 constexpr int kBackwardMaxTraj = 1 << 20;           // trajectories a problem in one call
 constexpr int kBackwardMaxDraws = 1 << 16;          // draw_index < this: the ordinals stay inside [2^41, 2^42)
 constexpr uint64_t kBackwardDrawBase = 1ull << 41;  // clear of the particles' statement ordinals and of the resampling draws at 2^40 + ...
+                                                    // (the table draws of csrc/batch_gibbs.hpp sit at 2^44, clear of these and of every range between)
 constexpr int kBackwardLdsMax = 32768;              // bytes of m table a tile stages: T <= 512
 constexpr int kSmoothCountGroups = 8192;            // workgroups the counting pass aims at: gridDim.y = min(rows owed, max(8, ceil(this / B)))
 constexpr int kSmoothLagGridMax = 4096;             // gridDim.y of batch_smooth_lag_kernel at most: kWaves times it items a problem and trip

@@ -36,6 +36,7 @@
 #include "batch_pass_plan.hpp"
 #include "batch_buffers.hpp"
 #include "batch_pool.hpp"
+#include "batch_gibbs.hpp"
 
 using namespace cph;
 
@@ -5713,6 +5714,45 @@ int cpprob_hip_batch_mstep_scaled_device(cpprob_hip_ctx* c, const double* d_stat
                                          double* d_log_norm, double sigma_floor)
 {
     return batch_mstep_device(c, d_stats, n_doubles, d_means, d_transition, kFamilyScaled, d_sigmas, d_log_norm, sigma_floor);
+}
+
+// ---- the conjugate draw of a Gibbs sweep (csrc/batch_gibbs.hpp) ---------------------------------------------------------------------
+static_assert(sizeof(cpprob_hip_gibbs_prior) == sizeof(GibbsPrior), "the kernel's prior is the C ABI's");
+
+int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, const uint64_t* d_seeds, uint64_t sweep,
+                                        const cpprob_hip_gibbs_prior* prior, int max_attempts, double* d_means, double* d_transition, double* d_sigmas,
+                                        int32_t* d_status)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the draw samples the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!bs->own_tables) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the batch was begun with the context's shared table: begin it with per-problem tables to draw them");
+    if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: the conjugate (gamma) draw of its rates is not built -- fit it with cpprob_hip_batch_mstep_poisson_device");
+    if (bs->scaled && !d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its draw takes d_sigmas");
+    if (!bs->scaled && d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: its draw takes no d_sigmas (begin it with cpprob_hip_batch_begin_problems_scaled)");
+    if (!d_stats || !d_seeds || !prior || !d_means || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    const cpprob_hip_gibbs_prior p = *prior;
+    if (!std::isfinite(p.alpha) || !std::isfinite(p.mu0) || !std::isfinite(p.tau0) || !std::isfinite(p.a0) || !std::isfinite(p.b0))
+        return fail(c, CPPROB_HIP_EINVAL, "the prior must be finite");
+    if (p.alpha < 1.0 || p.a0 < 1.0) return fail(c, CPPROB_HIP_EINVAL, "alpha >= 1 and a0 >= 1: the gamma generator serves shapes >= 1");
+    if (!(p.tau0 > 0.0) || !(p.b0 > 0.0)) return fail(c, CPPROB_HIP_EINVAL, "tau0 > 0 and b0 > 0");
+    if (max_attempts < 1 || max_attempts > kGibbsMaxAttempts) return fail(c, CPPROB_HIP_EINVAL, "max_attempts is 1 .. 64");
+    if (sweep >= kGibbsMaxSweep) return fail(c, CPPROB_HIP_EINVAL, "sweep < 2^16");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kRetableStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (88 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchDrawTablesArgs a{};
+    a.stats = d_stats; a.seeds = d_seeds; a.means = d_means; a.trans = d_transition; a.sigmas = d_sigmas; a.status = d_status;
+    a.prior = GibbsPrior{p.alpha, p.mu0, p.tau0, p.a0, p.b0};
+    a.draw_base = kTableDrawBase + (sweep << 24);
+    a.B = (int)B; a.k = bs->hk; a.max_attempts = max_attempts;
+    const dim3 grid((unsigned)((B + kWaves - 1) / kWaves));
+    if (bs->scaled) hipLaunchKernelGGL(batch_draw_tables_scaled_kernel, grid, dim3(kThreads), 0, c->stream, a);
+    else hipLaunchKernelGGL(batch_draw_tables_kernel, grid, dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
 }
 
 // ---- tied tables: a partition of the begun batch's problems and the pooled records of its groups (csrc/batch_pool.hpp) -------------

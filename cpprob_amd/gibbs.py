@@ -69,7 +69,7 @@ def draw_tables(one, k, rng, sigmas, tie, prior):
 
 
 def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps, rng, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, retable=False, sigmas0=None,
-                    groups=None, **prior):
+                    groups=None, resident=False, table_seeds=None, **prior):
     """Batched Gibbs sampling of the tables, one chain a problem.  observes: a list of B 1-D sequences, or one sequence every chain
     shares; means0 [B, k], trans0 [B, k, k] the chains' initial tables; seeds [B]; rng a numpy Generator; prior: sample_tables' alpha,
     mu0, tau0.  Sweep i begins a batch with the current tables (batch_begin_problems), runs it with seeds + i, takes the statistics of
@@ -91,7 +91,17 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
     groups int [B]: tied tables -- the chains of a group share one table, drawn from the posterior given all of their trajectories
     (draw_tables: the sweep's records pooled over each group, G tables drawn, expanded to the members).  The members' initial tables
     must be equal bit for bit (ValueError naming the group); every member keeps its own trajectory; the returned shapes stay, with
-    and without retable=True."""
+    and without retable=True.
+
+    resident=True: the whole chain is enqueued on the engine's stream (sweeps_resident) -- sweep 0 begins the batch, the observes go up
+    once, and every sweep runs batch_run, batch_traj_stats_device, (groups: batch_pool_stats_device in place,)
+    batch_draw_tables_device and batch_retable_device on tensors that stay on the device; the host looks at nothing between two
+    sweeps and reads the tables and evidences once after the last.  The tables are drawn by the device's own generator
+    (csrc/batch_gibbs.hpp: Marsaglia-Tsang gammas on polar normals over Philox blocks keyed by table_seeds, uint64 [B], default
+    seeds; a group's members take its first member's), so rng is not consumed and the chain is A DIFFERENT CHAIN from the numpy
+    one: the same posteriors, other variates.  alpha >= 1 and a0 >= 1 there.  A problem whose draw is refused (status bits of
+    Engine.batch_draw_tables_device) keeps its table for that sweep; the status words of the last sweep, int32 [B], are returned
+    behind the other arrays.  resident=False is the host route above, unchanged."""
     poisson_refusal(prior.pop("emission", "normal"))
     means = np.array(means0, np.float64)
     trans = np.array(trans0, np.float64)
@@ -107,6 +117,9 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
     if groups is not None:
         from .em import check_tied_start
         tie = check_tied_start(groups, means, trans, sigmas)
+    if resident and int(sweeps) > 0:
+        return sweeps_resident(engine, seqs, means, trans, n_particles, sd, int(sweeps), sigmas, tie, table_seeds, prior, particle=False, resampler=resampler,
+                               keep_history=bool(keep_history))
     m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(sweeps), B))
     s_hist = None if sigmas is None else [sigmas.copy()]
     for i in range(int(sweeps)):
@@ -130,3 +143,73 @@ def hmm_table_gibbs(engine, observes, means0, trans0, n_particles, seeds, sweeps
     if sigmas is None:
         return np.array(m_hist), np.array(t_hist), ev
     return np.array(m_hist), np.array(t_hist), ev, np.array(s_hist)
+
+
+def sweeps_resident(engine, seqs, means, trans, n_particles, sd, sweeps, sigmas, tie, table_seeds, prior, particle, resampler=RESAMPLE_SYSTEMATIC, keep_history=False):
+    """The resident route of hmm_table_gibbs (particle=False) and pgibbs.hmm_table_particle_gibbs (particle=True): their loops with the
+    tables, the observes, the records, the trajectories and the evidences in device tensors and the draw on the device
+    (Engine.batch_draw_tables_device); the host enqueues and looks at nothing until the loop is over.  Returns the host route's
+    arrays and the last sweep's status words."""
+    import torch
+    from .capi import STATS_PER_PROBLEM, batch_smooth_layout
+    B, k = means.shape
+    dev = torch.device("cuda", engine.device)
+    ts = sd if table_seeds is None else np.ascontiguousarray(table_seeds, np.uint64)
+    if ts.shape != (B,):
+        raise ValueError("table_seeds: one uint64 per problem")
+    if tie is not None:
+        ts = ts[tie[2][tie[0]]]                             # (a group's members draw with its first member's words: one table a group)
+    tables = (means, trans) if sigmas is None else (means, trans, sigmas)
+    if particle:
+        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, keep_history=False, keep_masses=True)
+    else:
+        engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, resampler=resampler, keep_history=keep_history, keep_masses=not keep_history)
+    if tie is not None:
+        engine.batch_tie(tie[0])                            # (once: the re-tables keep it)
+    obs = torch.from_numpy(np.ascontiguousarray(np.concatenate(seqs))).to(dev)
+    d_ts = torch.from_numpy(np.ascontiguousarray(ts).view(np.int64)).to(dev)
+    m_all = torch.zeros((sweeps + 1, B, k), dtype=torch.float64, device=dev)
+    t_all = torch.zeros((sweeps + 1, B, k, k), dtype=torch.float64, device=dev)
+    m_all[0].copy_(torch.from_numpy(means))
+    t_all[0].copy_(torch.from_numpy(trans))
+    s_all = None
+    if sigmas is not None:
+        s_all = torch.zeros((sweeps + 1, B, k), dtype=torch.float64, device=dev)
+        s_all[0].copy_(torch.from_numpy(sigmas))
+    stats = torch.zeros((B, 1, STATS_PER_PROBLEM), dtype=torch.float64, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    ev = None if particle else torch.zeros((sweeps, B, 4), dtype=torch.float64, device=dev)
+    traj = None
+    if particle:
+        total = int(batch_smooth_layout([len(o) for o in seqs], 1)[-1])
+        traj = [torch.empty(total, dtype=torch.int8, device=dev) for _ in range(2)]
+    torch.cuda.current_stream(dev).synchronize()            # (the engine's stream is not ordered behind torch's: the tensors are complete first)
+    stream = torch.cuda.ExternalStream(engine.stream_ptr, device=dev)
+    for i in range(sweeps):
+        draw = i % (1 << 16)
+        if particle and i > 0:
+            engine.batch_run_conditional_device(sd + np.uint64(i), traj[(i - 1) & 1])
+        else:
+            engine.batch_run(sd + np.uint64(i))
+        if particle:
+            engine.batch_smooth_device(traj_i8=traj[i & 1], n_traj=1, draw_index=draw)
+        engine.batch_traj_stats_device(stats, 1, draw_index=draw, observes=obs)
+        if ev is not None:
+            engine.batch_summaries_device(ev[i])
+        if tie is not None:
+            engine.batch_pool_stats_device(stats, stats)     # (in place: every member's record becomes its group's)
+        with torch.cuda.stream(stream):                     # (the next tables start as these: a copy on the engine's stream)
+            m_all[i + 1].copy_(m_all[i])
+            t_all[i + 1].copy_(t_all[i])
+            if s_all is not None:
+                s_all[i + 1].copy_(s_all[i])
+        nxt = None if s_all is None else s_all[i + 1]
+        engine.batch_draw_tables_device(stats, d_ts, draw, m_all[i + 1], t_all[i + 1], sigmas=nxt, status=status, **prior)
+        engine.batch_retable_device(m_all[i + 1], t_all[i + 1], obs, sigmas=nxt)
+    engine.sync()
+    out = (m_all.cpu().numpy(), t_all.cpu().numpy())
+    if ev is not None:
+        out += (np.ascontiguousarray(ev[:, :, 0].cpu().numpy()),)
+    if s_all is not None:
+        out += (s_all.cpu().numpy(),)
+    return out + (status.cpu().numpy(),)

@@ -24,6 +24,13 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     groups int [B] (a keyword likewise, default None): tied tables -- the chains of a group share one table, drawn given all of
     their trajectories (gibbs.draw_tables); the members' initial tables must be equal bit for bit (ValueError naming the group), and
     every member keeps its own trajectory and its own retained path.
+    resident=True, table_seeds=None (keywords likewise): the whole chain is enqueued on the engine's stream (gibbs.sweeps_resident:
+    sweep 0 begins the batch, the observes go up once; every sweep runs the run, batch_smooth_device, batch_traj_stats_device,
+    (groups: batch_pool_stats_device in place,) batch_draw_tables_device and batch_retable_device on device tensors) and the host
+    looks at nothing between two sweeps.  The tables are drawn by the device's own generator (csrc/batch_gibbs.hpp, keyed by
+    table_seeds, uint64 [B], default seeds; a group's members take its first member's), so rng is not consumed and the chain is A
+    DIFFERENT CHAIN from the numpy one: the same posteriors, other variates.  alpha >= 1 and a0 >= 1 there.  A problem whose draw is
+    refused keeps its table for that sweep; the last sweep's status words, int32 [B], are returned behind the other arrays.
 
     This is particle Gibbs with backward sampling: a conditional SMC run with multinomial resampling, its retained particle the
     previous trajectory, followed by backward simulation.  That kernel leaves the smoothing law of the states given the tables
@@ -36,6 +43,8 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     retable = bool(prior.pop("retable", False))
     sigmas0 = prior.pop("sigmas0", None)
     groups = prior.pop("groups", None)
+    resident = bool(prior.pop("resident", False))
+    table_seeds = prior.pop("table_seeds", None)
     sigmas = None if sigmas0 is None else np.array(sigmas0, np.float64)
     s_hist = None if sigmas is None else [sigmas.copy()]
     means = np.array(means0, np.float64)
@@ -51,6 +60,9 @@ def hmm_table_particle_gibbs(engine, observes, means0, trans0, n_particles, seed
     if groups is not None:
         from .em import check_tied_start
         tie = check_tied_start(groups, means, trans, sigmas)
+    if resident and int(sweeps) > 0:
+        from .gibbs import sweeps_resident
+        return sweeps_resident(engine, seqs, means, trans, n_particles, sd, int(sweeps), sigmas, tie, table_seeds, prior, particle=True)
     total = int(batch_smooth_layout([len(o) for o in seqs], 1)[-1])
     traj = [torch.empty(total, dtype=torch.int8, device="cuda:%d" % engine.device) for _ in range(2)]
     m_hist, t_hist = [means.copy()], [trans.copy()]

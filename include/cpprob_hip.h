@@ -922,6 +922,33 @@ int cpprob_hip_batch_learn_tie(cpprob_hip_ctx* ctx);
 /* The groups' pooled records [G][88] of the last tied learning advance (n_doubles >= 88 G; none yet: zeros).  Synchronises. */
 int cpprob_hip_batch_learn_pooled_record(cpprob_hip_ctx* ctx, double* h_out, size_t n_doubles);
 
+/* ---- the conjugate draw of a Gibbs sweep on the device (csrc/batch_gibbs.hpp) --
+ * Priors: every transition row Dirichlet(alpha, .., alpha), every mean N(mu0, tau0^2), every variance (a batch with emission scales)
+ * inverse-gamma(a0, b0).  Finite; alpha >= 1 and a0 >= 1 (the gamma generator serves shapes >= 1), tau0 > 0, b0 > 0. */
+typedef struct cpprob_hip_gibbs_prior {
+    double alpha, mu0, tau0, a0, b0;
+} cpprob_hip_gibbs_prior;
+/* Draws the next table of every problem of the begun CPPROB_HIP_MODEL_HMM_TABLE batch (per-problem tables) from its conjugate
+ * posterior given one trajectory's record a problem (d_stats [n_problems][88] as cpprob_hip_batch_traj_stats_device leaves them with
+ * n_traj = 1, pooled or not; n_doubles >= 88 n_problems), over the caller's device arrays d_means [B][k], d_transition [B][k][k] and
+ * -- a batch with emission scales -- d_sigmas [B][k], whose current values the mean's posterior reads:
+ *   G[s][j] ~ Gamma(alpha + xi[s][j]);  trans[s][j] = G[s][j] / (((0.0 + G[s][0]) + G[s][1]) + ...)
+ *   unit:    prec = 1 / tau0^2 + occ[s];  means[s] = (mu0 / tau0^2 + occ_y[s]) / prec + z / sqrt(prec),  z ~ N(0, 1)
+ *   scaled:  the same with occ[s] / sigma[s]^2 and occ_y[s] / sigma[s]^2;  g ~ Gamma(a0 + occ[s] / 2),
+ *            rate = b0 + (occ_yy[s] - 2 means[s] occ_y[s] + means[s]^2 occ[s]) / 2;  sigmas[s] = sqrt(rate / g)
+ * The variates are Marsaglia-Tsang gammas on Marsaglia polar normals over the Philox blocks of d_seeds[b] (uint64 [B], device) at
+ * ordinals 2^44 + (sweep << 24) + ..: log (table_log), sqrt and divide only, none contracted -- tests/gibbs_ref.py restates the call
+ * bit for bit.  Every rejection loop ends after max_attempts (1 .. 64) attempts.  d_status [B] (int32, or NULL): 0, or the bits of
+ * cpprob_hip_batch_retable_status on the drawn table, or 32 alone where a variate found no draw within max_attempts; a problem with
+ * a bit set keeps its table: nothing of it is stored.  The batch itself does not change: cpprob_hip_batch_retable_device (or
+ * _retable_scaled_device) gives it the new tables.  Enqueued on the context's stream, no host synchronisation.
+ * d_sigmas on a batch without scales, or none on a batch with them, and any call on a batch with Poisson emissions (the conjugate
+ * draw of rates is not built): CPPROB_HIP_ESTATE.  A prior outside the above, max_attempts outside 1 .. 64, sweep >= 2^16, a NULL
+ * argument: CPPROB_HIP_EINVAL.  After any refusal nothing has been enqueued. */
+int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, const uint64_t* d_seeds, uint64_t sweep,
+                                        const cpprob_hip_gibbs_prior* prior, int max_attempts, double* d_means, double* d_transition,
+                                        double* d_sigmas, int32_t* d_status);
+
 /* ---- one joint population sharded over several contexts (one per GPU; the caller runs the collective) --
  * cfg.resample_scope = GLOBAL with n_global > n_particles.  Per step t = 0..T-1 (SIS: t = T-1 only):
  *   step_begin(t) propagates and weighs the local shard and writes this shard's
