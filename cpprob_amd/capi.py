@@ -64,6 +64,7 @@ SYMBOLS = [
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
     "cpprob_hip_batch_draw_tables_device",
+    "cpprob_hip_batch_run_exact", "cpprob_hip_batch_exact_evidence", "cpprob_hip_batch_exact_evidence_device",
 ]
 
 
@@ -443,6 +444,9 @@ def load_library(path=None):
         "cpprob_hip_batch_learn_tie": (C.c_int, [vp]),
         "cpprob_hip_batch_learn_pooled_record": (C.c_int, [vp, vp, sz]),
         "cpprob_hip_batch_draw_tables_device": (C.c_int, [vp, vp, sz, vp, u64, C.POINTER(GibbsPrior), i32, vp, vp, vp, vp]),
+        "cpprob_hip_batch_run_exact": (C.c_int, [vp]),
+        "cpprob_hip_batch_exact_evidence": (C.c_int, [vp, vp, vp, sz]),
+        "cpprob_hip_batch_exact_evidence_device": (C.c_int, [vp, vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -786,6 +790,31 @@ class Engine:
         if ref_i8 is None or ref_i8.numel() != int(np.sum(h_T, dtype=np.int64)):
             raise ValueError("the reference paths hold one state per problem and step: %d entries" % int(np.sum(h_T, dtype=np.int64)))
         self._chk(self.L.cpprob_hip_batch_run_conditional_device(self.h, sd.ctypes.data_as(C.POINTER(C.c_uint64)), _dptr(ref_i8), ref_i8.numel()))
+
+    # ---- exact filter runs (include/cpprob_hip.h: cpprob_hip_batch_run_exact) -------------------------------------------
+    def batch_run_exact(self):
+        """The exact forward recursion in place of batch_run (cpprob_hip_batch_run_exact): no particles, no seeds, T_b k^2 a problem.
+        The batch: MODEL_HMM_TABLE of any emission family, keep_history=False, keep_masses=True.  The run keeps the m table (rows
+        that sum to 2^44) and its evidences: batch_masses, batch_smooth*, batch_smooth_stats*, batch_traj_stats*, batch_forecast*,
+        batch_predictive* and batch_decode* serve it as they serve a particle run -- as Baum-Welch's E-step, forward filtering /
+        backward sampling, Viterbi over all states and the exact prequential likelihood --, batch_results waits for the next
+        batch_run.  The backward draws are keyed by the seeds of the begun batch's last batch_run or batch_run_conditional.
+        Enqueued on the engine's stream without a host synchronisation."""
+        self._chk(self.L.cpprob_hip_batch_run_exact(self.h))
+
+    def batch_exact_evidence(self):
+        """(log_z float64 [B], dead int32 [B]) of the last run, an exact one: the exact log-likelihood of every problem's observes, and
+        the first step at which every reachable state had a -inf row (-1: none; from it on log_z is -inf and the rows are zeros)."""
+        log_z = np.zeros(self.batch_B)
+        dead = np.zeros(self.batch_B, np.int32)
+        self._chk(self.L.cpprob_hip_batch_exact_evidence(self.h, log_z.ctypes.data, dead.ctypes.data, self.batch_B))
+        return log_z, dead
+
+    def batch_exact_evidence_device(self, log_z, dead):
+        """The same into a torch float64 and a torch int32 device tensor of B entries each; no host sync."""
+        if log_z is None or dead is None or log_z.numel() < self.batch_B or dead.numel() < self.batch_B:
+            raise ValueError("log_z and dead hold one entry a problem")
+        self._chk(self.L.cpprob_hip_batch_exact_evidence_device(self.h, _dptr(log_z), _dptr(dead), self.batch_B))
 
     # ---- re-tabling a begun batch (include/cpprob_hip.h: cpprob_hip_batch_retable*) ----------------------------------
     def batch_retable(self, tables, observes=None, emission="normal"):

@@ -37,6 +37,7 @@
 #include "batch_buffers.hpp"
 #include "batch_pool.hpp"
 #include "batch_gibbs.hpp"
+#include "batch_exact.hpp"
 
 using namespace cph;
 
@@ -1126,6 +1127,11 @@ struct BatchState {
     // their pinned source, allocations of the context's own
     bool conditional = false, cfirst_ready = false;
     DeviceBuffer d_cfirst; PinnedBuffer pin_cfirst;
+    // exact filter runs (cpprob_hip_batch_run_exact; csrc/batch_exact.hpp): exact: read while `conditional` is set -- the run that left masses
+    // and no books was the exact recursion, and its evidences ([B] doubles) and first dead steps ([B] int32) stand in two allocations of
+    // the context's own
+    bool exact = false;
+    DeviceBuffer d_exact_lz, d_exact_dead;
     // re-tabling (cpprob_hip_batch_retable*; csrc/batch_retable.hpp): the status words [B] and the observes the host form staged, allocations
     // of the context's own; retabled: the begun batch has been re-tabled (its status words are those of the last one); robs_ready: d_robs
     // holds this begun batch's observes; tab_stale / thr_stale: the device holds rows / thresholds the host mirrors (h_tab, h_thr) do not
@@ -4351,6 +4357,7 @@ static int batch_conditional_enqueue(cpprob_hip_ctx* c, const uint64_t* h_seeds,
     hipLaunchKernelGGL(batch_csmc_kernel, dim3((unsigned)B), dim3(kThreads), 0, c->stream, a);
     HIP_TRY(c, hipGetLastError());
     bs->ran = true; bs->conditional = true;
+    bs->exact = false;
     return 0;
 }
 
@@ -4382,6 +4389,82 @@ int cpprob_hip_batch_run_conditional(cpprob_hip_ctx* c, const uint64_t* h_seeds,
     HIP_TRY(c, hipMemcpyAsync(d_ref, v.data(), n_entries, hipMemcpyHostToDevice, c->stream));
     if (int rc = batch_conditional_enqueue(c, h_seeds, d_ref)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));               // (the staged copy has read v; a later host call may take the staging over)
+    return 0;
+}
+
+// ---- exact filter runs of a batch (csrc/batch_exact.hpp) ---------------------------------------------------------------------------
+// The state an exact run needs; nothing is enqueued before it has passed.
+static int batch_exact_check(cpprob_hip_ctx* c)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
+    if (bs->online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "exact runs serve batches begun by cpprob_hip_batch_begin or _begin_problems: an online batch is advanced (cpprob_hip_batch_advance)");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "exact runs serve CPPROB_HIP_MODEL_HMM_TABLE");
+    if (bs->cfg.keep_history != 0 || !batch_masses(&bs->cfg))
+        return fail(c, CPPROB_HIP_ESTATE, "an exact run keeps masses, not a particle store: begin the batch with keep_history = 0 and CPPROB_HIP_BATCH_KEEP_MASSES");
+    return 0;
+}
+
+// The evidences of the last run where it was an exact one: [B] doubles and [B] int32 on the device.
+static int batch_exact_evidence_check(cpprob_hip_ctx* c, const void* log_z, const void* dead, size_t n)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    if (!log_z || !dead) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->ran || !bs->conditional || !bs->exact) return fail(c, CPPROB_HIP_ESTATE, "the evidences are those of an exact run: cpprob_hip_batch_run_exact has not been the batch's last run");
+    if ((uint64_t)n < bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "the arrays hold " + std::to_string(n) + " entries: the batch has " + std::to_string(bs->cfg.n_problems) + " problems");
+    return 0;
+}
+
+// Stream-ordered and without seeds: one launch; waits for nothing, but where the evidences' buffers have to grow, for the calls before it.
+int cpprob_hip_batch_run_exact(cpprob_hip_ctx* c)
+{
+    LANES_OWN(c);
+    if (int rc = batch_exact_check(c)) return rc;
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, bs->d_exact_lz.grow(c->stream, B * sizeof(double)));
+    HIP_TRY(c, bs->d_exact_dead.grow(c->stream, B * sizeof(int32_t)));
+    BatchExactArgs a{};
+    a.tab = reinterpret_cast<const double*>(bs->ws() + bs->lay.tab);
+    a.thr = reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.thr);
+    a.thr_stride = bs->described ? 64 : 0;
+    a.prob = bs->described ? reinterpret_cast<const BatchProblem*>(bs->ws() + bs->lay.prob) : nullptr;
+    a.mass = reinterpret_cast<double*>(bs->ws() + bs->lay.mass);
+    a.log_z = bs->d_exact_lz.as<double>();
+    a.dead = bs->d_exact_dead.as<int32_t>();
+    a.B = (int)B; a.T_max = bs->T; a.k = bs->hk;
+    const unsigned gx = (unsigned)std::min<size_t>((B + kWaves - 1) / kWaves, (size_t)kExactGridMax);
+    hipLaunchKernelGGL(batch_exact_kernel, dim3(gx), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    bs->ran = true; bs->conditional = true; bs->exact = true;  // (masses and no books, as a conditional run leaves the batch)
+    return 0;
+}
+
+int cpprob_hip_batch_exact_evidence_device(cpprob_hip_ctx* c, double* d_log_z, int32_t* d_dead, size_t n)
+{
+    LANES_OWN(c);
+    if (int rc = batch_exact_evidence_check(c, d_log_z, d_dead, n)) return rc;
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(d_log_z, bs->d_exact_lz.as<double>(), B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_dead, bs->d_exact_dead.as<int32_t>(), B * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+int cpprob_hip_batch_exact_evidence(cpprob_hip_ctx* c, double* h_log_z, int32_t* h_dead, size_t n)
+{
+    LANES_OWN(c);
+    if (int rc = batch_exact_evidence_check(c, h_log_z, h_dead, n)) return rc;
+    BatchState* bs = c->batch;
+    const size_t B = bs->cfg.n_problems;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(h_log_z, bs->d_exact_lz.as<double>(), B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_dead, bs->d_exact_dead.as<int32_t>(), B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -4571,6 +4654,7 @@ int cpprob_hip_batch_results(cpprob_hip_ctx* c, cpprob_hip_summary* h_out, doubl
     if (!c || !h_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->conditional && bs->exact) return fail(c, CPPROB_HIP_ESTATE, "an exact run keeps masses and its evidences (cpprob_hip_batch_exact_evidence), not books: the results wait for the next cpprob_hip_batch_run");
     if (bs->conditional) return fail(c, CPPROB_HIP_ESTATE, "a conditional run keeps masses, not books: the results wait for the next cpprob_hip_batch_run");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = bs->cfg.n_problems, T = (size_t)bs->T, need = B * T * (size_t)bs->K;
@@ -4609,6 +4693,7 @@ int cpprob_hip_batch_results_device(cpprob_hip_ctx* c, double* d_out, size_t n_d
     if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->conditional && bs->exact) return fail(c, CPPROB_HIP_ESTATE, "an exact run keeps masses and its evidences (cpprob_hip_batch_exact_evidence), not books: the results wait for the next cpprob_hip_batch_run");
     if (bs->conditional) return fail(c, CPPROB_HIP_ESTATE, "a conditional run keeps masses, not books: the results wait for the next cpprob_hip_batch_run");
     if (!bs->walked) return fail(c, CPPROB_HIP_ESTATE, "the statistics wait for an advance with readout = 1 (cpprob_hip_batch_advance)");
     const int64_t B = (int64_t)bs->cfg.n_problems, per = (int64_t)bs->T * bs->K;
@@ -6224,6 +6309,7 @@ int cpprob_hip_batch_summaries_device(cpprob_hip_ctx* c, double* d_out)
     if (!c || !d_out) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     if (!bs || !bs->ran) return fail(c, CPPROB_HIP_ESTATE, "no finished batch run");
+    if (bs->conditional && bs->exact) return fail(c, CPPROB_HIP_ESTATE, "an exact run keeps masses and its evidences (cpprob_hip_batch_exact_evidence_device), no books: the summaries wait for the next cpprob_hip_batch_run");
     if (bs->conditional) return fail(c, CPPROB_HIP_ESTATE, "a conditional run keeps masses and no books: the summaries wait for the next cpprob_hip_batch_run");
     HIP_TRY(c, hipSetDevice(c->device));
     const int64_t B = (int64_t)bs->cfg.n_problems, total = B * 4;

@@ -117,7 +117,7 @@ def check_tied_start(groups, means, trans, sigmas=None):
 
 
 def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iterations, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, resident=False,
-                 sigmas0=None, sigma_floor=1e-3, groups=None, emission="normal", rate_floor=1e-6):
+                 sigmas0=None, sigma_floor=1e-3, groups=None, emission="normal", rate_floor=1e-6, exact=False):
     """Batched particle EM.  observes: a list of B 1-D sequences, or one sequence every problem shares (restarts: one sequence under
     B initial tables); means0 [B, k], trans0 [B, k, k] the initial tables; seeds [B].  Iteration i begins a batch with the current
     tables (batch_begin_problems), runs it with seeds + i, takes the statistics and the M-step.  Returns (means [iterations + 1, B, k],
@@ -136,7 +136,15 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
     returned shapes stay: members repeat their group's table, log_evidence stays per problem (a group's log-likelihood is its
     members' sum).  Both routes, the same arrays bit for bit.
     emission="poisson": the observes are counts 0 .. 4095 and means0 [B, k] the initial rates of Poisson emissions, none fitted below
-    rate_floor; the means returned are the rates.  Host loop and resident=True, untied and tied, the same arrays bit for bit."""
+    rate_floor; the means returned are the rates.  Host loop and resident=True, untied and tied, the same arrays bit for bit.
+    exact=True: Baum-Welch -- every iteration's run is Engine.batch_run_exact, the exact forward recursion over all states
+    (csrc/batch_exact.hpp), and the statistics are the exact smoother's up to the run's quantisations.  n_particles and seeds are
+    accepted and not used (the batches are begun with n_particles, which the exact run does not read); the evidences returned are the
+    exact run's log-likelihoods (Engine.batch_exact_evidence; resident: its device form).  The batches keep masses, so
+    keep_history=True is a ValueError.  Every emission family, untied and tied, host loop and resident=True: the same arrays bit for
+    bit."""
+    if exact and keep_history:
+        raise ValueError("exact=True runs the exact recursion, which keeps masses and no particle store: pass keep_history=False")
     if emission not in ("normal", "poisson"):
         raise ValueError('emission is "normal" or "poisson"')
     if emission == "poisson" and sigmas0 is not None:
@@ -157,16 +165,19 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
         groups = check_tied_start(groups, means, trans, sigmas)[0]
     if resident and int(iterations) > 0:
         return _em_resident(engine, seqs, means, trans, n_particles, sd, int(iterations), resampler, bool(keep_history), sigmas, float(sigma_floor), groups,
-                            emission, float(rate_floor))
+                            emission, float(rate_floor), bool(exact))
     m_hist, t_hist, ev = [means.copy()], [trans.copy()], np.zeros((int(iterations), B))
     s_hist = None if sigmas is None else [sigmas.copy()]
     for it in range(int(iterations)):
         tables = (means, trans) if sigmas is None else (means, trans, sigmas)
         engine.batch_begin_problems(MODEL_HMM_TABLE, seqs, n_particles, tables=tables, resampler=resampler, keep_history=bool(keep_history),
                                     keep_masses=not keep_history, emission=emission)
-        engine.batch_run(sd + np.uint64(it))
+        if exact:
+            engine.batch_run_exact()
+        else:
+            engine.batch_run(sd + np.uint64(it))
         stats = engine.batch_smooth_stats(seqs)
-        ev[it] = [s["log_evidence"] for s in engine.batch_results()[0]]
+        ev[it] = engine.batch_exact_evidence()[0] if exact else [s["log_evidence"] for s in engine.batch_results()[0]]
         if groups is not None:
             stats = pool_stats(stats, groups)
         if sigmas is None:
@@ -182,7 +193,7 @@ def hmm_table_em(engine, observes, means0, trans0, n_particles, seeds, iteration
 
 
 def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resampler, keep_history, sigmas=None, sigma_floor=1e-3, groups=None,
-                 emission="normal", rate_floor=1e-6):
+                 emission="normal", rate_floor=1e-6, exact=False):
     """hmm_table_em's loop with the tables, the observes, the records and the evidences in device tensors; the host enqueues and
     looks at nothing until the loop is over."""
     import torch
@@ -204,14 +215,22 @@ def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resamp
         s_all[0].copy_(torch.from_numpy(sigmas))
     stats = torch.zeros((B, STATS_PER_PROBLEM), dtype=torch.float64, device=dev)
     ev = torch.zeros((iterations, B, 4), dtype=torch.float64, device=dev)
+    ev_exact = torch.zeros((iterations, B), dtype=torch.float64, device=dev) if exact else None
+    dead = torch.zeros(B, dtype=torch.int32, device=dev) if exact else None
     torch.cuda.current_stream(dev).synchronize()            # (the engine's stream is not ordered behind torch's: the tensors are complete first)
     stream = torch.cuda.ExternalStream(engine.stream_ptr, device=dev)
     for it in range(iterations):
-        engine.batch_run(sd + np.uint64(it))
+        if exact:
+            engine.batch_run_exact()
+        else:
+            engine.batch_run(sd + np.uint64(it))
         engine.batch_smooth_stats_device(stats, obs)
         if groups is not None:
             engine.batch_pool_stats_device(stats, stats)     # (in place: every member's record becomes its group's)
-        engine.batch_summaries_device(ev[it])
+        if exact:
+            engine.batch_exact_evidence_device(ev_exact[it], dead)
+        else:
+            engine.batch_summaries_device(ev[it])
         with torch.cuda.stream(stream):                     # (the next tables start as these: a copy on the engine's stream)
             m_all[it + 1].copy_(m_all[it])
             t_all[it + 1].copy_(t_all[it])
@@ -224,6 +243,7 @@ def _em_resident(engine, seqs, means, trans, n_particles, sd, iterations, resamp
         if it + 1 < iterations:
             engine.batch_retable_device(m_all[it + 1], t_all[it + 1], obs, sigmas=None if s_all is None else s_all[it + 1], emission=emission)
     engine.sync()
+    ev_host = np.ascontiguousarray((ev_exact if exact else ev[:, :, 0]).cpu().numpy())
     if s_all is None:
-        return m_all.cpu().numpy(), t_all.cpu().numpy(), np.ascontiguousarray(ev[:, :, 0].cpu().numpy())
-    return m_all.cpu().numpy(), t_all.cpu().numpy(), np.ascontiguousarray(ev[:, :, 0].cpu().numpy()), s_all.cpu().numpy()
+        return m_all.cpu().numpy(), t_all.cpu().numpy(), ev_host
+    return m_all.cpu().numpy(), t_all.cpu().numpy(), ev_host, s_all.cpu().numpy()

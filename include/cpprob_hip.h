@@ -583,6 +583,35 @@ int cpprob_hip_batch_run_conditional(cpprob_hip_ctx* ctx, const uint64_t* h_seed
  * keeps it alive and unchanged by other streams until the run has finished. */
 int cpprob_hip_batch_run_conditional_device(cpprob_hip_ctx* ctx, const uint64_t* h_seeds, const int8_t* d_ref, size_t n_entries);
 
+/* Exact filter runs of a batch (csrc/batch_exact.hpp): the forward recursion over all k <= 8 states of every problem, with no
+ * particles -- a third forward pass beside cpprob_hip_batch_run and _run_conditional, on a batch begun by cpprob_hip_batch_begin or
+ * _begin_problems* (any emission family) with model CPPROB_HIP_MODEL_HMM_TABLE, keep_history = 0 and CPPROB_HIP_BATCH_KEEP_MASSES.  It
+ * takes no seeds, costs T_b k^2 a problem whatever n_particles is, is enqueued on the context's stream without a host synchronisation,
+ * and writes the batch's m table and nothing else of the workspace.  Per problem (ll_t its per-step rows, P[s][s'] the integer
+ * transition masses of cpprob_hip_batch_smooth; every product one rounded operation, every sum from 0.0 in ascending state order,
+ * nothing contracted):
+ *   u_0[s] = 1.0 (s < k);  u_t[s'] = sum_s m_{t-1}[s] * P[s][s'];  M_t = max{ll_t[s] : u_t[s] > 0}
+ *   w_t[s] = u_t[s] * q_t[s], q_t[s] the run's own 32-bit weight of ll_t[s] under the reference M_t;  W_t = sum_s w_t[s], U_t = sum_s u_t[s]
+ *   m_t[s] = rint((w_t[s] / W_t) * 2^44);  log_z += (M_t + (log W_t - log U_t)) - 32 ln 2, the logarithm cpprob_hip_table_log
+ * The approximation's horizon: a state more than about 22 nats below M_t has the weight 0, as in the particle runs; P lies on a 2^-32
+ * grid and m on a 2^-44 grid.  Within those the run is the exact filter of the law the device draws from.  A step at which every
+ * reachable state has a -inf row (an observe outside the emission family's domain) is dead: from it on the rows are zeros,
+ * log_z = -inf, and the problem's entry of dead is that step (-1: none).
+ * After an exact run every entry point that serves a CPPROB_HIP_BATCH_KEEP_MASSES batch from its m table serves this one unchanged
+ * (the list under cpprob_hip_batch_run_conditional; the seeds of their draws are those of the batch's last seeded run, or the
+ * begin's zeros): the smoothing statistics are Baum-Welch's E-step, the backward simulation is forward filtering / backward sampling,
+ * the decode is Viterbi over all states, the predictive rows are the exact prequential likelihood.  It keeps masses and its
+ * evidences, not books: cpprob_hip_batch_results, _results_device and _summaries_device return CPPROB_HIP_ESTATE until the next
+ * cpprob_hip_batch_run, which returns exactly what it returns without the exact run before it; so does a conditional run or a re-table.
+ * CPPROB_HIP_ESTATE: no batch begun, keep_history = 1, no CPPROB_HIP_BATCH_KEEP_MASSES; CPPROB_HIP_EUNSUPPORTED:
+ * CPPROB_HIP_MODEL_HMM3, an online batch.  Nothing is enqueued where it refuses. */
+int cpprob_hip_batch_run_exact(cpprob_hip_ctx* ctx);
+/* The evidences of the batch's last run, an exact one (else CPPROB_HIP_ESTATE): h_log_z[b] the exact log-likelihood of problem b's
+ * observes, h_dead[b] its first dead step or -1; n the entries each array holds, >= n_problems (else CPPROB_HIP_EINVAL).  Synchronises. */
+int cpprob_hip_batch_exact_evidence(cpprob_hip_ctx* ctx, double* h_log_z, int32_t* h_dead, size_t n);
+/* The same into device buffers: two stream-ordered copies, the host looks at nothing. */
+int cpprob_hip_batch_exact_evidence_device(cpprob_hip_ctx* ctx, double* d_log_z, int32_t* d_dead, size_t n);
+
 /* Forecasts of a batch (csrc/batch_forecast.hpp): what lies ahead of the last observe, from the smoother's m table and the transition
  * law the device itself draws from.  Per problem b (L_b the length reached, k its states, m_t its rows of the m table, P[s][s'] the
  * integer transition masses of cpprob_hip_batch_smooth):
