@@ -65,6 +65,7 @@ SYMBOLS = [
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
     "cpprob_hip_batch_draw_tables_device",
     "cpprob_hip_batch_run_exact", "cpprob_hip_batch_exact_evidence", "cpprob_hip_batch_exact_evidence_device",
+    "cpprob_hip_batch_advance_exact", "cpprob_hip_batch_advance_learn_exact", "cpprob_hip_batch_advance_learn_exact_device",
 ]
 
 
@@ -447,6 +448,9 @@ def load_library(path=None):
         "cpprob_hip_batch_run_exact": (C.c_int, [vp]),
         "cpprob_hip_batch_exact_evidence": (C.c_int, [vp, vp, vp, sz]),
         "cpprob_hip_batch_exact_evidence_device": (C.c_int, [vp, vp, vp, sz]),
+        "cpprob_hip_batch_advance_exact": (C.c_int, [vp, C.POINTER(C.c_uint32), vp]),
+        "cpprob_hip_batch_advance_learn_exact": (C.c_int, [vp, C.POINTER(C.c_uint32), vp]),
+        "cpprob_hip_batch_advance_learn_exact_device": (C.c_int, [vp, C.POINTER(C.c_uint32), vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -802,8 +806,18 @@ class Engine:
         Enqueued on the engine's stream without a host synchronisation."""
         self._chk(self.L.cpprob_hip_batch_run_exact(self.h))
 
+    def batch_advance_exact(self, new_observes):
+        """batch_advance by the exact recursion (cpprob_hip_batch_advance_exact): the online batch -- MODEL_HMM_TABLE of any emission
+        family, keep_history=False, keep_masses=True -- becomes an exact stream at its first advance.  After any sequence of advances the
+        m table, the evidences and the step tables are those of batch_run_exact on the lengths reached, bit for bit; every reader of an
+        online keep_masses batch serves the stream, batch_exact_evidence returns its prequential log-likelihoods, batch_results
+        refuses it.  Exact and particle advances of one stream do not mix.  Enqueued without waiting."""
+        h_dT, flat = self._batch_new_observes(new_observes)
+        self._chk(self.L.cpprob_hip_batch_advance_exact(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), flat.ctypes.data if flat.size else None))
+        self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
+
     def batch_exact_evidence(self):
-        """(log_z float64 [B], dead int32 [B]) of the last run, an exact one: the exact log-likelihood of every problem's observes, and
+        """(log_z float64 [B], dead int32 [B]) of the last run, an exact one, or of an exact stream at the lengths reached: the exact log-likelihood of every problem's observes, and
         the first step at which every reachable state had a -inf row (-1: none; from it on log_z is -inf and the rows are zeros)."""
         log_z = np.zeros(self.batch_B)
         dead = np.zeros(self.batch_B, np.int32)
@@ -997,6 +1011,21 @@ class Engine:
         if h_dT.shape != (self.batch_B,):
             raise ValueError("one count per problem")
         self._chk(self.L.cpprob_hip_batch_advance_learn_device(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), _dptr(observes), 0 if observes is None else observes.numel()))
+        self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
+
+    def batch_advance_learn_exact(self, new_observes):
+        """batch_advance_learn on an armed exact stream (cpprob_hip_batch_advance_learn_exact): the new rows, the exact walk over the new
+        steps and the learn step in one launch, the tied tail behind it where the learner pools.  Enqueued without waiting."""
+        h_dT, flat = self._batch_new_observes(new_observes)
+        self._chk(self.L.cpprob_hip_batch_advance_learn_exact(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), flat.ctypes.data if flat.size else None))
+        self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
+
+    def batch_advance_learn_exact_device(self, dT, observes):
+        """The same with the new observes in a torch float64 device tensor, packed problem after problem; no host synchronisation."""
+        h_dT = np.ascontiguousarray(dT, np.uint32)
+        if h_dT.shape != (self.batch_B,):
+            raise ValueError("one count per problem")
+        self._chk(self.L.cpprob_hip_batch_advance_learn_exact_device(self.h, h_dT.ctypes.data_as(C.POINTER(C.c_uint32)), _dptr(observes), 0 if observes is None else observes.numel()))
         self.batch_shapes = (self.batch_lengths(), self.batch_shapes[1])
 
     def batch_online_tables(self, tables, emission="normal"):

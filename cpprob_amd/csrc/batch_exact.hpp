@@ -35,6 +35,14 @@
 // (Taking step t + 1's weights off the chain by a reachable-state bitmask is not done: a state's mass can round to 0 on the 2^-44 grid,
 // so the reachable set is a function of the values, not of P's zero pattern alone.)  A dead step leaves the walk by a wavefront-uniform
 // branch that shuffles nothing.  No LDS, no barrier, no atomics; rows t >= T_b and everything else in the workspace are not touched.
+//
+// batch_exact_advance_kernel (cpprob_hip_batch_advance_exact): the same statement for the steps t in [first[b], T_b) of every problem of
+// an online batch, in the same layout; the step (exact_step) and the walk (exact_walk) are one text under both kernels.  first[b] < 0
+// or >= T_b: the problem is idle, nothing of it is read or written.  first[b] == 0 starts as above.  first[b] > 0 resumes: m_{t-1} is
+// row first[b] - 1 of the m table -- integers <= 2^44, exact as doubles, so the lanes (s', s) hold the bits the one-shot walk holds --
+// and log_z and dead are the problem's entries of the evidence buffers, which are the carry.  The resumed walk is therefore the
+// one-shot walk of the length reached, bit for bit.  A problem already dead stores zeros in its new rows; its log_z = -inf and its
+// dead stay.  Rows t < first[b] and t >= T_b and everything else in the workspace are not touched.
 #pragma once
 #include "batch_scale.hpp"
 #include "batch_smooth.hpp"
@@ -74,56 +82,106 @@ __device__ __forceinline__ double exact_load_row(const double* row, int sp, doub
     return row[sp];
 }
 
+// One step t of the statement on the lanes (s', s): lc the step's row, lc_sp its entry of state s', ms = m_{t-1}[s] on entry and
+// m_t[s] on return, row = row t of the m table (the lanes (0, s) store it).  false: the step is dead, and nothing has been stored.
+__device__ __forceinline__ bool exact_step(int t, int k, int sp, int s, double p, const double (&lc)[8], double lc_sp, double& ms, double& log_z, double* row)
+{
+#pragma clang fp contract(off)
+    // u[s'] on the lanes (s', .)
+    const double av = dmul_rn(ms, p);
+    double u = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) u = u + __shfl(av, sp * 8 + j);
+    if (t == 0) u = sp < k ? 1.0 : 0.0;
+    // M and U from the eight u, alike in every lane
+    double M = -INFINITY, U = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const double uj = __shfl(u, 8 * j);
+        if (j < k && uj > 0.0) M = fmax(M, lc[j]);
+        U = U + uj;
+    }
+    if (M == -INFINITY) return false;                       // (wavefront-uniform)
+    const uint32_t q = sp < k ? fix_weight(lc_sp, M) : 0u;
+    const double w = dmul_rn(u, (double)q);
+    double W = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) W = W + __shfl(w, 8 * j);
+    const double mn = rint(dmul_rn(w / W, kExactScale));    // m_t[s'] on the lanes (s', .)
+    ms = __shfl(mn, 8 * s);
+    if (sp == 0) row[s] = ms;
+    const double dl = table_log(W) - table_log(U);
+    log_z = log_z + ((M + dl) - kExactLn2x32);
+    return true;
+}
+
+// The steps [t0, T) of one problem from its carry (ms = m_{t0-1}[s], log_z; the problem is not dead), the rows read from tab.
+__device__ __forceinline__ void exact_walk(const double* tab, double* mass, int t0, int T, int k, int sp, int s, double p, double ms, double& log_z, int& dead)
+{
+#pragma clang fp contract(off)
+    double ll[8];
+    double ll_sp = t0 < T ? exact_load_row(tab + (int64_t)t0 * kBatchTab, sp, ll) : 0.0;
+    for (int t = t0; t < T; ++t) {
+        double lc[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lc[j] = ll[j];
+        const double lc_sp = ll_sp;
+        ll_sp = exact_load_row(tab + (int64_t)(t + 1 < T ? t + 1 : t) * kBatchTab, sp, ll);   // (the last step loads its own row again: in bounds, never used)
+        if (!exact_step(t, k, sp, s, p, lc, lc_sp, ms, log_z, mass + (int64_t)t * 8)) {       // a dead step: zeros from here on
+            dead = t;
+            log_z = -INFINITY;
+            for (int tt = t; tt < T; ++tt) if (sp == 0) mass[(int64_t)tt * 8 + s] = 0.0;
+            break;
+        }
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void batch_exact_kernel(BatchExactArgs a)
 {
 #pragma clang fp contract(off)
     const int lane = lane_id(), sp = lane >> 3, s = lane & 7;
     for (int b = exact_uniform((int)blockIdx.x * kWaves + wave_id()); b < a.B; b += (int)gridDim.x * kWaves) {   // (wavefront-uniform)
         const int T = a.prob ? (int)a.prob[b].T : a.T_max;
-        const double* tab = a.tab + (int64_t)b * a.T_max * kBatchTab;
-        double* mass = a.mass + (int64_t)b * a.T_max * 8;
         const double p = smooth_trans_mass(a.thr + (int64_t)b * a.thr_stride, a.k, s, sp);
-        double log_z = 0.0, ms = 0.0;                           // ms: m_{t-1}[s]
+        double log_z = 0.0;
         int dead = -1;
-        double ll[8];
-        double ll_sp = T > 0 ? exact_load_row(tab, sp, ll) : 0.0;
-        for (int t = 0; t < T; ++t) {
-            double lc[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) lc[j] = ll[j];
-            const double lc_sp = ll_sp;
-            ll_sp = exact_load_row(tab + (int64_t)(t + 1 < T ? t + 1 : t) * kBatchTab, sp, ll);   // (the last step loads its own row again: in bounds, never used)
-            // u[s'] on the lanes (s', .)
-            const double av = dmul_rn(ms, p);
-            double u = 0.0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) u = u + __shfl(av, sp * 8 + j);
-            if (t == 0) u = sp < a.k ? 1.0 : 0.0;
-            // M and U from the eight u, alike in every lane
-            double M = -INFINITY, U = 0.0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const double uj = __shfl(u, 8 * j);
-                if (j < a.k && uj > 0.0) M = fmax(M, lc[j]);
-                U = U + uj;
-            }
-            if (M == -INFINITY) {                               // a dead step (wavefront-uniform): zeros from here on
-                dead = t;
-                log_z = -INFINITY;
-                for (int tt = t; tt < T; ++tt) if (sp == 0) mass[(int64_t)tt * 8 + s] = 0.0;
-                break;
-            }
-            const uint32_t q = sp < a.k ? fix_weight(lc_sp, M) : 0u;
-            const double w = dmul_rn(u, (double)q);
-            double W = 0.0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) W = W + __shfl(w, 8 * j);
-            const double mn = rint(dmul_rn(w / W, kExactScale));    // m_t[s'] on the lanes (s', .)
-            ms = __shfl(mn, 8 * s);
-            if (sp == 0) mass[(int64_t)t * 8 + s] = ms;
-            const double dl = table_log(W) - table_log(U);
-            log_z = log_z + ((M + dl) - kExactLn2x32);
+        exact_walk(a.tab + (int64_t)b * a.T_max * kBatchTab, a.mass + (int64_t)b * a.T_max * 8, 0, T, a.k, sp, s, p, 0.0, log_z, dead);
+        if (lane == 0) { a.log_z[b] = log_z; a.dead[b] = dead; }
+    }
+}
+
+// The resumed walk of an online batch (cpprob_hip_batch_advance_exact): batch_exact_kernel's arguments and the advance's first steps.
+struct BatchExactAdvanceArgs {
+    BatchExactArgs run;                        // prob: the lengths reached (never nullptr); log_z, dead: the carry, read and rewritten
+    const int32_t* first;                      // [B]: the length before the advance; < 0 or >= T_b: the problem is idle
+};
+
+// Problem b's carry at step t0 > 0: m_{t0-1}[s] from the m table onto the lanes (s', s), log_z and dead from the evidence buffers.
+__device__ __forceinline__ double exact_resume(const double* mass, const double* lz, const int32_t* dd, int b, int t0, int s, double& log_z, int& dead)
+{
+    log_z = lz[b];
+    dead = exact_uniform(dd[b]);
+    return mass[(int64_t)(t0 - 1) * 8 + s];
+}
+
+__global__ __launch_bounds__(kThreads) void batch_exact_advance_kernel(BatchExactAdvanceArgs aa)
+{
+#pragma clang fp contract(off)
+    const BatchExactArgs& a = aa.run;
+    const int lane = lane_id(), sp = lane >> 3, s = lane & 7;
+    for (int b = exact_uniform((int)blockIdx.x * kWaves + wave_id()); b < a.B; b += (int)gridDim.x * kWaves) {   // (wavefront-uniform)
+        const int T = (int)a.prob[b].T, t0 = exact_uniform(aa.first[b]);
+        if (t0 < 0 || t0 >= T) continue;                        // idle: nothing of it is read or written
+        double* mass = a.mass + (int64_t)b * a.T_max * 8;
+        double log_z = 0.0, ms = 0.0;
+        int dead = -1;
+        if (t0 > 0) ms = exact_resume(mass, a.log_z, a.dead, b, t0, s, log_z, dead);
+        if (dead >= 0) {                                        // dead before this advance: zeros, the carry stays
+            for (int tt = t0; tt < T; ++tt) if (sp == 0) mass[(int64_t)tt * 8 + s] = 0.0;
+            continue;
         }
+        const double p = smooth_trans_mass(a.thr + (int64_t)b * a.thr_stride, a.k, s, sp);
+        exact_walk(a.tab + (int64_t)b * a.T_max * kBatchTab, mass, t0, T, a.k, sp, s, p, ms, log_z, dead);
         if (lane == 0) { a.log_z[b] = log_z; a.dead[b] = dead; }
     }
 }

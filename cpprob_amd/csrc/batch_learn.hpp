@@ -139,9 +139,13 @@ struct BatchLearnScaledArgs {
     int fit;                                   // the learner fits the scales
 };
 
-// Args: BatchLearnArgs, or kScaled: BatchLearnScaledArgs
-template <bool kScaled, class Args>
-__device__ __forceinline__ void batch_learn_body(Args sa)
+struct BatchLearnNoBefore { __device__ void operator()(int) const {} };
+
+// Args: BatchLearnArgs, or kScaled: BatchLearnScaledArgs.  before(b): what problem b's wavefront does ahead of the statement -- nothing
+// under the learn kernels; the new rows and the exact walk under the fused exact advance (csrc/batch_exact_learn.hpp), which is this
+// body and no second copy of it.
+template <bool kScaled, class Args, class Before = BatchLearnNoBefore>
+__device__ __forceinline__ void batch_learn_body(Args sa, Before before = Before())
 {
 #pragma clang fp contract(off)
     BatchLearnArgs a;
@@ -149,6 +153,7 @@ __device__ __forceinline__ void batch_learn_body(Args sa)
     const int lane = lane_id(), sp = lane >> 3, c = lane & 7;
     const bool live = sp < a.k, diag = live && c == sp;
     for (int b = online_uniform((int)blockIdx.x * kWaves + wave_id()); b < a.B; b += (int)gridDim.x * kWaves) {   // (wavefront-uniform)
+        before(b);
         const BatchSmoothProblem d = a.desc[b];
         double* out = a.stats + (int64_t)b * kOnlineStats;
         const int T = d.T;

@@ -38,6 +38,7 @@
 #include "batch_pool.hpp"
 #include "batch_gibbs.hpp"
 #include "batch_exact.hpp"
+#include "batch_exact_learn.hpp"
 
 using namespace cph;
 
@@ -1130,8 +1131,12 @@ struct BatchState {
     // exact filter runs (cpprob_hip_batch_run_exact; csrc/batch_exact.hpp): exact: read while `conditional` is set -- the run that left masses
     // and no books was the exact recursion, and its evidences ([B] doubles) and first dead steps ([B] int32) stand in two allocations of
     // the context's own
+    // exact streams (cpprob_hip_batch_advance_exact, _advance_learn_exact*): stream_kind: what the begun online batch's first advance made
+    // of it -- a begin forgets it --; an exact stream sets `conditional` and `exact` (masses and evidences, no books), and the evidences'
+    // buffers are its carry: log_z and dead at the lengths reached, 0.0 and -1 from its first advance on for a problem without observes
     bool exact = false;
     DeviceBuffer d_exact_lz, d_exact_dead;
+    enum StreamKind { kStreamNone, kStreamParticle, kStreamExact } stream_kind = kStreamNone;
     // re-tabling (cpprob_hip_batch_retable*; csrc/batch_retable.hpp): the status words [B] and the observes the host form staged, allocations
     // of the context's own; retabled: the begun batch has been re-tabled (its status words are those of the last one); robs_ready: d_robs
     // holds this begun batch's observes; tab_stale / thr_stale: the device holds rows / thresholds the host mirrors (h_tab, h_thr) do not
@@ -1278,7 +1283,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->batch) c->batch = new BatchState();
     BatchState* bs = c->batch;
-    bs->begun = false; bs->ran = false; bs->conditional = false; bs->cfirst_ready = false;
+    bs->begun = false; bs->ran = false; bs->conditional = false; bs->cfirst_ready = false; bs->stream_kind = BatchState::kStreamNone;
     const uint64_t B = cfg->n_problems;
     bs->counted.assign(B, 0);
     bs->decoded.assign(B, 0); bs->lp_ready = false; bs->lp_sent = false;
@@ -4394,12 +4399,13 @@ int cpprob_hip_batch_run_conditional(cpprob_hip_ctx* c, const uint64_t* h_seeds,
 
 // ---- exact filter runs of a batch (csrc/batch_exact.hpp) ---------------------------------------------------------------------------
 // The state an exact run needs; nothing is enqueued before it has passed.
-static int batch_exact_check(cpprob_hip_ctx* c)
+// (online: the check of an exact advance, which serves the online batch an exact run refuses)
+static int batch_exact_check(cpprob_hip_ctx* c, bool online = false)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     BatchState* bs = c->batch;
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "cpprob_hip_batch_begin has not been called");
-    if (bs->online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "exact runs serve batches begun by cpprob_hip_batch_begin or _begin_problems: an online batch is advanced (cpprob_hip_batch_advance)");
+    if (bs->online && !online) return fail(c, CPPROB_HIP_EUNSUPPORTED, "exact runs serve batches begun by cpprob_hip_batch_begin or _begin_problems: an online batch is advanced (cpprob_hip_batch_advance)");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "exact runs serve CPPROB_HIP_MODEL_HMM_TABLE");
     if (bs->cfg.keep_history != 0 || !batch_masses(&bs->cfg))
         return fail(c, CPPROB_HIP_ESTATE, "an exact run keeps masses, not a particle store: begin the batch with keep_history = 0 and CPPROB_HIP_BATCH_KEEP_MASSES");
@@ -4412,7 +4418,7 @@ static int batch_exact_evidence_check(cpprob_hip_ctx* c, const void* log_z, cons
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     if (!log_z || !dead) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
-    if (!bs || !bs->ran || !bs->conditional || !bs->exact) return fail(c, CPPROB_HIP_ESTATE, "the evidences are those of an exact run: cpprob_hip_batch_run_exact has not been the batch's last run");
+    if (!bs || !bs->ran || !bs->conditional || !bs->exact) return fail(c, CPPROB_HIP_ESTATE, "the evidences are those of an exact run: cpprob_hip_batch_run_exact has not been the batch's last run, and the batch is no exact stream (cpprob_hip_batch_advance_exact)");
     if ((uint64_t)n < bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "the arrays hold " + std::to_string(n) + " entries: the batch has " + std::to_string(bs->cfg.n_problems) + " problems");
     return 0;
 }
@@ -4500,20 +4506,50 @@ int cpprob_hip_batch_begin_online_scaled(cpprob_hip_ctx* c, const cpprob_hip_bat
     return batch_begin_described(c, cfg, h_Tcap, h_n, nullptr, k_in, h_means, h_transition, h_sigmas, h_seeds, kFamilyScaled);
 }
 
-static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs);
+static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs, bool fused);
 
-// One advance of the begun online batch.  Plain (cpprob_hip_batch_advance): the new rows are evaluated on the host from bs->means and
-// copied.  Learning (cpprob_hip_batch_advance_learn*, learn: the batch is armed): the rows are written on the device from the
-// device-resident tables and the observes (d_obs, or h_obs copied into a buffer of the context's own), and the learn step follows the
-// launch (csrc/batch_learn.hpp).  Nothing changes before every check has passed.
-static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs, const double* d_obs, size_t n_observes, int32_t readout, bool learn)
+// The resumed exact walk over the new steps (csrc/batch_exact.hpp), where batch_launch stands in a particle advance.
+static int batch_exact_advance_launch(cpprob_hip_ctx* c, BatchState* bs)
 {
+    const size_t B = bs->cfg.n_problems;
+    BatchExactAdvanceArgs aa{};
+    BatchExactArgs& a = aa.run;
+    a.tab = reinterpret_cast<const double*>(bs->ws() + bs->lay.tab);
+    a.thr = reinterpret_cast<const uint64_t*>(bs->ws() + bs->lay.thr);
+    a.thr_stride = 64;                                          // (an online batch is described: a table a problem)
+    a.prob = reinterpret_cast<const BatchProblem*>(bs->ws() + bs->lay.prob);
+    a.mass = reinterpret_cast<double*>(bs->ws() + bs->lay.mass);
+    a.log_z = bs->d_exact_lz.as<double>();
+    a.dead = bs->d_exact_dead.as<int32_t>();
+    a.B = (int)B; a.T_max = bs->T; a.k = bs->hk;
+    aa.first = reinterpret_cast<const int32_t*>(bs->ws() + bs->lay.first);
+    const unsigned gx = (unsigned)std::min<size_t>((B + kWaves - 1) / kWaves, (size_t)kExactGridMax);
+    hipLaunchKernelGGL(batch_exact_advance_kernel, dim3(gx), dim3(kThreads), 0, c->stream, aa);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+// One advance of the begun online batch.  Plain (cpprob_hip_batch_advance, _advance_exact): the new rows are evaluated on the host from
+// bs->means and copied; the launch over the new steps is batch_launch or, exact, batch_exact_advance_kernel.  Learning
+// (cpprob_hip_batch_advance_learn*: the batch is armed): the rows are written on the device from the device-resident tables and the
+// observes (d_obs, or h_obs copied into a buffer of the context's own), and the learn step follows the launch (csrc/batch_learn.hpp);
+// exact (cpprob_hip_batch_advance_learn_exact*): one fused kernel stands for all three (csrc/batch_exact_learn.hpp).  The mode of the
+// four advances is the pair (learn, exact).  The first advance after the begin fixes the stream's kind, particle or exact.  Nothing
+// changes before every check has passed.
+static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs, const double* d_obs, size_t n_observes, int32_t readout, bool learn, bool exact = false)
+{
+    const bool fused = learn && exact;
+    const std::string who = std::string("cpprob_hip_batch_advance") + (learn ? "_learn" : "") + (exact ? "_exact" : "");
     if (!c || !h_dT) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
-    if (!bs || !bs->begun || !bs->online)
-        return fail(c, CPPROB_HIP_ESTATE, std::string(learn ? "cpprob_hip_batch_advance_learn" : "cpprob_hip_batch_advance") + " serves a batch begun by cpprob_hip_batch_begin_online");
+    if (!bs || !bs->begun || !bs->online) return fail(c, CPPROB_HIP_ESTATE, who + " serves a batch begun by cpprob_hip_batch_begin_online");
+    if (exact) if (int rc = batch_exact_check(c, true)) return rc;
     if (learn && !bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the online batch is not armed: call cpprob_hip_batch_learn_begin before its first advance");
-    if (!learn && bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the online batch learns its tables (cpprob_hip_batch_learn_begin): it is advanced by cpprob_hip_batch_advance_learn");
+    if (!learn && bs->armed) return fail(c, CPPROB_HIP_ESTATE, "the online batch learns its tables (cpprob_hip_batch_learn_begin): it is advanced by cpprob_hip_batch_advance_learn" + std::string(exact ? "_exact" : ""));
+    if (exact && bs->stream_kind == BatchState::kStreamParticle)
+        return fail(c, CPPROB_HIP_ESTATE, "the stream has taken a particle advance: it goes on by cpprob_hip_batch_advance" + std::string(learn ? "_learn" : "") + ", or is begun again");
+    if (!exact && bs->stream_kind == BatchState::kStreamExact)
+        return fail(c, CPPROB_HIP_ESTATE, "the stream has taken an exact advance: it goes on by cpprob_hip_batch_advance" + std::string(learn ? "_learn" : "") + "_exact, or is begun again");
     const uint64_t B = bs->cfg.n_problems;
     uint64_t total = 0;
     for (uint64_t b = 0; b < B; ++b) {
@@ -4526,6 +4562,15 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
     if (learn && !h_obs && (uint64_t)n_observes != total)
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the advance hands over " + std::to_string(total) + " observes (the sum of h_dT)");
     HIP_TRY(c, hipSetDevice(c->device));
+    if (exact && bs->stream_kind == BatchState::kStreamNone) {
+        // an exact stream's first advance: the carry of a problem without observes (the kernels leave an idle problem's entries alone)
+        HIP_TRY(c, bs->d_exact_lz.grow(c->stream, B * sizeof(double)));
+        HIP_TRY(c, bs->d_exact_dead.grow(c->stream, B * sizeof(int32_t)));
+        HIP_TRY(c, hipMemsetAsync(bs->d_exact_lz.as<double>(), 0, B * sizeof(double), c->stream));
+        HIP_TRY(c, hipMemsetAsync(bs->d_exact_dead.as<int32_t>(), 0xff, B * sizeof(int32_t), c->stream));
+    }
+    bs->stream_kind = exact ? BatchState::kStreamExact : BatchState::kStreamParticle;
+    if (exact) { bs->conditional = true; bs->exact = true; }   // (masses and evidences, no books: as an exact run leaves a batch)
     std::vector<uint32_t> before;                              // (learning: the lengths the learn step resumes from)
     if (learn) {
         before.resize(B);
@@ -4539,7 +4584,7 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
     BatchProblem* pr = reinterpret_cast<BatchProblem*>(sl);
     int32_t* first = reinterpret_cast<int32_t*>(sl + B * sizeof(BatchProblem));
     int32_t* order = first + B;
-    int64_t* ofirst = learn ? bs->learn.pin_first.as<int64_t>() + (size_t)slot * B : nullptr;
+    int64_t* ofirst = learn && !fused ? bs->learn.pin_first.as<int64_t>() + (size_t)slot * B : nullptr;       // (the fused kernel takes the first new observes from the learn step's descriptors)
     const bool hmm3 = bs->cfg.model == CPPROB_HIP_MODEL_HMM3, keep = bs->cfg.keep_history == 1;
     const size_t hk = (size_t)bs->hk, T_max = (size_t)bs->T, row_bytes = kBatchTab * sizeof(double);
     const bool own = !hmm3 && bs->means.size() > hk;
@@ -4548,7 +4593,8 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
     size_t at_obs = 0;
     for (uint64_t b = 0; b < B; ++b) {
         const size_t L = (size_t)bs->prob[b].T;
-        if (learn) { ofirst[b] = (int64_t)at_obs; at_obs += h_dT[b]; }
+        if (ofirst) ofirst[b] = (int64_t)at_obs;
+        if (learn) at_obs += h_dT[b];
         if (own && h_dT[b] && !learn) mean.assign(bs->means.begin() + (ptrdiff_t)(b * hk), bs->means.begin() + (ptrdiff_t)((b + 1) * hk));
         for (size_t t = L; !learn && t < L + h_dT[b]; ++t) {
             const double y = h_obs[at_obs++];
@@ -4583,11 +4629,14 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
     HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.prob, pr, B * sizeof(BatchProblem), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.first, first, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(bs->ws() + bs->lay.order, order, B * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    if (learn) HIP_TRY(c, hipMemcpyAsync(bs->learn.first.as<int64_t>(), ofirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    if (ofirst) HIP_TRY(c, hipMemcpyAsync(bs->learn.first.as<int64_t>(), ofirst, B * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, bs->advance_ring.commit(c->stream));
     if (learn && total) {
-        // the new rows, on the device: from the observes and the tables in force
         if (h_obs) { HIP_TRY(c, hipMemcpyAsync(bs->learn.obs.as<double>(), h_obs, (size_t)total * sizeof(double), hipMemcpyHostToDevice, c->stream)); d_obs = bs->learn.obs.as<double>(); }
+        bs->tab_stale = true;
+    }
+    if (learn && total && !fused) {
+        // the new rows, on the device: from the observes and the tables in force
         uint32_t top = 0;
         for (uint64_t b = 0; b < B; ++b) top = std::max(top, h_dT[b]);
         const dim3 grid((unsigned)B, retable_grid_y(top, (int64_t)B));
@@ -4610,13 +4659,12 @@ static int batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* 
             hipLaunchKernelGGL(batch_learn_rows_kernel, grid, dim3(kThreads), 0, c->stream, ra);
         }
         HIP_TRY(c, hipGetLastError());
-        bs->tab_stale = true;
     }
     bool work = false, walked = true;
     for (uint64_t b = 0; b < B; ++b) { work = work || first[b] >= 0; walked = walked && bs->walked_b[b]; }
-    if (work) if (int rc = batch_launch(c, bs, readout != 0)) return rc;
+    if (work && !fused) if (int rc = exact ? batch_exact_advance_launch(c, bs) : batch_launch(c, bs, readout != 0)) return rc;
     bs->walked = walked;
-    if (learn) return batch_learn_enqueue(c, before.data(), total ? d_obs : nullptr);
+    if (learn) return batch_learn_enqueue(c, before.data(), total ? d_obs : nullptr, fused);
     return 0;
 }
 
@@ -4624,6 +4672,24 @@ int cpprob_hip_batch_advance(cpprob_hip_ctx* c, const uint32_t* h_dT, const doub
 {
     LANES_OWN(c);
     return batch_advance(c, h_dT, h_obs, nullptr, 0, readout, false);
+}
+
+int cpprob_hip_batch_advance_exact(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs)
+{
+    LANES_OWN(c);
+    return batch_advance(c, h_dT, h_obs, nullptr, 0, 1, false, true);
+}
+
+int cpprob_hip_batch_advance_learn_exact(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs)
+{
+    LANES_OWN(c);
+    return batch_advance(c, h_dT, h_obs, nullptr, 0, 1, true, true);
+}
+
+int cpprob_hip_batch_advance_learn_exact_device(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* d_obs, size_t n_observes)
+{
+    LANES_OWN(c);
+    return batch_advance(c, h_dT, nullptr, d_obs, n_observes, 1, true, true);
 }
 
 int cpprob_hip_batch_advance_learn(cpprob_hip_ctx* c, const uint32_t* h_dT, const double* h_obs)
@@ -6109,7 +6175,9 @@ int cpprob_hip_batch_learn_pooled_record(cpprob_hip_ctx* c, double* h_out, size_
 // The learn step of a learning advance, behind its launch: the prologue of a running-statistics pass that resumes from the lengths
 // before the advance (a batch with a particle store: the counting pass over the new rows first), then batch_learn_kernel.  The
 // thresholds and, through them, the decode's log tables and step words are the device's from here on.
-static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs)
+// fused (cpprob_hip_batch_advance_learn_exact*): no rows kernel and no run stand before it -- batch_exact_learn_kernel writes the rows,
+// walks the new steps and learns (csrc/batch_exact_learn.hpp), on the exact walk's grid.
+static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const double* d_obs, bool fused)
 {
     BatchState* bs = c->batch; const size_t B = bs->cfg.n_problems;
     BatchPassPlan pl; BatchSmoothArgs a{};
@@ -6121,7 +6189,19 @@ static int batch_learn_enqueue(cpprob_hip_ctx* c, const uint32_t* before, const 
     la.B = (int)B; la.k = bs->hk; la.t_min = bs->learn_tied ? INT32_MAX : (int)std::min<uint32_t>(bs->learn_t_min, (uint32_t)INT32_MAX);
     BatchLearnScaledArgs ls{};
     ls.base = la; ls.sigmas = bs->d_sigma.as<double>(); ls.log_norms = bs->d_lognorm.as<double>(); ls.floor = bs->learn_floor; ls.fit = bs->learn_scales ? 1 : 0;
-    if (bs->scaled)
+    if (fused) {
+        BatchExactLearnArgs x{};
+        x.first = reinterpret_cast<const int32_t*>(bs->ws() + bs->lay.first);
+        x.tab = reinterpret_cast<double*>(bs->ws() + bs->lay.tab); x.mass = reinterpret_cast<double*>(bs->ws() + bs->lay.mass);
+        x.log_z = bs->d_exact_lz.as<double>(); x.dead = bs->d_exact_dead.as<int32_t>();
+        x.log_norm = std::log(2 * kPi * 1.0 * 1.0);             // (normal_logpdf's own expression at sigma = 1.0, as the rows kernel takes it)
+        x.T_max = bs->T;
+        const dim3 grid(std::min<unsigned>(pl.stats_gx, (unsigned)kExactGridMax));
+        if (bs->scaled)
+            hipLaunchKernelGGL(batch_exact_learn_scaled_kernel, grid, dim3(kThreads), 0, c->stream, ls, x);
+        else
+            hipLaunchKernelGGL(batch_exact_learn_kernel, grid, dim3(kThreads), 0, c->stream, la, x);
+    } else if (bs->scaled)
         hipLaunchKernelGGL(batch_learn_scaled_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, ls);
     else
         hipLaunchKernelGGL(batch_learn_kernel, dim3(pl.stats_gx), dim3(kThreads), 0, c->stream, la);

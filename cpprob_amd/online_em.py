@@ -18,7 +18,7 @@ def step_sizes(n, step_exponent=0.6):
 
 
 def hmm_table_online_em(engine, observes, tables0, n_particles, seeds, chunk, step_exponent=0.6, t_min=20, keep_history=False, resampler=RESAMPLE_SYSTEMATIC,
-                        sigma_floor=1e-3, groups=None):
+                        sigma_floor=1e-3, exact=False, groups=None):
     """observes: a list of B 1-D sequences (the streams; their lengths are the capacities), or one sequence every problem shares;
     tables0 = (means [B, k], transition [B, k, k]), the tables the streams start under; seeds [B].  The streams are fed `chunk`
     observes at a time; t_min: the length a stream must have reached before its first M-step (the chunk is the update period
@@ -30,7 +30,10 @@ def hmm_table_online_em(engine, observes, tables0, n_particles, seeds, chunk, st
     sigma_floor; a fifth element, sigmas [A + 1, B, k], is returned behind the four.
     groups (int [B], ids 0 .. G-1, every one used): tied online EM -- the streams of a group learn one table from their pooled records,
     every stream weighing equally whatever its length; t_min then counts the observes the group has seen, and tables0 must be equal
-    within a group (ValueError).  The shapes returned are unchanged: the members of a group hold equal rows."""
+    within a group (ValueError).  The shapes returned are unchanged: the members of a group hold equal rows.
+    exact=True: the streams are exact streams (Engine.batch_advance_learn_exact) -- a filtering-only batch with masses whatever
+    keep_history says, every advance one fused launch, no Monte-Carlo error; n_particles and seeds are accepted and not used, and the
+    summaries are the array of the streams' exact prequential log-likelihoods (float64 [B])."""
     if len(tables0) not in (2, 3):
         raise ValueError("tables0 = (means, transition) or (means, transition, sigmas)")
     means = np.array(tables0[0], np.float64)
@@ -58,7 +61,7 @@ def hmm_table_online_em(engine, observes, tables0, n_particles, seeds, chunk, st
     caps = np.array([max(1, len(o)) for o in seqs], np.uint32)
     tables = (means, trans) if sigmas is None else (means, trans, sigmas)
     engine.batch_begin_online(MODEL_HMM_TABLE, caps, n_particles, np.ascontiguousarray(seeds, np.uint64), tables=tables, resampler=resampler,
-                              keep_history=bool(keep_history), keep_masses=not keep_history)
+                              keep_history=bool(keep_history) and not exact, keep_masses=exact or not keep_history)
     if groups is not None:
         engine.batch_tie(groups)
     engine.batch_learn_begin(step_sizes(int(caps.max()), step_exponent), t_min, sigma_floor=None if sigmas is None else sigma_floor, tied=groups is not None)
@@ -66,7 +69,7 @@ def hmm_table_online_em(engine, observes, tables0, n_particles, seeds, chunk, st
     s_hist = None if sigmas is None else [sigmas.copy()]
     top = max(len(o) for o in seqs)
     for at in range(0, top, chunk):
-        engine.batch_advance_learn([o[at:at + chunk] for o in seqs])
+        (engine.batch_advance_learn_exact if exact else engine.batch_advance_learn)([o[at:at + chunk] for o in seqs])
         if sigmas is None:
             m, t, st = engine.batch_learn_tables(means.shape[1])
         else:
@@ -75,5 +78,6 @@ def hmm_table_online_em(engine, observes, tables0, n_particles, seeds, chunk, st
         m_hist.append(m)
         t_hist.append(t)
         st_hist.append(st)
-    out = (np.array(m_hist), np.array(t_hist), np.array(st_hist, np.int32).reshape(len(st_hist), B), engine.batch_results(with_stats=False)[0])
+    summaries = engine.batch_exact_evidence()[0] if exact else engine.batch_results(with_stats=False)[0]
+    out = (np.array(m_hist), np.array(t_hist), np.array(st_hist, np.int32).reshape(len(st_hist), B), summaries)
     return out if sigmas is None else out + (np.array(s_hist),)

@@ -797,6 +797,28 @@ int cpprob_hip_batch_advance_learn(cpprob_hip_ctx* ctx, const uint32_t* h_dT, co
 /* The same with the observes in device memory (n_observes = the sum of h_dT, else CPPROB_HIP_EINVAL); stream contract as
  * cpprob_hip_batch_online_stats_device. */
 int cpprob_hip_batch_advance_learn_device(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const double* d_observes, size_t n_observes);
+/* Exact streams (csrc/batch_exact.hpp, csrc/batch_exact_learn.hpp): the exact forward recursion of cpprob_hip_batch_run_exact, resumed.
+ * cpprob_hip_batch_advance_exact is cpprob_hip_batch_advance -- its checks, its host-evaluated rows of any emission family, its copies --
+ * with one launch of the exact walk over the steps [L_b, L_b + dT_b) in the particle launch's place; it takes no read-out flag and the
+ * stream's seeds are not used.  The carry is row L_b - 1 of the m table and the problem's evidence (log_z, dead), so after any
+ * sequence of advances the m table, the evidences and the rows are those of cpprob_hip_batch_run_exact on a batch of the lengths
+ * reached, bit for bit.  A problem dead before an advance stores zeros in its new rows.
+ * It serves an online CPPROB_HIP_MODEL_HMM_TABLE batch begun with keep_history = 0 and CPPROB_HIP_BATCH_KEEP_MASSES; anything else is
+ * refused with cpprob_hip_batch_run_exact's codes.  The first advance after the begin fixes the stream's kind: an exact advance of a
+ * stream that has taken a particle advance returns CPPROB_HIP_ESTATE, and so does the reverse; nothing is enqueued and the batch stays
+ * as it was.  A begin forgets the kind.  cpprob_hip_batch_exact_evidence / _device return log_z and dead at the lengths reached (a
+ * problem of length 0: 0.0 and -1); cpprob_hip_batch_results, _results_device and _summaries_device refuse an exact stream as they
+ * refuse an exact run.  Every call that serves an online CPPROB_HIP_BATCH_KEEP_MASSES batch from its m table serves the stream
+ * unchanged; backward draws are keyed by the seeds of cpprob_hip_batch_begin_online. */
+int cpprob_hip_batch_advance_exact(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const double* h_observes);
+/* A learning advance of an armed exact stream (unit or scaled; tied or not), the statement of cpprob_hip_batch_advance_learn with the
+ * exact walk as its run, in ONE launch: a problem's wavefront writes its new rows from the device tables in force, walks the new
+ * steps and runs the learn step.  The tied tail (cpprob_hip_batch_learn_tie) follows it unchanged.  After every advance the batch is
+ * what cpprob_hip_batch_advance_exact, the learn step on the m table and cpprob_hip_batch_online_tables leave, bit for bit.
+ * CPPROB_HIP_ESTATE: the batch is not armed (a Poisson batch cannot be: cpprob_hip_batch_learn_begin refuses it), or the stream has
+ * taken a particle advance.  On an armed batch cpprob_hip_batch_advance_exact returns CPPROB_HIP_ESTATE. */
+int cpprob_hip_batch_advance_learn_exact(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const double* h_observes);
+int cpprob_hip_batch_advance_learn_exact_device(cpprob_hip_ctx* ctx, const uint32_t* h_dT, const double* d_observes, size_t n_observes);
 /* The host route: new tables for the FUTURE steps of an online CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables, armed or
  * not.  The tables are validated as the begin validates them (the same codes and messages naming the problem); they replace the host
  * means the next cpprob_hip_batch_advance evaluates its rows from, the threshold words are uploaded stream-ordered, and on an armed
