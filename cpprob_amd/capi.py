@@ -60,6 +60,9 @@ SYMBOLS = [
     "cpprob_hip_batch_begin_problems_poisson", "cpprob_hip_batch_begin_online_poisson", "cpprob_hip_batch_retable_poisson",
     "cpprob_hip_batch_retable_poisson_device", "cpprob_hip_batch_mstep_poisson_device", "cpprob_hip_batch_online_tables_poisson",
     "cpprob_hip_batch_copy_rates",
+    "cpprob_hip_batch_begin_problems_categorical", "cpprob_hip_batch_retable_categorical", "cpprob_hip_batch_retable_categorical_device",
+    "cpprob_hip_batch_symbol_stats", "cpprob_hip_batch_symbol_stats_device", "cpprob_hip_batch_mstep_categorical_device",
+    "cpprob_hip_batch_copy_emission",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
@@ -219,6 +222,8 @@ def batch_smooth_layout(T, n_traj):
 FORECAST_MAX_HORIZON, FORECAST_MAX_TRAJ, FORECAST_MAX_DRAWS = 1 << 24, 1 << 20, 1 << 16      # cpprob_hip_batch_forecast: horizon <, n_traj <=, draw_index <
 DECODE_MAX_LAG = 1 << 24                      # cpprob_hip_batch_decode_lag: lag <=
 STATS_PER_PROBLEM = 88                        # doubles a problem of cpprob_hip_batch_smooth_stats: xi[8][8], occ[8], occ_y[8], occ_yy[8]
+CATEGORICAL_MAX_SYMBOLS = 64                  # cpprob_hip_batch_begin_problems_categorical: V in 1 ..=
+SYMBOL_STATS_PER_PROBLEM = 88 + 8 * 64        # doubles a problem of cpprob_hip_batch_symbol_stats: the 88 above, then cnt[8][64]
 
 
 TRAJ_STATS_TILE = 256                         # trajectories a workgroup of cpprob_hip_batch_traj_stats: its grid holds ceil(n_traj / this) tiles a problem
@@ -435,6 +440,13 @@ def load_library(path=None):
         "cpprob_hip_batch_mstep_poisson_device": (C.c_int, [vp, vp, sz, vp, vp, vp, dbl]),
         "cpprob_hip_batch_online_tables_poisson": (C.c_int, [vp, vp, vp]),
         "cpprob_hip_batch_copy_rates": (C.c_int, [vp, u64, vp, vp]),
+        "cpprob_hip_batch_begin_problems_categorical": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, C.c_int32, vp, vp]),
+        "cpprob_hip_batch_retable_categorical": (C.c_int, [vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_categorical_device": (C.c_int, [vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_symbol_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_symbol_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_mstep_categorical_device": (C.c_int, [vp, vp, sz, vp, vp, dbl]),
+        "cpprob_hip_batch_copy_emission": (C.c_int, [vp, u64, vp, vp]),
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
@@ -965,6 +977,73 @@ class Engine:
         rt, lr = np.zeros(k), np.zeros(k)
         self._chk(self.L.cpprob_hip_batch_copy_rates(self.h, int(b), rt.ctypes.data, lr.ctypes.data))
         return rt, lr
+
+    # ---- categorical emissions (include/cpprob_hip.h: cpprob_hip_batch_*_categorical, _symbol_stats*; csrc/batch_categorical.hpp) ----
+    def _batch_categorical_tables(self, emission, trans, B):
+        em = np.ascontiguousarray(emission, np.float64)
+        tr = np.ascontiguousarray(trans, np.float64)
+        if em.ndim != 3 or em.shape[0] != B or tr.shape != (B, em.shape[1], em.shape[1]):
+            raise ValueError("emission [B, k, V] and transition [B, k, k]")
+        return em, tr
+
+    def batch_begin_problems_categorical(self, observes, n_particles, emission, trans, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, keep_masses=False, max_particles=None):
+        """A MODEL_HMM_TABLE batch of discrete HMMs (cpprob_hip_batch_begin_problems_categorical): observes a list of 1-D arrays of
+        symbol indices 0 .. V-1 held in doubles, emission [B, k, V] (state s of problem b emits symbol v with probability
+        emission[b, s, v]; every entry > 0, finite and normal; rows are used as given, not normalised), trans [B, k, k]; k <= 8,
+        V <= 64.  Everything else as batch_begin_problems."""
+        seqs = [np.ascontiguousarray(o, np.float64).reshape(-1) for o in observes]
+        h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
+        flat = np.ascontiguousarray(np.concatenate(seqs) if seqs else np.zeros(0))
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(MODEL_HMM_TABLE, top, len(seqs), resampler, 2.0, keep_history, ALG_SMC, _batch_flags(0, keep_masses))
+        em, tr = self._batch_categorical_tables(emission, trans, len(seqs))
+        self._chk(self.L.cpprob_hip_batch_begin_problems_categorical(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                                     flat.ctypes.data_as(C.POINTER(C.c_double)), em.shape[1], em.shape[2], em.ctypes.data, tr.ctypes.data))
+        self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
+        self.batch_K, self.batch_k, self.batch_V = 8, em.shape[1], em.shape[2]
+        self.batch_shapes = (h_T, h_n)
+        return self
+
+    def batch_retable_categorical(self, emission, trans, observes=None):
+        """A new matrix and new transition rows for the begun categorical batch where it stands (cpprob_hip_batch_retable_categorical),
+        validated as the begin validates them; observes as batch_retable takes them."""
+        em, tr = self._batch_categorical_tables(emission, trans, self.batch_B)
+        flat = None if observes is None else self._batch_packed_observes(observes)
+        h_obs, n_obs = None if flat is None or flat.size == 0 else flat.ctypes.data, int(np.sum(self.batch_shapes[0], dtype=np.int64)) if flat is None else flat.size
+        self._chk(self.L.cpprob_hip_batch_retable_categorical(self.h, em.ctypes.data, tr.ctypes.data, h_obs, n_obs))
+
+    def batch_retable_categorical_device(self, emission, trans, observes):
+        """The same between torch float64 device tensors (emission [B, k, V], trans [B, k, k], observes packed), enqueued without a
+        host synchronisation; the tables are checked on the device (batch_retable_status: bit 32, an entry of the matrix not > 0, not
+        finite or not a normal number)."""
+        self._chk(self.L.cpprob_hip_batch_retable_categorical_device(self.h, _dptr(emission), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+
+    def batch_symbol_stats(self, observes):
+        """The E-step of a categorical batch (cpprob_hip_batch_symbol_stats): batch_smooth_stats' dict -- the same bits -- and cnt
+        [B, 8, 64], cnt[b, s, v] the expected visits of state s at the steps whose observe is symbol v."""
+        rec = np.zeros((self.batch_B, SYMBOL_STATS_PER_PROBLEM))
+        flat = self._batch_packed_observes(observes)
+        self._chk(self.L.cpprob_hip_batch_symbol_stats(self.h, flat.ctypes.data if flat.size else None, flat.size, rec.ctypes.data, rec.size))
+        out = split_stats(np.ascontiguousarray(rec[:, :STATS_PER_PROBLEM]))
+        out["cnt"] = rec[:, STATS_PER_PROBLEM:].reshape(-1, 8, CATEGORICAL_MAX_SYMBOLS)
+        return out
+
+    def batch_symbol_stats_device(self, stats, observes):
+        """The same left in a device tensor: stats torch float64 [B, 600], observes a torch float64 tensor packed problem after problem."""
+        self._chk(self.L.cpprob_hip_batch_symbol_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    def batch_mstep_categorical_device(self, stats, emission, trans, prob_floor=1e-6):
+        """categorical.m_step_categorical on the device (cpprob_hip_batch_mstep_categorical_device): stats torch float64 [B, 600];
+        emission [B, k, V] and trans [B, k, k] torch float64, updated in place; no fitted entry below prob_floor.  Enqueued."""
+        self._chk(self.L.cpprob_hip_batch_mstep_categorical_device(self.h, _dptr(stats), stats.numel(), _dptr(emission), _dptr(trans), float(prob_floor)))
+
+    def batch_copy_emission(self, b, k=None, V=None):
+        """(E [k, V], logE [k, V]) of problem b of a categorical batch, as the device holds them (cpprob_hip_batch_copy_emission).
+        Synchronises.  For tests."""
+        k, V = int(k if k is not None else self.batch_k), int(V if V is not None else self.batch_V)
+        e, le = np.zeros((8, CATEGORICAL_MAX_SYMBOLS)), np.zeros((8, CATEGORICAL_MAX_SYMBOLS))
+        self._chk(self.L.cpprob_hip_batch_copy_emission(self.h, int(b), e.ctypes.data, le.ctypes.data))
+        return e[:k, :V].copy(), le[:k, :V].copy()
 
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):

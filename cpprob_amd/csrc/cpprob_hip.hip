@@ -31,6 +31,7 @@
 #include "batch_retable.hpp"
 #include "batch_scale.hpp"
 #include "batch_poisson.hpp"
+#include "batch_categorical.hpp"
 #include "batch_learn.hpp"
 #include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
@@ -1011,6 +1012,13 @@ void poisson_step_ll(double y, const double* rate, const double* log_rate, const
 }
 // The emission family of a table batch and of a call that hands tables over: N(mean, 1), N(mean, sigma) or Poisson(rate).
 enum EmissionFamily { kFamilyUnit = 0, kFamilyScaled = 1, kFamilyPoisson = 2 };
+// ... or a symbol of a finite alphabet (csrc/batch_categorical.hpp): the fourth family, begun, re-tabled and fitted by its own calls
+constexpr EmissionFamily kFamilyCategorical = (EmissionFamily)3;
+// a categorical table's row, with the statements the device's re-table writes it with: log_e [8][64], slots outside the table -inf
+void categorical_step_ll(double y, int V, const double* log_e, double* ll)
+{
+    for (int s2 = 0; s2 < 8; ++s2) ll[s2] = categorical_entry(y, V, log_e + (size_t)s2 * kCategoricalMaxSymbols, 1);
+}
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
 {
     std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
@@ -1174,6 +1182,15 @@ struct BatchState {
     bool poisson = false;
     std::vector<double> lfact;
     DeviceBuffer d_lfact;
+    // categorical emissions (cpprob_hip_batch_begin_problems_categorical; csrc/batch_categorical.hpp): categorical: the begun batch has
+    // them, and is then neither scaled nor Poisson; cat_V its symbols.  The matrix in force and its logarithms, [B][8][64] (slots outside
+    // the table 0.0 and -inf), are the device's alone (allocations of the context's own): a begin uploads them, a re-table rewrites
+    // them.  cat_begin_E / cat_begin_V: the checked arguments of the begin in progress, read by batch_begin and by nothing else
+    bool categorical = false;
+    int cat_V = 0;
+    DeviceBuffer d_cat_e, d_cat_loge;
+    const double* cat_begin_E = nullptr;
+    int cat_begin_V = 0;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
@@ -1283,6 +1300,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->batch) c->batch = new BatchState();
     BatchState* bs = c->batch;
+    const bool categorical = family == kFamilyCategorical;   // (h_means: zeros no row reads; the matrix is bs->cat_begin_E)
     bs->begun = false; bs->ran = false; bs->conditional = false; bs->cfirst_ready = false; bs->stream_kind = BatchState::kStreamNone;
     const uint64_t B = cfg->n_problems;
     bs->counted.assign(B, 0);
@@ -1331,6 +1349,21 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         bs->lfact.swap(lf);
     }
+    bs->categorical = false;
+    std::vector<double> cat_e, cat_loge;                        // (live until the synchronisation below)
+    const int cat_V = categorical ? bs->cat_begin_V : 0;
+    if (categorical) {
+        cat_e.assign((size_t)B * kCategoricalSlots, 0.0); cat_loge.assign((size_t)B * kCategoricalSlots, -INFINITY);
+        for (size_t b = 0; b < (size_t)B; ++b)
+            for (size_t s = 0; s < (size_t)k; ++s)
+                for (size_t v = 0; v < (size_t)cat_V; ++v) {
+                    const double e = bs->cat_begin_E[(b * (size_t)k + s) * (size_t)cat_V + v];
+                    cat_e[b * kCategoricalSlots + s * kCategoricalMaxSymbols + v] = e;
+                    cat_loge[b * kCategoricalSlots + s * kCategoricalMaxSymbols + v] = table_log(e);
+                }
+        HIP_TRY(c, bs->d_cat_e.grow(c->stream, cat_e.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_cat_loge.grow(c->stream, cat_loge.size() * sizeof(double)));
+    }
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
@@ -1347,6 +1380,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
             else if (scaled) scale_step_ll(y, mean.data(), &bs->sigmas[b * 8], &bs->log_norms[b * 8], k, row);
             else if (poisson) poisson_step_ll(y, &bs->sigmas[b * 8], &bs->log_norms[b * 8], bs->lfact.data(), k, row);
+            else if (categorical) categorical_step_ll(y, cat_V, &cat_loge[b * kCategoricalSlots], row);
             else hmmk_step_ll(y, mean, k, row);
         }
         if (!hmm3 && b < tables) {
@@ -1367,6 +1401,10 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     if (scaled || poisson) {
         HIP_TRY(c, hipMemcpyAsync(bs->d_sigma.as<double>(), bs->sigmas.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_lognorm.as<double>(), bs->log_norms.data(), B * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    if (categorical) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_cat_e.as<double>(), cat_e.data(), cat_e.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_cat_loge.as<double>(), cat_loge.data(), cat_loge.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
@@ -1398,6 +1436,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
     bs->online = online; bs->walked = true; bs->own_tables = own; bs->scaled = scaled; bs->poisson = poisson;
+    bs->categorical = categorical; bs->cat_V = cat_V;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -5641,6 +5680,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "re-tabling serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
     const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
+    const bool categorical = family == kFamilyCategorical;
+    if (bs->categorical && !categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: it is re-tabled by cpprob_hip_batch_retable_categorical / _retable_categorical_device");
+    if (!bs->categorical && categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has no categorical emissions: begin it with cpprob_hip_batch_begin_problems_categorical, or re-table it with its own family's calls");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: it is re-tabled by cpprob_hip_batch_retable_poisson / _retable_poisson_device");
     if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: begin it with cpprob_hip_batch_begin_problems_poisson, or re-table it with its own family's calls");
     if (bs->scaled && !scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: it is re-tabled by cpprob_hip_batch_retable_scaled / _retable_scaled_device");
@@ -5670,6 +5712,13 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
         r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
+    if (bs->categorical) {
+        // (a categorical batch: d_means is its emission matrix [B][k][V]; the matrix and its logarithms in force are the device's)
+        BatchRetableCategoricalArgs ca{};
+        common(ca);
+        ca.emission = d_means; ca.V = bs->cat_V; ca.e_out = bs->d_cat_e.as<double>(); ca.log_e_out = bs->d_cat_loge.as<double>();
+        hipLaunchKernelGGL(batch_retable_categorical_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, ca);
+    } else
     if (bs->poisson) {
         // (a Poisson batch: d_means are its rates; the rates and log-rates in force are the device's from here on)
         BatchRetablePoissonArgs pa{};
@@ -5824,6 +5873,7 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
     BatchState* bs = c->batch;
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: its M-step is cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its M-step is cpprob_hip_batch_mstep_poisson_device");
     if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: its M-step is cpprob_hip_batch_mstep_device / _mstep_scaled_device");
     if (!d_stats || !d_means || !d_transition || (scaled && !d_sigmas)) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
@@ -5880,6 +5930,7 @@ int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* c, const double* d_stats
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the draw samples the tables of CPPROB_HIP_MODEL_HMM_TABLE");
     if (!bs->own_tables) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the batch was begun with the context's shared table: begin it with per-problem tables to draw them");
+    if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: the conjugate (Dirichlet) draw of its matrix is not built -- fit it with cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: the conjugate (gamma) draw of its rates is not built -- fit it with cpprob_hip_batch_mstep_poisson_device");
     if (bs->scaled && !d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its draw takes d_sigmas");
     if (!bs->scaled && d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: its draw takes no d_sigmas (begin it with cpprob_hip_batch_begin_problems_scaled)");
@@ -6048,6 +6099,167 @@ int cpprob_hip_batch_copy_rates(cpprob_hip_ctx* c, uint64_t problem, double* h_r
     const size_t k = (size_t)bs->hk;
     if (h_rates) HIP_TRY(c, hipMemcpyAsync(h_rates, bs->d_sigma.as<double>() + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_log_rates) HIP_TRY(c, hipMemcpyAsync(h_log_rates, bs->d_lognorm.as<double>() + problem * 8, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- categorical emissions of a batch (csrc/batch_categorical.hpp) ------------------------------------------------------------------
+// An emission matrix on the host ([B][k][V]): every entry > 0, finite and a normal number (categorical_check's bit 32, by name).
+static int batch_check_emission(cpprob_hip_ctx* c, uint64_t B, int k, int V, const double* h_emission)
+{
+    for (uint64_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < (size_t)k * (size_t)V; ++i)
+            if (categorical_bad(h_emission[b * (size_t)k * (size_t)V + i]))
+                return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": emission probabilities must be > 0, finite and normal numbers");
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems_categorical(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
+                                                int32_t k_in, int32_t V, const double* h_emission, const double* h_transition)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_emission || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "categorical emissions serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    if (V < 1 || V > kCategoricalMaxSymbols) return fail(c, CPPROB_HIP_EINVAL, "V, the symbols of the alphabet, must lie in 1 .. 64");
+    if (k_in < 1 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "k must lie in 1 .. 8");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    if (int rc = batch_check_emission(c, cfg->n_problems, k_in, V, h_emission)) return rc;
+    // (the begin's route takes means: zeros, which no categorical row reads; the matrix travels beside them)
+    const std::vector<double> zeros((size_t)cfg->n_problems * (size_t)k_in, 0.0);
+    if (!c->batch) c->batch = new BatchState();
+    c->batch->cat_begin_E = h_emission; c->batch->cat_begin_V = V;
+    const int rc = batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, zeros.data(), h_transition, nullptr, nullptr, kFamilyCategorical);
+    c->batch->cat_begin_E = nullptr; c->batch->cat_begin_V = 0;
+    return rc;
+}
+
+int cpprob_hip_batch_retable_categorical_device(cpprob_hip_ctx* c, const double* d_emission, const double* d_transition, const double* d_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyCategorical)) return rc;
+    if (!d_emission || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_emission, d_transition, d_observes, nullptr);
+}
+
+// The host form: the tables are validated with the begin's own statements, staged -- the matrix in front, the transition rows at the
+// back -- and re-tabled as by the device form.
+int cpprob_hip_batch_retable_categorical(cpprob_hip_ctx* c, const double* h_emission, const double* h_transition, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyCategorical)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_emission || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    const size_t B = bs->cfg.n_problems, kk = (size_t)bs->hk * bs->hk, kv = (size_t)bs->hk * (size_t)bs->cat_V;
+    int k = 0;
+    const std::vector<double> zeros(B * (size_t)bs->hk, 0.0);
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, zeros.data(), h_transition, k)) return rc;
+    if (int rc = batch_check_emission(c, B, k, bs->cat_V, h_emission)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_observes) if (int rc = batch_retable_observes(c, h_observes, n_observes)) return rc;
+    double *d_emission = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(B * kv * sizeof(double)), B * kk * sizeof(double), d_emission, d_trans)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(d_emission, h_emission, B * kv * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_emission, d_trans, bs->d_robs.as<double>(), nullptr)) return rc;
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    bs->thr_stale = false;
+    return 0;
+}
+
+// cpprob_hip_batch_symbol_stats' arguments against the batch's state (batch_smooth_stats_check's, at 600 doubles a problem).
+static int batch_symbol_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& rows)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
+    BatchState* bs = c->batch;
+    if (!bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has no categorical emissions (cpprob_hip_batch_begin_problems_categorical): its statistics are cpprob_hip_batch_smooth_stats'");
+    if (!stats || !observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    if ((uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    const uint64_t need = (uint64_t)bs->cfg.n_problems * (uint64_t)kSymbolStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (600 a problem)");
+    return 0;
+}
+
+// The pass: batch_smooth_enqueue's prologue under a Stats pass (descriptors, the counting pass), then the symbol walk in place of
+// batch_smooth_stats_kernel, a wavefront a problem under kSymbolGridMax workgroups.
+static int batch_symbol_stats_enqueue(cpprob_hip_ctx* c, const double* d_obs, double* d_stats)
+{
+    BatchState* bs = c->batch;
+    BatchPassPlan pl; BatchSmoothArgs a{};
+    if (int rc = batch_pass_prologue(c, BatchPass::stats(d_obs, d_stats), pl, a)) return rc;
+    if (pl.done) {                                                          // (no problem has a step: every record is zeros)
+        HIP_TRY(c, hipMemsetAsync(d_stats, 0, (size_t)bs->cfg.n_problems * kSymbolStats * sizeof(double), c->stream));
+        return 0;
+    }
+    BatchSymbolStatsArgs sa{};
+    sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = d_obs; sa.stats = d_stats;
+    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.V = bs->cat_V; sa.thr_stride = a.thr_stride;
+    hipLaunchKernelGGL(batch_symbol_stats_kernel, dim3(std::min<unsigned>(pl.stats_gx, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_symbol_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t rows = 0;
+    if (int rc = batch_symbol_stats_check(c, d_observes, n_observes, d_stats, n_doubles, rows)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_symbol_stats_enqueue(c, d_observes, d_stats);
+}
+
+int cpprob_hip_batch_symbol_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t rows = 0;
+    if (int rc = batch_symbol_stats_check(c, h_observes, n_observes, h_stats, n_doubles, rows)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kSymbolStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)rows, d_stats, d_obs)) return rc;
+    if (int rc = batch_symbol_stats_enqueue(c, d_obs, d_stats)) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
+}
+
+int cpprob_hip_batch_mstep_categorical_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_emission, double* d_transition, double prob_floor)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has no categorical emissions: its M-step is its own family's (cpprob_hip_batch_mstep_device, _mstep_scaled_device, _mstep_poisson_device)");
+    if (!d_stats || !d_emission || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (categorical_bad(prob_floor)) return fail(c, CPPROB_HIP_EINVAL, "prob_floor must be > 0, finite and a normal number");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kSymbolStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (600 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepCategoricalArgs a{};
+    a.stats = d_stats; a.emission = d_emission; a.trans = d_transition; a.floor = prob_floor; a.B = (int64_t)B; a.k = bs->hk; a.V = bs->cat_V;
+    hipLaunchKernelGGL(batch_mstep_categorical_kernel, dim3((unsigned)((B * (uint64_t)bs->hk + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_emission(cpprob_hip_ctx* c, uint64_t problem, double* h_E, double* h_logE)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has no categorical emissions (cpprob_hip_batch_begin_problems_categorical)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)kCategoricalSlots * sizeof(double);
+    if (h_E) HIP_TRY(c, hipMemcpyAsync(h_E, bs->d_cat_e.as<double>() + problem * kCategoricalSlots, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (h_logE) HIP_TRY(c, hipMemcpyAsync(h_logE, bs->d_cat_loge.as<double>() + problem * kCategoricalSlots, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -926,6 +926,51 @@ int cpprob_hip_batch_mstep_poisson_device(cpprob_hip_ctx* ctx, const double* d_s
 int cpprob_hip_batch_online_tables_poisson(cpprob_hip_ctx* ctx, const double* h_rates, const double* h_transition);
 int cpprob_hip_batch_copy_rates(cpprob_hip_ctx* ctx, uint64_t problem, double* h_rates, double* h_log_rates);
 
+/* ---- categorical emissions of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_categorical.hpp) --
+ * The discrete HMM: state s of problem b emits symbol v of an alphabet of V symbols, 1 <= V <= 64, with probability E[b][s][v]
+ * (h_emission [B][k][V], beside h_transition [B][k][k]; k <= 8).  An observe is a double that holds a symbol index 0 .. V-1; NaN,
+ * infinities, negatives, non-integers and values >= V are no symbol and have the row of an infinite observe under the Gaussian routes.
+ * A batch is unit, scaled, Poisson or categorical, never two of them: every call of one family on a batch of another returns
+ * CPPROB_HIP_ESTATE and leaves the batch as it was.  The step kernel and every pass behind it read the emission through the per-step
+ * rows alone, so a categorical batch is run (cpprob_hip_batch_run, _run_conditional, _run_exact), smoothed, counted, forecast and
+ * decoded by the calls above as they are.  Every categorical row, on the host and on the device, is
+ *   tab[t][s] = logE[s][c_t] for s < k and the symbol c_t that y_t is          (-inf for s >= k and for a y_t that is no symbol)
+ * with logE[s][v] = table_log(E[s][v]).  Every E[s][v], s < k, v < V, must be > 0, finite and a normal number (table_log's domain).
+ * THE ROWS OF E ARE USED AS GIVEN: the library does not normalise them, and a row that does not sum to 1 is the caller's model.
+ * cpprob_hip_batch_begin_problems_categorical: cpprob_hip_batch_begin_problems with the matrix in place of the means.  V outside
+ * 1 .. 64, k outside 1 .. 8, a NULL argument or an entry outside the domain (naming the problem): CPPROB_HIP_EINVAL; another model:
+ * CPPROB_HIP_EUNSUPPORTED; after a refusal nothing has changed.  There is no online categorical begin.
+ * cpprob_hip_batch_retable_categorical_device / _retable_categorical: cpprob_hip_batch_retable_device / _retable with the matrix
+ * ([B][k][V], V the begin's).  The device checks the transition rows as those calls do and sets status bit 32 where an entry of the
+ * matrix is outside the domain: such a problem keeps its rows, threshold words, matrix and logarithms.
+ * cpprob_hip_batch_symbol_stats_device / _symbol_stats: the E-step.  600 doubles a problem: the first 88 are the record of
+ * cpprob_hip_batch_smooth_stats on the same batch with the same observes, bit for bit; then cnt[s][v] at 88 + 64 s + v, the sum over
+ * the steps t whose observe is symbol v of the smoothed marginal g_t[s], added from 0.0 in the walk's order t = T-1 .. 0.  An observe
+ * that is no symbol adds to no bin; states >= k and symbols >= V are zero.  The observes are required (NULL: CPPROB_HIP_EINVAL);
+ * n_observes and n_doubles as cpprob_hip_batch_smooth_stats checks them, at 600 doubles a problem.  A batch of another family:
+ * CPPROB_HIP_ESTATE.
+ * cpprob_hip_batch_mstep_categorical_device: on d_emission [B][k][V] and d_transition [B][k][k] in place, from records of 600 doubles.
+ * The transition row as cpprob_hip_batch_mstep_device forms it; tot = cnt[s][0] + ... + cnt[s][V-1] added ascending from 0.0; where
+ * tot > 0
+ *   E[s][v] = cnt[s][v] / tot >= prob_floor ? cnt[s][v] / tot : prob_floor     (a NaN: the floor)
+ * and a state without mass keeps its row.  A fitted row may sum to as much as 1 + 64 prob_floor: it is NOT renormalised (the choice
+ * rate_floor makes).  prob_floor must be > 0, finite and a normal number (else CPPROB_HIP_EINVAL).
+ * cpprob_amd.categorical.m_step_categorical, bit for bit.  Enqueued.
+ * cpprob_hip_batch_draw_tables* on a categorical batch: CPPROB_HIP_ESTATE (the Dirichlet draw is not built); the tied pooling sums
+ * 88-double records and does not serve the 600.
+ * cpprob_hip_batch_copy_emission: problem `problem`'s matrix and logarithms in force as the device holds them, [8][64] each (slots
+ * outside the table 0.0 and -inf; either may be NULL); synchronises; CPPROB_HIP_ESTATE: no batch begun, or no categorical batch.
+ * For tests. */
+int cpprob_hip_batch_begin_problems_categorical(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                                const double* h_observes, int32_t k, int32_t V, const double* h_emission, const double* h_transition);
+int cpprob_hip_batch_retable_categorical_device(cpprob_hip_ctx* ctx, const double* d_emission, const double* d_transition, const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_categorical(cpprob_hip_ctx* ctx, const double* h_emission, const double* h_transition, const double* h_observes, size_t n_observes);
+int cpprob_hip_batch_symbol_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+int cpprob_hip_batch_symbol_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+int cpprob_hip_batch_mstep_categorical_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_emission, double* d_transition,
+                                              double prob_floor);
+int cpprob_hip_batch_copy_emission(cpprob_hip_ctx* ctx, uint64_t problem, double* h_E, double* h_logE);
+
 /* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
  * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
  * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
