@@ -63,6 +63,8 @@ SYMBOLS = [
     "cpprob_hip_batch_begin_problems_categorical", "cpprob_hip_batch_retable_categorical", "cpprob_hip_batch_retable_categorical_device",
     "cpprob_hip_batch_symbol_stats", "cpprob_hip_batch_symbol_stats_device", "cpprob_hip_batch_mstep_categorical_device",
     "cpprob_hip_batch_copy_emission",
+    "cpprob_hip_batch_begin_problems_diag", "cpprob_hip_batch_retable_diag", "cpprob_hip_batch_retable_diag_device",
+    "cpprob_hip_batch_diag_stats", "cpprob_hip_batch_diag_stats_device", "cpprob_hip_batch_mstep_diag_device", "cpprob_hip_batch_copy_diag",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
@@ -224,6 +226,8 @@ DECODE_MAX_LAG = 1 << 24                      # cpprob_hip_batch_decode_lag: lag
 STATS_PER_PROBLEM = 88                        # doubles a problem of cpprob_hip_batch_smooth_stats: xi[8][8], occ[8], occ_y[8], occ_yy[8]
 CATEGORICAL_MAX_SYMBOLS = 64                  # cpprob_hip_batch_begin_problems_categorical: V in 1 ..=
 SYMBOL_STATS_PER_PROBLEM = 88 + 8 * 64        # doubles a problem of cpprob_hip_batch_symbol_stats: the 88 above, then cnt[8][64]
+DIAG_MAX_DIM = 32                             # cpprob_hip_batch_begin_problems_diag: D in 1 ..=
+DIAG_STATS_PER_PROBLEM = 88 + 8 * 2 * 32      # doubles a problem of cpprob_hip_batch_diag_stats: the 88 above, then sy[32] and syy[32] of every state
 
 
 TRAJ_STATS_TILE = 256                         # trajectories a workgroup of cpprob_hip_batch_traj_stats: its grid holds ceil(n_traj / this) tiles a problem
@@ -447,6 +451,13 @@ def load_library(path=None):
         "cpprob_hip_batch_symbol_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_mstep_categorical_device": (C.c_int, [vp, vp, sz, vp, vp, dbl]),
         "cpprob_hip_batch_copy_emission": (C.c_int, [vp, u64, vp, vp]),
+        "cpprob_hip_batch_begin_problems_diag": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, C.c_int32, vp, vp, vp]),
+        "cpprob_hip_batch_retable_diag": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_diag_device": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_diag_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_diag_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_mstep_diag_device": (C.c_int, [vp, vp, sz, vp, vp, vp, dbl]),
+        "cpprob_hip_batch_copy_diag": (C.c_int, [vp, u64, vp, vp, vp]),
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
@@ -1044,6 +1055,79 @@ class Engine:
         e, le = np.zeros((8, CATEGORICAL_MAX_SYMBOLS)), np.zeros((8, CATEGORICAL_MAX_SYMBOLS))
         self._chk(self.L.cpprob_hip_batch_copy_emission(self.h, int(b), e.ctypes.data, le.ctypes.data))
         return e[:k, :V].copy(), le[:k, :V].copy()
+
+    # ---- diagonal-Gaussian vector emissions (include/cpprob_hip.h: cpprob_hip_batch_*_diag, _diag_stats*; csrc/batch_diag.hpp) ----
+    def _batch_diag_tables(self, means, sigmas, trans, B):
+        mu = np.ascontiguousarray(means, np.float64)
+        sg = np.ascontiguousarray(sigmas, np.float64)
+        tr = np.ascontiguousarray(trans, np.float64)
+        if mu.ndim != 3 or mu.shape[0] != B or sg.shape != mu.shape or tr.shape != (B, mu.shape[1], mu.shape[1]):
+            raise ValueError("means and sigmas [B, k, D] and transition [B, k, k]")
+        return mu, sg, tr
+
+    def batch_begin_problems_diag(self, observes, n_particles, means, sigmas, trans, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, keep_masses=False, max_particles=None):
+        """A MODEL_HMM_TABLE batch whose observe of a step is a vector (cpprob_hip_batch_begin_problems_diag): observes a list of
+        [T_b, D] arrays, means and sigmas [B, k, D] (state s of problem b emits independent coordinates N(means[b, s, d],
+        sigmas[b, s, d])), trans [B, k, k]; k <= 8, D <= 32.  Everything else as batch_begin_problems."""
+        mu, sg, tr = self._batch_diag_tables(means, sigmas, trans, len(observes))
+        D = mu.shape[2]
+        seqs = [np.ascontiguousarray(o, np.float64) for o in observes]
+        seqs = [o.reshape(-1, 1) if o.ndim == 1 else o for o in seqs]
+        if 1 <= D <= DIAG_MAX_DIM and any(o.ndim != 2 or o.shape[1] != D for o in seqs):      # (another D: the library's own refusal)
+            raise ValueError("observes: one [T_b, D] array a problem")
+        h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
+        flat = self._batch_packed_observes(seqs)
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(MODEL_HMM_TABLE, top, len(seqs), resampler, 2.0, keep_history, ALG_SMC, _batch_flags(0, keep_masses))
+        self._chk(self.L.cpprob_hip_batch_begin_problems_diag(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                              flat.ctypes.data_as(C.POINTER(C.c_double)), mu.shape[1], mu.shape[2], mu.ctypes.data, sg.ctypes.data, tr.ctypes.data))
+        self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
+        self.batch_K, self.batch_k, self.batch_D = 8, mu.shape[1], D
+        self.batch_shapes = (h_T, h_n)
+        return self
+
+    def batch_retable_diag(self, means, sigmas, trans, observes=None):
+        """New means, sigmas and transition rows for the begun diagonal batch where it stands (cpprob_hip_batch_retable_diag),
+        validated as the begin validates them; observes as the begin takes them, or None once a re-table has staged them."""
+        mu, sg, tr = self._batch_diag_tables(means, sigmas, trans, self.batch_B)
+        flat = None if observes is None else self._batch_packed_observes(list(observes))
+        n_obs = int(np.sum(self.batch_shapes[0], dtype=np.int64)) * getattr(self, "batch_D", 1) if flat is None else flat.size
+        self._chk(self.L.cpprob_hip_batch_retable_diag(self.h, mu.ctypes.data, sg.ctypes.data, tr.ctypes.data, None if flat is None or flat.size == 0 else flat.ctypes.data, n_obs))
+
+    def batch_retable_diag_device(self, means, sigmas, trans, observes):
+        """The same between torch float64 device tensors (means and sigmas [B, k, D], trans [B, k, k], observes packed, D doubles a
+        step), enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status: bit 4, a mean
+        that is not finite; bit 8, a sigma the scaled calls refuse)."""
+        self._chk(self.L.cpprob_hip_batch_retable_diag_device(self.h, _dptr(means), _dptr(sigmas), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+
+    def batch_diag_stats(self, observes):
+        """The E-step of a diagonal batch (cpprob_hip_batch_diag_stats): batch_smooth_stats' dict with coordinate 0 as the observe,
+        and sy, syy [B, 8, 32]: the expected visits of state s weighted by y_t[d] and by y_t[d]^2."""
+        rec = np.zeros((self.batch_B, DIAG_STATS_PER_PROBLEM))
+        flat = self._batch_packed_observes(list(observes))
+        self._chk(self.L.cpprob_hip_batch_diag_stats(self.h, flat.ctypes.data if flat.size else None, flat.size, rec.ctypes.data, rec.size))
+        out = split_stats(np.ascontiguousarray(rec[:, :STATS_PER_PROBLEM]))
+        tail = rec[:, STATS_PER_PROBLEM:].reshape(-1, 8, 2, DIAG_MAX_DIM)
+        out["sy"], out["syy"] = np.ascontiguousarray(tail[:, :, 0]), np.ascontiguousarray(tail[:, :, 1])
+        return out
+
+    def batch_diag_stats_device(self, stats, observes):
+        """The same left in a device tensor: stats torch float64 [B, 600], observes a torch float64 tensor packed problem after
+        problem, D doubles a step."""
+        self._chk(self.L.cpprob_hip_batch_diag_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    def batch_mstep_diag_device(self, stats, means, sigmas, trans, sigma_floor=1e-3):
+        """diag.m_step_diag on the device (cpprob_hip_batch_mstep_diag_device): stats torch float64 [B, 600]; means and sigmas
+        [B, k, D] and trans [B, k, k] torch float64, updated in place; no fitted sigma below sigma_floor.  Enqueued."""
+        self._chk(self.L.cpprob_hip_batch_mstep_diag_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(sigmas), _dptr(trans), float(sigma_floor)))
+
+    def batch_copy_diag(self, b, k=None, D=None):
+        """(means [k, D], sigmas [k, D], log_norms [k]) of problem b of a diagonal batch, as the device holds them
+        (cpprob_hip_batch_copy_diag).  Synchronises.  For tests."""
+        k, D = int(k if k is not None else self.batch_k), int(D if D is not None else getattr(self, "batch_D", 1))
+        mu, sg, ln = np.zeros((8, DIAG_MAX_DIM)), np.zeros((8, DIAG_MAX_DIM)), np.zeros(8)
+        self._chk(self.L.cpprob_hip_batch_copy_diag(self.h, int(b), mu.ctypes.data, sg.ctypes.data, ln.ctypes.data))
+        return mu[:k, :D].copy(), sg[:k, :D].copy(), ln[:k].copy()
 
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):

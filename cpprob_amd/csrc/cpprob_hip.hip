@@ -32,6 +32,7 @@
 #include "batch_scale.hpp"
 #include "batch_poisson.hpp"
 #include "batch_categorical.hpp"
+#include "batch_diag.hpp"
 #include "batch_learn.hpp"
 #include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
@@ -1010,14 +1011,44 @@ void poisson_step_ll(double y, const double* rate, const double* log_rate, const
 {
     for (int s2 = 0; s2 < 8; ++s2) ll[s2] = s2 < k ? poisson_entry(y, rate[s2], log_rate[s2], lf) : -INFINITY;
 }
-// The emission family of a table batch and of a call that hands tables over: N(mean, 1), N(mean, sigma) or Poisson(rate).
-enum EmissionFamily { kFamilyUnit = 0, kFamilyScaled = 1, kFamilyPoisson = 2 };
+// The emission family of a table batch and of a call that hands tables over: N(mean, 1), N(mean, sigma) or Poisson(rate); kFamilyDiag: a
+// vector with independent Gaussian coordinates (csrc/batch_diag.hpp), D doubles a step, begun, re-tabled and fitted by its own calls.
+enum EmissionFamily { kFamilyUnit = 0, kFamilyScaled = 1, kFamilyPoisson = 2, kFamilyDiag = 4 };
 // ... or a symbol of a finite alphabet (csrc/batch_categorical.hpp): the fourth family, begun, re-tabled and fitted by its own calls
 constexpr EmissionFamily kFamilyCategorical = (EmissionFamily)3;
 // a categorical table's row, with the statements the device's re-table writes it with: log_e [8][64], slots outside the table -inf
 void categorical_step_ll(double y, int V, const double* log_e, double* ll)
 {
     for (int s2 = 0; s2 < 8; ++s2) ll[s2] = categorical_entry(y, V, log_e + (size_t)s2 * kCategoricalMaxSymbols, 1);
+}
+// a diagonal table's row, with the statements the device's re-table writes it with: y the step's D coordinates; mean, sigma [8][32];
+// log_norm [8]
+void diag_step_ll(const double* y, int D, const double* mean, const double* sigma, const double* log_norm, int k, double* ll)
+{
+    for (int s2 = 0; s2 < 8; ++s2)
+        ll[s2] = s2 < k ? diag_entry(y, D, mean + (size_t)s2 * kDiagMaxDim, sigma + (size_t)s2 * kDiagMaxDim, 1, log_norm[s2]) : -INFINITY;
+}
+// a problem's rows (kept out of line: batch_begin's own loop stays the other families')
+__attribute__((noinline)) void diag_problem_rows(const double* y, size_t T, int D, const double* mean, const double* sigma, const double* log_norm, int k, double* rows)
+{
+    for (size_t t = 0; t < T; ++t) diag_step_ll(y + t * (size_t)D, D, mean, sigma, log_norm, k, rows + t * kBatchTab);
+}
+// the tables of a diagonal begin ([B][k][D]) in the device's layout, [B][8][32] and [B][8]: slots outside the table 0.0
+__attribute__((noinline)) void diag_expand_tables(size_t B, int k, int D, const double* h_means, const double* h_sigmas, std::vector<double>& mean, std::vector<double>& sigma,
+                                                  std::vector<double>& log_norm)
+{
+    mean.assign(B * kDiagSlots, 0.0); sigma.assign(B * kDiagSlots, 0.0); log_norm.assign(B * 8, 0.0);
+    double ln[kDiagMaxDim];
+    for (size_t b = 0; b < B; ++b)
+        for (size_t s = 0; s < (size_t)k; ++s) {
+            for (size_t d = 0; d < (size_t)D; ++d) {
+                const size_t from = (b * (size_t)k + s) * (size_t)D + d, to = b * kDiagSlots + s * kDiagMaxDim + d;
+                mean[to] = h_means[from];
+                sigma[to] = h_sigmas[from];
+                ln[d] = scale_log_norm(sigma[to]);
+            }
+            log_norm[b * 8 + s] = diag_log_norm(ln, D, 1);
+        }
 }
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
 {
@@ -1191,6 +1222,16 @@ struct BatchState {
     DeviceBuffer d_cat_e, d_cat_loge;
     const double* cat_begin_E = nullptr;
     int cat_begin_V = 0;
+    // diagonal-Gaussian vector emissions (cpprob_hip_batch_begin_problems_diag; csrc/batch_diag.hpp): diag: the begun batch has them, and
+    // is then of no other family; diag_D its coordinates, and every observes array of its calls holds diag_D doubles a step.  The means
+    // and sigmas in force, [B][8][32] (slots outside the table 0.0), and the states' log_norms, [B][8], are the device's alone
+    // (allocations of the context's own): a begin uploads them, a re-table rewrites them.  diag_begin_*: the checked arguments of the
+    // begin in progress, read by batch_begin and by nothing else
+    bool diag = false;
+    int diag_D = 0;
+    DeviceBuffer d_diag_mean, d_diag_sigma, d_diag_lognorm;
+    const double *diag_begin_means = nullptr, *diag_begin_sigmas = nullptr;
+    int diag_begin_D = 0;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
@@ -1364,6 +1405,17 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, bs->d_cat_e.grow(c->stream, cat_e.size() * sizeof(double)));
         HIP_TRY(c, bs->d_cat_loge.grow(c->stream, cat_loge.size() * sizeof(double)));
     }
+    const bool diag = family == kFamilyDiag;                    // (h_means: zeros no row reads; the tables are bs->diag_begin_*)
+    bs->diag = false;
+    std::vector<double> dg_mean, dg_sigma, dg_lognorm;          // (live until the synchronisation below)
+    const int diag_D = diag ? bs->diag_begin_D : 0;
+    if (diag) {
+        diag_expand_tables((size_t)B, k, diag_D, bs->diag_begin_means, bs->diag_begin_sigmas, dg_mean, dg_sigma, dg_lognorm);
+        HIP_TRY(c, bs->d_diag_mean.grow(c->stream, dg_mean.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_diag_sigma.grow(c->stream, dg_sigma.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_diag_lognorm.grow(c->stream, dg_lognorm.size() * sizeof(double)));
+    }
+    const size_t obs_stride = diag ? (size_t)diag_D : 1;        // doubles a step of h_obs
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
@@ -1374,7 +1426,9 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         const size_t T_b = described ? h_T[b] : T_max, n_b = described ? h_n[b] : (size_t)cfg->n_particles;
         if (own) { mean.assign(h_means + b * (size_t)k, h_means + (b + 1) * (size_t)k); trans.assign(h_transition + b * (size_t)k * k, h_transition + (b + 1) * (size_t)k * k); }
         if (online && own) { bs->means.insert(bs->means.end(), mean.begin(), mean.end()); bs->trans.insert(bs->trans.end(), trans.begin(), trans.end()); }
-        for (size_t t = 0; t < (online ? 0 : T_b); ++t) {
+        // (a diagonal batch: a row loop of its own, obs_stride doubles a step; at_obs counts steps)
+        if (diag) diag_problem_rows(h_obs + at_obs * obs_stride, T_b, diag_D, &dg_mean[b * kDiagSlots], &dg_sigma[b * kDiagSlots], &dg_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
+        for (size_t t = 0; t < (online || diag ? 0 : T_b); ++t) {
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
@@ -1405,6 +1459,11 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     if (categorical) {
         HIP_TRY(c, hipMemcpyAsync(bs->d_cat_e.as<double>(), cat_e.data(), cat_e.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_cat_loge.as<double>(), cat_loge.data(), cat_loge.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
+    if (diag) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_diag_mean.as<double>(), dg_mean.data(), dg_mean.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_diag_sigma.as<double>(), dg_sigma.data(), dg_sigma.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_diag_lognorm.as<double>(), dg_lognorm.data(), dg_lognorm.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
@@ -1437,6 +1496,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->cfg = *cfg; bs->T = (int)T_max; bs->K = spp; bs->hk = k; bs->described = described;
     bs->online = online; bs->walked = true; bs->own_tables = own; bs->scaled = scaled; bs->poisson = poisson;
     bs->categorical = categorical; bs->cat_V = cat_V;
+    bs->diag = diag; bs->diag_D = diag_D;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -5275,6 +5335,7 @@ static int batch_smooth_stats_check(cpprob_hip_ctx* c, bool with_obs, size_t n_o
 {
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
+    if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its statistics are cpprob_hip_batch_diag_stats / _diag_stats_device");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     rows = 0;
@@ -5378,6 +5439,7 @@ static int batch_traj_stats_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t d
 {
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_check(c, n_traj, draw_index, false, 0, false, 0, doubles, entries)) return rc;
+    if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (n_traj == 0) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 1 .. 2^20");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
@@ -5680,7 +5742,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "re-tabling serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
     const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
-    const bool categorical = family == kFamilyCategorical;
+    const bool categorical = family == kFamilyCategorical, diag = family == kFamilyDiag;
+    if (bs->diag && !diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: it is re-tabled by cpprob_hip_batch_retable_diag / _retable_diag_device");
+    if (!bs->diag && diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has no diagonal-Gaussian vector emissions: begin it with cpprob_hip_batch_begin_problems_diag, or re-table it with its own family's calls");
     if (bs->categorical && !categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: it is re-tabled by cpprob_hip_batch_retable_categorical / _retable_categorical_device");
     if (!bs->categorical && categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has no categorical emissions: begin it with cpprob_hip_batch_begin_problems_categorical, or re-table it with its own family's calls");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: it is re-tabled by cpprob_hip_batch_retable_poisson / _retable_poisson_device");
@@ -5689,7 +5753,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     if (!bs->scaled && scaled) return fail(c, CPPROB_HIP_ESTATE, "the batch has no emission scales: begin it with cpprob_hip_batch_begin_problems_scaled, or re-table it with cpprob_hip_batch_retable / _retable_device");
     uint64_t rows = 0;
     for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
-    if ((uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    if (diag && (uint64_t)n_observes != rows * (uint64_t)bs->diag_D)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->diag_D) + " doubles");
+    if (!diag && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
     return 0;
 }
 
@@ -5712,6 +5778,14 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
         r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
+    if (bs->diag) {
+        // (a diagonal batch: d_means [B][k][D] and d_sigmas [B][k][D]; the tables in force are the device's; the first entries count steps)
+        BatchRetableDiagArgs da{};
+        common(da);
+        da.means = d_means; da.sigmas = d_sigmas; da.D = bs->diag_D;
+        da.mean_out = bs->d_diag_mean.as<double>(); da.sigma_out = bs->d_diag_sigma.as<double>(); da.log_norm_out = bs->d_diag_lognorm.as<double>();
+        hipLaunchKernelGGL(batch_retable_diag_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, da);
+    } else
     if (bs->categorical) {
         // (a categorical batch: d_means is its emission matrix [B][k][V]; the matrix and its logarithms in force are the device's)
         BatchRetableCategoricalArgs ca{};
@@ -5873,6 +5947,7 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
     BatchState* bs = c->batch;
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_diag_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: its M-step is cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its M-step is cpprob_hip_batch_mstep_poisson_device");
     if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: its M-step is cpprob_hip_batch_mstep_device / _mstep_scaled_device");
@@ -5930,6 +6005,7 @@ int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* c, const double* d_stats
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the draw samples the tables of CPPROB_HIP_MODEL_HMM_TABLE");
     if (!bs->own_tables) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the batch was begun with the context's shared table: begin it with per-problem tables to draw them");
+    if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_diag_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: the conjugate (Dirichlet) draw of its matrix is not built -- fit it with cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: the conjugate (gamma) draw of its rates is not built -- fit it with cpprob_hip_batch_mstep_poisson_device");
     if (bs->scaled && !d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its draw takes d_sigmas");
@@ -6260,6 +6336,174 @@ int cpprob_hip_batch_copy_emission(cpprob_hip_ctx* c, uint64_t problem, double* 
     const size_t bytes = (size_t)kCategoricalSlots * sizeof(double);
     if (h_E) HIP_TRY(c, hipMemcpyAsync(h_E, bs->d_cat_e.as<double>() + problem * kCategoricalSlots, bytes, hipMemcpyDeviceToHost, c->stream));
     if (h_logE) HIP_TRY(c, hipMemcpyAsync(h_logE, bs->d_cat_loge.as<double>() + problem * kCategoricalSlots, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- diagonal-Gaussian vector emissions of a batch (csrc/batch_diag.hpp) ------------------------------------------------------------
+// Means and sigmas on the host ([B][k][D]): every mean finite (diag_check's bit 4), every sigma one scale_check takes (bit 8), by name.
+static int batch_check_diag(cpprob_hip_ctx* c, uint64_t B, int k, int D, const double* h_means, const double* h_sigmas)
+{
+    for (uint64_t b = 0; b < B; ++b)
+        for (size_t i = 0; i < (size_t)k * (size_t)D; ++i) {
+            if (!std::isfinite(h_means[b * (size_t)k * (size_t)D + i])) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": state means must be finite");
+            if (scale_bad(h_sigmas[b * (size_t)k * (size_t)D + i]))
+                return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": emission scales must be finite and > 0, with a normal finite 2 pi sigma^2");
+        }
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems_diag(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
+                                         int32_t k_in, int32_t D, const double* h_means, const double* h_sigmas, const double* h_transition)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_means || !h_sigmas || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "diagonal-Gaussian vector emissions serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    if (D < 1 || D > kDiagMaxDim) return fail(c, CPPROB_HIP_EINVAL, "D, the coordinates of an observe, must lie in 1 .. 32");
+    if (k_in < 1 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "k must lie in 1 .. 8");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    if (int rc = batch_check_diag(c, cfg->n_problems, k_in, D, h_means, h_sigmas)) return rc;
+    // (the begin's route takes means [B][k]: zeros, which no diagonal row reads; the tables travel beside them)
+    const std::vector<double> zeros((size_t)cfg->n_problems * (size_t)k_in, 0.0);
+    if (!c->batch) c->batch = new BatchState();
+    c->batch->diag_begin_means = h_means; c->batch->diag_begin_sigmas = h_sigmas; c->batch->diag_begin_D = D;
+    const int rc = batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, zeros.data(), h_transition, nullptr, nullptr, kFamilyDiag);
+    c->batch->diag_begin_means = nullptr; c->batch->diag_begin_sigmas = nullptr; c->batch->diag_begin_D = 0;
+    return rc;
+}
+
+int cpprob_hip_batch_retable_diag_device(cpprob_hip_ctx* c, const double* d_means, const double* d_sigmas, const double* d_transition, const double* d_observes,
+                                         size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyDiag)) return rc;
+    if (!d_means || !d_sigmas || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_means, d_transition, d_observes, d_sigmas);
+}
+
+// The host form: the tables are validated with the begin's own statements, staged -- the means and the sigmas in front, the transition
+// rows at the back -- and re-tabled as by the device form.
+int cpprob_hip_batch_retable_diag(cpprob_hip_ctx* c, const double* h_means, const double* h_sigmas, const double* h_transition, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyDiag)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_means || !h_sigmas || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    const size_t B = bs->cfg.n_problems, kk = (size_t)bs->hk * bs->hk, kd = (size_t)bs->hk * (size_t)bs->diag_D;
+    int k = 0;
+    const std::vector<double> zeros(B * (size_t)bs->hk, 0.0);
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, zeros.data(), h_transition, k)) return rc;
+    if (int rc = batch_check_diag(c, B, k, bs->diag_D, h_means, h_sigmas)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_observes) if (int rc = batch_retable_observes(c, h_observes, n_observes)) return rc;
+    double *d_means = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(2 * B * kd * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
+    double* d_sigmas = d_means + B * kd;
+    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * kd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * kd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs.as<double>(), d_sigmas)) return rc;
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    bs->thr_stale = false;
+    return 0;
+}
+
+// cpprob_hip_batch_diag_stats' arguments against the batch's state (batch_symbol_stats_check's, at D doubles a step).
+static int batch_diag_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& n_obs)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
+    BatchState* bs = c->batch;
+    if (!bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has no diagonal-Gaussian vector emissions (cpprob_hip_batch_begin_problems_diag): its statistics are its own family's");
+    if (!stats || !observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    uint64_t rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    n_obs = rows * (uint64_t)bs->diag_D;
+    if ((uint64_t)n_observes != n_obs)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->diag_D) + " doubles");
+    const uint64_t need = (uint64_t)bs->cfg.n_problems * (uint64_t)kSymbolStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (600 a problem)");
+    return 0;
+}
+
+// The pass: batch_symbol_stats_enqueue's, with the diagonal walk; the descriptors' first observes count steps.
+static int batch_diag_stats_enqueue(cpprob_hip_ctx* c, const double* d_obs, double* d_stats)
+{
+    BatchState* bs = c->batch;
+    BatchPassPlan pl; BatchSmoothArgs a{};
+    if (int rc = batch_pass_prologue(c, BatchPass::stats(d_obs, d_stats), pl, a)) return rc;
+    if (pl.done) {                                                          // (no problem has a step: every record is zeros)
+        HIP_TRY(c, hipMemsetAsync(d_stats, 0, (size_t)bs->cfg.n_problems * kSymbolStats * sizeof(double), c->stream));
+        return 0;
+    }
+    BatchDiagStatsArgs sa{};
+    sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = d_obs; sa.stats = d_stats;
+    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->diag_D; sa.thr_stride = a.thr_stride;
+    hipLaunchKernelGGL(batch_diag_stats_kernel, dim3(std::min<unsigned>(pl.stats_gx, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_diag_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_diag_stats_check(c, d_observes, n_observes, d_stats, n_doubles, n_obs)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_diag_stats_enqueue(c, d_observes, d_stats);
+}
+
+int cpprob_hip_batch_diag_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_diag_stats_check(c, h_observes, n_observes, h_stats, n_doubles, n_obs)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kSymbolStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)n_obs, d_stats, d_obs)) return rc;
+    if (int rc = batch_diag_stats_enqueue(c, d_obs, d_stats)) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
+}
+
+int cpprob_hip_batch_mstep_diag_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_sigmas, double* d_transition, double sigma_floor)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has no diagonal-Gaussian vector emissions: its M-step is its own family's");
+    if (!d_stats || !d_means || !d_sigmas || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor)) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kSymbolStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (600 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepDiagArgs a{};
+    a.stats = d_stats; a.means = d_means; a.sigmas = d_sigmas; a.trans = d_transition; a.floor = sigma_floor; a.B = (int64_t)B; a.k = bs->hk; a.D = bs->diag_D;
+    hipLaunchKernelGGL(batch_mstep_diag_kernel, dim3((unsigned)((B * (uint64_t)bs->hk * (uint64_t)bs->diag_D + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_diag(cpprob_hip_ctx* c, uint64_t problem, double* h_means, double* h_sigmas, double* h_log_norms)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has no diagonal-Gaussian vector emissions (cpprob_hip_batch_begin_problems_diag)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)kDiagSlots * sizeof(double);
+    if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_diag_mean.as<double>() + problem * kDiagSlots, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_diag_sigma.as<double>() + problem * kDiagSlots, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_diag_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }

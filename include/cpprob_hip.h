@@ -971,6 +971,54 @@ int cpprob_hip_batch_mstep_categorical_device(cpprob_hip_ctx* ctx, const double*
                                               double prob_floor);
 int cpprob_hip_batch_copy_emission(cpprob_hip_ctx* ctx, uint64_t problem, double* h_E, double* h_logE);
 
+/* ---- diagonal-Gaussian vector emissions of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_diag.hpp) --
+ * The observe of a step is a vector y in R^D, 1 <= D <= 32: state s of problem b emits independent coordinates
+ * y_d ~ N(mean[b][s][d], sigma[b][s][d]) (h_means and h_sigmas [B][k][D], beside h_transition [B][k][k]; k <= 8).  Every observes
+ * array of these calls holds D doubles a step, problem after problem and step after step, and n_observes counts doubles (D times the
+ * sum of the lengths).  A batch is unit, scaled, Poisson, categorical or diagonal, never two of them: every call of one family on a
+ * batch of another returns CPPROB_HIP_ESTATE and leaves the batch as it was.  The step kernel and every pass behind it read the
+ * emission through the per-step rows alone, so a diagonal batch is run (cpprob_hip_batch_run, _run_conditional, _run_exact), smoothed,
+ * counted, forecast and decoded by the calls above as they are.  Every diagonal row, on the host and on the device, is
+ *   r_d = (y_d - mean[s][d]) / sigma[s][d];  q = ((0.0 + r_0 r_0) + r_1 r_1) + ...;  tab[t][s] = (q + log_norm[s]) (-0.5)
+ *   log_norm[s] = ((0.0 + scale_log_norm(sigma[s][0])) + scale_log_norm(sigma[s][1])) + ...
+ * both sums ascending over d, nothing contracted; -inf for s >= k and where any |y_d| is infinite.  At D = 1 the rows, the log_norms
+ * and the M-step are those of the scaled calls above, bit for bit.  Every mean must be finite, every sigma one the scaled calls take.
+ * cpprob_hip_batch_begin_problems_diag: cpprob_hip_batch_begin_problems with D, the means and the sigmas.  D outside 1 .. 32, k outside
+ * 2 .. 8, a NULL argument, a mean or a sigma outside the domain (naming the problem): CPPROB_HIP_EINVAL; another model:
+ * CPPROB_HIP_EUNSUPPORTED; after a refusal nothing has changed.  There is no online diagonal begin.
+ * cpprob_hip_batch_retable_diag_device / _retable_diag: cpprob_hip_batch_retable_scaled_device / _retable_scaled with [B][k][D] tables.
+ * The device checks the transition rows as those calls do, sets status bit 4 for a mean that is not finite and bit 8 for a sigma
+ * outside the domain: such a problem keeps its rows, threshold words, means, sigmas and log_norms.
+ * cpprob_hip_batch_diag_stats_device / _diag_stats: the E-step.  600 doubles a problem: the first 88 are the record of
+ * cpprob_hip_batch_smooth_stats with coordinate 0 of every step as the observe; then sy[s][d] = sum over t of g_t[s] y_t[d] at
+ * 88 + 64 s + d and syy[s][d] = sum over t of g_t[s] (y_t[d] y_t[d]) at 88 + 64 s + 32 + d, g_t the smoothed marginal, added from 0.0
+ * in the walk's order t = T-1 .. 0, every product rounded once.  Slots with s >= k or d >= D are zero.  The observes are required
+ * (NULL: CPPROB_HIP_EINVAL).  A batch of another family: CPPROB_HIP_ESTATE.
+ * cpprob_hip_batch_mstep_diag_device: on d_means and d_sigmas [B][k][D] and d_transition [B][k][k] in place, from records of 600
+ * doubles.  The transition row as cpprob_hip_batch_mstep_device forms it; for a state with occ > 0 and every d < D
+ *   mean' = sy / occ;  v = syy / occ - mean' mean';  sigma' = v >= sigma_floor^2 ? sqrt(v) : sigma_floor     (a NaN v: the floor)
+ * and a state without mass keeps its tables.  sigma_floor must be finite and > 0 (else CPPROB_HIP_EINVAL).
+ * cpprob_amd.diag.m_step_diag, bit for bit.  Enqueued.
+ * On a diagonal batch the other families' re-tables and M-steps, cpprob_hip_batch_draw_tables_device and the calls that take one
+ * observe a step -- cpprob_hip_batch_smooth_stats*, _symbol_stats*, _traj_stats* -- return CPPROB_HIP_ESTATE; the online calls
+ * (cpprob_hip_batch_learn_begin*, _online_tables*) do so because the batch is not online.  The tied pooling sums 88-double records and
+ * does not serve the 600.
+ * cpprob_hip_batch_copy_diag: problem `problem`'s means and sigmas in force as the device holds them, [8][32] each (slots outside the
+ * table 0.0), and its log_norms [8] (any may be NULL); synchronises; CPPROB_HIP_ESTATE: no batch begun, or no diagonal batch.
+ * For tests. */
+int cpprob_hip_batch_begin_problems_diag(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                         const double* h_observes, int32_t k, int32_t D, const double* h_means, const double* h_sigmas,
+                                         const double* h_transition);
+int cpprob_hip_batch_retable_diag_device(cpprob_hip_ctx* ctx, const double* d_means, const double* d_sigmas, const double* d_transition,
+                                         const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_diag(cpprob_hip_ctx* ctx, const double* h_means, const double* h_sigmas, const double* h_transition,
+                                  const double* h_observes, size_t n_observes);
+int cpprob_hip_batch_diag_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+int cpprob_hip_batch_diag_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+int cpprob_hip_batch_mstep_diag_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_means, double* d_sigmas,
+                                       double* d_transition, double sigma_floor);
+int cpprob_hip_batch_copy_diag(cpprob_hip_ctx* ctx, uint64_t problem, double* h_means, double* h_sigmas, double* h_log_norms);
+
 /* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
  * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
  * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
