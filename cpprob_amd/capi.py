@@ -65,6 +65,8 @@ SYMBOLS = [
     "cpprob_hip_batch_copy_emission",
     "cpprob_hip_batch_begin_problems_diag", "cpprob_hip_batch_retable_diag", "cpprob_hip_batch_retable_diag_device",
     "cpprob_hip_batch_diag_stats", "cpprob_hip_batch_diag_stats_device", "cpprob_hip_batch_mstep_diag_device", "cpprob_hip_batch_copy_diag",
+    "cpprob_hip_batch_begin_problems_full", "cpprob_hip_batch_retable_full", "cpprob_hip_batch_retable_full_device",
+    "cpprob_hip_batch_full_stats", "cpprob_hip_batch_full_stats_device", "cpprob_hip_batch_mstep_full_device", "cpprob_hip_batch_copy_full",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
@@ -227,6 +229,9 @@ STATS_PER_PROBLEM = 88                        # doubles a problem of cpprob_hip_
 CATEGORICAL_MAX_SYMBOLS = 64                  # cpprob_hip_batch_begin_problems_categorical: V in 1 ..=
 SYMBOL_STATS_PER_PROBLEM = 88 + 8 * 64        # doubles a problem of cpprob_hip_batch_symbol_stats: the 88 above, then cnt[8][64]
 DIAG_MAX_DIM = 32                             # cpprob_hip_batch_begin_problems_diag: D in 1 ..=
+FULL_MAX_DIM = 16                             # cpprob_hip_batch_begin_problems_full: D in 1 ..=
+FULL_TRI = 136                                # the packed lower triangle of a state: entry (i, j), j <= i, at i (i + 1) / 2 + j
+FULL_STATS_PER_PROBLEM = 1304                 # doubles a problem of cpprob_hip_batch_full_stats: the 88 above, sy[8][16], syy[8][136]
 DIAG_STATS_PER_PROBLEM = 88 + 8 * 2 * 32      # doubles a problem of cpprob_hip_batch_diag_stats: the 88 above, then sy[32] and syy[32] of every state
 
 
@@ -238,6 +243,24 @@ def split_stats(rec):
     """The records [B, 88] of cpprob_hip_batch_smooth_stats as a dict of views: xi [B, 8, 8], occ, occ_y, occ_yy [B, 8]."""
     rec = np.asarray(rec).reshape(-1, STATS_PER_PROBLEM)
     return {"xi": rec[:, :64].reshape(-1, 8, 8), "occ": rec[:, 64:72], "occ_y": rec[:, 72:80], "occ_yy": rec[:, 80:88]}
+
+
+_FULL_I, _FULL_J = np.tril_indices(FULL_MAX_DIM)     # (row-major over the lower triangle: entry (i, j) is number i (i + 1) / 2 + j)
+
+
+def split_full_stats(rec):
+    """The records [B, 1304] of cpprob_hip_batch_full_stats as a dict: split_stats' entries, sy [B, 8, 16] and syy [B, 8, 16, 16],
+    unpacked from the lower triangle and symmetric."""
+    rec = np.asarray(rec, np.float64).reshape(-1, FULL_STATS_PER_PROBLEM)
+    out = split_stats(np.ascontiguousarray(rec[:, :STATS_PER_PROBLEM]))
+    at = STATS_PER_PROBLEM + 8 * FULL_MAX_DIM
+    out["sy"] = np.ascontiguousarray(rec[:, STATS_PER_PROBLEM:at]).reshape(-1, 8, FULL_MAX_DIM)
+    tri = rec[:, at:].reshape(-1, 8, FULL_TRI)
+    syy = np.zeros((len(rec), 8, FULL_MAX_DIM, FULL_MAX_DIM))
+    syy[:, :, _FULL_I, _FULL_J] = tri
+    syy[:, :, _FULL_J, _FULL_I] = tri
+    out["syy"] = syy
+    return out
 
 
 def split_traj_stats(rec):
@@ -458,6 +481,13 @@ def load_library(path=None):
         "cpprob_hip_batch_diag_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_mstep_diag_device": (C.c_int, [vp, vp, sz, vp, vp, vp, dbl]),
         "cpprob_hip_batch_copy_diag": (C.c_int, [vp, u64, vp, vp, vp]),
+        "cpprob_hip_batch_begin_problems_full": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, C.c_int32, vp, vp, vp]),
+        "cpprob_hip_batch_retable_full": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_full_device": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_full_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_full_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_mstep_full_device": (C.c_int, [vp, vp, sz, vp, vp, vp, dbl]),
+        "cpprob_hip_batch_copy_full": (C.c_int, [vp, u64, vp, vp, vp]),
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
@@ -1128,6 +1158,79 @@ class Engine:
         mu, sg, ln = np.zeros((8, DIAG_MAX_DIM)), np.zeros((8, DIAG_MAX_DIM)), np.zeros(8)
         self._chk(self.L.cpprob_hip_batch_copy_diag(self.h, int(b), mu.ctypes.data, sg.ctypes.data, ln.ctypes.data))
         return mu[:k, :D].copy(), sg[:k, :D].copy(), ln[:k].copy()
+
+    # ---- full-covariance Gaussian vector emissions (include/cpprob_hip.h: cpprob_hip_batch_*_full, _full_stats*; csrc/batch_full.hpp) ----
+    def _batch_full_tables(self, means, covs, trans, B):
+        mu = np.ascontiguousarray(means, np.float64)
+        cv = np.ascontiguousarray(covs, np.float64)
+        tr = np.ascontiguousarray(trans, np.float64)
+        if mu.ndim != 3 or mu.shape[0] != B or cv.shape != mu.shape + mu.shape[2:] or tr.shape != (B, mu.shape[1], mu.shape[1]):
+            raise ValueError("means [B, k, D], covs [B, k, D, D] and transition [B, k, k]")
+        return mu, cv, tr
+
+    def batch_begin_problems_full(self, observes, n_particles, means, covs, trans, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, keep_masses=False, max_particles=None):
+        """A MODEL_HMM_TABLE batch whose observe of a step is a vector with a full covariance (cpprob_hip_batch_begin_problems_full):
+        observes a list of [T_b, D] arrays, means [B, k, D], covs [B, k, D, D] (state s of problem b emits N(means[b, s], covs[b, s]);
+        the lower triangle is read), trans [B, k, k]; k <= 8, D <= 16.  Everything else as batch_begin_problems."""
+        mu, cv, tr = self._batch_full_tables(means, covs, trans, len(observes))
+        D = mu.shape[2]
+        seqs = [np.ascontiguousarray(o, np.float64) for o in observes]
+        seqs = [o.reshape(-1, 1) if o.ndim == 1 else o for o in seqs]
+        if 1 <= D <= FULL_MAX_DIM and any(o.ndim != 2 or o.shape[1] != D for o in seqs):      # (another D: the library's own refusal)
+            raise ValueError("observes: one [T_b, D] array a problem")
+        h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
+        flat = self._batch_packed_observes(seqs)
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(MODEL_HMM_TABLE, top, len(seqs), resampler, 2.0, keep_history, ALG_SMC, _batch_flags(0, keep_masses))
+        self._chk(self.L.cpprob_hip_batch_begin_problems_full(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                              flat.ctypes.data_as(C.POINTER(C.c_double)), mu.shape[1], mu.shape[2], mu.ctypes.data, cv.ctypes.data, tr.ctypes.data))
+        self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
+        self.batch_K, self.batch_k, self.batch_D = 8, mu.shape[1], D
+        self.batch_shapes = (h_T, h_n)
+        return self
+
+    def batch_retable_full(self, means, covs, trans, observes=None):
+        """New means, covariances and transition rows for the begun full batch where it stands (cpprob_hip_batch_retable_full),
+        validated as the begin validates them; observes as the begin takes them, or None once a re-table has staged them."""
+        mu, cv, tr = self._batch_full_tables(means, covs, trans, self.batch_B)
+        flat = None if observes is None else self._batch_packed_observes(list(observes))
+        n_obs = int(np.sum(self.batch_shapes[0], dtype=np.int64)) * getattr(self, "batch_D", 1) if flat is None else flat.size
+        self._chk(self.L.cpprob_hip_batch_retable_full(self.h, mu.ctypes.data, cv.ctypes.data, tr.ctypes.data, None if flat is None or flat.size == 0 else flat.ctypes.data, n_obs))
+
+    def batch_retable_full_device(self, means, covs, trans, observes):
+        """The same between torch float64 device tensors (means [B, k, D], covs [B, k, D, D], trans [B, k, k], observes packed, D
+        doubles a step), enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status: bit 4,
+        a mean that is not finite; bit 64, a covariance that does not factor)."""
+        self._chk(self.L.cpprob_hip_batch_retable_full_device(self.h, _dptr(means), _dptr(covs), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+
+    def batch_full_stats(self, observes):
+        """The E-step of a full batch (cpprob_hip_batch_full_stats): batch_smooth_stats' dict with coordinate 0 as the observe, sy
+        [B, 8, 16], the expected visits of state s weighted by y_t[d], and syy [B, 8, 16, 16], those weighted by y_t[i] y_t[j],
+        unpacked and symmetric."""
+        rec = np.zeros((self.batch_B, FULL_STATS_PER_PROBLEM))
+        flat = self._batch_packed_observes(list(observes))
+        self._chk(self.L.cpprob_hip_batch_full_stats(self.h, flat.ctypes.data if flat.size else None, flat.size, rec.ctypes.data, rec.size))
+        return split_full_stats(rec)
+
+    def batch_full_stats_device(self, stats, observes):
+        """The same left in a device tensor: stats torch float64 [B, 1304], observes a torch float64 tensor packed problem after
+        problem, D doubles a step."""
+        self._chk(self.L.cpprob_hip_batch_full_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    def batch_mstep_full_device(self, stats, means, covs, trans, var_floor=1e-6):
+        """full.m_step_full on the device (cpprob_hip_batch_mstep_full_device): stats torch float64 [B, 1304]; means [B, k, D], covs
+        [B, k, D, D] and trans [B, k, k] torch float64, updated in place; no fitted variance below var_floor^2.  Enqueued."""
+        self._chk(self.L.cpprob_hip_batch_mstep_full_device(self.h, _dptr(stats), stats.numel(), _dptr(means), _dptr(covs), _dptr(trans), float(var_floor)))
+
+    def batch_copy_full(self, b, k=None, D=None):
+        """(means [k, D], factors [k, D, D] lower-triangular, log_norms [k]) of problem b of a full batch, as the device holds them
+        (cpprob_hip_batch_copy_full).  Synchronises.  For tests."""
+        k, D = int(k if k is not None else self.batch_k), int(D if D is not None else getattr(self, "batch_D", 1))
+        mu, tri, ln = np.zeros((8, FULL_MAX_DIM)), np.zeros((8, FULL_TRI)), np.zeros(8)
+        self._chk(self.L.cpprob_hip_batch_copy_full(self.h, int(b), mu.ctypes.data, tri.ctypes.data, ln.ctypes.data))
+        L = np.zeros((8, FULL_MAX_DIM, FULL_MAX_DIM))
+        L[:, _FULL_I, _FULL_J] = tri
+        return mu[:k, :D].copy(), L[:k, :D, :D].copy(), ln[:k].copy()
 
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):

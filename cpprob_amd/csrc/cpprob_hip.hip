@@ -33,6 +33,7 @@
 #include "batch_poisson.hpp"
 #include "batch_categorical.hpp"
 #include "batch_diag.hpp"
+#include "batch_full.hpp"
 #include "batch_learn.hpp"
 #include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
@@ -1050,6 +1051,34 @@ __attribute__((noinline)) void diag_expand_tables(size_t B, int k, int D, const 
             log_norm[b * 8 + s] = diag_log_norm(ln, D, 1);
         }
 }
+// ... or a vector with a full covariance (csrc/batch_full.hpp): the sixth family, begun, re-tabled and fitted by its own calls
+constexpr EmissionFamily kFamilyFull = (EmissionFamily)5;
+// a full-covariance problem's rows, with the statements the device's re-table writes them with: mean [8][16], L [8][136] packed,
+// log_norm [8] (kept out of line: batch_begin's own loop stays the other families')
+__attribute__((noinline)) void full_problem_rows(const double* y, size_t T, int D, const double* mean, const double* L, const double* log_norm, int k, double* rows)
+{
+    for (size_t t = 0; t < T; ++t)
+        for (int s2 = 0; s2 < 8; ++s2)
+            rows[t * kBatchTab + s2] = s2 < k ? full_entry(y + t * (size_t)D, D, mean + (size_t)s2 * kFullMaxDim, 1, L + (size_t)s2 * kFullTri, 1, log_norm[s2]) : -INFINITY;
+}
+// the tables of a full begin (means [B][k][D], covs [B][k][D][D], checked: every covariance factors) in the device's layout, [B][8][16],
+// [B][8][136] and [B][8]: slots outside the table 0.0
+__attribute__((noinline)) void full_expand_tables(size_t B, int k, int D, const double* h_means, const double* h_covs, std::vector<double>& mean, std::vector<double>& L,
+                                                  std::vector<double>& log_norm)
+{
+    mean.assign(B * kFullMeanSlots, 0.0); L.assign(B * kFullTriSlots, 0.0); log_norm.assign(B * 8, 0.0);
+    for (size_t b = 0; b < B; ++b)
+        for (size_t s = 0; s < (size_t)k; ++s) {
+            double* Ls = &L[b * kFullTriSlots + s * kFullTri];
+            const double* cov = h_covs + (b * (size_t)k + s) * (size_t)D * (size_t)D;
+            for (int i = 0; i < D; ++i) {
+                mean[b * kFullMeanSlots + s * kFullMaxDim + (size_t)i] = h_means[(b * (size_t)k + s) * (size_t)D + (size_t)i];
+                for (int j = 0; j <= i; ++j) Ls[full_tri(i, j)] = cov[(size_t)i * D + j];
+            }
+            (void)full_factor(Ls, 1, D, Ls, 1);
+            log_norm[b * 8 + s] = full_log_norm(Ls, 1, D);
+        }
+}
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
 {
     std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
@@ -1232,6 +1261,15 @@ struct BatchState {
     DeviceBuffer d_diag_mean, d_diag_sigma, d_diag_lognorm;
     const double *diag_begin_means = nullptr, *diag_begin_sigmas = nullptr;
     int diag_begin_D = 0;
+    // full-covariance Gaussian vector emissions (cpprob_hip_batch_begin_problems_full; csrc/batch_full.hpp): full: the begun batch has
+    // them, and is then of no other family; full_D its coordinates, and every observes array of its calls holds full_D doubles a step.
+    // The means [B][8][16], packed factors [B][8][136] and log_norms [B][8] in force are the device's alone, as a diagonal batch's; d_full_g
+    // is the E-step's workspace, the walk's marginals [steps][8].  full_begin_*: the checked arguments of the begin in progress
+    bool full = false;
+    int full_D = 0;
+    DeviceBuffer d_full_mean, d_full_L, d_full_lognorm, d_full_g;
+    const double *full_begin_means = nullptr, *full_begin_covs = nullptr;
+    int full_begin_D = 0;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
@@ -1415,7 +1453,17 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, bs->d_diag_sigma.grow(c->stream, dg_sigma.size() * sizeof(double)));
         HIP_TRY(c, bs->d_diag_lognorm.grow(c->stream, dg_lognorm.size() * sizeof(double)));
     }
-    const size_t obs_stride = diag ? (size_t)diag_D : 1;        // doubles a step of h_obs
+    const bool full = family == kFamilyFull;                    // (as a diagonal begin: the tables are bs->full_begin_*)
+    bs->full = false;
+    std::vector<double> fl_mean, fl_L, fl_lognorm;              // (live until the synchronisation below)
+    const int full_D = full ? bs->full_begin_D : 0;
+    if (full) {
+        full_expand_tables((size_t)B, k, full_D, bs->full_begin_means, bs->full_begin_covs, fl_mean, fl_L, fl_lognorm);
+        HIP_TRY(c, bs->d_full_mean.grow(c->stream, fl_mean.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_full_L.grow(c->stream, fl_L.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_full_lognorm.grow(c->stream, fl_lognorm.size() * sizeof(double)));
+    }
+    const size_t obs_stride = diag ? (size_t)diag_D : full ? (size_t)full_D : 1;    // doubles a step of h_obs
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
@@ -1428,7 +1476,8 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         if (online && own) { bs->means.insert(bs->means.end(), mean.begin(), mean.end()); bs->trans.insert(bs->trans.end(), trans.begin(), trans.end()); }
         // (a diagonal batch: a row loop of its own, obs_stride doubles a step; at_obs counts steps)
         if (diag) diag_problem_rows(h_obs + at_obs * obs_stride, T_b, diag_D, &dg_mean[b * kDiagSlots], &dg_sigma[b * kDiagSlots], &dg_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
-        for (size_t t = 0; t < (online || diag ? 0 : T_b); ++t) {
+        if (full) full_problem_rows(h_obs + at_obs * obs_stride, T_b, full_D, &fl_mean[b * kFullMeanSlots], &fl_L[b * kFullTriSlots], &fl_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
+        for (size_t t = 0; t < (online || diag || full ? 0 : T_b); ++t) {
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
@@ -1465,6 +1514,11 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, hipMemcpyAsync(bs->d_diag_sigma.as<double>(), dg_sigma.data(), dg_sigma.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_diag_lognorm.as<double>(), dg_lognorm.data(), dg_lognorm.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
+    if (full) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_full_mean.as<double>(), fl_mean.data(), fl_mean.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_full_L.as<double>(), fl_L.data(), fl_L.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_full_lognorm.as<double>(), fl_lognorm.data(), fl_lognorm.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
     if (online) {
@@ -1497,6 +1551,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->online = online; bs->walked = true; bs->own_tables = own; bs->scaled = scaled; bs->poisson = poisson;
     bs->categorical = categorical; bs->cat_V = cat_V;
     bs->diag = diag; bs->diag_D = diag_D;
+    bs->full = full; bs->full_D = full_D;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -5336,6 +5391,7 @@ static int batch_smooth_stats_check(cpprob_hip_ctx* c, bool with_obs, size_t n_o
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
     if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its statistics are cpprob_hip_batch_diag_stats / _diag_stats_device");
+    if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its statistics are cpprob_hip_batch_full_stats / _full_stats_device");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     rows = 0;
@@ -5440,6 +5496,7 @@ static int batch_traj_stats_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t d
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_check(c, n_traj, draw_index, false, 0, false, 0, doubles, entries)) return rc;
     if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
+    if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (n_traj == 0) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 1 .. 2^20");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
@@ -5742,7 +5799,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "re-tabling serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
     const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
-    const bool categorical = family == kFamilyCategorical, diag = family == kFamilyDiag;
+    const bool categorical = family == kFamilyCategorical, diag = family == kFamilyDiag, full = family == kFamilyFull;
+    if (bs->full && !full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: it is re-tabled by cpprob_hip_batch_retable_full / _retable_full_device");
+    if (!bs->full && full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions: begin it with cpprob_hip_batch_begin_problems_full, or re-table it with its own family's calls");
     if (bs->diag && !diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: it is re-tabled by cpprob_hip_batch_retable_diag / _retable_diag_device");
     if (!bs->diag && diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has no diagonal-Gaussian vector emissions: begin it with cpprob_hip_batch_begin_problems_diag, or re-table it with its own family's calls");
     if (bs->categorical && !categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: it is re-tabled by cpprob_hip_batch_retable_categorical / _retable_categorical_device");
@@ -5755,7 +5814,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
     if (diag && (uint64_t)n_observes != rows * (uint64_t)bs->diag_D)
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->diag_D) + " doubles");
-    if (!diag && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    if (full && (uint64_t)n_observes != rows * (uint64_t)bs->full_D)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->full_D) + " doubles");
+    if (!diag && !full && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
     return 0;
 }
 
@@ -5778,6 +5839,14 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
         r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
+    if (bs->full) {
+        // (a full-covariance batch: d_means [B][k][D] and d_sigmas the covariances [B][k][D][D]; the tables in force are the device's)
+        BatchRetableFullArgs fa{};
+        common(fa);
+        fa.means = d_means; fa.covs = d_sigmas; fa.D = bs->full_D;
+        fa.mean_out = bs->d_full_mean.as<double>(); fa.L_out = bs->d_full_L.as<double>(); fa.log_norm_out = bs->d_full_lognorm.as<double>();
+        hipLaunchKernelGGL(batch_retable_full_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, fa);
+    } else
     if (bs->diag) {
         // (a diagonal batch: d_means [B][k][D] and d_sigmas [B][k][D]; the tables in force are the device's; the first entries count steps)
         BatchRetableDiagArgs da{};
@@ -5948,6 +6017,7 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
     if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
     if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_diag_device");
+    if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_full_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: its M-step is cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its M-step is cpprob_hip_batch_mstep_poisson_device");
     if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: its M-step is cpprob_hip_batch_mstep_device / _mstep_scaled_device");
@@ -6006,6 +6076,7 @@ int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* c, const double* d_stats
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the draw samples the tables of CPPROB_HIP_MODEL_HMM_TABLE");
     if (!bs->own_tables) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the batch was begun with the context's shared table: begin it with per-problem tables to draw them");
     if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_diag_device");
+    if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_full_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: the conjugate (Dirichlet) draw of its matrix is not built -- fit it with cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: the conjugate (gamma) draw of its rates is not built -- fit it with cpprob_hip_batch_mstep_poisson_device");
     if (bs->scaled && !d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its draw takes d_sigmas");
@@ -6504,6 +6575,181 @@ int cpprob_hip_batch_copy_diag(cpprob_hip_ctx* c, uint64_t problem, double* h_me
     if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_diag_mean.as<double>() + problem * kDiagSlots, bytes, hipMemcpyDeviceToHost, c->stream));
     if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_diag_sigma.as<double>() + problem * kDiagSlots, bytes, hipMemcpyDeviceToHost, c->stream));
     if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_diag_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- full-covariance Gaussian vector emissions of a batch (csrc/batch_full.hpp) ------------------------------------------------------
+// Means and covariances on the host ([B][k][D], [B][k][D][D]): every mean finite (full_check's bit 4), every covariance one full_factor
+// takes (bit 64), by name.
+static int batch_check_full(cpprob_hip_ctx* c, uint64_t B, int k, int D, const double* h_means, const double* h_covs, const double* h_transition)
+{
+    const size_t kd = (size_t)k * (size_t)D;
+    for (uint64_t b = 0; b < B; ++b) {
+        const int bits = full_check(h_means + b * kd, h_covs + b * kd * (size_t)D, h_transition + b * (size_t)k * (size_t)k, k, D);
+        if (bits & kRetableBadMean) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": state means must be finite");
+        if (bits & kRetableBadCov)
+            return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": a covariance does not factor (lower triangle finite, pivots > 0 with a normal finite 2 pi pivot^2)");
+    }
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems_full(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
+                                         int32_t k_in, int32_t D, const double* h_means, const double* h_covs, const double* h_transition)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_means || !h_covs || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "full-covariance Gaussian vector emissions serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    if (D < 1 || D > kFullMaxDim) return fail(c, CPPROB_HIP_EINVAL, "D, the coordinates of an observe, must lie in 1 .. 16");
+    if (k_in < 1 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "k must lie in 1 .. 8");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    if (int rc = batch_check_full(c, cfg->n_problems, k_in, D, h_means, h_covs, h_transition)) return rc;
+    // (the begin's route takes means [B][k]: zeros, which no full row reads; the tables travel beside them)
+    const std::vector<double> zeros((size_t)cfg->n_problems * (size_t)k_in, 0.0);
+    if (!c->batch) c->batch = new BatchState();
+    c->batch->full_begin_means = h_means; c->batch->full_begin_covs = h_covs; c->batch->full_begin_D = D;
+    const int rc = batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, zeros.data(), h_transition, nullptr, nullptr, kFamilyFull);
+    c->batch->full_begin_means = nullptr; c->batch->full_begin_covs = nullptr; c->batch->full_begin_D = 0;
+    return rc;
+}
+
+int cpprob_hip_batch_retable_full_device(cpprob_hip_ctx* c, const double* d_means, const double* d_covs, const double* d_transition, const double* d_observes,
+                                         size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyFull)) return rc;
+    if (!d_means || !d_covs || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_means, d_transition, d_observes, d_covs);
+}
+
+// The host form: the tables are validated with the begin's own statements, staged -- the means and the covariances in front, the
+// transition rows at the back -- and re-tabled as by the device form.
+int cpprob_hip_batch_retable_full(cpprob_hip_ctx* c, const double* h_means, const double* h_covs, const double* h_transition, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyFull)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_means || !h_covs || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    const size_t B = bs->cfg.n_problems, kk = (size_t)bs->hk * bs->hk, kd = (size_t)bs->hk * (size_t)bs->full_D, kdd = kd * (size_t)bs->full_D;
+    int k = 0;
+    const std::vector<double> zeros(B * (size_t)bs->hk, 0.0);
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, zeros.data(), h_transition, k)) return rc;
+    if (int rc = batch_check_full(c, B, k, bs->full_D, h_means, h_covs, h_transition)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_observes) if (int rc = batch_retable_observes(c, h_observes, n_observes)) return rc;
+    double *d_means = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(B * (kd + kdd) * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
+    double* d_covs = d_means + B * kd;
+    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * kd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_covs, h_covs, B * kdd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs.as<double>(), d_covs)) return rc;
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    bs->thr_stale = false;
+    return 0;
+}
+
+// cpprob_hip_batch_full_stats' arguments against the batch's state (batch_diag_stats_check's).
+static int batch_full_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& n_obs)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
+    BatchState* bs = c->batch;
+    if (!bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions (cpprob_hip_batch_begin_problems_full): its statistics are its own family's");
+    if (!stats || !observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    uint64_t rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    n_obs = rows * (uint64_t)bs->full_D;
+    if ((uint64_t)n_observes != n_obs)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->full_D) + " doubles");
+    const uint64_t need = (uint64_t)bs->cfg.n_problems * (uint64_t)kFullStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (1304 a problem)");
+    return 0;
+}
+
+// The pass: batch_diag_stats_enqueue's prologue, then the walk (the 88 doubles and the marginals of every step into the workspace, a
+// row a step of the batch) and the moments (sy and syy from the workspace and the observes).
+static int batch_full_stats_enqueue(cpprob_hip_ctx* c, const double* d_obs, double* d_stats)
+{
+    BatchState* bs = c->batch;
+    BatchPassPlan pl; BatchSmoothArgs a{};
+    if (int rc = batch_pass_prologue(c, BatchPass::stats(d_obs, d_stats), pl, a)) return rc;
+    if (pl.done) {                                                          // (no problem has a step: every record is zeros)
+        HIP_TRY(c, hipMemsetAsync(d_stats, 0, (size_t)bs->cfg.n_problems * kFullStats * sizeof(double), c->stream));
+        return 0;
+    }
+    uint64_t rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    HIP_TRY(c, bs->d_full_g.grow(c->stream, (size_t)rows * 8 * sizeof(double)));
+    BatchFullStatsArgs sa{};
+    sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = d_obs; sa.g = bs->d_full_g.as<double>(); sa.stats = d_stats;
+    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->full_D; sa.thr_stride = a.thr_stride;
+    hipLaunchKernelGGL(batch_full_walk_kernel, dim3(std::min<unsigned>(pl.stats_gx, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(batch_full_moments_kernel, dim3(std::min<unsigned>((unsigned)sa.B, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_full_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_full_stats_check(c, d_observes, n_observes, d_stats, n_doubles, n_obs)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_full_stats_enqueue(c, d_observes, d_stats);
+}
+
+int cpprob_hip_batch_full_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_full_stats_check(c, h_observes, n_observes, h_stats, n_doubles, n_obs)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kFullStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)n_obs, d_stats, d_obs)) return rc;
+    if (int rc = batch_full_stats_enqueue(c, d_obs, d_stats)) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
+}
+
+int cpprob_hip_batch_mstep_full_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_means, double* d_covs, double* d_transition, double var_floor)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions: its M-step is its own family's");
+    if (!d_stats || !d_means || !d_covs || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!(var_floor > 0.0) || !std::isfinite(var_floor)) return fail(c, CPPROB_HIP_EINVAL, "var_floor must be finite and > 0");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kFullStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (1304 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepFullArgs a{};
+    a.stats = d_stats; a.means = d_means; a.covs = d_covs; a.trans = d_transition; a.floor = var_floor; a.B = (int64_t)B; a.k = bs->hk; a.D = bs->full_D;
+    hipLaunchKernelGGL(batch_mstep_full_kernel, dim3((unsigned)((B * (uint64_t)bs->hk + kFullMstepThreads - 1) / kFullMstepThreads)), dim3(kFullMstepThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_full(cpprob_hip_ctx* c, uint64_t problem, double* h_means, double* h_factors, double* h_log_norms)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions (cpprob_hip_batch_begin_problems_full)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_full_mean.as<double>() + problem * kFullMeanSlots, kFullMeanSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_factors) HIP_TRY(c, hipMemcpyAsync(h_factors, bs->d_full_L.as<double>() + problem * kFullTriSlots, kFullTriSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_full_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }

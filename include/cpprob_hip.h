@@ -1019,6 +1019,48 @@ int cpprob_hip_batch_mstep_diag_device(cpprob_hip_ctx* ctx, const double* d_stat
                                        double* d_transition, double sigma_floor);
 int cpprob_hip_batch_copy_diag(cpprob_hip_ctx* ctx, uint64_t problem, double* h_means, double* h_sigmas, double* h_log_norms);
 
+/* ---- full-covariance Gaussian vector emissions of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_full.hpp) --
+ * State s of problem b emits a vector y in R^D, 1 <= D <= 16, y ~ N(mean[b][s], cov[b][s]): means [B][k][D], covs [B][k][D][D] of which
+ * only the lower triangle (i >= j) is read, the observes D doubles a step (n_observes counts doubles: D times the sum of the lengths).
+ * A batch is unit, scaled, Poisson, categorical, diagonal or full, never two of them: every call of one family on a batch of another
+ * returns CPPROB_HIP_ESTATE and the batch stays.  A full batch is run, smoothed, counted, forecast and decoded by the calls above as
+ * they are.  A covariance is taken through its Cholesky factor L, column by column (csrc/batch_full.hpp: full_factor); a row is
+ * -0.5 (|z|^2 + log_norm[s]) with z the forward substitution L z = y - mean, every division a real one, and
+ * log_norm[s] = the sum over d of log(2 pi L[d][d]^2), ascending.  With diagonal covariances sigma^2 the rows and log_norms are a
+ * diagonal batch's bits, at D = 1 a scaled batch's.  tests/full_ref.py restates every statement.
+ * cpprob_hip_batch_begin_problems_full: cpprob_hip_batch_begin_problems with D, the means and the covariances.  D outside 1 .. 16, k
+ * outside 1 .. 8, a mean that is not finite, or a covariance that does not factor (an entry of the lower triangle not finite, a pivot
+ * not > 0 or one the scaled calls refuse as a sigma): CPPROB_HIP_EINVAL, by problem.  There is no online full begin.
+ * cpprob_hip_batch_retable_full_device / _retable_full: cpprob_hip_batch_retable_diag_device / _retable_diag with the covariances.  The
+ * device form checks on the device: bit 64 of cpprob_hip_batch_retable_status, a covariance that does not factor; that problem keeps
+ * rows, thresholds and tables.
+ * cpprob_hip_batch_full_stats_device / _full_stats: the E-step.  1304 doubles a problem: the first 88 are the record of
+ * cpprob_hip_batch_smooth_stats with coordinate 0 as the observe; sy[s][d] = sum over t of g_t[s] y_t[d] at 88 + 16 s + d;
+ * syy[s][i][j] = sum over t of g_t[s] (y_t[i] y_t[j]), j <= i, at 216 + 136 s + i (i + 1) / 2 + j; slots outside (k, D) are 0.0.  Two
+ * kernels: the backward walk leaves every step's marginals in a workspace of the context's own, the moments are formed from it.
+ * cpprob_hip_batch_mstep_full_device: on d_means [B][k][D], d_covs [B][k][D][D] and d_transition [B][k][k] in place, from records of
+ * 1304 doubles.  A state with mass: mean' = sy / occ, c[i][j] = syy[i][j] / occ - mean'_i mean'_j, a diagonal entry not below
+ * var_floor^2 (a NaN takes it too); a candidate that does not factor leaves the state's mean and covariance as they were, as a state
+ * without mass; else both triangles are written.  var_floor finite and > 0, else CPPROB_HIP_EINVAL.  cpprob_amd.full.m_step_full, bit
+ * for bit.  Enqueued.
+ * On a full batch the other families' re-tables, statistics and M-steps and cpprob_hip_batch_draw_tables_device return
+ * CPPROB_HIP_ESTATE; cpprob_hip_batch_learn_begin* and _online_tables* do so because the batch is not online.
+ * cpprob_hip_batch_copy_full: problem `problem`'s means [8][16], packed factors [8][136] (entry (i, j) at i (i + 1) / 2 + j) and
+ * log_norms [8] in force as the device holds them (slots outside the table 0.0; any may be NULL); synchronises; CPPROB_HIP_ESTATE: no
+ * batch begun, or no full batch.  For tests. */
+int cpprob_hip_batch_begin_problems_full(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                         const double* h_observes, int32_t k, int32_t D, const double* h_means, const double* h_covs,
+                                         const double* h_transition);
+int cpprob_hip_batch_retable_full_device(cpprob_hip_ctx* ctx, const double* d_means, const double* d_covs, const double* d_transition,
+                                         const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_full(cpprob_hip_ctx* ctx, const double* h_means, const double* h_covs, const double* h_transition,
+                                  const double* h_observes, size_t n_observes);
+int cpprob_hip_batch_full_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+int cpprob_hip_batch_full_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+int cpprob_hip_batch_mstep_full_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_means, double* d_covs,
+                                       double* d_transition, double var_floor);
+int cpprob_hip_batch_copy_full(cpprob_hip_ctx* ctx, uint64_t problem, double* h_means, double* h_factors, double* h_log_norms);
+
 /* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
  * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
  * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
