@@ -15,6 +15,7 @@ from .em import hmm_table_em, m_step, pool_stats  # noqa: F401
 from .categorical import hmm_categorical_em, m_step_categorical  # noqa: F401
 from .diag import hmm_diag_em, m_step_diag  # noqa: F401
 from .full import hmm_full_em, m_step_full  # noqa: F401
+from .mix import hmm_mix_em, m_step_mix  # noqa: F401
 from . import online_em  # noqa: F401
 from .online_em import hmm_table_online_em  # noqa: F401
 from . import gibbs  # noqa: F401

@@ -67,6 +67,9 @@ SYMBOLS = [
     "cpprob_hip_batch_diag_stats", "cpprob_hip_batch_diag_stats_device", "cpprob_hip_batch_mstep_diag_device", "cpprob_hip_batch_copy_diag",
     "cpprob_hip_batch_begin_problems_full", "cpprob_hip_batch_retable_full", "cpprob_hip_batch_retable_full_device",
     "cpprob_hip_batch_full_stats", "cpprob_hip_batch_full_stats_device", "cpprob_hip_batch_mstep_full_device", "cpprob_hip_batch_copy_full",
+    "cpprob_hip_table_exp", "cpprob_hip_mix_rows",
+    "cpprob_hip_batch_begin_problems_mix", "cpprob_hip_batch_retable_mix", "cpprob_hip_batch_retable_mix_device",
+    "cpprob_hip_batch_mix_stats", "cpprob_hip_batch_mix_stats_device", "cpprob_hip_batch_mstep_mix_device", "cpprob_hip_batch_copy_mix",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
@@ -232,6 +235,8 @@ DIAG_MAX_DIM = 32                             # cpprob_hip_batch_begin_problems_
 FULL_MAX_DIM = 16                             # cpprob_hip_batch_begin_problems_full: D in 1 ..=
 FULL_TRI = 136                                # the packed lower triangle of a state: entry (i, j), j <= i, at i (i + 1) / 2 + j
 FULL_STATS_PER_PROBLEM = 1304                 # doubles a problem of cpprob_hip_batch_full_stats: the 88 above, sy[8][16], syy[8][136]
+MIX_MAX_DIM, MIX_MAX_COMP = 16, 8             # cpprob_hip_batch_begin_problems_mix: D and M in 1 ..=
+MIX_STATS_PER_PROBLEM = 88 + 64 * 33          # doubles a problem of cpprob_hip_batch_mix_stats: the 88 above, then occ_c, sy[16], syy[16] of every (s, c)
 DIAG_STATS_PER_PROBLEM = 88 + 8 * 2 * 32      # doubles a problem of cpprob_hip_batch_diag_stats: the 88 above, then sy[32] and syy[32] of every state
 
 
@@ -260,6 +265,18 @@ def split_full_stats(rec):
     syy[:, :, _FULL_I, _FULL_J] = tri
     syy[:, :, _FULL_J, _FULL_I] = tri
     out["syy"] = syy
+    return out
+
+
+def split_mix_stats(rec):
+    """The records [B, 2200] of cpprob_hip_batch_mix_stats as a dict: split_stats' entries, occ_c [B, 8, 8] (the expected visits of
+    component c of state s), sy and syy [B, 8, 8, 16] (those weighted by y_t[d] and by y_t[d]^2)."""
+    rec = np.asarray(rec, np.float64).reshape(-1, MIX_STATS_PER_PROBLEM)
+    out = split_stats(np.ascontiguousarray(rec[:, :STATS_PER_PROBLEM]))
+    blocks = rec[:, STATS_PER_PROBLEM:].reshape(-1, 8, MIX_MAX_COMP, 1 + 2 * MIX_MAX_DIM)
+    out["occ_c"] = np.ascontiguousarray(blocks[..., 0])
+    out["sy"] = np.ascontiguousarray(blocks[..., 1:1 + MIX_MAX_DIM])
+    out["syy"] = np.ascontiguousarray(blocks[..., 1 + MIX_MAX_DIM:])
     return out
 
 
@@ -488,6 +505,15 @@ def load_library(path=None):
         "cpprob_hip_batch_full_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_mstep_full_device": (C.c_int, [vp, vp, sz, vp, vp, vp, dbl]),
         "cpprob_hip_batch_copy_full": (C.c_int, [vp, u64, vp, vp, vp]),
+        "cpprob_hip_table_exp": (dbl, [dbl]),
+        "cpprob_hip_mix_rows": (C.c_int, [vp, sz, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]),
+        "cpprob_hip_batch_begin_problems_mix": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]),
+        "cpprob_hip_batch_retable_mix": (C.c_int, [vp, vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_mix_device": (C.c_int, [vp, vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_mix_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_mix_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_mstep_mix_device": (C.c_int, [vp, vp, sz, vp, vp, vp, vp, dbl]),
+        "cpprob_hip_batch_copy_mix": (C.c_int, [vp, u64, vp, vp, vp, vp]),
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
@@ -1231,6 +1257,80 @@ class Engine:
         L = np.zeros((8, FULL_MAX_DIM, FULL_MAX_DIM))
         L[:, _FULL_I, _FULL_J] = tri
         return mu[:k, :D].copy(), L[:k, :D, :D].copy(), ln[:k].copy()
+
+    # ---- Gaussian-mixture vector emissions (include/cpprob_hip.h: cpprob_hip_batch_*_mix, _mix_stats*; csrc/batch_mix.hpp) ----
+    def _batch_mix_tables(self, weights, means, sigmas, trans, B):
+        w = np.ascontiguousarray(weights, np.float64)
+        mu = np.ascontiguousarray(means, np.float64)
+        sg = np.ascontiguousarray(sigmas, np.float64)
+        tr = np.ascontiguousarray(trans, np.float64)
+        if mu.ndim != 4 or mu.shape[0] != B or sg.shape != mu.shape or w.shape != mu.shape[:3] or tr.shape != (B, mu.shape[1], mu.shape[1]):
+            raise ValueError("weights [B, k, M], means and sigmas [B, k, M, D] and transition [B, k, k]")
+        return w, mu, sg, tr
+
+    def batch_begin_problems_mix(self, observes, n_particles, weights, means, sigmas, trans, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, keep_masses=False,
+                                 max_particles=None):
+        """A MODEL_HMM_TABLE batch whose observe of a step is a vector from a Gaussian mixture (cpprob_hip_batch_begin_problems_mix):
+        observes a list of [T_b, D] arrays, weights [B, k, M], means and sigmas [B, k, M, D] (state s of problem b emits component c
+        with probability weights[b, s, c] / their sum, independent coordinates N(means[b, s, c, d], sigmas[b, s, c, d])), trans
+        [B, k, k]; k <= 8, M <= 8, D <= 16.  Everything else as batch_begin_problems."""
+        w, mu, sg, tr = self._batch_mix_tables(weights, means, sigmas, trans, len(observes))
+        M, D = mu.shape[2], mu.shape[3]
+        seqs = [np.ascontiguousarray(o, np.float64) for o in observes]
+        seqs = [o.reshape(-1, 1) if o.ndim == 1 else o for o in seqs]
+        if 1 <= D <= MIX_MAX_DIM and any(o.ndim != 2 or o.shape[1] != D for o in seqs):       # (another D: the library's own refusal)
+            raise ValueError("observes: one [T_b, D] array a problem")
+        h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
+        flat = self._batch_packed_observes(seqs)
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(MODEL_HMM_TABLE, top, len(seqs), resampler, 2.0, keep_history, ALG_SMC, _batch_flags(0, keep_masses))
+        self._chk(self.L.cpprob_hip_batch_begin_problems_mix(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                             flat.ctypes.data_as(C.POINTER(C.c_double)), mu.shape[1], M, D, w.ctypes.data, mu.ctypes.data, sg.ctypes.data, tr.ctypes.data))
+        self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
+        self.batch_K, self.batch_k, self.batch_D, self.batch_M = 8, mu.shape[1], D, M
+        self.batch_shapes = (h_T, h_n)
+        return self
+
+    def batch_retable_mix(self, weights, means, sigmas, trans, observes=None):
+        """New weights, means, sigmas and transition rows for the begun mixture batch where it stands (cpprob_hip_batch_retable_mix),
+        validated as the begin validates them; observes as the begin takes them, or None once a re-table has staged them."""
+        w, mu, sg, tr = self._batch_mix_tables(weights, means, sigmas, trans, self.batch_B)
+        flat = None if observes is None else self._batch_packed_observes(list(observes))
+        n_obs = int(np.sum(self.batch_shapes[0], dtype=np.int64)) * getattr(self, "batch_D", 1) if flat is None else flat.size
+        self._chk(self.L.cpprob_hip_batch_retable_mix(self.h, w.ctypes.data, mu.ctypes.data, sg.ctypes.data, tr.ctypes.data, None if flat is None or flat.size == 0 else flat.ctypes.data, n_obs))
+
+    def batch_retable_mix_device(self, weights, means, sigmas, trans, observes):
+        """The same between torch float64 device tensors (weights [B, k, M], means and sigmas [B, k, M, D], trans [B, k, k], observes
+        packed, D doubles a step), enqueued without a host synchronisation; the tables are checked on the device
+        (batch_retable_status: bits 4 and 8 as for a diagonal batch; bit 128, a refused mixture weight)."""
+        self._chk(self.L.cpprob_hip_batch_retable_mix_device(self.h, _dptr(weights), _dptr(means), _dptr(sigmas), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+
+    def batch_mix_stats(self, observes):
+        """The E-step of a mixture batch (cpprob_hip_batch_mix_stats): batch_smooth_stats' dict with coordinate 0 as the observe,
+        occ_c [B, 8, 8], the expected visits of component c of state s, and sy, syy [B, 8, 8, 16], those weighted by y_t[d] and
+        y_t[d]^2."""
+        rec = np.zeros((self.batch_B, MIX_STATS_PER_PROBLEM))
+        flat = self._batch_packed_observes(list(observes))
+        self._chk(self.L.cpprob_hip_batch_mix_stats(self.h, flat.ctypes.data if flat.size else None, flat.size, rec.ctypes.data, rec.size))
+        return split_mix_stats(rec)
+
+    def batch_mix_stats_device(self, stats, observes):
+        """The same left in a device tensor: stats torch float64 [B, 2200], observes a torch float64 tensor packed problem after
+        problem, D doubles a step."""
+        self._chk(self.L.cpprob_hip_batch_mix_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    def batch_mstep_mix_device(self, stats, weights, means, sigmas, trans, sigma_floor=1e-6):
+        """mix.m_step_mix on the device (cpprob_hip_batch_mstep_mix_device): stats torch float64 [B, 2200]; weights [B, k, M], means
+        and sigmas [B, k, M, D] and trans [B, k, k] torch float64, updated in place; no fitted sigma below sigma_floor.  Enqueued."""
+        self._chk(self.L.cpprob_hip_batch_mstep_mix_device(self.h, _dptr(stats), stats.numel(), _dptr(weights), _dptr(means), _dptr(sigmas), _dptr(trans), float(sigma_floor)))
+
+    def batch_copy_mix(self, b, k=None, M=None, D=None):
+        """(log-weights [k, M], means [k, M, D], sigmas [k, M, D], log_norms [k, M]) of problem b of a mixture batch, as the device
+        holds them (cpprob_hip_batch_copy_mix).  Synchronises.  For tests."""
+        k, M, D = int(k if k is not None else self.batch_k), int(M if M is not None else getattr(self, "batch_M", 1)), int(D if D is not None else getattr(self, "batch_D", 1))
+        lw, mu, sg, ln = np.zeros((8, 8)), np.zeros((8, 8, MIX_MAX_DIM)), np.zeros((8, 8, MIX_MAX_DIM)), np.zeros((8, 8))
+        self._chk(self.L.cpprob_hip_batch_copy_mix(self.h, int(b), lw.ctypes.data, mu.ctypes.data, sg.ctypes.data, ln.ctypes.data))
+        return lw[:k, :M].copy(), mu[:k, :M, :D].copy(), sg[:k, :M, :D].copy(), ln[:k, :M].copy()
 
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):

@@ -299,8 +299,8 @@ struct BatchFullStatsArgs {
     const uint64_t* thr;                       // as BatchSmoothArgs::thr
     const double* obs;                         // the observes packed problem after problem, D doubles a step
     double* g;                                 // [steps][8]: the walk's marginals, row trows + t (the walk writes, the moments read)
-    double* stats;                             // [B][kFullStats]
-    int B, k, D, thr_stride;
+    double* stats;                             // [B][stats_stride]: kFullStats of a full batch (the walk serves csrc/batch_mix.hpp's record too)
+    int B, k, D, thr_stride, stats_stride;
 };
 
 __global__ __launch_bounds__(kThreads) void batch_full_walk_kernel(BatchFullStatsArgs a)
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(kThreads) void batch_full_walk_kernel(BatchFullStat
     const int D = a.D;
     for (int b = suff_uniform((int)blockIdx.x * kWaves + wave_id()); b < a.B; b += (int)gridDim.x * kWaves) {   // (wavefront-uniform)
         const BatchSmoothProblem d = a.desc[b];
-        double* out = a.stats + (int64_t)b * kFullStats;
+        double* out = a.stats + (int64_t)b * a.stats_stride;
         const int T = d.T;
         double xi = 0.0, occ = 0.0, occ_y = 0.0, occ_yy = 0.0;
         if (T > 0) {

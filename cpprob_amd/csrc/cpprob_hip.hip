@@ -34,6 +34,7 @@
 #include "batch_categorical.hpp"
 #include "batch_diag.hpp"
 #include "batch_full.hpp"
+#include "batch_mix.hpp"
 #include "batch_learn.hpp"
 #include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
@@ -1079,6 +1080,43 @@ __attribute__((noinline)) void full_expand_tables(size_t B, int k, int D, const 
             log_norm[b * 8 + s] = full_log_norm(Ls, 1, D);
         }
 }
+// ... or a vector from a Gaussian mixture (csrc/batch_mix.hpp): the seventh family, begun, re-tabled and fitted by its own calls
+constexpr EmissionFamily kFamilyMix = (EmissionFamily)6;
+// a mixture problem's rows, with the statements the device's re-table writes them with: lw, ln [64], mean, sigma [64][16] (kept out of
+// line: batch_begin's own loop stays the other families')
+__attribute__((noinline)) void mix_problem_rows(const double* y, size_t T, int D, int M, const double* lw, const double* ln, const double* mean, const double* sigma, int k, double* rows)
+{
+    for (size_t t = 0; t < T; ++t)
+        for (int s2 = 0; s2 < 8; ++s2) {
+            double lc[kMixMaxComp], e[kMixMaxComp], S;
+            if (s2 < k) mix_components(y + t * (size_t)D, D, M, mean + (size_t)s2 * 8 * kMixMaxDim, sigma + (size_t)s2 * 8 * kMixMaxDim, kMixMaxDim, 1, lw + 8 * s2, ln + 8 * s2, 1, lc);
+            rows[t * kBatchTab + s2] = s2 < k ? mix_join(lc, M, e, S) : -INFINITY;
+        }
+}
+// the tables of a mixture begin (weights [B][k][M], means and sigmas [B][k][M][D], checked) in the device's layout, [B][64], [B][64],
+// [B][64][16] and [B][64][16]: slots outside the table 0.0
+__attribute__((noinline)) void mix_expand_tables(size_t B, int k, int M, int D, const double* h_weights, const double* h_means, const double* h_sigmas, std::vector<double>& lw,
+                                                 std::vector<double>& ln, std::vector<double>& mean, std::vector<double>& sigma)
+{
+    lw.assign(B * kMixComps, 0.0); ln.assign(B * kMixComps, 0.0); mean.assign(B * kMixSlots, 0.0); sigma.assign(B * kMixSlots, 0.0);
+    for (size_t b = 0; b < B; ++b)
+        for (size_t s = 0; s < (size_t)k; ++s) {
+            const double* w = h_weights + (b * (size_t)k + s) * (size_t)M;
+            double tot = 0.0;
+            for (int c = 0; c < M; ++c) tot = tot + w[c];
+            for (size_t c = 0; c < (size_t)M; ++c) {
+                const size_t sc = 8 * s + c, from = ((b * (size_t)k + s) * (size_t)M + c) * (size_t)D;
+                double lnd[kMixMaxDim];
+                for (size_t d = 0; d < (size_t)D; ++d) {
+                    mean[b * kMixSlots + sc * kMixMaxDim + d] = h_means[from + d];
+                    sigma[b * kMixSlots + sc * kMixMaxDim + d] = h_sigmas[from + d];
+                    lnd[d] = scale_log_norm(h_sigmas[from + d]);
+                }
+                lw[b * kMixComps + sc] = mix_log_weight(w[c], tot);
+                ln[b * kMixComps + sc] = diag_log_norm(lnd, D, 1);
+            }
+        }
+}
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
 {
     std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
@@ -1270,6 +1308,15 @@ struct BatchState {
     DeviceBuffer d_full_mean, d_full_L, d_full_lognorm, d_full_g;
     const double *full_begin_means = nullptr, *full_begin_covs = nullptr;
     int full_begin_D = 0;
+    // Gaussian-mixture vector emissions (cpprob_hip_batch_begin_problems_mix; csrc/batch_mix.hpp): mix: the begun batch has them, and is
+    // then of no other family; mix_D its coordinates and mix_M its components a state.  The log-weights and log_norms [B][64] and the
+    // means and sigmas [B][64][16] in force are the device's alone; the E-step's workspace is d_full_g.  mix_begin_*: the checked
+    // arguments of the begin in progress
+    bool mix = false;
+    int mix_D = 0, mix_M = 0;
+    DeviceBuffer d_mix_lw, d_mix_ln, d_mix_mean, d_mix_sigma;
+    const double *mix_begin_weights = nullptr, *mix_begin_means = nullptr, *mix_begin_sigmas = nullptr;
+    int mix_begin_D = 0, mix_begin_M = 0;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
@@ -1463,7 +1510,18 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, bs->d_full_L.grow(c->stream, fl_L.size() * sizeof(double)));
         HIP_TRY(c, bs->d_full_lognorm.grow(c->stream, fl_lognorm.size() * sizeof(double)));
     }
-    const size_t obs_stride = diag ? (size_t)diag_D : full ? (size_t)full_D : 1;    // doubles a step of h_obs
+    const bool mix = family == kFamilyMix;                      // (as a diagonal begin: the tables are bs->mix_begin_*)
+    bs->mix = false;
+    std::vector<double> mx_lw, mx_ln, mx_mean, mx_sigma;        // (live until the synchronisation below)
+    const int mix_D = mix ? bs->mix_begin_D : 0, mix_M = mix ? bs->mix_begin_M : 0;
+    if (mix) {
+        mix_expand_tables((size_t)B, k, mix_M, mix_D, bs->mix_begin_weights, bs->mix_begin_means, bs->mix_begin_sigmas, mx_lw, mx_ln, mx_mean, mx_sigma);
+        HIP_TRY(c, bs->d_mix_lw.grow(c->stream, mx_lw.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_mix_ln.grow(c->stream, mx_ln.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_mix_mean.grow(c->stream, mx_mean.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_mix_sigma.grow(c->stream, mx_sigma.size() * sizeof(double)));
+    }
+    const size_t obs_stride = diag ? (size_t)diag_D : full ? (size_t)full_D : mix ? (size_t)mix_D : 1;    // doubles a step of h_obs
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
@@ -1477,7 +1535,8 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         // (a diagonal batch: a row loop of its own, obs_stride doubles a step; at_obs counts steps)
         if (diag) diag_problem_rows(h_obs + at_obs * obs_stride, T_b, diag_D, &dg_mean[b * kDiagSlots], &dg_sigma[b * kDiagSlots], &dg_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
         if (full) full_problem_rows(h_obs + at_obs * obs_stride, T_b, full_D, &fl_mean[b * kFullMeanSlots], &fl_L[b * kFullTriSlots], &fl_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
-        for (size_t t = 0; t < (online || diag || full ? 0 : T_b); ++t) {
+        if (mix) mix_problem_rows(h_obs + at_obs * obs_stride, T_b, mix_D, mix_M, &mx_lw[b * kMixComps], &mx_ln[b * kMixComps], &mx_mean[b * kMixSlots], &mx_sigma[b * kMixSlots], k, &bs->h_tab[b * T_max * kBatchTab]);
+        for (size_t t = 0; t < (online || diag || full || mix ? 0 : T_b); ++t) {
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
@@ -1519,6 +1578,12 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, hipMemcpyAsync(bs->d_full_L.as<double>(), fl_L.data(), fl_L.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_full_lognorm.as<double>(), fl_lognorm.data(), fl_lognorm.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
+    if (mix) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_mix_lw.as<double>(), mx_lw.data(), mx_lw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_mix_ln.as<double>(), mx_ln.data(), mx_ln.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_mix_mean.as<double>(), mx_mean.data(), mx_mean.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_mix_sigma.as<double>(), mx_sigma.data(), mx_sigma.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
     if (online) {
@@ -1552,6 +1617,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->categorical = categorical; bs->cat_V = cat_V;
     bs->diag = diag; bs->diag_D = diag_D;
     bs->full = full; bs->full_D = full_D;
+    bs->mix = mix; bs->mix_D = mix_D; bs->mix_M = mix_M;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -5392,6 +5458,7 @@ static int batch_smooth_stats_check(cpprob_hip_ctx* c, bool with_obs, size_t n_o
     if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
     if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its statistics are cpprob_hip_batch_diag_stats / _diag_stats_device");
     if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its statistics are cpprob_hip_batch_full_stats / _full_stats_device");
+    if (c->batch->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: its statistics are cpprob_hip_batch_mix_stats / _mix_stats_device");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     rows = 0;
@@ -5497,6 +5564,7 @@ static int batch_traj_stats_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t d
     if (int rc = batch_smooth_check(c, n_traj, draw_index, false, 0, false, 0, doubles, entries)) return rc;
     if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
+    if (c->batch->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (n_traj == 0) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 1 .. 2^20");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
@@ -5799,7 +5867,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "re-tabling serves CPPROB_HIP_MODEL_HMM_TABLE: the table of CPPROB_HIP_MODEL_HMM3 is the model's");
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
     const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
-    const bool categorical = family == kFamilyCategorical, diag = family == kFamilyDiag, full = family == kFamilyFull;
+    const bool categorical = family == kFamilyCategorical, diag = family == kFamilyDiag, full = family == kFamilyFull, mix = family == kFamilyMix;
+    if (bs->mix && !mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: it is re-tabled by cpprob_hip_batch_retable_mix / _retable_mix_device");
+    if (!bs->mix && mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Gaussian-mixture vector emissions: begin it with cpprob_hip_batch_begin_problems_mix, or re-table it with its own family's calls");
     if (bs->full && !full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: it is re-tabled by cpprob_hip_batch_retable_full / _retable_full_device");
     if (!bs->full && full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions: begin it with cpprob_hip_batch_begin_problems_full, or re-table it with its own family's calls");
     if (bs->diag && !diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: it is re-tabled by cpprob_hip_batch_retable_diag / _retable_diag_device");
@@ -5816,14 +5886,16 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->diag_D) + " doubles");
     if (full && (uint64_t)n_observes != rows * (uint64_t)bs->full_D)
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->full_D) + " doubles");
-    if (!diag && !full && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    if (mix && (uint64_t)n_observes != rows * (uint64_t)bs->mix_D)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->mix_D) + " doubles");
+    if (!diag && !full && !mix && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
     return 0;
 }
 
 // Enqueues the first entries (once a begin) and the launch (d_sigmas given: a scaled batch's; a Poisson batch: its own, d_means the
 // rates); the batch then stands as after a begin.
 // Waits for nothing but, where the status words have to grow, for the calls before it.
-static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs, const double* d_sigmas)
+static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const double* d_trans, const double* d_obs, const double* d_sigmas, const double* d_weights = nullptr)
 {
     BatchState* bs = c->batch;
     const size_t B = bs->cfg.n_problems;
@@ -5839,6 +5911,15 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
         r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
+    if (bs->mix) {
+        // (a mixture batch: d_weights [B][k][M], d_means and d_sigmas [B][k][M][D]; the tables in force are the device's)
+        BatchRetableMixArgs ma{};
+        common(ma);
+        ma.weights = d_weights; ma.means = d_means; ma.sigmas = d_sigmas; ma.M = bs->mix_M; ma.D = bs->mix_D;
+        ma.lw_out = bs->d_mix_lw.as<double>(); ma.ln_out = bs->d_mix_ln.as<double>();
+        ma.mean_out = bs->d_mix_mean.as<double>(); ma.sigma_out = bs->d_mix_sigma.as<double>();
+        hipLaunchKernelGGL(batch_retable_mix_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, ma);
+    } else
     if (bs->full) {
         // (a full-covariance batch: d_means [B][k][D] and d_sigmas the covariances [B][k][D][D]; the tables in force are the device's)
         BatchRetableFullArgs fa{};
@@ -6018,6 +6099,7 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
     if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
     if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_diag_device");
     if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_full_device");
+    if (bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: its M-step is cpprob_hip_batch_mstep_mix_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: its M-step is cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its M-step is cpprob_hip_batch_mstep_poisson_device");
     if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: its M-step is cpprob_hip_batch_mstep_device / _mstep_scaled_device");
@@ -6077,6 +6159,7 @@ int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* c, const double* d_stats
     if (!bs->own_tables) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the batch was begun with the context's shared table: begin it with per-problem tables to draw them");
     if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_diag_device");
     if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_full_device");
+    if (bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_mix_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: the conjugate (Dirichlet) draw of its matrix is not built -- fit it with cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: the conjugate (gamma) draw of its rates is not built -- fit it with cpprob_hip_batch_mstep_poisson_device");
     if (bs->scaled && !d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its draw takes d_sigmas");
@@ -6688,7 +6771,7 @@ static int batch_full_stats_enqueue(cpprob_hip_ctx* c, const double* d_obs, doub
     HIP_TRY(c, bs->d_full_g.grow(c->stream, (size_t)rows * 8 * sizeof(double)));
     BatchFullStatsArgs sa{};
     sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = d_obs; sa.g = bs->d_full_g.as<double>(); sa.stats = d_stats;
-    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->full_D; sa.thr_stride = a.thr_stride;
+    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->full_D; sa.thr_stride = a.thr_stride; sa.stats_stride = kFullStats;
     hipLaunchKernelGGL(batch_full_walk_kernel, dim3(std::min<unsigned>(pl.stats_gx, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(batch_full_moments_kernel, dim3(std::min<unsigned>((unsigned)sa.B, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
@@ -6750,6 +6833,207 @@ int cpprob_hip_batch_copy_full(cpprob_hip_ctx* c, uint64_t problem, double* h_me
     if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_full_mean.as<double>() + problem * kFullMeanSlots, kFullMeanSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_factors) HIP_TRY(c, hipMemcpyAsync(h_factors, bs->d_full_L.as<double>() + problem * kFullTriSlots, kFullTriSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_full_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- Gaussian-mixture vector emissions of a batch (csrc/batch_mix.hpp) ---------------------------------------------------------------
+// Weights, means and sigmas on the host ([B][k][M], [B][k][M][D]): mix_check's bits 128, 4 and 8, by name.
+static int batch_check_mix(cpprob_hip_ctx* c, uint64_t B, int k, int M, int D, const double* h_weights, const double* h_means, const double* h_sigmas, const double* h_transition)
+{
+    const size_t km = (size_t)k * (size_t)M, kmd = km * (size_t)D;
+    for (uint64_t b = 0; b < B; ++b) {
+        const int bits = mix_check(h_weights + b * km, h_means + b * kmd, h_sigmas + b * kmd, h_transition + b * (size_t)k * (size_t)k, k, M, D);
+        if (bits & kRetableBadMixWeight)
+            return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": mixture weights must be finite and >= 0, a state's total > 0 and finite, a positive share a normal number");
+        if (bits & kRetableBadMean) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": component means must be finite");
+        if (bits & kRetableBadScale) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": emission scales must be finite and > 0, with a normal finite 2 pi sigma^2");
+    }
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems_mix(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
+                                        int32_t k_in, int32_t M, int32_t D, const double* h_weights, const double* h_means, const double* h_sigmas, const double* h_transition)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_weights || !h_means || !h_sigmas || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "Gaussian-mixture vector emissions serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    if (D < 1 || D > kMixMaxDim) return fail(c, CPPROB_HIP_EINVAL, "D, the coordinates of an observe, must lie in 1 .. 16");
+    if (M < 1 || M > kMixMaxComp) return fail(c, CPPROB_HIP_EINVAL, "M, the components of a state, must lie in 1 .. 8");
+    if (k_in < 1 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "k must lie in 1 .. 8");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    if (int rc = batch_check_mix(c, cfg->n_problems, k_in, M, D, h_weights, h_means, h_sigmas, h_transition)) return rc;
+    // (the begin's route takes means [B][k]: zeros, which no mixture row reads; the tables travel beside them)
+    const std::vector<double> zeros((size_t)cfg->n_problems * (size_t)k_in, 0.0);
+    if (!c->batch) c->batch = new BatchState();
+    BatchState* bs = c->batch;
+    bs->mix_begin_weights = h_weights; bs->mix_begin_means = h_means; bs->mix_begin_sigmas = h_sigmas; bs->mix_begin_D = D; bs->mix_begin_M = M;
+    const int rc = batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, zeros.data(), h_transition, nullptr, nullptr, kFamilyMix);
+    bs = c->batch;
+    bs->mix_begin_weights = nullptr; bs->mix_begin_means = nullptr; bs->mix_begin_sigmas = nullptr; bs->mix_begin_D = 0; bs->mix_begin_M = 0;
+    return rc;
+}
+
+// table_exp, and the rows the host begin writes for one problem (its two loops, no context): for tests, host only
+double cpprob_hip_table_exp(double x) { return table_exp(x); }
+
+int cpprob_hip_mix_rows(const double* h_obs, size_t T, int32_t k, int32_t M, int32_t D, const double* h_weights, const double* h_means, const double* h_sigmas, double* h_rows)
+{
+    if (!h_obs || !h_weights || !h_means || !h_sigmas || !h_rows) return fail(nullptr, CPPROB_HIP_EINVAL, "NULL argument");
+    if (k < 1 || k > 8 || M < 1 || M > kMixMaxComp || D < 1 || D > kMixMaxDim) return fail(nullptr, CPPROB_HIP_EINVAL, "k and M must lie in 1 .. 8, D in 1 .. 16");
+    std::vector<double> lw, ln, mean, sigma, rows(T * kBatchTab);
+    mix_expand_tables(1, k, M, D, h_weights, h_means, h_sigmas, lw, ln, mean, sigma);
+    mix_problem_rows(h_obs, T, D, M, lw.data(), ln.data(), mean.data(), sigma.data(), k, rows.data());
+    for (size_t t = 0; t < T; ++t) for (int s = 0; s < 8; ++s) h_rows[t * 8 + s] = rows[t * kBatchTab + s];
+    return 0;
+}
+
+int cpprob_hip_batch_retable_mix_device(cpprob_hip_ctx* c, const double* d_weights, const double* d_means, const double* d_sigmas, const double* d_transition,
+                                        const double* d_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyMix)) return rc;
+    if (!d_weights || !d_means || !d_sigmas || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_means, d_transition, d_observes, d_sigmas, d_weights);
+}
+
+// The host form: the tables are validated with the begin's own statements, staged -- weights, means and sigmas in front, the transition
+// rows at the back -- and re-tabled as by the device form.
+int cpprob_hip_batch_retable_mix(cpprob_hip_ctx* c, const double* h_weights, const double* h_means, const double* h_sigmas, const double* h_transition,
+                                 const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyMix)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_weights || !h_means || !h_sigmas || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    const size_t B = bs->cfg.n_problems, kk = (size_t)bs->hk * bs->hk, km = (size_t)bs->hk * (size_t)bs->mix_M, kmd = km * (size_t)bs->mix_D;
+    int k = 0;
+    const std::vector<double> zeros(B * (size_t)bs->hk, 0.0);
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, zeros.data(), h_transition, k)) return rc;
+    if (int rc = batch_check_mix(c, B, k, bs->mix_M, bs->mix_D, h_weights, h_means, h_sigmas, h_transition)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_observes) if (int rc = batch_retable_observes(c, h_observes, n_observes)) return rc;
+    double *d_means = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(B * (2 * kmd + km) * sizeof(double)), B * kk * sizeof(double), d_means, d_trans)) return rc;
+    double *d_sigmas = d_means + B * kmd, *d_weights = d_sigmas + B * kmd;
+    HIP_TRY(c, hipMemcpyAsync(d_means, h_means, B * kmd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * kmd * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_weights, h_weights, B * km * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_means, d_trans, bs->d_robs.as<double>(), d_sigmas, d_weights)) return rc;
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    bs->thr_stale = false;
+    return 0;
+}
+
+// cpprob_hip_batch_mix_stats' arguments against the batch's state (batch_diag_stats_check's).
+static int batch_mix_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& n_obs)
+{
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    uint64_t doubles = 0, entries = 0;
+    if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
+    BatchState* bs = c->batch;
+    if (!bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Gaussian-mixture vector emissions (cpprob_hip_batch_begin_problems_mix): its statistics are its own family's");
+    if (!stats || !observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    uint64_t rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    n_obs = rows * (uint64_t)bs->mix_D;
+    if ((uint64_t)n_observes != n_obs)
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->mix_D) + " doubles");
+    const uint64_t need = (uint64_t)bs->cfg.n_problems * (uint64_t)kMixStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (2200 a problem)");
+    return 0;
+}
+
+// The pass: batch_full_stats_enqueue's prologue and walk (the 88 doubles and the marginals of every step into the workspace), then the
+// mixture's moments from the workspace, the observes and the tables in force.
+static int batch_mix_stats_enqueue(cpprob_hip_ctx* c, const double* d_obs, double* d_stats)
+{
+    BatchState* bs = c->batch;
+    BatchPassPlan pl; BatchSmoothArgs a{};
+    if (int rc = batch_pass_prologue(c, BatchPass::stats(d_obs, d_stats), pl, a)) return rc;
+    if (pl.done) {                                                          // (no problem has a step: every record is zeros)
+        HIP_TRY(c, hipMemsetAsync(d_stats, 0, (size_t)bs->cfg.n_problems * kMixStats * sizeof(double), c->stream));
+        return 0;
+    }
+    uint64_t rows = 0;
+    for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
+    HIP_TRY(c, bs->d_full_g.grow(c->stream, (size_t)rows * 8 * sizeof(double)));
+    BatchFullStatsArgs sa{};
+    sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = d_obs; sa.g = bs->d_full_g.as<double>(); sa.stats = d_stats;
+    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->mix_D; sa.thr_stride = a.thr_stride; sa.stats_stride = kMixStats;
+    hipLaunchKernelGGL(batch_full_walk_kernel, dim3(std::min<unsigned>(pl.stats_gx, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
+    HIP_TRY(c, hipGetLastError());
+    BatchMixMomentsArgs ma{};
+    ma.desc = a.desc; ma.obs = d_obs; ma.g = sa.g; ma.stats = d_stats;
+    ma.lw = bs->d_mix_lw.as<double>(); ma.ln = bs->d_mix_ln.as<double>(); ma.mean = bs->d_mix_mean.as<double>(); ma.sigma = bs->d_mix_sigma.as<double>();
+    ma.B = sa.B; ma.k = a.k; ma.M = bs->mix_M; ma.D = bs->mix_D;
+    hipLaunchKernelGGL(batch_mix_moments_kernel, dim3(std::min<unsigned>((unsigned)ma.B, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, ma);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_mix_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_mix_stats_check(c, d_observes, n_observes, d_stats, n_doubles, n_obs)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_mix_stats_enqueue(c, d_observes, d_stats);
+}
+
+int cpprob_hip_batch_mix_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_mix_stats_check(c, h_observes, n_observes, h_stats, n_doubles, n_obs)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kMixStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)n_obs, d_stats, d_obs)) return rc;
+    if (int rc = batch_mix_stats_enqueue(c, d_obs, d_stats)) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
+}
+
+int cpprob_hip_batch_mstep_mix_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_weights, double* d_means, double* d_sigmas, double* d_transition,
+                                      double sigma_floor)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Gaussian-mixture vector emissions: its M-step is its own family's");
+    if (!d_stats || !d_weights || !d_means || !d_sigmas || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor)) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kMixStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (2200 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepMixArgs a{};
+    a.stats = d_stats; a.weights = d_weights; a.means = d_means; a.sigmas = d_sigmas; a.trans = d_transition; a.floor = sigma_floor;
+    a.B = (int64_t)B; a.k = bs->hk; a.M = bs->mix_M; a.D = bs->mix_D;
+    hipLaunchKernelGGL(batch_mstep_mix_kernel, dim3((unsigned)((B * (uint64_t)bs->hk * (uint64_t)bs->mix_M + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_mix(cpprob_hip_ctx* c, uint64_t problem, double* h_log_weights, double* h_means, double* h_sigmas, double* h_log_norms)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Gaussian-mixture vector emissions (cpprob_hip_batch_begin_problems_mix)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_log_weights) HIP_TRY(c, hipMemcpyAsync(h_log_weights, bs->d_mix_lw.as<double>() + problem * kMixComps, kMixComps * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_mix_mean.as<double>() + problem * kMixSlots, kMixSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_mix_sigma.as<double>() + problem * kMixSlots, kMixSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_mix_ln.as<double>() + problem * kMixComps, kMixComps * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }

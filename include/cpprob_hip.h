@@ -1061,6 +1061,58 @@ int cpprob_hip_batch_mstep_full_device(cpprob_hip_ctx* ctx, const double* d_stat
                                        double* d_transition, double var_floor);
 int cpprob_hip_batch_copy_full(cpprob_hip_ctx* ctx, uint64_t problem, double* h_means, double* h_factors, double* h_log_norms);
 
+/* ---- Gaussian-mixture vector emissions of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_mix.hpp) -----------
+ * State s of problem b emits a vector y in R^D, 1 <= D <= 16, with the density sum over c < M of w[b][s][c] prod_d N(y_d;
+ * mean[b][s][c][d], sigma[b][s][c][d]), 1 <= M <= 8 components: weights [B][k][M], means and sigmas [B][k][M][D], the observes D doubles
+ * a step (n_observes counts doubles: D times the sum of the lengths).  A batch is unit, scaled, Poisson, categorical, diagonal, full or
+ * mixture, never two of them: every call of one family on a batch of another returns CPPROB_HIP_ESTATE and the batch stays.  A mixture
+ * batch is run, smoothed, counted, forecast and decoded by the calls above as they are.  The weights of a state are used through
+ * lw = log(w_c / tot), tot the state's total added ascending (-inf for a weight of zero, which is allowed); a component's log_norm is a
+ * diagonal state's; a row is m + log(sum over c of exp(lc_c - m)) with lc_c = lw + the diagonal family's entry and m the largest lc_c,
+ * the logarithm and the exponential the library's own table_log and table_exp, so that the host's rows have the device's bits; a
+ * component more than 1000 below m counts at -1000, which is exactly 0.  At M = 1 the rows are a diagonal batch's bits.
+ * tests/mix_ref.py restates every statement.
+ * cpprob_hip_batch_begin_problems_mix: cpprob_hip_batch_begin_problems with M, D and the three tables.  D outside 1 .. 16, M or k outside
+ * 1 .. 8, a weight that is not finite or < 0, a state whose weights do not add to a finite total > 0, a positive share that is not a
+ * normal number, a mean that is not finite or a sigma the scaled calls refuse: CPPROB_HIP_EINVAL, by problem.  There is no online
+ * mixture begin.
+ * cpprob_hip_batch_retable_mix_device / _retable_mix: cpprob_hip_batch_retable_diag_device / _retable_diag with the weights.  The device
+ * form checks on the device: bit 128 of cpprob_hip_batch_retable_status, a refused weight; bits 4 and 8 as for a diagonal batch; that
+ * problem keeps rows, thresholds and tables.
+ * cpprob_hip_batch_mix_stats_device / _mix_stats: the E-step.  2200 doubles a problem: the first 88 are the record of
+ * cpprob_hip_batch_smooth_stats with coordinate 0 as the observe; component (s, c) has a block of 33 at 88 + 33 (8 s + c): occ_c = the
+ * sum over t of v, sy[d] = the sum of v y_t[d] at 1 + d, syy[d] = the sum of v (y_t[d] y_t[d]) at 17 + d, with v = g_t[s] r and r the
+ * component's responsibility e_c / S under the tables in force; slots outside (k, M, D) are 0.0.  Two kernels: the backward walk leaves
+ * every step's marginals in a workspace of the context's own, the moments are formed from it.
+ * cpprob_hip_batch_mstep_mix_device: on d_weights [B][k][M], d_means and d_sigmas [B][k][M][D] and d_transition [B][k][k] in place, from
+ * records of 2200 doubles.  A state with mass occ = the sum of its occ_c: w'_c = occ_c / occ; a component with occ_c > 0 takes
+ * mean' = sy / occ_c and sigma' = sqrt(syy / occ_c - mean'^2), not below sigma_floor; one with occ_c == 0 keeps mean and sigma and takes
+ * the weight 0.  A state without mass keeps everything.  sigma_floor finite and > 0, else CPPROB_HIP_EINVAL.  cpprob_amd.mix.m_step_mix,
+ * bit for bit.  Enqueued.
+ * On a mixture batch the other families' re-tables, statistics and M-steps and cpprob_hip_batch_draw_tables_device return
+ * CPPROB_HIP_ESTATE; cpprob_hip_batch_learn_begin* and _online_tables* do so because the batch is not online.
+ * cpprob_hip_batch_copy_mix: problem `problem`'s log-weights [8][8], means [8][8][16], sigmas [8][8][16] and log_norms [8][8] in force
+ * as the device holds them (slots outside the table 0.0; any may be NULL); synchronises; CPPROB_HIP_ESTATE: no batch begun, or no
+ * mixture batch.  For tests. */
+/* For tests, host only, no context: the exponential of the rows (x in [-1000, 0]), and the rows [T][8] the host begin writes for one
+ * problem of T steps (weights [k][M], means and sigmas [k][M][D], not validated; CPPROB_HIP_EINVAL for k, M or D out of range). */
+double cpprob_hip_table_exp(double x);
+int cpprob_hip_mix_rows(const double* h_observes, size_t T, int32_t k, int32_t M, int32_t D, const double* h_weights, const double* h_means,
+                        const double* h_sigmas, double* h_rows);
+int cpprob_hip_batch_begin_problems_mix(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                        const double* h_observes, int32_t k, int32_t M, int32_t D, const double* h_weights,
+                                        const double* h_means, const double* h_sigmas, const double* h_transition);
+int cpprob_hip_batch_retable_mix_device(cpprob_hip_ctx* ctx, const double* d_weights, const double* d_means, const double* d_sigmas,
+                                        const double* d_transition, const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_mix(cpprob_hip_ctx* ctx, const double* h_weights, const double* h_means, const double* h_sigmas,
+                                 const double* h_transition, const double* h_observes, size_t n_observes);
+int cpprob_hip_batch_mix_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+int cpprob_hip_batch_mix_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+int cpprob_hip_batch_mstep_mix_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_weights, double* d_means,
+                                      double* d_sigmas, double* d_transition, double sigma_floor);
+int cpprob_hip_batch_copy_mix(cpprob_hip_ctx* ctx, uint64_t problem, double* h_log_weights, double* h_means, double* h_sigmas,
+                              double* h_log_norms);
+
 /* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
  * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
  * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
