@@ -16,6 +16,7 @@ from .categorical import hmm_categorical_em, m_step_categorical  # noqa: F401
 from .diag import hmm_diag_em, m_step_diag  # noqa: F401
 from .full import hmm_full_em, m_step_full  # noqa: F401
 from .mix import hmm_mix_em, m_step_mix  # noqa: F401
+from .reg import ar_design, hmm_reg_em, m_step_reg  # noqa: F401
 from . import online_em  # noqa: F401
 from .online_em import hmm_table_online_em  # noqa: F401
 from . import gibbs  # noqa: F401

@@ -70,6 +70,8 @@ SYMBOLS = [
     "cpprob_hip_table_exp", "cpprob_hip_mix_rows",
     "cpprob_hip_batch_begin_problems_mix", "cpprob_hip_batch_retable_mix", "cpprob_hip_batch_retable_mix_device",
     "cpprob_hip_batch_mix_stats", "cpprob_hip_batch_mix_stats_device", "cpprob_hip_batch_mstep_mix_device", "cpprob_hip_batch_copy_mix",
+    "cpprob_hip_batch_begin_problems_reg", "cpprob_hip_batch_retable_reg", "cpprob_hip_batch_retable_reg_device",
+    "cpprob_hip_batch_reg_stats", "cpprob_hip_batch_reg_stats_device", "cpprob_hip_batch_mstep_reg_device", "cpprob_hip_batch_copy_reg",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
@@ -233,6 +235,7 @@ CATEGORICAL_MAX_SYMBOLS = 64                  # cpprob_hip_batch_begin_problems_
 SYMBOL_STATS_PER_PROBLEM = 88 + 8 * 64        # doubles a problem of cpprob_hip_batch_symbol_stats: the 88 above, then cnt[8][64]
 DIAG_MAX_DIM = 32                             # cpprob_hip_batch_begin_problems_diag: D in 1 ..=
 FULL_MAX_DIM = 16                             # cpprob_hip_batch_begin_problems_full: D in 1 ..=
+REG_MAX_COV = 15                              # cpprob_hip_batch_begin_problems_reg: P in 1 ..=; a step holds 1 + P doubles
 FULL_TRI = 136                                # the packed lower triangle of a state: entry (i, j), j <= i, at i (i + 1) / 2 + j
 FULL_STATS_PER_PROBLEM = 1304                 # doubles a problem of cpprob_hip_batch_full_stats: the 88 above, sy[8][16], syy[8][136]
 MIX_MAX_DIM, MIX_MAX_COMP = 16, 8             # cpprob_hip_batch_begin_problems_mix: D and M in 1 ..=
@@ -514,6 +517,13 @@ def load_library(path=None):
         "cpprob_hip_batch_mix_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_mstep_mix_device": (C.c_int, [vp, vp, sz, vp, vp, vp, vp, dbl]),
         "cpprob_hip_batch_copy_mix": (C.c_int, [vp, u64, vp, vp, vp, vp]),
+        "cpprob_hip_batch_begin_problems_reg": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, C.c_int32, vp, vp, vp]),
+        "cpprob_hip_batch_retable_reg": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_reg_device": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_reg_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_reg_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_mstep_reg_device": (C.c_int, [vp, vp, sz, vp, vp, vp, vp, dbl]),
+        "cpprob_hip_batch_copy_reg": (C.c_int, [vp, u64, vp, vp, vp]),
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
@@ -1331,6 +1341,77 @@ class Engine:
         lw, mu, sg, ln = np.zeros((8, 8)), np.zeros((8, 8, MIX_MAX_DIM)), np.zeros((8, 8, MIX_MAX_DIM)), np.zeros((8, 8))
         self._chk(self.L.cpprob_hip_batch_copy_mix(self.h, int(b), lw.ctypes.data, mu.ctypes.data, sg.ctypes.data, ln.ctypes.data))
         return lw[:k, :M].copy(), mu[:k, :M, :D].copy(), sg[:k, :M, :D].copy(), ln[:k, :M].copy()
+
+    # ---- switching-regression emissions (include/cpprob_hip.h: cpprob_hip_batch_*_reg, _reg_stats*; csrc/batch_reg.hpp) ----
+    def _batch_reg_tables(self, coef, sigmas, trans, B):
+        cf = np.ascontiguousarray(coef, np.float64)
+        sg = np.ascontiguousarray(sigmas, np.float64)
+        tr = np.ascontiguousarray(trans, np.float64)
+        if cf.ndim != 3 or cf.shape[0] != B or sg.shape != cf.shape[:2] or tr.shape != (B, cf.shape[1], cf.shape[1]):
+            raise ValueError("coef [B, k, P], sigmas [B, k] and transition [B, k, k]")
+        return cf, sg, tr
+
+    def batch_begin_problems_reg(self, observes, n_particles, coef, sigmas, trans, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, keep_masses=False, max_particles=None):
+        """A MODEL_HMM_TABLE batch whose states regress the observe on covariates known at the step
+        (cpprob_hip_batch_begin_problems_reg): observes a list of [T_b, 1 + P] arrays, column 0 the response y_t and columns 1 .. P
+        the covariates x_t; coef [B, k, P] and sigmas [B, k] (state s of problem b emits N(coef[b, s] . x_t, sigmas[b, s])), trans
+        [B, k, k]; k <= 8, P <= 15.  An intercept is a column of ones.  Everything else as batch_begin_problems."""
+        cf, sg, tr = self._batch_reg_tables(coef, sigmas, trans, len(observes))
+        P = cf.shape[2]
+        seqs = [np.ascontiguousarray(o, np.float64) for o in observes]
+        if 1 <= P <= REG_MAX_COV and any(o.ndim != 2 or o.shape[1] != 1 + P for o in seqs):      # (another P: the library's own refusal)
+            raise ValueError("observes: one [T_b, 1 + P] array a problem")
+        h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
+        flat = self._batch_packed_observes(seqs)
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(MODEL_HMM_TABLE, top, len(seqs), resampler, 2.0, keep_history, ALG_SMC, _batch_flags(0, keep_masses))
+        self._chk(self.L.cpprob_hip_batch_begin_problems_reg(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                             flat.ctypes.data_as(C.POINTER(C.c_double)), cf.shape[1], P, cf.ctypes.data, sg.ctypes.data, tr.ctypes.data))
+        self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
+        self.batch_K, self.batch_k, self.batch_D = 8, cf.shape[1], 1 + P
+        self.batch_shapes = (h_T, h_n)
+        return self
+
+    def batch_retable_reg(self, coef, sigmas, trans, observes=None):
+        """New coefficients, sigmas and transition rows for the begun regression batch where it stands (cpprob_hip_batch_retable_reg),
+        validated as the begin validates them; observes as the begin takes them, or None once a re-table has staged them."""
+        cf, sg, tr = self._batch_reg_tables(coef, sigmas, trans, self.batch_B)
+        flat = None if observes is None else self._batch_packed_observes(list(observes))
+        n_obs = int(np.sum(self.batch_shapes[0], dtype=np.int64)) * getattr(self, "batch_D", 1) if flat is None else flat.size
+        self._chk(self.L.cpprob_hip_batch_retable_reg(self.h, cf.ctypes.data, sg.ctypes.data, tr.ctypes.data, None if flat is None or flat.size == 0 else flat.ctypes.data, n_obs))
+
+    def batch_retable_reg_device(self, coef, sigmas, trans, observes):
+        """The same between torch float64 device tensors (coef [B, k, P], sigmas [B, k], trans [B, k, k], observes packed, 1 + P
+        doubles a step), enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status: bit 4,
+        a coefficient that is not finite; bit 8, a sigma)."""
+        self._chk(self.L.cpprob_hip_batch_retable_reg_device(self.h, _dptr(coef), _dptr(sigmas), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+
+    def batch_reg_stats(self, observes):
+        """The E-step of a regression batch (cpprob_hip_batch_reg_stats): batch_full_stats' dict over z_t = (y_t, x_t), so that
+        syy[b, s, 0, 0] is the visits of state s weighted by y y, syy[b, s, 1:, 0] by x y and syy[b, s, 1:, 1:] by x x^T."""
+        rec = np.zeros((self.batch_B, FULL_STATS_PER_PROBLEM))
+        flat = self._batch_packed_observes(list(observes))
+        self._chk(self.L.cpprob_hip_batch_reg_stats(self.h, flat.ctypes.data if flat.size else None, flat.size, rec.ctypes.data, rec.size))
+        return split_full_stats(rec)
+
+    def batch_reg_stats_device(self, stats, observes):
+        """The same left in a device tensor: stats torch float64 [B, 1304], observes a torch float64 tensor packed problem after
+        problem, 1 + P doubles a step."""
+        self._chk(self.L.cpprob_hip_batch_reg_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    def batch_mstep_reg_device(self, stats, coef, sigmas, trans, sigma_floor=1e-3, log_norms=None):
+        """reg.m_step_reg on the device (cpprob_hip_batch_mstep_reg_device): stats torch float64 [B, 1304]; coef [B, k, P], sigmas
+        [B, k] and trans [B, k, k] torch float64, updated in place; no fitted sigma below sigma_floor; log_norms [B, k], if given,
+        takes the new sigmas' log(2 pi sigma^2), for tests.  Enqueued."""
+        self._chk(self.L.cpprob_hip_batch_mstep_reg_device(self.h, _dptr(stats), stats.numel(), _dptr(coef), _dptr(sigmas), _dptr(trans), _dptr(log_norms), float(sigma_floor)))
+
+    def batch_copy_reg(self, b, k=None, P=None):
+        """(coef [k, P], sigmas [k], log_norms [k]) of problem b of a regression batch, as the device holds them
+        (cpprob_hip_batch_copy_reg).  Synchronises.  For tests."""
+        k, P = int(k if k is not None else self.batch_k), int(P if P is not None else getattr(self, "batch_D", 2) - 1)
+        cf, sg, ln = np.zeros((8, FULL_MAX_DIM)), np.zeros(8), np.zeros(8)
+        self._chk(self.L.cpprob_hip_batch_copy_reg(self.h, int(b), cf.ctypes.data, sg.ctypes.data, ln.ctypes.data))
+        return cf[:k, :P].copy(), sg[:k].copy(), ln[:k].copy()
 
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):

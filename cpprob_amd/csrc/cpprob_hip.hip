@@ -35,6 +35,7 @@
 #include "batch_diag.hpp"
 #include "batch_full.hpp"
 #include "batch_mix.hpp"
+#include "batch_reg.hpp"
 #include "batch_learn.hpp"
 #include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
@@ -1117,6 +1118,30 @@ __attribute__((noinline)) void mix_expand_tables(size_t B, int k, int M, int D, 
             }
         }
 }
+// ... or a scalar regressed on covariates known at the step (csrc/batch_reg.hpp): the eighth family, begun, re-tabled and fitted by its
+// own calls
+constexpr EmissionFamily kFamilyReg = (EmissionFamily)7;
+// a regression problem's rows, with the statements the device's re-table writes them with: coef [8][16], sigma and log_norm [8] (kept out
+// of line: batch_begin's own loop stays the other families')
+__attribute__((noinline)) void reg_problem_rows(const double* z, size_t T, int P, const double* coef, const double* sigma, const double* log_norm, int k, double* rows)
+{
+    for (size_t t = 0; t < T; ++t)
+        for (int s2 = 0; s2 < 8; ++s2)
+            rows[t * kBatchTab + s2] = s2 < k ? reg_entry(z + t * (size_t)(1 + P), P, coef + (size_t)s2 * kFullMaxDim, 1, sigma[s2], log_norm[s2]) : -INFINITY;
+}
+// the tables of a regression begin (coef [B][k][P], sigmas [B][k], checked) in the device's layout, [B][8][16], [B][8] and [B][8]: slots
+// outside the table 0.0
+__attribute__((noinline)) void reg_expand_tables(size_t B, int k, int P, const double* h_coef, const double* h_sigmas, std::vector<double>& coef, std::vector<double>& sigma,
+                                                 std::vector<double>& log_norm)
+{
+    coef.assign(B * kRegCoefSlots, 0.0); sigma.assign(B * 8, 0.0); log_norm.assign(B * 8, 0.0);
+    for (size_t b = 0; b < B; ++b)
+        for (size_t s = 0; s < (size_t)k; ++s) {
+            for (size_t i = 0; i < (size_t)P; ++i) coef[b * kRegCoefSlots + s * kFullMaxDim + i] = h_coef[(b * (size_t)k + s) * (size_t)P + i];
+            sigma[b * 8 + s] = h_sigmas[b * (size_t)k + s];
+            log_norm[b * 8 + s] = scale_log_norm(h_sigmas[b * (size_t)k + s]);
+        }
+}
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
 {
     std::vector<uint64_t> thr((size_t)k * 8, ~0ull);
@@ -1317,6 +1342,15 @@ struct BatchState {
     DeviceBuffer d_mix_lw, d_mix_ln, d_mix_mean, d_mix_sigma;
     const double *mix_begin_weights = nullptr, *mix_begin_means = nullptr, *mix_begin_sigmas = nullptr;
     int mix_begin_D = 0, mix_begin_M = 0;
+    // switching-regression emissions (cpprob_hip_batch_begin_problems_reg; csrc/batch_reg.hpp): reg: the begun batch has them, and is
+    // then of no other family; reg_P its covariates, and every observes array of its calls holds 1 + reg_P doubles a step.  The
+    // coefficients [B][8][16], sigmas and log_norms [B][8] in force are the device's alone; the E-step is the full family's, at
+    // D = 1 + reg_P, with its workspace d_full_g.  reg_begin_*: the checked arguments of the begin in progress
+    bool reg = false;
+    int reg_P = 0;
+    DeviceBuffer d_reg_coef, d_reg_sigma, d_reg_lognorm;
+    const double *reg_begin_coef = nullptr, *reg_begin_sigmas = nullptr;
+    int reg_begin_P = 0;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
@@ -1521,7 +1555,17 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, bs->d_mix_mean.grow(c->stream, mx_mean.size() * sizeof(double)));
         HIP_TRY(c, bs->d_mix_sigma.grow(c->stream, mx_sigma.size() * sizeof(double)));
     }
-    const size_t obs_stride = diag ? (size_t)diag_D : full ? (size_t)full_D : mix ? (size_t)mix_D : 1;    // doubles a step of h_obs
+    const bool reg = family == kFamilyReg;                      // (as a diagonal begin: the tables are bs->reg_begin_*)
+    bs->reg = false;
+    std::vector<double> rg_coef, rg_sigma, rg_lognorm;          // (live until the synchronisation below)
+    const int reg_P = reg ? bs->reg_begin_P : 0;
+    if (reg) {
+        reg_expand_tables((size_t)B, k, reg_P, bs->reg_begin_coef, bs->reg_begin_sigmas, rg_coef, rg_sigma, rg_lognorm);
+        HIP_TRY(c, bs->d_reg_coef.grow(c->stream, rg_coef.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_reg_sigma.grow(c->stream, rg_sigma.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_reg_lognorm.grow(c->stream, rg_lognorm.size() * sizeof(double)));
+    }
+    const size_t obs_stride = diag ? (size_t)diag_D : full ? (size_t)full_D : mix ? (size_t)mix_D : reg ? (size_t)(1 + reg_P) : 1;    // doubles a step of h_obs
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
@@ -1536,7 +1580,8 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         if (diag) diag_problem_rows(h_obs + at_obs * obs_stride, T_b, diag_D, &dg_mean[b * kDiagSlots], &dg_sigma[b * kDiagSlots], &dg_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
         if (full) full_problem_rows(h_obs + at_obs * obs_stride, T_b, full_D, &fl_mean[b * kFullMeanSlots], &fl_L[b * kFullTriSlots], &fl_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
         if (mix) mix_problem_rows(h_obs + at_obs * obs_stride, T_b, mix_D, mix_M, &mx_lw[b * kMixComps], &mx_ln[b * kMixComps], &mx_mean[b * kMixSlots], &mx_sigma[b * kMixSlots], k, &bs->h_tab[b * T_max * kBatchTab]);
-        for (size_t t = 0; t < (online || diag || full || mix ? 0 : T_b); ++t) {
+        if (reg) reg_problem_rows(h_obs + at_obs * obs_stride, T_b, reg_P, &rg_coef[b * kRegCoefSlots], &rg_sigma[b * 8], &rg_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
+        for (size_t t = 0; t < (online || diag || full || mix || reg ? 0 : T_b); ++t) {
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
@@ -1584,6 +1629,11 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, hipMemcpyAsync(bs->d_mix_mean.as<double>(), mx_mean.data(), mx_mean.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_mix_sigma.as<double>(), mx_sigma.data(), mx_sigma.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
+    if (reg) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_reg_coef.as<double>(), rg_coef.data(), rg_coef.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_reg_sigma.as<double>(), rg_sigma.data(), rg_sigma.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_reg_lognorm.as<double>(), rg_lognorm.data(), rg_lognorm.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
     if (online) {
@@ -1618,6 +1668,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->diag = diag; bs->diag_D = diag_D;
     bs->full = full; bs->full_D = full_D;
     bs->mix = mix; bs->mix_D = mix_D; bs->mix_M = mix_M;
+    bs->reg = reg; bs->reg_P = reg_P;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -5459,6 +5510,7 @@ static int batch_smooth_stats_check(cpprob_hip_ctx* c, bool with_obs, size_t n_o
     if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its statistics are cpprob_hip_batch_diag_stats / _diag_stats_device");
     if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its statistics are cpprob_hip_batch_full_stats / _full_stats_device");
     if (c->batch->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: its statistics are cpprob_hip_batch_mix_stats / _mix_stats_device");
+    if (c->batch->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: its statistics are cpprob_hip_batch_reg_stats / _reg_stats_device");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     rows = 0;
@@ -5565,6 +5617,7 @@ static int batch_traj_stats_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t d
     if (c->batch->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (c->batch->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: the trajectory statistics take one observe a step and do not serve it");
+    if (c->batch->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: the trajectory statistics take one observe a step and do not serve it");
     if (n_traj == 0) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 1 .. 2^20");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
@@ -5868,6 +5921,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
     const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
     const bool categorical = family == kFamilyCategorical, diag = family == kFamilyDiag, full = family == kFamilyFull, mix = family == kFamilyMix;
+    const bool reg = family == kFamilyReg;
+    if (bs->reg && !reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: it is re-tabled by cpprob_hip_batch_retable_reg / _retable_reg_device");
+    if (!bs->reg && reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no switching-regression emissions: begin it with cpprob_hip_batch_begin_problems_reg, or re-table it with its own family's calls");
     if (bs->mix && !mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: it is re-tabled by cpprob_hip_batch_retable_mix / _retable_mix_device");
     if (!bs->mix && mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Gaussian-mixture vector emissions: begin it with cpprob_hip_batch_begin_problems_mix, or re-table it with its own family's calls");
     if (bs->full && !full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: it is re-tabled by cpprob_hip_batch_retable_full / _retable_full_device");
@@ -5888,7 +5944,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->full_D) + " doubles");
     if (mix && (uint64_t)n_observes != rows * (uint64_t)bs->mix_D)
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->mix_D) + " doubles");
-    if (!diag && !full && !mix && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    if (reg && (uint64_t)n_observes != rows * (uint64_t)(1 + bs->reg_P))
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(1 + bs->reg_P) + " doubles");
+    if (!diag && !full && !mix && !reg && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
     return 0;
 }
 
@@ -5911,6 +5969,14 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
         r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
+    if (bs->reg) {
+        // (a regression batch: d_means the coefficients [B][k][P] and d_sigmas [B][k]; the tables in force are the device's)
+        BatchRetableRegArgs ra{};
+        common(ra);
+        ra.coef = d_means; ra.sigmas = d_sigmas; ra.P = bs->reg_P;
+        ra.coef_out = bs->d_reg_coef.as<double>(); ra.sigma_out = bs->d_reg_sigma.as<double>(); ra.log_norm_out = bs->d_reg_lognorm.as<double>();
+        hipLaunchKernelGGL(batch_retable_reg_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, ra);
+    } else
     if (bs->mix) {
         // (a mixture batch: d_weights [B][k][M], d_means and d_sigmas [B][k][M][D]; the tables in force are the device's)
         BatchRetableMixArgs ma{};
@@ -6100,6 +6166,7 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
     if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_diag_device");
     if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_full_device");
     if (bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: its M-step is cpprob_hip_batch_mstep_mix_device");
+    if (bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: its M-step is cpprob_hip_batch_mstep_reg_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: its M-step is cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its M-step is cpprob_hip_batch_mstep_poisson_device");
     if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: its M-step is cpprob_hip_batch_mstep_device / _mstep_scaled_device");
@@ -6160,6 +6227,7 @@ int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* c, const double* d_stats
     if (bs->diag) return fail(c, CPPROB_HIP_ESTATE, "the batch has diagonal-Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_diag_device");
     if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_full_device");
     if (bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_mix_device");
+    if (bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_reg_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: the conjugate (Dirichlet) draw of its matrix is not built -- fit it with cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: the conjugate (gamma) draw of its rates is not built -- fit it with cpprob_hip_batch_mstep_poisson_device");
     if (bs->scaled && !d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its draw takes d_sigmas");
@@ -6736,20 +6804,23 @@ int cpprob_hip_batch_retable_full(cpprob_hip_ctx* c, const double* h_means, cons
     return 0;
 }
 
-// cpprob_hip_batch_full_stats' arguments against the batch's state (batch_diag_stats_check's).
-static int batch_full_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& n_obs)
+// cpprob_hip_batch_full_stats' arguments against the batch's state (batch_diag_stats_check's).  reg: cpprob_hip_batch_reg_stats', the
+// same record of a regression batch at D = 1 + P (csrc/batch_reg.hpp).
+static int batch_full_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& n_obs, bool reg = false)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
     BatchState* bs = c->batch;
-    if (!bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions (cpprob_hip_batch_begin_problems_full): its statistics are its own family's");
+    if (reg && !bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no switching-regression emissions (cpprob_hip_batch_begin_problems_reg): its statistics are its own family's");
+    if (!reg && !bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions (cpprob_hip_batch_begin_problems_full): its statistics are its own family's");
     if (!stats || !observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     uint64_t rows = 0;
     for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
-    n_obs = rows * (uint64_t)bs->full_D;
+    const int D = reg ? 1 + bs->reg_P : bs->full_D;
+    n_obs = rows * (uint64_t)D;
     if ((uint64_t)n_observes != n_obs)
-        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->full_D) + " doubles");
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(D) + " doubles");
     const uint64_t need = (uint64_t)bs->cfg.n_problems * (uint64_t)kFullStats;
     if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (1304 a problem)");
     return 0;
@@ -6771,7 +6842,7 @@ static int batch_full_stats_enqueue(cpprob_hip_ctx* c, const double* d_obs, doub
     HIP_TRY(c, bs->d_full_g.grow(c->stream, (size_t)rows * 8 * sizeof(double)));
     BatchFullStatsArgs sa{};
     sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = d_obs; sa.g = bs->d_full_g.as<double>(); sa.stats = d_stats;
-    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->full_D; sa.thr_stride = a.thr_stride; sa.stats_stride = kFullStats;
+    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->reg ? 1 + bs->reg_P : bs->full_D; sa.thr_stride = a.thr_stride; sa.stats_stride = kFullStats;
     hipLaunchKernelGGL(batch_full_walk_kernel, dim3(std::min<unsigned>(pl.stats_gx, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(batch_full_moments_kernel, dim3(std::min<unsigned>((unsigned)sa.B, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
@@ -6833,6 +6904,138 @@ int cpprob_hip_batch_copy_full(cpprob_hip_ctx* c, uint64_t problem, double* h_me
     if (h_means) HIP_TRY(c, hipMemcpyAsync(h_means, bs->d_full_mean.as<double>() + problem * kFullMeanSlots, kFullMeanSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_factors) HIP_TRY(c, hipMemcpyAsync(h_factors, bs->d_full_L.as<double>() + problem * kFullTriSlots, kFullTriSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_full_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- switching-regression emissions of a batch (csrc/batch_reg.hpp) ------------------------------------------------------------------
+// Coefficients and sigmas on the host ([B][k][P], [B][k]): reg_check's bits 4 and 8, by name.
+static int batch_check_reg(cpprob_hip_ctx* c, uint64_t B, int k, int P, const double* h_coef, const double* h_sigmas, const double* h_transition)
+{
+    for (uint64_t b = 0; b < B; ++b) {
+        const int bits = reg_check(h_coef + b * (size_t)k * (size_t)P, h_sigmas + b * (size_t)k, h_transition + b * (size_t)k * (size_t)k, k, P);
+        if (bits & kRetableBadMean) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": regression coefficients must be finite");
+        if (bits & kRetableBadScale) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": sigmas must be finite and > 0, with a normal finite 2 pi sigma^2");
+    }
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems_reg(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
+                                        int32_t k_in, int32_t P, const double* h_coef, const double* h_sigmas, const double* h_transition)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_coef || !h_sigmas || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "switching-regression emissions serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    if (P < 1 || P > kRegMaxCov) return fail(c, CPPROB_HIP_EINVAL, "P, the covariates of a step, must lie in 1 .. 15");
+    if (k_in < 1 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "k must lie in 1 .. 8");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    if (int rc = batch_check_reg(c, cfg->n_problems, k_in, P, h_coef, h_sigmas, h_transition)) return rc;
+    // (the begin's route takes means [B][k]: zeros, which no regression row reads; the tables travel beside them)
+    const std::vector<double> zeros((size_t)cfg->n_problems * (size_t)k_in, 0.0);
+    if (!c->batch) c->batch = new BatchState();
+    c->batch->reg_begin_coef = h_coef; c->batch->reg_begin_sigmas = h_sigmas; c->batch->reg_begin_P = P;
+    const int rc = batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, zeros.data(), h_transition, nullptr, nullptr, kFamilyReg);
+    c->batch->reg_begin_coef = nullptr; c->batch->reg_begin_sigmas = nullptr; c->batch->reg_begin_P = 0;
+    return rc;
+}
+
+int cpprob_hip_batch_retable_reg_device(cpprob_hip_ctx* c, const double* d_coef, const double* d_sigmas, const double* d_transition, const double* d_observes,
+                                        size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyReg)) return rc;
+    if (!d_coef || !d_sigmas || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_coef, d_transition, d_observes, d_sigmas);
+}
+
+// The host form: the tables are validated with the begin's own statements, staged -- the coefficients and the sigmas in front, the
+// transition rows at the back -- and re-tabled as by the device form.
+int cpprob_hip_batch_retable_reg(cpprob_hip_ctx* c, const double* h_coef, const double* h_sigmas, const double* h_transition, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyReg)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_coef || !h_sigmas || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    const size_t B = bs->cfg.n_problems, kk = (size_t)bs->hk * bs->hk, kp = (size_t)bs->hk * (size_t)bs->reg_P;
+    int k = 0;
+    const std::vector<double> zeros(B * (size_t)bs->hk, 0.0);
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, zeros.data(), h_transition, k)) return rc;
+    if (int rc = batch_check_reg(c, B, k, bs->reg_P, h_coef, h_sigmas, h_transition)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_observes) if (int rc = batch_retable_observes(c, h_observes, n_observes)) return rc;
+    double *d_coef = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(B * (kp + (size_t)bs->hk) * sizeof(double)), B * kk * sizeof(double), d_coef, d_trans)) return rc;
+    double* d_sigmas = d_coef + B * kp;
+    HIP_TRY(c, hipMemcpyAsync(d_coef, h_coef, B * kp * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_sigmas, h_sigmas, B * (size_t)bs->hk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_coef, d_trans, bs->d_robs.as<double>(), d_sigmas)) return rc;
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    bs->thr_stale = false;
+    return 0;
+}
+
+// The E-step: the full family's walk and moments at D = 1 + P, behind the family check.
+int cpprob_hip_batch_reg_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_full_stats_check(c, d_observes, n_observes, d_stats, n_doubles, n_obs, true)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_full_stats_enqueue(c, d_observes, d_stats);
+}
+
+int cpprob_hip_batch_reg_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_full_stats_check(c, h_observes, n_observes, h_stats, n_doubles, n_obs, true)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kFullStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)n_obs, d_stats, d_obs)) return rc;
+    if (int rc = batch_full_stats_enqueue(c, d_obs, d_stats)) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
+}
+
+int cpprob_hip_batch_mstep_reg_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_coef, double* d_sigmas, double* d_transition, double* d_log_norms,
+                                      double sigma_floor)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no switching-regression emissions: its M-step is its own family's");
+    if (!d_stats || !d_coef || !d_sigmas || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!(sigma_floor > 0.0) || !std::isfinite(sigma_floor)) return fail(c, CPPROB_HIP_EINVAL, "sigma_floor must be finite and > 0");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kFullStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (1304 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepRegArgs a{};
+    a.stats = d_stats; a.coef = d_coef; a.sigmas = d_sigmas; a.log_norms = d_log_norms; a.trans = d_transition; a.floor = sigma_floor;
+    a.B = (int64_t)B; a.k = bs->hk; a.P = bs->reg_P;
+    hipLaunchKernelGGL(batch_mstep_reg_kernel, dim3((unsigned)std::min<uint64_t>((B + 1) / 2, (uint64_t)kRegMstepGridMax)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_reg(cpprob_hip_ctx* c, uint64_t problem, double* h_coef, double* h_sigmas, double* h_log_norms)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no switching-regression emissions (cpprob_hip_batch_begin_problems_reg)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_coef) HIP_TRY(c, hipMemcpyAsync(h_coef, bs->d_reg_coef.as<double>() + problem * kRegCoefSlots, kRegCoefSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_reg_sigma.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_reg_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }

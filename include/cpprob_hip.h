@@ -1113,6 +1113,48 @@ int cpprob_hip_batch_mstep_mix_device(cpprob_hip_ctx* ctx, const double* d_stats
 int cpprob_hip_batch_copy_mix(cpprob_hip_ctx* ctx, uint64_t problem, double* h_log_weights, double* h_means, double* h_sigmas,
                               double* h_log_norms);
 
+/* ---- switching-regression emissions of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_reg.hpp) --
+ * State s of problem b emits the scalar y_t ~ N(sum over i of coef[b][s][i] x_t[i], sigma[b][s]) on 1 <= P <= 15 covariates known at
+ * the step: coef [B][k][P], sigmas [B][k], and the observes 1 + P doubles a step, the response y_t first, then x_t[0] .. x_t[P-1]
+ * (n_observes counts doubles: 1 + P times the sum of the lengths).  An intercept is a covariate column of ones; the library adds none.
+ * The autoregressive HMM is the case x_t = (1, y_{t-1}, .., y_{t-p}) (cpprob_amd.reg.ar_design).  A batch is of one family: every call
+ * of one family on a batch of another returns CPPROB_HIP_ESTATE and the batch stays.  A regression batch is run, smoothed, counted,
+ * forecast and decoded by the calls above as they are.  A row is -0.5 (((y - pred) / sigma)^2 + log(2 pi sigma^2)) with
+ * pred = ((0.0 + coef_0 x_0) + coef_1 x_1) + ..; -inf where y or a covariate is infinite.  At P = 1 with the covariate identically 1.0
+ * rows, log_norms, threshold words and M-step are a scaled batch's bits.  tests/reg_ref.py restates every statement.
+ * cpprob_hip_batch_begin_problems_reg: cpprob_hip_batch_begin_problems with P, the coefficients and the sigmas.  P outside 1 .. 15, k
+ * outside 1 .. 8, a coefficient that is not finite or a sigma the scaled calls refuse: CPPROB_HIP_EINVAL, by problem.  There is no
+ * online regression begin.
+ * cpprob_hip_batch_retable_reg_device / _retable_reg: cpprob_hip_batch_retable_scaled_device / _retable_scaled with the coefficients
+ * in the means' place.  The device form checks on the device: bit 4 of cpprob_hip_batch_retable_status, a coefficient that is not
+ * finite; bit 8, a sigma; that problem keeps rows, thresholds and tables.
+ * cpprob_hip_batch_reg_stats_device / _reg_stats: the E-step, the record of cpprob_hip_batch_full_stats at D = 1 + P, 1304 doubles a
+ * problem: with z_t = (y_t, x_t), syy[s][i][j] = sum over t of g_t[s] (z_t[i] z_t[j]).
+ * cpprob_hip_batch_mstep_reg_device: on d_coef [B][k][P], d_sigmas [B][k] and d_transition [B][k][k] in place, from records of 1304
+ * doubles; d_log_norms [B][k], if not NULL, takes the new sigmas' log(2 pi sigma^2).  A state with mass solves the normal equations
+ * (sum g x x^T) beta = sum g x y through a square-root-free L D L^T factorisation (csrc/batch_reg.hpp: reg_mstep, every operation and
+ * its order), then sigma' = sqrt(v), v = sum g y y / occ - sum over i of beta_i (sum g x_i y / occ), where v >= sigma_floor^2, else
+ * sigma_floor (a NaN takes it too).  Where an entry read or a solved coefficient is not finite or a pivot is not > 0 and finite --
+ * collinear covariates -- the state keeps coefficients and sigma, as a state without mass.  sigma_floor finite and > 0, else
+ * CPPROB_HIP_EINVAL.  cpprob_amd.reg.m_step_reg, bit for bit.  Enqueued.
+ * On a regression batch the other families' re-tables, statistics and M-steps and cpprob_hip_batch_draw_tables_device (the Gibbs draw
+ * of its tables is not built) return CPPROB_HIP_ESTATE; cpprob_hip_batch_learn_begin* and _online_tables* do so because the batch is
+ * not online.
+ * cpprob_hip_batch_copy_reg: problem `problem`'s coefficients [8][16], sigmas [8] and log_norms [8] in force as the device holds them
+ * (slots outside the table 0.0; any may be NULL); synchronises; CPPROB_HIP_ESTATE: no batch begun, or no regression batch.  For tests. */
+int cpprob_hip_batch_begin_problems_reg(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                        const double* h_observes, int32_t k, int32_t P, const double* h_coef, const double* h_sigmas,
+                                        const double* h_transition);
+int cpprob_hip_batch_retable_reg_device(cpprob_hip_ctx* ctx, const double* d_coef, const double* d_sigmas, const double* d_transition,
+                                        const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_reg(cpprob_hip_ctx* ctx, const double* h_coef, const double* h_sigmas, const double* h_transition,
+                                 const double* h_observes, size_t n_observes);
+int cpprob_hip_batch_reg_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+int cpprob_hip_batch_reg_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+int cpprob_hip_batch_mstep_reg_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_coef, double* d_sigmas,
+                                      double* d_transition, double* d_log_norms, double sigma_floor);
+int cpprob_hip_batch_copy_reg(cpprob_hip_ctx* ctx, uint64_t problem, double* h_coef, double* h_sigmas, double* h_log_norms);
+
 /* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
  * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
  * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
