@@ -17,6 +17,7 @@ from .diag import hmm_diag_em, m_step_diag  # noqa: F401
 from .full import hmm_full_em, m_step_full  # noqa: F401
 from .mix import hmm_mix_em, m_step_mix  # noqa: F401
 from .reg import ar_design, hmm_reg_em, m_step_reg  # noqa: F401
+from .vreg import hmm_vreg_em, m_step_vreg, var_design  # noqa: F401
 from . import online_em  # noqa: F401
 from .online_em import hmm_table_online_em  # noqa: F401
 from . import gibbs  # noqa: F401

@@ -72,6 +72,8 @@ SYMBOLS = [
     "cpprob_hip_batch_mix_stats", "cpprob_hip_batch_mix_stats_device", "cpprob_hip_batch_mstep_mix_device", "cpprob_hip_batch_copy_mix",
     "cpprob_hip_batch_begin_problems_reg", "cpprob_hip_batch_retable_reg", "cpprob_hip_batch_retable_reg_device",
     "cpprob_hip_batch_reg_stats", "cpprob_hip_batch_reg_stats_device", "cpprob_hip_batch_mstep_reg_device", "cpprob_hip_batch_copy_reg",
+    "cpprob_hip_batch_begin_problems_vreg", "cpprob_hip_batch_retable_vreg", "cpprob_hip_batch_retable_vreg_device",
+    "cpprob_hip_batch_vreg_stats", "cpprob_hip_batch_vreg_stats_device", "cpprob_hip_batch_mstep_vreg_device", "cpprob_hip_batch_copy_vreg",
     "cpprob_hip_batch_learn_begin_scaled", "cpprob_hip_batch_learn_tables_scaled", "cpprob_hip_batch_learn_tables_scaled_device",
     "cpprob_hip_batch_tie", "cpprob_hip_batch_tie_get", "cpprob_hip_batch_pool_stats", "cpprob_hip_batch_pool_stats_device",
     "cpprob_hip_batch_learn_tie", "cpprob_hip_batch_learn_pooled_record",
@@ -236,6 +238,7 @@ SYMBOL_STATS_PER_PROBLEM = 88 + 8 * 64        # doubles a problem of cpprob_hip_
 DIAG_MAX_DIM = 32                             # cpprob_hip_batch_begin_problems_diag: D in 1 ..=
 FULL_MAX_DIM = 16                             # cpprob_hip_batch_begin_problems_full: D in 1 ..=
 REG_MAX_COV = 15                              # cpprob_hip_batch_begin_problems_reg: P in 1 ..=; a step holds 1 + P doubles
+VREG_MAX_COEF = 64                            # cpprob_hip_batch_begin_problems_vreg: Q, P >= 1 and Q + P <= FULL_MAX_DIM, so Q P <=
 FULL_TRI = 136                                # the packed lower triangle of a state: entry (i, j), j <= i, at i (i + 1) / 2 + j
 FULL_STATS_PER_PROBLEM = 1304                 # doubles a problem of cpprob_hip_batch_full_stats: the 88 above, sy[8][16], syy[8][136]
 MIX_MAX_DIM, MIX_MAX_COMP = 16, 8             # cpprob_hip_batch_begin_problems_mix: D and M in 1 ..=
@@ -524,6 +527,14 @@ def load_library(path=None):
         "cpprob_hip_batch_reg_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
         "cpprob_hip_batch_mstep_reg_device": (C.c_int, [vp, vp, sz, vp, vp, vp, vp, dbl]),
         "cpprob_hip_batch_copy_reg": (C.c_int, [vp, u64, vp, vp, vp]),
+        "cpprob_hip_batch_begin_problems_vreg": (C.c_int, [vp, C.POINTER(BatchConfig), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(dbl), C.c_int32, C.c_int32, C.c_int32,
+                                                          vp, vp, vp]),
+        "cpprob_hip_batch_retable_vreg": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_retable_vreg_device": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+        "cpprob_hip_batch_vreg_stats": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_vreg_stats_device": (C.c_int, [vp, vp, sz, vp, sz]),
+        "cpprob_hip_batch_mstep_vreg_device": (C.c_int, [vp, vp, sz, vp, vp, vp, dbl]),
+        "cpprob_hip_batch_copy_vreg": (C.c_int, [vp, u64, vp, vp, vp]),
         "cpprob_hip_batch_learn_begin_scaled": (C.c_int, [vp, vp, sz, C.c_uint32, dbl]),
         "cpprob_hip_batch_learn_tables_scaled": (C.c_int, [vp, vp, vp, vp, C.POINTER(i32)]),
         "cpprob_hip_batch_learn_tables_scaled_device": (C.c_int, [vp, vp, vp, vp]),
@@ -1412,6 +1423,81 @@ class Engine:
         cf, sg, ln = np.zeros((8, FULL_MAX_DIM)), np.zeros(8), np.zeros(8)
         self._chk(self.L.cpprob_hip_batch_copy_reg(self.h, int(b), cf.ctypes.data, sg.ctypes.data, ln.ctypes.data))
         return cf[:k, :P].copy(), sg[:k].copy(), ln[:k].copy()
+
+    # ---- Markov-switching vector regressions (include/cpprob_hip.h: cpprob_hip_batch_*_vreg, _vreg_stats*; csrc/batch_vreg.hpp) ----
+    def _batch_vreg_tables(self, coef, covs, trans, B):
+        cf = np.ascontiguousarray(coef, np.float64)
+        cv = np.ascontiguousarray(covs, np.float64)
+        tr = np.ascontiguousarray(trans, np.float64)
+        if cf.ndim != 4 or cf.shape[0] != B or cv.shape != cf.shape[:3] + cf.shape[2:3] or tr.shape != (B, cf.shape[1], cf.shape[1]):
+            raise ValueError("coef [B, k, Q, P], covs [B, k, Q, Q] and transition [B, k, k]")
+        return cf, cv, tr
+
+    def batch_begin_problems_vreg(self, observes, n_particles, coef, covs, trans, resampler=RESAMPLE_SYSTEMATIC, keep_history=True, keep_masses=False, max_particles=None):
+        """A MODEL_HMM_TABLE batch whose states regress a vector observe on covariates known at the step
+        (cpprob_hip_batch_begin_problems_vreg): observes a list of [T_b, Q + P] arrays, columns 0 .. Q-1 the responses y_t and the
+        rest the covariates x_t; coef [B, k, Q, P] and covs [B, k, Q, Q] (state s of problem b emits N(coef[b, s] x_t, covs[b, s]);
+        the lower triangle is read), trans [B, k, k]; k <= 8, Q + P <= 16.  An intercept is a column of ones.  Everything else as
+        batch_begin_problems."""
+        cf, cv, tr = self._batch_vreg_tables(coef, covs, trans, len(observes))
+        Q, P = cf.shape[2], cf.shape[3]
+        seqs = [np.ascontiguousarray(o, np.float64) for o in observes]
+        if Q >= 1 and P >= 1 and Q + P <= FULL_MAX_DIM and any(o.ndim != 2 or o.shape[1] != Q + P for o in seqs):    # (other Q, P: the library's own refusal)
+            raise ValueError("observes: one [T_b, Q + P] array a problem")
+        h_T, h_n = _problem_shapes([len(o) for o in seqs], n_particles)
+        flat = self._batch_packed_observes(seqs)
+        top = int(h_n.max()) if (max_particles is None and h_n.size) else int(max_particles or 0)
+        cfg = self.batch_config(MODEL_HMM_TABLE, top, len(seqs), resampler, 2.0, keep_history, ALG_SMC, _batch_flags(0, keep_masses))
+        self._chk(self.L.cpprob_hip_batch_begin_problems_vreg(self.h, C.byref(cfg), h_T.ctypes.data_as(C.POINTER(C.c_uint32)), h_n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                              flat.ctypes.data_as(C.POINTER(C.c_double)), cf.shape[1], Q, P, cf.ctypes.data, cv.ctypes.data, tr.ctypes.data))
+        self.batch_B, self.batch_T, self.batch_n = len(seqs), int(h_T.max()), top
+        self.batch_K, self.batch_k, self.batch_D, self.batch_Q = 8, cf.shape[1], Q + P, Q
+        self.batch_shapes = (h_T, h_n)
+        return self
+
+    def batch_retable_vreg(self, coef, covs, trans, observes=None):
+        """New coefficients, covariances and transition rows for the begun vector-regression batch where it stands
+        (cpprob_hip_batch_retable_vreg), validated as the begin validates them; observes as the begin takes them, or None once a
+        re-table has staged them."""
+        cf, cv, tr = self._batch_vreg_tables(coef, covs, trans, self.batch_B)
+        flat = None if observes is None else self._batch_packed_observes(list(observes))
+        n_obs = int(np.sum(self.batch_shapes[0], dtype=np.int64)) * getattr(self, "batch_D", 1) if flat is None else flat.size
+        self._chk(self.L.cpprob_hip_batch_retable_vreg(self.h, cf.ctypes.data, cv.ctypes.data, tr.ctypes.data, None if flat is None or flat.size == 0 else flat.ctypes.data, n_obs))
+
+    def batch_retable_vreg_device(self, coef, covs, trans, observes):
+        """The same between torch float64 device tensors (coef [B, k, Q, P], covs [B, k, Q, Q], trans [B, k, k], observes packed,
+        Q + P doubles a step), enqueued without a host synchronisation; the tables are checked on the device (batch_retable_status:
+        bit 4, a coefficient that is not finite; bit 64, a covariance that does not factor)."""
+        self._chk(self.L.cpprob_hip_batch_retable_vreg_device(self.h, _dptr(coef), _dptr(covs), _dptr(trans), _dptr(observes), 0 if observes is None else observes.numel()))
+
+    def batch_vreg_stats(self, observes):
+        """The E-step of a vector-regression batch (cpprob_hip_batch_vreg_stats): batch_full_stats' dict over z_t = (y_t, x_t), so
+        that syy[b, s, :Q, :Q] is the visits of state s weighted by y y^T, syy[b, s, Q:, :Q] by x y^T and syy[b, s, Q:, Q:] by x x^T."""
+        rec = np.zeros((self.batch_B, FULL_STATS_PER_PROBLEM))
+        flat = self._batch_packed_observes(list(observes))
+        self._chk(self.L.cpprob_hip_batch_vreg_stats(self.h, flat.ctypes.data if flat.size else None, flat.size, rec.ctypes.data, rec.size))
+        return split_full_stats(rec)
+
+    def batch_vreg_stats_device(self, stats, observes):
+        """The same left in a device tensor: stats torch float64 [B, 1304], observes a torch float64 tensor packed problem after
+        problem, Q + P doubles a step."""
+        self._chk(self.L.cpprob_hip_batch_vreg_stats_device(self.h, _dptr(observes), 0 if observes is None else observes.numel(), _dptr(stats), stats.numel()))
+
+    def batch_mstep_vreg_device(self, stats, coef, covs, trans, var_floor=1e-6):
+        """vreg.m_step_vreg on the device (cpprob_hip_batch_mstep_vreg_device): stats torch float64 [B, 1304]; coef [B, k, Q, P], covs
+        [B, k, Q, Q] and trans [B, k, k] torch float64, updated in place; no fitted variance below var_floor^2.  Enqueued."""
+        self._chk(self.L.cpprob_hip_batch_mstep_vreg_device(self.h, _dptr(stats), stats.numel(), _dptr(coef), _dptr(covs), _dptr(trans), float(var_floor)))
+
+    def batch_copy_vreg(self, b, k=None, Q=None, P=None):
+        """(coef [k, Q, P], factors [k, Q, Q] lower-triangular, log_norms [k]) of problem b of a vector-regression batch, as the device
+        holds them (cpprob_hip_batch_copy_vreg).  Synchronises.  For tests."""
+        k, Q = int(k if k is not None else self.batch_k), int(Q if Q is not None else self.batch_Q)
+        P = int(P if P is not None else self.batch_D - Q)
+        cf, tri, ln = np.zeros((8, VREG_MAX_COEF)), np.zeros((8, FULL_TRI)), np.zeros(8)
+        self._chk(self.L.cpprob_hip_batch_copy_vreg(self.h, int(b), cf.ctypes.data, tri.ctypes.data, ln.ctypes.data))
+        L = np.zeros((8, FULL_MAX_DIM, FULL_MAX_DIM))
+        L[:, _FULL_I, _FULL_J] = tri
+        return cf[:k, :Q * P].reshape(k, Q, P).copy(), L[:k, :Q, :Q].copy(), ln[:k].copy()
 
     # ---- online EM of an online batch (include/cpprob_hip.h: cpprob_hip_batch_learn_*) ------------------------------
     def _batch_tables(self, tables):

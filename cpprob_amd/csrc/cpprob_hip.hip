@@ -36,6 +36,7 @@
 #include "batch_full.hpp"
 #include "batch_mix.hpp"
 #include "batch_reg.hpp"
+#include "batch_vreg.hpp"
 #include "batch_learn.hpp"
 #include "batch_learn_tied.hpp"
 #include "batch_pass_plan.hpp"
@@ -1016,7 +1017,7 @@ void poisson_step_ll(double y, const double* rate, const double* log_rate, const
 }
 // The emission family of a table batch and of a call that hands tables over: N(mean, 1), N(mean, sigma) or Poisson(rate); kFamilyDiag: a
 // vector with independent Gaussian coordinates (csrc/batch_diag.hpp), D doubles a step, begun, re-tabled and fitted by its own calls.
-enum EmissionFamily { kFamilyUnit = 0, kFamilyScaled = 1, kFamilyPoisson = 2, kFamilyDiag = 4 };
+enum EmissionFamily { kFamilyUnit = 0, kFamilyScaled = 1, kFamilyPoisson = 2, kFamilyDiag = 4, kFamilyVreg = 8 };
 // ... or a symbol of a finite alphabet (csrc/batch_categorical.hpp): the fourth family, begun, re-tabled and fitted by its own calls
 constexpr EmissionFamily kFamilyCategorical = (EmissionFamily)3;
 // a categorical table's row, with the statements the device's re-table writes it with: log_e [8][64], slots outside the table -inf
@@ -1140,6 +1141,34 @@ __attribute__((noinline)) void reg_expand_tables(size_t B, int k, int P, const d
             for (size_t i = 0; i < (size_t)P; ++i) coef[b * kRegCoefSlots + s * kFullMaxDim + i] = h_coef[(b * (size_t)k + s) * (size_t)P + i];
             sigma[b * 8 + s] = h_sigmas[b * (size_t)k + s];
             log_norm[b * 8 + s] = scale_log_norm(h_sigmas[b * (size_t)k + s]);
+        }
+}
+// ... or a vector regressed on covariates known at the step, with a full residual covariance (csrc/batch_vreg.hpp): the ninth family,
+// begun, re-tabled and fitted by its own calls (kFamilyVreg = 8 stands in the enumeration: a value past 7 needs its fourth bit)
+// a vector-regression problem's rows, with the statements the device's re-table writes them with: coef [8][64], L [8][136] packed,
+// log_norm [8] (kept out of line: batch_begin's own loop stays the other families')
+__attribute__((noinline)) void vreg_problem_rows(const double* z, size_t T, int Q, int P, const double* coef, const double* L, const double* log_norm, int k, double* rows)
+{
+    for (size_t t = 0; t < T; ++t)
+        for (int s2 = 0; s2 < 8; ++s2)
+            rows[t * kBatchTab + s2] = s2 < k ? vreg_entry(z + t * (size_t)(Q + P), Q, P, coef + (size_t)s2 * kVregCoefs, 1, L + (size_t)s2 * kFullTri, 1, log_norm[s2]) : -INFINITY;
+}
+// the tables of a vector-regression begin (coef [B][k][Q][P], covs [B][k][Q][Q], checked: every covariance factors) in the device's
+// layout, [B][8][64], [B][8][136] and [B][8]: slots outside the table 0.0
+__attribute__((noinline)) void vreg_expand_tables(size_t B, int k, int Q, int P, const double* h_coef, const double* h_covs, std::vector<double>& coef, std::vector<double>& L,
+                                                  std::vector<double>& log_norm)
+{
+    coef.assign(B * kVregCoefSlots, 0.0); L.assign(B * kFullTriSlots, 0.0); log_norm.assign(B * 8, 0.0);
+    const size_t QP = (size_t)Q * (size_t)P;
+    for (size_t b = 0; b < B; ++b)
+        for (size_t s = 0; s < (size_t)k; ++s) {
+            double* Ls = &L[b * kFullTriSlots + s * kFullTri];
+            const double* cov = h_covs + (b * (size_t)k + s) * (size_t)Q * (size_t)Q;
+            for (size_t e = 0; e < QP; ++e) coef[b * kVregCoefSlots + s * kVregCoefs + e] = h_coef[(b * (size_t)k + s) * QP + e];
+            for (int i = 0; i < Q; ++i)
+                for (int j = 0; j <= i; ++j) Ls[full_tri(i, j)] = cov[(size_t)i * Q + j];
+            (void)full_factor(Ls, 1, Q, Ls, 1);
+            log_norm[b * 8 + s] = full_log_norm(Ls, 1, Q);
         }
 }
 std::vector<uint64_t> hmmk_thresholds(const std::vector<double>& trans, int k)
@@ -1351,6 +1380,16 @@ struct BatchState {
     DeviceBuffer d_reg_coef, d_reg_sigma, d_reg_lognorm;
     const double *reg_begin_coef = nullptr, *reg_begin_sigmas = nullptr;
     int reg_begin_P = 0;
+    // Markov-switching vector regressions (cpprob_hip_batch_begin_problems_vreg; csrc/batch_vreg.hpp): vreg: the begun batch has them, and
+    // is then of no other family; vreg_Q its responses and vreg_P its covariates, and every observes array of its calls holds
+    // vreg_Q + vreg_P doubles a step.  The coefficients [B][8][64], packed factors [B][8][136] and log_norms [B][8] in force are the
+    // device's alone; the E-step is the full family's, at D = vreg_Q + vreg_P, with its workspace d_full_g.  vreg_begin_*: the checked
+    // arguments of the begin in progress
+    bool vreg = false;
+    int vreg_Q = 0, vreg_P = 0;
+    DeviceBuffer d_vreg_coef, d_vreg_L, d_vreg_lognorm;
+    const double *vreg_begin_coef = nullptr, *vreg_begin_covs = nullptr;
+    int vreg_begin_Q = 0, vreg_begin_P = 0;
     // a tie (cpprob_hip_batch_tie; csrc/batch_pool.hpp): tied: the begun batch's problems are partitioned into tie_groups groups; one
     // allocation of the context's own holds the members sorted by (group, problem) [B], the groups' first positions [G + 1] and the
     // map problem -> group [B]; tie_map is the host's copy of the map.  A re-table keeps it, any begin forgets it.
@@ -1565,7 +1604,17 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, bs->d_reg_sigma.grow(c->stream, rg_sigma.size() * sizeof(double)));
         HIP_TRY(c, bs->d_reg_lognorm.grow(c->stream, rg_lognorm.size() * sizeof(double)));
     }
-    const size_t obs_stride = diag ? (size_t)diag_D : full ? (size_t)full_D : mix ? (size_t)mix_D : reg ? (size_t)(1 + reg_P) : 1;    // doubles a step of h_obs
+    const bool vreg = family == kFamilyVreg;                    // (as a diagonal begin: the tables are bs->vreg_begin_*)
+    bs->vreg = false;
+    std::vector<double> vr_coef, vr_L, vr_lognorm;              // (live until the synchronisation below)
+    const int vreg_Q = vreg ? bs->vreg_begin_Q : 0, vreg_P = vreg ? bs->vreg_begin_P : 0;
+    if (vreg) {
+        vreg_expand_tables((size_t)B, k, vreg_Q, vreg_P, bs->vreg_begin_coef, bs->vreg_begin_covs, vr_coef, vr_L, vr_lognorm);
+        HIP_TRY(c, bs->d_vreg_coef.grow(c->stream, vr_coef.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_vreg_L.grow(c->stream, vr_L.size() * sizeof(double)));
+        HIP_TRY(c, bs->d_vreg_lognorm.grow(c->stream, vr_lognorm.size() * sizeof(double)));
+    }
+    const size_t obs_stride = diag ? (size_t)diag_D : full ? (size_t)full_D : mix ? (size_t)mix_D : reg ? (size_t)(1 + reg_P) : vreg ? (size_t)(vreg_Q + vreg_P) : 1;    // doubles a step of h_obs
     std::vector<double> mean, trans;
     if (!hmm3 && !own) { mean = c->hk_mean; trans = c->hk_trans; }
     std::vector<uint64_t> thr;
@@ -1581,7 +1630,8 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         if (full) full_problem_rows(h_obs + at_obs * obs_stride, T_b, full_D, &fl_mean[b * kFullMeanSlots], &fl_L[b * kFullTriSlots], &fl_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
         if (mix) mix_problem_rows(h_obs + at_obs * obs_stride, T_b, mix_D, mix_M, &mx_lw[b * kMixComps], &mx_ln[b * kMixComps], &mx_mean[b * kMixSlots], &mx_sigma[b * kMixSlots], k, &bs->h_tab[b * T_max * kBatchTab]);
         if (reg) reg_problem_rows(h_obs + at_obs * obs_stride, T_b, reg_P, &rg_coef[b * kRegCoefSlots], &rg_sigma[b * 8], &rg_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
-        for (size_t t = 0; t < (online || diag || full || mix || reg ? 0 : T_b); ++t) {
+        if (vreg) vreg_problem_rows(h_obs + at_obs * obs_stride, T_b, vreg_Q, vreg_P, &vr_coef[b * kVregCoefSlots], &vr_L[b * kFullTriSlots], &vr_lognorm[b * 8], k, &bs->h_tab[b * T_max * kBatchTab]);
+        for (size_t t = 0; t < (online || diag || full || mix || reg || vreg ? 0 : T_b); ++t) {
             const double y = h_obs[at_obs + t];
             double* row = &bs->h_tab[(b * T_max + t) * kBatchTab];
             if (hmm3) hmm3_step_table(y, bs->mp.hmm_mean, row, row + 3, row[6]);
@@ -1634,6 +1684,11 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
         HIP_TRY(c, hipMemcpyAsync(bs->d_reg_sigma.as<double>(), rg_sigma.data(), rg_sigma.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(bs->d_reg_lognorm.as<double>(), rg_lognorm.data(), rg_lognorm.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
+    if (vreg) {
+        HIP_TRY(c, hipMemcpyAsync(bs->d_vreg_coef.as<double>(), vr_coef.data(), vr_coef.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_vreg_L.as<double>(), vr_L.data(), vr_L.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(bs->d_vreg_lognorm.as<double>(), vr_lognorm.data(), vr_lognorm.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     std::vector<int32_t> order;                               // (lives until the synchronisation below)
     std::vector<char> ctrl0;
     if (online) {
@@ -1669,6 +1724,7 @@ int batch_begin(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, size_t T_
     bs->full = full; bs->full_D = full_D;
     bs->mix = mix; bs->mix_D = mix_D; bs->mix_M = mix_M;
     bs->reg = reg; bs->reg_P = reg_P;
+    bs->vreg = vreg; bs->vreg_Q = vreg_Q; bs->vreg_P = vreg_P;
     bs->begun = true; bs->ran = online;         // (an online batch has results from its begin on: those of no observes)
     return 0;
 }
@@ -5511,6 +5567,7 @@ static int batch_smooth_stats_check(cpprob_hip_ctx* c, bool with_obs, size_t n_o
     if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its statistics are cpprob_hip_batch_full_stats / _full_stats_device");
     if (c->batch->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: its statistics are cpprob_hip_batch_mix_stats / _mix_stats_device");
     if (c->batch->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: its statistics are cpprob_hip_batch_reg_stats / _reg_stats_device");
+    if (c->batch->vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has vector-regression emissions: its statistics are cpprob_hip_batch_vreg_stats / _vreg_stats_device");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
     rows = 0;
@@ -5618,6 +5675,7 @@ static int batch_traj_stats_check(cpprob_hip_ctx* c, uint64_t n_traj, uint64_t d
     if (c->batch->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (c->batch->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: the trajectory statistics take one observe a step and do not serve it");
     if (c->batch->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: the trajectory statistics take one observe a step and do not serve it");
+    if (c->batch->vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has vector-regression emissions: the trajectory statistics take one observe a step and do not serve it");
     if (n_traj == 0) return fail(c, CPPROB_HIP_EINVAL, "n_traj must lie in 1 .. 2^20");
     if (!stats) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     BatchState* bs = c->batch;
@@ -5921,7 +5979,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
     if (!bs->described) return fail(c, CPPROB_HIP_EUNSUPPORTED, "a batch begun by cpprob_hip_batch_begin shares one table: begin it with cpprob_hip_batch_begin_problems to re-table it");
     const bool scaled = family == kFamilyScaled, poisson = family == kFamilyPoisson;
     const bool categorical = family == kFamilyCategorical, diag = family == kFamilyDiag, full = family == kFamilyFull, mix = family == kFamilyMix;
-    const bool reg = family == kFamilyReg;
+    const bool reg = family == kFamilyReg, vreg = family == kFamilyVreg;
+    if (bs->vreg && !vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has vector-regression emissions: it is re-tabled by cpprob_hip_batch_retable_vreg / _retable_vreg_device");
+    if (!bs->vreg && vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no vector-regression emissions: begin it with cpprob_hip_batch_begin_problems_vreg, or re-table it with its own family's calls");
     if (bs->reg && !reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: it is re-tabled by cpprob_hip_batch_retable_reg / _retable_reg_device");
     if (!bs->reg && reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no switching-regression emissions: begin it with cpprob_hip_batch_begin_problems_reg, or re-table it with its own family's calls");
     if (bs->mix && !mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: it is re-tabled by cpprob_hip_batch_retable_mix / _retable_mix_device");
@@ -5946,7 +6006,9 @@ static int batch_retable_check(cpprob_hip_ctx* c, size_t n_observes, EmissionFam
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->mix_D) + " doubles");
     if (reg && (uint64_t)n_observes != rows * (uint64_t)(1 + bs->reg_P))
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(1 + bs->reg_P) + " doubles");
-    if (!diag && !full && !mix && !reg && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
+    if (vreg && (uint64_t)n_observes != rows * (uint64_t)(bs->vreg_Q + bs->vreg_P))
+        return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(bs->vreg_Q + bs->vreg_P) + " doubles");
+    if (!diag && !full && !mix && !reg && !vreg && (uint64_t)n_observes != rows) return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows));
     return 0;
 }
 
@@ -5969,6 +6031,15 @@ static int batch_retable_enqueue(cpprob_hip_ctx* c, const double* d_means, const
         r.status = bs->d_rstatus.as<int32_t>();
         r.T_max = bs->T; r.k = bs->hk;
     };
+    if (bs->vreg) {
+        // (a vector-regression batch: d_means the coefficients [B][k][Q][P] and d_sigmas the covariances [B][k][Q][Q]; the tables in force
+        // are the device's)
+        BatchRetableVregArgs va{};
+        common(va);
+        va.coef = d_means; va.covs = d_sigmas; va.Q = bs->vreg_Q; va.P = bs->vreg_P;
+        va.coef_out = bs->d_vreg_coef.as<double>(); va.L_out = bs->d_vreg_L.as<double>(); va.log_norm_out = bs->d_vreg_lognorm.as<double>();
+        hipLaunchKernelGGL(batch_retable_vreg_kernel, dim3((unsigned)B, gy), dim3(kThreads), 0, c->stream, va);
+    } else
     if (bs->reg) {
         // (a regression batch: d_means the coefficients [B][k][P] and d_sigmas [B][k]; the tables in force are the device's)
         BatchRetableRegArgs ra{};
@@ -6167,6 +6238,7 @@ static int batch_mstep_device(cpprob_hip_ctx* c, const double* d_stats, size_t n
     if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: its M-step is cpprob_hip_batch_mstep_full_device");
     if (bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: its M-step is cpprob_hip_batch_mstep_mix_device");
     if (bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: its M-step is cpprob_hip_batch_mstep_reg_device");
+    if (bs->vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has vector-regression emissions: its M-step is cpprob_hip_batch_mstep_vreg_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: its M-step is cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson && !poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: its M-step is cpprob_hip_batch_mstep_poisson_device");
     if (!bs->poisson && poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has no Poisson emissions: its M-step is cpprob_hip_batch_mstep_device / _mstep_scaled_device");
@@ -6228,6 +6300,7 @@ int cpprob_hip_batch_draw_tables_device(cpprob_hip_ctx* c, const double* d_stats
     if (bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has full-covariance Gaussian vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_full_device");
     if (bs->mix) return fail(c, CPPROB_HIP_ESTATE, "the batch has Gaussian-mixture vector emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_mix_device");
     if (bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has switching-regression emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_reg_device");
+    if (bs->vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has vector-regression emissions: the conjugate draw of its tables is not built -- fit it with cpprob_hip_batch_mstep_vreg_device");
     if (bs->categorical) return fail(c, CPPROB_HIP_ESTATE, "the batch has categorical emissions: the conjugate (Dirichlet) draw of its matrix is not built -- fit it with cpprob_hip_batch_mstep_categorical_device");
     if (bs->poisson) return fail(c, CPPROB_HIP_ESTATE, "the batch has Poisson emissions: the conjugate (gamma) draw of its rates is not built -- fit it with cpprob_hip_batch_mstep_poisson_device");
     if (bs->scaled && !d_sigmas) return fail(c, CPPROB_HIP_ESTATE, "the batch has emission scales: its draw takes d_sigmas");
@@ -6805,19 +6878,22 @@ int cpprob_hip_batch_retable_full(cpprob_hip_ctx* c, const double* h_means, cons
 }
 
 // cpprob_hip_batch_full_stats' arguments against the batch's state (batch_diag_stats_check's).  reg: cpprob_hip_batch_reg_stats', the
-// same record of a regression batch at D = 1 + P (csrc/batch_reg.hpp).
-static int batch_full_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& n_obs, bool reg = false)
+// same record of a regression batch at D = 1 + P (csrc/batch_reg.hpp); vreg: cpprob_hip_batch_vreg_stats', at D = Q + P
+// (csrc/batch_vreg.hpp).
+static int batch_full_stats_check(cpprob_hip_ctx* c, const double* observes, size_t n_observes, const double* stats, size_t n_doubles, uint64_t& n_obs, bool reg = false,
+                                  bool vreg = false)
 {
     if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
     uint64_t doubles = 0, entries = 0;
     if (int rc = batch_smooth_check(c, 0, 0, false, 0, false, 0, doubles, entries)) return rc;
     BatchState* bs = c->batch;
     if (reg && !bs->reg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no switching-regression emissions (cpprob_hip_batch_begin_problems_reg): its statistics are its own family's");
-    if (!reg && !bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions (cpprob_hip_batch_begin_problems_full): its statistics are its own family's");
+    if (vreg && !bs->vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no vector-regression emissions (cpprob_hip_batch_begin_problems_vreg): its statistics are its own family's");
+    if (!reg && !vreg && !bs->full) return fail(c, CPPROB_HIP_ESTATE, "the batch has no full-covariance Gaussian vector emissions (cpprob_hip_batch_begin_problems_full): its statistics are its own family's");
     if (!stats || !observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
     uint64_t rows = 0;
     for (const BatchProblem& pr : bs->prob) rows += (uint64_t)pr.T;
-    const int D = reg ? 1 + bs->reg_P : bs->full_D;
+    const int D = vreg ? bs->vreg_Q + bs->vreg_P : reg ? 1 + bs->reg_P : bs->full_D;
     n_obs = rows * (uint64_t)D;
     if ((uint64_t)n_observes != n_obs)
         return fail(c, CPPROB_HIP_EINVAL, "n_observes = " + std::to_string(n_observes) + ", the problems' lengths sum to " + std::to_string(rows) + " steps of " + std::to_string(D) + " doubles");
@@ -6842,7 +6918,7 @@ static int batch_full_stats_enqueue(cpprob_hip_ctx* c, const double* d_obs, doub
     HIP_TRY(c, bs->d_full_g.grow(c->stream, (size_t)rows * 8 * sizeof(double)));
     BatchFullStatsArgs sa{};
     sa.desc = a.desc; sa.mass = a.mass; sa.thr = a.thr; sa.obs = d_obs; sa.g = bs->d_full_g.as<double>(); sa.stats = d_stats;
-    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->reg ? 1 + bs->reg_P : bs->full_D; sa.thr_stride = a.thr_stride; sa.stats_stride = kFullStats;
+    sa.B = (int)bs->cfg.n_problems; sa.k = a.k; sa.D = bs->vreg ? bs->vreg_Q + bs->vreg_P : bs->reg ? 1 + bs->reg_P : bs->full_D; sa.thr_stride = a.thr_stride; sa.stats_stride = kFullStats;
     hipLaunchKernelGGL(batch_full_walk_kernel, dim3(std::min<unsigned>(pl.stats_gx, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(batch_full_moments_kernel, dim3(std::min<unsigned>((unsigned)sa.B, (unsigned)kSymbolGridMax)), dim3(kThreads), 0, c->stream, sa);
@@ -7036,6 +7112,141 @@ int cpprob_hip_batch_copy_reg(cpprob_hip_ctx* c, uint64_t problem, double* h_coe
     if (h_coef) HIP_TRY(c, hipMemcpyAsync(h_coef, bs->d_reg_coef.as<double>() + problem * kRegCoefSlots, kRegCoefSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_sigmas) HIP_TRY(c, hipMemcpyAsync(h_sigmas, bs->d_reg_sigma.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_reg_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- Markov-switching vector regressions of a batch (csrc/batch_vreg.hpp) -------------------------------------------------------------
+// Coefficients and covariances on the host ([B][k][Q][P], [B][k][Q][Q]): vreg_check's bits 4 and 64, by name.
+static int batch_check_vreg(cpprob_hip_ctx* c, uint64_t B, int k, int Q, int P, const double* h_coef, const double* h_covs, const double* h_transition)
+{
+    const size_t kq = (size_t)k * (size_t)Q;
+    for (uint64_t b = 0; b < B; ++b) {
+        const int bits = vreg_check(h_coef + b * kq * (size_t)P, h_covs + b * kq * (size_t)Q, h_transition + b * (size_t)k * (size_t)k, k, Q, P);
+        if (bits & kRetableBadMean) return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": regression coefficients must be finite");
+        if (bits & kRetableBadCov)
+            return fail(c, CPPROB_HIP_EINVAL, "problem " + std::to_string(b) + ": a covariance does not factor (lower triangle finite, pivots > 0 with a normal finite 2 pi pivot^2)");
+    }
+    return 0;
+}
+
+int cpprob_hip_batch_begin_problems_vreg(cpprob_hip_ctx* c, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n, const double* h_obs,
+                                         int32_t k_in, int32_t Q, int32_t P, const double* h_coef, const double* h_covs, const double* h_transition)
+{
+    LANES_OWN(c);
+    if (!c || !cfg || !h_T || !h_n || !h_obs || !h_coef || !h_covs || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (cfg->model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "vector-regression emissions serve CPPROB_HIP_MODEL_HMM_TABLE with per-problem tables");
+    if (Q < 1 || P < 1 || Q > kFullMaxDim || P > kFullMaxDim || Q + P > kFullMaxDim)
+        return fail(c, CPPROB_HIP_EINVAL, "Q, the responses, and P, the covariates of a step, must be at least 1 each and at most 16 together");
+    if (k_in < 1 || k_in > 8) return fail(c, CPPROB_HIP_EINVAL, "k must lie in 1 .. 8");
+    std::string msg;
+    BatchProblemsShape sh;
+    if (int rc = batch_check_problems(cfg, h_T, h_n, sh, msg)) return fail(c, rc, msg);
+    if (int rc = batch_check_vreg(c, cfg->n_problems, k_in, Q, P, h_coef, h_covs, h_transition)) return rc;
+    // (the begin's route takes means [B][k]: zeros, which no row of this family reads; the tables travel beside them)
+    const std::vector<double> zeros((size_t)cfg->n_problems * (size_t)k_in, 0.0);
+    if (!c->batch) c->batch = new BatchState();
+    c->batch->vreg_begin_coef = h_coef; c->batch->vreg_begin_covs = h_covs; c->batch->vreg_begin_Q = Q; c->batch->vreg_begin_P = P;
+    const int rc = batch_begin_described(c, cfg, h_T, h_n, h_obs, k_in, zeros.data(), h_transition, nullptr, nullptr, kFamilyVreg);
+    c->batch->vreg_begin_coef = nullptr; c->batch->vreg_begin_covs = nullptr; c->batch->vreg_begin_Q = 0; c->batch->vreg_begin_P = 0;
+    return rc;
+}
+
+int cpprob_hip_batch_retable_vreg_device(cpprob_hip_ctx* c, const double* d_coef, const double* d_covs, const double* d_transition, const double* d_observes,
+                                         size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyVreg)) return rc;
+    if (!d_coef || !d_covs || !d_transition || !d_observes) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_retable_enqueue(c, d_coef, d_transition, d_observes, d_covs);
+}
+
+// The host form: the tables are validated with the begin's own statements, staged -- the coefficients and the covariances in front, the
+// transition rows at the back -- and re-tabled as by the device form.
+int cpprob_hip_batch_retable_vreg(cpprob_hip_ctx* c, const double* h_coef, const double* h_covs, const double* h_transition, const double* h_observes, size_t n_observes)
+{
+    LANES_OWN(c);
+    if (int rc = batch_retable_check(c, n_observes, kFamilyVreg)) return rc;
+    BatchState* bs = c->batch;
+    if (!h_coef || !h_covs || !h_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!h_observes && !bs->robs_ready) return fail(c, CPPROB_HIP_EINVAL, "h_observes is NULL and no re-table of this begun batch has staged the observes");
+    const size_t B = bs->cfg.n_problems, kk = (size_t)bs->hk * bs->hk, kqp = (size_t)bs->hk * (size_t)bs->vreg_Q * (size_t)bs->vreg_P;
+    const size_t kqq = (size_t)bs->hk * (size_t)bs->vreg_Q * (size_t)bs->vreg_Q;
+    int k = 0;
+    const std::vector<double> zeros(B * (size_t)bs->hk, 0.0);
+    if (int rc = batch_check_tables(c, &bs->cfg, (int32_t)bs->hk, zeros.data(), h_transition, k)) return rc;
+    if (int rc = batch_check_vreg(c, B, k, bs->vreg_Q, bs->vreg_P, h_coef, h_covs, h_transition)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_observes) if (int rc = batch_retable_observes(c, h_observes, n_observes)) return rc;
+    double *d_coef = nullptr, *d_trans = nullptr;
+    if (int rc = batch_stage(c, batch_round(B * (kqp + kqq) * sizeof(double)), B * kk * sizeof(double), d_coef, d_trans)) return rc;
+    double* d_covs = d_coef + B * kqp;
+    HIP_TRY(c, hipMemcpyAsync(d_coef, h_coef, B * kqp * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_covs, h_covs, B * kqq * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_trans, h_transition, B * kk * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (int rc = batch_retable_enqueue(c, d_coef, d_trans, bs->d_robs.as<double>(), d_covs)) return rc;
+    for (size_t b = 0; b < B; ++b) retable_thresholds(h_transition + b * kk, k, bs->h_thr.data() + b * 64);
+    bs->thr_stale = false;
+    return 0;
+}
+
+// The E-step: the full family's walk and moments at D = Q + P, behind the family check.
+int cpprob_hip_batch_vreg_stats_device(cpprob_hip_ctx* c, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_full_stats_check(c, d_observes, n_observes, d_stats, n_doubles, n_obs, false, true)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    return batch_full_stats_enqueue(c, d_observes, d_stats);
+}
+
+int cpprob_hip_batch_vreg_stats(cpprob_hip_ctx* c, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles)
+{
+    LANES_OWN(c);
+    uint64_t n_obs = 0;
+    if (int rc = batch_full_stats_check(c, h_observes, n_observes, h_stats, n_doubles, n_obs, false, true)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_stats = (size_t)c->batch->cfg.n_problems * kFullStats;
+    double *d_stats = nullptr, *d_obs = nullptr;
+    if (int rc = batch_stage_observes(c, n_stats, h_observes, (size_t)n_obs, d_stats, d_obs)) return rc;
+    if (int rc = batch_full_stats_enqueue(c, d_obs, d_stats)) return rc;
+    return batch_fetch(c, nullptr, nullptr, 0, h_stats, d_stats, n_stats);
+}
+
+int cpprob_hip_batch_mstep_vreg_device(cpprob_hip_ctx* c, const double* d_stats, size_t n_doubles, double* d_coef, double* d_covs, double* d_transition, double var_floor)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (bs->cfg.model != CPPROB_HIP_MODEL_HMM_TABLE) return fail(c, CPPROB_HIP_EUNSUPPORTED, "the M-step fits the tables of CPPROB_HIP_MODEL_HMM_TABLE");
+    if (!bs->vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no vector-regression emissions: its M-step is its own family's");
+    if (!d_stats || !d_coef || !d_covs || !d_transition) return fail(c, CPPROB_HIP_EINVAL, "NULL argument");
+    if (!(var_floor > 0.0) || !std::isfinite(var_floor)) return fail(c, CPPROB_HIP_EINVAL, "var_floor must be finite and > 0");
+    const uint64_t B = bs->cfg.n_problems, need = B * (uint64_t)kFullStats;
+    if (n_doubles < need) return fail(c, CPPROB_HIP_EINVAL, "the statistics buffer is too small: " + std::to_string(need) + " doubles (1304 a problem)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    BatchMstepVregArgs a{};
+    a.stats = d_stats; a.coef = d_coef; a.covs = d_covs; a.trans = d_transition; a.floor = var_floor;
+    a.B = (int64_t)B; a.k = bs->hk; a.Q = bs->vreg_Q; a.P = bs->vreg_P;
+    hipLaunchKernelGGL(batch_mstep_vreg_kernel, dim3((unsigned)std::min<uint64_t>((B + 1) / 2, (uint64_t)kRegMstepGridMax)), dim3(kThreads), 0, c->stream, a);
+    HIP_TRY(c, hipGetLastError());
+    return 0;
+}
+
+int cpprob_hip_batch_copy_vreg(cpprob_hip_ctx* c, uint64_t problem, double* h_coef, double* h_factors, double* h_log_norms)
+{
+    LANES_OWN(c);
+    if (!c) return fail(nullptr, CPPROB_HIP_EINVAL, "ctx is NULL");
+    BatchState* bs = c->batch;
+    if (!bs || !bs->begun) return fail(c, CPPROB_HIP_ESTATE, "no batch is begun");
+    if (!bs->vreg) return fail(c, CPPROB_HIP_ESTATE, "the batch has no vector-regression emissions (cpprob_hip_batch_begin_problems_vreg)");
+    if (problem >= bs->cfg.n_problems) return fail(c, CPPROB_HIP_EINVAL, "problem index out of range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (h_coef) HIP_TRY(c, hipMemcpyAsync(h_coef, bs->d_vreg_coef.as<double>() + problem * kVregCoefSlots, kVregCoefSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_factors) HIP_TRY(c, hipMemcpyAsync(h_factors, bs->d_vreg_L.as<double>() + problem * kFullTriSlots, kFullTriSlots * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (h_log_norms) HIP_TRY(c, hipMemcpyAsync(h_log_norms, bs->d_vreg_lognorm.as<double>() + problem * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -1155,6 +1155,52 @@ int cpprob_hip_batch_mstep_reg_device(cpprob_hip_ctx* ctx, const double* d_stats
                                       double* d_transition, double* d_log_norms, double sigma_floor);
 int cpprob_hip_batch_copy_reg(cpprob_hip_ctx* ctx, uint64_t problem, double* h_coef, double* h_sigmas, double* h_log_norms);
 
+/* ---- Markov-switching vector regressions (MS-VAR) of a CPPROB_HIP_MODEL_HMM_TABLE batch with per-problem tables (csrc/batch_vreg.hpp) --
+ * State s of problem b emits the vector y_t in R^Q, y_t ~ N(coef[b][s] x_t, covs[b][s]), on P covariates known at the step, Q >= 1,
+ * P >= 1, Q + P <= 16: coef [B][k][Q][P], covs [B][k][Q][Q] (the lower triangle is read), and the observes Q + P doubles a step, the
+ * responses y_t[0] .. y_t[Q-1] first, then x_t[0] .. x_t[P-1] (n_observes counts doubles: Q + P times the sum of the lengths).  An
+ * intercept is a covariate column of ones; the library adds none.  The Markov-switching VAR is the case x_t = (1, y_{t-1}, .., y_{t-p})
+ * (cpprob_amd.vreg.var_design).  A batch is of one family: every call of one family on a batch of another returns CPPROB_HIP_ESTATE and
+ * the batch stays.  A vector-regression batch is run, smoothed, counted, forecast and decoded by the calls above as they are.  A row is
+ * cpprob_hip_batch_begin_problems_full's at the mean pred_q = ((0.0 + coef_q0 x_0) + coef_q1 x_1) + ..; -inf where a response or a
+ * covariate is infinite.  At Q = 1 rows, log_norms, threshold words and fitted coefficients are a regression batch's bits with
+ * covs = sigma^2 (for sigmas with sqrt(fl(sigma sigma)) == sigma); at P = 1 with the covariate identically 1.0 rows and M-step are a
+ * full batch's bits.  tests/vreg_ref.py restates every statement.
+ * cpprob_hip_batch_begin_problems_vreg: cpprob_hip_batch_begin_problems with Q, P, the coefficients and the covariances.  Q or P below
+ * 1, Q + P above 16, k outside 1 .. 8, a coefficient that is not finite or a covariance the full calls refuse: CPPROB_HIP_EINVAL, by
+ * problem.  There is no online begin of this family.
+ * cpprob_hip_batch_retable_vreg_device / _retable_vreg: cpprob_hip_batch_retable_full_device / _retable_full with the coefficients in
+ * the means' place.  The device form checks on the device: bit 4 of cpprob_hip_batch_retable_status, a coefficient that is not finite;
+ * bit 64, a covariance that does not factor; that problem keeps rows, thresholds and tables.
+ * cpprob_hip_batch_vreg_stats_device / _vreg_stats: the E-step, the record of cpprob_hip_batch_full_stats at D = Q + P, 1304 doubles a
+ * problem: with z_t = (y_t, x_t), syy[s][i][j] = sum over t of g_t[s] (z_t[i] z_t[j]).
+ * cpprob_hip_batch_mstep_vreg_device: on d_coef [B][k][Q][P], d_covs [B][k][Q][Q] and d_transition [B][k][k] in place, from records of
+ * 1304 doubles.  A state with mass solves (sum g x x^T) beta_q = sum g x y_q for every response through ONE square-root-free L D L^T
+ * factorisation (csrc/batch_vreg.hpp: vreg_mstep, every operation and its order), then the candidate covariance
+ * c_qr = sum g y_q y_r / occ - sum over i of beta_qi (sum g x_i y_r / occ), a diagonal entry not below var_floor^2 (a NaN takes it
+ * too), which must factor.  Where an entry read or a solved coefficient is not finite, a pivot is not > 0 and finite -- collinear
+ * covariates -- or the candidate does not factor, the state keeps coefficients and covariance, as a state without mass; both triangles
+ * of a fitted covariance are written.  There is no log_norms output: a covariance's log_norm needs its factor, which the next re-table
+ * forms.  var_floor finite and > 0, else CPPROB_HIP_EINVAL.  cpprob_amd.vreg.m_step_vreg, bit for bit.  Enqueued.
+ * On a vector-regression batch the other families' re-tables, statistics and M-steps and cpprob_hip_batch_draw_tables_device (the Gibbs
+ * draw of its tables is not built) return CPPROB_HIP_ESTATE; cpprob_hip_batch_learn_begin* and _online_tables* do so because the batch
+ * is not online.
+ * cpprob_hip_batch_copy_vreg: problem `problem`'s coefficients [8][64] ((q, i) at q P + i), packed factors [8][136] and log_norms [8] in
+ * force as the device holds them (slots outside the table 0.0; any may be NULL); synchronises; CPPROB_HIP_ESTATE: no batch begun, or
+ * not of this family.  For tests. */
+int cpprob_hip_batch_begin_problems_vreg(cpprob_hip_ctx* ctx, const cpprob_hip_batch_config* cfg, const uint32_t* h_T, const uint32_t* h_n,
+                                         const double* h_observes, int32_t k, int32_t Q, int32_t P, const double* h_coef, const double* h_covs,
+                                         const double* h_transition);
+int cpprob_hip_batch_retable_vreg_device(cpprob_hip_ctx* ctx, const double* d_coef, const double* d_covs, const double* d_transition,
+                                         const double* d_observes, size_t n_observes);
+int cpprob_hip_batch_retable_vreg(cpprob_hip_ctx* ctx, const double* h_coef, const double* h_covs, const double* h_transition,
+                                  const double* h_observes, size_t n_observes);
+int cpprob_hip_batch_vreg_stats_device(cpprob_hip_ctx* ctx, const double* d_observes, size_t n_observes, double* d_stats, size_t n_doubles);
+int cpprob_hip_batch_vreg_stats(cpprob_hip_ctx* ctx, const double* h_observes, size_t n_observes, double* h_stats, size_t n_doubles);
+int cpprob_hip_batch_mstep_vreg_device(cpprob_hip_ctx* ctx, const double* d_stats, size_t n_doubles, double* d_coef, double* d_covs,
+                                       double* d_transition, double var_floor);
+int cpprob_hip_batch_copy_vreg(cpprob_hip_ctx* ctx, uint64_t problem, double* h_coef, double* h_factors, double* h_log_norms);
+
 /* ---- tied tables: one table for the problems of a group, fitted to their pooled records (csrc/batch_pool.hpp) --
  * A tie is a partition of the begun batch's problems and nothing else: h_group[b] in 0 .. G-1 names problem b's group, G = the largest
  * id + 1, and every id occurs.  Any begun batch may be tied (uniform, described or online; either batch model).  The context keeps the
